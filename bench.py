@@ -20,15 +20,23 @@ sends, on a side stream, overlapped with the next step's kernels).  --verify: ra
 byte-compares the records it received with its own.
 --force-dist: the same N > 1 code path with ONE rank, so that the RCCL backend itself (bring-up, collectives on device tensors, barrier) runs on a 1-GPU box.
 
-The JSON line also carries: the roofline of the dominant stage (the one with the largest stand-alone time; algorithmic bytes / HIP-event
-duration of its launch inside the timed region; `traffic` = 2 x FETCH_SIZE + WRITE_SIZE and `valu_issue` = its vector instructions against the
-part's issue rate, both from PMC summaries under profiles/ that carry the hash of the sources they were collected on), `roofline.stages`:
-every stage run alone, a measured copy-kernel ceiling next to the 8 TB/s specification, host-to-host latency of small batches (1, 8, 128
+A plain run sets up, warms up, times the --steps steps and prints one JSON line: `metric`, `value` (stereo frames/s over the timed steps),
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` (milliseconds per timed step), the configuration, every stage's time inside the timed
+steps (HIP events) and the roofline of the dominant stage (algorithmic bytes / HIP-event duration of its launch inside the timed region;
+`traffic` = 2 x FETCH_SIZE + WRITE_SIZE and `valu_issue` = its vector instructions against the part's issue rate, both from PMC summaries
+under profiles/ that carry the hash of the sources they were collected on).  --dump-outputs DIR also writes what the last timed step
+computed (dump_outputs).
+
+--full adds, after the timed steps, what the headline does not need and what takes runs of its own: every stage run alone
+(`roofline.stages`; the dominant stage is then the one with the largest stand-alone time), the companion workloads (runs of six consecutive
+frames, long thin bars), a measured copy-kernel ceiling next to the 8 TB/s specification, host-to-host latency of small batches (1, 8, 128
 pairs per call), the PCIe-inclusive rate of the double-buffered offline pipeline, and the CPU oracle timed on this box's host cores in two
 shapes (A: 4 threads per frame, one frame at a time, like the reference, 20 warm-up + 200 timed frames with a per-stage breakdown; B: one
-frame per thread as a thread-count sweep against the box's CPU quota).
+frame per thread as a thread-count sweep against the box's CPU quota).  --no-isolated / --no-extras / --no-cpu-baseline leave legs of
+--full out.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29501 bench.py --gpus 8 --steps 5 --warmup 2
 """
 import argparse
@@ -206,6 +214,61 @@ def small_batch_latency(params, W, H, sizes=(1, 8, 128)):
     return out
 
 
+DUMP_LIMIT = 64 << 20     # bytes: --dump-outputs writes at most this much
+DUMP_PAIRS = 16           # pairs of the batch whose per-feature outputs --dump-outputs writes (a fixed, seeded sample)
+
+
+def dump_outputs(out_dir, B, cap, lcap, t, f2f_orb_layout):
+    """--dump-outputs: what the timed path handed its caller in the last step, as DIR/<name>.npy (float32 / float64, exact for every value).
+    The counts of the whole batch (orb_counts, line_counts, f2f_orb_nmatches) and, for DUMP_PAIRS pairs drawn once with a fixed seed
+    (sample_pairs), every per-feature output at full capacity: key points / key lines as one column per record field, descriptors as bytes,
+    mvuRight / mvDepth, stereo line matches / mvDisparity_l / mvle_l, and the frame-to-frame matches of frame p + 1 against frame p
+    (f2f_*_matches, rows for the sampled p < B - 1).  Rows past a frame's count are not outputs: they are written as 0."""
+    import torch
+    import numpy.lib.recfunctions as rfn
+    import orb_line_slam_amd as ola
+    per_pair = 2 * cap * (7 * 8 + 32 * 4) + cap * (4 + 4 + 8) + 2 * lcap * (17 * 8 + 32 * 4) + lcap * (8 + 2 * 4 + 3 * 8 + 8)
+    n = max(1, min(B, DUMP_PAIRS, (DUMP_LIMIT - 3 * 8 * 2 * B - 8 * DUMP_PAIRS) // per_pair))
+    pairs = np.sort(np.random.default_rng(20261016).choice(B, n, replace=False)) if n < B else np.arange(B)
+    dev = t["counts"].device
+    pi = torch.from_numpy(pairs).to(dev)
+    ii = torch.stack([2 * pi, 2 * pi + 1], 1).reshape(-1)
+    cnt = t["counts"].cpu().numpy(); lcnt = t["lcounts"].cpu().numpy()
+    lim_img, llim_img = cnt[ii.cpu().numpy()], lcnt[ii.cpu().numpy()]       # rows in use per sampled image
+    lim_pair, llim_pair = cnt[2 * pairs], lcnt[2 * pairs]                  # per sampled pair: the left image's rows
+
+    def cut(a, lim):      # zero every row past its frame's count
+        a = a.copy()
+        a[np.arange(a.shape[1])[None, :] >= np.asarray(lim)[:, None]] = 0
+        return a
+    kp = t["kps"][ii].cpu().numpy().view(ola.KEYPOINT_DTYPE).reshape(2 * n, cap)
+    kl = t["kls"][ii].cpu().numpy().view(ola.KEYLINE_DTYPE).reshape(2 * n, lcap)
+    res = {"sample_pairs": pairs.astype(np.float64), "orb_counts": cnt.astype(np.float64), "line_counts": lcnt.astype(np.float64),
+           "keypoints": cut(rfn.structured_to_unstructured(kp, np.float64), lim_img),
+           "descriptors": cut(t["desc"][ii].cpu().numpy().astype(np.float32), lim_img),
+           "mvuRight": cut(t["ur"][pi].cpu().numpy(), lim_pair), "mvDepth": cut(t["dp"][pi].cpu().numpy(), lim_pair),
+           "keylines": cut(rfn.structured_to_unstructured(kl, np.float64), llim_img),
+           "line_descriptors": cut(t["ldesc"][ii].cpu().numpy().astype(np.float32), llim_img),
+           "line_matches_12": cut(t["lm"][pi].cpu().numpy().astype(np.float64), llim_pair),
+           "mvDisparity_l": cut(t["ldisp"][pi].cpu().numpy(), llim_pair), "mvle_l": cut(t["lle"][pi].cpu().numpy(), llim_pair)}
+    if B > 1:
+        # set s = frame s + 1 (its left image, 2s + 2) against frame s; olf_search_by_bow_batch_dev writes the sets at a stride of cap,
+        # olf_match_bf_dev (--no-bow) at the buffer's row stride of 2 * cap, the LBD matcher at 2 * lcap
+        fp = pairs[pairs < B - 1]
+        fo = t["f2f_orb"].reshape(-1, cap)[:B - 1] if f2f_orb_layout == "bow" else t["f2f_orb"][:B - 1, :cap]
+        fpi = torch.from_numpy(fp).to(dev)
+        res["f2f_orb_matches"] = cut(fo[fpi].cpu().numpy().astype(np.float64), cnt[2 * fp + 2])
+        res["f2f_line_matches"] = cut(t["f2f_lines"][:B - 1, :lcap][fpi].cpu().numpy().astype(np.float64), lcnt[2 * fp + 2])
+        if f2f_orb_layout == "bow":
+            res["f2f_orb_nmatches"] = t["f2f_n"][:B - 1].cpu().numpy().astype(np.float64)
+    total = sum(a.nbytes for a in res.values())
+    assert total <= DUMP_LIMIT, total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in res.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "pairs": int(n), "arrays": len(res), "bytes": int(total)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -216,14 +279,18 @@ def main():
     ap.add_argument("--distinct", type=int, default=512, help="distinct synthetic pairs per rank (tiled to --pairs)")
     ap.add_argument("--order", choices=("shuffled", "tiled"), default="shuffled", help="how the batch is drawn from the distinct pairs")
     ap.add_argument("--scene", choices=("default", "long", "bars"), default="default", help="long: fewer, larger shapes; bars: long thin bars -> key lines of about 0.08*W pixels (SURVEY App. D model)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run what the headline does not need: every stage alone, the companion workloads, "
+                    "copy ceiling, small-batch latency, PCIe-inclusive rate and the CPU baselines (--no-isolated / --no-extras / --no-cpu-baseline leave legs out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB: "
+                    "the batch's counts and every output of a fixed, seeded sample of pairs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-bow", action="store_true", help="frame-to-frame ORB matching by the dense kNN stand-in of rounds 1-2 instead of SearchByBoW")
     ap.add_argument("--no-deferred-join", action="store_true", help="join the two streams at the end of olf_stereo_frames_dev (the default of the C ABI) instead of behind the "
                                                                     "point features' matcher (olf_ctx_set_deferred_join, include/orbline.h)")
     ap.add_argument("--pipeline", action="store_true", help="hand the context an input-ready event (olf_ctx_set_input_event, include/orbline.h): the line path of step k + 1 then starts "
                                                             "beside the tail of step k instead of behind it (measured: no gain, profiles/r4q_pipelined_steps_ab.txt)")
-    ap.add_argument("--no-isolated", action="store_true", help="skip the pass that runs every stage alone (counter collections that must see exactly the timed steps)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the copy ceiling, small-batch latency and PCIe-inclusive legs")
+    ap.add_argument("--no-isolated", action="store_true", help="--full without the pass that runs every stage alone (counter collections that must see exactly the timed steps)")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the companion workloads, copy ceiling, small-batch latency and PCIe-inclusive legs")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--gather", choices=("overlap", "sync", "off"), default="overlap", help="N>1: gather of the feature records to rank 0 (inside the timed region)")
     ap.add_argument("--seed-order", type=int, choices=(0, 1), default=None, help="convention C.9: order of the LSD seeds inside a gradient bin (default: the library's)")
@@ -241,6 +308,11 @@ def main():
     ap.add_argument("--sequence", type=int, default=0, metavar="RUN", help="synthetic input as runs of RUN consecutive frames of one scene (frame k of a run = the scene "
                     "shifted by 2k pixels), so that the frame-to-frame matchers see related frames; 0: independent scenes (SURVEY 8(d)'s generator)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    isolated = args.full and not args.no_isolated        # the legs of --full
+    extras = args.full and not args.no_extras
+    cpu_base = args.full and not args.no_cpu_baseline
 
     import torch
     import orb_line_slam_amd as ola
@@ -490,6 +562,12 @@ def main():
     ctx.synchronize()                        # outside the timed region: raises if any step overflowed a fixed-capacity device buffer
     prof = ctx.profile_read()
     ctx.profile(False)
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        # before anything below runs the context again
+        dumped = dump_outputs(args.dump_outputs, B, cap, lcap, dict(kps=kps, desc=desc, counts=counts, ur=ur, dp=dp, kls=kls, ldesc=ldesc, lcounts=lcounts,
+                                                                  lm=lm, ldisp=ldisp, lle=lle, f2f_orb=f2f_orb, f2f_lines=f2f_lines, f2f_n=f2f_n),
+                              "bow" if voc is not None else "bf")
     rank_dt = None
     if dist is not None:
         # every rank's own time for the K steps (the first real multi-GPU run must be diagnosable from one line: a slow rank, a slow link), then the
@@ -504,7 +582,7 @@ def main():
     # every stage on its own: the four extraction / matching entries back to back on one stream (what OLF_ONE_STREAM=1 makes of a step), outside the
     # timed region -- in the two-stream step the stages slow each other down, so only these times can be set against a stage's own bytes
     alone = None
-    if rank == 0 and not args.no_isolated:
+    if rank == 0 and isolated:
         ctx.profile(True)
         s0 = torch.cuda.current_stream().cuda_stream
         for _ in range(2):
@@ -519,7 +597,7 @@ def main():
     # the companion line: the same step on runs of six consecutive frames of one scene, so that the frame-to-frame matchers (SearchByBoW, LBD match) meet related
     # frames as they do on a recording -- SURVEY 8(d)'s generator (independent scenes) is the headline, this is what it leaves out
     companion, companion_long = None, None
-    if rank == 0 and world == 1 and not args.no_extras and seq is None and args.sequence == 0 and B > 1:
+    if rank == 0 and world == 1 and extras and seq is None and args.sequence == 0 and B > 1:
         keep = imgs
         imgs = make_input(rank, 6)
         run_steps(1); barrier()
@@ -577,9 +655,10 @@ def main():
         total_pairs = world * B * args.steps
         fps = total_pairs / dt
         nk = counts.float().mean().item(); nkl = lcounts.float().mean().item()
-        kl_np = kls.cpu().numpy().view(ola.KEYLINE_DTYPE).reshape(2 * B, lcap)
+        nm = min(2 * B, 256)          # (the mean line length is taken over the first 256 images)
+        kl_np = kls[:nm].cpu().numpy().view(ola.KEYLINE_DTYPE).reshape(nm, lcap)
         lc_np = lcounts.cpu().numpy()
-        mean_len = float(np.mean([kl_np[i, :lc_np[i]]["numOfPixels"].mean() for i in range(min(2 * B, 256)) if lc_np[i] > 0]))
+        mean_len = float(np.mean([kl_np[i, :lc_np[i]]["numOfPixels"].mean() for i in range(nm) if lc_np[i] > 0]))
         ab = algorithmic_bytes(W, H, nk, nkl, mean_len)
         stages = {k: {"ms_per_step": v[0] / max(args.steps, 1), "calls": v[1]} for k, v in prof.items() if v[1]}
         # dominant stage: the largest stand-alone time over ALL stages (inside the two-stream step a dense stage that runs in the growth agents'
@@ -684,7 +763,7 @@ def main():
                              "GBps": round(gstat["bytes"] / max(gstat["seconds"], 1e-9) / 1e9, 3),
                              "rank0_ingest_GBps": round(gstat["bytes"] / dt / 1e9, 3),       # bytes rank 0 received per second of the timed region
                              "host_seconds_per_step": round(gstat["seconds"] / max(args.steps, 1), 5), "verify": verify}
-        if not args.no_extras:
+        if extras:
             # measured ceiling of a plain copy kernel, next to the 8 TB/s of the specification
             try:
                 g = C.c_double()
@@ -698,6 +777,8 @@ def main():
         out["companion_sequence6"] = companion
     if rank == 0 and out is not None and companion_long is not None:
         out["companion_long_lines"] = companion_long
+    if rank == 0 and out is not None and dumped is not None:
+        out["dump_outputs"] = dumped
     if rank == 0 and out is not None and voc is not None:
         out["config"]["search_by_bow_mean_matches"] = round(float(f2f_n[:B - 1].float().mean().item()), 1)
     del imgs, kps, desc, ur, dp, kls, ldesc, lm, ldisp, lle, f2f_lines, f2f_orb
@@ -706,7 +787,7 @@ def main():
     ctx.close()
     torch.cuda.empty_cache()
     if rank == 0:
-        if not args.no_extras:
+        if extras:
             try:
                 out["pair_latency_ms"] = small_batch_latency(params, W, H)
             except Exception as e:
@@ -720,7 +801,7 @@ def main():
                 out["pcie_inclusive"]["pageable_input"] = pcie_inclusive_rate(params, W, H, pairs=B, batches=4, producer="pageable")["value"]
             except Exception as e:
                 out["pcie_inclusive"] = {"error": str(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if cpu_base and world == 1:
             out["cpu_baseline"] = cb = cpu_baseline(W, H, params, args.cpu_seconds)
             # the GPU figure against both CPU shapes, side by side: Mode A = the reference's own (one frame at a time, 4 threads), Mode B = the box's
             # cores all busy with whole frames; and the drop-in's online shape (one pair per call) against Mode A's frame time

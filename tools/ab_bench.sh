@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; cd /tmp; export TMPDIR=/tmp
 STEPS=${AB_STEPS:-4}
 for spec in "$@"; do
   label=${spec%%:*}; envs=${spec#*:}
-  line=$(env $envs timeout 600 python $R/bench.py --no-cpu-baseline --no-extras --steps $STEPS --warmup 1 ${AB_ARGS:-} 2>/dev/null | grep '^{' | tail -1)
+  line=$(env $envs timeout 600 python $R/bench.py --full --no-cpu-baseline --no-extras --steps $STEPS --warmup 1 ${AB_ARGS:-} 2>/dev/null | grep '^{' | tail -1)
   python - "$label" "$line" <<'PY'
 import sys, json
 d = json.loads(sys.argv[2]); r = d["roofline"]; st = r.get("stages", {})

@@ -16,19 +16,19 @@ rm -rf /tmp/pb
 # instruction budget at the bench's batch (3072 pairs: the kernel variants the step really launches -- VERDICT r4 weak 7a)
 timeout 900 rocprofv3 --kernel-trace --output-format csv --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES -d /tmp/pb -o run -- $BENCH1 > /tmp/pb.log 2>&1
 python $R/tools/pmc_budget.py /tmp/pb 6144 $O/${T}_valu_budget.json > $O/${T}_valu_budget_per_kernel.txt 2>&1; cp $O/${T}_valu_budget.json $R/profiles/
-timeout 900 python $R/bench.py 2>/dev/null | tail -1 > $O/${T}_bench_C3.json; cut -c1-160 $O/${T}_bench_C3.json
-OLF_ONE_STREAM=1 timeout 600 python $R/bench.py --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/${T}_bench_C3_one_stream.json
+timeout 900 python $R/bench.py --full 2>/dev/null | tail -1 > $O/${T}_bench_C3.json; cut -c1-160 $O/${T}_bench_C3.json
+OLF_ONE_STREAM=1 timeout 600 python $R/bench.py --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/${T}_bench_C3_one_stream.json
 # the other configurations: the bench line AND the rocprofv3 kernel summary of the same command
 for c in C2 C4 C5; do
-  rm -rf /tmp/ks_$c; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$c -o run -- python $R/bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | grep '^{' | tail -1 > $O/${T}_bench_$c.json
+  rm -rf /tmp/ks_$c; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$c -o run -- python $R/bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | grep '^{' | tail -1 > $O/${T}_bench_$c.json
   cp $(ls /tmp/ks_$c/*kernel_stats.csv | head -1) $O/${T}_bench_${c}_kernel_stats.csv
 done
-timeout 600 python $R/bench.py --sequence 6 --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/${T}_bench_C3_sequence6.json
-timeout 600 python $R/bench.py --scene bars --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/${T}_bench_C3_long_scene.json
-rm -rf /tmp/ks; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o run -- python $R/bench.py --no-cpu-baseline --no-extras --steps 3 --warmup 1 > /tmp/ks.log 2>&1
+timeout 600 python $R/bench.py --full --sequence 6 --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/${T}_bench_C3_sequence6.json
+timeout 600 python $R/bench.py --full --scene bars --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/${T}_bench_C3_long_scene.json
+rm -rf /tmp/ks; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o run -- python $R/bench.py --full --no-cpu-baseline --no-extras --steps 3 --warmup 1 > /tmp/ks.log 2>&1
 cp $(ls /tmp/ks/*kernel_stats.csv | head -1) $O/${T}_bench_C3_kernel_stats.csv
 python $R/tools/timeline.py /tmp/ks > $O/${T}_timeline_two_streams.txt 2>&1
-rm -rf /tmp/ks1; OLF_ONE_STREAM=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks1 -o run -- python $R/bench.py --no-cpu-baseline --no-extras --steps 3 --warmup 1 > /tmp/ks1.log 2>&1
+rm -rf /tmp/ks1; OLF_ONE_STREAM=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks1 -o run -- python $R/bench.py --full --no-cpu-baseline --no-extras --steps 3 --warmup 1 > /tmp/ks1.log 2>&1
 cp $(ls /tmp/ks1/*kernel_stats.csv | head -1) $O/${T}_bench_C3_one_stream_kernel_stats.csv
 OLF_ONE_STREAM=1 timeout 600 python $R/tools/grow_sweep.py 1 8 128 512 1024 2048 3072 > $O/${T}_grow_sweep.txt 2>&1
 timeout 900 python $R/tools/soak.py $SOAK > $O/${T}_soak.txt 2>&1; tail -2 $O/${T}_soak.txt
