@@ -205,8 +205,8 @@ int olf_debug_lsd_log_cap(olf_ctx* ctx, int entries);
  * its heap-sort branch. */
 int olf_debug_seed_sort(olf_ctx* ctx, const uint32_t* keys, int n, int kthr, int depth_limit, uint32_t* out, int32_t* out_n);
 /* debug / tests: the kernel variant of that replay -- 0: one wave per image (batches), 1 / 2: 4 / 8 cooperating waves per image (few images: the
- * drop-in's one-pair-per-call shape), 3 / 4: groups of 4 / 8 images per workgroup whose waves take over each other's ranges (large batches), 5: 2 waves per image,
- * -1: chosen from the batch size.  Results do not depend on it. */
+ * drop-in's one-pair-per-call shape), 5: 2 waves per image, -1: chosen from the batch size; 3 and 4 are rejected (OLF_ERR_INVALID).  Results do not
+ * depend on it. */
 int olf_debug_seed_sort_mode(olf_ctx* ctx, int mode);
 /* debug / tests: the seed-order kernel of the capacity path (csrc/lsd_wide.hip: lsd_n_bins > 1024 or an LSD working image of 2^22 pixels and more -- free YAML
  * keys of the reference, src/Config.cpp:268,274) on a caller-supplied array of 64-bit keys (field << 32 | payload).  full = 0: the order libstdc++'s

@@ -48,9 +48,7 @@ struct olf_ctx {
     double* d_lle = nullptr;
     hipStream_t stream2 = nullptr;
     bool has_tables = false;       // holds a reference on the device's shared LSD angle tables
-    bool mark_front = false;
-    int orb_wait_after = 0;        // fused entry: the ORB stream waits for the LSD front behind this many of its own dense stages (pyramid, blur, FAST)
-    hipEvent_t ev_front = nullptr;
+    hipEvent_t ev_front = nullptr;     // fused entry: recorded behind the LSD front including the seed ordering (the ORB stream's FAST waits for it)
     hipEvent_t input_event = nullptr;  // olf_ctx_set_input_event: not owned; the fused entry's line stream waits for it instead of forking from the caller's stream
     hipEvent_t ev_lbd = nullptr;       // fused entry: the LBD gradient images are ready (computed on the ORB stream in the seed ordering's shadow)
     bool deferred_join = false;        // olf_ctx_set_deferred_join: olf_stereo_frames_dev returns with the line path still running on the line stream
@@ -64,9 +62,7 @@ struct olf_ctx {
     // waited (pend_stream); a join on another stream orders that stream and leaves the obligation standing
     struct { const uint8_t* p; size_t bytes; } pend[6] = {};
     hipStream_t pend_stream = nullptr;
-    bool defer_lbd = false;            // fused entry: olf_line_extract_dev stops behind the rectangles; selection + LBD are enqueued by the caller
-    bool lbd_pre = false;              // fused entry: olf_orb_extract_dev computes the LBD gradient images behind its blur and records ev_lbd
-    hipEvent_t ev_sort = nullptr;      // recorded in front of the seed ordering (the dense, bandwidth-bound half of the LSD front is through)
+    hipEvent_t ev_sort = nullptr;      // fused entry: recorded in front of the seed ordering (the dense, bandwidth-bound half of the LSD front is through)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // stage profiling (olf_profile_*): HIP events recorded on the stream each stage is launched on
     bool prof_on = false;
@@ -293,14 +289,11 @@ int olf_ctx_create(const olf_params* p, int width, int height, int max_images, o
     // The line stream gets a priority of its own.  The runtime multiplexes streams onto a few hardware queues, and two streams of the SAME priority can land on
     // one queue: the line path and the caller's stream then run back to back (measured: the host-to-host pipeline at 330 ms per 3072-pair batch instead of 220
     // whenever the caller's compute stream and this one aliased, profiles/r4aq_stream_queue_aliasing.txt).  Streams of different priorities never share a queue.
-    // OLF_S2_PRIO: 1 low (default: it leaves the high level to a caller's copy streams -- pipeline.py), -1 high, 0 the caller's level (the hazard, for A/B);
-    // the step time is the same for all three (226-231 ms on one box).
-    int s2prio = 1;
-    if (const char* e = getenv("OLF_S2_PRIO")) s2prio = atoi(e);
+    // The least priority leaves the high level to a caller's copy streams (pipeline.py); the step time was the same with the high one and with the caller's
+    // level (226-231 ms on one box).
     int prLeast = 0, prGreatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prLeast, &prGreatest);
-    const int prio = s2prio < 0 ? prGreatest : s2prio > 0 ? prLeast : 0;
-    if (hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio) != hipSuccess ||
+    if (hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prLeast) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_front, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_sort, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_lbd, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) { set_error("stream/event creation failed"); return fail(OLF_ERR_HIP); }
@@ -467,6 +460,28 @@ int olf_orb_level_sizes(const olf_ctx* c, int32_t* widths, int32_t* heights)
 
 int olf_orb_capacity(const olf_ctx* c) { return c ? c->orb.geom.outCap : OLF_ERR_INVALID; }
 
+// fused: part of olf_stereo_frames_dev.  The blur only needs the pyramid, so it runs ahead of FAST in the shadow of the seed sort -- behind the dense half of
+// the LSD front (ev_sort) -- and so do the LBD gradient images (GaussianBlur + Sobel of the LBD octave need the input images only; ev_lbd tells the line
+// stream they are done); FAST waits for the whole front (ev_front)
+static int orb_extract(olf_ctx* c, const uint8_t* d_images, int n_images, olf_keypoint* d_kps, uint8_t* d_desc, int32_t* d_counts, hipStream_t s, bool fused)
+{
+    const OrbGeom& g = c->orb.geom;
+    c->last_n_images = n_images;
+    { StageScope t(c, s, ST_ORB_PYRAMID); OLF_TRY(launch_orb_pyramid(g, c->ob, d_images, n_images, s)); }
+    if (fused) {
+        OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_sort, 0));
+        { StageScope t(c, s, ST_ORB_BLUR); OLF_TRY(launch_orb_blur(g, c->ob, n_images, s)); }
+        OLF_TRY(launch_lbd_dense(c->line.geom, c->lb, d_images, c->W, n_images, s));
+        OLF_HIP_CHECK(hipEventRecord(c->ev_lbd, s));
+        OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_front, 0));
+    }
+    { StageScope t(c, s, ST_ORB_FAST); OLF_TRY(launch_orb_fast(g, c->ob, n_images, s)); }
+    { StageScope t(c, s, ST_ORB_OCTREE); OLF_TRY(launch_orb_octree(g, c->ob, n_images, s)); }
+    if (!fused) { StageScope t(c, s, ST_ORB_BLUR); OLF_TRY(launch_orb_blur(g, c->ob, n_images, s)); }
+    { StageScope t(c, s, ST_ORB_DESCRIBE); OLF_TRY(launch_orb_describe(g, c->ob, n_images, d_kps, d_desc, d_counts, g.outCap, s)); }
+    return OLF_OK;
+}
+
 int olf_orb_extract_dev(olf_ctx* c, const uint8_t* d_images, int n_images, olf_keypoint* d_kps, uint8_t* d_desc, int32_t* d_counts,
                         void* stream)
 {
@@ -474,27 +489,7 @@ int olf_orb_extract_dev(olf_ctx* c, const uint8_t* d_images, int n_images, olf_k
     OLF_TRY(check_device(c, "olf_orb_extract_dev"));
     if (n_images < 0 || n_images > c->max_images) { set_error("olf_orb_extract_dev: n_images exceeds the context capacity"); return OLF_ERR_CAPACITY; }
     if (n_images == 0) return OLF_OK;   // ORBextractor::operator() returns silently on an empty image
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const OrbGeom& g = c->orb.geom;
-    c->last_n_images = n_images;
-    // (the blur only needs the pyramid: with orb_wait_after >= 2 it runs ahead of FAST, beside the dense half of the LSD front)
-    const int wa = c->orb_wait_after;
-    { StageScope t(c, s, ST_ORB_PYRAMID); OLF_TRY(launch_orb_pyramid(g, c->ob, d_images, n_images, s)); }
-    if (wa == 1) OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_front, 0));
-    // wa == 4 (OLF_SCHED=5): the blur in the shadow of the seed sort -- it waits for the dense half of the LSD front only (ev_sort), FAST for all of it
-    if (wa == 4) OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_sort, 0));
-    if (wa >= 2) { StageScope t(c, s, ST_ORB_BLUR); OLF_TRY(launch_orb_blur(g, c->ob, n_images, s)); }
-    if (c->lbd_pre) {      // (also beside the seed sort: GaussianBlur + Sobel of the LBD octave need the input images only)
-        OLF_TRY(launch_lbd_dense(c->line.geom, c->lb, d_images, c->W, n_images, s));
-        OLF_HIP_CHECK(hipEventRecord(c->ev_lbd, s));
-    }
-    if (wa == 2 || wa == 4) OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_front, 0));
-    { StageScope t(c, s, ST_ORB_FAST); OLF_TRY(launch_orb_fast(g, c->ob, n_images, s)); }
-    if (wa == 3) OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_front, 0));
-    { StageScope t(c, s, ST_ORB_OCTREE); OLF_TRY(launch_orb_octree(g, c->ob, n_images, s)); }
-    if (wa < 2) { StageScope t(c, s, ST_ORB_BLUR); OLF_TRY(launch_orb_blur(g, c->ob, n_images, s)); }
-    { StageScope t(c, s, ST_ORB_DESCRIBE); OLF_TRY(launch_orb_describe(g, c->ob, n_images, d_kps, d_desc, d_counts, g.outCap, s)); }
-    return OLF_OK;
+    return orb_extract(c, d_images, n_images, d_kps, d_desc, d_counts, stream ? (hipStream_t)stream : c->stream, false);
 }
 
 static int check_status(olf_ctx* c)
@@ -687,10 +682,10 @@ int olf_debug_seed_sort_wide(olf_ctx* c, const uint64_t* keys, int n, int64_t kt
     return check_status(c);
 }
 
-// debug / tests: which seed-sort kernel runs (-1: chosen from the batch size; 0: one wave per image; 1 / 2: 4 / 8 waves per image)
+// debug / tests: which seed-sort kernel runs (-1: chosen from the batch size; 0: one wave per image; 1 / 2 / 5: 4 / 8 / 2 waves per image)
 int olf_debug_seed_sort_mode(olf_ctx* c, int mode)
 {
-    if (!c || mode < -1 || mode > 5) { set_error("olf_debug_seed_sort_mode: bad argument"); return OLF_ERR_INVALID; }
+    if (!c || mode < -1 || mode == 3 || mode == 4 || mode > 5) { set_error("olf_debug_seed_sort_mode: bad argument"); return OLF_ERR_INVALID; }
     c->lb.forceSortMode = mode;
     return OLF_OK;
 }
@@ -1037,27 +1032,31 @@ int olf_distinctive_descriptors(olf_ctx* c, const uint8_t* desc, const int32_t* 
 // ---------------------------------------------------------------------------------------------
 int olf_line_capacity(const olf_ctx* c) { return c ? c->line.geom.outCap : OLF_ERR_INVALID; }
 
+// fused: part of olf_stereo_frames_dev.  The front records ev_sort in front of the seed ordering and ev_front behind it (the ORB stream waits for them), and
+// the path stops behind the rectangles: the caller enqueues selection + LBD behind the LBD gradient images of the ORB stream
+static int line_extract(olf_ctx* c, const uint8_t* d_images, int n_images, olf_keyline* d_kls, uint8_t* d_ldesc, int32_t* d_lcounts, hipStream_t s, bool fused)
+{
+    if (fused) {
+        if (c->line.geom.seedOrder == 1) c->lb.sortEvent = c->ev_sort;
+        else OLF_HIP_CHECK(hipEventRecord(c->ev_sort, s));      // (no sort kernel to hide behind: the event is already true)
+        c->lb.skipScaled = true;      // (nothing behind the fused kernel reads the working image)
+    }
+    { StageScope t(c, s, ST_LSD_FRONT); const int rc = launch_lsd_front(c->line.geom, c->lb, d_images, c->W, n_images, s); c->lb.sortEvent = nullptr; c->lb.skipScaled = false; OLF_TRY(rc); }
+    if (fused) OLF_HIP_CHECK(hipEventRecord(c->ev_front, s));
+    { StageScope t(c, s, ST_LSD_GROW); OLF_TRY(launch_lsd_grow(c->line.geom, c->lb, n_images, s)); }
+    { StageScope t(c, s, ST_LSD_RECT); OLF_TRY(launch_lsd_rect(c->line.geom, c->lb, n_images, s)); }
+    if (fused) return OLF_OK;
+    { StageScope t(c, s, ST_LINE_LBD); OLF_TRY(launch_line_select_lbd(c->line.geom, c->lb, d_images, c->W, n_images, d_kls, d_ldesc, d_lcounts, s)); }
+    return OLF_OK;
+}
+
 int olf_line_extract_dev(olf_ctx* c, const uint8_t* d_images, int n_images, olf_keyline* d_kls, uint8_t* d_ldesc, int32_t* d_lcounts, void* stream)
 {
     if (!c || !d_images || !d_kls || !d_ldesc || !d_lcounts) { set_error("olf_line_extract_dev: null argument"); return OLF_ERR_INVALID; }
     OLF_TRY(check_device(c, "olf_line_extract_dev"));
     if (n_images < 0 || n_images > c->max_images) return OLF_ERR_CAPACITY;
     if (n_images == 0) return OLF_OK;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    // mark_front: the ORB stream waits for ev_front, recorded behind the whole front including the seed ordering.  OLF_SCHED + 16 records it in
-    // front of the std::sort replay instead -- measured worse (297.7 against 282.7 ms per 3072-pair step: the ORB kernels then slow the sort down and
-    // still meet the growth agents afterwards), kept as a switch for experiments.
-    static const bool front_before_sort = getenv("OLF_SCHED") && (atoi(getenv("OLF_SCHED")) & 16);
-    const bool early = c->mark_front && c->line.geom.seedOrder == 1 && front_before_sort;
-    c->lb.sortEvent = early ? c->ev_front : (c->mark_front && c->line.geom.seedOrder == 1) ? c->ev_sort : nullptr;
-    if (c->mark_front && c->line.geom.seedOrder != 1) OLF_HIP_CHECK(hipEventRecord(c->ev_sort, s));      // (no sort kernel to hide behind: the event is already true)
-    { StageScope t(c, s, ST_LSD_FRONT); const int rc = launch_lsd_front(c->line.geom, c->lb, d_images, c->W, n_images, s); c->lb.sortEvent = nullptr; OLF_TRY(rc); }
-    if (c->mark_front && !early) OLF_HIP_CHECK(hipEventRecord(c->ev_front, s));
-    { StageScope t(c, s, ST_LSD_GROW); OLF_TRY(launch_lsd_grow(c->line.geom, c->lb, n_images, s)); }
-    { StageScope t(c, s, ST_LSD_RECT); OLF_TRY(launch_lsd_rect(c->line.geom, c->lb, n_images, s)); }
-    if (c->defer_lbd) return OLF_OK;
-    { StageScope t(c, s, ST_LINE_LBD); OLF_TRY(launch_line_select_lbd(c->line.geom, c->lb, d_images, c->W, n_images, d_kls, d_ldesc, d_lcounts, s)); }
-    return OLF_OK;
+    return line_extract(c, d_images, n_images, d_kls, d_ldesc, d_lcounts, stream ? (hipStream_t)stream : c->stream, false);
 }
 
 int olf_line_extract(olf_ctx* c, const uint8_t* images, int n_images, olf_keyline* kls, uint8_t* ldesc, int32_t* lcounts)
@@ -1164,11 +1163,11 @@ int olf_stereo_frames_dev(olf_ctx* c, const uint8_t* d_images, int n_pairs, cons
     const int n_images = 2 * n_pairs;
     if (c->join_pending) { OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_join, 0)); c->join_pending = false; }      // (a deferred join the caller never asked for)
     // The line path runs beside the ORB path on the second stream (the reference's 4 extraction threads, src/Frame.cc:164-171).  The ORB
-    // stream builds its pyramid beside the dense half of the LSD front and then waits for the front's end: two dense pipelines at once only
-    // slow each other down (OLF_SCHED=0: 290 ms per 3072-pair step), whereas FAST beside the latency-bound growth agents is hidden almost
-    // completely (105 ms beside them, 24 alone, and the agents keep their stand-alone speed).  Round 3, ms per step: wait before the pyramid
-    // 266.3, behind it 260.3, behind pyramid + blur 262.5, behind FAST 279.  Round 4 (profiles/r4o_*): behind the pyramid 241.6, and with the blur moved
-    // into the shadow of the one-wave seed sort (schedule 5, the default) 235.6 .. 239.5.  OLF_ONE_STREAM serialises the two paths.
+    // stream builds its pyramid beside the dense half of the LSD front, runs its blur and the LBD gradient images (6 ms of dense work) in the shadow of
+    // the seed ordering, and waits for the front's end before FAST: two dense pipelines at once only slow each other down (290 ms per 3072-pair step
+    // with no wait at all), whereas FAST beside the latency-bound growth agents is hidden almost completely (105 ms beside them, 24 alone, and the
+    // agents keep their stand-alone speed).  (The other schedules measured: profiles/HISTORY_design_rounds1-4.md, profiles/r4o_*.)
+    // OLF_ONE_STREAM serialises the two paths.
     static const bool one_stream = getenv("OLF_ONE_STREAM") != nullptr;
     if (one_stream) {
         OLF_TRY(olf_line_extract_dev(c, d_images, n_images, o->kls, o->ldesc, o->lcounts, s));
@@ -1177,47 +1176,26 @@ int olf_stereo_frames_dev(olf_ctx* c, const uint8_t* d_images, int n_pairs, cons
         OLF_TRY(olf_stereo_points_dev(c, n_pairs, o->kps, o->desc, o->counts, o->uright, o->depth, s));
         return OLF_OK;
     }
-    // OLF_SCHED: 0 both paths at once; 1 .. 4: the ORB stream waits for the LSD front before its pyramid / behind the pyramid / behind pyramid + blur /
-    // behind pyramid + blur + FAST (+ 16: the front ends before the seed sort); 5: pyramid beside the dense front, blur beside the seed sort, FAST behind it
-    static const int sched = (getenv("OLF_SCHED") ? atoi(getenv("OLF_SCHED")) : 5) & 15;
-    // schedule 5 also moves the LBD gradient images (GaussianBlur + Sobel of the input, 6 ms of dense work) from the tail of the line stream into the
-    // seed ordering's shadow on the ORB stream (OLF_LBD_PRE=0: off); the line stream's selection + LBD then wait for ev_lbd, so they are enqueued
-    // behind the ORB extraction here (an event has to be recorded before the wait for it is enqueued)
-    static const bool lbd_pre = sched == 5 && !(getenv("OLF_LBD_PRE") && atoi(getenv("OLF_LBD_PRE")) == 0);
     // Fork.  With the caller's input event (olf_ctx_set_input_event) the line stream does not wait for what is still queued on `s` -- the ORB / stereo /
-    // matching tail of the previous batch -- and the LSD front of this batch runs beside it.  Safe with lbd_pre only: the LSD front, growth and rectangles
-    // write line-path scratch that nothing on `s` reads, and selection / LBD / line stereo (which write the output buffers the previous batch's matchers
-    // and packer on `s` may still read) sit behind ev_lbd, recorded on `s` behind all of the previous batch's work there.
+    // matching tail of the previous batch -- and the LSD front of this batch runs beside it.  Safe: the LSD front, growth and rectangles write line-path
+    // scratch that nothing on `s` reads, and selection / LBD / line stereo (which write the output buffers the previous batch's matchers and packer on `s`
+    // may still read) sit behind ev_lbd, recorded on `s` behind all of the previous batch's work there.
     // (the event is consumed by the call: one-shot -- a stale handle must never order a later call)
     hipEvent_t in_ev = c->input_event;
     c->input_event = nullptr;
-    if (in_ev && lbd_pre) OLF_HIP_CHECK(hipStreamWaitEvent(c->stream2, in_ev, 0));
+    if (in_ev) OLF_HIP_CHECK(hipStreamWaitEvent(c->stream2, in_ev, 0));
     else {
         OLF_HIP_CHECK(hipEventRecord(c->ev_fork, s));
         OLF_HIP_CHECK(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
     }
-    c->mark_front = sched != 0;
-    c->defer_lbd = lbd_pre;
-    c->lb.skipScaled = !(getenv("OLF_KEEP_SCALED") && atoi(getenv("OLF_KEEP_SCALED")) != 0);      // (nothing behind the fused kernel reads the working image)
-    const int rcl = olf_line_extract_dev(c, d_images, n_images, o->kls, o->ldesc, o->lcounts, c->stream2);
-    c->mark_front = false; c->defer_lbd = false; c->lb.skipScaled = false;
-    OLF_TRY(rcl);
-    if (!lbd_pre) {
-        OLF_TRY(olf_stereo_lines_dev(c, n_pairs, o->kls, o->ldesc, o->lcounts, o->lmatches12, o->ldisp, o->lle, c->stream2));
-        OLF_HIP_CHECK(hipEventRecord(c->ev_join, c->stream2));
-    }
-    if (sched == 1) OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_front, 0));
-    c->orb_wait_after = sched >= 2 ? sched - 1 : 0;
-    c->lbd_pre = lbd_pre;
-    const int rco = olf_orb_extract_dev(c, d_images, n_images, o->kps, o->desc, o->counts, s);
-    c->orb_wait_after = 0; c->lbd_pre = false;
-    OLF_TRY(rco);
-    if (lbd_pre) {
-        OLF_HIP_CHECK(hipStreamWaitEvent(c->stream2, c->ev_lbd, 0));
-        { StageScope t(c, c->stream2, ST_LINE_LBD); OLF_TRY(launch_line_select_lbd(c->line.geom, c->lb, d_images, c->W, n_images, o->kls, o->ldesc, o->lcounts, c->stream2, true)); }
-        OLF_TRY(olf_stereo_lines_dev(c, n_pairs, o->kls, o->ldesc, o->lcounts, o->lmatches12, o->ldisp, o->lle, c->stream2));
-        OLF_HIP_CHECK(hipEventRecord(c->ev_join, c->stream2));
-    }
+    OLF_TRY(line_extract(c, d_images, n_images, o->kls, o->ldesc, o->lcounts, c->stream2, true));
+    OLF_TRY(orb_extract(c, d_images, n_images, o->kps, o->desc, o->counts, s, true));
+    // the line stream's selection + LBD wait for ev_lbd, so they are enqueued behind the ORB extraction (an event has to be recorded before the wait for it
+    // is enqueued)
+    OLF_HIP_CHECK(hipStreamWaitEvent(c->stream2, c->ev_lbd, 0));
+    { StageScope t(c, c->stream2, ST_LINE_LBD); OLF_TRY(launch_line_select_lbd(c->line.geom, c->lb, d_images, c->W, n_images, o->kls, o->ldesc, o->lcounts, c->stream2, true)); }
+    OLF_TRY(olf_stereo_lines_dev(c, n_pairs, o->kls, o->ldesc, o->lcounts, o->lmatches12, o->ldisp, o->lle, c->stream2));
+    OLF_HIP_CHECK(hipEventRecord(c->ev_join, c->stream2));
     OLF_TRY(olf_stereo_points_dev(c, n_pairs, o->kps, o->desc, o->counts, o->uright, o->depth, s));
     // the join.  Deferred (olf_ctx_set_deferred_join): the caller's stream goes on with the ORB outputs -- key points, descriptors, stereo points are complete on
     // it here -- while the line path's tail (selection, LBD, line stereo: 20 ms of a 3072-pair batch) still runs on the line stream; olf_stereo_frames_join_dev

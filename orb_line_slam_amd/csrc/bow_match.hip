@@ -79,10 +79,7 @@ __global__ __launch_bounds__(256) void k_bow_sort_nodes(const int* __restrict__ 
     if (threadIdx.x == 0) mOut[f] = s_m;
 }
 
-#ifndef OLF_BM_WAVES
-#define OLF_BM_WAVES 8
-#endif
-constexpr int BM_WAVES = OLF_BM_WAVES;
+constexpr int BM_WAVES = 8;
 
 __device__ __forceinline__ int bm_lower_bound(const unsigned long long* a, int n, unsigned long long key)      // first position with a[p] >= key
 {

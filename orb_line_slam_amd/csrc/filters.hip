@@ -125,10 +125,7 @@ __global__ __launch_bounds__(256) void k_sep7(const uint8_t* __restrict__ src, s
 // BORDER_REFLECT_101 in y is an index computation per row; the strips whose window leaves the image in x (strip 0, strips beyond nsx) are a second, small
 // launch of the same kernel with a byte-wise row window (k_sep7_strip<true>).
 constexpr int SS_ROWS = 16;
-#ifndef OLF_SS_BROWS
-#define OLF_SS_BROWS 8
-#endif
-constexpr int SS_BROWS = OLF_SS_BROWS;       // rows per thread of the border strips (k_sep7_strip)
+constexpr int SS_BROWS = 8;       // rows per thread of the border strips (k_sep7_strip)
 
 __device__ __forceinline__ int ss_reflect(int p, int n) { p = p < 0 ? -p : p; return p >= n ? 2 * (n - 1) - p : p; }
 
@@ -262,9 +259,8 @@ int launch_sep7(const uint8_t* src, size_t srcImgStride, int srcPitch, uint8_t* 
     }
     for (int i = 0; i < 7; ++i)
         if (t.t[i] < 0 || t.t[i] > 255) { set_error("launch_sep7: taps must be 8-bit fractions"); return OLF_ERR_INVALID; }
-    // OLF_SEP7=0: the LDS-tiled kernel of rounds 1-3 (A/B measurements); images too small for a strip (or a reflection that would leave them) take it too
-    static const bool strips = [] { const char* e = getenv("OLF_SEP7"); return !e || atoi(e) != 0; }();
-    if (strips && W >= 16 && H >= 8 && (dstPitch & 3) == 0 && (dstImgStride & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 3) == 0) {
+    // images too small for a strip (or a reflection that would leave them) take the LDS-tiled kernel of rounds 1-3
+    if (W >= 16 && H >= 8 && (dstPitch & 3) == 0 && (dstImgStride & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 3) == 0) {
         const int nsx = (W - 7) / 4, nsy = (H + SS_ROWS - 1) / SS_ROWS, nb = 1 + ((W + 3) / 4 - (nsx + 1));
         const int nsyB = (H + SS_BROWS - 1) / SS_BROWS;
         hipLaunchKernelGGL(k_sep7_strip<false>, dim3((nsx * nsy + 255) / 256, n_images), dim3(256), 0, s, src, srcImgStride, srcPitch, dst, dstImgStride, dstPitch, W, H, t, nsx, nsy);
@@ -507,9 +503,8 @@ bool resize_tiled_fits(const ResizeCoef* rx, const ResizeCoef* ry, int sw, int s
 int launch_resize_tiled(const uint8_t* src, size_t srcImgStride, int srcPitch, int sw, int sh, uint8_t* dst, size_t dstImgStride, int dstPitch,
                         int dw, int dh, const ResizeCoef* d_rx, const ResizeCoef* d_ry, int n_images, hipStream_t s, bool strip)
 {
-    static const bool stripsOn = [] { const char* e = getenv("OLF_RESIZE"); return !e || atoi(e) != 0; }();
-    strip = strip && stripsOn && (dstPitch & 3) == 0 && (dstImgStride & 3) == 0 && srcPitch >= 8;
-    if (strip) {      // (resize_strip_fits on the host tables; OLF_RESIZE=0 keeps the LDS-tiled kernel for A/B measurements)
+    strip = strip && (dstPitch & 3) == 0 && (dstImgStride & 3) == 0 && srcPitch >= 8;
+    if (strip) {      // (resize_strip_fits on the host tables; what does not fit takes the LDS-tiled kernel)
         const int nsx = (dw + 3) / 4;
         hipLaunchKernelGGL(k_resize_strip, dim3((nsx + 63) / 64, (dh + RS_ROWS - 1) / RS_ROWS, n_images), dim3(64), 0, s, src, srcImgStride, srcPitch, sw, sh,
                            dst, dstImgStride, dstPitch, dw, dh, d_rx, d_ry, nsx);

@@ -159,7 +159,7 @@ constexpr int LR_U = 16, LR_P = LR_U + 1;      // samples per step; row pitch of
 template <bool LEAN>      // LEAN: the image is smaller than 32768 - 256 pixels a side (chosen at the launch): the lean form of the sample coordinates below
 __global__ __launch_bounds__(256) void k_lbd_rows(const LineGeom* __restrict__ gp, const uint32_t* __restrict__ dxdyAll,
                                                   const olf_keyline* __restrict__ kls, const int* __restrict__ counts,
-                                                  const float2* __restrict__ starts, float4* __restrict__ rowSums, int transposeFlat)
+                                                  const float2* __restrict__ starts, float4* __restrict__ rowSums)
 {
     __shared__ uint32_t s_t[4][64 * LR_P];
     const LineGeom& g = *gp;
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void k_lbd_rows(const LineGeom* __restrict__ g
     const float dO0 = -dL1, dO1 = dL0;
     float sCorX = s0.x, sCorY = s0.y;
     float pgdL = 0, ngdL = 0, pgdO = 0, ngdO = 0;
-    const bool flat = transposeFlat && fabsf(dL0) >= fabsf(dL1);      // (wave-uniform: one line per wave)
+    const bool flat = fabsf(dL0) >= fabsf(dL1);      // (wave-uniform: one line per wave)
     uint32_t* tb = s_t[wv];
     // the sample coordinates are a cheap sequential float chain, the sums a sequential one on the loaded values: 16 samples are
     // addressed and loaded per step so that their loads are in flight together, then accumulated in order
@@ -346,8 +346,6 @@ __global__ __launch_bounds__(64) void k_lbd_desc(const LineGeom* __restrict__ gp
 
 // LBD gradient images: GaussianBlur(5x5, sigma 1) then Sobel (computeGaussianPyramid / computeSobel) -- they depend on the input images only, so the
 // fused entry runs them on the ORB stream in the shadow of the seed ordering (api.cpp, schedule 5)
-// OLF_LBD_T=0: every line through the direct loads (A/B)
-static int lbd_rows_transpose() { static const int v = !(getenv("OLF_LBD_T") && atoi(getenv("OLF_LBD_T")) == 0); return v; }
 
 int launch_lbd_dense(const LineGeom& g, const LineDeviceBufs& b, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s)
 {
@@ -370,10 +368,10 @@ int launch_line_select_lbd(const LineGeom& g, const LineDeviceBufs& b, const uin
     hipLaunchKernelGGL(k_lbd_prep, dim3((g.outCap + 63) / 64, n_images), dim3(64), 0, s, b.geom, d_kls, d_counts, reinterpret_cast<float2*>(b.lbdStarts));
     if (g.W + 256 < 32768 && g.H + 256 < 32768)
         hipLaunchKernelGGL(k_lbd_rows<true>, dim3((g.outCap + 3) / 4, n_images), dim3(256), 0, s, b.geom, b.dxdy, d_kls, d_counts,
-                           reinterpret_cast<const float2*>(b.lbdStarts), reinterpret_cast<float4*>(b.rowSums), lbd_rows_transpose());
+                           reinterpret_cast<const float2*>(b.lbdStarts), reinterpret_cast<float4*>(b.rowSums));
     else
         hipLaunchKernelGGL(k_lbd_rows<false>, dim3((g.outCap + 3) / 4, n_images), dim3(256), 0, s, b.geom, b.dxdy, d_kls, d_counts,
-                           reinterpret_cast<const float2*>(b.lbdStarts), reinterpret_cast<float4*>(b.rowSums), lbd_rows_transpose());
+                           reinterpret_cast<const float2*>(b.lbdStarts), reinterpret_cast<float4*>(b.rowSums));
     hipLaunchKernelGGL(k_lbd_desc, dim3((g.outCap + 63) / 64, n_images), dim3(64), 0, s, b.geom, reinterpret_cast<const float4*>(b.rowSums),
                        d_counts, d_desc);
     OLF_HIP_CHECK(hipGetLastError());
@@ -388,10 +386,10 @@ int launch_lbd_only(const LineGeom& g, const LineDeviceBufs& b, const uint8_t* d
     hipLaunchKernelGGL(k_lbd_prep, dim3((g.outCap + 63) / 64, n_images), dim3(64), 0, s, b.geom, d_kls, d_counts, reinterpret_cast<float2*>(b.lbdStarts));
     if (g.W + 256 < 32768 && g.H + 256 < 32768)
         hipLaunchKernelGGL(k_lbd_rows<true>, dim3((g.outCap + 3) / 4, n_images), dim3(256), 0, s, b.geom, b.dxdy, d_kls, d_counts,
-                           reinterpret_cast<const float2*>(b.lbdStarts), reinterpret_cast<float4*>(b.rowSums), lbd_rows_transpose());
+                           reinterpret_cast<const float2*>(b.lbdStarts), reinterpret_cast<float4*>(b.rowSums));
     else
         hipLaunchKernelGGL(k_lbd_rows<false>, dim3((g.outCap + 3) / 4, n_images), dim3(256), 0, s, b.geom, b.dxdy, d_kls, d_counts,
-                           reinterpret_cast<const float2*>(b.lbdStarts), reinterpret_cast<float4*>(b.rowSums), lbd_rows_transpose());
+                           reinterpret_cast<const float2*>(b.lbdStarts), reinterpret_cast<float4*>(b.rowSums));
     hipLaunchKernelGGL(k_lbd_desc, dim3((g.outCap + 63) / 64, n_images), dim3(64), 0, s, b.geom, reinterpret_cast<const float4*>(b.rowSums),
                        d_counts, d_desc);
     OLF_HIP_CHECK(hipGetLastError());

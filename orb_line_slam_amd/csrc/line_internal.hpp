@@ -116,12 +116,8 @@ struct LineDeviceBufs {
     int logCapOverride = 0;        // olf_debug_lsd_log_cap: > 0 caps the primary log (entries) -- tests of the spill path
 };
 
-#ifdef OLF_NO_BATCH_CTX
-constexpr int kBatchCtxImages = 1 << 30;      // (A/B builds)
-#else
+// contexts for more images than this are batch contexts: the one-wave agent only (no owner words), pixel log sized by a bound + spill arena
 constexpr int kBatchCtxImages = 2048;
-#endif
-//        // contexts for more images than this are batch contexts: the one-wave agent only (no owner words), pixel log sized by a bound + spill arena
 
 struct LineHostTables {
     LineGeom geom;

@@ -136,10 +136,7 @@ __global__ __launch_bounds__(256) void k_lsd_grad(const uint8_t* __restrict__ sc
 // LSD_REFINE_ADV's rect_nfa read nothing of it, but olf_lsd_debug_scaled does) and never read back.  Saves k_lsd_grad's pass (its loads, unpacking and
 // index arithmetic: 0.49 M instructions per image) and a kernel boundary.  Only for the std::sort seed order, which does not need k_lsd_grad's per-chunk
 // counts of defined pixels.
-#ifndef OLF_UG_ROWS
-#define OLF_UG_ROWS 8
-#endif
-constexpr int UG_ROWS = OLF_UG_ROWS;
+constexpr int UG_ROWS = 8;
 __global__ __launch_bounds__(64) void k_lsd_upgrad(const uint8_t* __restrict__ src, uint8_t* __restrict__ scaled, uint32_t* __restrict__ grad,
                                                    const LineGeom* __restrict__ gp, const ResizeCoef* __restrict__ rx, const ResizeCoef* __restrict__ ry,
                                                    int* __restrict__ maxN, int nsx, int writeScaled)
@@ -932,7 +929,7 @@ constexpr int PEND = 1024;   // hash table of pixels whose USED store may not be
 // REFINE (lsd_refine = LSD_REFINE_STD): every region of minRegSize pixels is fitted and, if its density is below the threshold, un-used, grown again
 // under the tolerance tau derived from its angles, and shrunk (reduce_region_radius) -- all inside the seed loop, because the pixels it gives back are
 // seeds and neighbours of later regions.  The agent then writes the segment candidates itself (candAll) and k_lsd_rect is not launched.
-// PF (REFINE = 0 only; bits, A/B through OLF_GROW_PF): 1 = the seed windows as a software pipeline (keys two windows ahead, the windows' gradient words one
+// PF (REFINE = 0 only; bits): 1 = the seed windows as a software pipeline (keys two windows ahead, the windows' gradient words one
 // window ahead; a flush of the pending table first folds the table into the seed masks, so no window is ever gathered twice), 2 = the rows above and
 // below every live seed of a window are requested when the window starts (a region's first 3x3 gather then finds them in the cache instead of in HBM),
 // 4 = the row beyond every candidate of a growth step is requested beside its table entry (the next step's gather).
@@ -941,7 +938,7 @@ constexpr int PEND = 1024;   // hash table of pixels whose USED store may not be
 // registers: the candidates of an entry are (3 x 3 mask << lane) & live & aligned, lane order inside the window IS the reference's raster order, an accept
 // is the plain sequential step, an entry without candidates costs a handful of scalar instructions instead of a gather.  The accepted pixels are published
 // in one batch (USED bits, pending table; ring and log only if the region goes on or reaches minRegSize).  The general loop takes over at the first entry
-// on the window's outer ring, or when OLF_WIN_MAXPEND entries are pending (there its 8 entries per gather and its speculative rounds pay).  On the bench
+// on the window's outer ring, or when kWinMaxPend entries are pending (there its 8 entries per gather and its speculative rounds pay).  On the bench
 // scene 10.4 k regions per image have 8.4 k non-isolated starts; 6.9 k of them end inside the window (tools/grow_region_model.py), and the general loop's
 // 38.5 k iterations per image become 8.4 k window gathers + < 20 k iterations.
 // 16 = the CHEAP ALIGNMENT TEST (round 6): the reference's region angle is cv::fastAtan2 of the float sums -- 33 vector instructions for a value that is only
@@ -959,7 +956,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                                                  int* __restrict__ status, const AngEnt* __restrict__ ent, int* __restrict__ growFmt,
                                                  SegCand* __restrict__ candAll, int retry)
 {
-    OLF_SET_AGENT_PRIO();
     // PF bit 32 = WIDE (lsd_wide.hip: lsd_n_bins > 1024 or a working image of 2^22 pixels and more): the seed list holds plain 32-bit addresses, 2 Ps words per image
     constexpr bool WIDE = (PF & 32) != 0;
     constexpr uint32_t kAddrMask = WIDE ? 0xffffffffu : 0x3fffffu;
@@ -997,13 +993,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
     }
     const uint32_t logLast = (uint32_t)logCap - 1u;
     bool over = false;
-#ifdef OLF_NO_LOGCHECK      // (A/B builds only: the log is assumed to fit)
-#define LOG_ROOM(NEED) do { } while (0)
-#define LOG_AT(IDX) reg[rbase + (IDX)]
-#else
 #define LOG_ROOM(NEED) do { if (rbase + (NEED) > logCap) over = true; } while (0)
 #define LOG_AT(IDX) reg[min((uint32_t)(rbase + (IDX)), logLast)]
-#endif
     RegionRec* recs = recsAll + (size_t)img * g.maxRegions;
     const int nkeys = keyCount[img * 32];
     const double prec = g.prec, precWrap = g.precWrap;
@@ -1022,15 +1013,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
     long long st_win = 0, st_seedl = 0, st_regl = 0, st_acc = 0, st_isos = 0, st_logged = 0, st_winLive = 0, st_first = 0, st_cand1 = 0, st_acc1 = 0;
     long long st_wentries = 0, st_whand = 0, st_wdone = 0, st_wpend = 0;
 #endif
-#ifdef OLF_TIMING2
-    long long p_ring = 0, p_gather = 0, p_table = 0, p_chain = 0, p_commit = 0, p_n = 0, ps;
-#define PSTAMP(acc) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const long long _t = __builtin_readcyclecounter(); acc += _t - ps; ps = _t; } while (0)
-#else
-#define PSTAMP(acc)
-#endif
-#ifdef OLF_TIMING
-    long long t_seed = 0, t_small = 0, t_big = 0, t_rect = 0, n_small = 0, n_big = 0, it_small = 0, it_big = 0; long long t0 = __builtin_readcyclecounter();
-#endif
 
 #ifdef OLF_STATS
 #define ST_FLUSH ++st_flush;
@@ -1048,9 +1030,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                                               SN = wave_vote(fabsf(_crs) >= __fmaf_rn(tanHi, _dot, kAlDelta)); } while (0)
 // reg_angle as the reference has it at this point (CHEAP keeps the sums only: a region's first angle is its seed's own, every later one fastAtan2 of the sums)
 #define ENSURE_ANGLE() do { if (CHEAP) reg_angle = n == 1 ? rlane_d(seedAng, l) : d_mul((double)agent_fastAtan2(sumdy, sumdx), kDegToRads); } while (0)
-#ifndef OLF_WIN_MAXPEND
-#define OLF_WIN_MAXPEND 16
-#endif
+    constexpr int kWinMaxPend = 16;
     // window phase: lane L < 49 is pixel (seed.x + L % 7 - 3, seed.y + L / 7 - 3)
     constexpr unsigned long long kW49 = (1ull << 49) - 1ull, kSeedBit = 1ull << 24, kM3 = 7ull | (7ull << 7) | (7ull << 14);
     constexpr unsigned long long kRow5 = 0x3eull, kD2 = (kRow5 << 7) | (kRow5 << 14) | (kRow5 << 21) | (kRow5 << 28) | (kRow5 << 35);      // rows, columns 1 .. 5
@@ -1244,7 +1224,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                             cand &= after;                                   // the entry's later neighbours, under the new angle
                             al = cand & alM;
                         } while (al);
-                        lim = n - i > OLF_WIN_MAXPEND ? i + 1 : min(n, ringAt);
+                        lim = n - i > kWinMaxPend ? i + 1 : min(n, ringAt);
                     }
                     if (++i >= lim) break;
                 }
@@ -1272,9 +1252,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                 if (lane == 0) { const uint32_t pk = sx0 | (sy0 << 16); s_ring[0] = pk; LOG_AT(0) = make_uint2(pk, pseed); }
                 __builtin_amdgcn_wave_barrier();
             }
-#ifdef OLF_TIMING
-            { long long t1 = __builtin_readcyclecounter(); t_seed += t1 - t0; t0 = t1; }
-#endif
             // the check that two pixels accepted in one iteration did not hash to one table slot is read back after the commit's writes but only
             // looked at below the next iteration's ring read (one LDS round trip less on the agent's dependent chain)
             bool chkOn = false;
@@ -1286,9 +1263,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                                               _bad = wave_vote(wave_bit(_bad) && s_pend[_s] != chkA); } \
                                chkOn = false; } } while (0)
             while (i < n) {
-#ifdef OLF_TIMING
-                if (n >= minRegSize) ++it_big; else ++it_small;
-#endif
                 const int nb = min(8, n - i);
                 const int e = lane >> 3, k = (lane & 7) + ((lane & 7) >= 4 ? 1 : 0);      // 8 FIFO entries x 8 neighbours (k = 4 is the entry's own pixel)
                 const int pfOff = (k / 3 - 1) * Ws;
@@ -1297,9 +1271,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
 #endif
                 // one predicate, no nested regions: every lane forms an address (0 when it has nothing to look at) and loads; only the
                 // table lookups, which cost real cache traffic, are skipped for non-candidates
-#ifdef OLF_TIMING2
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); ps = __builtin_readcyclecounter(); ++p_n;
-#endif
                 // candidates as lane masks (scalar registers) from here on: lane 8 e + j looks at neighbour j of FIFO entry e, the first nb entries count
                 const unsigned long long geo = ~0ull >> (64 - 8 * nb);      // (nb in [1, 8]: one shift instead of shift + not + two selects)
                 // (the ring read is unconditional and the memory read a rare wave-uniform branch: as one conditional expression the two became a
@@ -1311,7 +1282,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                 const int xx = (int)(rp & 0xffffu) + (k % 3) - 1, yy = (int)(rp >> 16) + (k / 3) - 1;
                 const unsigned long long inImg = geo & wave_vote((unsigned)xx < (unsigned)Ws) & wave_vote((unsigned)yy < (unsigned)Hs);
                 const int a = wave_bit(inImg) ? yy * Ws + xx : 0;
-                PSTAMP(p_ring);
                 const uint32_t pw = grad[(uint32_t)a];      // (an unsigned index: the 32-bit offset form of the load, no sign extension and 64-bit add)
                 const int pendv = s_pend[a & (PEND - 1)];      // (unconditional: issued beside the gradient load instead of behind it; the commit reuses it)
                 const int xy = xx | (yy << 16);
@@ -1320,7 +1290,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                 double ang, cs, sn;
                 float2 dir;
                 if (CHEAP) asm volatile("" : "=v"(cs), "=v"(sn), "=v"(dir.x), "=v"(dir.y)); else asm volatile("" : "=v"(ang), "=v"(cs), "=v"(sn));
-                PSTAMP(p_gather);
                 uint32_t pfC = 0;
                 if (wave_bit(cm)) {
                     const AngEnt* t = ent + (pw & 0x3fffffu);      // one 32-byte sector per candidate
@@ -1333,7 +1302,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                 // candidates in lane order = the reference's visiting order.  Under a fixed reg_angle every lane tests
                 // its own candidate at once; the first aligned one is accepted (everything before it is rejected under
                 // that same angle, as in the reference), the angle is updated and the rest is re-tested.
-                PSTAMP(p_table);
                 unsigned long long acc = 0;
 #ifdef OLF_STATS
                 st_cand += __popcll(cm); if (i == 0) { ++st_first; st_cand1 += __popcll(cm); }
@@ -1364,10 +1332,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                     }
                     const unsigned long long al = wasM & cm;      // cm only ever holds live candidates
                     if (!al) break;
-#ifndef OLF_GROW_SINGLE_MAX
-#define OLF_GROW_SINGLE_MAX 2      // (two aligned candidates: two plain steps are 110 instructions, a speculative round 139; from three on the round wins -- profiles/r4p_stages.txt)
-#endif
-                    if (OLF_GROW_SINGLE_MAX == 1 ? (al & (al - 1ull)) == 0 : __popcll(al) <= OLF_GROW_SINGLE_MAX) {
+                    // (up to two aligned candidates: two plain steps are 110 instructions, a speculative round 139; from three on the round wins -- profiles/r4p_stages.txt)
+                    if (__popcll(al) <= 2) {
                         // a single aligned candidate: the plain sequential step
 #ifdef OLF_STATS
                         ++st_single;
@@ -1458,7 +1424,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                         if (!CHEAP) reg_angle = d_mul((double)agent_fastAtan2(sy, sx), kDegToRads);
                     }
                 }
-                PSTAMP(p_chain);
                 // vmcnt(0) while only loads can be outstanding (they have long returned): behind this point the stores below are the only vector
                 // memory operations in flight, so the next iteration's ring read and address arithmetic need not wait for their acknowledgement
                 // (without it the compiler waits at the loop head -- a table load of a lane that was no candidate may still target a live register)
@@ -1485,7 +1450,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                 }
                 i += nb;
                 __builtin_amdgcn_wave_barrier();
-                PSTAMP(p_commit);
             }
             PEND_VERIFY();
 #undef PEND_VERIFY
@@ -1574,9 +1538,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                     } else if (lane == 0) atomicOr(status, 8);
                 }
             }
-#ifdef OLF_TIMING
-            { long long t1 = __builtin_readcyclecounter(); if (n >= minRegSize) { t_big += t1 - t0; ++n_big; } else { t_small += t1 - t0; ++n_small; } t0 = t1; }
-#endif
             if (!REFINE && n >= minRegSize) {
                 // a region large enough to become a segment: keep its pixel list (the log only moves forward for these) and record
                 // (start, size, final region angle); k_lsd_rect fits all rectangles of the batch in parallel afterwards
@@ -1589,9 +1550,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                     rbase += n;
                 } else if (lane == 0) atomicOr(status, 8);
             }
-#ifdef OLF_TIMING
-            { long long t1 = __builtin_readcyclecounter(); t_rect += t1 - t0; t0 = t1; }
-#endif
             // seeds later in this 64-key window may have been consumed by the region just grown
 #ifdef OLF_STATS
             st_acc += n; if (n >= minRegSize) st_logged += n; if (n > 1) st_regl += __popcll(wave_vote(valid && lane > l));
@@ -1625,12 +1583,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
 #undef MARK_USED
 #undef PEND_FLUSH
 #undef PEND_CLEAR
-#ifdef OLF_TIMING
-    if (lane == 0 && img == 0) { long long* o = reinterpret_cast<long long*>(status + 16); o[0] = t_seed; o[1] = t_small; o[2] = t_big; o[3] = t_rect; o[4] = n_small; o[5] = n_big; o[6] = it_small; o[7] = it_big; }
-#endif
-#ifdef OLF_TIMING2
-    if (lane == 0 && img == 0) { long long* o = reinterpret_cast<long long*>(status + 16); o[0] = p_ring; o[1] = p_gather; o[2] = p_table; o[3] = p_chain; o[4] = p_commit; o[5] = p_n; }
-#endif
 #ifdef OLF_STATS
     if (lane == 0 && img == 0) { long long* o = reinterpret_cast<long long*>(status + 16); o[0] = st_rounds; o[1] = st_k; o[2] = st_t; o[3] = st_full; o[4] = st_single; o[5] = st_rounds_big; o[6] = st_k_big; o[7] = st_t_big;
         o[8] = st_flush; o[9] = st_iters; o[10] = st_deep1; o[11] = st_deep2; o[12] = st_cand; o[13] = st_regions; o[14] = st_mem;
@@ -1875,9 +1827,7 @@ int launch_lsd_front(const LineGeom& g, LineDeviceBufs& b, const uint8_t* d_in, 
     OLF_HIP_CHECK(hipMemsetAsync(b.keyCount, 0, (size_t)n_images * 32 * sizeof(int), s));
     { int rc = launch_gauss7_img(d_in, in_pitch, (size_t)in_pitch * g.H, b.lsdBlur, g.pitchW, (size_t)g.pitchW * g.H, g.W, g.H, g, 0, n_images, s);
       if (rc != OLF_OK) return rc; }
-    // OLF_UPGRAD=0: enlargement and gradient as two kernels (A/B measurements)
-    static const bool upgrad = [] { const char* e = getenv("OLF_UPGRAD"); return !e || atoi(e) != 0; }();
-    const bool fused = upgrad && (g.resizeTiled & 4) && g.seedOrder == 1;
+    const bool fused = (g.resizeTiled & 4) && g.seedOrder == 1;
     if (fused) {
         const int nsx = (g.Ws + 3) / 4;
         hipLaunchKernelGGL(k_lsd_upgrad, dim3((nsx + 63) / 64, (g.Hs + UG_ROWS - 1) / UG_ROWS, n_images), dim3(64), 0, s, b.lsdBlur, b.scaled, b.grad, b.geom, b.rx, b.ry,
@@ -1892,13 +1842,10 @@ int launch_lsd_front(const LineGeom& g, LineDeviceBufs& b, const uint8_t* d_in, 
     }
     if (!fused) hipLaunchKernelGGL(k_lsd_grad, dim3((g.Ps + LG_CHUNK - 1) / LG_CHUNK, n_images), dim3(256), 0, s, b.scaled, b.grad, b.geom, b.maxN, b.chunkCnt);
     {
-        // (ALLKEYS, OLF_KEYS_CHUNK=8192: 8192-pixel chunks -- the stage alone 62.6 against 63.4 ms per 6144 images, the two-stream step 231-236 against 232-234:
-        // two blocks of 61 KB per CU overlap worse with the pyramid beside them than four of 36 KB; 4096 stays the default, profiles/r4y_keys_chunk_ab.txt)
-        static const int envCh = getenv("OLF_KEYS_CHUNK") ? atoi(getenv("OLF_KEYS_CHUNK")) : 4096;
-        const bool big = g.seedOrder == 1 && envCh == 8192 && (size_t)(8192 + 2 * g.Ws + 2) * sizeof(float) + 8192 * 2 + 64 <= 64 * 1024;
-        const int CHK = big ? 8192 : LG_CHUNK;
-        const int nChunks = (g.Ps + CHK - 1) / CHK, total = nChunks * n_images;
-        const size_t lds = (size_t)(CHK + 2 * g.Ws + 2) * sizeof(float);
+        // (4096-pixel chunks: 8192 ran the stage alone 62.6 against 63.4 ms per 6144 images, but the two-stream step 231-236 against 232-234 -- two blocks
+        // of 61 KB per CU overlap worse with the pyramid beside them than four of 36 KB, profiles/r4y_keys_chunk_ab.txt)
+        const int nChunks = (g.Ps + LG_CHUNK - 1) / LG_CHUNK, total = nChunks * n_images;
+        const size_t lds = (size_t)(LG_CHUNK + 2 * g.Ws + 2) * sizeof(float);
         if (lds > 60 * 1024) { set_error("LSD image wider than the key kernel's LDS window"); return OLF_ERR_CAPACITY; }
         const bool ow = lsd_grow_path(g, b, n_images) != 0;
         if (g.wide) {      // 64-bit keys, both conventions into keysA (lsd_wide.hip sorts them in place and lists the addresses in keysB)
@@ -1908,13 +1855,9 @@ int launch_lsd_front(const LineGeom& g, LineDeviceBufs& b, const uint8_t* d_in, 
             if (b.sortEvent) OLF_HIP_CHECK(hipEventRecord(b.sortEvent, s));
             return launch_lsd_sort_wide(g, b, n_images, s, -1, -1, -1, -1);
         }
-#define KEYS_LAUNCH(OW, AK, C, KBUF) hipLaunchKernelGGL((k_lsd_keys<OW, AK, C>), dim3(total), dim3(KEYS_THREADS), lds, s, b.grad, b.geom, b.maxN, b.chunkCnt, KBUF, b.keyCount, b.owner, b.angDeg, nChunks, total)
-        if (g.seedOrder == 1) {
-            if (big) { if (ow) KEYS_LAUNCH(true, true, 8192, b.keysA); else KEYS_LAUNCH(false, true, 8192, b.keysA); }
-            else { if (ow) KEYS_LAUNCH(true, true, LG_CHUNK, b.keysA); else KEYS_LAUNCH(false, true, LG_CHUNK, b.keysA); }
-        } else {
-            if (ow) KEYS_LAUNCH(true, false, LG_CHUNK, b.keysB); else KEYS_LAUNCH(false, false, LG_CHUNK, b.keysB);
-        }
+#define KEYS_LAUNCH(OW, AK, KBUF) hipLaunchKernelGGL((k_lsd_keys<OW, AK, LG_CHUNK>), dim3(total), dim3(KEYS_THREADS), lds, s, b.grad, b.geom, b.maxN, b.chunkCnt, KBUF, b.keyCount, b.owner, b.angDeg, nChunks, total)
+        if (g.seedOrder == 1) { if (ow) KEYS_LAUNCH(true, true, b.keysA); else KEYS_LAUNCH(false, true, b.keysA); }
+        else { if (ow) KEYS_LAUNCH(true, false, b.keysB); else KEYS_LAUNCH(false, false, b.keysB); }
 #undef KEYS_LAUNCH
     }
     OLF_HIP_CHECK(hipGetLastError());
@@ -1928,12 +1871,9 @@ int launch_lsd_front(const LineGeom& g, LineDeviceBufs& b, const uint8_t* d_in, 
 int launch_lsd_grow_mw(const LineGeom& g, LineDeviceBufs& b, int n_images, int nw, int E, int G, hipStream_t s);
 
 // workgroups (CUs) per image of the multi-wave growth: the drop-in's online shape -- one stereo pair per call -- leaves 254 CUs idle with one workgroup per image
-// (OLF_LSD_GROUPS forces 1 / 2 / 4 for A/B runs)
 int lsd_grow_groups(int n_images, int nw)
 {
-    static const int forced = [] { const char* e = getenv("OLF_LSD_GROUPS"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 2 || v == 4) ? v : 0; }();
     if (nw < 16) return 1;
-    if (forced) return n_images <= kMgMaxImages ? forced : 1;      // (launch_lsd_grow halves it until every group fits a CU of its own)
     // (two groups, not four: one pair 8.45 against 8.95 ms, 8 pairs 10.3 against 10.8 -- the further a group runs ahead of the commit order the more of what it grows
     // is taken from it again by older seeds, profiles/r5a_growth_groups.txt)
     if (n_images <= kMgMaxImages) return 2;
@@ -1941,11 +1881,9 @@ int lsd_grow_groups(int n_images, int nw)
 }
 
 // waves per image of the multi-wave growth: as many as keep the chip full (8 waves per SIMD x 1024 SIMDs) without leaving a small batch
-// to a handful of waves; 0 selects the one-wave agent of round 1 (kept for A/B measurements, OLF_LSD_NW=0)
+// to a handful of waves; 0 selects the one-wave agent of round 1
 int lsd_grow_waves(int n_images)
 {
-    static const int forced = [] { const char* e = getenv("OLF_LSD_NW"); return e ? std::max(-1, std::min(16, atoi(e))) : -1; }();
-    if (forced >= 0) return forced;
     if (n_images <= 512) return 16;
     if (n_images <= 1024) return 8;
     if (n_images <= 1536) return 4;      // (8 waves x 1280 images no longer fit the 8192 wave slots: the 1080p batch takes 203 ms with 8, 188 with 4; KITTI size: equal)
@@ -1960,9 +1898,7 @@ int launch_lsd_grow(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStrea
     if (b.spillCtl) OLF_HIP_CHECK(hipMemsetAsync(b.spillCtl, 0, sizeof(int), s));      // blocks of the spill arena handed out in this call
     b.chained = nw != 0;
     if (nw > 0) {
-        // OLF_LSD_ROB: reorder-buffer entries for experiments (a power of two in [128, 512]; anything else is ignored)
-        static const int envE = [] { const char* e = getenv("OLF_LSD_ROB"); const int v = e ? atoi(e) : 0; return (v == 128 || v == 256 || v == 512 || v == 1024) ? v : 0; }();
-        int E = b.forceE > 0 ? b.forceE : envE > 0 ? envE : (nw >= 16 ? 512 : nw >= 8 ? 256 : 128);
+        const int E = b.forceE > 0 ? b.forceE : (nw >= 16 ? 512 : nw >= 8 ? 256 : 128);
         int G = b.forceG > 0 ? b.forceG : lsd_grow_groups(n_images, nw);
         const int pool = b.poolChunks > 0 ? std::min(b.poolChunks, b.nChunks) : b.nChunks;
         // (every group of an image has to be resident -- a group spins on its partners' watermarks -- i.e. one workgroup per CU of THIS device)
@@ -1996,11 +1932,9 @@ int launch_lsd_grow(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStrea
         hipLaunchKernelGGL((k_lsd_grow<1, 0>), dim3(n_images), dim3(64), 0, s, b.geom, b.grad, b.keysB, b.keyCount, b.region,
                            (RegionRec*)nullptr, b.regCount, b.status, reinterpret_cast<const AngEnt*>(b.angEnt), (int*)nullptr, reinterpret_cast<SegCand*>(b.keysA), RETRY);
     else {
-        static const int pfEnv = [] { const char* e = getenv("OLF_GROW_PF"); return e ? atoi(e) : 27; }();
-        const int pf = g.alignTanLo < 0.f ? (pfEnv & ~16) : pfEnv;      // (ang_th > 80 degrees: no cheap alignment test)
 #define GROW0(PFV) hipLaunchKernelGGL((k_lsd_grow<0, PFV>), dim3(n_images), dim3(64), 0, s, b.geom, b.grad, b.keysB, b.keyCount, b.region, \
                            reinterpret_cast<RegionRec*>(b.keysA), b.regCount, b.status, reinterpret_cast<const AngEnt*>(b.angEnt), (int*)nullptr, (SegCand*)nullptr, RETRY)
-        if (pf == 0) GROW0(0); else if (pf == 3) GROW0(3); else if (pf == 11) GROW0(11); else if (pf == 19) GROW0(19); else GROW0(27);
+        if (g.alignTanLo < 0.f) GROW0(11); else GROW0(27);      // (ang_th > 80 degrees: no cheap alignment test)
 #undef GROW0
     }
     }

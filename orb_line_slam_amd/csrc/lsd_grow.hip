@@ -513,7 +513,6 @@ __device__ __forceinline__ int mw_pick(const MwCtx& c, const MwCtl& cv, int* pre
         int st = i < t ? WG_LOAD(c.eState + slot) : (int)ST_EMPTY;
         uint32_t bl = WG_LOAD(c.eBlock + slot);
         const uint32_t iv = WG_LOAD(c.eInval + slot);
-#ifndef OLF_MW_NO_BULK
         {
             // seeds parked on a region that is final now -- all of this step at once: one look at the seed's owner word decides "consumed for good" (DEAD, the
             // common case behind the first few thousand seeds) without a region run of its own (pick, prologue, claim, finish: 6-7 k cycles each); a seed that
@@ -534,7 +533,6 @@ __device__ __forceinline__ int mw_pick(const MwCtx& c, const MwCtl& cv, int* pre
                 }
             }
         }
-#endif
         if (open) {
             const unsigned long long sm = wave_vote(st == ST_DEAD || (st == ST_DONE && iv == MW_FREE));
             const int run = sm == ~0ull ? 64 : __builtin_ctzll(~sm);
@@ -895,8 +893,7 @@ __global__ __launch_bounds__(1024) void k_lsd_grow_mw(const LineGeom* __restrict
     }
     __syncthreads();
     const double prec = g.prec, precWrap = g.precWrap;
-    const bool dedicated = MG && nw >= 4 && !(ahead & 0x10000);        // wave 0 of the group commits and publishes, the others grow (bit 16 of `ahead`: OLF_MW_NO_COMMIT_WAVE, A/B)
-    ahead &= 0xffff;
+    const bool dedicated = MG && nw >= 4;        // wave 0 of the group commits and publishes, the others grow
     int idle = 0, cwHead = -1, cwTail = -1;
     PROF_DECL;
     for (;;) {
@@ -1031,28 +1028,23 @@ int launch_lsd_grow_mw(const LineGeom& g, LineDeviceBufs& b, int n_images, int n
         }
     }
     const int poolLimit = b.poolChunks > 0 ? std::min(b.poolChunks, b.nChunks) : b.nChunks;
-    // entries in the buffer below which any wave tops it up before it looks for a region (OLF_MW_AHEAD for A/B runs)
-    static const int envAhead = [] { const char* e = getenv("OLF_MW_AHEAD"); return e ? atoi(e) : 0; }();
-    static const int noCw = getenv("OLF_MW_NO_COMMIT_WAVE") ? 0x10000 : 0;
-    const int ahead = (envAhead > 0 ? std::min(envAhead, E - 64) : E / 2) | noCw;
+    // entries in the buffer below which any wave tops it up before it looks for a region
+    const int ahead = E / 2;
+    // log2 of the seed window the groups are dealt
+    const int wsBits = 10;
     if (G > 1) {
-        // OLF_LSD_WS: log2 of the seed window the groups are dealt (6 .. 10), for A/B runs
-        static const int envWs = [] { const char* e = getenv("OLF_LSD_WS"); const int v = e ? atoi(e) : 0; return (v >= 6 && v <= 13) ? v : 0; }();
-        const int wsBits = envWs ? envWs : 10;
         if (G > MG_MAX_G || E > MG_MAX_E || !b.mg || n_images > b.mgImages || poolLimit / G < E + 64) { set_error("launch_lsd_grow_mw: groups"); return OLF_ERR_INVALID; }
         // the control words of every image start at zero (watermarks 0 = nothing final yet; the notice words are set when a slot is filled)
         OLF_HIP_CHECK(hipMemset2DAsync(b.mg, b.mgStride, 0, MG_INVAL_OFF, (size_t)n_images, s));
         const int blocks = ((n_images + 7) / 8) * 8 * G;
-        static const int envScatter = getenv("OLF_LSD_SCATTER") ? atoi(getenv("OLF_LSD_SCATTER")) : 0;       // (tools/stress_mg.py under scatter)
-        const int scatter = b.scatter || envScatter;
         hipLaunchKernelGGL(k_lsd_grow_mw<true>, dim3(blocks), dim3(64 * nw), lds, s, b.geom, b.grad, b.owner, b.keysB, b.keyCount, b.region, b.links,
                            reinterpret_cast<RegionRec*>(b.keysA), b.regCount, b.status, b.angDeg, reinterpret_cast<const AngEnt*>(b.angEnt), E,
-                           b.nChunks, poolLimit, b.growFmt, b.mg, b.mgStride, G, n_images, wsBits, ahead, scatter);
+                           b.nChunks, poolLimit, b.growFmt, b.mg, b.mgStride, G, n_images, wsBits, ahead, b.scatter);
         hipLaunchKernelGGL(k_mg_merge, dim3(n_images), dim3(256), 0, s, b.geom, b.mg, b.mgStride, G, reinterpret_cast<RegionRec*>(b.keysA), b.regCount, b.growFmt);
     } else
         hipLaunchKernelGGL(k_lsd_grow_mw<false>, dim3(n_images), dim3(64 * nw), lds, s, b.geom, b.grad, b.owner, b.keysB, b.keyCount, b.region, b.links,
                            reinterpret_cast<RegionRec*>(b.keysA), b.regCount, b.status, b.angDeg, reinterpret_cast<const AngEnt*>(b.angEnt), E,
-                           b.nChunks, poolLimit, b.growFmt, (unsigned char*)nullptr, (size_t)0, 1, n_images, 10, ahead, 0);
+                           b.nChunks, poolLimit, b.growFmt, (unsigned char*)nullptr, (size_t)0, 1, n_images, wsBits, ahead, 0);
     OLF_HIP_CHECK(hipGetLastError());
     return OLF_OK;
 }

@@ -30,13 +30,7 @@
 namespace olf {
 
 // the grid-wide top levels (launch_seedsort_top, below)
-#ifndef OLF_SS_TOP_LEVELS
-#define OLF_SS_TOP_LEVELS 8
-#endif
-#ifndef OLF_SS_TOP_MIN
-#define OLF_SS_TOP_MIN 8192
-#endif
-constexpr int SS_TOP_MIN = OLF_SS_TOP_MIN, SS_TOP_JOBS = 128, SS_TOP_LEVELS = OLF_SS_TOP_LEVELS, SS_TOP_FINAL = 512;
+constexpr int SS_TOP_MIN = 8192, SS_TOP_JOBS = 128, SS_TOP_LEVELS = 8, SS_TOP_FINAL = 512;
 constexpr int SS_JW = 12;      // words of a job: first, last, depth of its children, lb, ub, pivot key, first tile, tiles, s, cut
 constexpr int SS_TOP_WORDS = 8 + 2 * SS_TOP_JOBS * SS_JW + SS_TOP_FINAL * 5;      // per image: counters [nJobs, nNext, nFinal, tiles, Kthr, n], two job lists, final entries
 constexpr int SS_CAP = 1024;      // elements of a range held in LDS (4 KB + 2 KB of exchange arrays: 24 waves = 24 images per CU)
@@ -419,26 +413,20 @@ enum { SP_PART_MEM = 0, SP_PART_LDS, SP_EQUAL, SP_LEAF, SP_LOAD, SP_PIVOT, SP_OT
 // the sorted array, so no wave needs to know what the others have emitted: ranges that stream from memory go through a stack in LDS that any idle
 // wave pops from, a range that fits a wave's LDS buffer is finished by that wave alone (its own register stack).  NEM: tiles per streamed block --
 // one wave alone is bound by the latency of a block step, not by issue slots, so the few-images variant uses larger blocks.
-// NI > 1 (= NW): the workgroup sorts NI images, one per wave to begin with, and the shared stack holds the streamed ranges of all of them (the image's
-// slot travels in the entry's depth word): a wave that runs out of work takes over a range of a neighbour's image, so the launch ends near the *mean*
-// sorting time of the images of a CU instead of the slowest one's (the big batch).
-template <int NW, int NEM, int NI = 1>
+template <int NW, int NEM>
 __device__ __forceinline__ void ss_sort_image(const LineGeom& g, int img, int n_images, uint32_t* keysInAll, uint32_t* keysOutAll, int* __restrict__ keyCount,
                                               const int* __restrict__ maxN, int* __restrict__ status, int nOverride, int kthrOverride, int depthOverride,
                                               uint32_t* s_buf, uint32_t* s_x, int* ctl, int* topImg = nullptr, int grp = 0, int Gs = 1)
 {
-    // (grp, Gs: NI == 1 behind the grid-wide top levels only -- Gs workgroups share one image: a wave that finds its workgroup's stack empty takes the next of the
+    // (grp, Gs: behind the grid-wide top levels only -- Gs workgroups share one image: a wave that finds its workgroup's stack empty takes the next of the
     // ranges the top levels left from the image's list (a counter in global memory); the ranges are disjoint in the key array and in the seed list, so nothing but
     // that counter and the seed count is shared, and the result does not depend on who sorts which range)
-    static_assert(NI == 1 || NI == NW, "one wave per image of the group");
 #ifdef OLF_SS_PROF
     long long sp_acc[SP_N] = {0}, sp_t = __builtin_readcyclecounter();
 #endif
     constexpr int CAP = NEM > SS_NE_MEM ? 4 * 64 * NEM : SS_CAP;          // elements of a range a wave keeps in LDS (= the words of its range buffer)
-    constexpr int SHCAP = NI > 1 ? 64 : 256;                              // entries of the shared stack (NW > 1)
+    constexpr int SHCAP = 256;                                            // entries of the shared stack (NW > 1)
     const int lane = threadIdx.x & 63;
-    const int img0 = img;                                                 // NI > 1: the group's first image; this wave starts on image img0 + wave
-    if (NI > 1) img = img0 + ssU((int)(threadIdx.x >> 6));      // (pinned: the wave index is uniform, the compiler does not know it)
     SsCtx c;
     c.A = keysInAll + (size_t)img * g.Ps;
     c.out = keysOutAll + (size_t)img * g.Ps;
@@ -460,8 +448,8 @@ __device__ __forceinline__ void ss_sort_image(const LineGeom& g, int img, int n_
             Kthr = (uint32_t)(g.nBins - 1 - binT);
         }
     }
-    if (NI == 1 && empty) { if (threadIdx.x == 0 && grp == 0) keyCount[img * 32] = 0; return; }
-    if (NI == 1 && Gs > 1 && !topImg && grp != 0) return;      // (no ranges to share: the first workgroup sorts the image)
+    if (empty) { if (threadIdx.x == 0 && grp == 0) keyCount[img * 32] = 0; return; }
+    if (Gs > 1 && !topImg && grp != 0) return;      // (no ranges to share: the first workgroup sorts the image)
     const int depth0 = depthOverride >= 0 ? depthOverride : 2 * (31 - __builtin_clz((unsigned)n));
     // the ranges still to do (right siblings on the path), one per lane: at most depth0 + 1 <= 43 of them
     int stF = 0, stL = 0, stD = 0;
@@ -472,11 +460,10 @@ __device__ __forceinline__ void ss_sort_image(const LineGeom& g, int img, int n_
     int* const shF = ctl + 4; int* const shL = shF + SHCAP; int* const shD = shL + SHCAP; int* const shLb = shD + SHCAP; int* const shUb = shLb + SHCAP;
 #define SS_LOCK() do { if (lane == 0) { int _sp = 0; while (atomicCAS(&ctl[0], 0, 1) != 0) { __builtin_amdgcn_s_sleep(2); if (++_sp > (1 << 22)) { atomicOr(status, 128); break; } } } __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
 #define SS_UNLOCK() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); if (lane == 0) atomicExch(&ctl[0], 0); } while (0)
-    // NI > 1: per image slot the seeds listed so far and its Kthr, behind the stack's arrays
-    int* const cntS = shUb + SHCAP; int* const kthS = cntS + 8; int* const okS = kthS + 8;
-    int curSlot = NI > 1 ? ssU((int)(threadIdx.x >> 6)) : 0;
+    // behind the stack's arrays: nonzero once the image's list of top-level ranges is exhausted
+    int* const topDone = shUb + SHCAP;
     if (NW == 1) SS_PUSH(0, n, depth0, 0u, (uint32_t)(g.nBins - 1));
-    else if (NI == 1) {
+    else {
         if (threadIdx.x == 0) {
             ctl[0] = 0; ctl[2] = 0; ctl[3] = 0;
             if (topImg) {
@@ -484,22 +471,12 @@ __device__ __forceinline__ void ss_sort_image(const LineGeom& g, int img, int n_
                 const int nf = min(topImg[2], SHCAP);
                 const int* f = topImg + 8 + 2 * SS_TOP_JOBS * SS_JW;
                 ctl[1] = 0;              // (the stack starts empty: the waves pull the ranges the top levels left one by one ...)
-                cntS[0] = 0;             // ... until the image's list is exhausted
+                topDone[0] = 0;          // ... until the image's list is exhausted
             } else { ctl[1] = 1; shF[0] = 0; shL[0] = n; shD[0] = depth0; shLb[0] = 0; shUb[0] = g.nBins - 1; }
         }
         __syncthreads();
-    } else {
-        if (lane == 0) { cntS[curSlot] = 0; kthS[curSlot] = (int)Kthr; okS[curSlot] = empty ? 0 : 1; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int e = 0;
-            for (int i = NI - 1; i >= 0; --i)      // (slot 0 on top)
-                if (okS[i]) { shF[e] = 0; shL[e] = n; shD[e] = depth0 | (i << 8); shLb[e] = 0; shUb[e] = g.nBins - 1; ++e; }
-            ctl[0] = 0; ctl[1] = e; ctl[2] = 0; ctl[3] = 0;
-        }
-        __syncthreads();
     }
-    int listedEnd = 0;                 // one past the last seed this wave has listed (of the image it is working on)
+    int listedEnd = 0;                 // one past the last seed this wave has listed
     bool inLDS = false, holding = false;
     int ldsLast = 0;
     int guard = 0;
@@ -522,7 +499,7 @@ __device__ __forceinline__ void ss_sort_image(const LineGeom& g, int img, int n_
                 const int e = ssU(__hip_atomic_load(&ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
                 const int bz = ssU(__hip_atomic_load(&ctl[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
                 if (e > 0 || bz == 0) break;
-                if (NI == 1 && topImg && ssU(__hip_atomic_load(&cntS[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0) break;      // (ranges left in the image's list)
+                if (topImg && ssU(__hip_atomic_load(&topDone[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0) break;      // (ranges left in the image's list)
                 __builtin_amdgcn_s_sleep(16);
                 if (idle > (1 << 21)) { if (lane == 0) atomicOr(status, 64); break; }
             }
@@ -531,13 +508,13 @@ __device__ __forceinline__ void ss_sort_image(const LineGeom& g, int img, int n_
             if (lane == 0) {
                 const int e = atomicAdd(&ctl[1], 0);
                 if (e > 0) { f = shF[e - 1]; l = shL[e - 1]; d = shD[e - 1]; a = shLb[e - 1]; b = shUb[e - 1]; atomicAdd(&ctl[2], 1); atomicExch(&ctl[1], e - 1); got = 1; }
-                else if (NI == 1 && topImg && cntS[0] == 0) {
+                else if (topImg && topDone[0] == 0) {
                     // the next range of the image's list (cnt[3], zero when the last top level ends)
                     const int q = atomicAdd(topImg + 3, 1);
                     if (q < topImg[2]) {
                         const int* fq = topImg + 8 + 2 * SS_TOP_JOBS * SS_JW + 5 * q;
                         f = fq[0]; l = fq[1]; d = fq[2]; a = fq[3]; b = fq[4]; atomicAdd(&ctl[2], 1); got = 1;
-                    } else cntS[0] = 1;
+                    } else topDone[0] = 1;
                 }
                 else if (atomicAdd(&ctl[2], 0) == 0) done = 1;
             }
@@ -547,17 +524,6 @@ __device__ __forceinline__ void ss_sort_image(const LineGeom& g, int img, int n_
             if (done) break;
             if (!got) continue;
             first = ssU(f); last = ssU(l); depth = ssU(d); lb = (uint32_t)ssU(a); ub = (uint32_t)ssU(b);
-            if (NI > 1) {
-                const int slot = depth >> 8;
-                depth &= 255;
-                if (slot != curSlot) {
-                    if (lane == 0 && listedEnd > 0) atomicMax(&cntS[curSlot], listedEnd);
-                    listedEnd = 0; curSlot = slot;
-                    c.A = keysInAll + (size_t)(img0 + slot) * g.Ps;
-                    c.out = keysOutAll + (size_t)(img0 + slot) * g.Ps;
-                }
-                Kthr = (uint32_t)ssU(kthS[slot]);
-            }
         }
         first = ssU(first); last = ssU(last); depth = ssU(depth); lb = (uint32_t)ssU((int)lb); ub = (uint32_t)ssU((int)ub);
         if (inLDS && first >= ldsLast) inLDS = false;
@@ -625,12 +591,11 @@ __device__ __forceinline__ void ss_sort_image(const LineGeom& g, int img, int n_
                 SS_LOCK();
                 if (lane == 0) {
                     const int e = atomicAdd(&ctl[1], 0);
-                    if (e < SHCAP) { shF[e] = cut; shL[e] = last; shD[e] = NI > 1 ? depth | (curSlot << 8) : depth; shLb[e] = (int)max(lb, Kp); shUb[e] = (int)ub; atomicExch(&ctl[1], e + 1); }
+                    if (e < SHCAP) { shF[e] = cut; shL[e] = last; shD[e] = depth; shLb[e] = (int)max(lb, Kp); shUb[e] = (int)ub; atomicExch(&ctl[1], e + 1); }
                     else full = 1;
                 }
                 SS_UNLOCK();
-                // a full stack: the wave keeps the range for itself (its own stack is emptied before it looks at the shared one again, so the
-                // range is still of the image the wave is on)
+                // a full stack: the wave keeps the range for itself
                 if (ssU(full)) SS_PUSH(cut, last, depth, max(lb, Kp), ub);
             }
             last = cut; ub = min(ub, Kp);                             // [first, cut): K <= Kp (the pivot sits at first)
@@ -644,11 +609,7 @@ __device__ __forceinline__ void ss_sort_image(const LineGeom& g, int img, int n_
     if (NW == 1 && lane == 0 && img == 0) { long long* o = reinterpret_cast<long long*>(status + 16); for (int q = 0; q < SP_N; ++q) o[q] = sp_acc[q]; }
 #endif
     if (NW == 1) { if (lane == 0) keyCount[img * 32] = listedEnd; }
-    else if (NI > 1) {
-        if (lane == 0 && listedEnd > 0) atomicMax(&cntS[curSlot], listedEnd);
-        __syncthreads();
-        if (threadIdx.x < NI && img0 + (int)threadIdx.x < n_images) keyCount[(img0 + (int)threadIdx.x) * 32] = cntS[threadIdx.x];
-    } else {
+    else {
         if (lane == 0) atomicMax(&ctl[3], listedEnd);
         __syncthreads();
         if (threadIdx.x == 0) { if (Gs > 1 && topImg) atomicMax(&keyCount[img * 32], ctl[3]); else keyCount[img * 32] = ctl[3]; }
@@ -665,14 +626,14 @@ __global__ __launch_bounds__(64) void k_lsd_seedsort(const LineGeom* __restrict_
 }
 
 // few images (the drop-in's online shape: one stereo pair per call): NW waves per image, blocks of NEM tiles
-template <int NW, int NEM, int NI>
+template <int NW, int NEM>
 __global__ __launch_bounds__(64 * NW) void k_lsd_seedsort_mw(const LineGeom* __restrict__ gp, uint32_t* keysInAll, uint32_t* keysOutAll, int* __restrict__ keyCount,
                                                             const int* __restrict__ maxN, int* __restrict__ status, int nOverride, int kthrOverride, int depthOverride,
                                                             int n_images, int* __restrict__ topAll, int Gs)
 {
     extern __shared__ __align__(8) uint32_t s_dyn[];
     constexpr int BUFW = 4 * 64 * NEM, XW = 2 * 64 * NEM;
-    const int blk = NI == 1 ? (int)blockIdx.x / Gs : (int)blockIdx.x, grp = NI == 1 ? (int)blockIdx.x % Gs : 0;
+    const int blk = (int)blockIdx.x / Gs, grp = (int)blockIdx.x % Gs;
     static_assert(XW >= 4 * 64 * SS_NE_LDS, "the LDS path's queues fit the staging area");
     const int wv = threadIdx.x >> 6;
     // the staging areas first: global_load_lds takes its LDS base from 16 bits of M0, so a staged block must lie in the first 64 KB of the
@@ -681,32 +642,8 @@ __global__ __launch_bounds__(64 * NW) void k_lsd_seedsort_mw(const LineGeom* __r
     uint32_t* s_buf = s_dyn + (size_t)NW * XW + (size_t)wv * BUFW;
     int* ctl = reinterpret_cast<int*>(s_dyn + (size_t)NW * (BUFW + XW));
     static_assert((size_t)NW * XW * 4 <= 65536, "staged blocks within reach of M0");
-    ss_sort_image<NW, NEM, NI>(*gp, blk * NI, n_images, keysInAll, keysOutAll, keyCount, maxN, status, nOverride, kthrOverride, depthOverride, s_buf, s_x, ctl,
-                               NI == 1 && topAll ? topAll + (size_t)blk * SS_TOP_WORDS : nullptr, grp, NI == 1 ? Gs : 1);
-}
-
-// the batch in image groups: NI waves, NI images, the one-wave kernel's block size and LDS per wave -- and its six waves per SIMD
-template <int NI>
-__global__ __launch_bounds__(64 * NI) __attribute__((amdgpu_waves_per_eu(6, 6)))
-void k_lsd_seedsort_grp(const LineGeom* __restrict__ gp, uint32_t* keysInAll, uint32_t* keysOutAll, int* __restrict__ keyCount,
-                        const int* __restrict__ maxN, int* __restrict__ status, int nOverride, int kthrOverride, int depthOverride, int n_images)
-{
-    extern __shared__ __align__(8) uint32_t s_dyn[];
-    constexpr int BUFW = SS_CAP, XW = 4 * 64 * SS_NE_LDS;
-    const int wv = threadIdx.x >> 6;
-    uint32_t* s_x = s_dyn + (size_t)wv * XW;                              // (staging areas first: within reach of M0)
-    uint32_t* s_buf = s_dyn + (size_t)NI * XW + (size_t)wv * BUFW;
-    int* ctl = reinterpret_cast<int*>(s_dyn + (size_t)NI * (BUFW + XW));
-    ss_sort_image<NI, SS_NE_MEM, NI>(*gp, blockIdx.x * NI, n_images, keysInAll, keysOutAll, keyCount, maxN, status, nOverride, kthrOverride, depthOverride, s_buf, s_x, ctl);
-}
-
-template <int NI>
-static int launch_seedsort_grp(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride)
-{
-    const size_t lds = ((size_t)NI * (SS_CAP + 4 * 64 * SS_NE_LDS) + 4 + 5 * 64 + 24) * 4;
-    hipLaunchKernelGGL((k_lsd_seedsort_grp<NI>), dim3((n_images + NI - 1) / NI), dim3(64 * NI), lds, s, b.geom, b.keysA, b.keysB, b.keyCount, b.maxN, b.status,
-                       nOverride, kthrOverride, depthOverride, n_images);
-    return OLF_OK;
+    ss_sort_image<NW, NEM>(*gp, blk, n_images, keysInAll, keysOutAll, keyCount, maxN, status, nOverride, kthrOverride, depthOverride, s_buf, s_x, ctl,
+                           topAll ? topAll + (size_t)blk * SS_TOP_WORDS : nullptr, grp, Gs);
 }
 
 // ---- the top of the recursion on the whole GPU (few images) -------------------------------------------------------------------------------------
@@ -1007,62 +944,55 @@ static int launch_seedsort_top(const LineGeom& g, LineDeviceBufs& b, int n_image
     return OLF_OK;
 }
 
-template <int NW, int NEM, int NI>
+template <int NW, int NEM>
 static int launch_seedsort_mw(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride)
 {
-    // per wave: range buffer + staging area; then lock / counters, the shared stack's five arrays (256 entries, 64 for image groups) and the groups' slots
-    const size_t lds = ((size_t)NW * (4 * 64 * NEM + 2 * 64 * NEM) + 4 + 5 * (NI > 1 ? 64 : 256) + 24) * 4;
+    // per wave: range buffer + staging area; then lock / counters, the shared stack's five arrays (256 entries) and the top-level list's flag
+    const size_t lds = ((size_t)NW * (4 * 64 * NEM + 2 * 64 * NEM) + 4 + 5 * 256 + 1) * 4;
     if (lds > 64 * 1024) {     // the attribute belongs to the device the launch goes to: set once per device (the call is a host round trip in front of every one-pair call otherwise)
         static bool done[64] = {};
         int dev = 0;
         OLF_HIP_CHECK(hipGetDevice(&dev));
         if (dev < 0 || dev >= 64 || !done[dev]) {
-            OLF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lsd_seedsort_mw<NW, NEM, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            OLF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lsd_seedsort_mw<NW, NEM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             if (dev >= 0 && dev < 64) done[dev] = true;
         }
     }
-    // OLF_SS_TOP=0: the whole recursion inside the per-image workgroup (A/B measurements)
-    static const bool top = [] { const char* e = getenv("OLF_SS_TOP"); return !e || atoi(e) != 0; }();
     // (few images only: the grids cover every possible tile of every image at every level -- at 128 images the two forms are level, at 1024 the
     // grid-wide one loses 104 against 73 ms, on a 1080p batch 330 against 102)
-    const bool useTop = top && NI == 1 && b.topBuf && n_images <= 64;
+    const bool useTop = b.topBuf && n_images <= 64;
     if (useTop) { const int rc = launch_seedsort_top(g, b, n_images, s, nOverride, kthrOverride, depthOverride); if (rc != OLF_OK) return rc; }
     // behind the top levels a few images leave most of the chip idle: Gs workgroups (CUs) per image, each starting from every Gs-th of the ranges the top levels
-    // left (OLF_SS_GROUPS forces 1 .. 8)
-    static const int envG = [] { const char* e = getenv("OLF_SS_GROUPS"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 8 ? v : 0; }();
-    const int Gs = !useTop ? 1 : envG ? envG : n_images <= 16 ? 8 : 4;      // (useTop: at most 64 images; 8 pairs 9.85 against 9.91 ms with 4, 32 pairs 14.0 with 4 against 14.6 with 8)
+    // left
+    const int Gs = !useTop ? 1 : n_images <= 16 ? 8 : 4;      // (useTop: at most 64 images; 8 pairs 9.85 against 9.91 ms with 4, 32 pairs 14.0 with 4 against 14.6 with 8)
     // (the groups' seed counts meet in an atomicMax: the counts start at zero -- launch_lsd_front has cleared them; the debug entry, which comes without a front, has not)
     if (Gs > 1 && nOverride >= 0) OLF_HIP_CHECK(hipMemsetAsync(b.keyCount, 0, (size_t)n_images * 32 * sizeof(int), s));
-    hipLaunchKernelGGL((k_lsd_seedsort_mw<NW, NEM, NI>), dim3(((n_images + NI - 1) / NI) * Gs), dim3(64 * NW), lds, s, b.geom, b.keysA, b.keysB, b.keyCount, b.maxN, b.status,
+    hipLaunchKernelGGL((k_lsd_seedsort_mw<NW, NEM>), dim3(n_images * Gs), dim3(64 * NW), lds, s, b.geom, b.keysA, b.keysB, b.keyCount, b.maxN, b.status,
                        nOverride, kthrOverride, depthOverride, n_images, useTop ? b.topBuf : (int*)nullptr, Gs);
     return OLF_OK;
 }
 
 int launch_lsd_seedsort(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride)
 {
-    // OLF_SS_MW: 0 forces the one-wave kernel, 1 / 2 the 4- / 8-wave variant, 3 / 4 groups of 4 / 8 images (A/B measurements); default: by batch size
-    static const int forced = [] { const char* e = getenv("OLF_SS_MW"); return e ? atoi(e) : -1; }();
+    // modes: 0 the one-wave kernel, 1 / 2 / 5 the 4- / 8- / 2-wave variant; by batch size unless olf_debug_seed_sort_mode forces one
     // up to 256 images: 8 waves per image (101 KB of LDS, one workgroup per CU); up to 640: 4 waves (53 KB, three per CU); up to 1536: 2 waves (30 KB, five per
     // CU: the 1280 images of a 1080p batch go 144 -> 103 ms; KITTI size, ms: 512 images 9.3 / 12.2 with 4 / 2 waves, 768: 17.3 / 13.0, 1024: 18.3 / 13.7 and
     // 23.2 with one, 1536: 27.1 / 24.2 / 24.7); beyond: one wave per image --
-    // alone (mode 0).  Modes 3 / 4 (groups of 4 / 8 images whose waves take over each other's streamed ranges) are opt-in: on 6144 copies of 32 images
-    // the kernel goes 43.5 -> 37.9 ms (groups of 8; 40.2 with 4; equal at 1536 images), on the bench's 512 distinct pairs the front does not move
-    // (71.3 against 71.7 ms) and the step is 278.9 against 276.8 ms -- the launch is bound by issue slots, not by its slowest image.
+    // alone (mode 0).  (Groups of 4 / 8 images whose waves take over each other's streamed ranges were built and removed: on the bench's 512 distinct pairs the
+    // front did not move, 71.3 against 71.7 ms -- the launch is bound by issue slots, not by its slowest image.)
     // One stereo pair through olf_stereo_frames, host to host: 25.6 ms with the one-wave kernel, 16.5 ms with 4 waves, 15.1 ms with 8
-    int mode = b.forceSortMode >= 0 ? b.forceSortMode : forced >= 0 ? forced : (n_images <= 256 ? 2 : n_images <= 640 ? 1 : n_images <= 1536 ? 5 : 0);
+    int mode = b.forceSortMode >= 0 ? b.forceSortMode : (n_images <= 256 ? 2 : n_images <= 640 ? 1 : n_images <= 1536 ? 5 : 0);
     {   // the multi-wave kernels ask for 101 / 53 / 30 KB of dynamic LDS (8 / 4 / 2 waves): on a device whose workgroups cannot have that much (the Makefile
         // accepts other ARCH values than gfx950) take the largest variant that fits instead of failing the launch -- the result does not depend on it
         int dev = 0, maxLds = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&maxLds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) maxLds = 64 * 1024;
-        auto need = [](int m) { return m == 2 ? 104 * 1024 : m == 1 ? 56 * 1024 : m == 5 ? 32 * 1024 : m == 4 ? 104 * 1024 : m == 3 ? 56 * 1024 : 0; };
-        while (need(mode) > maxLds) mode = mode == 2 ? 1 : mode == 1 ? 5 : mode == 4 ? 3 : 0;
+        auto need = [](int m) { return m == 2 ? 104 * 1024 : m == 1 ? 56 * 1024 : m == 5 ? 32 * 1024 : 0; };
+        while (need(mode) > maxLds) mode = mode == 2 ? 1 : mode == 1 ? 5 : 0;
     }
     int rc = OLF_OK;
-    if (mode == 1) rc = launch_seedsort_mw<4, 8, 1>(g, b, n_images, s, nOverride, kthrOverride, depthOverride);
-    else if (mode == 2) rc = launch_seedsort_mw<8, 8, 1>(g, b, n_images, s, nOverride, kthrOverride, depthOverride);
-    else if (mode == 5) rc = launch_seedsort_mw<2, 8, 1>(g, b, n_images, s, nOverride, kthrOverride, depthOverride);
-    else if (mode == 3) rc = launch_seedsort_grp<4>(g, b, n_images, s, nOverride, kthrOverride, depthOverride);
-    else if (mode == 4) rc = launch_seedsort_grp<8>(g, b, n_images, s, nOverride, kthrOverride, depthOverride);
+    if (mode == 1) rc = launch_seedsort_mw<4, 8>(g, b, n_images, s, nOverride, kthrOverride, depthOverride);
+    else if (mode == 2) rc = launch_seedsort_mw<8, 8>(g, b, n_images, s, nOverride, kthrOverride, depthOverride);
+    else if (mode == 5) rc = launch_seedsort_mw<2, 8>(g, b, n_images, s, nOverride, kthrOverride, depthOverride);
     else
         hipLaunchKernelGGL(k_lsd_seedsort, dim3(n_images), dim3(64), 0, s, b.geom, b.keysA, b.keysB, b.keyCount, b.maxN, b.status, nOverride, kthrOverride, depthOverride);
     if (rc != OLF_OK) return rc;

@@ -35,16 +35,6 @@ void set_error(const std::string& s);
 #ifdef __HIPCC__
 // Wave-wide vote.  hip's __ballot() converts the predicate to an int first and compares that with 0 (a v_cndmask + v_cmp_ne pair per vote);
 // the wave64 builtin takes the compare's lane mask as it is.
-// Wave priority experiments (profiles/r4t_wave_priority_ab.txt): -DOLF_GUEST_PRIO=n raises the ORB-stream kernels that run beside the growth agents,
-// -DOLF_AGENT_PRIO=n the agents themselves (s_setprio 0 .. 3; 0 = the hardware default, no instruction emitted)
-#ifndef OLF_GUEST_PRIO
-#define OLF_GUEST_PRIO 0
-#endif
-#ifndef OLF_AGENT_PRIO
-#define OLF_AGENT_PRIO 0
-#endif
-#define OLF_SET_GUEST_PRIO() do { if (OLF_GUEST_PRIO) __builtin_amdgcn_s_setprio(OLF_GUEST_PRIO); } while (0)
-#define OLF_SET_AGENT_PRIO() do { if (OLF_AGENT_PRIO) __builtin_amdgcn_s_setprio(OLF_AGENT_PRIO); } while (0)
 // sum over the 64 lanes of a wave, wave-uniform result: two quad permutes, the two row mirrors (DPP, no LDS), then the four rows' sums through scalar registers
 __device__ __forceinline__ int wave_sum_i32(int v)
 {

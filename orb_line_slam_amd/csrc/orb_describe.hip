@@ -15,10 +15,7 @@ __constant__ __attribute__((aligned(16))) int8_t c_pattern[1024] = {
 #include "orb_pattern_31.inc"
 };
 
-#ifndef OLF_DESC_KPW
-#define OLF_DESC_KPW 1
-#endif
-constexpr int DESC_KPW = OLF_DESC_KPW;      // key point slots per wave: the per-lane constants (16 pattern floats, 8 disc weight words) and the block's set-up are paid once for four
+constexpr int DESC_KPW = 1;      // key point slots per wave: the per-lane constants (16 pattern floats, 8 disc weight words) and the block's set-up are paid once for four
 
 __global__ __launch_bounds__(256) void k_describe(const OrbGeom* __restrict__ gp, const uint8_t* __restrict__ pyr,
                                                   const uint8_t* __restrict__ blur, const uint32_t* __restrict__ lvlKp,
@@ -26,7 +23,6 @@ __global__ __launch_bounds__(256) void k_describe(const OrbGeom* __restrict__ gp
                                                   uint8_t* __restrict__ desc, int* __restrict__ counts, int out_cap,
                                                   int* __restrict__ status)
 {
-    OLF_SET_GUEST_PRIO();
     constexpr int PR = 18, PW = 2 * PR + 1, PDW = 10;      // patch radius (|rotated pattern coordinate| <= round(13 * sqrt 2) = 18), 37 rows of 10 dwords
     __shared__ float4 s_patf[256];                        // the test pattern as floats (x0, y0, x1, y1): one 16-byte LDS read per test, no unpacking
     __shared__ uint32_t s_w0[256], s_w1[256];             // IC_Angle disc as byte weights per (row, dword) slot: 1 / (u + 16) inside, 0 outside
@@ -63,12 +59,8 @@ __global__ __launch_bounds__(256) void k_describe(const OrbGeom* __restrict__ gp
     // cost 24 VGPRs, i.e. two of the eight waves a SIMD can hold, and the kernel lives on its occupancy)
     // XCD-aware numbering: workgroups are dealt round-robin to the 8 XCDs (each with an L2 of its own), so the blocks x, x + 8, x + 16, ... of an image share
     // one; they take CONSECUTIVE groups of key point slots -- neighbours in the octree's output order, whose 37 x 37 patches overlap -- instead of every eighth
-    // (OLF_DESC_XCD=0 in the environment of the build's A/B: -DOLF_DESC_XCD=0)
-#ifndef OLF_DESC_XCD
-#define OLF_DESC_XCD 1
-#endif
     const int nbx = (int)gridDim.x, per = nbx >> 3;
-    const int vblock = (OLF_DESC_XCD && (int)blockIdx.x < per * 8) ? ((int)blockIdx.x & 7) * per + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
+    const int vblock = ((int)blockIdx.x < per * 8) ? ((int)blockIdx.x & 7) * per + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
     const int r6 = lane / PDW, c10 = lane - r6 * PDW;      // staging: lanes 0 .. 59 take six rows of ten dwords per step
     uint32_t* patch = s_patch[wv];
 #pragma unroll 1

@@ -83,15 +83,13 @@ constexpr int FT_INW = (FT_W + 8) / 4;
 // scores its corners into an LDS score tile, suppresses non-maxima there (neighbours in another cell do not count) and appends the
 // survivors to their cell's list.  No dense score map exists in memory; k_cells_sort orders each list and applies the dual threshold.
 // Footprint: 17.4 KB of LDS and <= 64 VGPRs, so that TWO blocks per CU fit beside the 24 resident growth agents (they leave 37 KB of LDS, two wave
-// slots and 128 VGPRs per SIMD): in the fused entry this kernel runs in the agents' shadow (api.cpp, OLF_SCHED).
-// NT threads per block: 256 (128 x 32 tile, 17.4 KB of LDS) or 128 (128 x 16, 9 KB): beside the resident growth agents a CU has eight free wave slots and
-// 40 KB of LDS -- two big blocks or four small ones; the small ones overlap each other's barriers and loads better (OLF_FAST_NT, api.cpp schedule)
+// slots and 128 VGPRs per SIMD): in the fused entry this kernel runs in the agents' shadow (api.cpp, olf_stereo_frames_dev).
+// NT threads per block: 256 (128 x 32 tile, 17.4 KB of LDS) -- the only form launched (a 128-thread form, 128 x 16 tiles, is in profiles/HISTORY_design_rounds1-4.md)
 template <int NT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void k_fast_score(const uint8_t* __restrict__ pyr, int pyrBytes, LevelGeom L, int minTh,
                   uint32_t* __restrict__ cells, int* __restrict__ cellCount, int totalCells, int cellCap)
 {
-    OLF_SET_GUEST_PRIO();
     constexpr int FT_H = NT / 8, FT_EH = FT_H - 2, FT_INH = FT_H + 6;
     __shared__ uint32_t tile[FT_INH * FT_INW];
     __shared__ unsigned short s_cand[FT_W * FT_H];      // A1's survivors, compacted in place to the corners by A2 (s_list)
@@ -277,7 +275,6 @@ void k_fast_score(const uint8_t* __restrict__ pyr, int pyrBytes, LevelGeom L, in
 constexpr int CS_MAX = 1024;    // a cell is < 60 px wide and high (ceil(width / (width / 30))), so at most 30 x 30 strict local maxima
 __global__ __launch_bounds__(64) void k_cells_sort(const OrbGeom* __restrict__ gp, uint32_t* __restrict__ cells, int* __restrict__ cellCount)
 {
-    OLF_SET_GUEST_PRIO();
     __shared__ uint32_t s_k[CS_MAX];
     const OrbGeom& g = *gp;
     const int img = blockIdx.y, cell = blockIdx.x, lane = threadIdx.x;
@@ -365,13 +362,8 @@ int launch_orb_fast(const OrbGeom& g, const OrbDeviceBufs& b, int n_images, hipS
         const LevelGeom& L = g.lv[l];
         const int fw = L.maxBorderX - 3 - (kMinBorder - 2), fh = L.maxBorderY - 3 - (kMinBorder + 3);   // emitted columns start at 14, rows at 19
         if (fw <= 0 || fh <= 0) continue;
-        static const int nt = [] { const char* e = getenv("OLF_FAST_NT"); const int v = e ? atoi(e) : 256; return v == 128 ? 128 : 256; }();
-        if (nt == 128)
-            hipLaunchKernelGGL(k_fast_score<128>, dim3((fw + FT_EW - 1) / FT_EW, (fh + 14 - 1) / 14, n_images), dim3(128), 0, s, b.pyr,
-                               g.pyrBytes, L, g.minTh, b.cells, b.cellCount, g.totalCells, g.cellCap);
-        else
-            hipLaunchKernelGGL(k_fast_score<256>, dim3((fw + FT_EW - 1) / FT_EW, (fh + 30 - 1) / 30, n_images), dim3(256), 0, s, b.pyr,
-                               g.pyrBytes, L, g.minTh, b.cells, b.cellCount, g.totalCells, g.cellCap);
+        hipLaunchKernelGGL(k_fast_score<256>, dim3((fw + FT_EW - 1) / FT_EW, (fh + 30 - 1) / 30, n_images), dim3(256), 0, s, b.pyr,
+                           g.pyrBytes, L, g.minTh, b.cells, b.cellCount, g.totalCells, g.cellCap);
     }
     hipLaunchKernelGGL(k_cells_sort, dim3(g.totalCells, n_images), dim3(64), 0, s, b.geom, b.cells, b.cellCount);
     OLF_HIP_CHECK(hipGetLastError());

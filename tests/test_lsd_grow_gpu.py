@@ -201,11 +201,10 @@ def test_growth_groups_scattered_over_xcds(oracle):
 
 
 def test_cross_xcd_hand_over_under_uneven_load():
-    """tools/stress_mg.py with the groups of every image scattered over XCDs (OLF_LSD_SCATTER=1) while 256-pair batches keep every CU busy."""
+    """tools/stress_mg.py with the groups of every image scattered over XCDs (--scatter) while 256-pair batches keep every CU busy."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, OLF_LSD_SCATTER="1")
-    out = subprocess.run([sys.executable, os.path.join(root, "tools", "stress_mg.py"), "8"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600).stdout.decode()
+    out = subprocess.run([sys.executable, os.path.join(root, "tools", "stress_mg.py"), "8", "--scatter"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600).stdout.decode()
     assert "STRESS OK" in out, out[-1500:]
 
 

@@ -54,10 +54,10 @@ def test_sort_kernel_equals_std_sort_on_random_arrays(oracle, sorter):
         assert np.array_equal(sorter(keys, kthr=kthr), want[(want >> 22) <= kthr]), (n, kthr)
 
 
-def test_sort_kernel_variants_agree(oracle):
-    """one wave per image (the batch kernel), 4 / 8 cooperating waves per image (few images; ranges handed from wave to wave through a stack
-    in LDS, larger blocks) and groups of 4 / 8 images per workgroup whose waves take over each other's ranges give the same list: arrays that
-    keep every wave busy, and the line path on seven KITTI-sized images (a group that is not full, an image without any seed) under each variant"""
+def test_sort_kernel_variants_agree_and_group_modes_rejected(oracle):
+    """one wave per image (the batch kernel) and 2 / 4 / 8 cooperating waves per image (few images; ranges handed from wave to wave through a stack
+    in LDS, larger blocks) give the same list: arrays that keep every wave busy, and the line path on seven KITTI-sized images (an image without
+    any seed among them) under each variant.  Modes 3 and 4 (the image-group kernels, removed) are rejected."""
     ex = ola.Lineextractor(500, 0.025, max_images=7)
     ctx = ex._context(1242, 375, 7)
     rng = np.random.default_rng(8)
@@ -67,7 +67,9 @@ def test_sort_kernel_variants_agree(oracle):
     imgs = imgs[[0, 1, 6, 2, 3, 4, 5]]
     want_lines = [oracle.line_extract(im, p.line) for im in imgs]
     assert len(want_lines[2]["kls"]) == 0 and len(want_lines[0]["kls"]) > 100
-    for mode in (0, 1, 2, 3, 4, 5):
+    for mode in (3, 4):
+        assert _lib.lib().olf_debug_seed_sort_mode(ctx.handle, mode) == _lib.OLF_ERR_INVALID, mode
+    for mode in (0, 1, 2, 5):
         _lib.check(_lib.lib().olf_debug_seed_sort_mode(ctx.handle, mode), "olf_debug_seed_sort_mode")
         for keys in cases:
             out = np.zeros(len(keys), np.uint32); n = C.c_int32()

@@ -1,5 +1,5 @@
 """One pair / few pairs through olf_stereo_frames (host buffers in and out) by workgroups per image of the growth kernel:
-python tools/ab_groups.py [pairs ...]    (OLF_AB_SETTINGS="groups:rob,..." e.g. "1:512,2:512,2:1024,4:1024"; OLF_LSD_WS picks the window)"""
+python tools/ab_groups.py [pairs ...]    (OLF_AB_SETTINGS="groups:rob,..." e.g. "1:512,2:512,2:1024,4:1024")"""
 import sys, time, os, numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import orb_line_slam_amd as ola
@@ -19,4 +19,4 @@ for n in [int(a) for a in sys.argv[1:]] or [1, 8]:
             t = time.perf_counter(); out = fe.frames(imgs); ts.append(time.perf_counter() - t)
         kl = [out.pair(i)["mvKeys_Line"].tobytes() for i in range(n)]
         if ref is None: ref = kl
-        print("ws %s %3d pairs, %d groups, rob %4d: median %.2f ms, min %.2f ms per call; lines identical: %s" % (os.environ.get("OLF_LSD_WS", "10"), n, groups, rob, 1e3 * np.median(ts), 1e3 * min(ts), kl == ref), flush=True)
+        print("%3d pairs, %d groups, rob %4d: median %.2f ms, min %.2f ms per call; lines identical: %s" % (n, groups, rob, 1e3 * np.median(ts), 1e3 * min(ts), kl == ref), flush=True)

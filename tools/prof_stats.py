@@ -3,7 +3,6 @@ import os; sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__fil
 import orb_line_slam_amd as ola
 from orb_line_slam_amd import synth, _lib
 n = 64
-os.environ['OLF_LSD_NW'] = '0'
 imgs = synth.stereo_batch(7000, 16, 1242, 375)
 imgs = np.tile(imgs, (n // 32 + 1, 1, 1))[:n].copy()
 if len(sys.argv) > 1 and sys.argv[1] == "bars":
@@ -17,6 +16,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "wide":     # 1.5 grey levels / pixel wi
     imgs[:] = np.clip(np.abs((x % 170) - 85) * 3, 0, 255).astype(np.uint8)
     kw = dict(lsd_quant=0.3, lsd_scale=2.0)
 ex = ola.Lineextractor(500, 0.025, max_images=n, **kw)
+_lib.check(_lib.lib().olf_debug_lsd_waves(ex._context(imgs.shape[2], imgs.shape[1], n).handle, 0, 0), "olf_debug_lsd_waves")      # the one-wave agent
 k, d, c = ex.extract_batch(imgs)
 out = np.zeros(128, np.int32)
 _lib.lib().olf_debug_status_n(ex._ctx.handle, out.ctypes.data_as(C.c_void_p), 128)

@@ -1,25 +1,35 @@
 """The several-workgroups-per-image growth under UNEVEN load: one thread runs single-pair calls (2 growth groups + 8 sort groups per image, cross-CU agent-scope traffic)
-and compares every result with the first one, while another thread keeps the chip busy with 256-pair batches on a context of its own.  python tools/stress_mg.py [seconds]"""
+and compares every result with the first one, while another thread keeps the chip busy with 256-pair batches on a context of its own.
+python tools/stress_mg.py [seconds] [--scatter]    (--scatter: the groups of every image on different XCDs, olf_debug_lsd_scatter)"""
 import sys, os, time, threading, numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import orb_line_slam_amd as ola
 from orb_line_slam_amd import synth, _lib
-secs = float(sys.argv[1]) if len(sys.argv) > 1 else 20.0
+args = [a for a in sys.argv[1:] if a != "--scatter"]
+scatter = len(args) < len(sys.argv) - 1
+secs = float(args[0]) if args else 20.0
 p = _lib.default_params()
 W, H = 1242, 375
 stop = threading.Event()
 stats = {"pair_calls": 0, "mismatch": 0, "batches": 0}
 
 
+def front_end(max_pairs):
+    fe = ola.StereoFrontEnd(p, W, H, max_pairs=max_pairs)
+    if scatter:
+        _lib.check(_lib.lib().olf_debug_lsd_scatter(fe.ctx.handle, 1), "olf_debug_lsd_scatter")
+    return fe
+
+
 def load():
-    fe = ola.StereoFrontEnd(p, W, H, max_pairs=256)
+    fe = front_end(256)
     imgs = np.tile(synth.stereo_batch(500, 16, W, H), (16, 1, 1))
     while not stop.is_set():
         fe.frames(imgs); stats["batches"] += 1
 
 
 def probe(seed):
-    fe = ola.StereoFrontEnd(p, W, H, max_pairs=1)
+    fe = front_end(1)
     imgs = synth.stereo_batch(seed, 1, W, H)
     ref = None
     while not stop.is_set():
