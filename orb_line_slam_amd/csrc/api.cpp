@@ -37,6 +37,8 @@ struct olf_ctx {
     // line side
     LineHostTables line;
     LineDeviceBufs lb;
+    LsdOverrides lsd_force;            // olf_debug_lsd_* / olf_debug_seed_sort_mode (tests)
+    DeviceLimits limits;               // of `device`
     olf_keyline* d_kls = nullptr;      // [max_images][lineCap]   (host-pointer staging / fused path)
     uint8_t* d_ldesc = nullptr;
     int* d_lcounts = nullptr;
@@ -259,6 +261,8 @@ int olf_ctx_create(const olf_params* p, int width, int height, int max_images, o
     }
     auto fail = [&](int code) { olf_ctx_destroy(c); return code; };
     if (hipGetDevice(&c->device) != hipSuccess) return fail(OLF_ERR_HIP);
+    if (hipDeviceGetAttribute(&c->limits.nCU, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || c->limits.nCU <= 0) c->limits.nCU = 64;
+    if (hipDeviceGetAttribute(&c->limits.maxLds, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device) != hipSuccess) c->limits.maxLds = 64 * 1024;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); return fail(OLF_ERR_HIP); }
     const OrbGeom& g = c->orb.geom;
     const size_t n = (size_t)max_images;
@@ -285,7 +289,7 @@ int olf_ctx_create(const olf_params* p, int width, int height, int max_images, o
     // ---- line side ----
     rc = c->line.build(p->line, width, height, max_images);
     if (rc != OLF_OK) { set_error("olf_ctx_create: LSD parameters not supported"); return fail(rc); }
-    const LineGeom& lg = c->line.geom;
+    LineGeom& lg = c->line.geom;
     // The line stream gets a priority of its own.  The runtime multiplexes streams onto a few hardware queues, and two streams of the SAME priority can land on
     // one queue: the line path and the caller's stream then run back to back (measured: the host-to-host pipeline at 330 ms per 3072-pair batch instead of 220
     // whenever the caller's compute stream and this one aliased, profiles/r4aq_stream_queue_aliasing.txt).  Streams of different priorities never share a queue.
@@ -316,10 +320,10 @@ int olf_ctx_create(const olf_params* p, int width, int height, int max_images, o
     // (batch contexts: the one-wave agent only -- no owner words, a log sized by a bound (host_tables.cpp) and a spill arena of full-size logs for the images that outgrow it)
     A(l.region, n * (size_t)lg.regionStride); l.ownerImages = (batchCtx || lg.wide) ? 0 : (int)std::min<size_t>(n, kMwMaxImages); A(l.owner, (size_t)l.ownerImages * lg.Ps); A(l.links, n * (size_t)l.nChunks);
     // (a full-size log never spills: other contexts get an arena only when olf_debug_lsd_log_cap asks for one)
-    l.spillBlocks = lg.regionStride / 2 >= lg.Ps ? 0 : (int)std::max<size_t>(4, n / 16);      // (one image in 16 may have more than half of its pixels in logged regions)
-    if (l.spillBlocks) A(l.spill, (size_t)l.spillBlocks * 2 * lg.Ps);
-    A(l.spillCtl, 64); A(l.spillOf, n);
-    c->line.geom.logCap = lg.regionStride / 2; c->line.geom.spillBlocks = l.spillBlocks; c->line.geom.spillArena = l.spill; c->line.geom.spillCtl = l.spillCtl; c->line.geom.spillOf = l.spillOf;
+    lg.logCap = lg.regionStride / 2;
+    lg.spillBlocks = lg.regionStride / 2 >= lg.Ps ? 0 : (int)std::max<size_t>(4, n / 16);      // (one image in 16 may have more than half of its pixels in logged regions)
+    if (lg.spillBlocks) A(lg.spillArena, (size_t)lg.spillBlocks * 2 * lg.Ps);
+    A(lg.spillCtl, 64); A(lg.spillOf, n);
     l.mgImages = (int)std::min<size_t>(n, kMgMaxImages); l.mgStride = lsd_grow_mg_stride(lg.maxRegions);
     A(l.mg, (size_t)l.mgImages * l.mgStride);
     A(l.rawLines, n * lg.maxDetect); A(l.rawCount, n); A(l.regCount, n); A(l.growFmt, n); A(l.lbdBlur, n * lg.pitchW * lg.H); A(l.dxdy, n * lg.pitchD * lg.H);
@@ -605,8 +609,8 @@ int olf_debug_lsd_waves(olf_ctx* c, int waves_per_image, int rob_entries)
     if (!c || waves_per_image > 16 || waves_per_image < -1 || (rob_entries != 0 && (!pow2 || rob_entries < 128 || rob_entries > 1024))) {
         set_error("olf_debug_lsd_waves: bad argument"); return OLF_ERR_INVALID;
     }
-    c->lb.forceNW = waves_per_image;
-    c->lb.forceE = rob_entries;
+    c->lsd_force.waves = waves_per_image;
+    c->lsd_force.robEntries = rob_entries;
     return OLF_OK;
 }
 
@@ -614,7 +618,7 @@ int olf_debug_lsd_waves(olf_ctx* c, int waves_per_image, int rob_entries)
 int olf_debug_lsd_groups(olf_ctx* c, int groups)
 {
     if (!c || !(groups == 0 || groups == 1 || groups == 2 || groups == 4)) { set_error("olf_debug_lsd_groups: bad argument"); return OLF_ERR_INVALID; }
-    c->lb.forceG = groups > 0 ? groups : -1;
+    c->lsd_force.groups = groups > 0 ? groups : -1;
     return OLF_OK;
 }
 
@@ -623,16 +627,14 @@ int olf_debug_lsd_log_cap(olf_ctx* c, int entries)
 {
     if (!c || entries < 0) { set_error("olf_debug_lsd_log_cap: bad argument"); return OLF_ERR_INVALID; }
     OLF_TRY(check_device(c, "olf_debug_lsd_log_cap"));
-    if (entries > 0 && !c->lb.spill) {      // a context whose log holds every pixel has no arena of its own
+    LineGeom& g = c->line.geom;
+    if (entries > 0 && !g.spillArena) {      // a context whose log holds every pixel has no arena of its own
         const size_t blocks = std::max<size_t>(2, (size_t)c->max_images - (size_t)c->max_images / 4);      // (tests: three quarters of the images may spill)
         void* q = nullptr;
-        OLF_HIP_CHECK(hipMalloc(&q, blocks * 8 * (size_t)c->line.geom.Ps));
+        OLF_HIP_CHECK(hipMalloc(&q, blocks * 8 * (size_t)g.Ps));
         c->allocs.push_back(q);
-        c->lb.spill = static_cast<uint32_t*>(q); c->lb.spillBlocks = (int)blocks;
+        g.spillArena = static_cast<uint32_t*>(q); g.spillBlocks = (int)blocks;
     }
-    c->lb.logCapOverride = entries;
-    LineGeom& g = c->line.geom;
-    g.spillArena = c->lb.spill; g.spillBlocks = c->lb.spillBlocks;
     g.logCap = entries > 0 ? std::min(entries, g.regionStride / 2) : g.regionStride / 2;
     OLF_HIP_CHECK(hipDeviceSynchronize());
     OLF_HIP_CHECK(hipMemcpy(c->lb.geom, &g, sizeof(LineGeom), hipMemcpyHostToDevice));
@@ -643,7 +645,7 @@ int olf_debug_lsd_log_cap(olf_ctx* c, int entries)
 int olf_debug_lsd_scatter(olf_ctx* c, int on)
 {
     if (!c) { set_error("olf_debug_lsd_scatter: bad argument"); return OLF_ERR_INVALID; }
-    c->lb.scatter = on ? 1 : 0;
+    c->lsd_force.scatter = on ? 1 : 0;
     return OLF_OK;
 }
 
@@ -654,7 +656,7 @@ int olf_debug_seed_sort(olf_ctx* c, const uint32_t* keys, int n, int kthr, int d
 {
     if (!c || !keys || !out || !out_n || n < 0 || n > c->line.geom.Ps || kthr < 0 || kthr > 1023) { set_error("olf_debug_seed_sort: bad argument"); return OLF_ERR_INVALID; }
     OLF_HIP_CHECK(hipMemcpyAsync(c->lb.keysA, keys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(launch_lsd_seedsort(c->line.geom, c->lb, 1, c->stream, n, kthr, depth_limit));
+    OLF_TRY(launch_lsd_seedsort(c->line.geom, c->lb, lsd_plan(c->line.geom, c->lb, c->lsd_force, c->limits, 1), 1, c->stream, n, kthr, depth_limit));
     int cnt = 0;
     OLF_HIP_CHECK(hipMemcpyAsync(&cnt, c->lb.keyCount, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -686,7 +688,7 @@ int olf_debug_seed_sort_wide(olf_ctx* c, const uint64_t* keys, int n, int64_t kt
 int olf_debug_seed_sort_mode(olf_ctx* c, int mode)
 {
     if (!c || mode < -1 || mode == 3 || mode == 4 || mode > 5) { set_error("olf_debug_seed_sort_mode: bad argument"); return OLF_ERR_INVALID; }
-    c->lb.forceSortMode = mode;
+    c->lsd_force.sortMode = mode;
     return OLF_OK;
 }
 
@@ -694,7 +696,7 @@ int olf_debug_seed_sort_mode(olf_ctx* c, int mode)
 int olf_debug_lsd_pool(olf_ctx* c, int pool_chunks)
 {
     if (!c || pool_chunks < 0) { set_error("olf_debug_lsd_pool: bad argument"); return OLF_ERR_INVALID; }
-    c->lb.poolChunks = pool_chunks;
+    c->lsd_force.poolChunks = pool_chunks;
     return OLF_OK;
 }
 
@@ -1036,15 +1038,17 @@ int olf_line_capacity(const olf_ctx* c) { return c ? c->line.geom.outCap : OLF_E
 // the path stops behind the rectangles: the caller enqueues selection + LBD behind the LBD gradient images of the ORB stream
 static int line_extract(olf_ctx* c, const uint8_t* d_images, int n_images, olf_keyline* d_kls, uint8_t* d_ldesc, int32_t* d_lcounts, hipStream_t s, bool fused)
 {
+    const LineGeom& g = c->line.geom;
+    const LsdPlan plan = lsd_plan(g, c->lb, c->lsd_force, c->limits, n_images);
+    hipEvent_t sortEvent = nullptr;
     if (fused) {
-        if (c->line.geom.seedOrder == 1) c->lb.sortEvent = c->ev_sort;
+        if (g.seedOrder == 1) sortEvent = c->ev_sort;
         else OLF_HIP_CHECK(hipEventRecord(c->ev_sort, s));      // (no sort kernel to hide behind: the event is already true)
-        c->lb.skipScaled = true;      // (nothing behind the fused kernel reads the working image)
     }
-    { StageScope t(c, s, ST_LSD_FRONT); const int rc = launch_lsd_front(c->line.geom, c->lb, d_images, c->W, n_images, s); c->lb.sortEvent = nullptr; c->lb.skipScaled = false; OLF_TRY(rc); }
+    { StageScope t(c, s, ST_LSD_FRONT); OLF_TRY(launch_lsd_front(g, c->lb, plan, d_images, c->W, n_images, s, sortEvent, !fused)); }      // (fused: nothing behind reads the working image)
     if (fused) OLF_HIP_CHECK(hipEventRecord(c->ev_front, s));
-    { StageScope t(c, s, ST_LSD_GROW); OLF_TRY(launch_lsd_grow(c->line.geom, c->lb, n_images, s)); }
-    { StageScope t(c, s, ST_LSD_RECT); OLF_TRY(launch_lsd_rect(c->line.geom, c->lb, n_images, s)); }
+    { StageScope t(c, s, ST_LSD_GROW); OLF_TRY(launch_lsd_grow(g, c->lb, plan, n_images, s)); }
+    { StageScope t(c, s, ST_LSD_RECT); OLF_TRY(launch_lsd_rect(g, c->lb, plan, n_images, s)); }
     if (fused) return OLF_OK;
     { StageScope t(c, s, ST_LINE_LBD); OLF_TRY(launch_line_select_lbd(c->line.geom, c->lb, d_images, c->W, n_images, d_kls, d_ldesc, d_lcounts, s)); }
     return OLF_OK;

@@ -93,28 +93,42 @@ struct LineDeviceBufs {
     int* status = nullptr;
     float* angDeg = nullptr;       // [2^22] level-line angle (degrees) of the packed gradient pair (gx:11 | gy:11), image independent
     void* angEnt = nullptr;        // [2^22] AngEnt (lsd_device.hpp): angle in radians, cos / sin as an added pixel, the sums a seed starts with -- 32 B
-    int ownerImages = 0;           // images `owner` is sized for: the multi-wave growth runs on at most 3072 images per call (lsd_grow_waves), larger calls take the one-wave agent, which has no owner words
+    int ownerImages = 0;           // images `owner` is sized for: the multi-wave growth runs on at most 3072 images per call (lsd_plan), larger calls take the one-wave agent, which has no owner words
     uint32_t* owner = nullptr;     // [ownerImages][Ps] region growing: FREE or (seed rank << 10 | ROB slot) of the region that claimed the pixel (lsd_grow.hip)
     int* links = nullptr;          // [n][nChunks] next chunk of a region's pixel list (-1: last)
     int nChunks = 0;               // 32-pixel chunks per image in `region` (ids < 1024: the ROB slots' own chunks, then the pool)
-    bool skipScaled = false;         // fused stereo entry: the enlarged working image is consumed inside k_lsd_upgrad and not written (olf_lsd_debug_scaled needs the stand-alone entry)
-    hipEvent_t sortEvent = nullptr;  // when set, launch_lsd_front records it in front of the seed ordering (the dense, bandwidth-bound part of the front is through)
     int* growFmt = nullptr;        // [n] after the multi-wave growth: 0 chunk chains, -1 given up (pool exhausted), 1 grown again by the one-wave agent (contiguous log)
-    int poolChunks = 0;            // olf_debug_lsd_pool: > 0 caps the chunk pool the multi-wave kernel may use (tests of the fall-back)
     int* topBuf = nullptr;         // [n][SS_TOP_WORDS] job lists / counters / final ranges of the seed sort's grid-wide top levels (lsd_seedsort.hip)
-    int forceSortMode = -1;        // olf_debug_seed_sort_mode: 0 one wave per image, 1 / 2 the 4- / 8-wave kernel of lsd_seedsort.hip; -1: by batch size
-    int forceNW = -1, forceE = 0;  // olf_debug_lsd_waves: waves per image (0: the one-wave agent) and ROB entries of the growth kernel; -1 / 0: automatic
     unsigned char* mg = nullptr;   // [mgImages][mgStride] several workgroups per image (lsd_grow.hip, MG): control words, steal-notice words, the groups' staging lists of logged regions
     size_t mgStride = 0;
     int mgImages = 0;              // images `mg` is sized for (small batches only: the latency path)
-    int forceG = -1;               // olf_debug_lsd_groups: workgroups per image of the multi-wave growth (1, 2, 4); -1: by batch size
-    int scatter = 0;               // olf_debug_lsd_scatter: the groups of an image on consecutive blocks (different XCDs) instead of on one XCD
-    bool chained = false;          // the last growth wrote chunk chains (multi-wave kernel), not the contiguous log of the one-wave agent
-    // the one-wave agent's pixel log is sized by a measured bound in batch contexts (LineGeom::regionStride): an image whose logged regions outgrow it moves on
-    // to a block of the spill arena -- a full-size log (Ps entries); spillCtl[0] counts the blocks handed out in a call, spillOf[img] is the image's block or -1
-    uint32_t* spill = nullptr; int* spillCtl = nullptr; int* spillOf = nullptr; int spillBlocks = 0;
-    int logCapOverride = 0;        // olf_debug_lsd_log_cap: > 0 caps the primary log (entries) -- tests of the spill path
 };
+
+// the olf_debug_lsd_* / olf_debug_seed_sort_mode settings of a context (tests): choices forced on lsd_plan, which alone reads them
+struct LsdOverrides {
+    int sortMode = -1;             // olf_debug_seed_sort_mode: 0 one wave per image, 1 / 2 / 5 the 4- / 8- / 2-wave kernel of lsd_seedsort.hip; -1: by batch size
+    int waves = -1, robEntries = 0;  // olf_debug_lsd_waves: waves per image (0: the one-wave agent) and ROB entries of the growth kernel; -1 / 0: automatic
+    int groups = -1;               // olf_debug_lsd_groups: workgroups per image of the multi-wave growth (1, 2, 4); -1: by batch size
+    int poolChunks = 0;            // olf_debug_lsd_pool: > 0 caps the chunk pool the multi-wave kernel may use (tests of the fall-back)
+    int scatter = 0;               // olf_debug_lsd_scatter: the groups of an image on consecutive blocks (different XCDs) instead of on one XCD
+};
+
+// of the context's device, read when the context is created: compute units, bytes of LDS a workgroup may have
+struct DeviceLimits { int nCU = 64, maxLds = 64 * 1024; };
+
+// what one call of the LSD path launches (lsd_plan, lsd.hip); the launchers of lsd.hip, lsd_seedsort.hip and lsd_grow.hip follow it
+struct LsdPlan {
+    enum Resize { Upgrad, Tiled, Upsample } resize;   // the working image: k_lsd_upgrad (resize and gradient in one), or launch_resize_tiled / k_lsd_upsample + k_lsd_grad
+    enum Sort { Radix, Seed, Wide } sort;             // the seed order: radix sort (lsd_sort.hip), libstdc++'s std::sort order (lsd_seedsort.hip), 64-bit keys (lsd_wide.hip)
+    bool keysOwner, keysAll;       // k_lsd_keys<OWNER, ALLKEYS, LG_CHUNK, sort == Wide>
+    int sortWaves;                 // lsd_seedsort.hip: waves per image, 1 k_lsd_seedsort, 2 / 4 / 8 k_lsd_seedsort_mw
+    bool sortTop; int sortGroups;  // ... multi-wave: the grid-wide top levels first, and sortGroups workgroups per image behind them
+    int growWaves;                 // 0: the one-wave agent grows every image; > 0: waves per image of k_lsd_grow_mw, the agent grows the images it gave up
+    int robEntries, growGroups, poolChunks, scatter;   // k_lsd_grow_mw
+    int agentRefine, agentPF, agentLaunches;   // k_lsd_grow<REFINE, PF>, launched agentLaunches times (a second launch regrows, on the spill arena, the images that outgrew their log)
+    enum Rect { Emit, Mixed, Plain } rect;   // the rectangles: fitted by the agent (k_lsd_emit only), k_lsd_rect_mixed or k_lsd_rect, then k_lsd_emit
+};
+LsdPlan lsd_plan(const LineGeom& g, const LineDeviceBufs& b, const LsdOverrides& o, const DeviceLimits& d, int n_images);
 
 // contexts for more images than this are batch contexts: the one-wave agent only (no owner words), pixel log sized by a bound + spill arena
 constexpr int kBatchCtxImages = 2048;
@@ -125,9 +139,12 @@ struct LineHostTables {
     int build(const olf_line_params& p, int W, int H, int max_images = 2);
 };
 
-int launch_lsd_front(const LineGeom& g, LineDeviceBufs& b, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s);
-int launch_lsd_grow(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s);
-int launch_lsd_rect(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s);
+// sortEvent (when set) is recorded in front of the seed ordering (the dense, bandwidth-bound part of the front is through); writeScaled = false: the fused
+// k_lsd_upgrad does not write the enlarged working image (nothing behind the fused stereo entry reads it; olf_lsd_debug_scaled needs the stand-alone entry)
+int launch_lsd_front(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s,
+                     hipEvent_t sortEvent, bool writeScaled);
+int launch_lsd_grow(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s);
+int launch_lsd_rect(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s);
 int launch_lbd_dense(const LineGeom& g, const LineDeviceBufs& b, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s);
 int launch_line_select_lbd(const LineGeom& g, const LineDeviceBufs& b, const uint8_t* d_in, int in_pitch, int n_images,
                            olf_keyline* d_kls, uint8_t* d_desc, int* d_counts, hipStream_t s, bool denseDone = false);
@@ -141,11 +158,13 @@ int launch_sqrtq_sweep(int count, unsigned long long* d_mismatches, hipStream_t 
 int launch_align_sweep(const LineDeviceBufs& b, unsigned long long seed, int blocks, int per_thread, unsigned long long* d_out, hipStream_t s);
 int lsd_sort_max_chunks(int Ps);
 size_t lsd_grow_mg_stride(int maxRegions);   // bytes per image of LineDeviceBufs::mg
-constexpr int kMwMaxImages = 3072;           // images per call up to which the multi-wave growth is chosen (lsd_grow_waves)
+constexpr int kMwMaxImages = 3072;           // images per call up to which the multi-wave growth is chosen (lsd_plan)
 constexpr int kMgMaxImages = 64;             // images grown by several workgroups each in one call, at most
+int launch_lsd_grow_mw(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s);
 int lsd_seedsort_top_words();      // ints per image of LineDeviceBufs::topBuf
-int launch_lsd_seedsort(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride);
-int launch_lsd_sort_wide(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, long long kthrOverride, int depthOverride, int fullOverride);
+int launch_lsd_sort(const LineGeom& g, const LineDeviceBufs& b, int n_images, hipStream_t s);
+int launch_lsd_seedsort(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride);
+int launch_lsd_sort_wide(const LineGeom& g, const LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, long long kthrOverride, int depthOverride, int fullOverride);
 
 size_t stereo_lines_prep_bytes(int n_images, int cap);
 int launch_stereo_lines(int W, int H, const olf_stereo_params& P, int n_pairs, const olf_keyline* d_kls, const uint8_t* d_desc,

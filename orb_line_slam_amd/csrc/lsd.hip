@@ -931,8 +931,7 @@ constexpr int PEND = 1024;   // hash table of pixels whose USED store may not be
 // seeds and neighbours of later regions.  The agent then writes the segment candidates itself (candAll) and k_lsd_rect is not launched.
 // PF (REFINE = 0 only; bits): 1 = the seed windows as a software pipeline (keys two windows ahead, the windows' gradient words one
 // window ahead; a flush of the pending table first folds the table into the seed masks, so no window is ever gathered twice), 2 = the rows above and
-// below every live seed of a window are requested when the window starts (a region's first 3x3 gather then finds them in the cache instead of in HBM),
-// 4 = the row beyond every candidate of a growth step is requested beside its table entry (the next step's gather).
+// below every live seed of a window are requested when the window starts (a region's first 3x3 gather then finds them in the cache instead of in HBM).
 // 8 = the WINDOW PHASE of a region start (round 6): the 7 x 7 pixels around the seed are gathered ONCE, one lane per pixel (word, pending-table slot, table
 // entry), and the leading FIFO entries -- every entry within Chebyshev distance 2 of the seed, whose 3 x 3 lies inside the window -- are replayed from
 // registers: the candidates of an entry are (3 x 3 mask << lane) & live & aligned, lane order inside the window IS the reference's raster order, an accept
@@ -1019,9 +1018,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
 #else
 #define ST_FLUSH
 #endif
-    constexpr bool PIPE = !REFINE && (PF & 1), PFSEED = !REFINE && (PF & 2), PFCAND = !REFINE && (PF & 4), WIN = !REFINE && (PF & 8), CHEAP = !REFINE && (PF & 16);
+    constexpr bool PIPE = !REFINE && (PF & 1), PFSEED = !REFINE && (PF & 2), WIN = !REFINE && (PF & 8), CHEAP = !REFINE && (PF & 16);
 
-    const float tanLo = g.alignTanLo, tanHi = g.alignTanHi;      // (a tolerance too wide for the folded test -- alignTanLo < 0 -- takes the kernel without the bit: launch_lsd_grow)
+    const float tanLo = g.alignTanLo, tanHi = g.alignTanHi;      // (a tolerance too wide for the folded test -- alignTanLo < 0 -- takes the kernel without the bit: lsd_plan)
     constexpr float kAlDelta = 1e-4f;      // sums shorter than this decide nothing (fastAtan2 of a vanishing vector is dominated by its epsilon)
 // the lanes whose direction DIR is aligned / not aligned with the sums (SX, SY) for certain (garbage in the lanes that hold no table entry)
 #define ALIGN_CHEAP(SX, SY, DIR, SA, SN) do { const float _dot = __fmaf_rn((SY), (DIR).y, __fmul_rn((SX), (DIR).x)); \
@@ -1265,7 +1264,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
             while (i < n) {
                 const int nb = min(8, n - i);
                 const int e = lane >> 3, k = (lane & 7) + ((lane & 7) >= 4 ? 1 : 0);      // 8 FIFO entries x 8 neighbours (k = 4 is the entry's own pixel)
-                const int pfOff = (k / 3 - 1) * Ws;
 #ifdef OLF_STATS
                 ++st_iters; if (n - i >= 14) ++st_deep1; if (n - i >= 21) ++st_deep2; if (n - i > RING) ++st_mem;
 #endif
@@ -1290,14 +1288,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                 double ang, cs, sn;
                 float2 dir;
                 if (CHEAP) asm volatile("" : "=v"(cs), "=v"(sn), "=v"(dir.x), "=v"(dir.y)); else asm volatile("" : "=v"(ang), "=v"(cs), "=v"(sn));
-                uint32_t pfC = 0;
                 if (wave_bit(cm)) {
                     const AngEnt* t = ent + (pw & 0x3fffffu);      // one 32-byte sector per candidate
                     cs = t->cs; sn = t->sn;
                     if (CHEAP) dir = t->seed; else ang = t->ang;
-                    // PFCAND: an accepted candidate is a FIFO entry of the next step, whose gather reaches one row further out (issued behind the table
-                    // loads: vector memory returns in order)
-                    if (PFCAND) { const int ar = a + pfOff; if ((unsigned)ar < (unsigned)g.Ps && pfOff != 0) pfC = grad[ar]; }
                 }
                 // candidates in lane order = the reference's visiting order.  Under a fixed reg_angle every lane tests
                 // its own candidate at once; the first aligned one is accepted (everything before it is rejected under
@@ -1428,7 +1422,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REFINE == 2 
                 // memory operations in flight, so the next iteration's ring read and address arithmetic need not wait for their acknowledgement
                 // (without it the compiler waits at the loop head -- a table load of a lane that was no candidate may still target a live register)
                 __builtin_amdgcn_s_waitcnt(0x0F70);
-                if (PFCAND) asm volatile("" :: "v"(pfC));
                 // the accepted lanes publish their pixel: USED bit, FIFO slot (ring + memory), pending-visibility table
                 if (acc) {
                     LOG_ROOM(n);
@@ -1811,28 +1804,85 @@ __global__ __launch_bounds__(256) void k_lsd_emit(const LineGeom* __restrict__ g
 }
 
 // ---------------------------------------------------------------------------------------------
-int launch_lsd_sort(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s);
-int launch_lsd_seedsort(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride);
-int launch_lsd_sort_wide(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, long long kthrOverride, int depthOverride, int fullOverride);
+// which kernels one call of the LSD path launches, and their shapes: every batch-size threshold of the front, the seed order, the growth and the rectangle
+// stage.  The launchers below, launch_lsd_seedsort and launch_lsd_grow_mw follow the plan.
+LsdPlan lsd_plan(const LineGeom& g, const LineDeviceBufs& b, const LsdOverrides& o, const DeviceLimits& d, int n)
+{
+    LsdPlan p{};
+    p.resize = (g.resizeTiled & 4) && g.seedOrder == 1 ? LsdPlan::Upgrad : g.resizeTiled ? LsdPlan::Tiled : LsdPlan::Upsample;
+    // the seed order: bins high to low; inside a bin raster order (a stable radix sort of the defined pixels' keys) or libstdc++'s std::sort order
+    // over all pixels (convention C.9)
+    p.sort = g.wide ? LsdPlan::Wide : g.seedOrder == 1 ? LsdPlan::Seed : LsdPlan::Radix;
+    p.keysAll = g.seedOrder == 1;
 
-int lsd_grow_waves(int n_images);
-// the growth kernel a batch of n_images takes: 0 the one-wave agent, > 0 waves per image of the multi-wave kernel
-// (lsd_refine = STD runs in the one-wave agent only)
-// (a call of more images than the owner words are allocated for -- kMwMaxImages -- takes the one-wave agent whatever is forced)
-static int lsd_grow_path(const LineGeom& g, const LineDeviceBufs& b, int n_images) { return (g.refine || g.wide || n_images > b.ownerImages) ? 0 : b.forceNW >= 0 ? b.forceNW : lsd_grow_waves(n_images); }
+    // lsd_seedsort.hip (planned whatever the order: olf_debug_seed_sort runs it on any context).  Up to 256 images: 8 waves per image (101 KB of LDS, one
+    // workgroup per CU); up to 640: 4 waves (53 KB, three per CU); up to 1536: 2 waves (30 KB, five per CU: the 1280 images of a 1080p batch go 144 -> 103 ms;
+    // KITTI size, ms: 512 images 9.3 / 12.2 with 4 / 2 waves, 768: 17.3 / 13.0, 1024: 18.3 / 13.7 and 23.2 with one, 1536: 27.1 / 24.2 / 24.7); beyond: one wave
+    // per image -- alone.  (Groups of 4 / 8 images whose waves take over each other's streamed ranges were built and removed: on the bench's 512 distinct pairs
+    // the front did not move, 71.3 against 71.7 ms -- the launch is bound by issue slots, not by its slowest image.)
+    // One stereo pair through olf_stereo_frames, host to host: 25.6 ms with the one-wave kernel, 16.5 ms with 4 waves, 15.1 ms with 8
+    const int m = o.sortMode;      // (olf_debug_seed_sort_mode: 0 / 1 / 2 / 5 = 1 / 4 / 8 / 2 waves)
+    p.sortWaves = m < 0 ? (n <= 256 ? 8 : n <= 640 ? 4 : n <= 1536 ? 2 : 1) : m == 2 ? 8 : m == 1 ? 4 : m == 5 ? 2 : 1;
+    // the multi-wave kernels ask for 101 / 53 / 30 KB of dynamic LDS (8 / 4 / 2 waves): on a device whose workgroups cannot have that much (the Makefile
+    // accepts other ARCH values than gfx950) take the largest variant that fits instead of failing the launch -- the result does not depend on it
+    auto sortLds = [](int w) { return w == 8 ? 104 * 1024 : w == 4 ? 56 * 1024 : w == 2 ? 32 * 1024 : 0; };
+    while (sortLds(p.sortWaves) > d.maxLds) p.sortWaves /= 2;
+    // (few images only: the grids cover every possible tile of every image at every level -- at 128 images the two forms are level, at 1024 the
+    // grid-wide one loses 104 against 73 ms, on a 1080p batch 330 against 102)
+    p.sortTop = p.sortWaves > 1 && b.topBuf && n <= 64;
+    // behind the top levels a few images leave most of the chip idle: sortGroups workgroups (CUs) per image, each starting from every sortGroups-th of the
+    // ranges the top levels left (8 pairs 9.85 against 9.91 ms with 4, 32 pairs 14.0 with 4 against 14.6 with 8)
+    p.sortGroups = !p.sortTop ? 1 : n <= 16 ? 8 : 4;
 
-int launch_lsd_front(const LineGeom& g, LineDeviceBufs& b, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s)
+    // waves per image of the multi-wave growth: as many as keep the chip full (8 waves per SIMD x 1024 SIMDs) without leaving a small batch
+    // to a handful of waves; 0 selects the one-wave agent of round 1
+    const int autoWaves = n <= 512 ? 16 : n <= 1024 ? 8
+                        : n <= 1536 ? 4      // (8 waves x 1280 images no longer fit the 8192 wave slots: the 1080p batch takes 203 ms with 8, 188 with 4; KITTI size: equal)
+                        : n <= 2048 ? 8 : n <= kMwMaxImages ? 4
+                        : 0;      // big batches are throughput bound, and there the one-wave agent does the least work per image
+    // (lsd_refine = STD runs in the one-wave agent only; a call of more images than the owner words are allocated for takes it whatever is forced)
+    p.growWaves = (g.refine || g.wide || n > b.ownerImages) ? 0 : o.waves >= 0 ? o.waves : autoWaves;
+    p.keysOwner = p.growWaves > 0;      // (the key kernel resets the owner words of the multi-wave growth)
+    if (p.growWaves > 0) {
+        const int nw = p.growWaves;
+        p.robEntries = o.robEntries > 0 ? o.robEntries : (nw >= 16 ? 512 : nw >= 8 ? 256 : 128);
+        p.poolChunks = o.poolChunks > 0 ? std::min(o.poolChunks, b.nChunks) : b.nChunks;
+        // workgroups (CUs) per image: the drop-in's online shape -- one stereo pair per call -- leaves 254 CUs idle with one workgroup per image.
+        // (two groups, not four: one pair 8.45 against 8.95 ms, 8 pairs 10.3 against 10.8 -- the further a group runs ahead of the commit order the more of what it grows
+        // is taken from it again by older seeds, profiles/r5a_growth_groups.txt)
+        int G = o.groups > 0 ? o.groups : nw >= 16 && n <= kMgMaxImages ? 2 : 1;
+        // (every group of an image has to be resident -- a group spins on its partners' watermarks -- i.e. one workgroup per CU of the device)
+        while (G > 1 && (!b.mg || n > b.mgImages || n * G > d.nCU || p.poolChunks / G < p.robEntries + 64)) G >>= 1;
+        p.growGroups = G;
+        p.scatter = o.scatter;
+        // an image whose chunk pool or region log ran out under the multi-wave kernel (it re-runs regions, so it needs more of both than the
+        // sequential replay) is grown again by the one-wave agent, whose log cannot overflow
+        p.agentRefine = 0; p.agentPF = 0; p.agentLaunches = 1;
+    } else {
+        p.agentRefine = g.refine;
+        // PF (k_lsd_grow): 1 + 2 + 8 the pipelined seed windows, the seed-row prefetch and the window phase; 16 the cheap alignment test, which a tolerance too
+        // wide for the folded form (ang_th > 80 degrees: alignTanLo < 0) goes without; 32 the 64-bit sort keys' seed list (lsd_wide.hip)
+        p.agentPF = (g.wide ? 32 : 0) | (g.refine ? 0 : g.alignTanLo < 0.f ? 11 : 27);
+        // a log smaller than the image (batch contexts, olf_debug_lsd_log_cap): a second launch grows the images that outgrew theirs again, on blocks of the
+        // spill arena; every other workgroup of it exits at once
+        p.agentLaunches = g.logCap < g.Ps ? 2 : 1;
+    }
+    p.rect = g.refine ? LsdPlan::Emit : p.growWaves > 0 ? LsdPlan::Mixed : LsdPlan::Plain;
+    return p;
+}
+
+int launch_lsd_front(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s,
+                     hipEvent_t sortEvent, bool writeScaled)
 {
     OLF_HIP_CHECK(hipMemsetAsync(b.maxN, 0, (size_t)n_images * 32 * sizeof(int), s));
     OLF_HIP_CHECK(hipMemsetAsync(b.keyCount, 0, (size_t)n_images * 32 * sizeof(int), s));
     { int rc = launch_gauss7_img(d_in, in_pitch, (size_t)in_pitch * g.H, b.lsdBlur, g.pitchW, (size_t)g.pitchW * g.H, g.W, g.H, g, 0, n_images, s);
       if (rc != OLF_OK) return rc; }
-    const bool fused = (g.resizeTiled & 4) && g.seedOrder == 1;
-    if (fused) {
+    if (p.resize == LsdPlan::Upgrad) {
         const int nsx = (g.Ws + 3) / 4;
         hipLaunchKernelGGL(k_lsd_upgrad, dim3((nsx + 63) / 64, (g.Hs + UG_ROWS - 1) / UG_ROWS, n_images), dim3(64), 0, s, b.lsdBlur, b.scaled, b.grad, b.geom, b.rx, b.ry,
-                           b.maxN, nsx, b.skipScaled ? 0 : 1);
-    } else if (g.resizeTiled) {
+                           b.maxN, nsx, writeScaled ? 1 : 0);
+    } else if (p.resize == LsdPlan::Tiled) {
         int rc = launch_resize_tiled(b.lsdBlur, (size_t)g.pitchW * g.H, g.pitchW, g.W, g.H, b.scaled, (size_t)g.pitchS * g.Hs, g.pitchS, g.Ws, g.Hs, b.rx,
                                      b.ry, n_images, s, (g.resizeTiled & 2) != 0);
         if (rc != OLF_OK) return rc;
@@ -1840,126 +1890,67 @@ int launch_lsd_front(const LineGeom& g, LineDeviceBufs& b, const uint8_t* d_in, 
         const int quads = ((g.Ws + 3) >> 2) * g.Hs;
         hipLaunchKernelGGL(k_lsd_upsample, dim3((quads + 255) / 256, n_images), dim3(256), 0, s, b.lsdBlur, b.scaled, b.geom, b.rx, b.ry);
     }
-    if (!fused) hipLaunchKernelGGL(k_lsd_grad, dim3((g.Ps + LG_CHUNK - 1) / LG_CHUNK, n_images), dim3(256), 0, s, b.scaled, b.grad, b.geom, b.maxN, b.chunkCnt);
+    if (p.resize != LsdPlan::Upgrad) hipLaunchKernelGGL(k_lsd_grad, dim3((g.Ps + LG_CHUNK - 1) / LG_CHUNK, n_images), dim3(256), 0, s, b.scaled, b.grad, b.geom, b.maxN, b.chunkCnt);
     {
         // (4096-pixel chunks: 8192 ran the stage alone 62.6 against 63.4 ms per 6144 images, but the two-stream step 231-236 against 232-234 -- two blocks
         // of 61 KB per CU overlap worse with the pyramid beside them than four of 36 KB, profiles/r4y_keys_chunk_ab.txt)
         const int nChunks = (g.Ps + LG_CHUNK - 1) / LG_CHUNK, total = nChunks * n_images;
         const size_t lds = (size_t)(LG_CHUNK + 2 * g.Ws + 2) * sizeof(float);
         if (lds > 60 * 1024) { set_error("LSD image wider than the key kernel's LDS window"); return OLF_ERR_CAPACITY; }
-        const bool ow = lsd_grow_path(g, b, n_images) != 0;
-        if (g.wide) {      // 64-bit keys, both conventions into keysA (lsd_wide.hip sorts them in place and lists the addresses in keysB)
-            if (g.seedOrder == 1) hipLaunchKernelGGL((k_lsd_keys<false, true, LG_CHUNK, true>), dim3(total), dim3(KEYS_THREADS), lds, s, b.grad, b.geom, b.maxN, b.chunkCnt, b.keysA, b.keyCount, b.owner, b.angDeg, nChunks, total);
-            else hipLaunchKernelGGL((k_lsd_keys<false, false, LG_CHUNK, true>), dim3(total), dim3(KEYS_THREADS), lds, s, b.grad, b.geom, b.maxN, b.chunkCnt, b.keysA, b.keyCount, b.owner, b.angDeg, nChunks, total);
-            OLF_HIP_CHECK(hipGetLastError());
-            if (b.sortEvent) OLF_HIP_CHECK(hipEventRecord(b.sortEvent, s));
-            return launch_lsd_sort_wide(g, b, n_images, s, -1, -1, -1, -1);
-        }
-#define KEYS_LAUNCH(OW, AK, KBUF) hipLaunchKernelGGL((k_lsd_keys<OW, AK, LG_CHUNK>), dim3(total), dim3(KEYS_THREADS), lds, s, b.grad, b.geom, b.maxN, b.chunkCnt, KBUF, b.keyCount, b.owner, b.angDeg, nChunks, total)
-        if (g.seedOrder == 1) { if (ow) KEYS_LAUNCH(true, true, b.keysA); else KEYS_LAUNCH(false, true, b.keysA); }
-        else { if (ow) KEYS_LAUNCH(true, false, b.keysB); else KEYS_LAUNCH(false, false, b.keysB); }
-#undef KEYS_LAUNCH
+        // the radix sort reads its keys from keysB; the other orders sort keysA (64-bit keys: lsd_wide.hip sorts them in place and lists the addresses in keysB)
+        const auto keys = p.sort == LsdPlan::Wide ? (p.keysAll ? k_lsd_keys<false, true, LG_CHUNK, true> : k_lsd_keys<false, false, LG_CHUNK, true>)
+                        : p.keysAll ? (p.keysOwner ? k_lsd_keys<true, true, LG_CHUNK> : k_lsd_keys<false, true, LG_CHUNK>)
+                        : p.keysOwner ? k_lsd_keys<true, false, LG_CHUNK> : k_lsd_keys<false, false, LG_CHUNK>;
+        hipLaunchKernelGGL(keys, dim3(total), dim3(KEYS_THREADS), lds, s, b.grad, b.geom, b.maxN, b.chunkCnt, p.sort == LsdPlan::Radix ? b.keysB : b.keysA, b.keyCount,
+                           b.owner, b.angDeg, nChunks, total);
     }
     OLF_HIP_CHECK(hipGetLastError());
-    if (b.sortEvent) OLF_HIP_CHECK(hipEventRecord(b.sortEvent, s));
-    // the seed order: bins high to low; inside a bin raster order (a stable radix sort of the defined pixels' keys) or libstdc++'s std::sort order
-    // over all pixels (convention C.9)
-    { int rc = g.seedOrder == 1 ? launch_lsd_seedsort(g, b, n_images, s, -1, -1, -1) : launch_lsd_sort(g, b, n_images, s); if (rc != OLF_OK) return rc; }
-    return OLF_OK;
+    if (sortEvent) OLF_HIP_CHECK(hipEventRecord(sortEvent, s));
+    if (p.sort == LsdPlan::Wide) return launch_lsd_sort_wide(g, b, n_images, s, -1, -1, -1, -1);
+    if (p.sort == LsdPlan::Seed) return launch_lsd_seedsort(g, b, p, n_images, s, -1, -1, -1);
+    return launch_lsd_sort(g, b, n_images, s);
 }
 
-int launch_lsd_grow_mw(const LineGeom& g, LineDeviceBufs& b, int n_images, int nw, int E, int G, hipStream_t s);
-
-// workgroups (CUs) per image of the multi-wave growth: the drop-in's online shape -- one stereo pair per call -- leaves 254 CUs idle with one workgroup per image
-int lsd_grow_groups(int n_images, int nw)
+int launch_lsd_grow(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s)
 {
-    if (nw < 16) return 1;
-    // (two groups, not four: one pair 8.45 against 8.95 ms, 8 pairs 10.3 against 10.8 -- the further a group runs ahead of the commit order the more of what it grows
-    // is taken from it again by older seeds, profiles/r5a_growth_groups.txt)
-    if (n_images <= kMgMaxImages) return 2;
-    return 1;
-}
-
-// waves per image of the multi-wave growth: as many as keep the chip full (8 waves per SIMD x 1024 SIMDs) without leaving a small batch
-// to a handful of waves; 0 selects the one-wave agent of round 1
-int lsd_grow_waves(int n_images)
-{
-    if (n_images <= 512) return 16;
-    if (n_images <= 1024) return 8;
-    if (n_images <= 1536) return 4;      // (8 waves x 1280 images no longer fit the 8192 wave slots: the 1080p batch takes 203 ms with 8, 188 with 4; KITTI size: equal)
-    if (n_images <= 2048) return 8;
-    if (n_images <= kMwMaxImages) return 4;
-    return 0;      // big batches are throughput bound, and there the one-wave agent does the least work per image
-}
-
-int launch_lsd_grow(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s)
-{
-    const int nw = lsd_grow_path(g, b, n_images);
-    if (b.spillCtl) OLF_HIP_CHECK(hipMemsetAsync(b.spillCtl, 0, sizeof(int), s));      // blocks of the spill arena handed out in this call
-    b.chained = nw != 0;
-    if (nw > 0) {
-        const int E = b.forceE > 0 ? b.forceE : (nw >= 16 ? 512 : nw >= 8 ? 256 : 128);
-        int G = b.forceG > 0 ? b.forceG : lsd_grow_groups(n_images, nw);
-        const int pool = b.poolChunks > 0 ? std::min(b.poolChunks, b.nChunks) : b.nChunks;
-        // (every group of an image has to be resident -- a group spins on its partners' watermarks -- i.e. one workgroup per CU of THIS device)
-        static const int nCU = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 64; return n; }();
-        while (G > 1 && (!b.mg || n_images > b.mgImages || n_images * G > nCU || pool / G < E + 64)) G >>= 1;
-        const int rc = launch_lsd_grow_mw(g, b, n_images, nw, E, G, s);
-        if (rc != OLF_OK) return rc;
-        // an image whose chunk pool or region log ran out under the multi-wave kernel (it re-runs regions, so it needs more of both than the
-        // sequential replay) is grown again by the one-wave agent, whose log cannot overflow; every other workgroup of this launch exits at once
-        hipLaunchKernelGGL((k_lsd_grow<0, 0>), dim3(n_images), dim3(64), 0, s, b.geom, b.grad, b.keysB, b.keyCount, b.region,
-                           reinterpret_cast<RegionRec*>(b.keysA), b.regCount, b.status, reinterpret_cast<const AngEnt*>(b.angEnt), b.growFmt, (SegCand*)nullptr, 0);
-        OLF_HIP_CHECK(hipGetLastError());
-        return OLF_OK;
-    }
-    // a log smaller than the image (batch contexts, olf_debug_lsd_log_cap): a second launch grows the images that outgrew theirs again, on blocks of the spill
-    // arena; every other workgroup of it exits at once
-    for (int RETRY = 0; RETRY < (g.logCap < g.Ps ? 2 : 1); ++RETRY) {
-    // (lsd_refine: the candidates go to keysA -- keysB still holds the seed list the agent is reading; launch_lsd_rect emits from there)
-    if (g.wide) {
-        // (64-bit sort keys: the agent reading 32-bit addresses, the capacity path of lsd_wide.hip; lsd_ang_th > 80 degrees takes it without the cheap alignment test)
-#define GROWW(RF) hipLaunchKernelGGL((k_lsd_grow<RF, (RF ? 32 : 32 | 27)>), dim3(n_images), dim3(64), 0, s, b.geom, b.grad, b.keysB, b.keyCount, b.region, \
-                           RF ? (RegionRec*)nullptr : reinterpret_cast<RegionRec*>(b.keysA), b.regCount, b.status, reinterpret_cast<const AngEnt*>(b.angEnt), (int*)nullptr, \
-                           RF ? reinterpret_cast<SegCand*>(b.keysA) : (SegCand*)nullptr, RETRY)
-        if (g.refine >= 2) GROWW(2); else if (g.refine) GROWW(1); else if (g.alignTanLo < 0.f) hipLaunchKernelGGL((k_lsd_grow<0, 32 | 11>), dim3(n_images), dim3(64), 0, s, b.geom, b.grad, b.keysB, b.keyCount, b.region,
-                           reinterpret_cast<RegionRec*>(b.keysA), b.regCount, b.status, reinterpret_cast<const AngEnt*>(b.angEnt), (int*)nullptr, (SegCand*)nullptr, RETRY); else GROWW(0);
-#undef GROWW
-    } else if (g.refine >= 2)
-        hipLaunchKernelGGL((k_lsd_grow<2, 0>), dim3(n_images), dim3(64), 0, s, b.geom, b.grad, b.keysB, b.keyCount, b.region,
-                           (RegionRec*)nullptr, b.regCount, b.status, reinterpret_cast<const AngEnt*>(b.angEnt), (int*)nullptr, reinterpret_cast<SegCand*>(b.keysA), RETRY);
-    else if (g.refine)
-        hipLaunchKernelGGL((k_lsd_grow<1, 0>), dim3(n_images), dim3(64), 0, s, b.geom, b.grad, b.keysB, b.keyCount, b.region,
-                           (RegionRec*)nullptr, b.regCount, b.status, reinterpret_cast<const AngEnt*>(b.angEnt), (int*)nullptr, reinterpret_cast<SegCand*>(b.keysA), RETRY);
-    else {
-#define GROW0(PFV) hipLaunchKernelGGL((k_lsd_grow<0, PFV>), dim3(n_images), dim3(64), 0, s, b.geom, b.grad, b.keysB, b.keyCount, b.region, \
-                           reinterpret_cast<RegionRec*>(b.keysA), b.regCount, b.status, reinterpret_cast<const AngEnt*>(b.angEnt), (int*)nullptr, (SegCand*)nullptr, RETRY)
-        if (g.alignTanLo < 0.f) GROW0(11); else GROW0(27);      // (ang_th > 80 degrees: no cheap alignment test)
-#undef GROW0
-    }
-    }
+    // the instantiations of the one-wave agent lsd_plan chooses among (in the order they are laid out in the code object)
+    static const struct { int refine, pf; decltype(&k_lsd_grow<0, 0>) kernel; } kAgents[] = {
+        {0, 0, k_lsd_grow<0, 0>}, {2, 32, k_lsd_grow<2, 32>}, {1, 32, k_lsd_grow<1, 32>}, {0, 32 | 11, k_lsd_grow<0, 32 | 11>}, {0, 32 | 27, k_lsd_grow<0, 32 | 27>},
+        {2, 0, k_lsd_grow<2, 0>}, {1, 0, k_lsd_grow<1, 0>}, {0, 11, k_lsd_grow<0, 11>}, {0, 27, k_lsd_grow<0, 27>}};
+    decltype(&k_lsd_grow<0, 0>) agent = nullptr;
+    for (const auto& a : kAgents) if (a.refine == p.agentRefine && a.pf == p.agentPF) agent = a.kernel;
+    if (!agent) { set_error("launch_lsd_grow: no such k_lsd_grow instantiation"); return OLF_ERR_INVALID; }
+    if (g.spillCtl) OLF_HIP_CHECK(hipMemsetAsync(g.spillCtl, 0, sizeof(int), s));      // blocks of the spill arena handed out in this call
+    if (p.growWaves > 0) { const int rc = launch_lsd_grow_mw(g, b, p, n_images, s); if (rc != OLF_OK) return rc; }
+    // growFmt: behind the multi-wave kernel, every image it finished exits the agent at once.  (lsd_refine: the candidates go to keysA -- keysB still holds
+    // the seed list the agent is reading; launch_lsd_rect emits from there)
+    for (int retry = 0; retry < p.agentLaunches; ++retry)
+        hipLaunchKernelGGL(agent, dim3(n_images), dim3(64), 0, s, b.geom, b.grad, b.keysB, b.keyCount, b.region,
+                           p.agentRefine ? (RegionRec*)nullptr : reinterpret_cast<RegionRec*>(b.keysA), b.regCount, b.status, reinterpret_cast<const AngEnt*>(b.angEnt),
+                           p.growWaves > 0 ? b.growFmt : (int*)nullptr, p.agentRefine ? reinterpret_cast<SegCand*>(b.keysA) : (SegCand*)nullptr, retry);
     OLF_HIP_CHECK(hipGetLastError());
     return OLF_OK;
 }
 
-int launch_lsd_rect(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s)
+int launch_lsd_rect(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s)
 {
-    if (g.refine) {      // the agent has fitted the rectangles itself (candidates in keysA)
+    if (p.rect == LsdPlan::Emit) {      // the agent has fitted the rectangles itself (candidates in keysA)
         hipLaunchKernelGGL(k_lsd_emit, dim3(n_images), dim3(256), 0, s, b.geom, reinterpret_cast<const SegCand*>(b.keysA), b.regCount, b.rawLines,
                            b.rawCount, b.status);
         OLF_HIP_CHECK(hipGetLastError());
         return OLF_OK;
     }
     // the sorted keys (keysB) are dead once the agents are done: the 24-byte segment candidates live there
-    if (b.chained)
+    const int* spillOf = g.logCap < g.Ps ? g.spillOf : nullptr;
+    if (p.rect == LsdPlan::Mixed)      // chunk chains of the multi-wave kernel, or the contiguous log of the agent behind it (growFmt)
         hipLaunchKernelGGL(k_lsd_rect_mixed, dim3((g.rectGrid + 255) / 256, n_images), dim3(256), 0, s, b.geom, b.grad, b.region,
-                           reinterpret_cast<const RegionRec*>(b.keysA), b.regCount, reinterpret_cast<SegCand*>(b.keysB), b.links, b.nChunks, b.growFmt, g.logCap < g.Ps ? b.spillOf : (const int*)nullptr, b.spill);
+                           reinterpret_cast<const RegionRec*>(b.keysA), b.regCount, reinterpret_cast<SegCand*>(b.keysB), b.links, b.nChunks, b.growFmt, spillOf, g.spillArena);
     else
         // (one thread per region in index order.  Dealing an image's regions out by size -- one block per image, (size, index) keys sorted in LDS, so that a wave's 64
         // lists have similar lengths -- was built and measured: 10.2 against 8.1 ms per 6144 images (profiles/r4ac_rect_sorted_ab.txt); the fit waits for its list
         // loads, not for the longest list of its wave)
         hipLaunchKernelGGL(k_lsd_rect<false>, dim3((g.rectGrid + 255) / 256, n_images), dim3(256), 0, s, b.geom, b.grad, b.region,
-                           reinterpret_cast<const RegionRec*>(b.keysA), b.regCount, reinterpret_cast<SegCand*>(b.keysB), b.links, b.nChunks, g.logCap < g.Ps ? b.spillOf : (const int*)nullptr, b.spill);
+                           reinterpret_cast<const RegionRec*>(b.keysA), b.regCount, reinterpret_cast<SegCand*>(b.keysB), b.links, b.nChunks, spillOf, g.spillArena);
     hipLaunchKernelGGL(k_lsd_emit, dim3(n_images), dim3(256), 0, s, b.geom, reinterpret_cast<const SegCand*>(b.keysB), b.regCount, b.rawLines,
                        b.rawCount, b.status);
     OLF_HIP_CHECK(hipGetLastError());

@@ -1011,8 +1011,9 @@ __global__ __launch_bounds__(256) void k_mg_merge(const LineGeom* __restrict__ g
     if (threadIdx.x == 0) { regCount[img] = total; growFmt[img] = 0; }
 }
 
-int launch_lsd_grow_mw(const LineGeom& g, LineDeviceBufs& b, int n_images, int nw, int E, int G, hipStream_t s)
+int launch_lsd_grow_mw(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s)
 {
+    const int nw = p.growWaves, E = p.robEntries, G = p.growGroups, poolLimit = p.poolChunks;
     const size_t lds = lsd_grow_mw_lds_bytes(nw, E);
     // up to 46 KB (16 waves, 512 entries) fits the 64 KB a launch may ask for without a function attribute; a 1024-entry buffer (70 KB) needs the attribute,
     // which is a property of the function ON THE CURRENT DEVICE: set per device, remembered per device
@@ -1027,7 +1028,6 @@ int launch_lsd_grow_mw(const LineGeom& g, LineDeviceBufs& b, int n_images, int n
             done[dev] = true;
         }
     }
-    const int poolLimit = b.poolChunks > 0 ? std::min(b.poolChunks, b.nChunks) : b.nChunks;
     // entries in the buffer below which any wave tops it up before it looks for a region
     const int ahead = E / 2;
     // log2 of the seed window the groups are dealt
@@ -1039,7 +1039,7 @@ int launch_lsd_grow_mw(const LineGeom& g, LineDeviceBufs& b, int n_images, int n
         const int blocks = ((n_images + 7) / 8) * 8 * G;
         hipLaunchKernelGGL(k_lsd_grow_mw<true>, dim3(blocks), dim3(64 * nw), lds, s, b.geom, b.grad, b.owner, b.keysB, b.keyCount, b.region, b.links,
                            reinterpret_cast<RegionRec*>(b.keysA), b.regCount, b.status, b.angDeg, reinterpret_cast<const AngEnt*>(b.angEnt), E,
-                           b.nChunks, poolLimit, b.growFmt, b.mg, b.mgStride, G, n_images, wsBits, ahead, b.scatter);
+                           b.nChunks, poolLimit, b.growFmt, b.mg, b.mgStride, G, n_images, wsBits, ahead, p.scatter);
         hipLaunchKernelGGL(k_mg_merge, dim3(n_images), dim3(256), 0, s, b.geom, b.mg, b.mgStride, G, reinterpret_cast<RegionRec*>(b.keysA), b.regCount, b.growFmt);
     } else
         hipLaunchKernelGGL(k_lsd_grow_mw<false>, dim3(n_images), dim3(64 * nw), lds, s, b.geom, b.grad, b.owner, b.keysB, b.keyCount, b.region, b.links,

@@ -919,7 +919,7 @@ __global__ __launch_bounds__(SS_TOP_JOBS) void k_top_next(int* __restrict__ topA
 
 int lsd_seedsort_top_words() { return SS_TOP_WORDS; }
 
-static int launch_seedsort_top(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride)
+static int launch_seedsort_top(const LineGeom& g, const LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride)
 {
     const int n = nOverride >= 0 ? nOverride : (g.Ws - 1) * (g.Hs - 1);
     const int maxTiles = n / 64 + SS_TOP_JOBS + 2, half = maxTiles + SS_TOP_JOBS + 2;
@@ -945,7 +945,7 @@ static int launch_seedsort_top(const LineGeom& g, LineDeviceBufs& b, int n_image
 }
 
 template <int NW, int NEM>
-static int launch_seedsort_mw(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride)
+static int launch_seedsort_mw(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride)
 {
     // per wave: range buffer + staging area; then lock / counters, the shared stack's five arrays (256 entries) and the top-level list's flag
     const size_t lds = ((size_t)NW * (4 * 64 * NEM + 2 * 64 * NEM) + 4 + 5 * 256 + 1) * 4;
@@ -958,41 +958,20 @@ static int launch_seedsort_mw(const LineGeom& g, LineDeviceBufs& b, int n_images
             if (dev >= 0 && dev < 64) done[dev] = true;
         }
     }
-    // (few images only: the grids cover every possible tile of every image at every level -- at 128 images the two forms are level, at 1024 the
-    // grid-wide one loses 104 against 73 ms, on a 1080p batch 330 against 102)
-    const bool useTop = b.topBuf && n_images <= 64;
-    if (useTop) { const int rc = launch_seedsort_top(g, b, n_images, s, nOverride, kthrOverride, depthOverride); if (rc != OLF_OK) return rc; }
-    // behind the top levels a few images leave most of the chip idle: Gs workgroups (CUs) per image, each starting from every Gs-th of the ranges the top levels
-    // left
-    const int Gs = !useTop ? 1 : n_images <= 16 ? 8 : 4;      // (useTop: at most 64 images; 8 pairs 9.85 against 9.91 ms with 4, 32 pairs 14.0 with 4 against 14.6 with 8)
+    if (p.sortTop) { const int rc = launch_seedsort_top(g, b, n_images, s, nOverride, kthrOverride, depthOverride); if (rc != OLF_OK) return rc; }
     // (the groups' seed counts meet in an atomicMax: the counts start at zero -- launch_lsd_front has cleared them; the debug entry, which comes without a front, has not)
-    if (Gs > 1 && nOverride >= 0) OLF_HIP_CHECK(hipMemsetAsync(b.keyCount, 0, (size_t)n_images * 32 * sizeof(int), s));
-    hipLaunchKernelGGL((k_lsd_seedsort_mw<NW, NEM>), dim3(n_images * Gs), dim3(64 * NW), lds, s, b.geom, b.keysA, b.keysB, b.keyCount, b.maxN, b.status,
-                       nOverride, kthrOverride, depthOverride, n_images, useTop ? b.topBuf : (int*)nullptr, Gs);
+    if (p.sortGroups > 1 && nOverride >= 0) OLF_HIP_CHECK(hipMemsetAsync(b.keyCount, 0, (size_t)n_images * 32 * sizeof(int), s));
+    hipLaunchKernelGGL((k_lsd_seedsort_mw<NW, NEM>), dim3(n_images * p.sortGroups), dim3(64 * NW), lds, s, b.geom, b.keysA, b.keysB, b.keyCount, b.maxN, b.status,
+                       nOverride, kthrOverride, depthOverride, n_images, p.sortTop ? b.topBuf : (int*)nullptr, p.sortGroups);
     return OLF_OK;
 }
 
-int launch_lsd_seedsort(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride)
+int launch_lsd_seedsort(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride)
 {
-    // modes: 0 the one-wave kernel, 1 / 2 / 5 the 4- / 8- / 2-wave variant; by batch size unless olf_debug_seed_sort_mode forces one
-    // up to 256 images: 8 waves per image (101 KB of LDS, one workgroup per CU); up to 640: 4 waves (53 KB, three per CU); up to 1536: 2 waves (30 KB, five per
-    // CU: the 1280 images of a 1080p batch go 144 -> 103 ms; KITTI size, ms: 512 images 9.3 / 12.2 with 4 / 2 waves, 768: 17.3 / 13.0, 1024: 18.3 / 13.7 and
-    // 23.2 with one, 1536: 27.1 / 24.2 / 24.7); beyond: one wave per image --
-    // alone (mode 0).  (Groups of 4 / 8 images whose waves take over each other's streamed ranges were built and removed: on the bench's 512 distinct pairs the
-    // front did not move, 71.3 against 71.7 ms -- the launch is bound by issue slots, not by its slowest image.)
-    // One stereo pair through olf_stereo_frames, host to host: 25.6 ms with the one-wave kernel, 16.5 ms with 4 waves, 15.1 ms with 8
-    int mode = b.forceSortMode >= 0 ? b.forceSortMode : (n_images <= 256 ? 2 : n_images <= 640 ? 1 : n_images <= 1536 ? 5 : 0);
-    {   // the multi-wave kernels ask for 101 / 53 / 30 KB of dynamic LDS (8 / 4 / 2 waves): on a device whose workgroups cannot have that much (the Makefile
-        // accepts other ARCH values than gfx950) take the largest variant that fits instead of failing the launch -- the result does not depend on it
-        int dev = 0, maxLds = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&maxLds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) maxLds = 64 * 1024;
-        auto need = [](int m) { return m == 2 ? 104 * 1024 : m == 1 ? 56 * 1024 : m == 5 ? 32 * 1024 : 0; };
-        while (need(mode) > maxLds) mode = mode == 2 ? 1 : mode == 1 ? 5 : 0;
-    }
     int rc = OLF_OK;
-    if (mode == 1) rc = launch_seedsort_mw<4, 8>(g, b, n_images, s, nOverride, kthrOverride, depthOverride);
-    else if (mode == 2) rc = launch_seedsort_mw<8, 8>(g, b, n_images, s, nOverride, kthrOverride, depthOverride);
-    else if (mode == 5) rc = launch_seedsort_mw<2, 8>(g, b, n_images, s, nOverride, kthrOverride, depthOverride);
+    if (p.sortWaves == 4) rc = launch_seedsort_mw<4, 8>(g, b, p, n_images, s, nOverride, kthrOverride, depthOverride);
+    else if (p.sortWaves == 8) rc = launch_seedsort_mw<8, 8>(g, b, p, n_images, s, nOverride, kthrOverride, depthOverride);
+    else if (p.sortWaves == 2) rc = launch_seedsort_mw<2, 8>(g, b, p, n_images, s, nOverride, kthrOverride, depthOverride);
     else
         hipLaunchKernelGGL(k_lsd_seedsort, dim3(n_images), dim3(64), 0, s, b.geom, b.keysA, b.keysB, b.keyCount, b.maxN, b.status, nOverride, kthrOverride, depthOverride);
     if (rc != OLF_OK) return rc;

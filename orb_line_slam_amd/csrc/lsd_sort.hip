@@ -160,7 +160,7 @@ __global__ __launch_bounds__(SCATTER_THREADS) void k_radix_scatter(const uint32_
 int lsd_sort_max_chunks(int Ps) { return (Ps + SORT_CHUNK - 1) / SORT_CHUNK; }
 
 // keysB (raster order, from k_lsd_keys) -> keysA (by the low digit) -> keysB (by the high digit): the order the growth kernels read
-int launch_lsd_sort(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s)
+int launch_lsd_sort(const LineGeom& g, const LineDeviceBufs& b, int n_images, hipStream_t s)
 {
     const int mc = lsd_sort_max_chunks(g.Ps);
     hipLaunchKernelGGL(k_radix_hist<22>, dim3(mc, n_images), dim3(256), 0, s, b.keysB, b.keyCount, g.Ps, b.sortHist, mc);

@@ -322,7 +322,7 @@ __global__ __launch_bounds__(WS_NT) void k_wide_sort(const LineGeom* __restrict_
     if (tid == 0) keyCount[img * 32] = cnt;
 }
 
-int launch_lsd_sort_wide(const LineGeom& g, LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, long long kthrOverride, int depthOverride, int fullOverride)
+int launch_lsd_sort_wide(const LineGeom& g, const LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, long long kthrOverride, int depthOverride, int fullOverride)
 {
     const bool full = fullOverride >= 0 ? fullOverride != 0 : g.seedOrder == 0;
     if (full)
