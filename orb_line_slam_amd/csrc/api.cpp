@@ -7,7 +7,7 @@
 #include <map>
 #include <mutex>
 #include <cstring>
-#include <mutex>
+#include <cstddef>
 
 namespace olf {
 static thread_local std::string g_err;
@@ -15,6 +15,30 @@ void set_error(const std::string& s) { g_err = s; }
 }  // namespace olf
 
 using namespace olf;
+
+// ---- the layout of olf_frame_buffers (include/orbline.h), in the order of its fields: whose rows an array has (every image's or every pair's), how many
+// per image or pair (the ORB capacity, the line capacity, or one for the two count arrays) and the bytes of a row
+enum { FB_KPS, FB_DESC, FB_COUNTS, FB_URIGHT, FB_DEPTH, FB_KLS, FB_LDESC, FB_LCOUNTS, FB_LMATCHES12, FB_LDISP, FB_LLE, FB_FIELDS };
+enum FieldCap { CAP_ONE, CAP_ORB, CAP_LINE };
+struct FrameField { const char* name; size_t offset; bool perPair; FieldCap cap; size_t rowBytes; };
+#define FIELD(f, perPair, cap, rowBytes) {#f, offsetof(olf_frame_buffers, f), perPair, cap, rowBytes}
+constexpr FrameField kFrameFields[] = {
+    FIELD(kps, false, CAP_ORB, sizeof(olf_keypoint)),   FIELD(desc, false, CAP_ORB, OLF_DESC_BYTES),    FIELD(counts, false, CAP_ONE, sizeof(int32_t)),
+    FIELD(uright, true, CAP_ORB, sizeof(float)),        FIELD(depth, true, CAP_ORB, sizeof(float)),
+    FIELD(kls, false, CAP_LINE, sizeof(olf_keyline)),   FIELD(ldesc, false, CAP_LINE, OLF_DESC_BYTES),  FIELD(lcounts, false, CAP_ONE, sizeof(int32_t)),
+    FIELD(lmatches12, true, CAP_LINE, sizeof(int32_t)), FIELD(ldisp, true, CAP_LINE, 2 * sizeof(float)), FIELD(lle, true, CAP_LINE, 3 * sizeof(double))};
+#undef FIELD
+// (the struct is eleven object pointers and nothing else: a field is read and written through its offset as a void*)
+constexpr bool frame_fields_in_order()
+{
+    for (size_t k = 0; k < sizeof(kFrameFields) / sizeof(kFrameFields[0]); ++k) if (kFrameFields[k].offset != k * sizeof(void*)) return false;
+    return true;
+}
+static_assert(sizeof(kFrameFields) / sizeof(kFrameFields[0]) == FB_FIELDS && sizeof(olf_frame_buffers) == FB_FIELDS * sizeof(void*) && frame_fields_in_order(),
+              "kFrameFields has one entry per field of olf_frame_buffers, in the struct's order");
+
+static void* fb_field(const olf_frame_buffers& f, int k) { void* p; std::memcpy(&p, reinterpret_cast<const char*>(&f) + kFrameFields[k].offset, sizeof(p)); return p; }
+static void fb_set_field(olf_frame_buffers& f, int k, void* p) { std::memcpy(reinterpret_cast<char*>(&f) + kFrameFields[k].offset, &p, sizeof(p)); }
 
 struct olf_ctx {
     olf_params params;
@@ -25,13 +49,8 @@ struct olf_ctx {
     OrbDeviceBufs ob;
     // staging for the host-pointer entry points
     uint8_t* d_images = nullptr;
-    olf_keypoint* d_kps = nullptr;
-    uint8_t* d_desc = nullptr;
-    int* d_counts = nullptr;
-    int last_n_images = 0;
-    float* d_uright = nullptr;     // [max_pairs][outCap]
-    float* d_depth = nullptr;
-    int* d_sad = nullptr;
+    olf_frame_buffers d_out = {};  // the eleven output arrays, sized for max_images (kFrameFields)
+    int* d_sad = nullptr;          // [max_pairs][outCap]
     int* d_bestkey = nullptr;
     unsigned* d_rowperm = nullptr; // [max_images][outCap] key point lists ordered by row (stereo candidate search)
     // line side
@@ -39,15 +58,9 @@ struct olf_ctx {
     LineDeviceBufs lb;
     LsdOverrides lsd_force;            // olf_debug_lsd_* / olf_debug_seed_sort_mode (tests)
     DeviceLimits limits;               // of `device`
-    olf_keyline* d_kls = nullptr;      // [max_images][lineCap]   (host-pointer staging / fused path)
-    uint8_t* d_ldesc = nullptr;
-    int* d_lcounts = nullptr;
     void* d_lprep = nullptr;
     uint16_t* d_ldist = nullptr;
     int* d_lm21 = nullptr;
-    int* d_lm12 = nullptr;
-    float* d_ldisp = nullptr;
-    double* d_lle = nullptr;
     hipStream_t stream2 = nullptr;
     bool has_tables = false;       // holds a reference on the device's shared LSD angle tables
     hipEvent_t ev_front = nullptr;     // fused entry: recorded behind the LSD front including the seed ordering (the ORB stream's FAST waits for it)
@@ -56,13 +69,13 @@ struct olf_ctx {
     bool deferred_join = false;        // olf_ctx_set_deferred_join: olf_stereo_frames_dev returns with the line path still running on the line stream
     bool scaled_aliased = false;       // batch context: the LSD working images live in the key buffers (dead before those are written)
     bool join_pending = false;         // ... and this call's line path has not been joined yet (olf_stereo_frames_join_dev, or the next call)
-    // small contexts (the drop-in's one-pair-per-call shape): the eleven output arrays of olf_stereo_frames sit in ONE device slab, so that the host entry brings them
+    // small contexts (the drop-in's one-pair-per-call shape): the eleven arrays of d_out sit in ONE device slab, so that the host entry brings them
     // back with one copy into pinned memory instead of eleven (each a launch and a gap of its own: 0.44 ms of a 9 ms call, profiles/r5b_pair_timeline.txt)
-    uint8_t* d_outslab = nullptr; uint8_t* h_outslab = nullptr; size_t outslab_bytes = 0; size_t outslab_off[12] = {0};
+    uint8_t* d_outslab = nullptr; uint8_t* h_outslab = nullptr; size_t outslab_bytes = 0; size_t outslab_off[11] = {0};
     // every line-side output that call is still writing (key lines, LBD descriptors, counts, line matches, disparities, line equations): an entry that is handed
     // one of them (matcher, line stereo, packer) joins first.  The obligation is discharged for the whole context only when the frame call's OWN stream has
     // waited (pend_stream); a join on another stream orders that stream and leaves the obligation standing
-    struct { const uint8_t* p; size_t bytes; } pend[6] = {};
+    struct { const uint8_t* p; size_t bytes; } pend[FB_FIELDS - FB_KLS] = {};
     hipStream_t pend_stream = nullptr;
     hipEvent_t ev_sort = nullptr;      // fused entry: recorded in front of the seed ordering (the dense, bandwidth-bound half of the LSD front is through)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -85,6 +98,22 @@ static int check_device(const olf_ctx* c, const char* who)
 {
     int d = -1;
     if (hipGetDevice(&d) != hipSuccess || d != c->device) { set_error(std::string(who) + ": the context belongs to another device than the current one"); return OLF_ERR_INVALID; }
+    return OLF_OK;
+}
+
+// bytes of field k for n_images images (the pairs they make: an odd last image counts as a pair)
+static size_t fb_bytes(const olf_ctx* c, int k, size_t n_images)
+{
+    const FrameField& f = kFrameFields[k];
+    const size_t cap = f.cap == CAP_ORB ? c->orb.geom.outCap : f.cap == CAP_LINE ? c->line.geom.outCap : 1;
+    return (f.perPair ? (n_images + 1) / 2 : n_images) * cap * f.rowBytes;
+}
+
+// the copies of the host-pointer entries: fields first..last of n_images images between the context's arrays and the caller's (`h`, host pointers)
+static int fb_copy(olf_ctx* c, const olf_frame_buffers& h, int first, int last, size_t n_images, hipMemcpyKind kind)
+{
+    const olf_frame_buffers &src = kind == hipMemcpyDeviceToHost ? c->d_out : h, &dst = kind == hipMemcpyDeviceToHost ? h : c->d_out;
+    for (int k = first; k <= last; ++k) OLF_HIP_CHECK(hipMemcpyAsync(fb_field(dst, k), fb_field(src, k), fb_bytes(c, k, n_images), kind, c->stream));
     return OLF_OK;
 }
 
@@ -276,8 +305,8 @@ int olf_ctx_create(const olf_params* p, int width, int height, int max_images, o
     if (g.maxNodes > 2048) A(b.octSpill, n * g.nlevels * octree_lds_bytes(g.maxNodes));
     A(b.lvlKp, n * g.kpTotal); A(b.lvlCount, n * g.nlevels); A(b.lvlAngle, n * g.kpTotal);
     A(b.rx, c->orb.rx.size() + 1); A(b.ry, c->orb.ry.size() + 1); A(b.geom, 1); A(b.status, 256);
-    A(c->d_uright, ((n + 1) / 2) * g.outCap); A(c->d_depth, ((n + 1) / 2) * g.outCap); A(c->d_sad, ((n + 1) / 2) * g.outCap); A(c->d_bestkey, ((n + 1) / 2) * g.outCap); A(c->d_rowperm, n * g.outCap);
-    A(c->d_images, n * width * height); A(c->d_kps, n * g.outCap); A(c->d_desc, n * g.outCap * OLF_DESC_BYTES); A(c->d_counts, n);
+    A(c->d_sad, ((n + 1) / 2) * g.outCap); A(c->d_bestkey, ((n + 1) / 2) * g.outCap); A(c->d_rowperm, n * g.outCap);
+    A(c->d_images, n * width * height);
 #undef A
     if (hipMemcpy(b.rx, c->orb.rx.data(), c->orb.rx.size() * sizeof(ResizeCoef), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(b.ry, c->orb.ry.data(), c->orb.ry.size() * sizeof(ResizeCoef), hipMemcpyHostToDevice) != hipSuccess ||
@@ -328,29 +357,24 @@ int olf_ctx_create(const olf_params* p, int width, int height, int max_images, o
     A(l.mg, (size_t)l.mgImages * l.mgStride);
     A(l.rawLines, n * lg.maxDetect); A(l.rawCount, n); A(l.regCount, n); A(l.growFmt, n); A(l.lbdBlur, n * lg.pitchW * lg.H); A(l.dxdy, n * lg.pitchD * lg.H);
     A(l.rowSums, n * lg.outCap * 63 * 4); A(l.lbdStarts, n * lg.outCap * 64 * 2); A(l.rx, c->line.rx.size()); A(l.ry, c->line.ry.size()); A(l.geom, 1);
-    A(c->d_kls, n * lg.outCap); A(c->d_ldesc, n * lg.outCap * OLF_DESC_BYTES); A(c->d_lcounts, n);
-    {
-        const size_t np = (n + 1) / 2;
-        A(c->d_ldist, np * lg.outCap * lg.outCap); A(c->d_lm21, np * lg.outCap); A(c->d_lm12, np * lg.outCap);
-        A(c->d_ldisp, np * lg.outCap * 2); A(c->d_lle, np * lg.outCap * 3);
-        void* q = nullptr;
-        if (hipMalloc(&q, stereo_lines_prep_bytes((int)n, lg.outCap)) != hipSuccess) { set_error("hipMalloc failed"); return fail(OLF_ERR_HIP); }
-        c->allocs.push_back(q); c->d_lprep = q;
-    }
-    if (n <= 16) {
-        const size_t np = (n + 1) / 2, ocap = g.outCap, lcap = lg.outCap;
-        const size_t sz[11] = {n * ocap * sizeof(olf_keypoint), n * ocap * OLF_DESC_BYTES, n * sizeof(int), np * ocap * sizeof(float), np * ocap * sizeof(float),
-                               n * lcap * sizeof(olf_keyline), n * lcap * OLF_DESC_BYTES, n * sizeof(int), np * lcap * sizeof(int), np * lcap * 2 * sizeof(float), np * lcap * 3 * sizeof(double)};
+    A(c->d_ldist, ((n + 1) / 2) * lg.outCap * lg.outCap); A(c->d_lm21, ((n + 1) / 2) * lg.outCap);
+    if (hipMalloc(&c->d_lprep, stereo_lines_prep_bytes((int)n, lg.outCap)) != hipSuccess) { set_error("hipMalloc failed"); return fail(OLF_ERR_HIP); }
+    c->allocs.push_back(c->d_lprep);
+    // the output arrays: one slab for small contexts (256-byte aligned offsets), an allocation each otherwise
+    const bool slab = n <= 16;
+    if (slab) {
         size_t off = 0;
-        for (int k = 0; k < 11; ++k) { c->outslab_off[k] = off; off += (sz[k] + 255) & ~(size_t)255; }
-        c->outslab_off[11] = off; c->outslab_bytes = off;
+        for (int k = 0; k < FB_FIELDS; ++k) { c->outslab_off[k] = off; off += (fb_bytes(c, k, n) + 255) & ~(size_t)255; }
+        c->outslab_bytes = off;
         A(c->d_outslab, off);
         if (hipHostMalloc(reinterpret_cast<void**>(&c->h_outslab), off, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return fail(OLF_ERR_HIP); }
-        uint8_t* q = c->d_outslab;
-        c->d_kps = reinterpret_cast<olf_keypoint*>(q + c->outslab_off[0]); c->d_desc = q + c->outslab_off[1]; c->d_counts = reinterpret_cast<int*>(q + c->outslab_off[2]);
-        c->d_uright = reinterpret_cast<float*>(q + c->outslab_off[3]); c->d_depth = reinterpret_cast<float*>(q + c->outslab_off[4]);
-        c->d_kls = reinterpret_cast<olf_keyline*>(q + c->outslab_off[5]); c->d_ldesc = q + c->outslab_off[6]; c->d_lcounts = reinterpret_cast<int*>(q + c->outslab_off[7]);
-        c->d_lm12 = reinterpret_cast<int*>(q + c->outslab_off[8]); c->d_ldisp = reinterpret_cast<float*>(q + c->outslab_off[9]); c->d_lle = reinterpret_cast<double*>(q + c->outslab_off[10]);
+    }
+    for (int k = 0; k < FB_FIELDS; ++k) {
+        uint8_t* q = nullptr;
+        if (slab) q = c->d_outslab + c->outslab_off[k];
+        else if ((rc = dev_alloc(c, &q, fb_bytes(c, k, n))) != OLF_OK) return fail(rc);
+        fb_set_field(c->d_out, k, q);
+        if (allocTrace) fprintf(stderr, "alloc %-18s %8.3f MB per image\n", kFrameFields[k].name, (double)fb_bytes(c, k, n) / 1e6 / (double)n);
     }
 #undef A
     l.status = b.status;
@@ -464,26 +488,39 @@ int olf_orb_level_sizes(const olf_ctx* c, int32_t* widths, int32_t* heights)
 
 int olf_orb_capacity(const olf_ctx* c) { return c ? c->orb.geom.outCap : OLF_ERR_INVALID; }
 
-// fused: part of olf_stereo_frames_dev.  The blur only needs the pyramid, so it runs ahead of FAST in the shadow of the seed sort -- behind the dense half of
-// the LSD front (ev_sort) -- and so do the LBD gradient images (GaussianBlur + Sobel of the LBD octave need the input images only; ev_lbd tells the line
-// stream they are done); FAST waits for the whole front (ev_front)
-static int orb_extract(olf_ctx* c, const uint8_t* d_images, int n_images, olf_keypoint* d_kps, uint8_t* d_desc, int32_t* d_counts, hipStream_t s, bool fused)
+// ---- the stages: each opens its StageScope on the stream it is launched on and calls its launcher.  The entries below list them in the order they enqueue them
+static int stage_orb_pyramid(olf_ctx* c, const uint8_t* d_images, int n, hipStream_t s) { StageScope t(c, s, ST_ORB_PYRAMID); return launch_orb_pyramid(c->orb.geom, c->ob, d_images, n, s); }
+static int stage_orb_fast(olf_ctx* c, int n, hipStream_t s) { StageScope t(c, s, ST_ORB_FAST); return launch_orb_fast(c->orb.geom, c->ob, n, s); }
+static int stage_orb_octree(olf_ctx* c, int n, hipStream_t s) { StageScope t(c, s, ST_ORB_OCTREE); return launch_orb_octree(c->orb.geom, c->ob, n, s); }
+static int stage_orb_blur(olf_ctx* c, int n, hipStream_t s) { StageScope t(c, s, ST_ORB_BLUR); return launch_orb_blur(c->orb.geom, c->ob, n, s); }
+static int stage_orb_describe(olf_ctx* c, int n, olf_keypoint* kps, uint8_t* desc, int32_t* counts, hipStream_t s) { StageScope t(c, s, ST_ORB_DESCRIBE); return launch_orb_describe(c->orb.geom, c->ob, n, kps, desc, counts, c->orb.geom.outCap, s); }
+static int stage_stereo_points(olf_ctx* c, int n_pairs, const olf_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_counts, float* d_uright, float* d_depth, hipStream_t s)
 {
-    const OrbGeom& g = c->orb.geom;
-    c->last_n_images = n_images;
-    { StageScope t(c, s, ST_ORB_PYRAMID); OLF_TRY(launch_orb_pyramid(g, c->ob, d_images, n_images, s)); }
-    if (fused) {
-        OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_sort, 0));
-        { StageScope t(c, s, ST_ORB_BLUR); OLF_TRY(launch_orb_blur(g, c->ob, n_images, s)); }
-        OLF_TRY(launch_lbd_dense(c->line.geom, c->lb, d_images, c->W, n_images, s));
-        OLF_HIP_CHECK(hipEventRecord(c->ev_lbd, s));
-        OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_front, 0));
-    }
-    { StageScope t(c, s, ST_ORB_FAST); OLF_TRY(launch_orb_fast(g, c->ob, n_images, s)); }
-    { StageScope t(c, s, ST_ORB_OCTREE); OLF_TRY(launch_orb_octree(g, c->ob, n_images, s)); }
-    if (!fused) { StageScope t(c, s, ST_ORB_BLUR); OLF_TRY(launch_orb_blur(g, c->ob, n_images, s)); }
-    { StageScope t(c, s, ST_ORB_DESCRIBE); OLF_TRY(launch_orb_describe(g, c->ob, n_images, d_kps, d_desc, d_counts, g.outCap, s)); }
-    return OLF_OK;
+    StageScope t(c, s, ST_STEREO_POINTS);
+    return launch_stereo_points(c->orb.geom, c->ob, n_pairs, d_kps, d_desc, d_counts, c->orb.geom.outCap, c->params.stereo.bf, c->params.stereo.fx, d_uright, d_depth,
+                                c->d_sad, c->d_bestkey, c->d_rowperm, s);
+}
+// (dense half, seed order; olf_stereo_frames_dev records an event between the two and spells them out)
+static int stage_lsd_front(olf_ctx* c, const LsdPlan& plan, const uint8_t* d_images, int n, hipStream_t s, bool writeScaled)
+{
+    StageScope t(c, s, ST_LSD_FRONT);
+    OLF_TRY(launch_lsd_dense(c->line.geom, c->lb, plan, d_images, c->W, n, s, writeScaled));
+    return launch_lsd_seed_order(c->line.geom, c->lb, plan, n, s);
+}
+static int stage_lsd_grow(olf_ctx* c, const LsdPlan& plan, int n, hipStream_t s) { StageScope t(c, s, ST_LSD_GROW); return launch_lsd_grow(c->line.geom, c->lb, plan, n, s); }
+static int stage_lsd_rect(olf_ctx* c, const LsdPlan& plan, int n, hipStream_t s) { StageScope t(c, s, ST_LSD_RECT); return launch_lsd_rect(c->line.geom, c->lb, plan, n, s); }
+// (selection, LBD gradient images, descriptors; olf_stereo_frames_dev has the gradient images from its ORB stream and spells the rest out)
+static int stage_line_lbd(olf_ctx* c, const uint8_t* d_images, int n, olf_keyline* d_kls, uint8_t* d_ldesc, int32_t* d_lcounts, hipStream_t s)
+{
+    StageScope t(c, s, ST_LINE_LBD);
+    OLF_TRY(launch_line_select(c->line.geom, c->lb, n, d_kls, d_lcounts, s));
+    OLF_TRY(launch_lbd_dense(c->line.geom, c->lb, d_images, c->W, n, s));
+    return launch_lbd_desc(c->line.geom, c->lb, n, d_kls, d_ldesc, d_lcounts, s);
+}
+static int stage_stereo_lines(olf_ctx* c, int n_pairs, const olf_keyline* d_kls, const uint8_t* d_ldesc, const int32_t* d_lcounts, int32_t* d_m12, float* d_disp, double* d_le, hipStream_t s)
+{
+    StageScope t(c, s, ST_STEREO_LINES);
+    return launch_stereo_lines(c->W, c->H, c->params.stereo, n_pairs, d_kls, d_ldesc, d_lcounts, c->line.geom.outCap, c->d_lprep, c->d_ldist, c->d_lm21, d_m12, d_disp, d_le, s);
 }
 
 int olf_orb_extract_dev(olf_ctx* c, const uint8_t* d_images, int n_images, olf_keypoint* d_kps, uint8_t* d_desc, int32_t* d_counts,
@@ -493,7 +530,12 @@ int olf_orb_extract_dev(olf_ctx* c, const uint8_t* d_images, int n_images, olf_k
     OLF_TRY(check_device(c, "olf_orb_extract_dev"));
     if (n_images < 0 || n_images > c->max_images) { set_error("olf_orb_extract_dev: n_images exceeds the context capacity"); return OLF_ERR_CAPACITY; }
     if (n_images == 0) return OLF_OK;   // ORBextractor::operator() returns silently on an empty image
-    return orb_extract(c, d_images, n_images, d_kps, d_desc, d_counts, stream ? (hipStream_t)stream : c->stream, false);
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    OLF_TRY(stage_orb_pyramid(c, d_images, n_images, s));
+    OLF_TRY(stage_orb_fast(c, n_images, s));
+    OLF_TRY(stage_orb_octree(c, n_images, s));
+    OLF_TRY(stage_orb_blur(c, n_images, s));
+    return stage_orb_describe(c, n_images, d_kps, d_desc, d_counts, s);
 }
 
 static int check_status(olf_ctx* c)
@@ -514,12 +556,10 @@ int olf_orb_extract(olf_ctx* c, const uint8_t* images, int n_images, olf_keypoin
     if (!c || !images || !kps || !desc || !counts) { set_error("olf_orb_extract: null argument"); return OLF_ERR_INVALID; }
     if (n_images < 0 || n_images > c->max_images) return OLF_ERR_CAPACITY;
     if (n_images == 0) return OLF_OK;
-    const size_t npx = (size_t)c->W * c->H, cap = c->orb.geom.outCap;
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, npx * n_images, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_orb_extract_dev(c, c->d_images, n_images, c->d_kps, c->d_desc, c->d_counts, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(kps, c->d_kps, cap * n_images * sizeof(olf_keypoint), hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(desc, c->d_desc, cap * n_images * OLF_DESC_BYTES, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(counts, c->d_counts, n_images * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    olf_frame_buffers h = {}; h.kps = kps; h.desc = desc; h.counts = counts;
+    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, (size_t)c->W * c->H * n_images, hipMemcpyHostToDevice, c->stream));
+    OLF_TRY(olf_orb_extract_dev(c, c->d_images, n_images, c->d_out.kps, c->d_out.desc, c->d_out.counts, c->stream));
+    OLF_TRY(fb_copy(c, h, FB_KPS, FB_COUNTS, n_images, hipMemcpyDeviceToHost));
     OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
     return check_status(c);
 }
@@ -527,12 +567,10 @@ int olf_orb_extract(olf_ctx* c, const uint8_t* images, int n_images, olf_keypoin
 int olf_orb_extract_strided(olf_ctx* c, const uint8_t* image, size_t row_stride, olf_keypoint* kps, uint8_t* desc, int32_t* count)
 {
     if (!c || !image || !kps || !desc || !count || row_stride < (size_t)c->W) { set_error("olf_orb_extract_strided: bad argument"); return OLF_ERR_INVALID; }
-    const size_t cap = c->orb.geom.outCap;
+    olf_frame_buffers h = {}; h.kps = kps; h.desc = desc; h.counts = count;
     OLF_HIP_CHECK(hipMemcpy2DAsync(c->d_images, c->W, image, row_stride, c->W, c->H, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_orb_extract_dev(c, c->d_images, 1, c->d_kps, c->d_desc, c->d_counts, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(count, c->d_counts, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(kps, c->d_kps, cap * sizeof(olf_keypoint), hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(desc, c->d_desc, cap * OLF_DESC_BYTES, hipMemcpyDeviceToHost, c->stream));
+    OLF_TRY(olf_orb_extract_dev(c, c->d_images, 1, c->d_out.kps, c->d_out.desc, c->d_out.counts, c->stream));
+    OLF_TRY(fb_copy(c, h, FB_KPS, FB_COUNTS, 1, hipMemcpyDeviceToHost));
     OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
     return check_status(c);
 }
@@ -794,10 +832,7 @@ int olf_stereo_points_dev(olf_ctx* c, int n_pairs, const olf_keypoint* d_kps, co
     OLF_TRY(check_device(c, "olf_stereo_points_dev"));
     if (n_pairs < 0 || 2 * n_pairs > c->max_images) return OLF_ERR_CAPACITY;
     if (n_pairs == 0) return OLF_OK;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    StageScope t(c, s, ST_STEREO_POINTS);
-    return launch_stereo_points(c->orb.geom, c->ob, n_pairs, d_kps, d_desc, d_counts, c->orb.geom.outCap, c->params.stereo.bf,
-                                c->params.stereo.fx, d_uright, d_depth, c->d_sad, c->d_bestkey, c->d_rowperm, s);
+    return stage_stereo_points(c, n_pairs, d_kps, d_desc, d_counts, d_uright, d_depth, stream ? (hipStream_t)stream : c->stream);
 }
 
 int olf_stereo_points(olf_ctx* c, const uint8_t* images, int n_pairs, olf_keypoint* kps, uint8_t* desc, int32_t* counts, float* uright,
@@ -807,15 +842,11 @@ int olf_stereo_points(olf_ctx* c, const uint8_t* images, int n_pairs, olf_keypoi
     const int n_images = 2 * n_pairs;
     if (n_pairs < 0 || n_images > c->max_images) return OLF_ERR_CAPACITY;
     if (n_pairs == 0) return OLF_OK;
-    const size_t npx = (size_t)c->W * c->H, cap = c->orb.geom.outCap;
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, npx * n_images, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_orb_extract_dev(c, c->d_images, n_images, c->d_kps, c->d_desc, c->d_counts, c->stream));
-    OLF_TRY(olf_stereo_points_dev(c, n_pairs, c->d_kps, c->d_desc, c->d_counts, c->d_uright, c->d_depth, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(kps, c->d_kps, cap * n_images * sizeof(olf_keypoint), hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(desc, c->d_desc, cap * n_images * OLF_DESC_BYTES, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(counts, c->d_counts, n_images * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(uright, c->d_uright, cap * n_pairs * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(depth, c->d_depth, cap * n_pairs * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    olf_frame_buffers h = {}; h.kps = kps; h.desc = desc; h.counts = counts; h.uright = uright; h.depth = depth;
+    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, (size_t)c->W * c->H * n_images, hipMemcpyHostToDevice, c->stream));
+    OLF_TRY(olf_orb_extract_dev(c, c->d_images, n_images, c->d_out.kps, c->d_out.desc, c->d_out.counts, c->stream));
+    OLF_TRY(olf_stereo_points_dev(c, n_pairs, c->d_out.kps, c->d_out.desc, c->d_out.counts, c->d_out.uright, c->d_out.depth, c->stream));
+    OLF_TRY(fb_copy(c, h, FB_KPS, FB_DEPTH, n_images, hipMemcpyDeviceToHost));
     OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
     return check_status(c);
 }
@@ -1034,33 +1065,18 @@ int olf_distinctive_descriptors(olf_ctx* c, const uint8_t* desc, const int32_t* 
 // ---------------------------------------------------------------------------------------------
 int olf_line_capacity(const olf_ctx* c) { return c ? c->line.geom.outCap : OLF_ERR_INVALID; }
 
-// fused: part of olf_stereo_frames_dev.  The front records ev_sort in front of the seed ordering and ev_front behind it (the ORB stream waits for them), and
-// the path stops behind the rectangles: the caller enqueues selection + LBD behind the LBD gradient images of the ORB stream
-static int line_extract(olf_ctx* c, const uint8_t* d_images, int n_images, olf_keyline* d_kls, uint8_t* d_ldesc, int32_t* d_lcounts, hipStream_t s, bool fused)
-{
-    const LineGeom& g = c->line.geom;
-    const LsdPlan plan = lsd_plan(g, c->lb, c->lsd_force, c->limits, n_images);
-    hipEvent_t sortEvent = nullptr;
-    if (fused) {
-        if (g.seedOrder == 1) sortEvent = c->ev_sort;
-        else OLF_HIP_CHECK(hipEventRecord(c->ev_sort, s));      // (no sort kernel to hide behind: the event is already true)
-    }
-    { StageScope t(c, s, ST_LSD_FRONT); OLF_TRY(launch_lsd_front(g, c->lb, plan, d_images, c->W, n_images, s, sortEvent, !fused)); }      // (fused: nothing behind reads the working image)
-    if (fused) OLF_HIP_CHECK(hipEventRecord(c->ev_front, s));
-    { StageScope t(c, s, ST_LSD_GROW); OLF_TRY(launch_lsd_grow(g, c->lb, plan, n_images, s)); }
-    { StageScope t(c, s, ST_LSD_RECT); OLF_TRY(launch_lsd_rect(g, c->lb, plan, n_images, s)); }
-    if (fused) return OLF_OK;
-    { StageScope t(c, s, ST_LINE_LBD); OLF_TRY(launch_line_select_lbd(c->line.geom, c->lb, d_images, c->W, n_images, d_kls, d_ldesc, d_lcounts, s)); }
-    return OLF_OK;
-}
-
 int olf_line_extract_dev(olf_ctx* c, const uint8_t* d_images, int n_images, olf_keyline* d_kls, uint8_t* d_ldesc, int32_t* d_lcounts, void* stream)
 {
     if (!c || !d_images || !d_kls || !d_ldesc || !d_lcounts) { set_error("olf_line_extract_dev: null argument"); return OLF_ERR_INVALID; }
     OLF_TRY(check_device(c, "olf_line_extract_dev"));
     if (n_images < 0 || n_images > c->max_images) return OLF_ERR_CAPACITY;
     if (n_images == 0) return OLF_OK;
-    return line_extract(c, d_images, n_images, d_kls, d_ldesc, d_lcounts, stream ? (hipStream_t)stream : c->stream, false);
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const LsdPlan plan = lsd_plan(c->line.geom, c->lb, c->lsd_force, c->limits, n_images);
+    OLF_TRY(stage_lsd_front(c, plan, d_images, n_images, s, true));
+    OLF_TRY(stage_lsd_grow(c, plan, n_images, s));
+    OLF_TRY(stage_lsd_rect(c, plan, n_images, s));
+    return stage_line_lbd(c, d_images, n_images, d_kls, d_ldesc, d_lcounts, s);
 }
 
 int olf_line_extract(olf_ctx* c, const uint8_t* images, int n_images, olf_keyline* kls, uint8_t* ldesc, int32_t* lcounts)
@@ -1068,12 +1084,10 @@ int olf_line_extract(olf_ctx* c, const uint8_t* images, int n_images, olf_keylin
     if (!c || !images || !kls || !ldesc || !lcounts) { set_error("olf_line_extract: null argument"); return OLF_ERR_INVALID; }
     if (n_images < 0 || n_images > c->max_images) return OLF_ERR_CAPACITY;
     if (n_images == 0) return OLF_OK;
-    const size_t npx = (size_t)c->W * c->H, cap = c->line.geom.outCap;
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, npx * n_images, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_line_extract_dev(c, c->d_images, n_images, c->d_kls, c->d_ldesc, c->d_lcounts, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(kls, c->d_kls, cap * n_images * sizeof(olf_keyline), hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(ldesc, c->d_ldesc, cap * n_images * OLF_DESC_BYTES, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(lcounts, c->d_lcounts, n_images * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    olf_frame_buffers h = {}; h.kls = kls; h.ldesc = ldesc; h.lcounts = lcounts;
+    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, (size_t)c->W * c->H * n_images, hipMemcpyHostToDevice, c->stream));
+    OLF_TRY(olf_line_extract_dev(c, c->d_images, n_images, c->d_out.kls, c->d_out.ldesc, c->d_out.lcounts, c->stream));
+    OLF_TRY(fb_copy(c, h, FB_KLS, FB_LCOUNTS, n_images, hipMemcpyDeviceToHost));
     OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
     return check_status(c);
 }
@@ -1081,12 +1095,10 @@ int olf_line_extract(olf_ctx* c, const uint8_t* images, int n_images, olf_keylin
 int olf_line_extract_strided(olf_ctx* c, const uint8_t* image, size_t row_stride, olf_keyline* kls, uint8_t* ldesc, int32_t* lcount)
 {
     if (!c || !image || !kls || !ldesc || !lcount || row_stride < (size_t)c->W) { set_error("olf_line_extract_strided: bad argument"); return OLF_ERR_INVALID; }
-    const size_t cap = c->line.geom.outCap;
+    olf_frame_buffers h = {}; h.kls = kls; h.ldesc = ldesc; h.lcounts = lcount;
     OLF_HIP_CHECK(hipMemcpy2DAsync(c->d_images, c->W, image, row_stride, c->W, c->H, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_line_extract_dev(c, c->d_images, 1, c->d_kls, c->d_ldesc, c->d_lcounts, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(kls, c->d_kls, cap * sizeof(olf_keyline), hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(ldesc, c->d_ldesc, cap * OLF_DESC_BYTES, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(lcount, c->d_lcounts, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    OLF_TRY(olf_line_extract_dev(c, c->d_images, 1, c->d_out.kls, c->d_out.ldesc, c->d_out.lcounts, c->stream));
+    OLF_TRY(fb_copy(c, h, FB_KLS, FB_LCOUNTS, 1, hipMemcpyDeviceToHost));
     OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
     return check_status(c);
 }
@@ -1096,15 +1108,16 @@ int olf_lbd_compute(olf_ctx* c, const uint8_t* images, int n_images, const olf_k
     if (!c || !images || !kls || !lcounts || !ldesc) { set_error("olf_lbd_compute: null argument"); return OLF_ERR_INVALID; }
     if (n_images < 0 || n_images > c->max_images) return OLF_ERR_CAPACITY;
     if (n_images == 0) return OLF_OK;
-    const size_t npx = (size_t)c->W * c->H, cap = c->line.geom.outCap;
     for (int i = 0; i < n_images; ++i)
-        if (lcounts[i] < 0 || lcounts[i] > (int)cap) { set_error("olf_lbd_compute: count exceeds capacity"); return OLF_ERR_CAPACITY; }
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, npx * n_images, hipMemcpyHostToDevice, c->stream));
-    // stage the caller's key lines as the "raw" list, with selection disabled by pretending they are final
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_kls, kls, cap * n_images * sizeof(olf_keyline), hipMemcpyHostToDevice, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_lcounts, lcounts, n_images * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(launch_lbd_only(c->line.geom, c->lb, c->d_images, c->W, n_images, c->d_kls, c->d_ldesc, c->d_lcounts, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(ldesc, c->d_ldesc, cap * n_images * OLF_DESC_BYTES, hipMemcpyDeviceToHost, c->stream));
+        if (lcounts[i] < 0 || lcounts[i] > c->line.geom.outCap) { set_error("olf_lbd_compute: count exceeds capacity"); return OLF_ERR_CAPACITY; }
+    olf_frame_buffers h = {}; h.kls = const_cast<olf_keyline*>(kls); h.ldesc = ldesc; h.lcounts = const_cast<int32_t*>(lcounts);
+    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, (size_t)c->W * c->H * n_images, hipMemcpyHostToDevice, c->stream));
+    // BinaryDescriptor::compute on the caller's key lines: no LSD, no selection
+    OLF_TRY(fb_copy(c, h, FB_KLS, FB_KLS, n_images, hipMemcpyHostToDevice));
+    OLF_TRY(fb_copy(c, h, FB_LCOUNTS, FB_LCOUNTS, n_images, hipMemcpyHostToDevice));
+    OLF_TRY(launch_lbd_dense(c->line.geom, c->lb, c->d_images, c->W, n_images, c->stream));
+    OLF_TRY(launch_lbd_desc(c->line.geom, c->lb, n_images, c->d_out.kls, c->d_out.ldesc, c->d_out.lcounts, c->stream));
+    OLF_TRY(fb_copy(c, h, FB_LDESC, FB_LDESC, n_images, hipMemcpyDeviceToHost));
     OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
     return OLF_OK;
 }
@@ -1131,9 +1144,7 @@ int olf_stereo_lines_dev(olf_ctx* c, int n_pairs, const olf_keyline* d_kls, cons
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     // key lines / descriptors of a frame call whose line path is still running (deferred join): this stream waits for it first
     if (s != c->stream2 && (in_pending_line_outputs(c, d_kls) || in_pending_line_outputs(c, d_ldesc) || in_pending_line_outputs(c, d_lcounts))) OLF_TRY(join_if_pending(c, s));
-    StageScope t(c, s, ST_STEREO_LINES);
-    return launch_stereo_lines(c->W, c->H, c->params.stereo, n_pairs, d_kls, d_ldesc, d_lcounts, c->line.geom.outCap, c->d_lprep, c->d_ldist,
-                               c->d_lm21, d_m12, d_disp, d_le, s);
+    return stage_stereo_lines(c, n_pairs, d_kls, d_ldesc, d_lcounts, d_m12, d_disp, d_le, s);
 }
 
 int olf_stereo_lines(olf_ctx* c, int n_pairs, const olf_keyline* kls, const uint8_t* ldesc, const int32_t* lcounts, int32_t* m12, float* disp,
@@ -1145,41 +1156,68 @@ int olf_stereo_lines(olf_ctx* c, int n_pairs, const olf_keyline* kls, const uint
     const size_t cap = c->line.geom.outCap, ni = 2 * (size_t)n_pairs;
     for (size_t i = 0; i < ni; ++i)
         if (lcounts[i] < 0 || lcounts[i] > (int)cap) { set_error("olf_stereo_lines: count exceeds capacity"); return OLF_ERR_CAPACITY; }
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_kls, kls, cap * ni * sizeof(olf_keyline), hipMemcpyHostToDevice, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_ldesc, ldesc, cap * ni * OLF_DESC_BYTES, hipMemcpyHostToDevice, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_lcounts, lcounts, ni * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_stereo_lines_dev(c, n_pairs, c->d_kls, c->d_ldesc, c->d_lcounts, c->d_lm12, c->d_ldisp, c->d_lle, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(m12, c->d_lm12, cap * n_pairs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(disp, c->d_ldisp, cap * n_pairs * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(le, c->d_lle, cap * n_pairs * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    olf_frame_buffers h = {}; h.kls = const_cast<olf_keyline*>(kls); h.ldesc = const_cast<uint8_t*>(ldesc); h.lcounts = const_cast<int32_t*>(lcounts);
+    h.lmatches12 = m12; h.ldisp = disp; h.lle = le;
+    OLF_TRY(fb_copy(c, h, FB_KLS, FB_LCOUNTS, ni, hipMemcpyHostToDevice));
+    OLF_TRY(olf_stereo_lines_dev(c, n_pairs, c->d_out.kls, c->d_out.ldesc, c->d_out.lcounts, c->d_out.lmatches12, c->d_out.ldisp, c->d_out.lle, c->stream));
+    OLF_TRY(fb_copy(c, h, FB_LMATCHES12, FB_LLE, ni, hipMemcpyDeviceToHost));
     OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
     return OLF_OK;
 }
 
 int olf_stereo_frames_dev(olf_ctx* c, const uint8_t* d_images, int n_pairs, const olf_frame_buffers* o, void* stream)
 {
-    if (!c || !d_images || !o || !o->kps || !o->desc || !o->counts || !o->uright || !o->depth || !o->kls || !o->ldesc || !o->lcounts ||
-        !o->lmatches12 || !o->ldisp || !o->lle) { set_error("olf_stereo_frames_dev: null argument"); return OLF_ERR_INVALID; }
+    bool args = c && d_images && o;
+    for (int k = 0; args && k < FB_FIELDS; ++k) args = fb_field(*o, k) != nullptr;
+    if (!args) { set_error("olf_stereo_frames_dev: null argument"); return OLF_ERR_INVALID; }
     OLF_TRY(check_device(c, "olf_stereo_frames_dev"));
     if (n_pairs < 0 || 2 * n_pairs > c->max_images) return OLF_ERR_CAPACITY;
     if (n_pairs == 0) return OLF_OK;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream, ls = c->stream2;
     const int n_images = 2 * n_pairs;
+    const LineGeom& lg = c->line.geom;
+    const LsdPlan plan = lsd_plan(lg, c->lb, c->lsd_force, c->limits, n_images);
     if (c->join_pending) { OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_join, 0)); c->join_pending = false; }      // (a deferred join the caller never asked for)
+    // OLF_ONE_STREAM serialises the two paths: every stage on the caller's stream, the line path first
+    static const bool one_stream = getenv("OLF_ONE_STREAM") != nullptr;
+    if (one_stream) {
+        OLF_TRY(stage_lsd_front(c, plan, d_images, n_images, s, true));
+        OLF_TRY(stage_lsd_grow(c, plan, n_images, s));
+        OLF_TRY(stage_lsd_rect(c, plan, n_images, s));
+        OLF_TRY(stage_line_lbd(c, d_images, n_images, o->kls, o->ldesc, o->lcounts, s));
+        OLF_TRY(stage_stereo_lines(c, n_pairs, o->kls, o->ldesc, o->lcounts, o->lmatches12, o->ldisp, o->lle, s));
+        OLF_TRY(stage_orb_pyramid(c, d_images, n_images, s));
+        OLF_TRY(stage_orb_fast(c, n_images, s));
+        OLF_TRY(stage_orb_octree(c, n_images, s));
+        OLF_TRY(stage_orb_blur(c, n_images, s));
+        OLF_TRY(stage_orb_describe(c, n_images, o->kps, o->desc, o->counts, s));
+        return stage_stereo_points(c, n_pairs, o->kps, o->desc, o->counts, o->uright, o->depth, s);
+    }
+    // The schedule.  What follows is every stage of both streams and every record / wait of the five events, in the order the host enqueues them (which
+    // matters: a wait enqueued before its event's record is a no-op):
+    //
+    //      caller's stream `s`: the ORB path                    line stream `ls`: the line path
+    //      ---------------------------------                    -------------------------------
+    //      ev_fork (or the caller's input event) ------------>
+    //      pyramid                                              LSD front, dense half
+    //                      <------------------------ ev_sort
+    //      blur                                                 LSD front, seed order
+    //      LBD gradient images
+    //      ev_lbd ---------------------------------+
+    //                      <---------------------- | ev_front
+    //      FAST                                    |            growth
+    //      octree                                  |            rectangles
+    //      describe                                +--------->
+    //      stereo points                                        selection, LBD descriptors
+    //                                                           line stereo
+    //                      <------------------------ ev_join
+    //
     // The line path runs beside the ORB path on the second stream (the reference's 4 extraction threads, src/Frame.cc:164-171).  The ORB
     // stream builds its pyramid beside the dense half of the LSD front, runs its blur and the LBD gradient images (6 ms of dense work) in the shadow of
     // the seed ordering, and waits for the front's end before FAST: two dense pipelines at once only slow each other down (290 ms per 3072-pair step
     // with no wait at all), whereas FAST beside the latency-bound growth agents is hidden almost completely (105 ms beside them, 24 alone, and the
     // agents keep their stand-alone speed).  (The other schedules measured: profiles/HISTORY_design_rounds1-4.md, profiles/r4o_*.)
-    // OLF_ONE_STREAM serialises the two paths.
-    static const bool one_stream = getenv("OLF_ONE_STREAM") != nullptr;
-    if (one_stream) {
-        OLF_TRY(olf_line_extract_dev(c, d_images, n_images, o->kls, o->ldesc, o->lcounts, s));
-        OLF_TRY(olf_stereo_lines_dev(c, n_pairs, o->kls, o->ldesc, o->lcounts, o->lmatches12, o->ldisp, o->lle, s));
-        OLF_TRY(olf_orb_extract_dev(c, d_images, n_images, o->kps, o->desc, o->counts, s));
-        OLF_TRY(olf_stereo_points_dev(c, n_pairs, o->kps, o->desc, o->counts, o->uright, o->depth, s));
-        return OLF_OK;
-    }
+    //
     // Fork.  With the caller's input event (olf_ctx_set_input_event) the line stream does not wait for what is still queued on `s` -- the ORB / stereo /
     // matching tail of the previous batch -- and the LSD front of this batch runs beside it.  Safe: the LSD front, growth and rectangles write line-path
     // scratch that nothing on `s` reads, and selection / LBD / line stereo (which write the output buffers the previous batch's matchers and packer on `s`
@@ -1187,33 +1225,53 @@ int olf_stereo_frames_dev(olf_ctx* c, const uint8_t* d_images, int n_pairs, cons
     // (the event is consumed by the call: one-shot -- a stale handle must never order a later call)
     hipEvent_t in_ev = c->input_event;
     c->input_event = nullptr;
-    if (in_ev) OLF_HIP_CHECK(hipStreamWaitEvent(c->stream2, in_ev, 0));
+    if (in_ev) OLF_HIP_CHECK(hipStreamWaitEvent(ls, in_ev, 0));
     else {
         OLF_HIP_CHECK(hipEventRecord(c->ev_fork, s));
-        OLF_HIP_CHECK(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+        OLF_HIP_CHECK(hipStreamWaitEvent(ls, c->ev_fork, 0));
     }
-    OLF_TRY(line_extract(c, d_images, n_images, o->kls, o->ldesc, o->lcounts, c->stream2, true));
-    OLF_TRY(orb_extract(c, d_images, n_images, o->kps, o->desc, o->counts, s, true));
+    // line stream, up to the rectangles.  ev_sort is recorded in front of the seed ordering (the dense, bandwidth-bound half of the front is through) and
+    // ev_front behind it.  One quirk, kept: without the std::sort seed order ev_sort is recorded in front of the WHOLE front, not behind its dense half
+    if (lg.seedOrder != 1) OLF_HIP_CHECK(hipEventRecord(c->ev_sort, ls));      // (no sort kernel to hide behind: the event is already true)
+    {
+        StageScope t(c, ls, ST_LSD_FRONT);
+        OLF_TRY(launch_lsd_dense(lg, c->lb, plan, d_images, c->W, n_images, ls, false));      // (nothing behind reads the working image)
+        if (lg.seedOrder == 1) OLF_HIP_CHECK(hipEventRecord(c->ev_sort, ls));
+        OLF_TRY(launch_lsd_seed_order(lg, c->lb, plan, n_images, ls));
+    }
+    OLF_HIP_CHECK(hipEventRecord(c->ev_front, ls));
+    OLF_TRY(stage_lsd_grow(c, plan, n_images, ls));
+    OLF_TRY(stage_lsd_rect(c, plan, n_images, ls));
+    // ORB stream.  The blur only needs the pyramid, so it runs ahead of FAST in the shadow of the seed sort -- behind the dense half of
+    // the LSD front (ev_sort) -- and so do the LBD gradient images (GaussianBlur + Sobel of the LBD octave need the input images only; ev_lbd tells the line
+    // stream they are done); FAST waits for the whole front (ev_front)
+    OLF_TRY(stage_orb_pyramid(c, d_images, n_images, s));
+    OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_sort, 0));
+    OLF_TRY(stage_orb_blur(c, n_images, s));
+    OLF_TRY(launch_lbd_dense(lg, c->lb, d_images, c->W, n_images, s));
+    OLF_HIP_CHECK(hipEventRecord(c->ev_lbd, s));
+    OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_front, 0));
+    OLF_TRY(stage_orb_fast(c, n_images, s));
+    OLF_TRY(stage_orb_octree(c, n_images, s));
+    OLF_TRY(stage_orb_describe(c, n_images, o->kps, o->desc, o->counts, s));
     // the line stream's selection + LBD wait for ev_lbd, so they are enqueued behind the ORB extraction (an event has to be recorded before the wait for it
     // is enqueued)
-    OLF_HIP_CHECK(hipStreamWaitEvent(c->stream2, c->ev_lbd, 0));
-    { StageScope t(c, c->stream2, ST_LINE_LBD); OLF_TRY(launch_line_select_lbd(c->line.geom, c->lb, d_images, c->W, n_images, o->kls, o->ldesc, o->lcounts, c->stream2, true)); }
-    OLF_TRY(olf_stereo_lines_dev(c, n_pairs, o->kls, o->ldesc, o->lcounts, o->lmatches12, o->ldisp, o->lle, c->stream2));
-    OLF_HIP_CHECK(hipEventRecord(c->ev_join, c->stream2));
-    OLF_TRY(olf_stereo_points_dev(c, n_pairs, o->kps, o->desc, o->counts, o->uright, o->depth, s));
+    OLF_HIP_CHECK(hipStreamWaitEvent(ls, c->ev_lbd, 0));
+    {
+        StageScope t(c, ls, ST_LINE_LBD);
+        OLF_TRY(launch_line_select(lg, c->lb, n_images, o->kls, o->lcounts, ls));
+        OLF_TRY(launch_lbd_desc(lg, c->lb, n_images, o->kls, o->ldesc, o->lcounts, ls));
+    }
+    OLF_TRY(stage_stereo_lines(c, n_pairs, o->kls, o->ldesc, o->lcounts, o->lmatches12, o->ldisp, o->lle, ls));
+    OLF_HIP_CHECK(hipEventRecord(c->ev_join, ls));
+    OLF_TRY(stage_stereo_points(c, n_pairs, o->kps, o->desc, o->counts, o->uright, o->depth, s));
     // the join.  Deferred (olf_ctx_set_deferred_join): the caller's stream goes on with the ORB outputs -- key points, descriptors, stereo points are complete on
     // it here -- while the line path's tail (selection, LBD, line stereo: 20 ms of a 3072-pair batch) still runs on the line stream; olf_stereo_frames_join_dev
     // (or the next call) makes the stream wait for it
     if (c->deferred_join) {
         c->join_pending = true;
         c->pend_stream = s;
-        const size_t lc = (size_t)c->line.geom.outCap;
-        c->pend[0] = {reinterpret_cast<const uint8_t*>(o->kls), (size_t)n_images * lc * sizeof(olf_keyline)};
-        c->pend[1] = {reinterpret_cast<const uint8_t*>(o->ldesc), (size_t)n_images * lc * OLF_DESC_BYTES};
-        c->pend[2] = {reinterpret_cast<const uint8_t*>(o->lcounts), (size_t)n_images * sizeof(int32_t)};
-        c->pend[3] = {reinterpret_cast<const uint8_t*>(o->lmatches12), (size_t)n_pairs * lc * sizeof(int32_t)};
-        c->pend[4] = {reinterpret_cast<const uint8_t*>(o->ldisp), (size_t)n_pairs * lc * 2 * sizeof(float)};
-        c->pend[5] = {reinterpret_cast<const uint8_t*>(o->lle), (size_t)n_pairs * lc * 3 * sizeof(double)};
+        for (int k = FB_KLS; k < FB_FIELDS; ++k) c->pend[k - FB_KLS] = {static_cast<const uint8_t*>(fb_field(*o, k)), fb_bytes(c, k, n_images)};
     } else OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_join, 0));
     return OLF_OK;
 }
@@ -1236,40 +1294,20 @@ int olf_stereo_frames(olf_ctx* c, const uint8_t* images, int n_pairs, const olf_
     if (!c || !images || !o) { set_error("olf_stereo_frames: null argument"); return OLF_ERR_INVALID; }
     if (n_pairs < 0 || 2 * n_pairs > c->max_images) return OLF_ERR_CAPACITY;
     if (n_pairs == 0) return OLF_OK;
-    const size_t npx = (size_t)c->W * c->H, cap = c->orb.geom.outCap, lcap = c->line.geom.outCap, ni = 2 * (size_t)n_pairs;
-    olf_frame_buffers d;
-    d.kps = c->d_kps; d.desc = c->d_desc; d.counts = c->d_counts; d.uright = c->d_uright; d.depth = c->d_depth;
-    d.kls = c->d_kls; d.ldesc = c->d_ldesc; d.lcounts = c->d_lcounts; d.lmatches12 = c->d_lm12; d.ldisp = c->d_ldisp; d.lle = c->d_lle;
+    const size_t ni = 2 * (size_t)n_pairs;
     c->input_event = nullptr;           // (the upload below is on the context's stream: the line stream must fork from it, whatever event an earlier caller left)
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, npx * ni, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_stereo_frames_dev(c, c->d_images, n_pairs, &d, c->stream));
+    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, (size_t)c->W * c->H * ni, hipMemcpyHostToDevice, c->stream));
+    OLF_TRY(olf_stereo_frames_dev(c, c->d_images, n_pairs, &c->d_out, c->stream));
     OLF_TRY(olf_stereo_frames_join_dev(c, c->stream));      // (a context with the deferred join on: the copies below read the line outputs)
-    hipStream_t s = c->stream;
     if (c->d_outslab && (int)ni == c->max_images) {
         // one copy for all eleven arrays, then host copies out of the pinned slab (the arrays are laid out for exactly this many images)
-        OLF_HIP_CHECK(hipMemcpyAsync(c->h_outslab, c->d_outslab, c->outslab_bytes, hipMemcpyDeviceToHost, s));
-        OLF_HIP_CHECK(hipStreamSynchronize(s));
-        const uint8_t* h = c->h_outslab;
-        memcpy(o->kps, h + c->outslab_off[0], cap * ni * sizeof(olf_keypoint)); memcpy(o->desc, h + c->outslab_off[1], cap * ni * OLF_DESC_BYTES);
-        memcpy(o->counts, h + c->outslab_off[2], ni * sizeof(int)); memcpy(o->uright, h + c->outslab_off[3], cap * n_pairs * sizeof(float));
-        memcpy(o->depth, h + c->outslab_off[4], cap * n_pairs * sizeof(float)); memcpy(o->kls, h + c->outslab_off[5], lcap * ni * sizeof(olf_keyline));
-        memcpy(o->ldesc, h + c->outslab_off[6], lcap * ni * OLF_DESC_BYTES); memcpy(o->lcounts, h + c->outslab_off[7], ni * sizeof(int));
-        memcpy(o->lmatches12, h + c->outslab_off[8], lcap * n_pairs * sizeof(int)); memcpy(o->ldisp, h + c->outslab_off[9], lcap * n_pairs * 2 * sizeof(float));
-        memcpy(o->lle, h + c->outslab_off[10], lcap * n_pairs * 3 * sizeof(double));
+        OLF_HIP_CHECK(hipMemcpyAsync(c->h_outslab, c->d_outslab, c->outslab_bytes, hipMemcpyDeviceToHost, c->stream));
+        OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
+        for (int k = 0; k < FB_FIELDS; ++k) memcpy(fb_field(*o, k), c->h_outslab + c->outslab_off[k], fb_bytes(c, k, ni));
         return check_status(c);
     }
-    OLF_HIP_CHECK(hipMemcpyAsync(o->kps, d.kps, cap * ni * sizeof(olf_keypoint), hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipMemcpyAsync(o->desc, d.desc, cap * ni * OLF_DESC_BYTES, hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipMemcpyAsync(o->counts, d.counts, ni * sizeof(int), hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipMemcpyAsync(o->uright, d.uright, cap * n_pairs * sizeof(float), hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipMemcpyAsync(o->depth, d.depth, cap * n_pairs * sizeof(float), hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipMemcpyAsync(o->kls, d.kls, lcap * ni * sizeof(olf_keyline), hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipMemcpyAsync(o->ldesc, d.ldesc, lcap * ni * OLF_DESC_BYTES, hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipMemcpyAsync(o->lcounts, d.lcounts, ni * sizeof(int), hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipMemcpyAsync(o->lmatches12, d.lmatches12, lcap * n_pairs * sizeof(int), hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipMemcpyAsync(o->ldisp, d.ldisp, lcap * n_pairs * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipMemcpyAsync(o->lle, d.lle, lcap * n_pairs * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipStreamSynchronize(s));
+    OLF_TRY(fb_copy(c, *o, 0, FB_FIELDS - 1, ni, hipMemcpyDeviceToHost));
+    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
     return check_status(c);
 }
 

@@ -346,7 +346,6 @@ __global__ __launch_bounds__(64) void k_lbd_desc(const LineGeom* __restrict__ gp
 
 // LBD gradient images: GaussianBlur(5x5, sigma 1) then Sobel (computeGaussianPyramid / computeSobel) -- they depend on the input images only, so the
 // fused entry runs them on the ORB stream in the shadow of the seed ordering (api.cpp, schedule 5)
-
 int launch_lbd_dense(const LineGeom& g, const LineDeviceBufs& b, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s)
 {
     OLF_TRY_RC(launch_gauss7_img(d_in, in_pitch, (size_t)in_pitch * g.H, b.lbdBlur, g.pitchW, (size_t)g.pitchW * g.H, g.W, g.H, g, 1, n_images, s));
@@ -355,8 +354,8 @@ int launch_lbd_dense(const LineGeom& g, const LineDeviceBufs& b, const uint8_t* 
     return OLF_OK;
 }
 
-int launch_line_select_lbd(const LineGeom& g, const LineDeviceBufs& b, const uint8_t* d_in, int in_pitch, int n_images,
-                           olf_keyline* d_kls, uint8_t* d_desc, int* d_counts, hipStream_t s, bool denseDone)
+// Lineextractor's top-N by response of the raw key lines
+int launch_line_select(const LineGeom& g, const LineDeviceBufs& b, int n_images, olf_keyline* d_kls, int* d_counts, hipStream_t s)
 {
     int sortN = 64;
     while (sortN < g.maxDetect) sortN <<= 1;
@@ -364,25 +363,13 @@ int launch_line_select_lbd(const LineGeom& g, const LineDeviceBufs& b, const uin
     // maxDetect <= Ps / 48 keeps 8 bytes x the next power of two below that)
     hipLaunchKernelGGL(k_line_select, dim3(n_images), dim3(256), std::min(sortN, LS_LDS_KEYS) * sizeof(unsigned long long), s, b.geom, b.rawLines, b.rawCount, d_kls,
                        d_counts, reinterpret_cast<unsigned long long*>(b.keysA), (size_t)g.Ps / 2);
-    if (!denseDone) OLF_TRY_RC(launch_lbd_dense(g, b, d_in, in_pitch, n_images, s));
-    hipLaunchKernelGGL(k_lbd_prep, dim3((g.outCap + 63) / 64, n_images), dim3(64), 0, s, b.geom, d_kls, d_counts, reinterpret_cast<float2*>(b.lbdStarts));
-    if (g.W + 256 < 32768 && g.H + 256 < 32768)
-        hipLaunchKernelGGL(k_lbd_rows<true>, dim3((g.outCap + 3) / 4, n_images), dim3(256), 0, s, b.geom, b.dxdy, d_kls, d_counts,
-                           reinterpret_cast<const float2*>(b.lbdStarts), reinterpret_cast<float4*>(b.rowSums));
-    else
-        hipLaunchKernelGGL(k_lbd_rows<false>, dim3((g.outCap + 3) / 4, n_images), dim3(256), 0, s, b.geom, b.dxdy, d_kls, d_counts,
-                           reinterpret_cast<const float2*>(b.lbdStarts), reinterpret_cast<float4*>(b.rowSums));
-    hipLaunchKernelGGL(k_lbd_desc, dim3((g.outCap + 63) / 64, n_images), dim3(64), 0, s, b.geom, reinterpret_cast<const float4*>(b.rowSums),
-                       d_counts, d_desc);
     OLF_HIP_CHECK(hipGetLastError());
     return OLF_OK;
 }
 
-// BinaryDescriptor::compute on key lines already in d_kls/d_counts (no LSD, no selection)
-int launch_lbd_only(const LineGeom& g, const LineDeviceBufs& b, const uint8_t* d_in, int in_pitch, int n_images, const olf_keyline* d_kls,
-                    uint8_t* d_desc, const int* d_counts, hipStream_t s)
+// BinaryDescriptor::compute on the key lines in d_kls / d_counts, behind launch_lbd_dense
+int launch_lbd_desc(const LineGeom& g, const LineDeviceBufs& b, int n_images, const olf_keyline* d_kls, uint8_t* d_desc, const int* d_counts, hipStream_t s)
 {
-    OLF_TRY_RC(launch_lbd_dense(g, b, d_in, in_pitch, n_images, s));
     hipLaunchKernelGGL(k_lbd_prep, dim3((g.outCap + 63) / 64, n_images), dim3(64), 0, s, b.geom, d_kls, d_counts, reinterpret_cast<float2*>(b.lbdStarts));
     if (g.W + 256 < 32768 && g.H + 256 < 32768)
         hipLaunchKernelGGL(k_lbd_rows<true>, dim3((g.outCap + 3) / 4, n_images), dim3(256), 0, s, b.geom, b.dxdy, d_kls, d_counts,

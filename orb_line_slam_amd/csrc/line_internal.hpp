@@ -139,17 +139,16 @@ struct LineHostTables {
     int build(const olf_line_params& p, int W, int H, int max_images = 2);
 };
 
-// sortEvent (when set) is recorded in front of the seed ordering (the dense, bandwidth-bound part of the front is through); writeScaled = false: the fused
+// the LSD front in its two halves: the dense, bandwidth-bound one (blur, working image, gradient, sort keys) and the seed order.  writeScaled = false: the
 // k_lsd_upgrad does not write the enlarged working image (nothing behind the fused stereo entry reads it; olf_lsd_debug_scaled needs the stand-alone entry)
-int launch_lsd_front(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s,
-                     hipEvent_t sortEvent, bool writeScaled);
+int launch_lsd_dense(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s, bool writeScaled);
+int launch_lsd_seed_order(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s);
 int launch_lsd_grow(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s);
 int launch_lsd_rect(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s);
+// selection of the key lines, the LBD gradient images (of the input images alone), the descriptors (of both)
+int launch_line_select(const LineGeom& g, const LineDeviceBufs& b, int n_images, olf_keyline* d_kls, int* d_counts, hipStream_t s);
 int launch_lbd_dense(const LineGeom& g, const LineDeviceBufs& b, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s);
-int launch_line_select_lbd(const LineGeom& g, const LineDeviceBufs& b, const uint8_t* d_in, int in_pitch, int n_images,
-                           olf_keyline* d_kls, uint8_t* d_desc, int* d_counts, hipStream_t s, bool denseDone = false);
-int launch_lbd_only(const LineGeom& g, const LineDeviceBufs& b, const uint8_t* d_in, int in_pitch, int n_images, const olf_keyline* d_kls,
-                    uint8_t* d_desc, const int* d_counts, hipStream_t s);
+int launch_lbd_desc(const LineGeom& g, const LineDeviceBufs& b, int n_images, const olf_keyline* d_kls, uint8_t* d_desc, const int* d_counts, hipStream_t s);
 int launch_gauss7_img(const uint8_t* src, int srcPitch, size_t srcStride, uint8_t* dst, int dstPitch, size_t dstStride, int W, int H,
                       const LineGeom& g, int which, int n_images, hipStream_t s);
 int launch_lsd_angle_table(LineDeviceBufs& b, int libmFloat, hipStream_t s);

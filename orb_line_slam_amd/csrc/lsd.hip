@@ -1871,8 +1871,8 @@ LsdPlan lsd_plan(const LineGeom& g, const LineDeviceBufs& b, const LsdOverrides&
     return p;
 }
 
-int launch_lsd_front(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s,
-                     hipEvent_t sortEvent, bool writeScaled)
+// the dense, bandwidth-bound half of the LSD front: blur, working image, gradient, sort keys
+int launch_lsd_dense(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s, bool writeScaled)
 {
     OLF_HIP_CHECK(hipMemsetAsync(b.maxN, 0, (size_t)n_images * 32 * sizeof(int), s));
     OLF_HIP_CHECK(hipMemsetAsync(b.keyCount, 0, (size_t)n_images * 32 * sizeof(int), s));
@@ -1905,7 +1905,12 @@ int launch_lsd_front(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& 
                            b.owner, b.angDeg, nChunks, total);
     }
     OLF_HIP_CHECK(hipGetLastError());
-    if (sortEvent) OLF_HIP_CHECK(hipEventRecord(sortEvent, s));
+    return OLF_OK;
+}
+
+// the other half: the seed order of the keys
+int launch_lsd_seed_order(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s)
+{
     if (p.sort == LsdPlan::Wide) return launch_lsd_sort_wide(g, b, n_images, s, -1, -1, -1, -1);
     if (p.sort == LsdPlan::Seed) return launch_lsd_seedsort(g, b, p, n_images, s, -1, -1, -1);
     return launch_lsd_sort(g, b, n_images, s);

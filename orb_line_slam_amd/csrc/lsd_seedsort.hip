@@ -959,7 +959,7 @@ static int launch_seedsort_mw(const LineGeom& g, const LineDeviceBufs& b, const 
         }
     }
     if (p.sortTop) { const int rc = launch_seedsort_top(g, b, n_images, s, nOverride, kthrOverride, depthOverride); if (rc != OLF_OK) return rc; }
-    // (the groups' seed counts meet in an atomicMax: the counts start at zero -- launch_lsd_front has cleared them; the debug entry, which comes without a front, has not)
+    // (the groups' seed counts meet in an atomicMax: the counts start at zero -- launch_lsd_dense has cleared them; the debug entry, which comes without a front, has not)
     if (p.sortGroups > 1 && nOverride >= 0) OLF_HIP_CHECK(hipMemsetAsync(b.keyCount, 0, (size_t)n_images * 32 * sizeof(int), s));
     hipLaunchKernelGGL((k_lsd_seedsort_mw<NW, NEM>), dim3(n_images * p.sortGroups), dim3(64 * NW), lds, s, b.geom, b.keysA, b.keysB, b.keyCount, b.maxN, b.status,
                        nOverride, kthrOverride, depthOverride, n_images, p.sortTop ? b.topBuf : (int*)nullptr, p.sortGroups);
