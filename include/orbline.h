@@ -254,7 +254,7 @@ int olf_match_bf(olf_ctx* ctx, const uint8_t* descA, int nA, const uint8_t* desc
 int olf_knn2(olf_ctx* ctx, const uint8_t* descQ, int nQ, const uint8_t* descT, int nT, int32_t* idx0, int32_t* dist0, int32_t* dist1);
 /* Candidate-list distances for ORBmatcher::SearchByProjection (src/ORBmatcher.cc:1330-1472) / SearchByBoW (:161-290):
  * query i is compared with train rows cand_idx[cand_offsets[i] .. cand_offsets[i+1]) (CSR, built by the caller from
- * Frame::GetFeaturesInArea / the BoW feature vectors); dist[k] receives the Hamming distance of pair k (0xffff for an
+ * Frame::GetFeaturesInArea -- on the device: olf_features_in_area_dev -- / the BoW feature vectors); dist[k] receives the Hamming distance of pair k (0xffff for an
  * out-of-range index).  The order-dependent greedy resolution stays with the caller. */
 int olf_match_candidates_dev(olf_ctx* ctx, const uint8_t* d_descQ, int nQ, const uint8_t* d_descT, int nT, const int32_t* d_cand_offsets,
                              const int32_t* d_cand_idx, uint16_t* d_dist, void* stream);
@@ -266,7 +266,8 @@ int olf_match_candidates(olf_ctx* ctx, const uint8_t* descQ, int nQ, const uint8
  * searches that assign map points to the current frame update them in place, as the reference updates mvpMapPoints.
  * Constness: the entry points take `const olf_frame_view*` -- the VIEW (its pointers and counts) is never modified; mp_valid and mp_obs are
  * deliberately pointers to non-const bytes, because for the current frame they are outputs (each function's comment names what it updates).
- * Every other array is read-only. */
+ * Every other array is read-only.  A supplied grid (grid_offsets / grid_index) is checked in O(OLF_GRID_CELLS + n) before a search walks it --
+ * offsets monotone from 0, the last one <= n, indices in [0, n) -- and a grid that fails is OLF_ERR_INVALID. */
 typedef struct olf_frame_view {
     const olf_keypoint* keys;     /* mvKeysUn (= mvKeys for a rectified camera, src/Frame.cc:601-605)            */
     const uint8_t* desc;          /* mDescriptors [n][32]                                                        */
@@ -288,6 +289,8 @@ typedef struct olf_frame_view {
     const int32_t* fv_offsets;    /*   offsets [fv_n + 1],                                                       */
     const int32_t* fv_features;   /*   feature indices                                                           */
     int32_t        fv_n;
+    const int32_t* grid_offsets;  /* mGrid, prebuilt (olf_frame_grid; layout in orbline_types.h): [OLF_GRID_CELLS + 1] and              */
+    const int32_t* grid_index;    /*   [grid_offsets[OLF_GRID_CELLS]], host pointers.  NULL: the search builds the grid from `keys` itself */
 } olf_frame_view;
 /* int ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, const float th, const bool bMono), src/ORBmatcher.cc:1330-1472
  * (Tracking::TrackWithMotionModel, every frame).  matches[i2] = index of the LastFrame feature whose map point CurrentFrame feature i2
@@ -415,6 +418,39 @@ typedef struct olf_frame_buffers {
  * device pointers for the _dev form, host pointers otherwise. */
 int olf_stereo_frames_dev(olf_ctx* ctx, const uint8_t* d_images, int n_pairs, const olf_frame_buffers* out, void* stream);
 int olf_stereo_frames(olf_ctx* ctx, const uint8_t* images, int n_pairs, const olf_frame_buffers* out);
+
+/* ---- Frame::mGrid and Frame::GetFeaturesInArea on the device (layout: orbline_types.h, "Frame::mGrid as two arrays") --------------------
+ * void Frame::AssignFeaturesToGrid() (src/Frame.cc:334-349, PosInGrid :572-582; called by Frame::Frame at :215) for n_frames frames: frame j is
+ * image j * img_stride of the key point / count buffers of olf_orb_extract_dev / olf_stereo_frames_dev (stride olf_orb_capacity(); img_stride 2 =
+ * the left images of a stereo batch -- the convention of olf_search_by_bow_batch_dev).  Called on the stream given to olf_stereo_frames_dev right
+ * after that call it delivers the batch's mGrid: the point outputs are final on that stream, with or without the deferred join.  The bounds are
+ * mnMinX .. mnMaxY; the caller passes undistorted key points (mvKeysUn) -- what the extractor returns for a rectified camera (src/Frame.cc:601-605).
+ * wInv = 64.f / (maxX - minX) and hInv = 48.f / (maxY - minY) are formed once in float (:186-187); posX = round((x - minX) * wInv), C round() on the
+ * float product; a feature is kept iff 0 <= posX < 64 && 0 <= posY < 48.  d_cell_offsets [n_frames][OLF_GRID_CELLS + 1]; d_cell_index
+ * [n_frames][olf_orb_capacity()].  A count beyond the capacity is read as the capacity.  Contexts whose olf_orb_capacity() exceeds
+ * OLF_GRID_MAX_KEYS are refused (OLF_ERR_CAPACITY); maxX <= minX or maxY <= minY is OLF_ERR_INVALID. */
+int olf_frame_grid_dev(olf_ctx* ctx, int n_frames, int img_stride, const olf_keypoint* d_kps, const int32_t* d_counts, float minX, float maxX,
+                       float minY, float maxY, int32_t* d_cell_offsets, int32_t* d_cell_index, void* stream);
+/* host buffers, one frame of n <= OLF_GRID_MAX_KEYS key points (more: OLF_ERR_CAPACITY; n == 0 gives all-zero offsets): uploads, runs the same kernel,
+ * downloads.  cell_offsets [OLF_GRID_CELLS + 1], cell_index [n]. */
+int olf_frame_grid(olf_ctx* ctx, const olf_keypoint* keys, int n, float minX, float maxX, float minY, float maxY, int32_t* cell_offsets,
+                   int32_t* cell_index);
+/* vector<size_t> Frame::GetFeaturesInArea(x, y, r, minLevel, maxLevel) (src/Frame.cc:517-570) for n_queries queries on one frame's key points and
+ * grid: exactly the CSR olf_match_candidates_dev consumes -- d_cand_idx[d_cand_offsets[q] .. d_cand_offsets[q + 1]) is the reference's vIndices of query
+ * q in the reference's order (ix outer, iy inner, stored order inside a cell).  d_cand_offsets [n_queries + 1] is always complete, so a caller can size
+ * a retry; nothing is written at or past cand_capacity, and a total beyond it sets the context's capacity flag (olf_ctx_synchronize /
+ * olf_ctx_poll_status, as for olf_frames_pack_dev). */
+int olf_features_in_area_dev(olf_ctx* ctx, const olf_keypoint* d_keys, const int32_t* d_cell_offsets, const int32_t* d_cell_index, float minX, float maxX,
+                             float minY, float maxY, int n_queries, const olf_area_query* d_queries, int32_t* d_cand_offsets, int32_t* d_cand_idx,
+                             int cand_capacity, void* stream);
+/* host buffers (n_keys key points; the grid is checked as the searches check a supplied one): OLF_ERR_CAPACITY when cand_capacity is too small --
+ * cand_offsets is complete then and cand_idx holds the first cand_capacity entries. */
+int olf_features_in_area(olf_ctx* ctx, const olf_keypoint* keys, int n_keys, const int32_t* cell_offsets, const int32_t* cell_index, float minX,
+                         float maxX, float minY, float maxY, int n_queries, const olf_area_query* queries, int32_t* cand_offsets, int32_t* cand_idx,
+                         int cand_capacity);
+/* The context's own device arrays, which the host-pointer entry points stage through: after olf_stereo_frames / olf_stereo_points / olf_orb_extract they
+ * hold that call's results (until the next host-pointer call), so a *_dev entry can go on from them without another upload. */
+int olf_ctx_device_buffers(const olf_ctx* ctx, olf_frame_buffers* out);
 
 /* getLineCoords(x1, y1, x2, y2, line_coords), src/gridStructure.cpp:33-41: cells of the reference's Bresenham walk (src/LineIterator.cpp), host
  * arithmetic.  xy receives up to cap (x, y) pairs, *n the number of cells. */

@@ -9,6 +9,7 @@
 //   matchGrid(points1 | lines1, desc1, grid, desc2, [directions2,] w, matches_12)    src/Frame.cc:926            (include/LineMatcher.h:66-69)
 //   GridStructure / GridWindow / getLineCoords                                       include/gridStructure.h:33-58
 //   StereoFrameFeatures(frame, imLeft, imRight)  = the feature part of Frame::Frame  src/Frame.cc:164-171,199-207
+//   FrameGrid(frame)                             = AssignFeaturesToGrid()            src/Frame.cc:215            (:334-349)
 //   and every other ORBmatcher call of the reference: SearchByProjection(cur, pKF, sFound, th, ORBdist) Tracking.cc:2322,2336;
 //   SearchForTriangulation LocalMapping.cc:268; Fuse(pKF, vpMapPoints[, th]) LocalMapping.cc:489,514; SearchByBoW(pKF1, pKF2, vpMatches12)
 //   LoopClosing.cc:271; SearchBySim3 LoopClosing.cc:329; SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) LoopClosing.cc:381;
@@ -596,6 +597,42 @@ int matchGrid(const std::vector<line_2d>& lines1, const MatT& desc1, const GridS
                                        [&](int i1, int i2) { return !(std::abs(v1[i1].first * directions2[i2].first + v1[i1].second * directions2[i2].second) < sim); },
                                        matches_12);
 }
+
+// ---- void Frame::AssignFeaturesToGrid() (src/Frame.cc:334-349; called by Frame::Frame at :215, after UndistortKeyPoints) ----------------------------------
+// Fills F.mGrid[i][j] (std::vector<std::size_t> mGrid[FRAME_GRID_COLS][FRAME_GRID_ROWS], include/Frame.h:228) from olf_frame_grid: reads F.mvKeysUn and
+// F.mnMinX .. F.mnMaxY, nothing else.  Every cell is assigned, so a frame that is filled twice does not accumulate.  More than OLF_GRID_MAX_KEYS key
+// points throw (OLF_ERR_CAPACITY).  Frame::GetFeaturesInArea then works on the member as in the reference; the searches of this header do not read it --
+// a caller that wants them to skip their own rebuild flattens it with olf_detail::GridCSR and attaches that to the view it passes to the C ABI.
+template <class FrameT> void FrameGrid(FrameT& F)
+{
+    const int n = (int)F.mvKeysUn.size();
+    std::vector<int32_t> offs(OLF_GRID_CELLS + 1, 0), idx((size_t)(n > 0 ? n : 1));
+    olf_detail::check(olf_frame_grid(olf_detail::thread_ctx(), n ? olf_detail::keypoints(F.mvKeysUn) : nullptr, n, (float)F.mnMinX, (float)F.mnMaxX,
+                                     (float)F.mnMinY, (float)F.mnMaxY, offs.data(), idx.data()), "olf_frame_grid");
+    for (int i = 0; i < OLF_GRID_COLS; ++i)
+        for (int j = 0; j < OLF_GRID_ROWS; ++j) {
+            const int e = i * OLF_GRID_ROWS + j;
+            F.mGrid[i][j].assign(idx.begin() + offs[e], idx.begin() + offs[e + 1]);
+        }
+}
+
+namespace olf_detail {
+// F.mGrid flattened into the two arrays of orbline_types.h ("Frame::mGrid as two arrays"), e.g. for olf_frame_view::grid_offsets / grid_index
+struct GridCSR {
+    std::vector<int32_t> offs, idx;
+    template <class FrameT> explicit GridCSR(const FrameT& F)
+    {
+        offs.reserve(OLF_GRID_CELLS + 1);
+        offs.push_back(0);
+        for (int i = 0; i < OLF_GRID_COLS; ++i)
+            for (int j = 0; j < OLF_GRID_ROWS; ++j) {
+                for (size_t k = 0; k < F.mGrid[i][j].size(); ++k) idx.push_back((int32_t)F.mGrid[i][j][k]);
+                offs.push_back((int32_t)idx.size());
+            }
+    }
+    void attach(olf_frame_view& v) const { v.grid_offsets = offs.data(); v.grid_index = idx.data(); }
+};
+}  // namespace olf_detail
 
 // ---- the feature part of Frame::Frame(imLeft, imRight, ...) (src/Frame.cc:136-221) as one call -------------------------------------------
 // Replaces the four extraction threads (:164-171), ComputeStereoMatches (:202) and ComputeStereoMatches_Lines (:205): fills mvKeys,

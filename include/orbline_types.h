@@ -23,6 +23,16 @@ extern "C" {
 #define OLF_MAX_LEVELS 16
 #define OLF_GRID_COLS 64       /* include/Frame.h:51 FRAME_GRID_COLS                  */
 #define OLF_GRID_ROWS 48       /* include/Frame.h:52 FRAME_GRID_ROWS                  */
+#define OLF_GRID_CELLS 3072    /* OLF_GRID_COLS * OLF_GRID_ROWS                       */
+#define OLF_GRID_MAX_KEYS 8192 /* key points per frame olf_frame_grid* sorts (their cells sit in LDS) */
+/* Frame::mGrid as two arrays (std::vector<std::size_t> mGrid[FRAME_GRID_COLS][FRAME_GRID_ROWS], include/Frame.h:228; filled by
+ * Frame::AssignFeaturesToGrid, src/Frame.cc:334-349) -- the one definition every producer and consumer of a grid cites:
+ *   int32 cell_offsets[OLF_GRID_CELLS + 1], int32 cell_index[cell_offsets[OLF_GRID_CELLS]]
+ *   - cell (ix, iy) = mGrid[ix][iy] is entry ix * OLF_GRID_ROWS + iy: its features are cell_index[cell_offsets[e] .. cell_offsets[e + 1]), so the
+ *     cells iy0 .. iy1 of one column are one contiguous range;
+ *   - inside a cell the feature indices ascend (the reference's push_back order);
+ *   - a feature whose PosInGrid (src/Frame.cc:572-582) is false is in no cell: cell_offsets[OLF_GRID_CELLS] <= N;
+ *   - entries of cell_index past cell_offsets[OLF_GRID_CELLS] are unspecified. */
 
 typedef struct olf_keypoint {
     float x, y;        /* pt, level-0 pixel coordinates                                 */
@@ -45,6 +55,12 @@ typedef struct olf_keyline {
     float lineLength;
     int32_t numOfPixels;
 } olf_keyline;
+
+/* one call of Frame::GetFeaturesInArea(x, y, r, minLevel, maxLevel), src/Frame.cc:517-570 (include/Frame.h:117: the levels default to -1, -1) */
+typedef struct olf_area_query {
+    float x, y, r;
+    int32_t min_level, max_level;
+} olf_area_query;
 
 /* ORBextractor ctor arguments, src/ORBextractor.cc:412-416; values from
  * Examples/PL/PL_KITTI00-02.yaml:42-55 are the defaults of olf_default_params(). */

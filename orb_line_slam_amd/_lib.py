@@ -62,7 +62,14 @@ class FrameViewC(C.Structure):
                 [(n, C.c_void_p) for n in ("mp_valid", "mp_obs", "mp_bad", "mp_world", "mp_desc", "outlier", "Tcw")] +
                 [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "mbf", "minX", "maxX", "minY", "maxY")] +
                 [("scale_factors", C.c_void_p), ("n_levels", C.c_int32)] +
-                [(n, C.c_void_p) for n in ("mp_maxd", "mp_mind", "fv_nodes", "fv_offsets", "fv_features")] + [("fv_n", C.c_int32)])
+                [(n, C.c_void_p) for n in ("mp_maxd", "mp_mind", "fv_nodes", "fv_offsets", "fv_features")] + [("fv_n", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("grid_offsets", "grid_index")])
+
+
+# Frame::mGrid as two int32 arrays (include/orbline_types.h) and one Frame::GetFeaturesInArea call
+GRID_COLS, GRID_ROWS, GRID_CELLS, GRID_MAX_KEYS = 64, 48, 3072, 8192
+AREA_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("r", "<f4"), ("min_level", "<i4"), ("max_level", "<i4")])
+assert AREA_QUERY_DTYPE.itemsize == 20
 
 
 class OlfError(RuntimeError):
@@ -145,6 +152,12 @@ def lib():
         L.olf_search_local_map.argtypes = [C.c_void_p, C.POINTER(FrameViewC), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         L.olf_match_candidates_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.olf_frame_grid_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p] * 3
+        L.olf_frame_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_float] * 4 + [C.c_void_p] * 2
+        L.olf_features_in_area_dev.argtypes = ([C.c_void_p] * 4 + [C.c_float] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p])
+        L.olf_features_in_area.argtypes = ([C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_float] * 4 +
+                                           [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int])
+        L.olf_ctx_device_buffers.argtypes = [C.c_void_p, C.POINTER(FrameBuffers)]
         L.olf_cvt_gray.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.olf_remap_linear.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.olf_debug_lsd_waves.argtypes = [C.c_void_p, C.c_int, C.c_int]

@@ -545,7 +545,7 @@ static int check_status(olf_ctx* c)
     if (st[0]) {
         (void)hipMemset(c->ob.status, 0, 16);
         set_error("device capacity overflow, flags=" + std::to_string(st[0]) +
-                  " (1/2/4: ORB corner / candidate / key point buffers, 8: LSD regions, segments or pixel-list pool, 16: LSD growth watchdog, 32: frame record buffer, 64: LSD seed sort, final-range list of the grid-wide top levels)");
+                  " (1/2/4: ORB corner / candidate / key point buffers, 8: LSD regions, segments or pixel-list pool, 16: LSD growth watchdog, 32: frame record buffer, 64: LSD seed sort, final-range list of the grid-wide top levels, 128: candidate list of olf_features_in_area_dev)");
         return OLF_ERR_CAPACITY;
     }
     return OLF_OK;
@@ -934,6 +934,106 @@ int olf_match_candidates(olf_ctx* c, const uint8_t* descQ, int nQ, const uint8_t
     OLF_TRY(olf_match_candidates_dev(c, dQ, nQ, dT, nT, dO, dC, dD, c->stream));
     OLF_HIP_CHECK(hipMemcpyAsync(dist, dD, (size_t)nnz * 2, hipMemcpyDeviceToHost, c->stream));
     OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return OLF_OK;
+}
+
+// ---- Frame::mGrid (grid.hip) -----------------------------------------------------------------------------------------------------------
+// mfGridElementWidthInv / mfGridElementHeightInv, src/Frame.cc:186-187: static_cast<float>(FRAME_GRID_COLS) / (mnMaxX - mnMinX), in float
+static bool grid_scales(float minX, float maxX, float minY, float maxY, float* wInv, float* hInv)
+{
+    if (!(maxX > minX) || !(maxY > minY)) return false;
+    *wInv = static_cast<float>(OLF_GRID_COLS) / (maxX - minX);
+    *hInv = static_cast<float>(OLF_GRID_ROWS) / (maxY - minY);
+    return true;
+}
+
+int olf_frame_grid_dev(olf_ctx* c, int n_frames, int img_stride, const olf_keypoint* d_kps, const int32_t* d_counts, float minX, float maxX, float minY,
+                       float maxY, int32_t* d_cell_offsets, int32_t* d_cell_index, void* stream)
+{
+    float wInv, hInv;
+    if (!c || n_frames < 0 || img_stride < 1 || !d_kps || !d_counts || !d_cell_offsets || !d_cell_index || !grid_scales(minX, maxX, minY, maxY, &wInv, &hInv)) {
+        set_error("olf_frame_grid_dev: bad argument"); return OLF_ERR_INVALID;
+    }
+    OLF_TRY(check_device(c, "olf_frame_grid_dev"));
+    const int cap = c->orb.geom.outCap;
+    if (cap > OLF_GRID_MAX_KEYS) { set_error("olf_frame_grid_dev: more than OLF_GRID_MAX_KEYS key points per frame (their cells sit in LDS)"); return OLF_ERR_CAPACITY; }
+    return launch_assign_grid(d_kps, (size_t)img_stride * cap, d_counts, img_stride, 0, cap, minX, minY, wInv, hInv, n_frames, d_cell_offsets, d_cell_index,
+                              (size_t)cap, stream ? (hipStream_t)stream : c->stream);
+}
+
+int olf_frame_grid(olf_ctx* c, const olf_keypoint* keys, int n, float minX, float maxX, float minY, float maxY, int32_t* cell_offsets, int32_t* cell_index)
+{
+    float wInv, hInv;
+    if (!c || n < 0 || (n && (!keys || !cell_index)) || !cell_offsets || !grid_scales(minX, maxX, minY, maxY, &wInv, &hInv)) {
+        set_error("olf_frame_grid: bad argument"); return OLF_ERR_INVALID;
+    }
+    if (n > OLF_GRID_MAX_KEYS) { set_error("olf_frame_grid: more than OLF_GRID_MAX_KEYS key points"); return OLF_ERR_CAPACITY; }
+    OLF_TRY(check_device(c, "olf_frame_grid"));
+    void* st = nullptr;
+    const size_t bK = ((size_t)std::max(n, 1) * sizeof(olf_keypoint) + 15) & ~(size_t)15, bO = ((size_t)(OLF_GRID_CELLS + 1) * 4 + 15) & ~(size_t)15;
+    OLF_TRY(scratch_get(c, 1, bK + bO + (size_t)std::max(n, 1) * 4, &st));
+    olf_keypoint* dK = (olf_keypoint*)st; int* dO = (int*)((uint8_t*)st + bK); int* dI = (int*)((uint8_t*)dO + bO);
+    if (n) OLF_HIP_CHECK(hipMemcpyAsync(dK, keys, (size_t)n * sizeof(olf_keypoint), hipMemcpyHostToDevice, c->stream));
+    OLF_TRY(launch_assign_grid(dK, 0, nullptr, 0, n, n, minX, minY, wInv, hInv, 1, dO, dI, (size_t)std::max(n, 1), c->stream));
+    OLF_HIP_CHECK(hipMemcpyAsync(cell_offsets, dO, (size_t)(OLF_GRID_CELLS + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
+    const int used = cell_offsets[OLF_GRID_CELLS];
+    if (used > 0) OLF_HIP_CHECK(hipMemcpy(cell_index, dI, (size_t)used * 4, hipMemcpyDeviceToHost));
+    return OLF_OK;
+}
+
+int olf_features_in_area_dev(olf_ctx* c, const olf_keypoint* d_keys, const int32_t* d_cell_offsets, const int32_t* d_cell_index, float minX, float maxX,
+                             float minY, float maxY, int n_queries, const olf_area_query* d_queries, int32_t* d_cand_offsets, int32_t* d_cand_idx,
+                             int cand_capacity, void* stream)
+{
+    float wInv, hInv;
+    if (!c || n_queries < 0 || cand_capacity < 0 || !d_cell_offsets || !d_cand_offsets || (n_queries && !d_queries) || (cand_capacity && !d_cand_idx) ||
+        !grid_scales(minX, maxX, minY, maxY, &wInv, &hInv)) {
+        set_error("olf_features_in_area_dev: bad argument"); return OLF_ERR_INVALID;
+    }
+    OLF_TRY(check_device(c, "olf_features_in_area_dev"));
+    return launch_features_in_area(d_keys, d_cell_offsets, d_cell_index, minX, minY, wInv, hInv, n_queries, d_queries, d_cand_offsets, d_cand_idx,
+                                   cand_capacity, c->ob.status, stream ? (hipStream_t)stream : c->stream);
+}
+
+int olf_features_in_area(olf_ctx* c, const olf_keypoint* keys, int n_keys, const int32_t* cell_offsets, const int32_t* cell_index, float minX, float maxX,
+                         float minY, float maxY, int n_queries, const olf_area_query* queries, int32_t* cand_offsets, int32_t* cand_idx, int cand_capacity)
+{
+    if (!c || n_keys < 0 || (n_keys && !keys) || n_queries < 0 || cand_capacity < 0 || !cand_offsets || (n_queries && !queries) || (cand_capacity && !cand_idx) ||
+        !(maxX > minX) || !(maxY > minY)) {
+        set_error("olf_features_in_area: bad argument"); return OLF_ERR_INVALID;
+    }
+    if (!grid_is_valid(cell_offsets, cell_index, n_keys)) { set_error("olf_features_in_area: the grid does not describe n_keys features"); return OLF_ERR_INVALID; }
+    OLF_TRY(check_device(c, "olf_features_in_area"));
+    const int used = cell_offsets[OLF_GRID_CELLS];
+    auto up16 = [](size_t b) { return (std::max<size_t>(b, 1) + 15) & ~(size_t)15; };
+    const size_t bK = up16((size_t)n_keys * sizeof(olf_keypoint)), bO = up16((size_t)(OLF_GRID_CELLS + 1) * 4), bI = up16((size_t)used * 4),
+                 bQ = up16((size_t)n_queries * sizeof(olf_area_query)), bCO = up16((size_t)(n_queries + 1) * 4), bC = up16((size_t)cand_capacity * 4);
+    void* st = nullptr;
+    OLF_TRY(scratch_get(c, 1, bK + bO + bI + bQ + bCO + bC, &st));
+    uint8_t* p = (uint8_t*)st;
+    olf_keypoint* dK = (olf_keypoint*)p; p += bK;
+    int* dO = (int*)p; p += bO;
+    int* dI = (int*)p; p += bI;
+    olf_area_query* dQ = (olf_area_query*)p; p += bQ;
+    int* dCO = (int*)p; p += bCO;
+    int* dC = (int*)p;
+    if (n_keys) OLF_HIP_CHECK(hipMemcpyAsync(dK, keys, (size_t)n_keys * sizeof(olf_keypoint), hipMemcpyHostToDevice, c->stream));
+    OLF_HIP_CHECK(hipMemcpyAsync(dO, cell_offsets, (size_t)(OLF_GRID_CELLS + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    if (used) OLF_HIP_CHECK(hipMemcpyAsync(dI, cell_index, (size_t)used * 4, hipMemcpyHostToDevice, c->stream));
+    if (n_queries) OLF_HIP_CHECK(hipMemcpyAsync(dQ, queries, (size_t)n_queries * sizeof(olf_area_query), hipMemcpyHostToDevice, c->stream));
+    OLF_TRY(olf_features_in_area_dev(c, dK, dO, dI, minX, maxX, minY, maxY, n_queries, dQ, dCO, dC, cand_capacity, c->stream));
+    OLF_HIP_CHECK(hipMemcpyAsync(cand_offsets, dCO, (size_t)(n_queries + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
+    const int have = std::min(cand_offsets[n_queries], cand_capacity);
+    if (have > 0) OLF_HIP_CHECK(hipMemcpy(cand_idx, dC, (size_t)have * 4, hipMemcpyDeviceToHost));
+    return check_status(c);
+}
+
+int olf_ctx_device_buffers(const olf_ctx* c, olf_frame_buffers* out)
+{
+    if (!c || !out) { set_error("olf_ctx_device_buffers: null argument"); return OLF_ERR_INVALID; }
+    *out = c->d_out;
     return OLF_OK;
 }
 

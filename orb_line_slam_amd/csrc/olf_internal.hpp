@@ -178,4 +178,14 @@ int launch_match_candidates(const uint8_t* q, int nQ, const uint8_t* t, int nT, 
 int launch_distinctive(const uint8_t* desc, const int* offs, int n_points, int* best, hipStream_t s);
 int launch_hamming_matrix(const uint8_t* a, int nA, const uint8_t* b, int nB, uint16_t* out, hipStream_t s);
 
+
+// grid.hip
+int launch_assign_grid(const olf_keypoint* d_kps, size_t frame_stride, const int* d_counts, int count_stride, int n_fixed, int n_limit, float minX,
+                       float minY, float wInv, float hInv, int n_frames, int* d_cell_offsets, int* d_cell_index, size_t index_stride, hipStream_t s);
+int launch_features_in_area(const olf_keypoint* d_keys, const int* d_cell_offsets, const int* d_cell_index, float minX, float minY, float wInv, float hInv,
+                            int n_queries, const olf_area_query* d_queries, int* d_cand_offsets, int* d_cand_idx, int cand_capacity, int* d_status,
+                            hipStream_t s);
+// a caller-supplied Frame::mGrid (layout: orbline_types.h) for n features, checked in O(OLF_GRID_CELLS + n): offsets monotone from 0, last <= n, indices in [0, n)
+bool grid_is_valid(const int32_t* cell_offsets, const int32_t* cell_index, int n);
+
 }  // namespace olf

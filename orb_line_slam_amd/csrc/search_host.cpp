@@ -23,29 +23,40 @@
 namespace {
 using namespace olf;
 constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;          // src/ORBmatcher.cc:39-41
-constexpr int GRID_COLS = 64, GRID_ROWS = 48;                          // FRAME_GRID_COLS / FRAME_GRID_ROWS, include/Frame.h:43-44
+constexpr int GRID_COLS = OLF_GRID_COLS, GRID_ROWS = OLF_GRID_ROWS;      // FRAME_GRID_COLS / FRAME_GRID_ROWS, include/Frame.h:51-52
 
-// Frame::mGrid (src/Frame.cc:334-349) as one index array: the features of cell (ix, iy) are cell[ix * GRID_ROWS + iy] .. [+1), in
-// feature order -- the order push_back gives them in the reference.
+// Frame::mGrid (src/Frame.cc:334-349) as one index array (layout: include/orbline_types.h): the features of cell (ix, iy) are
+// item[cell[ix * GRID_ROWS + iy]] .. [+1), in feature order -- the order push_back gives them in the reference.  A view that carries a prebuilt grid
+// (grid_offsets / grid_index, e.g. from olf_frame_grid) is walked as it is once checked (ok == false: the search returns OLF_ERR_INVALID); otherwise the
+// grid is built here from the key points.
 struct Grid {
     const olf_frame_view& f;
     float wInv, hInv;
-    std::vector<int> cell, item;
+    std::vector<int> built_cell, built_item;
+    const int32_t* cell;
+    const int32_t* item;
+    bool ok = true;
     explicit Grid(const olf_frame_view& fr) : f(fr)
     {
         wInv = static_cast<float>(GRID_COLS) / (f.maxX - f.minX);      // mfGridElementWidthInv, src/Frame.cc:186-187
         hInv = static_cast<float>(GRID_ROWS) / (f.maxY - f.minY);
+        if (f.grid_offsets || f.grid_index) {
+            cell = f.grid_offsets; item = f.grid_index;
+            ok = grid_is_valid(cell, item, f.n);
+            return;
+        }
         std::vector<int> where((size_t)std::max(f.n, 0));
-        cell.assign(GRID_COLS * GRID_ROWS + 1, 0);
+        built_cell.assign(GRID_COLS * GRID_ROWS + 1, 0);
         for (int i = 0; i < f.n; ++i) {                                 // PosInGrid, src/Frame.cc:572-582
             const int posX = (int)std::round((f.keys[i].x - f.minX) * wInv), posY = (int)std::round((f.keys[i].y - f.minY) * hInv);
             where[i] = (posX < 0 || posX >= GRID_COLS || posY < 0 || posY >= GRID_ROWS) ? -1 : posX * GRID_ROWS + posY;
-            if (where[i] >= 0) ++cell[where[i] + 1];
+            if (where[i] >= 0) ++built_cell[where[i] + 1];
         }
-        for (int c = 0; c < GRID_COLS * GRID_ROWS; ++c) cell[c + 1] += cell[c];
-        item.resize(cell.back());
-        std::vector<int> fill(cell.begin(), cell.end() - 1);
-        for (int i = 0; i < f.n; ++i) if (where[i] >= 0) item[fill[where[i]]++] = i;
+        for (int c = 0; c < GRID_COLS * GRID_ROWS; ++c) built_cell[c + 1] += built_cell[c];
+        built_item.resize(built_cell.back());
+        std::vector<int> fill(built_cell.begin(), built_cell.end() - 1);
+        for (int i = 0; i < f.n; ++i) if (where[i] >= 0) built_item[fill[where[i]]++] = i;
+        cell = built_cell.data(); item = built_item.data();
     }
     // Frame::GetFeaturesInArea: appends the indices to `out`, returns how many
     int area(float x, float y, float r, int minLevel, int maxLevel, std::vector<int>& out) const
@@ -128,6 +139,7 @@ void rot_apply(const float* T, const float* v, float alpha_t, float* out)     //
     for (int r = 0; r < 3; ++r) out[r] = (float)((double)dot3_small(T + 4 * r, v) + (double)alpha_t * (double)T[4 * r + 3]);
 }
 
+int bad_grid() { set_error("the view's grid_offsets / grid_index do not describe its n features (orbline_types.h: Frame::mGrid as two arrays)"); return OLF_ERR_INVALID; }
 bool bad_view(const olf_frame_view* f, bool needs_pose)
 {
     return !f || f->n < 0 || (f->n && (!f->keys || !f->desc)) || (needs_pose && !f->Tcw);
@@ -161,6 +173,7 @@ int search_by_projection_frames(olf_ctx* c, const olf_frame_view* cur, const olf
     const bool bForward = tlc[2] > mb && !bMono, bBackward = -tlc[2] > mb && !bMono;
 
     const Grid grid(*cur);
+    if (!grid.ok) return bad_grid();
     Batch q;
     struct Meta { float u, invzc, radius; };
     std::vector<Meta> meta;
@@ -252,6 +265,7 @@ int olf_search_for_initialization(olf_ctx* c, const olf_frame_view* f1, const ol
     *nmatches = 0;
     // candidate lists: GetFeaturesInArea(vbPrevMatched[i1], windowSize, level1, level1) for the level-0 key points of F1   (:421-429)
     const Grid grid(*f2);
+    if (!grid.ok) return bad_grid();
     Batch q;
     for (int i1 = 0; i1 < f1->n; ++i1) {
         const int level1 = f1->keys[i1].octave;
@@ -369,6 +383,7 @@ int olf_search_local_map(olf_ctx* c, const olf_frame_view* f, int n_mp, const ui
     *nmatches = 0;
     const bool bFactor = th != 1.0;
     const Grid grid(*f);
+    if (!grid.ok) return bad_grid();
     Batch q;
     std::vector<float> radii;
     for (int iMP = 0; iMP < n_mp; ++iMP) {
@@ -531,6 +546,7 @@ int olf_search_by_projection_kf(olf_ctx* c, const olf_frame_view* cur, const olf
     camera_centre(cur->Tcw, Ow);
     const float logSF = log_scale_factor(*cur);
     const Grid grid(*cur);
+    if (!grid.ok) return bad_grid();
     Batch q;
     for (int i = 0; i < kf->n; ++i) {
         if (!kf->mp_valid[i]) continue;
@@ -742,6 +758,7 @@ int fuse_core(olf_ctx* c, const char* who, const olf_frame_view* kf, const float
     if (bad_levels(kf)) { set_error(std::string(who) + ": n_levels / scale_factors missing"); return OLF_ERR_INVALID; }
     const float logSF = log_scale_factor(*kf);
     const Grid grid(*kf);
+    if (!grid.ok) return bad_grid();
     Batch q;
     struct Meta { float u, v, ur; int level; };
     std::vector<Meta> meta;
@@ -890,6 +907,7 @@ int olf_search_by_sim3(olf_ctx* c, const olf_frame_view* kf1, const olf_frame_vi
         int32_t* out = dir ? vn_match2 : vn_match1;
         for (int i = 0; i < src.n; ++i) out[i] = -1;
         const Grid grid(dst);
+        if (!grid.ok) return bad_grid();
         Batch q;
         std::vector<int> levels;
         for (int i = 0; i < src.n; ++i) {

@@ -40,6 +40,7 @@ class StereoFrontEnd:
         self.params = params or _lib.default_params()
         self.ctx = _lib.Context(self.params, width, height, 2 * max_pairs)
         self.width, self.height, self.max_pairs = width, height, max_pairs
+        self._last_images = 0          # images of the last frames() call: what the context's device buffers hold (frame_grid)
 
     def stereo_points(self, images):
         """images: (2*n_pairs, H, W) uint8, image 2p = left, 2p+1 = right (host memory)."""
@@ -108,4 +109,74 @@ class StereoFrontEnd:
         f.mvKeys_Line, f.mvKeysRight_Line = kls[0::2], kls[1::2]
         f.mDescriptors_Line, f.mDescriptorsRight_Line = ldesc[0::2], ldesc[1::2]
         f.line_matches_12, f.mvDisparity_l, f.mvle_l = lm, ldisp, lle
+        self._last_images = 2 * n_pairs
         return f
+
+    def frame_grid(self, bounds=None, img_stride=2, counts=None, fill=None, n_frames=None):
+        """Frame::mGrid (AssignFeaturesToGrid, src/Frame.cc:334-349) of the frames of the last frames() call, built by olf_frame_grid_dev on the
+        context's device buffers -- the key points are not uploaded again.  Frame j is image j * img_stride (2: the left images).  bounds =
+        (mnMinX, mnMaxX, mnMinY, mnMaxY), default the image (0, width, 0, height).  counts: an int32 array over ALL images of the call that
+        replaces the device counts (N per image; a frame can be shortened or emptied); fill: value the output arrays hold before the call;
+        n_frames: build the first n_frames grids only (the rows of the others keep the fill value).
+        Returns (cell_offsets [frames, 3073], cell_index [frames, capacity]) -- layout in include/orbline_types.h."""
+        import torch
+        n_images = self._last_images
+        if not n_images:
+            raise RuntimeError("frame_grid: no frames() call to take the key points from")
+        all_frames = (n_images + img_stride - 1) // img_stride
+        n_frames = all_frames if n_frames is None else int(n_frames)
+        if not 0 <= n_frames <= all_frames:
+            raise ValueError("frame_grid: n_frames exceeds the frames of the last frames() call")
+        minX, maxX, minY, maxY = (0.0, float(self.width), 0.0, float(self.height)) if bounds is None else (float(v) for v in bounds)
+        fb = FrameBuffers()
+        check(lib().olf_ctx_device_buffers(self.ctx.handle, C.byref(fb)), "olf_ctx_device_buffers")
+        d_counts, keep = fb.counts, None
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, np.int32)
+            if counts.shape != (n_images,):
+                raise ValueError("frame_grid: counts has one entry per image of the last frames() call")
+            keep = torch.from_numpy(counts).cuda()
+            d_counts = keep.data_ptr()
+        cap = self.ctx.orb_capacity
+        offs = torch.full((all_frames, _lib.GRID_CELLS + 1), 0 if fill is None else int(fill), dtype=torch.int32, device="cuda")
+        idx = torch.full((all_frames, cap), 0 if fill is None else int(fill), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()          # (the context's stream is not ordered with torch's)
+        check(lib().olf_frame_grid_dev(self.ctx.handle, n_frames, int(img_stride), fb.kps, d_counts, minX, maxX, minY, maxY,
+                                       C.c_void_p(offs.data_ptr()), C.c_void_p(idx.data_ptr()), None), "olf_frame_grid_dev")
+        self.ctx.synchronize()
+        return offs.cpu().numpy(), idx.cpu().numpy()
+
+
+def assign_features_to_grid(keys, bounds, context=None):
+    """Frame::AssignFeaturesToGrid (src/Frame.cc:334-349) for one frame's key points (KEYPOINT_DTYPE, mvKeysUn) on the device: olf_frame_grid.
+    bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY).  Returns (cell_offsets [3073], cell_index [cell_offsets[-1]]): cell (ix, iy) = mGrid[ix][iy] holds
+    cell_index[cell_offsets[ix * 48 + iy] : cell_offsets[ix * 48 + iy + 1]]."""
+    from .matcher import _ctx
+    keys = np.ascontiguousarray(keys, KEYPOINT_DTYPE)
+    offs, idx = np.zeros(_lib.GRID_CELLS + 1, np.int32), np.zeros(max(len(keys), 1), np.int32)
+    check(lib().olf_frame_grid(_ctx(context).handle, ptr(keys), len(keys), *(float(v) for v in bounds), ptr(offs), ptr(idx)), "olf_frame_grid")
+    return offs, idx[:offs[-1]].copy()
+
+
+def features_in_area(keys, grid, bounds, queries, capacity=None, context=None):
+    """Frame::GetFeaturesInArea (src/Frame.cc:517-570) for many queries on the device: olf_features_in_area.  grid = (cell_offsets, cell_index) of
+    `keys` under `bounds`; queries: AREA_QUERY_DTYPE records (x, y, r, min_level, max_level; the reference's default levels are -1, -1).
+    Returns the CSR (cand_offsets [n_queries + 1], cand_idx) olf_match_candidates consumes: query q's vIndices, in the reference's order, are
+    cand_idx[cand_offsets[q] : cand_offsets[q + 1]].  capacity: size of the index buffer (default: sized by a first call with none)."""
+    from .matcher import _ctx
+    keys = np.ascontiguousarray(keys, KEYPOINT_DTYPE)
+    offs, idx = np.ascontiguousarray(grid[0], np.int32), np.ascontiguousarray(grid[1], np.int32)
+    if offs.shape != (_lib.GRID_CELLS + 1,):
+        raise ValueError("features_in_area: cell_offsets has OLF_GRID_CELLS + 1 entries")
+    queries = np.ascontiguousarray(np.asarray(queries, _lib.AREA_QUERY_DTYPE).reshape(-1))
+    h, b = _ctx(context).handle, [float(v) for v in bounds]
+
+    def run(cap):
+        co, ci = np.zeros(len(queries) + 1, np.int32), np.zeros(max(cap, 1), np.int32)
+        rc = lib().olf_features_in_area(h, ptr(keys), len(keys), ptr(offs), ptr(idx), *b, len(queries), ptr(queries), ptr(co), ptr(ci), cap)
+        return rc, co, ci
+    rc, co, ci = run(0 if capacity is None else int(capacity))
+    if capacity is None and rc == _lib.OLF_ERR_CAPACITY:           # the offsets are complete: they size the second call
+        rc, co, ci = run(int(co[-1]))
+    check(rc, "olf_features_in_area")
+    return co, ci[:co[-1]].copy()

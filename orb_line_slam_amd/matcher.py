@@ -132,6 +132,12 @@ class FrameView:
         self.mFeatVec = mFeatVec or {}
         self.AssignFeaturesToGrid()
 
+    def attach_grid(self, offsets, index):
+        """Hand the C-backed searches a prebuilt mGrid (frame.assign_features_to_grid / StereoFrontEnd.frame_grid; layout in
+        include/orbline_types.h) instead of letting each of them rebuild it from the key points.  attach_grid(None, None) detaches it."""
+        self.grid_offsets = None if offsets is None else np.ascontiguousarray(offsets, np.int32)
+        self.grid_index = None if index is None else np.ascontiguousarray(index, np.int32)
+
     def AssignFeaturesToGrid(self):
         """src/Frame.cc:334-349 + PosInGrid :572-582 (C round(): half away from zero)"""
         self.mGrid = [[[] for _ in range(self.FRAME_GRID_ROWS)] for _ in range(self.FRAME_GRID_COLS)]
@@ -254,6 +260,7 @@ def _view_c(v, keep):
     offs[1:] = np.cumsum([len(v.mFeatVec[k]) for k in nodes])
     feats = np.array([i for k in nodes for i in v.mFeatVec[k]], np.int32)
     c.fv_nodes, c.fv_offsets, c.fv_features, c.fv_n = p(np.array(nodes, np.int32)), p(offs), p(feats), len(nodes)
+    c.grid_offsets, c.grid_index = p(getattr(v, "grid_offsets", None), np.int32), p(getattr(v, "grid_index", None), np.int32)
     return c
 
 
