@@ -469,6 +469,45 @@ int olf_frames_pack_dev(olf_ctx* ctx, const olf_frame_buffers* out, int n_pairs,
  * d_depth 16-byte aligned, d_mask 4-byte aligned. */
 int olf_stereo_points_mask_dev(olf_ctx* ctx, const float* d_depth, size_t n, uint8_t* d_mask, void* stream);
 
+/* ---- ORBmatcher::SearchByProjection(Frame&, const Frame&, ...) for a batch on the device (csrc/track_batch.hip) -------------------------------
+ * The frames of a batch in the roles the search reads them in.  Device pointers; frame j = image j * img_stride of the extractor-layout arrays
+ * (img_stride 2 = the left images of a stereo batch, as olf_search_by_bow_batch_dev / olf_frame_grid_dev); the per-frame planes are
+ * [n_frames][olf_orb_capacity()].  desc / mp_desc 16-byte aligned. */
+typedef struct olf_track_batch {
+    const olf_keypoint* kps; const uint8_t* desc; const int32_t* counts; int32_t img_stride;   /* mvKeysUn, mDescriptors, N */
+    const float*   uright;            /* mvuRight                         (olf_frame_buffers.uright)                 */
+    const int32_t* cell_offsets;      /* [n_frames][OLF_GRID_CELLS + 1]   (olf_frame_grid_dev)                       */
+    const int32_t* cell_index;        /* [n_frames][capacity]                                                        */
+    const float*   Tcw;               /* [n_frames][16] mTcw, row-major                                              */
+    const float*   mp_world;          /* [n_frames][capacity][3] pMP->GetWorldPos() of the frame in its LastFrame role (olf_unproject_stereo_dev) */
+    const uint8_t* mp_valid;          /* mvpMapPoints[i] != NULL      NULL: every feature holds one (olf_stereo_points_mask_dev) */
+    const uint8_t* mp_obs;            /* pMP->Observations() > 0      NULL: all do (key-frame points); temporal points of UpdateLastFrame: 0 */
+    const uint8_t* outlier;           /* mvbOutlier                   NULL: none                                      */
+    const uint8_t* mp_desc;           /* pMP->GetDescriptor() [n_frames][capacity][32]   NULL: the frame's own descriptors */
+    float fx, fy, cx, cy, mbf, minX, maxX, minY, maxY;
+} olf_track_batch;
+/* int ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, const float th, const bool bMono) (src/ORBmatcher.cc:1330-1472) and the
+ * overload with map<int,int>& match12 (:1474-1618), the matcher of Tracking::TrackWithMotionModel[WithLine] (src/Tracking.cc:1296,1302), for the
+ * n_frames - 1 pairs of consecutive frames of a batch: pair j has LastFrame = frame j and CurrentFrame = frame j + 1.  The CurrentFrame starts without
+ * map points (both call sites fill(..., NULL) first, src/Tracking.cc:1295,1301); mvScaleFactors are the context's.  Arithmetic: that of
+ * olf_search_by_projection (convention C.12).  d_th (or NULL) [n_frames - 1]: a radius per pair that replaces th; an entry <= 0 skips the pair and leaves
+ * its three output rows untouched -- the wider retry of src/Tracking.cc:1299-1303 is a second call with d_th[j] = nmatches[j] < 20 ? 2 * th : 0.
+ * d_matches [n_frames - 1][capacity]: the LastFrame index whose point CurrentFrame feature i2 holds at the end (-1: none; -1 from N on);
+ * d_match12 (or NULL), same shape: the value the reference's map holds under key i2 (the FIRST index, :1577), -1: no such key; d_nmatches [n_frames - 1]:
+ * the return values.  A LastFrame feature that reaches its window with an octave outside the context's levels (caller-made key points) makes its pair
+ * end with nmatches = -1 and its rows untouched, and sets bit 256 of the context's status word (olf_ctx_synchronize / olf_ctx_poll_status report it).
+ * There is no other limit: the lists the search keeps are bounded per query and a query that outgrows them is recomputed.  n_frames < 2: nothing is
+ * written.  Contexts above OLF_GRID_MAX_KEYS: OLF_ERR_CAPACITY; maxX <= minX or maxY <= minY: OLF_ERR_INVALID. */
+int olf_search_by_projection_batch_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, float th, const float* d_th, int bMono,
+                                       int check_orientation, int32_t* d_matches, int32_t* d_match12, int32_t* d_nmatches, void* stream);
+/* cv::Mat Frame::UnprojectStereo(const int &i) (src/Frame.cc:1073-1087) for every feature of n_frames frames -- the world positions of the stereo
+ * points a frame owns (Tracking::UpdateLastFrame, src/Tracking.cc:1096-1101), i.e. mp_world of olf_track_batch.  invfx = 1.0f / fx and invfy are formed
+ * once in float (:188-189); x = (u - cx) * z * invfx left to right in float; world = mRwc * x3Dc + mOw under C.12.  d_depth [n_frames][capacity] (mvDepth),
+ * d_Twc [n_frames][16]: camera to world, rows of mRwc | mOw; d_world [n_frames][capacity][3].  Features with z <= 0 (the reference returns an empty
+ * cv::Mat) or past the count get (0, 0, 0); their validity is the byte of olf_stereo_points_mask_dev. */
+int olf_unproject_stereo_dev(olf_ctx* ctx, int n_frames, int img_stride, const olf_keypoint* d_kps, const int32_t* d_counts, const float* d_depth,
+                             float fx, float fy, float cx, float cy, const float* d_Twc, float* d_world, void* stream);
+
 /* measurement: rate of a plain 16-byte-per-thread device copy kernel over `bytes` (read + written bytes per second): the practical HBM
  * ceiling bench.py reports next to the specification's 8 TB/s */
 int olf_debug_copy_bandwidth(olf_ctx* ctx, size_t bytes, int reps, double* gbytes_per_s);

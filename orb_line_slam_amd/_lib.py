@@ -66,6 +66,13 @@ class FrameViewC(C.Structure):
                 [(n, C.c_void_p) for n in ("grid_offsets", "grid_index")])
 
 
+class TrackBatchC(C.Structure):
+    """olf_track_batch (include/orbline.h): device pointers of a batch of frames as SearchByProjection(Frame, Frame) reads them"""
+    _fields_ = ([(n, C.c_void_p) for n in ("kps", "desc", "counts")] + [("img_stride", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("uright", "cell_offsets", "cell_index", "Tcw", "mp_world", "mp_valid", "mp_obs", "outlier", "mp_desc")] +
+                [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "mbf", "minX", "maxX", "minY", "maxY")])
+
+
 # Frame::mGrid as two int32 arrays (include/orbline_types.h) and one Frame::GetFeaturesInArea call
 GRID_COLS, GRID_ROWS, GRID_CELLS, GRID_MAX_KEYS = 64, 48, 3072, 8192
 AREA_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("r", "<f4"), ("min_level", "<i4"), ("max_level", "<i4")])
@@ -174,7 +181,10 @@ def lib():
         L.olf_ctx_set_deferred_join.argtypes = [C.c_void_p, C.c_int]
         L.olf_stereo_frames_join_dev.argtypes = [C.c_void_p, C.c_void_p]
         L.olf_stereo_points_mask_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        L.olf_debug_copy_bandwidth.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
+        L.olf_search_by_projection_batch_dev.argtypes = [C.c_void_p, C.POINTER(TrackBatchC), C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.olf_unproject_stereo_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p] * 3
+        L.olf_debug_copy_bandwidth.argtypes =[C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
         L.olf_debug_fdiv_sweep.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         L.olf_debug_sqrtq_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
         L.olf_debug_align_sweep.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]

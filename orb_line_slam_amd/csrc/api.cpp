@@ -184,6 +184,9 @@ int launch_depth_mask(const float* depth, uint8_t* mask, size_t n, hipStream_t s
 namespace olf {
 hipStream_t ctx_stream(olf_ctx* c) { return c->stream; }
 int ctx_scratch(olf_ctx* c, int slot, size_t bytes, void** out) { return scratch_get(c, slot, bytes, out); }
+int* ctx_status(olf_ctx* c) { return c->ob.status; }
+int ctx_check_device(const olf_ctx* c, const char* who) { return check_device(c, who); }
+int ctx_orb_levels(const olf_ctx* c) { return c->params.orb.nlevels; }
 }
 
 enum { ST_ORB_PYRAMID, ST_ORB_FAST, ST_ORB_OCTREE, ST_ORB_BLUR, ST_ORB_DESCRIBE, ST_STEREO_POINTS, ST_LSD_FRONT, ST_LSD_GROW, ST_LSD_RECT, ST_LINE_LBD,
@@ -545,7 +548,7 @@ static int check_status(olf_ctx* c)
     if (st[0]) {
         (void)hipMemset(c->ob.status, 0, 16);
         set_error("device capacity overflow, flags=" + std::to_string(st[0]) +
-                  " (1/2/4: ORB corner / candidate / key point buffers, 8: LSD regions, segments or pixel-list pool, 16: LSD growth watchdog, 32: frame record buffer, 64: LSD seed sort, final-range list of the grid-wide top levels, 128: candidate list of olf_features_in_area_dev)");
+                  " (1/2/4: ORB corner / candidate / key point buffers, 8: LSD regions, segments or pixel-list pool, 16: LSD growth watchdog, 32: frame record buffer, 64: LSD seed sort, final-range list of the grid-wide top levels, 128: candidate list of olf_features_in_area_dev, 256: olf_search_by_projection_batch_dev skipped a pair whose last frame holds an octave outside the context's levels)");
         return OLF_ERR_CAPACITY;
     }
     return OLF_OK;

@@ -146,6 +146,62 @@ class StereoFrontEnd:
         self.ctx.synchronize()
         return offs.cpu().numpy(), idx.cpu().numpy()
 
+    def _last_frames(self, who):
+        """(device buffers, number of left frames) of the last frames() call"""
+        if not self._last_images:
+            raise RuntimeError(f"{who}: no frames() call to take the features from")
+        fb = FrameBuffers()
+        check(lib().olf_ctx_device_buffers(self.ctx.handle, C.byref(fb)), "olf_ctx_device_buffers")
+        return fb, self._last_images // 2
+
+    def stereo_points_mask(self):
+        """mvDepth > 0 of the last frames() call as a device byte mask [n_pairs, capacity] (olf_stereo_points_mask_dev): the map points a frame owns
+        right after stereo matching, i.e. mp_valid of search_by_projection_batch."""
+        import torch
+        fb, n = self._last_frames("stereo_points_mask")
+        from .matcher import _torch_stream
+        mask = torch.zeros((n, self.ctx.orb_capacity), dtype=torch.uint8, device="cuda")
+        with _torch_stream() as s:
+            check(lib().olf_stereo_points_mask_dev(self.ctx.handle, fb.depth, n * self.ctx.orb_capacity, C.c_void_p(mask.data_ptr()), s),
+                  "olf_stereo_points_mask_dev")
+        return mask
+
+    def unproject_stereo(self, camera, Twc):
+        """Frame::UnprojectStereo (src/Frame.cc:1073-1087) for every left-image feature of the last frames() call, on the context's device buffers
+        (olf_unproject_stereo_dev).  camera = (fx, fy, cx, cy); Twc [n_pairs, 4, 4] float32, camera to world (rows of mRwc | mOw), numpy or device
+        tensor.  Returns world [n_pairs, capacity, 3] as a device tensor."""
+        import torch
+        from . import matcher
+        fb, n = self._last_frames("unproject_stereo")
+        Twc = torch.as_tensor(np.ascontiguousarray(Twc, np.float32) if isinstance(Twc, np.ndarray) else Twc).cuda().contiguous()
+        if tuple(Twc.shape) != (n, 4, 4):
+            raise ValueError("unproject_stereo: Twc has one 4 x 4 matrix per stereo pair of the last frames() call")
+        return matcher.unproject_stereo(n, fb.kps, fb.counts, fb.depth, camera, Twc, img_stride=2, context=self.ctx)
+
+    def search_by_projection_batch(self, Tcw, mp_world, camera, th, bMono=False, checkOri=True, bounds=None, mp_valid=None, mp_obs=None,
+                                   outlier=None, mp_desc=None, d_th=None, match12=True, out=None):
+        """ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono[, match12]) between consecutive left frames of the last frames() call,
+        on the context's device buffers (olf_search_by_projection_batch_dev; the grids come from olf_frame_grid_dev in the same call, nothing is
+        downloaded).  Tcw [n_pairs, 4, 4] float32 (numpy or device tensor); mp_world [n_pairs, capacity, 3] device tensor (unproject_stereo);
+        camera = (fx, fy, cx, cy, mbf); bounds default to the image; mp_valid e.g. stereo_points_mask().  The other arguments and the result
+        (matches, match12, nmatches: device tensors over the n_pairs - 1 frame pairs) are those of matcher.search_by_projection_batch."""
+        import torch
+        from . import matcher
+        fb, n = self._last_frames("search_by_projection_batch")
+        cap = self.ctx.orb_capacity
+        minX, maxX, minY, maxY = (0.0, float(self.width), 0.0, float(self.height)) if bounds is None else (float(v) for v in bounds)
+        Tcw = torch.as_tensor(np.ascontiguousarray(Tcw, np.float32) if isinstance(Tcw, np.ndarray) else Tcw).cuda().contiguous()
+        if tuple(Tcw.shape) != (n, 4, 4):
+            raise ValueError("search_by_projection_batch: Tcw has one 4 x 4 matrix per stereo pair of the last frames() call")
+        offs = torch.zeros((n, _lib.GRID_CELLS + 1), dtype=torch.int32, device="cuda")
+        idx = torch.zeros((n, cap), dtype=torch.int32, device="cuda")
+        with matcher._torch_stream() as s:
+            check(lib().olf_frame_grid_dev(self.ctx.handle, n, 2, fb.kps, fb.counts, minX, maxX, minY, maxY, C.c_void_p(offs.data_ptr()),
+                                           C.c_void_p(idx.data_ptr()), s), "olf_frame_grid_dev")
+        return matcher.search_by_projection_batch(n, fb.kps, fb.desc, fb.counts, fb.uright, offs, idx, Tcw, mp_world, camera, (minX, maxX, minY, maxY), th,
+                                                  bMono=bMono, checkOri=checkOri, img_stride=2, mp_valid=mp_valid, mp_obs=mp_obs, outlier=outlier,
+                                                  mp_desc=mp_desc, d_th=d_th, match12=match12, out=out, context=self.ctx)
+
 
 def assign_features_to_grid(keys, bounds, context=None):
     """Frame::AssignFeaturesToGrid (src/Frame.cc:334-349) for one frame's key points (KEYPOINT_DTYPE, mvKeysUn) on the device: olf_frame_grid.

@@ -320,6 +320,82 @@ def _search_by_bow(self, pKF, F):
     return int(n[0]), matched
 
 
+def _dev(a, dtype=None, what="argument"):
+    """device address of a torch tensor (checked: on the GPU, contiguous, of `dtype`), of a raw address (int), or None"""
+    if a is None or isinstance(a, int):
+        return a
+    import torch
+    if not (isinstance(a, torch.Tensor) and a.is_cuda and a.is_contiguous() and (dtype is None or a.dtype == dtype)):
+        raise TypeError(f"{what}: a contiguous device tensor of {dtype} (or a device address) expected")
+    return a.data_ptr()
+
+
+class _torch_stream:
+    """The stream handle that orders a *_dev entry with torch's work: torch's current stream -- or, when that is the default stream (whose handle, 0,
+    means "the context's own stream" to the library), the context's stream between two device-wide synchronisations."""
+
+    def __enter__(self):
+        import torch
+        self.handle = torch.cuda.current_stream().cuda_stream
+        if not self.handle:
+            torch.cuda.synchronize()
+        return self.handle or None
+
+    def __exit__(self, *exc):
+        if not self.handle:
+            import torch
+            torch.cuda.synchronize()
+        return False
+
+
+def search_by_projection_batch(n_frames, kps, desc, counts, uright, cell_offsets, cell_index, Tcw, mp_world, camera, bounds, th, bMono=False,
+                               checkOri=True, img_stride=2, mp_valid=None, mp_obs=None, outlier=None, mp_desc=None, d_th=None, match12=True, out=None,
+                               context=None):
+    """ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono[, match12]) (src/ORBmatcher.cc:1330-1472, :1474-1618) for the n_frames - 1
+    consecutive pairs of a device-resident batch: olf_search_by_projection_batch_dev (include/orbline.h describes every array; csrc/track_batch.hip).
+    The arrays are torch device tensors (or raw device addresses) in the extractor's layout -- kps / desc / counts per image, frame j = image
+    j * img_stride -- and per-frame planes [n_frames, capacity] for the rest; the context must be the one whose capacity they were made for.
+    camera = (fx, fy, cx, cy, mbf); bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY); d_th: float32 [n_frames - 1] per-pair radii (<= 0 skips a pair).
+    match12: also return the reference's match12 map as an array.  out = (matches, match12 or None, nmatches): int32 tensors to write into (rows of
+    skipped pairs keep what they hold); by default they are made here, filled with -1.  Runs on torch's current stream.
+    Returns (matches [n_frames - 1, capacity], match12 or None, nmatches [n_frames - 1]) as device tensors."""
+    import ctypes as C
+    import torch
+    ctx = _ctx(context)
+    cap, n_pairs = ctx.orb_capacity, max(int(n_frames) - 1, 0)
+    tb = _lib.TrackBatchC()
+    tb.kps, tb.desc, tb.counts, tb.img_stride = _dev(kps, None, "kps"), _dev(desc, torch.uint8, "desc"), _dev(counts, torch.int32, "counts"), int(img_stride)
+    tb.uright, tb.cell_offsets, tb.cell_index = _dev(uright, torch.float32, "uright"), _dev(cell_offsets, torch.int32, "cell_offsets"), _dev(cell_index, torch.int32, "cell_index")
+    tb.Tcw, tb.mp_world = _dev(Tcw, torch.float32, "Tcw"), _dev(mp_world, torch.float32, "mp_world")
+    tb.mp_valid, tb.mp_obs, tb.outlier = _dev(mp_valid, torch.uint8, "mp_valid"), _dev(mp_obs, torch.uint8, "mp_obs"), _dev(outlier, torch.uint8, "outlier")
+    tb.mp_desc = _dev(mp_desc, torch.uint8, "mp_desc")
+    tb.fx, tb.fy, tb.cx, tb.cy, tb.mbf = (float(v) for v in camera)
+    tb.minX, tb.maxX, tb.minY, tb.maxY = (float(v) for v in bounds)
+    if out is None:
+        mk = lambda *shape: torch.full(shape, -1, dtype=torch.int32, device="cuda")
+        out = (mk(n_pairs, cap), mk(n_pairs, cap) if match12 else None, mk(n_pairs))
+    m, m12, n = out
+    with _torch_stream() as s:
+        check(lib().olf_search_by_projection_batch_dev(ctx.handle, C.byref(tb), int(n_frames), float(th), _dev(d_th, torch.float32, "d_th"), int(bool(bMono)),
+                                                       int(bool(checkOri)), _dev(m, torch.int32, "matches"), _dev(m12, torch.int32, "match12"),
+                                                       _dev(n, torch.int32, "nmatches"), s), "olf_search_by_projection_batch_dev")
+    return m, m12, n
+
+
+def unproject_stereo(n_frames, kps, counts, depth, camera, Twc, img_stride=2, out=None, context=None):
+    """Frame::UnprojectStereo (src/Frame.cc:1073-1087) for every feature of n_frames device-resident frames: olf_unproject_stereo_dev.  kps / counts in
+    the extractor's layout, depth [n_frames, capacity] (mvDepth), camera = (fx, fy, cx, cy), Twc [n_frames, 4, 4] camera-to-world (rows of mRwc | mOw).
+    Returns world [n_frames, capacity, 3] float32 on the device ((0, 0, 0) where the reference returns an empty cv::Mat).  torch's current stream."""
+    import torch
+    ctx = _ctx(context)
+    world = torch.zeros((int(n_frames), ctx.orb_capacity, 3), dtype=torch.float32, device="cuda") if out is None else out
+    with _torch_stream() as s:
+        check(lib().olf_unproject_stereo_dev(ctx.handle, int(n_frames), int(img_stride), _dev(kps, None, "kps"), _dev(counts, torch.int32, "counts"),
+                                             _dev(depth, torch.float32, "depth"), *(float(v) for v in camera), _dev(Twc, torch.float32, "Twc"),
+                                             _dev(world, torch.float32, "world"), s), "olf_unproject_stereo_dev")
+    return world
+
+
 class MapPointView:
     """The MapPoint members read by SearchByProjection(Frame&, const vector<MapPoint*>&, th) (src/ORBmatcher.cc:47-131), gathered by the
     host (mutex-guarded in the reference, src/MapPoint.cc:321-325) into SoA buffers:

@@ -1,0 +1,622 @@
+"""GPU parity: olf_search_by_projection_batch_dev -- ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono[, match12])
+(src/ORBmatcher.cc:1330-1472, :1474-1618) for the consecutive pairs of a device-resident batch -- and olf_unproject_stereo_dev
+(Frame::UnprojectStereo, src/Frame.cc:1073-1087).  Every expectation comes from the CPU oracle's two restatements of the search, pair by pair:
+nmatches, all of matches, the match12 pairs in order, and -1 beyond N.  The floors are asserted on the ORACLE's outputs, so that no test can pass by
+having nothing to compare."""
+import copy
+import ctypes as C
+import functools
+import numpy as np
+import pytest
+import orb_line_slam_amd as ola
+from orb_line_slam_amd import _lib, matcher, synth
+from orb_line_slam_amd._lib import KEYPOINT_DTYPE, OLF_ERR_CAPACITY, OLF_ERR_INVALID, lib
+
+pytestmark = pytest.mark.gpu
+
+W, H = 320, 240
+FX = FY = 200.0
+CX, CY, MBF = 160.0, 120.0, 40.0          # mb = 0.2
+CAM = (FX, FY, CX, CY, MBF)
+BOUNDS = (0.0, 320.0, 0.0, 240.0)
+f32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import torch  # noqa: F401  (the device tensors below)
+    p = _lib.default_params()
+    p.orb.nfeatures = 1400
+    c = _lib.Context(p, W, H, 2)
+    assert c.orb_capacity >= 1400
+    yield c
+    c.close()
+
+
+def scale_factors(ctx):
+    sf = np.zeros(ctx.nlevels, np.float32)
+    lib().olf_orb_scale_tables(ctx.handle, sf.ctypes.data_as(C.c_void_p), None, None, None, None)
+    return sf
+
+
+# ---- synthetic chain generator (no extractor) ------------------------------------------------------------------------------------------
+def pose(tx=0.0, ty=0.0, tz=0.0, ry_deg=0.0):
+    """relative motion D of a pair: Xc_cur = D * Xc_last"""
+    T = np.eye(4)
+    a = np.deg2rad(ry_deg)
+    T[:3, :3] = [[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]]
+    T[:3, 3] = [tx, ty, tz]
+    return T
+
+
+class SynthFrame:
+    """one frame: keys / desc / uright / depth of its features, its pose, and its map points in the LastFrame role"""
+
+    def roles(self, rng, obs_p, bad_desc_p=0.3):
+        n = len(self.keys)
+        Twc = np.linalg.inv(self.Tcw.astype(np.float64))
+        z = self.depth.astype(np.float64)
+        Xc = np.stack([(self.keys["x"] - CX) * z / FX, (self.keys["y"] - CY) * z / FY, z], 1)
+        self.mp_world = (Xc @ Twc[:3, :3].T + Twc[:3, 3]).astype(np.float32)
+        self.mp_valid = rng.random(n) < 0.9
+        self.outlier = rng.random(n) < 0.05
+        self.mp_obs = rng.random(n) < obs_p
+        self.mp_desc = self.desc.copy()                      # pMP->GetDescriptor(): the feature's own, one bit off for a share of them
+        for i in np.flatnonzero(rng.random(n) < bad_desc_p):
+            self.mp_desc[i, rng.integers(32)] ^= np.uint8(1 << rng.integers(8))
+        return self
+
+    def view(self, sf, n=None):
+        n = len(self.keys) if n is None else n
+        v = ola.FrameView(self.keys[:n], self.desc[:n], self.uright[:n], sf, FX, FY, CX, CY, MBF, BOUNDS, mTcw=self.Tcw)
+        v.mp_valid, v.mp_world, v.mp_desc = self.mp_valid[:n].copy(), self.mp_world[:n].copy(), self.mp_desc[:n].copy()
+        v.mp_obs, v.mvbOutlier = self.mp_obs[:n].copy(), self.outlier[:n].copy()
+        return v
+
+
+def _flip(rng, desc, k):
+    d = desc.copy()
+    for r in range(len(d)):
+        for _ in range(k):
+            d[r, rng.integers(32)] ^= np.uint8(1 << rng.integers(8))
+    return d
+
+
+def _dup(fr, rng):
+    """every feature listed twice; the second copy has 2 flipped descriptor bits"""
+    fr.keys = np.concatenate([fr.keys, fr.keys])
+    fr.desc = np.concatenate([fr.desc, _flip(rng, fr.desc, 2)])
+    fr.uright, fr.depth = np.concatenate([fr.uright, fr.uright]), np.concatenate([fr.depth, fr.depth])
+
+
+def first_frame(rng, n, squeeze=1.0, max_octave=7, similar=False):
+    fr = SynthFrame()
+    k = np.zeros(n, KEYPOINT_DTYPE)
+    k["x"] = (CX + (rng.uniform(8, 312, n) - CX) * squeeze).astype(f32)
+    k["y"] = (CY + (rng.uniform(8, 232, n) - CY) * squeeze).astype(f32)
+    k["octave"] = rng.integers(0, max_octave + 1, n)
+    k["angle"] = rng.uniform(0, 360, n).astype(f32)
+    k["size"], k["class_id"] = 31, -1
+    fr.keys, fr.depth = k, rng.uniform(2, 20, n).astype(f32)
+    fr.desc = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    if similar:                                              # every descriptor within a few bits of one base: every candidate is below TH_HIGH
+        fr.desc = _flip(rng, np.repeat(rng.integers(0, 256, (1, 32), dtype=np.uint8), n, 0), 12)
+    fr.uright = np.where(rng.random(n) < 0.2, -1.0, k["x"] - MBF / fr.depth + rng.uniform(-1, 1, n)).astype(f32)
+    fr.Tcw = np.eye(4, dtype=f32)
+    fr.n_unique = n
+    return fr
+
+
+def next_frame(rng, prev, D, n_dis, rot_p, jitter=2.0, flips=4, far_jitter=False, keep=None, max_octave=7, squeeze=1.0):
+    """re-observes prev's (unique) points under the pose D * prev.Tcw, adds distractors, permutes"""
+    fr = SynthFrame()
+    Tcw = D @ prev.Tcw.astype(np.float64)
+    nu = prev.n_unique
+    Xw = prev.mp_world[:nu].astype(np.float64)
+    Xc = Xw @ Tcw[:3, :3].T + Tcw[:3, 3]
+    z = Xc[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u, v = FX * Xc[:, 0] / z + CX, FY * Xc[:, 1] / z + CY
+    if far_jitter:                                           # 9 .. 13 px off in x: outside a 7 px window, inside the doubled one
+        u = u + rng.uniform(9, 13, nu) * rng.choice([-1.0, 1.0], nu)
+        v = v + rng.uniform(-2, 2, nu)
+    else:
+        u, v = u + rng.uniform(-jitter, jitter, nu), v + rng.uniform(-jitter, jitter, nu)
+    ok = np.flatnonzero((z > 0.5) & (u >= 8) & (u <= 312) & (v >= 8) & (v <= 232))
+    if keep is not None:
+        ok = ok[:keep]
+    m = len(ok)
+    k = np.zeros(m + n_dis, KEYPOINT_DTYPE)
+    k["x"][:m], k["y"][:m] = u[ok], v[ok]
+    k["octave"][:m] = np.clip(prev.keys["octave"][ok] + rng.integers(-1, 2, m), 0, max_octave)
+    off = np.where(rng.random(m) < rot_p, rng.choice([120.0, 240.0, 60.0], m, p=[0.5, 0.3, 0.2]), rng.uniform(-3, 3, m))
+    k["angle"][:m] = ((prev.keys["angle"][ok] + off) % 360).astype(f32)
+    k["angle"][:m][k["angle"][:m] >= 360] = 0
+    depth = np.concatenate([z[ok], rng.uniform(2, 20, n_dis)]).astype(f32)
+    desc = np.concatenate([_flip(rng, prev.desc[ok], flips), rng.integers(0, 256, (n_dis, 32), dtype=np.uint8)])
+    k["x"][m:] = CX + (rng.uniform(8, 312, n_dis) - CX) * squeeze
+    k["y"][m:] = CY + (rng.uniform(8, 232, n_dis) - CY) * squeeze
+    k["octave"][m:], k["angle"][m:] = rng.integers(0, max_octave + 1, n_dis), rng.uniform(0, 360, n_dis)
+    k["size"], k["class_id"] = 31, -1
+    ur = np.where(rng.random(m + n_dis) < 0.2, -1.0, k["x"] - MBF / depth + rng.uniform(-1, 1, m + n_dis)).astype(f32)
+    perm = rng.permutation(m + n_dis)
+    fr.keys, fr.desc, fr.uright, fr.depth = k[perm], desc[perm], ur[perm], depth[perm]
+    fr.Tcw = Tcw.astype(f32)
+    fr.n_unique = m + n_dis
+    return fr
+
+
+def make_chain(seed, motions, n=300, n_dis=60, rot_p=0.3, obs_p=0.5, dup=False, far=(), **kw):
+    """frame 0 and one further frame per relative motion"""
+    rng = np.random.default_rng(seed)
+    first_kw = {k: kw[k] for k in ("squeeze", "max_octave", "similar") if k in kw}
+    next_kw = {k: kw[k] for k in ("squeeze", "max_octave", "flips", "keep") if k in kw}
+    frames = [first_frame(rng, n, **first_kw)]
+    for j, D in enumerate([None] + list(motions)):
+        if j:
+            frames.append(next_frame(rng, frames[-1], D, n_dis, rot_p, far_jitter=(j in far), **next_kw))
+        fr = frames[-1]
+        fr.roles(rng, obs_p)                                 # (the world points the next frame re-observes)
+        if dup:
+            nu = fr.n_unique
+            _dup(fr, rng)
+            fr.roles(rng, obs_p)
+            fr.n_unique = nu
+    return frames
+
+
+MOTIONS5 = [pose(), pose(tz=-0.5), pose(tz=0.5), pose(tx=0.05), pose(ry_deg=2.0)]      # still, forward, backward, sideways, 2 deg about y
+
+
+@functools.lru_cache(maxsize=None)
+def chain5():
+    return make_chain(11, MOTIONS5)
+
+
+@functools.lru_cache(maxsize=None)
+def crowded(obs_p, similar=False):
+    # 700 points squeezed to 15 % of the image area around the centre, every point listed twice
+    # (similar: see test_crowded_chain_obs; 280 of the 700 points are then not observed again, and their queries take other points' features)
+    extra = dict(similar=True, keep=420, n_dis=280) if similar else dict(n_dis=0)
+    return make_chain(23, [pose(), pose()], n=700, rot_p=0.3, obs_p=obs_p, dup=True, squeeze=float(np.sqrt(0.15)), flips=3, **extra)
+
+
+# ---- device side ----------------------------------------------------------------------------------------------------------------------
+class DeviceBatch:
+    """the frames of a chain as the device arrays of olf_track_batch; counts may shorten a frame (its rows keep the full data)"""
+
+    def __init__(self, ctx, frames, img_stride=1, counts=None):
+        import torch
+        self.ctx, self.n, self.st, cap = ctx, len(frames), img_stride, ctx.orb_capacity
+        self.cap = cap
+        nf, ni = self.n, max(self.n * img_stride, 1)
+        rng = np.random.default_rng(5)
+        kps = np.zeros((ni, cap), KEYPOINT_DTYPE)
+        kps["octave"] = 99                                   # rows nothing may read: images between the frames, features past the count
+        desc = rng.integers(0, 256, (ni, cap, 32), dtype=np.uint8)
+        cnt = np.full(ni, 17, np.int32)
+        ur, world = np.full((max(nf, 1), cap), 5.0, f32), np.zeros((max(nf, 1), cap, 3), f32)
+        valid, obs, outl = (np.ones((max(nf, 1), cap), np.uint8) for _ in range(3))
+        mpd = rng.integers(0, 256, (max(nf, 1), cap, 32), dtype=np.uint8)
+        Tcw = np.zeros((max(nf, 1), 4, 4), f32)
+        for j, fr in enumerate(frames):
+            m = len(fr.keys)
+            assert m <= cap
+            kps[j * img_stride, :m], desc[j * img_stride, :m] = fr.keys, fr.desc
+            cnt[j * img_stride] = m if counts is None or counts[j] is None else counts[j]
+            ur[j, :m], world[j, :m], Tcw[j] = fr.uright, fr.mp_world, fr.Tcw
+            valid[j, :m], obs[j, :m], outl[j, :m], mpd[j, :m] = fr.mp_valid, fr.mp_obs, fr.outlier, fr.mp_desc
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        self.kps, self.desc, self.counts = up(kps.view(np.uint8).reshape(ni, cap, 28)), up(desc), up(cnt)
+        self.uright, self.world, self.Tcw = up(ur), up(world), up(Tcw)
+        self.valid, self.obs, self.outl, self.mpd = up(valid), up(obs), up(outl), up(mpd)
+        self.offs = torch.full((max(nf, 1), _lib.GRID_CELLS + 1), -5, dtype=torch.int32, device="cuda")
+        self.idx = torch.full((max(nf, 1), cap), -5, dtype=torch.int32, device="cuda")
+        if nf:
+            with matcher._torch_stream() as s:
+                _lib.check(lib().olf_frame_grid_dev(ctx.handle, nf, img_stride, self.kps.data_ptr(), self.counts.data_ptr(), *BOUNDS, self.offs.data_ptr(),
+                                                    self.idx.data_ptr(), s), "olf_frame_grid_dev")
+
+    def search(self, th, bMono=False, check=True, match12=True, planes=True, **kw):
+        opt = dict(mp_valid=self.valid, mp_obs=self.obs, outlier=self.outl, mp_desc=self.mpd) if planes else {}
+        opt.update(kw)
+        return matcher.search_by_projection_batch(self.n, self.kps, self.desc, self.counts, self.uright, self.offs, self.idx, self.Tcw, self.world, CAM,
+                                                  BOUNDS, th, bMono=bMono, checkOri=check, img_stride=self.st, match12=match12, context=self.ctx, **opt)
+
+
+def oracle_pair(oracle, sf, last, cur, th, bMono=False, check=True, n_last=None, n_cur=None, edit=None):
+    """(nmatches, matches, match12 pairs) of one pair; edit(last_view) adjusts the LastFrame's map-point arrays first"""
+    lv, cv = last.view(sf, n_last), cur.view(sf, n_cur)
+    cv.mp_valid[:], cv.mp_obs[:] = False, False             # fill(mvpMapPoints, NULL), src/Tracking.cc:1295,1301
+    if edit:
+        edit(lv)
+    n, m, pairs, _ = oracle.search_by_projection_match12(cv, lv, th, bMono, checkOri=check)
+    n2, m2 = oracle.search_by_projection(copy.deepcopy(cv), lv, th, bMono, checkOri=check)
+    assert n2 == n and np.array_equal(m2, m)                # the two overloads differ in match12 alone
+    return n, m, pairs
+
+
+def assert_pair(res, j, exp, cap, with12=True):
+    m, m12, n = res
+    n_o, m_o, pairs_o = exp
+    N = len(m_o)
+    row = m[j].cpu().numpy()
+    assert int(n[j].item()) == n_o
+    assert np.array_equal(row[:N], m_o) and np.all(row[N:] == -1) and len(row) == cap
+    if with12:
+        r12 = m12[j].cpu().numpy()
+        assert [(int(k), int(r12[k])) for k in np.flatnonzero(r12 >= 0)] == [(int(a), int(b)) for a, b in pairs_o]
+        assert np.all(r12[N:] == -1)
+
+
+def branch(last, cur):
+    """forward / backward / neither, from tlc = Rlw * twc + tlw (src/ORBmatcher.cc:1341-1352)"""
+    twc = -cur.Tcw[:3, :3].astype(np.float64).T @ cur.Tcw[:3, 3].astype(np.float64)
+    tlc = last.Tcw[:3, :3].astype(np.float64) @ twc + last.Tcw[:3, 3].astype(np.float64)
+    return "forward" if tlc[2] > MBF / FX else "backward" if -tlc[2] > MBF / FX else "neither"
+
+
+# ---- 1, 2: the chain of 6 frames ------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _chain5_expect(oracle, sf_key, th, bMono, check):
+    sf = np.frombuffer(sf_key, np.float32)
+    fr = chain5()
+    return [oracle_pair(oracle, sf, fr[j], fr[j + 1], th, bMono, check) for j in range(5)]
+
+
+@pytest.mark.parametrize("check", [True, False])
+@pytest.mark.parametrize("with12", [True, False])
+def test_chain_of_six_frames(oracle, ctx, check, with12):
+    sf = scale_factors(ctx)
+    fr = chain5()
+    assert {branch(fr[j], fr[j + 1]) for j in range(5)} == {"forward", "backward", "neither"}
+    exp = _chain5_expect(oracle, sf.tobytes(), 7.0, False, check)
+    off = _chain5_expect(oracle, sf.tobytes(), 7.0, False, False)
+    for j in range(5):
+        assert exp[j][0] >= 100, (j, exp[j][0])
+        assert off[j][0] - _chain5_expect(oracle, sf.tobytes(), 7.0, False, True)[j][0] >= 10      # events the rotation check rejects
+    res = DeviceBatch(ctx, fr, img_stride=2).search(7.0, check=check, match12=with12)          # the layout of a stereo batch's left images
+    assert (res[1] is None) == (not with12)
+    for j in range(5):
+        assert_pair(res, j, exp[j], ctx.orb_capacity, with12)
+
+
+def test_chain_mono(oracle, ctx):
+    sf = scale_factors(ctx)
+    fr = chain5()
+    exp = _chain5_expect(oracle, sf.tobytes(), 15.0, True, True)
+    res = DeviceBatch(ctx, fr).search(15.0, bMono=True)
+    for j in range(5):
+        assert exp[j][0] >= 100
+        assert_pair(res, j, exp[j], ctx.orb_capacity)
+
+
+# ---- 3: crowded chain -----------------------------------------------------------------------------------------------------------------
+def _long_lists(sf, last, cur, th):
+    """candidate lists longer than 64 among the LastFrame's queries (forward / backward never holds here: identity motion)"""
+    cv = cur.view(sf)
+    T = cur.Tcw.astype(np.float64)
+    Xc = last.mp_world.astype(np.float64) @ T[:3, :3].T + T[:3, 3]
+    long_ = 0
+    for i in np.flatnonzero(last.mp_valid & ~last.outlier & (Xc[:, 2] > 0)):
+        u, v = FX * Xc[i, 0] / Xc[i, 2] + CX, FY * Xc[i, 1] / Xc[i, 2] + CY
+        o = int(last.keys["octave"][i])
+        long_ += len(cv.GetFeaturesInArea(u, v, f32(th) * sf[o], o - 1, o + 1)) > 64
+        if long_ >= 500:                                     # (the floor; counting on costs seconds of Python)
+            break
+    return long_
+
+
+def test_crowded_chain(oracle, ctx):
+    sf = scale_factors(ctx)
+    fr = crowded(0.5)
+    assert [len(f.keys) for f in fr] == [1400, 1400, 1400]
+    db = DeviceBatch(ctx, fr)
+    for check in (False, True):
+        res = db.search(14.0, check=check)
+        for j in range(2):
+            exp = oracle_pair(oracle, sf, fr[j], fr[j + 1], 14.0, check=check)
+            if not check:
+                def clear(v):
+                    v.mp_obs[:] = False
+                cleared = oracle_pair(oracle, sf, fr[j], fr[j + 1], 14.0, check=False, edit=clear)
+                assert int((cleared[1] != exp[1]).sum()) >= 100                    # the blocked state decides many matches
+                assert sum(1 for k, v in exp[2] if exp[1][k] != v) >= 100             # first != last
+                assert exp[0] > len(exp[2])                                          # nmatches counts overwrites
+                assert _long_lists(sf, fr[j], fr[j + 1], 14.0) >= 500
+            assert_pair(res, j, exp, ctx.orb_capacity)
+
+
+@pytest.mark.parametrize("obs_p,similar", [(0.0, False), (1.0, False), (1.0, True), (0.5, True)])
+def test_crowded_chain_obs(oracle, ctx, obs_p, similar):
+    """every map point temporal / none; `similar`: all descriptors within a few bits of each other, so that every window entry is below TH_HIGH, and
+    280 points without a second observation, whose queries take other points' features: the few entries kept per query are then often all blocked
+    (hundreds of queries per pair in a CPU replay of the scheme) -- the queries the walk recomputes"""
+    sf = scale_factors(ctx)
+    fr = crowded(obs_p, similar)
+    res = DeviceBatch(ctx, fr).search(14.0)
+    for j in range(2):
+        exp = oracle_pair(oracle, sf, fr[j], fr[j + 1], 14.0)
+        assert exp[0] >= 100
+        assert_pair(res, j, exp, ctx.orb_capacity)
+
+
+# ---- 4: edges ----------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def chain3(seed=31):
+    return make_chain(seed, [pose(tx=0.02), pose(tz=-0.3)])
+
+
+@pytest.mark.parametrize("N", [0, 1, 65])
+@pytest.mark.parametrize("where", [0, 2])
+def test_short_frames(oracle, ctx, N, where):
+    """a frame of N features as the LastFrame of pair 0 (where = 0) or the CurrentFrame of pair 1 (where = 2), beside a normal pair"""
+    sf = scale_factors(ctx)
+    fr = chain3()
+    counts = [None, None, None]
+    counts[where] = N
+    res = DeviceBatch(ctx, fr, counts=counts).search(7.0)
+    e0 = oracle_pair(oracle, sf, fr[0], fr[1], 7.0, n_last=N if where == 0 else None)
+    e1 = oracle_pair(oracle, sf, fr[1], fr[2], 7.0, n_cur=N if where == 2 else None)
+    assert (e1 if where == 0 else e0)[0] >= 100
+    assert_pair(res, 0, e0, ctx.orb_capacity)
+    assert_pair(res, 1, e1, ctx.orb_capacity)
+
+
+@pytest.mark.parametrize("kind", ["no_points", "behind", "outside"])
+def test_pairs_without_windows(oracle, ctx, kind):
+    sf = scale_factors(ctx)
+    fr = [copy.deepcopy(f) for f in chain3()]
+    if kind == "no_points":
+        fr[0].mp_valid[:] = False
+    elif kind == "behind":
+        fr[0].mp_world[:, 2] = -np.abs(fr[0].mp_world[:, 2]) - 1
+    else:
+        fr[0].mp_world[:, 0] += 1000
+    res = DeviceBatch(ctx, fr).search(7.0)
+    e0, e1 = oracle_pair(oracle, sf, fr[0], fr[1], 7.0), oracle_pair(oracle, sf, fr[1], fr[2], 7.0)
+    assert e0[0] == 0 and e1[0] >= 100
+    assert_pair(res, 0, e0, ctx.orb_capacity)
+    assert_pair(res, 1, e1, ctx.orb_capacity)
+
+
+def test_full_capacity_last_frame(oracle, ctx):
+    sf = scale_factors(ctx)
+    cap = ctx.orb_capacity
+    fr = make_chain(37, [pose(tx=0.02), pose()], n=cap, keep=400)
+    assert len(fr[0].keys) == cap
+    res = DeviceBatch(ctx, fr).search(7.0)
+    for j in range(2):
+        exp = oracle_pair(oracle, sf, fr[j], fr[j + 1], 7.0)
+        assert exp[0] >= 100
+        assert_pair(res, j, exp, cap)
+
+
+@pytest.mark.parametrize("n_frames", [0, 1])
+def test_no_pairs(ctx, n_frames):
+    import torch
+    db = DeviceBatch(ctx, chain3()[:n_frames])
+    out = tuple(torch.full(s, 7, dtype=torch.int32, device="cuda") for s in ((2, ctx.orb_capacity), (2, ctx.orb_capacity), (2,)))
+    db.search(7.0, out=out)
+    torch.cuda.synchronize()
+    assert all(bool((t == 7).all()) for t in out)
+
+
+# ---- 5: per-pair radii -------------------------------------------------------------------------------------------------------------------
+def test_per_pair_radius(oracle, ctx):
+    import torch
+    sf = scale_factors(ctx)
+    fr = make_chain(41, [pose(tx=0.02), pose(), pose(tz=0.3)])
+    db = DeviceBatch(ctx, fr)
+    cap = ctx.orb_capacity
+    out = tuple(torch.full(s, 7, dtype=torch.int32, device="cuda") for s in ((3, cap), (3, cap), (3,)))
+    db.search(3.0, d_th=torch.tensor([7.0, 0.0, 14.0], device="cuda"), out=out)
+    assert bool((out[0][1] == 7).all()) and bool((out[1][1] == 7).all()) and int(out[2][1].item()) == 7
+    for j, th in ((0, 7.0), (2, 14.0)):
+        exp = oracle_pair(oracle, sf, fr[j], fr[j + 1], th)
+        assert exp[0] >= 100
+        assert_pair(out, j, exp, cap)
+
+
+def test_retry_with_doubled_radius(oracle, ctx):
+    """src/Tracking.cc:1299-1303: `if(nmatches<20)` search again with 2*th -- a second call whose radii are formed on the device"""
+    import torch
+    sf = scale_factors(ctx)
+    th = 7.0
+    fr = make_chain(43, [pose(tx=0.02), pose(), pose(tx=-0.02)], far=(2,), max_octave=1)      # frame 2 sits 9 .. 13 px off its prediction
+    db = DeviceBatch(ctx, fr)
+    res = db.search(th)
+    d_th = torch.where(res[2] < 20, torch.tensor(2 * th, device="cuda"), torch.tensor(0.0, device="cuda")).to(torch.float32)
+    res = db.search(th, d_th=d_th, out=res)
+    retried = []
+    for j in range(3):
+        exp = oracle_pair(oracle, sf, fr[j], fr[j + 1], th)
+        if exp[0] < 20:
+            retried.append(j)
+            exp = oracle_pair(oracle, sf, fr[j], fr[j + 1], 2 * th)
+        assert exp[0] >= 100
+        assert_pair(res, j, exp, ctx.orb_capacity)
+    assert retried == [1]
+
+
+# ---- 6, 7 ---------------------------------------------------------------------------------------------------------------------------------
+def test_optional_planes_null(oracle, ctx):
+    sf = scale_factors(ctx)
+    fr = chain3()
+    res = DeviceBatch(ctx, fr).search(7.0, planes=False)
+
+    def defaults(v):
+        v.mp_valid[:], v.mp_obs[:], v.mvbOutlier[:] = True, True, False
+        v.mp_desc = v.mDescriptors.copy()
+    for j in range(2):
+        exp = oracle_pair(oracle, sf, fr[j], fr[j + 1], 7.0, edit=defaults)
+        assert exp[0] >= 100 and exp[1].tolist() != oracle_pair(oracle, sf, fr[j], fr[j + 1], 7.0)[1].tolist()
+        assert_pair(res, j, exp, ctx.orb_capacity)
+
+
+@pytest.mark.parametrize("th,bMono,check", [(7.0, False, True), (15.0, True, False)])
+def test_agrees_with_host_entry(ctx, th, bMono, check):
+    sf = scale_factors(ctx)
+    fr = chain3()[:2]
+    res = DeviceBatch(ctx, fr).search(th, bMono=bMono, check=check)
+    last, cur = fr[0].view(sf), fr[1].view(sf)
+    cur.mp_valid[:], cur.mp_obs[:] = False, False
+    m12 = {}
+    n_h, m_h = ola.ORBmatcher(0.9, check).SearchByProjection(cur, last, th, bMono, m12)
+    assert n_h >= 100
+    assert_pair(res, 0, (n_h, m_h, list(m12.items())), ctx.orb_capacity)
+
+
+# ---- 8: extracted frames, end to end on the context's buffers -----------------------------------------------------------------------------
+def test_end_to_end_on_extracted_frames(oracle):
+    import torch
+    w, h, th = 640, 480, 7.0
+    p = oracle.full_params(2000, 500)
+    fe = ola.StereoFrontEnd(p, w, h, max_pairs=3)
+    imgs = np.zeros((6, h, w), np.uint8)
+    imgs[:2] = synth.stereo_batch(41, 1, w, h)
+    imgs[2:4], imgs[4:6] = np.roll(imgs[:2], 3, axis=2), np.roll(imgs[:2], 6, axis=2)
+    f = fe.frames(imgs)
+    fx, cx, cy, mbf = float(p.stereo.fx), w / 2.0, h / 2.0, float(p.stereo.bf)
+    Tcw = np.tile(np.eye(4, dtype=f32), (3, 1, 1))
+    Tcw[:, 0, 3] = 0.02                                      # small predicted translation
+    mask = fe.stereo_points_mask()
+    world = fe.unproject_stereo((fx, fx, cx, cy), np.tile(np.eye(4, dtype=f32), (3, 1, 1)))
+    res = fe.search_by_projection_batch(Tcw, world, (fx, fx, cx, cy, mbf), th, mp_valid=mask)
+    sf = scale_factors(fe.ctx)
+    world_h, mask_h = world.cpu().numpy(), mask.cpu().numpy().astype(bool)
+    views = []
+    for i in range(3):
+        g = f.pair(i)
+        n = len(g["mvKeys"])
+        v = ola.FrameView(g["mvKeys"], g["mDescriptors"], g["mvuRight"], sf, fx, fx, cx, cy, mbf, (0.0, float(w), 0.0, float(h)), mTcw=Tcw[i])
+        assert np.array_equal(mask_h[i, :n], g["mvDepth"] > 0)      # (past N the depth plane, and so the mask, is unspecified: the search stops at N)
+        assert not world_h[i, n:].any()
+        v.mp_valid, v.mp_world, v.mp_desc, v.mp_obs = mask_h[i, :n].copy(), world_h[i, :n].copy(), v.mDescriptors.copy(), np.ones(n, bool)
+        views.append(v)
+    for j in range(2):
+        cur = copy.deepcopy(views[j + 1])
+        cur.mp_valid[:], cur.mp_obs[:] = False, False
+        n, m, pairs, _ = oracle.search_by_projection_match12(cur, views[j], th, False, checkOri=True)
+        assert n >= 100
+        assert_pair(res, j, (n, m, pairs), fe.ctx.orb_capacity)
+
+
+# ---- 9: Frame::UnprojectStereo ------------------------------------------------------------------------------------------------------------
+def test_unproject_stereo(ctx):
+    import torch
+    cap = ctx.orb_capacity
+    rng = np.random.default_rng(3)
+    counts = np.array([cap, 65, 1, 0, cap, cap], np.int32)
+    nf = len(counts)
+    a, b = np.deg2rad(20.0), np.deg2rad(-35.0)
+    Ry = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+    Rx = np.array([[1, 0, 0], [0, np.cos(b), -np.sin(b)], [0, np.sin(b), np.cos(b)]])
+    Twc = np.tile(np.eye(4, dtype=f32), (nf, 1, 1))
+    Twc[1, :3, 3] = Twc[4, :3, 3] = [0.3, -1.25, 7.5]          # pure translation
+    Twc[2, :3, :3] = Twc[3, :3, :3] = Twc[5, :3, :3] = (Ry @ Rx).astype(f32)
+    Twc[5, :3, 3] = [-2.0, 0.1, 0.7]                           # general pose
+    kps = np.zeros((nf, cap), KEYPOINT_DTYPE)
+    kps["x"], kps["y"] = rng.uniform(0, 320, (nf, cap)).astype(f32), rng.uniform(0, 240, (nf, cap)).astype(f32)
+    special = np.array([-1.0, 0.0, -0.0, np.nan, 1e-42, 0.5, 37.25], f32)
+    depth = rng.uniform(0.5, 40, (nf, cap)).astype(f32)
+    depth[:, :49] = np.tile(special, 7)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    fx, fy, cx, cy = f32(200.0), f32(187.5), f32(160.25), f32(119.5)
+    world = matcher.unproject_stereo(nf, up(kps.view(np.uint8).reshape(nf, cap, 28)), up(counts), up(depth), (fx, fy, cx, cy), up(Twc), img_stride=1,
+                                     out=torch.full((nf, cap, 3), 9.0, dtype=torch.float32, device="cuda"), context=ctx).cpu().numpy()
+    # the reference's expression in numpy: float32 left to right, mRwc * x3Dc + mOw under C.12 (three float products summed in float, the translation
+    # added in double, one rounding)
+    with np.errstate(all="ignore"):
+        invfx, invfy = f32(1.0) / fx, f32(1.0) / fy
+        x = ((kps["x"] - cx) * depth * invfx).astype(f32)
+        y = ((kps["y"] - cy) * depth * invfy).astype(f32)
+        exp = np.zeros((nf, cap, 3), f32)
+        for r in range(3):
+            R = Twc[:, r, :3][:, None, :]
+            t = ((R[..., 0] * x).astype(f32) + (R[..., 1] * y).astype(f32)).astype(f32)
+            t = (t + (R[..., 2] * depth).astype(f32)).astype(f32)
+            exp[..., r] = (t.astype(np.float64) + Twc[:, r, 3].astype(np.float64)[:, None]).astype(f32)
+    live = (depth > 0) & (np.arange(cap)[None, :] < counts[:, None])
+    exp[~live] = 0
+    assert live[0, 4] and live[0, 5] and not live[0, :4].any()          # 1e-42 is a point; -1, 0, -0 and NaN are not
+    assert np.array_equal(world.view(np.uint32), exp.view(np.uint32))
+
+
+# ---- 10: errors ----------------------------------------------------------------------------------------------------------------------------
+def test_bad_arguments(ctx):
+    db = DeviceBatch(ctx, chain3())
+    full = dict(kps=db.kps, desc=db.desc, counts=db.counts, uright=db.uright, cell_offsets=db.offs, cell_index=db.idx, Tcw=db.Tcw, mp_world=db.world)
+
+    def call(tb, m, n):
+        return lib().olf_search_by_projection_batch_dev(ctx.handle, C.byref(tb), 3, 7.0, None, 0, 1, m.data_ptr() if m is not None else None, None,
+                                                        n.data_ptr() if n is not None else None, None)
+
+    def fill(skip=None, bounds=BOUNDS):
+        t = _lib.TrackBatchC()
+        for k, v in full.items():
+            setattr(t, k, None if k == skip else v.data_ptr())
+        t.img_stride = 1
+        t.fx, t.fy, t.cx, t.cy, t.mbf = CAM
+        t.minX, t.maxX, t.minY, t.maxY = bounds
+        return t
+    import torch
+    m = torch.full((2, ctx.orb_capacity), -1, dtype=torch.int32, device="cuda")
+    n = torch.zeros(2, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()                                # (stream NULL = the context's own stream)
+    assert call(fill(), m, n) == 0
+    for k in full:
+        assert call(fill(skip=k), m, n) == OLF_ERR_INVALID, k
+    assert call(fill(), None, n) == OLF_ERR_INVALID and call(fill(), m, None) == OLF_ERR_INVALID
+    assert lib().olf_search_by_projection_batch_dev(None, C.byref(fill()), 3, 7.0, None, 0, 1, m.data_ptr(), None, n.data_ptr(), None) == OLF_ERR_INVALID
+    assert call(fill(bounds=(320.0, 320.0, 0.0, 240.0)), m, n) == OLF_ERR_INVALID
+    assert call(fill(bounds=(0.0, 320.0, 240.0, 0.0)), m, n) == OLF_ERR_INVALID
+    t = fill()
+    t.img_stride = 0
+    assert call(t, m, n) == OLF_ERR_INVALID
+    rc = lib().olf_unproject_stereo_dev(ctx.handle, 3, 1, db.kps.data_ptr(), db.counts.data_ptr(), None, 200.0, 200.0, 160.0, 120.0, db.Tcw.data_ptr(),
+                                        db.world.data_ptr(), None)
+    assert rc == OLF_ERR_INVALID
+    ctx.synchronize()
+
+
+def test_context_above_grid_max_keys():
+    p = _lib.default_params()
+    p.orb.nfeatures = _lib.GRID_MAX_KEYS + 1
+    big = _lib.Context(p, W, H, 1)
+    try:
+        assert big.orb_capacity > _lib.GRID_MAX_KEYS
+        import torch
+        one = torch.zeros(64, dtype=torch.int32, device="cuda")
+        t = _lib.TrackBatchC()
+        for k in ("kps", "desc", "counts", "uright", "cell_offsets", "cell_index", "Tcw", "mp_world"):
+            setattr(t, k, one.data_ptr())                   # (never read: the call is refused first)
+        t.img_stride, t.minX, t.maxX, t.minY, t.maxY = 1, *BOUNDS
+        rc = lib().olf_search_by_projection_batch_dev(big.handle, C.byref(t), 2, 7.0, None, 0, 1, one.data_ptr(), None, one.data_ptr(), None)
+        assert rc == OLF_ERR_CAPACITY
+    finally:
+        big.close()
+
+
+def test_octave_outside_the_levels(oracle, ctx):
+    """a caller-made key whose octave would index past mvScaleFactors: invalid input, rejected -- its pair ends with nmatches = -1 and untouched rows, the
+    context's status word reports it, and the neighbouring pair is exact"""
+    import torch
+    sf = scale_factors(ctx)
+    fr = [copy.deepcopy(f) for f in chain3()]
+    m0 = oracle_pair(oracle, sf, fr[0], fr[1], 7.0)[1]
+    i = int(m0[m0 >= 0][3])                                   # a feature whose window the search reaches
+    fr[0].keys["octave"][i] = ctx.nlevels
+    db = DeviceBatch(ctx, fr)
+    cap = ctx.orb_capacity
+    out = tuple(torch.full(s, 7, dtype=torch.int32, device="cuda") for s in ((2, cap), (2, cap), (2,)))
+    db.search(7.0, out=out)
+    torch.cuda.synchronize()
+    assert int(out[2][0].item()) == -1 and bool((out[0][0] == 7).all()) and bool((out[1][0] == 7).all())
+    with pytest.raises(ola.OlfError) as e:
+        ctx.poll_status()
+    assert e.value.code == OLF_ERR_CAPACITY and "flags=256" in str(e.value)
+    ctx.poll_status()                                       # reported once, then clear
+    exp = oracle_pair(oracle, sf, fr[1], fr[2], 7.0)
+    assert exp[0] >= 100
+    assert_pair(out, 1, exp, cap)
