@@ -508,6 +508,65 @@ int olf_search_by_projection_batch_dev(olf_ctx* ctx, const olf_track_batch* in, 
 int olf_unproject_stereo_dev(olf_ctx* ctx, int n_frames, int img_stride, const olf_keypoint* d_kps, const int32_t* d_counts, const float* d_depth,
                              float fx, float fy, float cx, float cy, const float* d_Twc, float* d_world, void* stream);
 
+/* ---- Tracking::SearchLocalPoints for a batch on the device (csrc/local_batch.hip) ------------------------------------------------------------------
+ * The point half of Tracking::SearchLocalPointsAndLines (src/Tracking.cc:1877-1942): Frame::isInFrustum for every local map point, then
+ * ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th).
+ *
+ * The map the frames of a batch are matched against, as arrays of n_mp points (device pointers), and optionally each frame's mvpLocalMapPoints as a
+ * list of indices into them.  Entries: with list_offsets, entry e in [list_offsets[j], list_offsets[j + 1]) is the (e - list_offsets[j])-th local map
+ * point of frame j, the point list_index[e] -- the reference's iteration order; list_offsets[n_frames] <= n_entries.  With list_offsets == NULL every
+ * frame sees all n_mp points in index order: entry e = j * n_mp + i is point i for frame j, there are n_frames * n_mp entries, and list_index / n_entries
+ * are not read.  Every per-entry array of the two calls below is indexed by e. */
+typedef struct olf_local_map {
+    const float*   world;         /* [n_mp][3] GetWorldPos()                                                                       */
+    const float*   normal;        /* [n_mp][3] GetNormal()                                                                         */
+    const float*   maxd;          /* [n_mp] mfMaxDistance, unscaled (GetMaxDistanceInvariance() / 1.2f), as olf_is_in_frustum      */
+    const float*   mind;          /* [n_mp] mfMinDistance, unscaled                                                                */
+    const uint8_t* desc;          /* [n_mp][32] GetDescriptor(), 16-byte aligned                                                   */
+    const uint8_t* obs;           /* [n_mp] Observations() > 0                                                                     */
+    const uint8_t* bad;           /* [n_mp] isBad()                                                                                */
+    int32_t        n_mp;
+    const int32_t* list_offsets;  /* [n_frames + 1], non-decreasing from >= 0, or NULL                                             */
+    const int32_t* list_index;    /* [n_entries]                                                                                   */
+    int32_t        n_entries;
+} olf_local_map;
+/* int MapPoint::PredictScale(const float &currentDist, Frame* pF) (src/MapPoint.cc:414-429) as a table.  Host only, no context.  thr[k - 1], for
+ * k = 1 .. n_levels - 1, is the smallest positive float `ratio` (= mfMaxDistance / currentDist) at which the host searches' own evaluation of PredictScale
+ * (csrc/predict_scale.hpp: ceil(logf(ratio) / logf(scale_factors[1])), clamped to [0, n_levels - 1]) returns >= k -- found by bisection over the float bit
+ * patterns on that function, so the predicted level is the number of thresholds <= ratio and the device needs no logarithm.  That rests on the level not
+ * decreasing with the ratio, which is a property of the libm in use: the call checks the 4096 floats on either side of every threshold and returns
+ * OLF_ERR_INVALID if the level is not constant on each side (or if a level is never reached, or scale_factors[1] <= 1).  thr [n_levels - 1]; n_levels = 1
+ * writes nothing. */
+int olf_predict_scale_thresholds(const float* scale_factors, int n_levels, float* thr);
+/* bool Frame::isInFrustum(MapPoint *pMP, float viewingCosLimit) (src/Frame.cc:388-444) for every entry of every frame, with the two tests
+ * Tracking::SearchLocalPointsAndLines makes first (src/Tracking.cc:1880-1896, :1921-1924).  Arithmetic: that of olf_is_in_frustum, operation for
+ * operation; the level comes from olf_predict_scale_thresholds of the context's mvScaleFactors.  `in`: only Tcw, the calibration and the bounds are read --
+ * and counts (with img_stride) when d_frame_mp is given and counts is not NULL: frame j then holds d_frame_mp[j][0 .. N).
+ * d_frame_mp [n_frames][capacity] (or NULL: the frames hold nothing): mvpMapPoints on entry as indices into the map; negative = none, or a point outside
+ * the map (a temporal point).  A held point that is bad is dropped from its feature first, as :1885-1888 does.
+ * An entry is skipped (in view = 0) when its point is bad (:1923) or is held by a feature of its frame (mnLastFrameSeen == mCurrentFrame.mnId, :1921).
+ * Outputs per entry: d_in_view (uint8, mbTrackInView), d_level (mnTrackScaleLevel), d_view_cos (mTrackViewCos), d_proj3 (mTrackProjX, mTrackProjY,
+ * mTrackProjXR); an entry that is skipped or fails a gate only gets in view = 0, as with olf_is_in_frustum.  MapPoint::IncreaseVisible (:1891, :1928) is
+ * the caller's, from d_frame_mp and d_in_view.  A list index outside [0, n_mp) is left out (in view = 0) and a d_frame_mp value >= n_mp counts as "holds
+ * nothing"; either sets bit 512 of the context's status word (olf_ctx_synchronize / olf_ctx_poll_status).  Entries outside every frame's list get
+ * in view = 0.  Scratch: one bit per (frame, map point). */
+int olf_is_in_frustum_batch_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const olf_local_map* map, const int32_t* d_frame_mp,
+                                float viewing_cos_limit, uint8_t* d_in_view, int32_t* d_level, float* d_view_cos, float* d_proj3, void* stream);
+/* The frustum pass above (into context scratch), then int ORBmatcher::SearchByProjection(Frame &F, const vector<MapPoint*> &vpMapPoints, const float th)
+ * (src/ORBmatcher.cc:47-131) for every frame, F.mvpMapPoints being d_frame_mp without its bad points.  `in`: kps, desc, counts, img_stride, uright, the
+ * grids of olf_frame_grid_dev, Tcw, the calibration and the bounds are read; mvScaleFactors are the context's.  d_th (or NULL) [n_frames]: a radius
+ * factor per frame that replaces th (the reference uses 1, 3 and 5, src/Tracking.cc:1935-1940); an entry <= 0 skips the frame and leaves its rows
+ * untouched.  bFactor is `th != 1.0` of the factor in force for the frame.  mfNNratio = nnratio and viewing_cos_limit (0.8 and 0.5 at this call site).
+ * d_matches [n_frames][capacity]: the MAP index feature idx received in this call (-1: none; -1 from N on); d_nmatches [n_frames]: the return values --
+ * they count events: a feature that receives a point without observations can receive another one later, and both count (as olf_search_local_map).
+ * Results equal a loop of olf_is_in_frustum + olf_search_local_map over the frames.  There is no capacity to exceed: the search keeps 16 bytes per entry
+ * and recomputes an entry that outgrows them.  Errors: contexts above OLF_GRID_MAX_KEYS: OLF_ERR_CAPACITY; maxX <= minX, maxY <= minY or a NULL
+ * required pointer: OLF_ERR_INVALID.  Malformed indices as above (bit 512), never out of bounds.  n_frames == 0 writes nothing; no entries: the rows
+ * are -1 / 0.  Scratch: 37 bytes per entry, one bit per (frame, map point) and per (frame, feature). */
+int olf_search_local_map_batch_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const olf_local_map* map, const int32_t* d_frame_mp,
+                                   float viewing_cos_limit, float th, const float* d_th, float nnratio, int32_t* d_matches, int32_t* d_nmatches,
+                                   void* stream);
+
 /* measurement: rate of a plain 16-byte-per-thread device copy kernel over `bytes` (read + written bytes per second): the practical HBM
  * ceiling bench.py reports next to the specification's 8 TB/s */
 int olf_debug_copy_bandwidth(olf_ctx* ctx, size_t bytes, int reps, double* gbytes_per_s);

@@ -73,6 +73,12 @@ class TrackBatchC(C.Structure):
                 [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "mbf", "minX", "maxX", "minY", "maxY")])
 
 
+class LocalMapC(C.Structure):
+    """olf_local_map (include/orbline.h): the local map of a batch as device arrays, and optionally each frame's list of indices into it"""
+    _fields_ = ([(n, C.c_void_p) for n in ("world", "normal", "maxd", "mind", "desc", "obs", "bad")] + [("n_mp", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("list_offsets", "list_index")] + [("n_entries", C.c_int32)])
+
+
 # Frame::mGrid as two int32 arrays (include/orbline_types.h) and one Frame::GetFeaturesInArea call
 GRID_COLS, GRID_ROWS, GRID_CELLS, GRID_MAX_KEYS = 64, 48, 3072, 8192
 AREA_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("r", "<f4"), ("min_level", "<i4"), ("max_level", "<i4")])
@@ -184,6 +190,10 @@ def lib():
         L.olf_search_by_projection_batch_dev.argtypes = [C.c_void_p, C.POINTER(TrackBatchC), C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int,
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.olf_unproject_stereo_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p] * 3
+        L.olf_predict_scale_thresholds.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.olf_is_in_frustum_batch_dev.argtypes = [C.c_void_p, C.POINTER(TrackBatchC), C.c_int, C.POINTER(LocalMapC), C.c_void_p, C.c_float] + [C.c_void_p] * 5
+        L.olf_search_local_map_batch_dev.argtypes = [C.c_void_p, C.POINTER(TrackBatchC), C.c_int, C.POINTER(LocalMapC), C.c_void_p, C.c_float, C.c_float,
+                                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         L.olf_debug_copy_bandwidth.argtypes =[C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
         L.olf_debug_fdiv_sweep.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         L.olf_debug_sqrtq_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]

@@ -90,6 +90,9 @@ struct olf_ctx {
     void* scratch[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t scratch_bytes[4] = {0, 0, 0, 0};
     std::vector<void*> allocs;
+    // olf_predict_scale_thresholds of the context's own scale factors, built by the first call that needs it (level_thr_rc > 0: not built yet)
+    float level_thr[OLF_MAX_LEVELS] = {0};
+    int level_thr_rc = 1;
 };
 
 // A context (and everything it owns) lives on the device that was current when it was created; calling into it with another device
@@ -187,6 +190,13 @@ int ctx_scratch(olf_ctx* c, int slot, size_t bytes, void** out) { return scratch
 int* ctx_status(olf_ctx* c) { return c->ob.status; }
 int ctx_check_device(const olf_ctx* c, const char* who) { return check_device(c, who); }
 int ctx_orb_levels(const olf_ctx* c) { return c->params.orb.nlevels; }
+int ctx_level_thresholds(olf_ctx* c, float* thr)
+{
+    const int n = c->params.orb.nlevels;
+    if (c->level_thr_rc > 0) c->level_thr_rc = n <= OLF_MAX_LEVELS ? olf_predict_scale_thresholds(c->orb.sf.data(), n, c->level_thr) : OLF_ERR_INVALID;
+    for (int k = 0; k + 1 < n && c->level_thr_rc == OLF_OK; ++k) thr[k] = c->level_thr[k];
+    return c->level_thr_rc;
+}
 }
 
 enum { ST_ORB_PYRAMID, ST_ORB_FAST, ST_ORB_OCTREE, ST_ORB_BLUR, ST_ORB_DESCRIBE, ST_STEREO_POINTS, ST_LSD_FRONT, ST_LSD_GROW, ST_LSD_RECT, ST_LINE_LBD,
@@ -548,7 +558,7 @@ static int check_status(olf_ctx* c)
     if (st[0]) {
         (void)hipMemset(c->ob.status, 0, 16);
         set_error("device capacity overflow, flags=" + std::to_string(st[0]) +
-                  " (1/2/4: ORB corner / candidate / key point buffers, 8: LSD regions, segments or pixel-list pool, 16: LSD growth watchdog, 32: frame record buffer, 64: LSD seed sort, final-range list of the grid-wide top levels, 128: candidate list of olf_features_in_area_dev, 256: olf_search_by_projection_batch_dev skipped a pair whose last frame holds an octave outside the context's levels)");
+                  " (1/2/4: ORB corner / candidate / key point buffers, 8: LSD regions, segments or pixel-list pool, 16: LSD growth watchdog, 32: frame record buffer, 64: LSD seed sort, final-range list of the grid-wide top levels, 128: candidate list of olf_features_in_area_dev, 256: olf_search_by_projection_batch_dev skipped a pair whose last frame holds an octave outside the context's levels, 512: olf_is_in_frustum_batch_dev / olf_search_local_map_batch_dev met a list index or a d_frame_mp value outside the map)");
         return OLF_ERR_CAPACITY;
     }
     return OLF_OK;

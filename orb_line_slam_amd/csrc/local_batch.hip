@@ -1,0 +1,504 @@
+// local_batch.hip -- the point half of Tracking::SearchLocalPointsAndLines (src/Tracking.cc:1877-1942) for a whole batch of frames on the device:
+// Frame::isInFrustum (src/Frame.cc:388-444) for every (frame, local map point), then ORBmatcher::SearchByProjection(Frame &F, const vector<MapPoint*>&, th)
+// (src/ORBmatcher.cc:47-131).  The arithmetic is that of search_host.cpp (olf_is_in_frustum, olf_search_local_map): convention C.12 for the cv::Mat
+// products, no contraction (-ffp-contract=off), correctly rounded divisions and square root.
+//
+// Only one thing in the matcher's loop depends on the order of the map points: a feature is passed over while the point it holds has observations
+// (:89-91), and a point that is assigned changes that (:125).  Everything else -- radius, grid walk, level gates, the mvuRight gate, the distance -- is a
+// function of (frame, point) alone.  The reference's running best / second best (:104-116) ends as the first two elements of the candidates sorted stably
+// by distance (a candidate at distance 256 never registers, :112), so a point's outcome is decided by the first two UNBLOCKED entries of that sorted list:
+//   k_local_held     one thread per (frame, feature): the bitmap of map points a frame holds (the mnLastFrameSeen test, src/Tracking.cc:1921), and the
+//                    features blocked from the start (they hold a point with observations; a blocked feature stays blocked)
+//   k_local_frustum  one thread per (frame, entry): Frame::isInFrustum; the level from the table of olf_predict_scale_thresholds, no logarithm
+//   k_local_lists    one wave per (frame, entry in view): walks the window as k_features_in_area does and keeps the LB_K best candidates that are not
+//                    blocked from the start, in (distance, scan position) order, each with "octave == predicted level", plus "there were more" (16 bytes
+//                    per entry).  No cut at TH_HIGH: the second best decides the ratio test at any distance
+//   k_local_walk     one workgroup per frame: one wave walks the entries in list order against the blocked bits in LDS; an entry whose kept candidates
+//                    do not yield two unblocked ones although the window held more is recomputed on the spot by the wave, with the blocked test inside
+//                    the scan -- there is no capacity and no approximate case
+// (lb_scan is tb_scan of track_batch.hip on this file's argument block: the walk of k_features_in_area, grid.hip.)
+#include <algorithm>
+#include "olf_internal.hpp"
+#include "../../include/orbline.h"
+
+namespace olf {
+
+hipStream_t ctx_stream(olf_ctx* c);
+int ctx_scratch(olf_ctx* c, int slot, size_t bytes, void** out);
+int* ctx_status(olf_ctx* c);
+int ctx_check_device(const olf_ctx* c, const char* who);
+int ctx_orb_levels(const olf_ctx* c);
+int ctx_level_thresholds(olf_ctx* c, float* thr);
+
+constexpr int LB_TH_HIGH = 100;                     // src/ORBmatcher.cc:39
+constexpr int LB_K = 4;                             // candidates kept per entry (one uint4)
+constexpr int LB_ROWS = OLF_GRID_ROWS, LB_COLS = OLF_GRID_COLS;
+// a kept candidate: distance << 18 | (octave == predicted level) << 13 | feature (< OLF_GRID_MAX_KEYS = 2^13); the first word of a list also carries two flags
+constexpr unsigned LB_NONE = 0x3fffffffu, LB_OBS = 1u << 30, LB_MORE = 1u << 31;
+constexpr int LB_NOKEY = 0x7fffffff;
+constexpr int LB_STATUS_INDEX = 512;                // status bit: a list index or a d_frame_mp value outside the map
+static_assert(OLF_GRID_MAX_KEYS <= (1 << 13), "candidate layout");
+
+struct LocalArgs {
+    olf_track_batch in;
+    olf_local_map map;
+    const int* frame_mp;
+    int n_frames, n_entries, cap, nlevels;
+    int mpW, capW;                 // per frame: 32-bit words of the held bitmap, 64-bit words of the blocked bitmap
+    float cosLimit, th, nnratio;
+    const float* d_th;
+    float wInv, hInv;
+    float sf[OLF_MAX_LEVELS];      // mvScaleFactors
+    float thr[OLF_MAX_LEVELS];     // olf_predict_scale_thresholds
+};
+
+struct LbFrame {
+    const olf_keypoint* k;
+    const uint4* d;
+    const float* ur;
+    const int *offs, *idx;
+    int n;
+};
+
+struct LbQuery {
+    float u, v, xr, radius;
+    int level;
+};
+
+// the frame entry e belongs to (-1: none) and its map index (unchecked)
+__device__ __forceinline__ int lb_frame_of(const LocalArgs& A, int e, int& mi)
+{
+    if (!A.map.list_offsets) {
+        const int j = e / A.map.n_mp;
+        mi = e - j * A.map.n_mp;
+        return j;
+    }
+    const int* o = A.map.list_offsets;
+    int lo = 0, hi = A.n_frames;                    // the last frame whose list starts at or before e
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (o[mid] <= e) lo = mid; else hi = mid;
+    }
+    mi = A.map.list_index[e];
+    return (e >= o[lo] && e < o[lo + 1]) ? lo : -1;
+}
+
+// the entries of frame j, inside [0, n_entries) whatever the offsets hold
+__device__ __forceinline__ void lb_range(const LocalArgs& A, int j, int& b, int& e)
+{
+    if (!A.map.list_offsets) { b = j * A.map.n_mp; e = b + A.map.n_mp; return; }
+    b = min(max(A.map.list_offsets[j], 0), A.n_entries);
+    e = min(max(A.map.list_offsets[j + 1], b), A.n_entries);
+}
+
+__device__ __forceinline__ int lb_count(const LocalArgs& A, int j)
+{
+    return A.in.counts ? min(max(A.in.counts[(size_t)j * A.in.img_stride], 0), A.cap) : A.cap;
+}
+
+// the radius factor of frame j; false: the frame is skipped (d_th[j] <= 0)
+__device__ __forceinline__ bool lb_radius(const LocalArgs& A, int j, float& th)
+{
+    th = A.th;
+    if (!A.d_th) return true;
+    th = A.d_th[j];
+    return th > 0.f;
+}
+
+__device__ __forceinline__ LbFrame lb_frame(const LocalArgs& A, int j)
+{
+    const olf_track_batch& in = A.in;
+    const size_t cap = (size_t)A.cap, f = (size_t)j, st = (size_t)in.img_stride;
+    LbFrame F;
+    F.k = in.kps + f * st * cap;
+    F.d = reinterpret_cast<const uint4*>(in.desc + 32 * f * st * cap);
+    F.ur = in.uright + f * cap;
+    F.offs = in.cell_offsets + f * (OLF_GRID_CELLS + 1);
+    F.idx = in.cell_index + f * cap;
+    F.n = lb_count(A, j);
+    return F;
+}
+
+__global__ __launch_bounds__(256) void k_local_held(LocalArgs A, unsigned* __restrict__ held, unsigned long long* __restrict__ blk0, int* __restrict__ status)
+{
+    const int j = blockIdx.y, idx = blockIdx.x * 256 + threadIdx.x;
+    bool blocked = false;
+    if (idx < lb_count(A, j)) {
+        const int v = A.frame_mp[(size_t)j * A.cap + idx];
+        if (v >= A.map.n_mp) atomicOr(status, LB_STATUS_INDEX);
+        else if (v >= 0 && !A.map.bad[v]) {                          // (a bad point is dropped from its feature, src/Tracking.cc:1885-1888)
+            atomicOr(&held[(size_t)j * A.mpW + (v >> 5)], 1u << (v & 31));
+            blocked = blk0 && A.map.obs[v] != 0;
+        }
+    }
+    const unsigned long long m = wave_vote(blocked);
+    if (blk0 && (threadIdx.x & 63) == 0 && (idx >> 6) < A.capW) blk0[(size_t)j * A.capW + (idx >> 6)] = m;
+}
+
+// Frame::isInFrustum as olf_is_in_frustum evaluates it (search_host.cpp)
+__global__ __launch_bounds__(256) void k_local_frustum(LocalArgs A, const unsigned* __restrict__ held, uint8_t* __restrict__ in_view, int* __restrict__ level,
+                                                      float* __restrict__ view_cos, float* __restrict__ proj3, int* __restrict__ status)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= A.n_entries) return;
+    int i = -1;
+    const int j = lb_frame_of(A, e, i);
+    in_view[e] = 0;
+    if (j < 0) return;
+    if ((unsigned)i >= (unsigned)A.map.n_mp) { atomicOr(status, LB_STATUS_INDEX); return; }
+    if (A.map.bad[i]) return;
+    if (held && ((held[(size_t)j * A.mpW + (i >> 5)] >> (i & 31)) & 1u)) return;
+    const olf_track_batch& in = A.in;
+    const float* T = in.Tcw + 16 * (size_t)j;
+    const float* P = A.map.world + 3 * (size_t)i;
+    const float* N = A.map.normal + 3 * (size_t)i;
+    float Ow[3], Pc[3];
+    for (int r = 0; r < 3; ++r) {                                    // mOw = -mRcw.t() * mtcw (camera_centre)
+        double acc = 0;
+        for (int k = 0; k < 3; ++k) acc += (double)T[4 * k + r] * (double)T[4 * k + 3];
+        Ow[r] = (float)(-acc);
+    }
+    for (int r = 0; r < 3; ++r) {                                    // rot_apply, C.12
+        const float t = T[4 * r] * P[0] + T[4 * r + 1] * P[1] + T[4 * r + 2] * P[2];
+        Pc[r] = (float)((double)t + (double)1.0f * (double)T[4 * r + 3]);
+    }
+    const float PcX = Pc[0], PcY = Pc[1], PcZ = Pc[2];
+    if (PcZ < 0.0f) return;
+    const float invz = __fdiv_rn(1.0f, PcZ);
+    const float u = in.fx * PcX * invz + in.cx, v = in.fy * PcY * invz + in.cy;
+    if (u < in.minX || u > in.maxX) return;
+    if (v < in.minY || v > in.maxY) return;
+    const float maxd = A.map.maxd[i];
+    const float maxDistance = 1.2f * maxd, minDistance = 0.8f * A.map.mind[i];
+    double nrm = 0, dot = 0;
+    for (int k = 0; k < 3; ++k) { const float po = P[k] - Ow[k]; nrm += (double)po * (double)po; dot += (double)po * (double)N[k]; }
+    const float dist = (float)__dsqrt_rn(nrm);
+    if (dist < minDistance || dist > maxDistance) return;
+    const float viewCos = (float)__ddiv_rn(dot, (double)dist);
+    if (viewCos < A.cosLimit) return;
+    const float ratio = __fdiv_rn(maxd, dist);                     // MapPoint::PredictScale: the number of thresholds <= ratio
+    int lv = 0;
+    for (int k = 0; k + 1 < A.nlevels; ++k) lv += A.thr[k] <= ratio ? 1 : 0;
+    level[e] = lv;
+    in_view[e] = 1;
+    proj3[3 * (size_t)e] = u; proj3[3 * (size_t)e + 1] = v; proj3[3 * (size_t)e + 2] = u - in.mbf * invz;
+    view_cos[e] = viewCos;
+}
+
+// the window of an entry in view (src/ORBmatcher.cc:62-71)
+__device__ __forceinline__ LbQuery lb_query(const LocalArgs& A, float th, int level, float viewCos, const float* p3)
+{
+    LbQuery q;
+    float r = viewCos > 0.998 ? 2.5f : 4.0f;                          // RadiusByViewingCos, :133-139
+    if (th != 1.0) r *= th;                                          // bFactor
+    q.level = min(max(level, 0), A.nlevels - 1);
+    q.radius = r * A.sf[q.level];
+    q.u = p3[0]; q.v = p3[1]; q.xr = p3[2];
+    return q;
+}
+
+// Frame::GetFeaturesInArea(u, v, radius, level - 1, level) on the frame's grid, by one wave: f(take, j, pos) is called by every lane for every chunk of 64
+// grid entries; `take` lanes hold feature j, the pos-th index the reference's vIndices would hold (ix outer, iy inner, stored order inside a cell).  Entries
+// that a malformed grid points outside the frame are left out.
+template <class F>
+__device__ __forceinline__ void lb_scan(const LbFrame& P, const LocalArgs& A, const LbQuery& q, int lane, F&& f)
+{
+    const float x = q.u, y = q.v, r = q.radius, minX = A.in.minX, minY = A.in.minY;
+    const float fx0 = floorf((x - minX - r) * A.wInv), fx1 = ceilf((x - minX + r) * A.wInv);
+    const float fy0 = floorf((y - minY - r) * A.hInv), fy1 = ceilf((y - minY + r) * A.hInv);
+    if (!(fx0 < (float)LB_COLS) || !(fx1 >= 0.f) || !(fy0 < (float)LB_ROWS) || !(fy1 >= 0.f)) return;
+    const int nMinCellX = fx0 < 0.f ? 0 : (int)fx0, nMaxCellX = fx1 > (float)(LB_COLS - 1) ? LB_COLS - 1 : (int)fx1;
+    const int nMinCellY = fy0 < 0.f ? 0 : (int)fy0, nMaxCellY = fy1 > (float)(LB_ROWS - 1) ? LB_ROWS - 1 : (int)fy1;
+    if (nMinCellY > nMaxCellY) return;
+    const int minLevel = q.level - 1, maxLevel = q.level;           // (maxLevel >= 0: the levels are always checked)
+    int total = 0;
+    for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
+        const int p0 = max(P.offs[ix * LB_ROWS + nMinCellY], 0), p1 = min(P.offs[ix * LB_ROWS + nMaxCellY + 1], A.cap);
+        for (int pb = p0; pb < p1; pb += 64) {
+            const int p = pb + lane;
+            bool take = false;
+            int j = 0;
+            if (p < p1) {
+                j = P.idx[p];
+                if ((unsigned)j < (unsigned)P.n) {
+                    const olf_keypoint& kp = P.k[j];
+                    take = !(kp.octave < minLevel) && !(kp.octave > maxLevel);
+                    const float distx = kp.x - x, disty = kp.y - y;
+                    if (!(fabsf(distx) < r && fabsf(disty) < r)) take = false;
+                }
+            }
+            const unsigned long long m = wave_vote(take);
+            f(take, j, total + wave_rank_below(m));
+            total += __popcll(m);
+        }
+    }
+}
+
+// the tests on one candidate that do not depend on the blocked state (:93-102).  true: the candidate registers as best or second best (distance < 256);
+// key orders such candidates as the reference's scan does, ent is the kept form
+__device__ __forceinline__ bool lb_candidate(const LbFrame& P, const LbQuery& q, const uint4& a0, const uint4& a1, int j, int pos, int& key, unsigned& ent)
+{
+    const float uR = P.ur[j];
+    if (uR > 0) {
+        const float er = fabsf(q.xr - uR);
+        if (er > q.radius) return false;
+    }
+    const uint4 x0 = P.d[2 * (size_t)j], x1 = P.d[2 * (size_t)j + 1];
+    const int dist = __popc(a0.x ^ x0.x) + __popc(a0.y ^ x0.y) + __popc(a0.z ^ x0.z) + __popc(a0.w ^ x0.w) + __popc(a1.x ^ x1.x) + __popc(a1.y ^ x1.y) +
+                     __popc(a1.z ^ x1.z) + __popc(a1.w ^ x1.w);
+    if (dist >= 256) return false;
+    key = (dist << 16) | pos;
+    ent = ((unsigned)dist << 18) | (P.k[j].octave == q.level ? 1u << 13 : 0u) | (unsigned)j;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_local_lists(LocalArgs A, const uint8_t* __restrict__ in_view, const int* __restrict__ level,
+                                                    const float* __restrict__ view_cos, const float* __restrict__ proj3,
+                                                    const unsigned long long* __restrict__ blk0, uint4* __restrict__ lists)
+{
+    const int e = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (e >= A.n_entries) return;                                    // (wave-uniform, as every branch on e below)
+    int i = -1;
+    const int j = lb_frame_of(A, e, i);
+    unsigned out[LB_K] = {LB_NONE, LB_NONE, LB_NONE, LB_NONE};
+    int cnt = 0;
+    bool obs = false;
+    float th;
+    if (j >= 0 && in_view[e] && lb_radius(A, j, th)) {               // (in view: i is inside the map; a skipped frame's entries get empty lists)
+        const LbFrame P = lb_frame(A, j);
+        const LbQuery q = lb_query(A, th, level[e], view_cos[e], proj3 + 3 * (size_t)e);
+        const uint4* md = reinterpret_cast<const uint4*>(A.map.desc) + 2 * (size_t)i;
+        const uint4 a0 = md[0], a1 = md[1];
+        const unsigned long long* b0 = blk0 + (size_t)j * A.capW;
+        obs = A.map.obs[i] != 0;
+        // every lane keeps the LB_K smallest keys it meets, ascending; the LB_K smallest of the window are among them
+        int h0 = LB_NOKEY, h1 = LB_NOKEY, h2 = LB_NOKEY, h3 = LB_NOKEY;
+        unsigned e0 = LB_NONE, e1 = LB_NONE, e2 = LB_NONE, e3 = LB_NONE;
+        lb_scan(P, A, q, lane, [&](bool take, int j2, int pos) {
+            int key = LB_NOKEY;
+            unsigned ent = LB_NONE;
+            const bool ok = take && !((b0[j2 >> 6] >> (j2 & 63)) & 1ull) && lb_candidate(P, q, a0, a1, j2, pos, key, ent);
+            cnt += __popcll(wave_vote(ok));
+            if (ok && key < h3) {
+                h3 = key; e3 = ent;
+                if (h3 < h2) { const int t = h2; h2 = h3; h3 = t; const unsigned u = e2; e2 = e3; e3 = u; }
+                if (h2 < h1) { const int t = h1; h1 = h2; h2 = t; const unsigned u = e1; e1 = e2; e2 = u; }
+                if (h1 < h0) { const int t = h0; h0 = h1; h1 = t; const unsigned u = e0; e0 = e1; e1 = u; }
+            }
+        });
+        for (int k = 0; k < LB_K; ++k) {
+            const int m = wave_min_i32(h0);
+            if (m == LB_NOKEY) break;
+            const bool mine = h0 == m;                               // keys are distinct: one lane
+            const int owner = __ffsll((long long)wave_vote(mine)) - 1;
+            out[k] = (unsigned)__shfl((int)e0, owner, 64);
+            if (mine) { h0 = h1; e0 = e1; h1 = h2; e1 = e2; h2 = h3; e2 = e3; h3 = LB_NOKEY; e3 = LB_NONE; }
+        }
+    }
+    if (lane == 0) {
+        unsigned x = out[0];
+        if (cnt > LB_K) x |= LB_MORE;
+        if (obs) x |= LB_OBS;
+        lists[e] = make_uint4(x, out[1], out[2], out[3]);
+    }
+}
+
+// the window of entry e again, with the blocked test inside the scan: the first two candidates of the sorted list that are not blocked now (LB_NONE: none)
+__device__ __forceinline__ void lb_rescan(const LbFrame& P, const LocalArgs& A, const LbQuery& q, int i, int lane, const unsigned* s_blk, unsigned& c1, unsigned& c2)
+{
+    const uint4* md = reinterpret_cast<const uint4*>(A.map.desc) + 2 * (size_t)i;
+    const uint4 a0 = md[0], a1 = md[1];
+    int k1 = LB_NOKEY, k2 = LB_NOKEY;
+    c1 = c2 = LB_NONE;
+    lb_scan(P, A, q, lane, [&](bool take, int j2, int pos) {
+        int key = LB_NOKEY;
+        unsigned ent = LB_NONE;
+        const bool ok = take && !((s_blk[j2 >> 5] >> (j2 & 31)) & 1u) && lb_candidate(P, q, a0, a1, j2, pos, key, ent);
+        if (!ok) key = LB_NOKEY;
+        for (int t = 0; t < 2; ++t) {                                // the chunk's two smallest keys, merged into the running two (keys are distinct)
+            const int m = wave_min_i32(key);
+            if (m >= k2) break;
+            const int owner = __ffsll((long long)wave_vote(key == m)) - 1;
+            const unsigned em = (unsigned)__shfl((int)ent, owner, 64);
+            if (m < k1) { k2 = k1; c2 = c1; k1 = m; c1 = em; }
+            else { k2 = m; c2 = em; }
+            if (lane == owner) key = LB_NOKEY;
+        }
+    });
+}
+
+// One workgroup per frame; dynamic LDS: cap ints (the map index a feature received), then 2 * capW words (blocked bits).
+__global__ __launch_bounds__(256) void k_local_walk(LocalArgs A, const uint4* __restrict__ lists, const int* __restrict__ level, const float* __restrict__ view_cos,
+                                                   const float* __restrict__ proj3, const unsigned long long* __restrict__ blk0, int* __restrict__ matches,
+                                                   int* __restrict__ nmatches)
+{
+    extern __shared__ int s_match[];
+    __shared__ int s_n;
+    unsigned* s_blk = reinterpret_cast<unsigned*>(s_match + A.cap);
+    const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, cap = A.cap;
+    float th;
+    if (!lb_radius(A, j, th)) return;
+    const LbFrame P = lb_frame(A, j);
+    const unsigned* b0 = reinterpret_cast<const unsigned*>(blk0 + (size_t)j * A.capW);
+    for (int i = tid; i < cap; i += 256) s_match[i] = -1;
+    for (int w = tid; w < 2 * A.capW; w += 256) s_blk[w] = b0[w];
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    if (tid < 64) {
+        int n = 0, eb, ee;
+        lb_range(A, j, eb, ee);
+        for (int c0 = eb; c0 < ee; c0 += 64) {
+            const int e = c0 + lane;
+            uint4 L = make_uint4(LB_NONE, LB_NONE, LB_NONE, LB_NONE);
+            int mi = -1;
+            if (e < ee) { L = lists[e]; mi = A.map.list_offsets ? A.map.list_index[e] : e - eb; }
+            unsigned long long todo = wave_vote((L.x & LB_NONE) != LB_NONE);
+            while (todo) {
+                const int l = __ffsll((long long)todo) - 1;
+                todo &= todo - 1;
+                const unsigned x = (unsigned)__shfl((int)L.x, l, 64);
+                const unsigned k[LB_K] = {x & LB_NONE, (unsigned)__shfl((int)L.y, l, 64), (unsigned)__shfl((int)L.z, l, 64), (unsigned)__shfl((int)L.w, l, 64)};
+                const int i = __shfl(mi, l, 64);
+                // the first two kept candidates that are not blocked now
+                unsigned c1 = LB_NONE, c2 = LB_NONE;
+                bool complete = false;                               // the kept candidates decide the entry
+                for (int t = 0; t < LB_K; ++t) {
+                    if (k[t] == LB_NONE) { complete = true; break; }
+                    const unsigned f = k[t] & 0x1fffu;
+                    if (f >= (unsigned)P.n || ((s_blk[f >> 5] >> (f & 31)) & 1u)) continue;
+                    if (c1 == LB_NONE) {
+                        c1 = k[t];
+                        if ((int)(c1 >> 18) > LB_TH_HIGH) { complete = true; break; }      // (bestDist > TH_HIGH: the second best is not looked at, :120)
+                    } else { c2 = k[t]; complete = true; break; }
+                }
+                if (!complete && !(x & LB_MORE)) complete = true;
+                if (!complete && c1 == LB_NONE && (int)(k[LB_K - 1] >> 18) > LB_TH_HIGH) complete = true;      // (whatever follows is no nearer)
+                if (!complete) {
+                    const int e1 = c0 + l;
+                    lb_rescan(P, A, lb_query(A, th, level[e1], view_cos[e1], proj3 + 3 * (size_t)e1), i, lane, s_blk, c1, c2);
+                }
+                if (c1 == LB_NONE) continue;
+                const int bestDist = (int)(c1 >> 18);
+                if (bestDist > LB_TH_HIGH) continue;
+                // Apply ratio to second match (only if best and second are in the same scale level), :119-123 -- without a second: bestLevel2 = -1
+                if (c2 != LB_NONE && ((c1 ^ c2) & (1u << 13)) == 0 && (float)bestDist > A.nnratio * (float)(int)(c2 >> 18)) continue;
+                const unsigned f = c1 & 0x1fffu;
+                s_match[f] = i;                                       // (every lane stores the same values: the next entry's reads are ordered behind them)
+                if (x & LB_OBS) s_blk[f >> 5] |= 1u << (f & 31);
+                ++n;
+            }
+        }
+        if (lane == 0) s_n = n;
+    }
+    __syncthreads();
+    for (int i = tid; i < cap; i += 256) matches[(size_t)j * cap + i] = s_match[i];
+    if (tid == 0) nmatches[j] = s_n;
+}
+
+}  // namespace olf
+
+using namespace olf;
+
+namespace {
+
+// the checks and the argument block the two entries share; n_entries is formed here when the map carries no lists
+int local_args(olf_ctx* c, const char* who, const olf_track_batch* in, int n_frames, const olf_local_map* map, bool search, LocalArgs& A)
+{
+    const std::string w(who);
+    if (!c || !in || !map || n_frames < 0 || map->n_mp < 0 || !in->Tcw || !(in->maxX > in->minX) || !(in->maxY > in->minY) ||
+        (map->n_mp && (!map->world || !map->normal || !map->maxd || !map->mind || !map->bad)) ||
+        (map->list_offsets && (map->n_entries < 0 || (map->n_entries && !map->list_index))) ||
+        (search && (!in->kps || !in->desc || !in->counts || in->img_stride < 1 || !in->uright || !in->cell_offsets || !in->cell_index ||
+                    (map->n_mp && (!map->desc || !map->obs))))) {
+        set_error(w + ": bad argument"); return OLF_ERR_INVALID;
+    }
+    const int rcd = ctx_check_device(c, who);
+    if (rcd != OLF_OK) return rcd;
+    const int cap = olf_orb_capacity(c);
+    if (cap > OLF_GRID_MAX_KEYS) { set_error(w + ": more than OLF_GRID_MAX_KEYS key points per frame (a kept candidate holds 13 index bits)"); return OLF_ERR_CAPACITY; }
+    const long long ne = map->list_offsets ? (long long)map->n_entries : (long long)n_frames * map->n_mp;
+    if (ne > 0x7fffffffLL - 256) { set_error(w + ": more than 2^31 entries"); return OLF_ERR_CAPACITY; }
+    A.in = *in; A.map = *map;
+    A.frame_mp = nullptr;
+    A.n_frames = n_frames; A.n_entries = (int)ne; A.cap = cap;
+    A.nlevels = std::min(ctx_orb_levels(c), (int)OLF_MAX_LEVELS);
+    A.mpW = (map->n_mp + 31) / 32; A.capW = (cap + 63) / 64;
+    A.cosLimit = 0.f; A.th = 1.f; A.nnratio = 0.f; A.d_th = nullptr;
+    // mfGridElementWidthInv / mfGridElementHeightInv, src/Frame.cc:186-187
+    A.wInv = static_cast<float>(OLF_GRID_COLS) / (in->maxX - in->minX);
+    A.hInv = static_cast<float>(OLF_GRID_ROWS) / (in->maxY - in->minY);
+    for (int l = 0; l < OLF_MAX_LEVELS; ++l) { A.sf[l] = 1.f; A.thr[l] = 0.f; }
+    olf_orb_scale_tables(c, A.sf, nullptr, nullptr, nullptr, nullptr);
+    return ctx_level_thresholds(c, A.thr);
+}
+
+size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// the held / blocked bitmaps, then the frustum pass
+int launch_frustum(olf_ctx* c, const LocalArgs& A, unsigned* held, unsigned long long* blk0, uint8_t* in_view, int* level, float* view_cos, float* proj3, hipStream_t s)
+{
+    const size_t bh = (size_t)A.n_frames * A.mpW * 4;
+    const bool scatter = A.frame_mp != nullptr;
+    if (bh) OLF_HIP_CHECK(hipMemsetAsync(held, 0, bh, s));
+    if (blk0 && !scatter) OLF_HIP_CHECK(hipMemsetAsync(blk0, 0, (size_t)A.n_frames * A.capW * 8, s));
+    if (scatter) hipLaunchKernelGGL(k_local_held, dim3((A.cap + 255) / 256, A.n_frames), dim3(256), 0, s, A, held, blk0, ctx_status(c));
+    if (A.n_entries) hipLaunchKernelGGL(k_local_frustum, dim3((A.n_entries + 255) / 256), dim3(256), 0, s, A, scatter ? held : nullptr, in_view, level, view_cos, proj3, ctx_status(c));
+    OLF_HIP_CHECK(hipGetLastError());
+    return OLF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int olf_is_in_frustum_batch_dev(olf_ctx* c, const olf_track_batch* in, int n_frames, const olf_local_map* map, const int32_t* d_frame_mp,
+                                float viewing_cos_limit, uint8_t* d_in_view, int32_t* d_level, float* d_view_cos, float* d_proj3, void* stream)
+{
+    LocalArgs A;
+    const int rc = local_args(c, "olf_is_in_frustum_batch_dev", in, n_frames, map, false, A);
+    if (rc != OLF_OK) return rc;
+    if (d_frame_mp && in->counts && in->img_stride < 1) { set_error("olf_is_in_frustum_batch_dev: bad argument"); return OLF_ERR_INVALID; }
+    if (n_frames == 0 || A.n_entries == 0) return OLF_OK;
+    if (!d_in_view || !d_level || !d_view_cos || !d_proj3) { set_error("olf_is_in_frustum_batch_dev: bad argument"); return OLF_ERR_INVALID; }
+    A.frame_mp = d_frame_mp; A.cosLimit = viewing_cos_limit;
+    void* st = nullptr;
+    const int rs = ctx_scratch(c, 2, (size_t)n_frames * A.mpW * 4 + 64, &st);
+    if (rs != OLF_OK) return rs;
+    return launch_frustum(c, A, (unsigned*)st, nullptr, d_in_view, d_level, d_view_cos, d_proj3, stream ? (hipStream_t)stream : ctx_stream(c));
+}
+
+int olf_search_local_map_batch_dev(olf_ctx* c, const olf_track_batch* in, int n_frames, const olf_local_map* map, const int32_t* d_frame_mp,
+                                   float viewing_cos_limit, float th, const float* d_th, float nnratio, int32_t* d_matches, int32_t* d_nmatches,
+                                   void* stream)
+{
+    LocalArgs A;
+    const int rc = local_args(c, "olf_search_local_map_batch_dev", in, n_frames, map, true, A);
+    if (rc != OLF_OK) return rc;
+    if (!d_matches || !d_nmatches) { set_error("olf_search_local_map_batch_dev: bad argument"); return OLF_ERR_INVALID; }
+    if (n_frames == 0) return OLF_OK;
+    A.frame_mp = d_frame_mp; A.cosLimit = viewing_cos_limit; A.th = th; A.d_th = d_th; A.nnratio = nnratio;
+    // scratch, 37 bytes per entry: the kept candidates (16), mTrackProjX / Y / XR (12), mnTrackScaleLevel (4), mTrackViewCos (4), mbTrackInView (1); then the bitmaps
+    const size_t ne = (size_t)A.n_entries;
+    const size_t bl = ne * 16, bp = up16(ne * 12), b4 = up16(ne * 4), bv = up16(ne), bh = up16((size_t)n_frames * A.mpW * 4), bb = (size_t)n_frames * A.capW * 8;
+    void* st = nullptr;
+    const int rs = ctx_scratch(c, 2, bl + bp + 2 * b4 + bv + bh + bb + 64, &st);
+    if (rs != OLF_OK) return rs;
+    uint8_t* p = (uint8_t*)st;
+    uint4* lists = (uint4*)p; p += bl;
+    float* proj3 = (float*)p; p += bp;
+    int* level = (int*)p; p += b4;
+    float* view_cos = (float*)p; p += b4;
+    uint8_t* in_view = p; p += bv;
+    unsigned* held = (unsigned*)p; p += bh;
+    unsigned long long* blk0 = (unsigned long long*)p;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
+    const int rf = launch_frustum(c, A, held, blk0, in_view, level, view_cos, proj3, s);
+    if (rf != OLF_OK) return rf;
+    if (A.n_entries) hipLaunchKernelGGL(k_local_lists, dim3((A.n_entries + 3) / 4), dim3(256), 0, s, A, in_view, level, view_cos, proj3, blk0, lists);
+    const size_t lds = (size_t)A.cap * 4 + (size_t)A.capW * 8;
+    hipLaunchKernelGGL(k_local_walk, dim3(n_frames), dim3(256), lds, s, A, lists, level, view_cos, proj3, blk0, d_matches, d_nmatches);
+    OLF_HIP_CHECK(hipGetLastError());
+    return OLF_OK;
+}
+
+}  // extern "C"

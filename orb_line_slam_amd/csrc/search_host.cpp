@@ -17,6 +17,7 @@
 #include <vector>
 #include "../../include/orbline.h"
 #include "olf_internal.hpp"
+#include "predict_scale.hpp"
 
 #define OLF_TRY(expr) do { const int _rc = (expr); if (_rc != OLF_OK) return _rc; } while (0)
 
@@ -467,15 +468,8 @@ void r3_apply(const float* R9, const float* v, const float* t3, float* out, doub
     }
 }
 
-int predict_scale(float maxd, float dist, float logScaleFactor, int nLevels)       // MapPoint::PredictScale, src/MapPoint.cc:414-429
-{
-    const float ratio = maxd / dist;
-    int n = (int)std::ceil(std::log(ratio) / logScaleFactor);
-    if (n < 0) n = 0; else if (n >= nLevels) n = nLevels - 1;
-    return n;
-}
-
-float log_scale_factor(const olf_frame_view& f) { return f.n_levels > 1 ? std::log(f.scale_factors[1]) : 1.0f; }    // mfLogScaleFactor
+// (predict_scale: predict_scale.hpp)
+float log_scale_factor(const olf_frame_view& f) { return olf::log_scale_factor(f.scale_factors, f.n_levels); }
 
 // pinhole projection + IsInImage (half-open, KeyFrame::IsInImage)
 bool project_in_image(const olf_frame_view& K, const float* p3Dc, float& u, float& v, float& invz)
@@ -528,6 +522,33 @@ int olf_is_in_frustum(const olf_frame_view* f, int n_mp, const float* world, con
         track_in_view[i] = 1;
         track_proj3[3 * (size_t)i] = u; track_proj3[3 * (size_t)i + 1] = v; track_proj3[3 * (size_t)i + 2] = u - f->mbf * invz;
         track_view_cos[i] = viewCos;
+    }
+    return OLF_OK;
+}
+
+// The ratios at which predict_scale steps, found on predict_scale itself: thr[k - 1] = the smallest positive float whose level is >= k.  The level is a
+// non-decreasing function of the ratio wherever ceil(logf(ratio) / logSF) is (a property of the libm in use, checked around every threshold below), so
+// "the number of thresholds <= ratio" is the level.
+int olf_predict_scale_thresholds(const float* scale_factors, int n_levels, float* thr)
+{
+    if (!scale_factors || n_levels < 1 || n_levels > OLF_MAX_LEVELS || (n_levels > 1 && !thr)) { set_error("olf_predict_scale_thresholds: bad argument"); return OLF_ERR_INVALID; }
+    const float logSF = log_scale_factor(scale_factors, n_levels);
+    if (!(logSF > 0.f)) { set_error("olf_predict_scale_thresholds: the scale factor must exceed 1"); return OLF_ERR_INVALID; }
+    auto level = [&](uint32_t bits) { float r; std::memcpy(&r, &bits, 4); return predict_scale(r, 1.0f, logSF, n_levels); };      // (r / 1.0f == r)
+    constexpr uint32_t kMinPos = 0x00000001u, kMaxFinite = 0x7f7fffffu, kNear = 4096;
+    for (int k = 1; k < n_levels; ++k) {
+        uint32_t lo = kMinPos, hi = kMaxFinite;          // positive floats order as their bit patterns do
+        if (level(lo) >= k || level(hi) < k) { set_error("olf_predict_scale_thresholds: level " + std::to_string(k) + " has no threshold"); return OLF_ERR_INVALID; }
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (level(mid) >= k) hi = mid; else lo = mid;
+        }
+        const int below = level(lo), above = level(hi);
+        for (uint32_t d = 1; d < kNear; ++d) {
+            const bool okLo = lo - kMinPos < d || level(lo - d) == below, okHi = kMaxFinite - hi < d || level(hi + d) == above;
+            if (!okLo || !okHi) { set_error("olf_predict_scale_thresholds: the level is not monotone around the threshold of level " + std::to_string(k)); return OLF_ERR_INVALID; }
+        }
+        std::memcpy(&thr[k - 1], &hi, 4);
     }
     return OLF_OK;
 }

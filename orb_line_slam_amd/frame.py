@@ -202,6 +202,29 @@ class StereoFrontEnd:
                                                   bMono=bMono, checkOri=checkOri, img_stride=2, mp_valid=mp_valid, mp_obs=mp_obs, outlier=outlier,
                                                   mp_desc=mp_desc, d_th=d_th, match12=match12, out=out, context=self.ctx)
 
+    def search_local_map_batch(self, Tcw, local_map, camera, th=1.0, nnratio=0.8, viewingCosLimit=0.5, bounds=None, frame_mp=None, d_th=None, out=None):
+        """The point half of Tracking::SearchLocalPointsAndLines (src/Tracking.cc:1877-1942) for the left frames of the last frames() call, on the
+        context's device buffers: olf_frame_grid_dev, then olf_search_local_map_batch_dev -- nothing is downloaded.  Tcw [n_pairs, 4, 4] float32
+        (numpy or device tensor); local_map: a matcher.LocalMapDev; camera = (fx, fy, cx, cy, mbf); bounds default to the image.  The other
+        arguments and the result (matches [n_pairs, capacity] as map indices, nmatches [n_pairs]: device tensors) are those of
+        matcher.search_local_map_batch."""
+        import torch
+        from . import matcher
+        fb, n = self._last_frames("search_local_map_batch")
+        cap = self.ctx.orb_capacity
+        minX, maxX, minY, maxY = (0.0, float(self.width), 0.0, float(self.height)) if bounds is None else (float(v) for v in bounds)
+        Tcw = torch.as_tensor(np.ascontiguousarray(Tcw, np.float32) if isinstance(Tcw, np.ndarray) else Tcw).cuda().contiguous()
+        if tuple(Tcw.shape) != (n, 4, 4):
+            raise ValueError("search_local_map_batch: Tcw has one 4 x 4 matrix per stereo pair of the last frames() call")
+        offs = torch.zeros((n, _lib.GRID_CELLS + 1), dtype=torch.int32, device="cuda")
+        idx = torch.zeros((n, cap), dtype=torch.int32, device="cuda")
+        with matcher._torch_stream() as s:
+            check(lib().olf_frame_grid_dev(self.ctx.handle, n, 2, fb.kps, fb.counts, minX, maxX, minY, maxY, C.c_void_p(offs.data_ptr()),
+                                           C.c_void_p(idx.data_ptr()), s), "olf_frame_grid_dev")
+        return matcher.search_local_map_batch(n, fb.kps, fb.desc, fb.counts, fb.uright, offs, idx, Tcw, local_map, camera, (minX, maxX, minY, maxY), th=th,
+                                              nnratio=nnratio, viewingCosLimit=viewingCosLimit, frame_mp=frame_mp, d_th=d_th, img_stride=2, out=out,
+                                              context=self.ctx)
+
 
 def assign_features_to_grid(keys, bounds, context=None):
     """Frame::AssignFeaturesToGrid (src/Frame.cc:334-349) for one frame's key points (KEYPOINT_DTYPE, mvKeysUn) on the device: olf_frame_grid.

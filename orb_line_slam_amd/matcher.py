@@ -396,6 +396,100 @@ def unproject_stereo(n_frames, kps, counts, depth, camera, Twc, img_stride=2, ou
     return world
 
 
+def predict_scale_thresholds(scale_factors):
+    """olf_predict_scale_thresholds: the ratios mfMaxDistance / dist at which MapPoint::PredictScale (src/MapPoint.cc:414-429) steps, as float32
+    [n_levels - 1]; the predicted level of a ratio is the number of thresholds <= it.  Host arithmetic, no device, no context."""
+    sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+    thr = np.zeros(max(len(sf) - 1, 0), np.float32)
+    check(lib().olf_predict_scale_thresholds(ptr(sf), len(sf), ptr(thr) if len(thr) else None), "olf_predict_scale_thresholds")
+    return thr
+
+
+class LocalMapDev:
+    """olf_local_map (include/orbline.h): the local map a batch of frames is matched against, as device tensors over n_mp points -- world, normal
+    [n_mp, 3] float32, maxd / mind [n_mp] float32 (mfMaxDistance / mfMinDistance, unscaled), desc [n_mp, 32] uint8, obs / bad [n_mp] uint8 -- and
+    optionally every frame's mvpLocalMapPoints as (list_offsets [n_frames + 1], list_index [n_entries]) int32.  Without lists every frame sees all
+    points in index order.  n_mp: the number of points (default: the length of bad)."""
+
+    def __init__(self, world, normal, maxd, mind, desc, obs, bad, list_offsets=None, list_index=None, n_mp=None):
+        self.world, self.normal, self.maxd, self.mind, self.desc, self.obs, self.bad = world, normal, maxd, mind, desc, obs, bad
+        self.list_offsets, self.list_index = list_offsets, list_index
+        self.n_mp = int(bad.shape[0]) if n_mp is None else int(n_mp)
+
+    def n_entries(self, n_frames):
+        if self.list_offsets is None:
+            return int(n_frames) * self.n_mp
+        return 0 if self.list_index is None else int(self.list_index.shape[0])
+
+    def c(self, n_frames):
+        import torch
+        m = _lib.LocalMapC()
+        f, b, i = torch.float32, torch.uint8, torch.int32
+        m.world, m.normal, m.maxd, m.mind = (_dev(getattr(self, k), f, k) for k in ("world", "normal", "maxd", "mind"))
+        m.desc, m.obs, m.bad = (_dev(getattr(self, k), b, k) for k in ("desc", "obs", "bad"))
+        m.n_mp = self.n_mp
+        m.list_offsets, m.list_index, m.n_entries = _dev(self.list_offsets, i, "list_offsets"), _dev(self.list_index, i, "list_index"), self.n_entries(n_frames)
+        return m
+
+
+def _track_batch_c(kps, desc, counts, img_stride, uright, cell_offsets, cell_index, Tcw, camera, bounds):
+    import torch
+    tb = _lib.TrackBatchC()
+    tb.kps, tb.desc, tb.counts, tb.img_stride = _dev(kps, None, "kps"), _dev(desc, torch.uint8, "desc"), _dev(counts, torch.int32, "counts"), int(img_stride)
+    tb.uright, tb.cell_offsets, tb.cell_index = _dev(uright, torch.float32, "uright"), _dev(cell_offsets, torch.int32, "cell_offsets"), _dev(cell_index, torch.int32, "cell_index")
+    tb.Tcw = _dev(Tcw, torch.float32, "Tcw")
+    tb.fx, tb.fy, tb.cx, tb.cy, tb.mbf = (float(v) for v in camera)
+    tb.minX, tb.maxX, tb.minY, tb.maxY = (float(v) for v in bounds)
+    return tb
+
+
+def is_in_frustum_batch(n_frames, Tcw, local_map, camera, bounds, viewingCosLimit=0.5, frame_mp=None, counts=None, img_stride=2, out=None, context=None):
+    """Frame::isInFrustum (src/Frame.cc:388-444) for every (frame, local map point) of a device-resident batch, with the bad / already-held tests of
+    Tracking::SearchLocalPointsAndLines (src/Tracking.cc:1880-1896, :1921-1924): olf_is_in_frustum_batch_dev (include/orbline.h).  Tcw [n_frames, 4, 4];
+    local_map: a LocalMapDev; camera = (fx, fy, cx, cy, mbf); bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY); frame_mp int32 [n_frames, capacity]: the
+    frames' mvpMapPoints as map indices (negative: none), counts (extractor layout, with img_stride): their N.  Runs on torch's current stream.
+    Returns (in_view uint8, level int32, view_cos float32, proj3 float32 [.., 3]) over the entries (LocalMapDev.n_entries); entries not in view keep
+    what `out` held (zeros by default) in the last three."""
+    import ctypes as C
+    import torch
+    ctx = _ctx(context)
+    ne = local_map.n_entries(n_frames)
+    tb = _track_batch_c(None, None, counts, img_stride, None, None, None, Tcw, camera, bounds)
+    lm = local_map.c(n_frames)
+    if out is None:
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda")
+        out = (z((ne,), torch.uint8), z((ne,), torch.int32), z((ne,), torch.float32), z((ne, 3), torch.float32))
+    v, l, c, p = out
+    with _torch_stream() as s:
+        check(lib().olf_is_in_frustum_batch_dev(ctx.handle, C.byref(tb), int(n_frames), C.byref(lm), _dev(frame_mp, torch.int32, "frame_mp"), float(viewingCosLimit),
+                                                _dev(v, torch.uint8, "in_view"), _dev(l, torch.int32, "level"), _dev(c, torch.float32, "view_cos"),
+                                                _dev(p, torch.float32, "proj3"), s), "olf_is_in_frustum_batch_dev")
+    return out
+
+
+def search_local_map_batch(n_frames, kps, desc, counts, uright, cell_offsets, cell_index, Tcw, local_map, camera, bounds, th=1.0, nnratio=0.8,
+                           viewingCosLimit=0.5, frame_mp=None, d_th=None, img_stride=2, out=None, context=None):
+    """The point half of Tracking::SearchLocalPointsAndLines (src/Tracking.cc:1877-1942) for a device-resident batch: Frame::isInFrustum for every
+    (frame, local map point), then ORBmatcher(nnratio).SearchByProjection(F, mvpLocalMapPoints, th) (src/ORBmatcher.cc:47-131) for every frame --
+    olf_search_local_map_batch_dev (include/orbline.h describes every array; csrc/local_batch.hip).  The frame arrays are those of
+    search_by_projection_batch; local_map: a LocalMapDev; frame_mp int32 [n_frames, capacity]: mvpMapPoints on entry as map indices (negative: none);
+    d_th float32 [n_frames]: per-frame radius factors (<= 0 skips a frame, whose rows of `out` keep what they hold).  out = (matches, nmatches).
+    Runs on torch's current stream.  Returns (matches [n_frames, capacity]: the map index feature idx received, -1 none; nmatches [n_frames])."""
+    import ctypes as C
+    import torch
+    ctx = _ctx(context)
+    tb = _track_batch_c(kps, desc, counts, img_stride, uright, cell_offsets, cell_index, Tcw, camera, bounds)
+    lm = local_map.c(n_frames)
+    if out is None:
+        out = (torch.full((int(n_frames), ctx.orb_capacity), -1, dtype=torch.int32, device="cuda"), torch.zeros((int(n_frames),), dtype=torch.int32, device="cuda"))
+    m, n = out
+    with _torch_stream() as s:
+        check(lib().olf_search_local_map_batch_dev(ctx.handle, C.byref(tb), int(n_frames), C.byref(lm), _dev(frame_mp, torch.int32, "frame_mp"), float(viewingCosLimit),
+                                                   float(th), _dev(d_th, torch.float32, "d_th"), float(nnratio), _dev(m, torch.int32, "matches"),
+                                                   _dev(n, torch.int32, "nmatches"), s), "olf_search_local_map_batch_dev")
+    return out
+
+
 class MapPointView:
     """The MapPoint members read by SearchByProjection(Frame&, const vector<MapPoint*>&, th) (src/ORBmatcher.cc:47-131), gathered by the
     host (mutex-guarded in the reference, src/MapPoint.cc:321-325) into SoA buffers:
