@@ -5,6 +5,7 @@
 // reference's children vector order), so a level is one 32*k-byte contiguous read.  The top levels (1 + k + k^2 + ... nodes) stay
 // in L2; the leaves' level is the only one that misses.  Strict '<' keeps the first minimum, like the reference's scan.
 #include "olf_internal.hpp"
+#include "device_math.hpp"
 
 namespace olf {
 
@@ -23,8 +24,7 @@ __global__ __launch_bounds__(256) void k_bow_descend(const uint4* __restrict__ s
         int best = b, bd = 257;
         for (int s = b; s < e; ++s) {
             const uint4 c0 = slotDesc[2 * (size_t)s], c1 = slotDesc[2 * (size_t)s + 1];
-            const int d = __popc(f0.x ^ c0.x) + __popc(f0.y ^ c0.y) + __popc(f0.z ^ c0.z) + __popc(f0.w ^ c0.w) + __popc(f1.x ^ c1.x) +
-                          __popc(f1.y ^ c1.y) + __popc(f1.z ^ c1.z) + __popc(f1.w ^ c1.w);
+            const int d = ham256(f0, f1, c0, c1);
             if (d < bd) { bd = d; best = s; }
         }
         node = slotNode[best];

@@ -22,8 +22,6 @@ struct olf_voc {
 namespace olf {
 int launch_bow_descend(const uint8_t* slotDesc, const int* childOff, const int* slotNode, const int* nodeWord, const double* nodeWeight,
                        const uint8_t* desc, int n, int nid_level, int* word, double* weight, int* nodeOut, hipStream_t s);
-hipStream_t ctx_stream(olf_ctx* c);
-int ctx_scratch(olf_ctx* c, int slot, size_t bytes, void** out);
 int launch_search_by_bow_batch(const uint8_t* slotDesc, const int* childOff, const int* slotNode, const double* nodeWeight, int nid_level, int n_frames,
                                int img_stride, int cap, const olf_keypoint* d_kps, const uint8_t* d_desc, const int* d_counts, const uint8_t* d_mp_valid,
                                const uint8_t* d_mp_bad, float nnratio, int check_ori, int* d_nodes, unsigned long long* d_sorted, int* d_m, int* d_matches,

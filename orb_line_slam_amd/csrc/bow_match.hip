@@ -13,10 +13,12 @@
 //                        wave walks them in index order, its lanes hold the node's features of F, best / second-best distance by wave reductions
 //                        with the reference's scan-order tie rule; then the rotation histogram (ComputeThreeMaxima, :1749-1790) per pair.
 #include "olf_internal.hpp"
+#include "device_math.hpp"
+#include "search_math.hpp"
 
 namespace olf {
 
-constexpr int BM_TH_LOW = 50, BM_HISTO = 30;      // src/ORBmatcher.cc:39-41
+constexpr int BM_TH_LOW = 50;                     // src/ORBmatcher.cc:40
 
 __global__ __launch_bounds__(256) void k_bow_descend_nodes(const uint4* __restrict__ slotDesc, const int* __restrict__ childOff, const int* __restrict__ slotNode,
                                                            const double* __restrict__ nodeWeight, const uint4* __restrict__ desc, const int* __restrict__ counts,
@@ -35,8 +37,7 @@ __global__ __launch_bounds__(256) void k_bow_descend_nodes(const uint4* __restri
             int best = b, bd = 257;
             for (int s = b; s < e; ++s) {
                 const uint4 c0 = slotDesc[2 * (size_t)s], c1 = slotDesc[2 * (size_t)s + 1];
-                const int dd = __popc(f0.x ^ c0.x) + __popc(f0.y ^ c0.y) + __popc(f0.z ^ c0.z) + __popc(f0.w ^ c0.w) + __popc(f1.x ^ c1.x) +
-                               __popc(f1.y ^ c1.y) + __popc(f1.z ^ c1.z) + __popc(f1.w ^ c1.w);
+                const int dd = ham256(f0, f1, c0, c1);
                 if (dd < bd) { bd = dd; best = s; }
             }
             node = slotNode[best];
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(64 * BM_WAVES) void k_search_by_bow(const unsigned 
                                                        int* __restrict__ matches, int* __restrict__ nmatches)
 {
     extern __shared__ int s_mem[];                   // matched[cap] (key-frame feature or -1), then one rotation bin byte per feature
-    __shared__ int s_hist[BM_HISTO], s_seg, s_n, s_keep[3];
+    __shared__ int s_hist[HISTO_LENGTH], s_seg, s_n, s_keep[3];
     int* matched = s_mem;
     uint8_t* binOf = reinterpret_cast<uint8_t*>(s_mem + cap);
     const int p = blockIdx.x, lane = threadIdx.x & 63;
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(64 * BM_WAVES) void k_search_by_bow(const unsigned 
     const uint4* dK = desc + 2 * (size_t)fK * img_stride * cap;
     const uint4* dF = desc + 2 * (size_t)fF * img_stride * cap;
     for (int i = threadIdx.x; i < cap; i += 64 * BM_WAVES) { matched[i] = -1; binOf[i] = 0; }
-    if (threadIdx.x < BM_HISTO) s_hist[threadIdx.x] = 0;
+    if (threadIdx.x < HISTO_LENGTH) s_hist[threadIdx.x] = 0;
     if (threadIdx.x == 0) { s_seg = 0; s_n = 0; }
     __syncthreads();
     // the key frame's list is cut into node segments on the fly: a wave claims the next unclaimed list position, finds the end of the node it
@@ -143,8 +144,7 @@ __global__ __launch_bounds__(64 * BM_WAVES) void k_search_by_bow(const unsigned 
                 int d = 0x7fff;
                 if (on && matched[iF] < 0) {
                     const uint4 x0 = dF[2 * (size_t)iF], x1 = dF[2 * (size_t)iF + 1];
-                    d = __popc(a0.x ^ x0.x) + __popc(a0.y ^ x0.y) + __popc(a0.z ^ x0.z) + __popc(a0.w ^ x0.w) + __popc(a1.x ^ x1.x) + __popc(a1.y ^ x1.y) +
-                        __popc(a1.z ^ x1.z) + __popc(a1.w ^ x1.w);
+                    d = ham256(a0, a1, x0, x1);
                 }
                 // smallest (distance, lane) of the chunk, then the smallest distance among the other lanes
                 // (DPP minima with a scalar result: the two 6-step butterflies through the LDS crossbar were the dependent chain of this serial walk)
@@ -162,10 +162,7 @@ __global__ __launch_bounds__(64 * BM_WAVES) void k_search_by_bow(const unsigned 
                 if (lane == 0) {
                     matched[bi] = iKF;
                     if (checkOri) {
-                        float rot = kK[iKF].angle - kF[bi].angle;
-                        if (rot < 0.0) rot += 360.0f;
-                        int bin = (int)roundf(rot * (1.0f / BM_HISTO));
-                        if (bin == BM_HISTO) bin = 0;
+                        const int bin = rot_bin(kK[iKF].angle, kF[bi].angle);
                         binOf[bi] = (uint8_t)bin;
                         atomicAdd(&s_hist[bin], 1);
                     }
@@ -178,15 +175,8 @@ __global__ __launch_bounds__(64 * BM_WAVES) void k_search_by_bow(const unsigned 
     __syncthreads();
     if (checkOri) {
         if (threadIdx.x == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;      // ComputeThreeMaxima, src/ORBmatcher.cc:1749-1790
-            for (int i = 0; i < BM_HISTO; i++) {
-                const int s = s_hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float)max1) ind3 = -1;
+            int ind1, ind2, ind3;
+            three_maxima(s_hist, ind1, ind2, ind3);
             s_keep[0] = ind1; s_keep[1] = ind2; s_keep[2] = ind3;
         }
         __syncthreads();

@@ -12,6 +12,7 @@
 //                     (read from libm.so.6's __sincosf_table); only IEEE double mul/add/sub and one
 //                     double->float rounding are involved, so device and host agree exactly.
 //                     tests/test_device_math.py sweeps it against the box's libm.
+//  * ham256         : the 256-bit Hamming distance of every matcher (device only)
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -235,5 +236,15 @@ OLF_HD float glibc_atan2f(float y, float x)
         default: return f_sub(f_sub(z, pi_lo), pi);
     }
 }
+
+#if defined(__HIPCC__)
+// ---- ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:1795-1811) of two 256-bit descriptors held as two uint4 each: XOR and v_bcnt
+__device__ __forceinline__ int ham256(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1)
+{
+    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
+           __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
+__device__ __forceinline__ int ham256(const uint4* a, const uint4* b) { return ham256(a[0], a[1], b[0], b[1]); }
+#endif
 
 }  // namespace olf

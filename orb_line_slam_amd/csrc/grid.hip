@@ -1,10 +1,11 @@
 // grid.hip -- Frame::mGrid on the device (layout: include/orbline_types.h, "Frame::mGrid as two arrays").
 //   k_assign_grid       Frame::AssignFeaturesToGrid + PosInGrid (src/Frame.cc:334-349, :572-582): one wave per frame, a stable counting sort of the
 //                       frame's key points by cell with the OLF_GRID_CELLS counters in LDS
-//   k_features_in_area  Frame::GetFeaturesInArea (src/Frame.cc:517-570) for many queries: one wave per query, once to count and once to fill
+//   k_features_in_area  Frame::GetFeaturesInArea (src/Frame.cc:517-570) for many queries: one wave per query (the walk: grid_walk.hpp), once to count and once to fill
 //   k_area_scan         the prefix sum between the two passes (one workgroup)
 // Float expressions are written as the reference writes them; the library is built with -ffp-contract=off.
-#include "olf_internal.hpp"
+#include <climits>
+#include "grid_walk.hpp"
 #include "../../include/orbline.h"
 
 namespace olf {
@@ -110,8 +111,7 @@ int launch_assign_grid(const olf_keypoint* d_kps, size_t frame_stride, const int
 
 // One wave per query, four queries per block.  fill == 0: cand_offsets[q + 1] = the number of indices GetFeaturesInArea returns for query q;
 // fill != 0 (cand_offsets scanned): the indices themselves at cand_idx[cand_offsets[q] ..), in the reference's order -- ix outer, iy inner, stored order
-// inside a cell.  The cells (ix, nMinCellY .. nMaxCellY) of a column are one range of cell_index: it is read 64 entries at a time and compacted by
-// vote + rank, which keeps the order.  Nothing is written at or past cand_capacity.
+// inside a cell (grid_walk's scan positions).  Nothing is written at or past cand_capacity.
 __global__ __launch_bounds__(256) void k_features_in_area(const olf_keypoint* __restrict__ keys, const int* __restrict__ cell_offsets,
                                                           const int* __restrict__ cell_index, float minX, float minY, float wInv, float hInv,
                                                           int n_queries, const olf_area_query* __restrict__ queries, int* __restrict__ cand_offsets,
@@ -119,46 +119,14 @@ __global__ __launch_bounds__(256) void k_features_in_area(const olf_keypoint* __
 {
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (q >= n_queries) return;                                   // (wave-uniform)
-    const float x = queries[q].x, y = queries[q].y, r = queries[q].r;
-    const int minLevel = queries[q].min_level, maxLevel = queries[q].max_level;
-    int total = 0;
-    // max(0,(int)floor(v)) then ">= COLS -> return", min(COLS-1,(int)ceil(v)) then "< 0 -> return": decided on the float so that no value outside int's
-    // range is ever converted (a NaN takes the early return)
-    const float fx0 = floorf((x - minX - r) * wInv), fx1 = ceilf((x - minX + r) * wInv);
-    const float fy0 = floorf((y - minY - r) * hInv), fy1 = ceilf((y - minY + r) * hInv);
-    const bool empty = !(fx0 < (float)kCols) || !(fx1 >= 0.f) || !(fy0 < (float)kRows) || !(fy1 >= 0.f);
-    if (!empty) {
-        const int nMinCellX = fx0 < 0.f ? 0 : (int)fx0, nMaxCellX = fx1 > (float)(kCols - 1) ? kCols - 1 : (int)fx1;
-        const int nMinCellY = fy0 < 0.f ? 0 : (int)fy0, nMaxCellY = fy1 > (float)(kRows - 1) ? kRows - 1 : (int)fy1;
-        const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-        const long long out0 = fill ? cand_offsets[q] : 0;
-        for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-            if (nMinCellY > nMaxCellY) break;
-            const int p0 = cell_offsets[ix * kRows + nMinCellY], p1 = cell_offsets[ix * kRows + nMaxCellY + 1];
-            for (int pb = p0; pb < p1; pb += 64) {
-                const int p = pb + lane;
-                bool take = false;
-                int j = 0;
-                if (p < p1) {
-                    j = cell_index[p];
-                    const olf_keypoint& kp = keys[j];
-                    take = true;
-                    if (bCheckLevels) {
-                        if (kp.octave < minLevel) take = false;
-                        if (maxLevel >= 0 && kp.octave > maxLevel) take = false;
-                    }
-                    const float distx = kp.x - x, disty = kp.y - y;
-                    if (!(fabsf(distx) < r && fabsf(disty) < r)) take = false;
-                }
-                const unsigned long long m = wave_vote(take);
-                if (fill && take) {
-                    const long long at = out0 + total + wave_rank_below(m);
-                    if (at < (long long)cand_capacity) cand_idx[at] = j;
-                }
-                total += __popcll(m);
-            }
+    const GridView G = {keys, cell_offsets, cell_index, INT_MAX, INT_MAX, minX, minY, wInv, hInv};      // (the entry knows neither the key count nor the index length)
+    const long long out0 = fill ? cand_offsets[q] : 0;
+    const int total = grid_walk(G, queries[q].x, queries[q].y, queries[q].r, queries[q].min_level, queries[q].max_level, lane, [&](bool take, int j, int pos) {
+        if (fill && take) {
+            const long long at = out0 + pos;
+            if (at < (long long)cand_capacity) cand_idx[at] = j;
         }
-    }
+    });
     if (!fill && lane == 0) cand_offsets[q + 1] = total;
 }
 

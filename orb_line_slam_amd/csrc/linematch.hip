@@ -23,13 +23,6 @@ struct LinePrep {
     unsigned char lo[GR], hi[GR];   // per grid row: first/last covered cell, lo > hi = row not covered
 };
 
-__device__ __forceinline__ int ham256_u4(const uint4* a, const uint4* b)
-{
-    const uint4 a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
-           __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
 // one thread per line (left and right): grid coordinates, direction, per-row cell spans
 __global__ __launch_bounds__(64) void k_lines_prep(const olf_keyline* __restrict__ kls, const int* __restrict__ counts, int cap, int W, int H,
                                                    LinePrep* __restrict__ prep)
@@ -108,7 +101,7 @@ __global__ __launch_bounds__(64) void k_lines_dist(const LinePrep* __restrict__ 
         if (in_window(R, Lp.spx, Lp.spy, ws) || in_window(R, Lp.epx, Lp.epy, ws)) {
             const double dt = d_add(d_mul(Lp.vx, R.vx), d_mul(Lp.vy, R.vy));
             if (!(fabs(dt) < sim_th)) {
-                const int d = ham256_u4(reinterpret_cast<const uint4*>(desc + ((size_t)(2 * pair) * cap + i1) * OLF_DESC_BYTES), dR);
+                const int d = ham256(reinterpret_cast<const uint4*>(desc + ((size_t)(2 * pair) * cap + i1) * OLF_DESC_BYTES), dR);
                 if (best_lr) {
                     if (d < running) { running = d; who = i1; outv = (uint16_t)d; }
                 } else outv = (uint16_t)d;
@@ -150,7 +143,7 @@ __global__ __launch_bounds__(256) void k_lines_dist_w(const LinePrep* __restrict
             const int spx = Lp->spx, spy = Lp->spy, epx = Lp->epx, epy = Lp->epy;
             if (in_window_g(Rp, spx, spy, ws) || in_window_g(Rp, epx, epy, ws)) {
                 const double dt = d_add(d_mul(Lp->vx, Rvx), d_mul(Lp->vy, Rvy));
-                if (!(fabs(dt) < sim_th)) d = ham256_u4(reinterpret_cast<const uint4*>(desc + ((size_t)(2 * pair) * cap + i1) * OLF_DESC_BYTES), dR);
+                if (!(fabs(dt) < sim_th)) d = ham256(reinterpret_cast<const uint4*>(desc + ((size_t)(2 * pair) * cap + i1) * OLF_DESC_BYTES), dR);
             }
         }
         uint16_t outv = 0xffff;

@@ -1,7 +1,7 @@
 // local_batch.hip -- the point half of Tracking::SearchLocalPointsAndLines (src/Tracking.cc:1877-1942) for a whole batch of frames on the device:
 // Frame::isInFrustum (src/Frame.cc:388-444) for every (frame, local map point), then ORBmatcher::SearchByProjection(Frame &F, const vector<MapPoint*>&, th)
-// (src/ORBmatcher.cc:47-131).  The arithmetic is that of search_host.cpp (olf_is_in_frustum, olf_search_local_map): convention C.12 for the cv::Mat
-// products, no contraction (-ffp-contract=off), correctly rounded divisions and square root.
+// (src/ORBmatcher.cc:47-131).  The arithmetic is that of search_host.cpp (olf_is_in_frustum, olf_search_local_map): its own cv::Mat products of
+// convention C.12 (search_math.hpp), no contraction (-ffp-contract=off), correctly rounded divisions and square root.
 //
 // Only one thing in the matcher's loop depends on the order of the map points: a feature is passed over while the point it holds has observations
 // (:89-91), and a point that is assigned changes that (:125).  Everything else -- radius, grid walk, level gates, the mvuRight gate, the distance -- is a
@@ -10,34 +10,27 @@
 //   k_local_held     one thread per (frame, feature): the bitmap of map points a frame holds (the mnLastFrameSeen test, src/Tracking.cc:1921), and the
 //                    features blocked from the start (they hold a point with observations; a blocked feature stays blocked)
 //   k_local_frustum  one thread per (frame, entry): Frame::isInFrustum; the level from the table of olf_predict_scale_thresholds, no logarithm
-//   k_local_lists    one wave per (frame, entry in view): walks the window as k_features_in_area does and keeps the LB_K best candidates that are not
+//   k_local_lists    one wave per (frame, entry in view): walks the window (grid_walk, grid_walk.hpp) and keeps the LB_K best candidates (Best4) that are not
 //                    blocked from the start, in (distance, scan position) order, each with "octave == predicted level", plus "there were more" (16 bytes
 //                    per entry).  No cut at TH_HIGH: the second best decides the ratio test at any distance
 //   k_local_walk     one workgroup per frame: one wave walks the entries in list order against the blocked bits in LDS; an entry whose kept candidates
 //                    do not yield two unblocked ones although the window held more is recomputed on the spot by the wave, with the blocked test inside
 //                    the scan -- there is no capacity and no approximate case
-// (lb_scan is tb_scan of track_batch.hip on this file's argument block: the walk of k_features_in_area, grid.hip.)
 #include <algorithm>
-#include "olf_internal.hpp"
+#include "grid_walk.hpp"
+#include "device_math.hpp"
+#include "search_math.hpp"
 #include "../../include/orbline.h"
 
 namespace olf {
 
-hipStream_t ctx_stream(olf_ctx* c);
-int ctx_scratch(olf_ctx* c, int slot, size_t bytes, void** out);
-int* ctx_status(olf_ctx* c);
-int ctx_check_device(const olf_ctx* c, const char* who);
-int ctx_orb_levels(const olf_ctx* c);
-int ctx_level_thresholds(olf_ctx* c, float* thr);
-
 constexpr int LB_TH_HIGH = 100;                     // src/ORBmatcher.cc:39
 constexpr int LB_K = 4;                             // candidates kept per entry (one uint4)
-constexpr int LB_ROWS = OLF_GRID_ROWS, LB_COLS = OLF_GRID_COLS;
 // a kept candidate: distance << 18 | (octave == predicted level) << 13 | feature (< OLF_GRID_MAX_KEYS = 2^13); the first word of a list also carries two flags
-constexpr unsigned LB_NONE = 0x3fffffffu, LB_OBS = 1u << 30, LB_MORE = 1u << 31;
-constexpr int LB_NOKEY = 0x7fffffff;
+constexpr unsigned LB_NONE = Best4::NONE, LB_OBS = 1u << 30, LB_MORE = 1u << 31;
+constexpr int LB_NOKEY = Best4::NOKEY;
 constexpr int LB_STATUS_INDEX = 512;                // status bit: a list index or a d_frame_mp value outside the map
-static_assert(OLF_GRID_MAX_KEYS <= (1 << 13), "candidate layout");
+static_assert(OLF_GRID_MAX_KEYS <= (1 << 13) && LB_K == Best4::K, "candidate layout");
 
 struct LocalArgs {
     olf_track_batch in;
@@ -96,15 +89,6 @@ __device__ __forceinline__ int lb_count(const LocalArgs& A, int j)
     return A.in.counts ? min(max(A.in.counts[(size_t)j * A.in.img_stride], 0), A.cap) : A.cap;
 }
 
-// the radius factor of frame j; false: the frame is skipped (d_th[j] <= 0)
-__device__ __forceinline__ bool lb_radius(const LocalArgs& A, int j, float& th)
-{
-    th = A.th;
-    if (!A.d_th) return true;
-    th = A.d_th[j];
-    return th > 0.f;
-}
-
 __device__ __forceinline__ LbFrame lb_frame(const LocalArgs& A, int j)
 {
     const olf_track_batch& in = A.in;
@@ -117,6 +101,12 @@ __device__ __forceinline__ LbFrame lb_frame(const LocalArgs& A, int j)
     F.idx = in.cell_index + f * cap;
     F.n = lb_count(A, j);
     return F;
+}
+
+// the frame's grid as grid_walk reads it (built at the walk, as tb_grid of track_batch.hip is)
+__device__ __forceinline__ GridView lb_grid(const LbFrame& P, const LocalArgs& A)
+{
+    return {P.k, P.offs, P.idx, P.n, A.cap, A.in.minX, A.in.minY, A.wInv, A.hInv};
 }
 
 __global__ __launch_bounds__(256) void k_local_held(LocalArgs A, unsigned* __restrict__ held, unsigned long long* __restrict__ blk0, int* __restrict__ status)
@@ -153,15 +143,8 @@ __global__ __launch_bounds__(256) void k_local_frustum(LocalArgs A, const unsign
     const float* P = A.map.world + 3 * (size_t)i;
     const float* N = A.map.normal + 3 * (size_t)i;
     float Ow[3], Pc[3];
-    for (int r = 0; r < 3; ++r) {                                    // mOw = -mRcw.t() * mtcw (camera_centre)
-        double acc = 0;
-        for (int k = 0; k < 3; ++k) acc += (double)T[4 * k + r] * (double)T[4 * k + 3];
-        Ow[r] = (float)(-acc);
-    }
-    for (int r = 0; r < 3; ++r) {                                    // rot_apply, C.12
-        const float t = T[4 * r] * P[0] + T[4 * r + 1] * P[1] + T[4 * r + 2] * P[2];
-        Pc[r] = (float)((double)t + (double)1.0f * (double)T[4 * r + 3]);
-    }
+    camera_centre(T, Ow);                                            // mOw = -mRcw.t() * mtcw
+    rot_apply(T, P, 1.0f, Pc);
     const float PcX = Pc[0], PcY = Pc[1], PcZ = Pc[2];
     if (PcZ < 0.0f) return;
     const float invz = __fdiv_rn(1.0f, PcZ);
@@ -185,7 +168,7 @@ __global__ __launch_bounds__(256) void k_local_frustum(LocalArgs A, const unsign
     view_cos[e] = viewCos;
 }
 
-// the window of an entry in view (src/ORBmatcher.cc:62-71)
+// the window of an entry in view (src/ORBmatcher.cc:62-71); it is searched as GetFeaturesInArea(u, v, radius, level - 1, level)
 __device__ __forceinline__ LbQuery lb_query(const LocalArgs& A, float th, int level, float viewCos, const float* p3)
 {
     LbQuery q;
@@ -197,43 +180,6 @@ __device__ __forceinline__ LbQuery lb_query(const LocalArgs& A, float th, int le
     return q;
 }
 
-// Frame::GetFeaturesInArea(u, v, radius, level - 1, level) on the frame's grid, by one wave: f(take, j, pos) is called by every lane for every chunk of 64
-// grid entries; `take` lanes hold feature j, the pos-th index the reference's vIndices would hold (ix outer, iy inner, stored order inside a cell).  Entries
-// that a malformed grid points outside the frame are left out.
-template <class F>
-__device__ __forceinline__ void lb_scan(const LbFrame& P, const LocalArgs& A, const LbQuery& q, int lane, F&& f)
-{
-    const float x = q.u, y = q.v, r = q.radius, minX = A.in.minX, minY = A.in.minY;
-    const float fx0 = floorf((x - minX - r) * A.wInv), fx1 = ceilf((x - minX + r) * A.wInv);
-    const float fy0 = floorf((y - minY - r) * A.hInv), fy1 = ceilf((y - minY + r) * A.hInv);
-    if (!(fx0 < (float)LB_COLS) || !(fx1 >= 0.f) || !(fy0 < (float)LB_ROWS) || !(fy1 >= 0.f)) return;
-    const int nMinCellX = fx0 < 0.f ? 0 : (int)fx0, nMaxCellX = fx1 > (float)(LB_COLS - 1) ? LB_COLS - 1 : (int)fx1;
-    const int nMinCellY = fy0 < 0.f ? 0 : (int)fy0, nMaxCellY = fy1 > (float)(LB_ROWS - 1) ? LB_ROWS - 1 : (int)fy1;
-    if (nMinCellY > nMaxCellY) return;
-    const int minLevel = q.level - 1, maxLevel = q.level;           // (maxLevel >= 0: the levels are always checked)
-    int total = 0;
-    for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-        const int p0 = max(P.offs[ix * LB_ROWS + nMinCellY], 0), p1 = min(P.offs[ix * LB_ROWS + nMaxCellY + 1], A.cap);
-        for (int pb = p0; pb < p1; pb += 64) {
-            const int p = pb + lane;
-            bool take = false;
-            int j = 0;
-            if (p < p1) {
-                j = P.idx[p];
-                if ((unsigned)j < (unsigned)P.n) {
-                    const olf_keypoint& kp = P.k[j];
-                    take = !(kp.octave < minLevel) && !(kp.octave > maxLevel);
-                    const float distx = kp.x - x, disty = kp.y - y;
-                    if (!(fabsf(distx) < r && fabsf(disty) < r)) take = false;
-                }
-            }
-            const unsigned long long m = wave_vote(take);
-            f(take, j, total + wave_rank_below(m));
-            total += __popcll(m);
-        }
-    }
-}
-
 // the tests on one candidate that do not depend on the blocked state (:93-102).  true: the candidate registers as best or second best (distance < 256);
 // key orders such candidates as the reference's scan does, ent is the kept form
 __device__ __forceinline__ bool lb_candidate(const LbFrame& P, const LbQuery& q, const uint4& a0, const uint4& a1, int j, int pos, int& key, unsigned& ent)
@@ -243,9 +189,7 @@ __device__ __forceinline__ bool lb_candidate(const LbFrame& P, const LbQuery& q,
         const float er = fabsf(q.xr - uR);
         if (er > q.radius) return false;
     }
-    const uint4 x0 = P.d[2 * (size_t)j], x1 = P.d[2 * (size_t)j + 1];
-    const int dist = __popc(a0.x ^ x0.x) + __popc(a0.y ^ x0.y) + __popc(a0.z ^ x0.z) + __popc(a0.w ^ x0.w) + __popc(a1.x ^ x1.x) + __popc(a1.y ^ x1.y) +
-                     __popc(a1.z ^ x1.z) + __popc(a1.w ^ x1.w);
+    const int dist = ham256(a0, a1, P.d[2 * (size_t)j], P.d[2 * (size_t)j + 1]);
     if (dist >= 256) return false;
     key = (dist << 16) | pos;
     ent = ((unsigned)dist << 18) | (P.k[j].octave == q.level ? 1u << 13 : 0u) | (unsigned)j;
@@ -264,36 +208,22 @@ __global__ __launch_bounds__(256) void k_local_lists(LocalArgs A, const uint8_t*
     int cnt = 0;
     bool obs = false;
     float th;
-    if (j >= 0 && in_view[e] && lb_radius(A, j, th)) {               // (in view: i is inside the map; a skipped frame's entries get empty lists)
+    if (j >= 0 && in_view[e] && item_radius(A.th, A.d_th, j, th)) {               // (in view: i is inside the map; a skipped frame's entries get empty lists)
         const LbFrame P = lb_frame(A, j);
         const LbQuery q = lb_query(A, th, level[e], view_cos[e], proj3 + 3 * (size_t)e);
         const uint4* md = reinterpret_cast<const uint4*>(A.map.desc) + 2 * (size_t)i;
         const uint4 a0 = md[0], a1 = md[1];
         const unsigned long long* b0 = blk0 + (size_t)j * A.capW;
         obs = A.map.obs[i] != 0;
-        // every lane keeps the LB_K smallest keys it meets, ascending; the LB_K smallest of the window are among them
-        int h0 = LB_NOKEY, h1 = LB_NOKEY, h2 = LB_NOKEY, h3 = LB_NOKEY;
-        unsigned e0 = LB_NONE, e1 = LB_NONE, e2 = LB_NONE, e3 = LB_NONE;
-        lb_scan(P, A, q, lane, [&](bool take, int j2, int pos) {
+        Best4 best;
+        grid_walk(lb_grid(P, A), q.u, q.v, q.radius, q.level - 1, q.level, lane, [&](bool take, int j2, int pos) {
             int key = LB_NOKEY;
             unsigned ent = LB_NONE;
             const bool ok = take && !((b0[j2 >> 6] >> (j2 & 63)) & 1ull) && lb_candidate(P, q, a0, a1, j2, pos, key, ent);
             cnt += __popcll(wave_vote(ok));
-            if (ok && key < h3) {
-                h3 = key; e3 = ent;
-                if (h3 < h2) { const int t = h2; h2 = h3; h3 = t; const unsigned u = e2; e2 = e3; e3 = u; }
-                if (h2 < h1) { const int t = h1; h1 = h2; h2 = t; const unsigned u = e1; e1 = e2; e2 = u; }
-                if (h1 < h0) { const int t = h0; h0 = h1; h1 = t; const unsigned u = e0; e0 = e1; e1 = u; }
-            }
+            best.push(ok, key, ent);
         });
-        for (int k = 0; k < LB_K; ++k) {
-            const int m = wave_min_i32(h0);
-            if (m == LB_NOKEY) break;
-            const bool mine = h0 == m;                               // keys are distinct: one lane
-            const int owner = __ffsll((long long)wave_vote(mine)) - 1;
-            out[k] = (unsigned)__shfl((int)e0, owner, 64);
-            if (mine) { h0 = h1; e0 = e1; h1 = h2; e1 = e2; h2 = h3; e2 = e3; h3 = LB_NOKEY; e3 = LB_NONE; }
-        }
+        best.drain(out);
     }
     if (lane == 0) {
         unsigned x = out[0];
@@ -310,7 +240,7 @@ __device__ __forceinline__ void lb_rescan(const LbFrame& P, const LocalArgs& A, 
     const uint4 a0 = md[0], a1 = md[1];
     int k1 = LB_NOKEY, k2 = LB_NOKEY;
     c1 = c2 = LB_NONE;
-    lb_scan(P, A, q, lane, [&](bool take, int j2, int pos) {
+    grid_walk(lb_grid(P, A), q.u, q.v, q.radius, q.level - 1, q.level, lane, [&](bool take, int j2, int pos) {
         int key = LB_NOKEY;
         unsigned ent = LB_NONE;
         const bool ok = take && !((s_blk[j2 >> 5] >> (j2 & 31)) & 1u) && lb_candidate(P, q, a0, a1, j2, pos, key, ent);
@@ -337,7 +267,7 @@ __global__ __launch_bounds__(256) void k_local_walk(LocalArgs A, const uint4* __
     unsigned* s_blk = reinterpret_cast<unsigned*>(s_match + A.cap);
     const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, cap = A.cap;
     float th;
-    if (!lb_radius(A, j, th)) return;
+    if (!item_radius(A.th, A.d_th, j, th)) return;
     const LbFrame P = lb_frame(A, j);
     const unsigned* b0 = reinterpret_cast<const unsigned*>(blk0 + (size_t)j * A.capW);
     for (int i = tid; i < cap; i += 256) s_match[i] = -1;

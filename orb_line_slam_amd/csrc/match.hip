@@ -9,12 +9,6 @@
 
 namespace olf {
 
-__device__ __forceinline__ int ham256(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1)
-{
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
-           __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
 // ---------------------------------------------------------------------------------------------
 // ComputeStereoMatches, one wave per left key point of one stereo pair (images 2p, 2p+1).
 constexpr int TH_HIGH = 100, TH_LOW = 50;

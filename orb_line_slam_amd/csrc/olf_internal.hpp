@@ -28,9 +28,19 @@
         }                                                                                   \
     } while (0)
 
+struct olf_ctx;
+
 namespace olf {
 
 void set_error(const std::string& s);
+
+// what the entry points outside api.cpp need of a context (api.cpp)
+hipStream_t ctx_stream(olf_ctx* c);
+int ctx_scratch(olf_ctx* c, int slot, size_t bytes, void** out);
+int* ctx_status(olf_ctx* c);
+int ctx_check_device(const olf_ctx* c, const char* who);
+int ctx_orb_levels(const olf_ctx* c);
+int ctx_level_thresholds(olf_ctx* c, float* thr);      // the table of olf_predict_scale_thresholds for the context's levels, built once
 
 #ifdef __HIPCC__
 // Wave-wide vote.  hip's __ballot() converts the predicate to an int first and compares that with 0 (a v_cndmask + v_cmp_ne pair per vote);

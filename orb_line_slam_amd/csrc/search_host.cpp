@@ -18,12 +18,13 @@
 #include "../../include/orbline.h"
 #include "olf_internal.hpp"
 #include "predict_scale.hpp"
+#include "search_math.hpp"
 
 #define OLF_TRY(expr) do { const int _rc = (expr); if (_rc != OLF_OK) return _rc; } while (0)
 
 namespace {
 using namespace olf;
-constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;          // src/ORBmatcher.cc:39-41
+constexpr int TH_HIGH = 100, TH_LOW = 50;                             // src/ORBmatcher.cc:39-40 (HISTO_LENGTH: search_math.hpp)
 constexpr int GRID_COLS = OLF_GRID_COLS, GRID_ROWS = OLF_GRID_ROWS;      // FRAME_GRID_COLS / FRAME_GRID_ROWS, include/Frame.h:51-52
 
 // Frame::mGrid (src/Frame.cc:334-349) as one index array (layout: include/orbline_types.h): the features of cell (ix, iy) are
@@ -103,43 +104,15 @@ struct Batch {
     }
 };
 
-// ORBmatcher::ComputeThreeMaxima, src/ORBmatcher.cc:1749-1790
+// ORBmatcher::ComputeThreeMaxima on the sizes of the reference's rotHist vectors
 void three_maxima(const std::vector<int>* histo, int& ind1, int& ind2, int& ind3)
 {
-    int max1 = 0, max2 = 0, max3 = 0;
-    ind1 = ind2 = ind3 = -1;
-    for (int i = 0; i < HISTO_LENGTH; i++) {
-        const int s = (int)histo[i].size();
-        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-        else if (s > max3) { max3 = s; ind3 = i; }
-    }
-    if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-    else if (max3 < 0.1f * (float)max1) ind3 = -1;
+    int counts[HISTO_LENGTH];
+    for (int i = 0; i < HISTO_LENGTH; i++) counts[i] = (int)histo[i].size();
+    olf::three_maxima(counts, ind1, ind2, ind3);
 }
 
-int rot_bin(float angle1, float angle2)
-{
-    float rot = angle1 - angle2;
-    if (rot < 0.0) rot += 360.0f;
-    int bin = (int)std::round(rot * (1.0f / HISTO_LENGTH));
-    if (bin == HISTO_LENGTH) bin = 0;
-    return bin;
-}
-
-// cv::Mat products of CV_32F operands (convention C.12): a plain product A*b (+ c) of inner length 3 takes cv::gemm's
-// small-matrix path (flags == 0, 2 <= len <= 4): the three products are summed in float, alpha and the C term are applied in double and the
-// result is rounded once.  Products with a transposed operand (A.t()*b) take the generic path: double accumulation, one rounding.
-inline float dot3_small(const float* a, const float* b)
-{
-    float t = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];        // ((a0*b0 + a1*b1) + a2*b2) in float, no contraction (-ffp-contract=off)
-    return t;
-}
-void rot_apply(const float* T, const float* v, float alpha_t, float* out)     // R * v + alpha_t * t, T = 4x4 row-major
-{
-    for (int r = 0; r < 3; ++r) out[r] = (float)((double)dot3_small(T + 4 * r, v) + (double)alpha_t * (double)T[4 * r + 3]);
-}
-
+// (rot_bin; dot3_small, rot_apply, camera_centre -- convention C.12: search_math.hpp)
 int bad_grid() { set_error("the view's grid_offsets / grid_index do not describe its n features (orbline_types.h: Frame::mGrid as two arrays)"); return OLF_ERR_INVALID; }
 bool bad_view(const olf_frame_view* f, bool needs_pose)
 {
@@ -165,11 +138,7 @@ int search_by_projection_frames(olf_ctx* c, const olf_frame_view* cur, const olf
     const float mb = cur->mbf / cur->fx;
     // twc = -Rcw.t() * tcw;  tlc = Rlw * twc + tlw                                   (:1341-1349)
     float twc[3], tlc[3];
-    for (int r = 0; r < 3; ++r) {
-        double acc = 0;
-        for (int k = 0; k < 3; ++k) acc += (double)cur->Tcw[4 * k + r] * (double)cur->Tcw[4 * k + 3];
-        twc[r] = (float)(-acc);
-    }
+    camera_centre(cur->Tcw, twc);
     rot_apply(last->Tcw, twc, 1.0f, tlc);
     const bool bForward = tlc[2] > mb && !bMono, bBackward = -tlc[2] > mb && !bMono;
 
@@ -447,15 +416,6 @@ void for_common_nodes(const olf_frame_view& A, const olf_frame_view& B, F&& f)
 }
 
 bool bad_fv(const olf_frame_view* v) { return v->fv_n < 0 || (v->fv_n && (!v->fv_nodes || !v->fv_offsets || !v->fv_features)); }
-
-void camera_centre(const float* Tcw, float* Ow)                 // -Rcw.t() * tcw
-{
-    for (int r = 0; r < 3; ++r) {
-        double acc = 0;
-        for (int k = 0; k < 3; ++k) acc += (double)Tcw[4 * k + r] * (double)Tcw[4 * k + 3];
-        Ow[r] = (float)(-acc);
-    }
-}
 
 // alpha * R * v (+ t), cv::gemm.  transposed: R9 holds the transpose of the matrix the reference multiplies with .t() -> generic path
 void r3_apply(const float* R9, const float* v, const float* t3, float* out, double alpha = 1.0, bool transposed = false)

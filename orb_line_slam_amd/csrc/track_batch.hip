@@ -1,40 +1,36 @@
 // track_batch.hip -- ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono[, map<int,int>& match12])
 // (src/ORBmatcher.cc:1330-1472, :1474-1618; Tracking::TrackWithMotionModel[WithLine], src/Tracking.cc:1296,1302) for a whole batch of consecutive frames on
 // the device, and Frame::UnprojectStereo (src/Frame.cc:1073-1087) for every feature of a batch.  The arithmetic is that of search_host.cpp
-// (search_by_projection_frames): convention C.12 for the cv::Mat products, no contraction (-ffp-contract=off).
+// (search_by_projection_frames), and where it is a cv::Mat product (convention C.12) or the rotation histogram it is the same text: search_math.hpp.
+// No contraction (-ffp-contract=off).
 //
 // Only one thing in the reference's loop depends on the order of the last frame's features: a CurrentFrame feature is skipped while the map point it received
 // last has observations (:1405-1407).  Everything else -- projection, image gates, the grid walk, level gates, the window tests, the mvuRight gate, the
 // distance -- is a function of (pair, last feature) alone, and a query's outcome is "the first entry, in (distance, scan position) order, with distance <=
 // TH_HIGH, whose feature is not blocked".  So:
-//   k_track_lists   one wave per (pair, last feature): walks the window as k_features_in_area does and keeps the TB_K best entries with distance <= TH_HIGH
+//   k_track_lists   one wave per (pair, last feature): walks the window (grid_walk, grid_walk.hpp) and keeps the TB_K best entries (Best4) with distance <= TH_HIGH
 //                   (16 bytes per query, whatever the window holds), plus "there were more" and the point's Observations() bit
 //   k_track_walk    one workgroup per pair: one wave walks the lists in index order against the pair's blocked bits in LDS; a query whose kept entries
 //                   are all blocked although the window held more is recomputed on the spot by the whole wave, with the blocked test inside the scan -- so
 //                   there is no capacity to exceed; then the rotation histogram (ComputeThreeMaxima, :1749-1790) and the output rows
 //   k_unproject_stereo  Frame::UnprojectStereo, one thread per feature
 #include <algorithm>
-#include "olf_internal.hpp"
+#include "grid_walk.hpp"
+#include "device_math.hpp"
+#include "search_math.hpp"
 #include "../../include/orbline.h"
 
 namespace olf {
 
-hipStream_t ctx_stream(olf_ctx* c);
-int ctx_scratch(olf_ctx* c, int slot, size_t bytes, void** out);
-int* ctx_status(olf_ctx* c);
-int ctx_check_device(const olf_ctx* c, const char* who);
-int ctx_orb_levels(const olf_ctx* c);
-
-constexpr int TB_TH_HIGH = 100, TB_HISTO = 30;      // src/ORBmatcher.cc:39-41
+constexpr int TB_TH_HIGH = 100, TB_HISTO = HISTO_LENGTH;      // src/ORBmatcher.cc:39-41
 constexpr int TB_K = 4;                             // entries kept per query (one uint4)
-constexpr int TB_ROWS = OLF_GRID_ROWS, TB_COLS = OLF_GRID_COLS;
 // a list entry: distance << 18 | rotation bin << 13 | CurrentFrame feature (< OLF_GRID_MAX_KEYS = 2^13); the first word of a list also carries two flags
-constexpr unsigned TB_NONE = 0x3fffffffu, TB_OBS = 1u << 30, TB_MORE = 1u << 31;
+constexpr unsigned TB_NONE = Best4::NONE, TB_OBS = 1u << 30, TB_MORE = 1u << 31;
 // per CurrentFrame feature in the walk: bit b = an event of rotation bin b landed here, then
 constexpr unsigned TB_SEEN = 1u << 30, TB_BLOCKED = 1u << 31;
-constexpr int TB_NOKEY = 0x7fffffff;
+constexpr int TB_NOKEY = Best4::NOKEY;
 constexpr int TB_STATUS_OCTAVE = 256;               // status bit: a pair was skipped, its last frame holds an octave outside the context's levels
-static_assert(OLF_GRID_MAX_KEYS <= (1 << 13) && TB_HISTO <= 30, "entry and word layouts");
+static_assert(OLF_GRID_MAX_KEYS <= (1 << 13) && TB_HISTO <= 30 && TB_K == Best4::K, "entry and word layouts");
 
 struct TrackArgs {
     olf_track_batch in;
@@ -62,15 +58,6 @@ struct TbQuery {
     int state;                     // 0: no window, 1: search it, 2: octave outside the levels
 };
 
-// the radius of pair j; false: the pair is skipped (d_th[j] <= 0)
-__device__ __forceinline__ bool tb_radius(const TrackArgs& A, int j, float& th)
-{
-    th = A.th;
-    if (!A.d_th) return true;
-    th = A.d_th[j];
-    return th > 0.f;
-}
-
 __device__ __forceinline__ TbPair tb_pair(const TrackArgs& A, int j, float th)
 {
     const olf_track_batch& in = A.in;
@@ -91,19 +78,12 @@ __device__ __forceinline__ TbPair tb_pair(const TrackArgs& A, int j, float th)
     P.nC = min(max(in.counts[fC * st], 0), A.cap);
     P.th = th;
     // twc = -Rcw.t() * tcw;  tlc = Rlw * twc + tlw                                   (:1341-1349)
-    const float* Tc = P.TcwC;
-    const float* Tl = in.Tcw + 16 * fL;
-    float twc[3];
-    for (int r = 0; r < 3; ++r) {
-        double acc = 0;
-        for (int k = 0; k < 3; ++k) acc += (double)Tc[4 * k + r] * (double)Tc[4 * k + 3];
-        twc[r] = (float)(-acc);
-    }
-    const float t = Tl[8] * twc[0] + Tl[9] * twc[1] + Tl[10] * twc[2];
-    const float tlc2 = (float)((double)t + (double)1.0f * (double)Tl[11]);
+    float twc[3], tlc[3];
+    camera_centre(P.TcwC, twc);
+    rot_apply(in.Tcw + 16 * fL, twc, 1.0f, tlc);
     const float mb = in.mbf / in.fx;
-    P.fwd = tlc2 > mb && !A.bMono;
-    P.bwd = -tlc2 > mb && !A.bMono;
+    P.fwd = tlc[2] > mb && !A.bMono;
+    P.bwd = -tlc[2] > mb && !A.bMono;
     return P;
 }
 
@@ -114,13 +94,8 @@ __device__ __forceinline__ TbQuery tb_query(const TbPair& P, const TrackArgs& A,
     q.state = 0; q.u = q.v = q.invzc = q.radius = 0.f; q.minLevel = q.maxLevel = -1;
     if (P.valid && !P.valid[i]) return q;
     if (P.outl && P.outl[i]) return q;
-    const float* T = P.TcwC;
-    const float* w = P.world + 3 * (size_t)i;
     float x3Dc[3];
-    for (int r = 0; r < 3; ++r) {
-        const float t = T[4 * r] * w[0] + T[4 * r + 1] * w[1] + T[4 * r + 2] * w[2];
-        x3Dc[r] = (float)((double)t + (double)1.0f * (double)T[4 * r + 3]);
-    }
+    rot_apply(P.TcwC, P.world + 3 * (size_t)i, 1.0f, x3Dc);
     const float xc = x3Dc[0], yc = x3Dc[1];
     const float invzc = (float)(1.0 / x3Dc[2]);
     if (invzc < 0) return q;
@@ -139,45 +114,11 @@ __device__ __forceinline__ TbQuery tb_query(const TbPair& P, const TrackArgs& A,
     return q;
 }
 
-// Frame::GetFeaturesInArea(u, v, radius, minLevel, maxLevel) on the CurrentFrame's grid, by one wave: f(take, j, pos) is called by every lane for every chunk
-// of 64 grid entries; `take` lanes hold feature j, the pos-th index the reference's vIndices2 would hold (ix outer, iy inner, stored order inside a cell --
-// the walk of k_features_in_area, grid.hip).  Entries that a malformed grid points outside the frame are left out.
-template <class F>
-__device__ __forceinline__ void tb_scan(const TbPair& P, const TrackArgs& A, const TbQuery& q, int lane, F&& f)
+// the CurrentFrame's grid as grid_walk reads it; built at the walk, so that the four floats hold scalar registers only there (held from the start of
+// k_track_lists they cost it four more, and 0.5 ms per call on an MI355X: DESIGN 4.5)
+__device__ __forceinline__ GridView tb_grid(const TbPair& P, const TrackArgs& A)
 {
-    const float x = q.u, y = q.v, r = q.radius, minX = A.in.minX, minY = A.in.minY;
-    const float fx0 = floorf((x - minX - r) * A.wInv), fx1 = ceilf((x - minX + r) * A.wInv);
-    const float fy0 = floorf((y - minY - r) * A.hInv), fy1 = ceilf((y - minY + r) * A.hInv);
-    if (!(fx0 < (float)TB_COLS) || !(fx1 >= 0.f) || !(fy0 < (float)TB_ROWS) || !(fy1 >= 0.f)) return;
-    const int nMinCellX = fx0 < 0.f ? 0 : (int)fx0, nMaxCellX = fx1 > (float)(TB_COLS - 1) ? TB_COLS - 1 : (int)fx1;
-    const int nMinCellY = fy0 < 0.f ? 0 : (int)fy0, nMaxCellY = fy1 > (float)(TB_ROWS - 1) ? TB_ROWS - 1 : (int)fy1;
-    if (nMinCellY > nMaxCellY) return;
-    const bool bCheckLevels = (q.minLevel > 0) || (q.maxLevel >= 0);
-    int total = 0;
-    for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-        const int p0 = max(P.offs[ix * TB_ROWS + nMinCellY], 0), p1 = min(P.offs[ix * TB_ROWS + nMaxCellY + 1], A.cap);
-        for (int pb = p0; pb < p1; pb += 64) {
-            const int p = pb + lane;
-            bool take = false;
-            int j = 0;
-            if (p < p1) {
-                j = P.idx[p];
-                if ((unsigned)j < (unsigned)P.nC) {
-                    const olf_keypoint& kp = P.kC[j];
-                    take = true;
-                    if (bCheckLevels) {
-                        if (kp.octave < q.minLevel) take = false;
-                        if (q.maxLevel >= 0 && kp.octave > q.maxLevel) take = false;
-                    }
-                    const float distx = kp.x - x, disty = kp.y - y;
-                    if (!(fabsf(distx) < r && fabsf(disty) < r)) take = false;
-                }
-            }
-            const unsigned long long m = wave_vote(take);
-            f(take, j, total + wave_rank_below(m));
-            total += __popcll(m);
-        }
-    }
+    return {P.kC, P.offs, P.idx, P.nC, A.cap, A.in.minX, A.in.minY, A.wInv, A.hInv};
 }
 
 // the state-free tests on one candidate (:1409-1423): the mvuRight gate and the distance.  true: the candidate could be chosen (distance <= TH_HIGH);
@@ -191,14 +132,9 @@ __device__ __forceinline__ bool tb_candidate(const TbPair& P, const TrackArgs& A
         const float er = fabsf(ur - uR);
         if (er > q.radius) return false;
     }
-    const uint4 x0 = P.dC[2 * (size_t)j], x1 = P.dC[2 * (size_t)j + 1];
-    const int dist = __popc(a0.x ^ x0.x) + __popc(a0.y ^ x0.y) + __popc(a0.z ^ x0.z) + __popc(a0.w ^ x0.w) + __popc(a1.x ^ x1.x) + __popc(a1.y ^ x1.y) +
-                     __popc(a1.z ^ x1.z) + __popc(a1.w ^ x1.w);
+    const int dist = ham256(a0, a1, P.dC[2 * (size_t)j], P.dC[2 * (size_t)j + 1]);
     if (dist > TB_TH_HIGH) return false;
-    float rot = angL - P.kC[j].angle;                                           // (:1434-1441)
-    if (rot < 0.0) rot += 360.0f;
-    int bin = (int)roundf(rot * (1.0f / TB_HISTO));
-    if (bin == TB_HISTO) bin = 0;
+    int bin = rot_bin(angL, P.kC[j].angle);                                     // (:1434-1441)
     bin = min(max(bin, 0), TB_HISTO - 1);      // (angles outside [0, 360) index past rotHist in the reference; here they land in an end bin)
     key = (dist << 16) | pos;
     ent = ((unsigned)dist << 18) | ((unsigned)bin << 13) | (unsigned)j;
@@ -209,7 +145,7 @@ __global__ __launch_bounds__(256) void k_track_lists(TrackArgs A, uint4* __restr
 {
     const int j = blockIdx.y, i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     float th;
-    if (!tb_radius(A, j, th)) return;
+    if (!item_radius(A.th, A.d_th, j, th)) return;
     const TbPair P = tb_pair(A, j, th);
     if (i >= P.nL) return;                                       // (wave-uniform)
     const TbQuery q = tb_query(P, A, i);
@@ -220,29 +156,15 @@ __global__ __launch_bounds__(256) void k_track_lists(TrackArgs A, uint4* __restr
     } else if (q.state == 1) {
         const uint4 a0 = P.dL[2 * (size_t)i], a1 = P.dL[2 * (size_t)i + 1];
         const float angL = P.kL[i].angle;
-        // every lane keeps the TB_K smallest keys it meets, ascending; the TB_K smallest of the window are among them
-        int h0 = TB_NOKEY, h1 = TB_NOKEY, h2 = TB_NOKEY, h3 = TB_NOKEY;
-        unsigned e0 = TB_NONE, e1 = TB_NONE, e2 = TB_NONE, e3 = TB_NONE;
-        tb_scan(P, A, q, lane, [&](bool take, int j2, int pos) {
+        Best4 best;
+        grid_walk(tb_grid(P, A), q.u, q.v, q.radius, q.minLevel, q.maxLevel, lane, [&](bool take, int j2, int pos) {
             int key = TB_NOKEY;
             unsigned ent = TB_NONE;
             const bool ok = take && tb_candidate(P, A, q, a0, a1, angL, j2, pos, key, ent);
             cnt += __popcll(wave_vote(ok));
-            if (ok && key < h3) {
-                h3 = key; e3 = ent;
-                if (h3 < h2) { const int t = h2; h2 = h3; h3 = t; const unsigned u = e2; e2 = e3; e3 = u; }
-                if (h2 < h1) { const int t = h1; h1 = h2; h2 = t; const unsigned u = e1; e1 = e2; e2 = u; }
-                if (h1 < h0) { const int t = h0; h0 = h1; h1 = t; const unsigned u = e0; e0 = e1; e1 = u; }
-            }
+            best.push(ok, key, ent);
         });
-        for (int k = 0; k < TB_K; ++k) {
-            const int m = wave_min_i32(h0);
-            if (m == TB_NOKEY) break;
-            const bool mine = h0 == m;                               // keys are distinct: one lane
-            const int owner = __ffsll((long long)wave_vote(mine)) - 1;
-            out[k] = (unsigned)__shfl((int)e0, owner, 64);
-            if (mine) { h0 = h1; e0 = e1; h1 = h2; e1 = e2; h2 = h3; e2 = e3; h3 = TB_NOKEY; e3 = TB_NONE; }
-        }
+        best.drain(out);
     }
     if (lane == 0) {
         unsigned x = out[0];
@@ -261,7 +183,7 @@ __device__ __forceinline__ unsigned tb_rescan(const TbPair& P, const TrackArgs& 
     const float angL = P.kL[i].angle;
     int best = TB_NOKEY;
     unsigned bestEnt = TB_NONE;
-    tb_scan(P, A, q, lane, [&](bool take, int j2, int pos) {
+    grid_walk(tb_grid(P, A), q.u, q.v, q.radius, q.minLevel, q.maxLevel, lane, [&](bool take, int j2, int pos) {
         int key = TB_NOKEY;
         unsigned ent = TB_NONE;
         const bool ok = take && !(s_word[j2] & TB_BLOCKED) && tb_candidate(P, A, q, a0, a1, angL, j2, pos, key, ent);
@@ -285,7 +207,7 @@ __global__ __launch_bounds__(256) void k_track_walk(TrackArgs A, const uint4* __
     unsigned short* s_last = reinterpret_cast<unsigned short*>(s_word + A.cap);
     const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, cap = A.cap;
     float th;
-    if (!tb_radius(A, j, th)) return;
+    if (!item_radius(A.th, A.d_th, j, th)) return;
     if (pairBad[j]) { if (tid == 0) nmatches[j] = -1; return; }
     const TbPair P = tb_pair(A, j, th);
     for (int i = tid; i < cap; i += 256) { s_word[i] = 0; s_last[i] = 0xffff; }
@@ -332,15 +254,8 @@ __global__ __launch_bounds__(256) void k_track_walk(TrackArgs A, const uint4* __
     __syncthreads();
     if (checkOri) {
         if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;      // ComputeThreeMaxima, src/ORBmatcher.cc:1749-1790
-            for (int i = 0; i < TB_HISTO; i++) {
-                const int s = s_hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float)max1) ind3 = -1;
+            int ind1, ind2, ind3;
+            three_maxima(s_hist, ind1, ind2, ind3);
             unsigned rej = 0;
             int n = s_n;
             for (int i = 0; i < TB_HISTO; i++) if (i != ind1 && i != ind2 && i != ind3) { rej |= 1u << i; n -= s_hist[i]; }
@@ -373,11 +288,7 @@ __global__ __launch_bounds__(256) void k_unproject_stereo(const olf_keypoint* __
         const olf_keypoint& kp = kps[(size_t)f * img_stride * cap + i];
         const float u = kp.x, v = kp.y;
         const float x3Dc[3] = {(u - cx) * z * invfx, (v - cy) * z * invfy, z};
-        const float* T = Twc + 16 * (size_t)f;
-        for (int r = 0; r < 3; ++r) {
-            const float t = T[4 * r] * x3Dc[0] + T[4 * r + 1] * x3Dc[1] + T[4 * r + 2] * x3Dc[2];
-            o[r] = (float)((double)t + (double)1.0f * (double)T[4 * r + 3]);
-        }
+        rot_apply(Twc + 16 * (size_t)f, x3Dc, 1.0f, o);
     }
     world[3 * at] = o[0]; world[3 * at + 1] = o[1]; world[3 * at + 2] = o[2];
 }
