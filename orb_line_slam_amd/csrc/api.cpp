@@ -1,126 +1,24 @@
-// api.cpp -- the extern "C" boundary of liborbline_hip.so (include/orbline.h).
+// api.cpp -- the extern "C" boundary of liborbline_hip.so (include/orbline.h): the context, its status and profiling, the stages, the _dev entries
+// and the fused frame call.  (api_host.cpp: the host-pointer entries; api_debug.cpp: the entries that read intermediate buffers for the tests.)
 // Owns the device context; every compute entry point launches HIP kernels -- there is no CPU
 // fallback: without a gfx950 device olf_ctx_create fails with OLF_ERR_NODEVICE.
-#include "olf_internal.hpp"
-#include "line_internal.hpp"
-#include "../../include/orbline.h"
+#include "ctx.hpp"
+#include "staging.hpp"
 #include <map>
 #include <mutex>
-#include <cstring>
-#include <cstddef>
 
 namespace olf {
 static thread_local std::string g_err;
 void set_error(const std::string& s) { g_err = s; }
-}  // namespace olf
 
-using namespace olf;
-
-// ---- the layout of olf_frame_buffers (include/orbline.h), in the order of its fields: whose rows an array has (every image's or every pair's), how many
-// per image or pair (the ORB capacity, the line capacity, or one for the two count arrays) and the bytes of a row
-enum { FB_KPS, FB_DESC, FB_COUNTS, FB_URIGHT, FB_DEPTH, FB_KLS, FB_LDESC, FB_LCOUNTS, FB_LMATCHES12, FB_LDISP, FB_LLE, FB_FIELDS };
-enum FieldCap { CAP_ONE, CAP_ORB, CAP_LINE };
-struct FrameField { const char* name; size_t offset; bool perPair; FieldCap cap; size_t rowBytes; };
-#define FIELD(f, perPair, cap, rowBytes) {#f, offsetof(olf_frame_buffers, f), perPair, cap, rowBytes}
-constexpr FrameField kFrameFields[] = {
-    FIELD(kps, false, CAP_ORB, sizeof(olf_keypoint)),   FIELD(desc, false, CAP_ORB, OLF_DESC_BYTES),    FIELD(counts, false, CAP_ONE, sizeof(int32_t)),
-    FIELD(uright, true, CAP_ORB, sizeof(float)),        FIELD(depth, true, CAP_ORB, sizeof(float)),
-    FIELD(kls, false, CAP_LINE, sizeof(olf_keyline)),   FIELD(ldesc, false, CAP_LINE, OLF_DESC_BYTES),  FIELD(lcounts, false, CAP_ONE, sizeof(int32_t)),
-    FIELD(lmatches12, true, CAP_LINE, sizeof(int32_t)), FIELD(ldisp, true, CAP_LINE, 2 * sizeof(float)), FIELD(lle, true, CAP_LINE, 3 * sizeof(double))};
-#undef FIELD
-// (the struct is eleven object pointers and nothing else: a field is read and written through its offset as a void*)
-constexpr bool frame_fields_in_order()
-{
-    for (size_t k = 0; k < sizeof(kFrameFields) / sizeof(kFrameFields[0]); ++k) if (kFrameFields[k].offset != k * sizeof(void*)) return false;
-    return true;
-}
-static_assert(sizeof(kFrameFields) / sizeof(kFrameFields[0]) == FB_FIELDS && sizeof(olf_frame_buffers) == FB_FIELDS * sizeof(void*) && frame_fields_in_order(),
-              "kFrameFields has one entry per field of olf_frame_buffers, in the struct's order");
-
-static void* fb_field(const olf_frame_buffers& f, int k) { void* p; std::memcpy(&p, reinterpret_cast<const char*>(&f) + kFrameFields[k].offset, sizeof(p)); return p; }
-static void fb_set_field(olf_frame_buffers& f, int k, void* p) { std::memcpy(reinterpret_cast<char*>(&f) + kFrameFields[k].offset, &p, sizeof(p)); }
-
-struct olf_ctx {
-    olf_params params;
-    int W = 0, H = 0, max_images = 0;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    OrbHostTables orb;
-    OrbDeviceBufs ob;
-    // staging for the host-pointer entry points
-    uint8_t* d_images = nullptr;
-    olf_frame_buffers d_out = {};  // the eleven output arrays, sized for max_images (kFrameFields)
-    int* d_sad = nullptr;          // [max_pairs][outCap]
-    int* d_bestkey = nullptr;
-    unsigned* d_rowperm = nullptr; // [max_images][outCap] key point lists ordered by row (stereo candidate search)
-    // line side
-    LineHostTables line;
-    LineDeviceBufs lb;
-    LsdOverrides lsd_force;            // olf_debug_lsd_* / olf_debug_seed_sort_mode (tests)
-    DeviceLimits limits;               // of `device`
-    void* d_lprep = nullptr;
-    uint16_t* d_ldist = nullptr;
-    int* d_lm21 = nullptr;
-    hipStream_t stream2 = nullptr;
-    bool has_tables = false;       // holds a reference on the device's shared LSD angle tables
-    hipEvent_t ev_front = nullptr;     // fused entry: recorded behind the LSD front including the seed ordering (the ORB stream's FAST waits for it)
-    hipEvent_t input_event = nullptr;  // olf_ctx_set_input_event: not owned; the fused entry's line stream waits for it instead of forking from the caller's stream
-    hipEvent_t ev_lbd = nullptr;       // fused entry: the LBD gradient images are ready (computed on the ORB stream in the seed ordering's shadow)
-    bool deferred_join = false;        // olf_ctx_set_deferred_join: olf_stereo_frames_dev returns with the line path still running on the line stream
-    bool scaled_aliased = false;       // batch context: the LSD working images live in the key buffers (dead before those are written)
-    bool join_pending = false;         // ... and this call's line path has not been joined yet (olf_stereo_frames_join_dev, or the next call)
-    // small contexts (the drop-in's one-pair-per-call shape): the eleven arrays of d_out sit in ONE device slab, so that the host entry brings them
-    // back with one copy into pinned memory instead of eleven (each a launch and a gap of its own: 0.44 ms of a 9 ms call, profiles/r5b_pair_timeline.txt)
-    uint8_t* d_outslab = nullptr; uint8_t* h_outslab = nullptr; size_t outslab_bytes = 0; size_t outslab_off[11] = {0};
-    // every line-side output that call is still writing (key lines, LBD descriptors, counts, line matches, disparities, line equations): an entry that is handed
-    // one of them (matcher, line stereo, packer) joins first.  The obligation is discharged for the whole context only when the frame call's OWN stream has
-    // waited (pend_stream); a join on another stream orders that stream and leaves the obligation standing
-    struct { const uint8_t* p; size_t bytes; } pend[FB_FIELDS - FB_KLS] = {};
-    hipStream_t pend_stream = nullptr;
-    hipEvent_t ev_sort = nullptr;      // fused entry: recorded in front of the seed ordering (the dense, bandwidth-bound half of the LSD front is through)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // stage profiling (olf_profile_*): HIP events recorded on the stream each stage is launched on
-    bool prof_on = false;
-    struct ProfRec { int stage; hipEvent_t a, b; };
-    std::vector<ProfRec> prof_recs;
-    std::vector<hipEvent_t> prof_pool;
-    double prof_ms[16] = {0};
-    int prof_calls[16] = {0};
-    // grow-on-demand scratch (matcher k-NN tables, host-pointer staging)
-    void* scratch[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[4] = {0, 0, 0, 0};
-    std::vector<void*> allocs;
-    // olf_predict_scale_thresholds of the context's own scale factors, built by the first call that needs it (level_thr_rc > 0: not built yet)
-    float level_thr[OLF_MAX_LEVELS] = {0};
-    int level_thr_rc = 1;
-};
-
-// A context (and everything it owns) lives on the device that was current when it was created; calling into it with another device
-// current would send its launches and allocations to the wrong GPU.
-static int check_device(const olf_ctx* c, const char* who)
+int check_device(const olf_ctx* c, const char* who)
 {
     int d = -1;
     if (hipGetDevice(&d) != hipSuccess || d != c->device) { set_error(std::string(who) + ": the context belongs to another device than the current one"); return OLF_ERR_INVALID; }
     return OLF_OK;
 }
 
-// bytes of field k for n_images images (the pairs they make: an odd last image counts as a pair)
-static size_t fb_bytes(const olf_ctx* c, int k, size_t n_images)
-{
-    const FrameField& f = kFrameFields[k];
-    const size_t cap = f.cap == CAP_ORB ? c->orb.geom.outCap : f.cap == CAP_LINE ? c->line.geom.outCap : 1;
-    return (f.perPair ? (n_images + 1) / 2 : n_images) * cap * f.rowBytes;
-}
-
-// the copies of the host-pointer entries: fields first..last of n_images images between the context's arrays and the caller's (`h`, host pointers)
-static int fb_copy(olf_ctx* c, const olf_frame_buffers& h, int first, int last, size_t n_images, hipMemcpyKind kind)
-{
-    const olf_frame_buffers &src = kind == hipMemcpyDeviceToHost ? c->d_out : h, &dst = kind == hipMemcpyDeviceToHost ? h : c->d_out;
-    for (int k = first; k <= last; ++k) OLF_HIP_CHECK(hipMemcpyAsync(fb_field(dst, k), fb_field(src, k), fb_bytes(c, k, n_images), kind, c->stream));
-    return OLF_OK;
-}
-
-static int scratch_get(olf_ctx* c, int slot, size_t bytes, void** out)
+int scratch_get(olf_ctx* c, ScratchSlot slot, size_t bytes, void** out)
 {
     if (c->scratch_bytes[slot] < bytes) {
         if (c->scratch[slot]) { OLF_HIP_CHECK(hipDeviceSynchronize()); (void)hipFree(c->scratch[slot]); c->scratch[slot] = nullptr; c->scratch_bytes[slot] = 0; }
@@ -131,6 +29,45 @@ static int scratch_get(olf_ctx* c, int slot, size_t bytes, void** out)
     *out = c->scratch[slot];
     return OLF_OK;
 }
+
+int check_status(olf_ctx* c)
+{
+    int st[4] = {0, 0, 0, 0};
+    OLF_HIP_CHECK(hipMemcpy(st, c->ob.status, sizeof(st), hipMemcpyDeviceToHost));
+    if (st[0]) {
+        (void)hipMemset(c->ob.status, 0, 16);
+        set_error("device capacity overflow, flags=" + std::to_string(st[0]) +
+                  " (1/2/4: ORB corner / candidate / key point buffers, 8: LSD regions, segments or pixel-list pool, 16: LSD growth watchdog, 32: frame record buffer, 64: LSD seed sort, final-range list of the grid-wide top levels, 128: candidate list of olf_features_in_area_dev, 256: olf_search_by_projection_batch_dev skipped a pair whose last frame holds an octave outside the context's levels, 512: olf_is_in_frustum_batch_dev / olf_search_local_map_batch_dev met a list index or a d_frame_mp value outside the map)");
+        return OLF_ERR_CAPACITY;
+    }
+    return OLF_OK;
+}
+
+int join_if_pending(olf_ctx* c, hipStream_t s)
+{
+    if (!c->join_pending) return OLF_OK;
+    OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_join, 0));
+    if (s == c->pend_stream) c->join_pending = false;      // (a side stream's wait orders the side stream only)
+    return OLF_OK;
+}
+bool in_pending_line_outputs(const olf_ctx* c, const void* p)
+{
+    if (!c->join_pending || !p) return false;
+    const uint8_t* q = static_cast<const uint8_t*>(p);
+    for (const auto& r : c->pend) if (r.p && q >= r.p && q < r.p + r.bytes) return true;
+    return false;
+}
+
+hipEvent_t prof_event(olf_ctx* c)
+{
+    if (!c->prof_pool.empty()) { hipEvent_t e = c->prof_pool.back(); c->prof_pool.pop_back(); return e; }
+    hipEvent_t e = nullptr;
+    (void)hipEventCreate(&e);
+    return e;
+}
+}  // namespace olf
+
+using namespace olf;
 
 // The LSD angle / cos-sin tables depend on nothing but the packed gradient pair: one copy per device, shared by every context of the process
 // (a reference Frame is served by four extractor objects, each with a context of its own; include/orbline_adaptor.hpp).
@@ -180,16 +117,21 @@ namespace olf {
 int launch_pack_records(const olf_frame_buffers& fb, int n_pairs, int cap, int lcap, uint8_t* d_dst, size_t dst_capacity, int* d_rowOfs,
                         unsigned long long* d_bytes, int* d_status, hipStream_t s);
 size_t pack_records_bound(int n_pairs, int cap, int lcap);
-int launch_copy16(const void* src, void* dst, size_t bytes, hipStream_t s);
 int launch_depth_mask(const float* depth, uint8_t* mask, size_t n, hipStream_t s);
 }
 
 namespace olf {
-hipStream_t ctx_stream(olf_ctx* c) { return c->stream; }
-int ctx_scratch(olf_ctx* c, int slot, size_t bytes, void** out) { return scratch_get(c, slot, bytes, out); }
+hipStream_t ctx_stream(olf_ctx* c, void* stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
+int ctx_scratch(olf_ctx* c, ScratchSlot slot, size_t bytes, void** out) { return scratch_get(c, slot, bytes, out); }
 int* ctx_status(olf_ctx* c) { return c->ob.status; }
 int ctx_check_device(const olf_ctx* c, const char* who) { return check_device(c, who); }
-int ctx_orb_levels(const olf_ctx* c) { return c->params.orb.nlevels; }
+int ctx_check_status(olf_ctx* c) { return check_status(c); }
+int ctx_level_scales(const olf_ctx* c, float* sf)
+{
+    const int n = std::min(c->params.orb.nlevels, (int)OLF_MAX_LEVELS);
+    for (int l = 0; l < OLF_MAX_LEVELS; ++l) sf[l] = l < n ? c->orb.sf[l] : 1.f;
+    return n;
+}
 int ctx_level_thresholds(olf_ctx* c, float* thr)
 {
     const int n = c->params.orb.nlevels;
@@ -199,23 +141,8 @@ int ctx_level_thresholds(olf_ctx* c, float* thr)
 }
 }
 
-enum { ST_ORB_PYRAMID, ST_ORB_FAST, ST_ORB_OCTREE, ST_ORB_BLUR, ST_ORB_DESCRIBE, ST_STEREO_POINTS, ST_LSD_FRONT, ST_LSD_GROW, ST_LSD_RECT, ST_LINE_LBD,
-       ST_STEREO_LINES, ST_MATCH_BF, ST_COUNT };
 static const char* kStageNames[ST_COUNT] = {"orb_pyramid", "orb_fast_cells", "orb_octree", "orb_blur", "orb_describe", "stereo_points",
                                             "lsd_front", "lsd_grow", "lsd_rect", "line_select_lbd", "stereo_lines", "match_bf"};
-
-static hipEvent_t prof_event(olf_ctx* c)
-{
-    if (!c->prof_pool.empty()) { hipEvent_t e = c->prof_pool.back(); c->prof_pool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
-    return e;
-}
-struct StageScope {
-    olf_ctx* c; hipStream_t s; int stage; hipEvent_t a = nullptr;
-    StageScope(olf_ctx* c_, hipStream_t s_, int st) : c(c_), s(s_), stage(st) { if (c->prof_on) { a = prof_event(c); (void)hipEventRecord(a, s); } }
-    ~StageScope() { if (a) { hipEvent_t b = prof_event(c); (void)hipEventRecord(b, s); c->prof_recs.push_back({stage, a, b}); } }
-};
 
 template <typename T>
 static int dev_alloc(olf_ctx* c, T** p, size_t n)
@@ -226,12 +153,6 @@ static int dev_alloc(olf_ctx* c, T** p, size_t n)
     *p = reinterpret_cast<T*>(q);
     return OLF_OK;
 }
-
-#define OLF_TRY(expr)                  \
-    do {                               \
-        int _rc = (expr);              \
-        if (_rc != OLF_OK) return _rc; \
-    } while (0)
 
 extern "C" {
 
@@ -400,24 +321,6 @@ int olf_ctx_create(const olf_params* p, int width, int height, int max_images, o
     return OLF_OK;
 }
 
-static int check_status(olf_ctx* c);
-
-// a deferred join that the caller has not asked for yet, in front of an entry that reads what the line stream is still writing
-static int join_if_pending(olf_ctx* c, hipStream_t s)
-{
-    if (!c->join_pending) return OLF_OK;
-    OLF_HIP_CHECK(hipStreamWaitEvent(s, c->ev_join, 0));
-    if (s == c->pend_stream) c->join_pending = false;      // (a side stream's wait orders the side stream only)
-    return OLF_OK;
-}
-static bool in_pending_line_outputs(const olf_ctx* c, const void* p)
-{
-    if (!c->join_pending || !p) return false;
-    const uint8_t* q = static_cast<const uint8_t*>(p);
-    for (const auto& r : c->pend) if (r.p && q >= r.p && q < r.p + r.bytes) return true;
-    return false;
-}
-
 int olf_ctx_synchronize(olf_ctx* c)
 {
     if (!c) return OLF_ERR_INVALID;
@@ -543,67 +446,12 @@ int olf_orb_extract_dev(olf_ctx* c, const uint8_t* d_images, int n_images, olf_k
     OLF_TRY(check_device(c, "olf_orb_extract_dev"));
     if (n_images < 0 || n_images > c->max_images) { set_error("olf_orb_extract_dev: n_images exceeds the context capacity"); return OLF_ERR_CAPACITY; }
     if (n_images == 0) return OLF_OK;   // ORBextractor::operator() returns silently on an empty image
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = ctx_stream(c, stream);
     OLF_TRY(stage_orb_pyramid(c, d_images, n_images, s));
     OLF_TRY(stage_orb_fast(c, n_images, s));
     OLF_TRY(stage_orb_octree(c, n_images, s));
     OLF_TRY(stage_orb_blur(c, n_images, s));
     return stage_orb_describe(c, n_images, d_kps, d_desc, d_counts, s);
-}
-
-static int check_status(olf_ctx* c)
-{
-    int st[4] = {0, 0, 0, 0};
-    OLF_HIP_CHECK(hipMemcpy(st, c->ob.status, sizeof(st), hipMemcpyDeviceToHost));
-    if (st[0]) {
-        (void)hipMemset(c->ob.status, 0, 16);
-        set_error("device capacity overflow, flags=" + std::to_string(st[0]) +
-                  " (1/2/4: ORB corner / candidate / key point buffers, 8: LSD regions, segments or pixel-list pool, 16: LSD growth watchdog, 32: frame record buffer, 64: LSD seed sort, final-range list of the grid-wide top levels, 128: candidate list of olf_features_in_area_dev, 256: olf_search_by_projection_batch_dev skipped a pair whose last frame holds an octave outside the context's levels, 512: olf_is_in_frustum_batch_dev / olf_search_local_map_batch_dev met a list index or a d_frame_mp value outside the map)");
-        return OLF_ERR_CAPACITY;
-    }
-    return OLF_OK;
-}
-
-int olf_orb_extract(olf_ctx* c, const uint8_t* images, int n_images, olf_keypoint* kps, uint8_t* desc, int32_t* counts)
-{
-    if (!c || !images || !kps || !desc || !counts) { set_error("olf_orb_extract: null argument"); return OLF_ERR_INVALID; }
-    if (n_images < 0 || n_images > c->max_images) return OLF_ERR_CAPACITY;
-    if (n_images == 0) return OLF_OK;
-    olf_frame_buffers h = {}; h.kps = kps; h.desc = desc; h.counts = counts;
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, (size_t)c->W * c->H * n_images, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_orb_extract_dev(c, c->d_images, n_images, c->d_out.kps, c->d_out.desc, c->d_out.counts, c->stream));
-    OLF_TRY(fb_copy(c, h, FB_KPS, FB_COUNTS, n_images, hipMemcpyDeviceToHost));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return check_status(c);
-}
-
-int olf_orb_extract_strided(olf_ctx* c, const uint8_t* image, size_t row_stride, olf_keypoint* kps, uint8_t* desc, int32_t* count)
-{
-    if (!c || !image || !kps || !desc || !count || row_stride < (size_t)c->W) { set_error("olf_orb_extract_strided: bad argument"); return OLF_ERR_INVALID; }
-    olf_frame_buffers h = {}; h.kps = kps; h.desc = desc; h.counts = count;
-    OLF_HIP_CHECK(hipMemcpy2DAsync(c->d_images, c->W, image, row_stride, c->W, c->H, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_orb_extract_dev(c, c->d_images, 1, c->d_out.kps, c->d_out.desc, c->d_out.counts, c->stream));
-    OLF_TRY(fb_copy(c, h, FB_KPS, FB_COUNTS, 1, hipMemcpyDeviceToHost));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return check_status(c);
-}
-
-int olf_orb_pyramid_level(olf_ctx* c, int image, int level, int blurred, uint8_t* dst)
-{
-    if (!c || !dst || image < 0 || image >= c->max_images || level < 0 || level >= c->orb.geom.nlevels) return OLF_ERR_INVALID;
-    const LevelGeom& L = c->orb.geom.lv[level];
-    const uint8_t* src = (blurred ? c->ob.blur : c->ob.pyr) + (size_t)image * c->orb.geom.pyrBytes + L.offset;
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    OLF_HIP_CHECK(hipMemcpy2D(dst, L.w, src, L.pitch, L.w, L.h, hipMemcpyDeviceToHost));
-    return OLF_OK;
-}
-
-int olf_debug_status(olf_ctx* c, int32_t* out64)
-{
-    if (!c || !out64) return OLF_ERR_INVALID;
-    OLF_HIP_CHECK(hipDeviceSynchronize());
-    OLF_HIP_CHECK(hipMemcpy(out64, c->ob.status, 256, hipMemcpyDeviceToHost));
-    return OLF_OK;
 }
 
 size_t olf_frames_pack_bound(const olf_ctx* c, int n_pairs)
@@ -615,7 +463,7 @@ int olf_stereo_points_mask_dev(olf_ctx* c, const float* d_depth, size_t n, uint8
 {
     if (!c || !d_depth || !d_mask) { set_error("olf_stereo_points_mask_dev: null argument"); return OLF_ERR_INVALID; }
     OLF_TRY(check_device(c, "olf_stereo_points_mask_dev"));
-    return olf::launch_depth_mask(d_depth, d_mask, n, stream ? (hipStream_t)stream : c->stream);
+    return olf::launch_depth_mask(d_depth, d_mask, n, ctx_stream(c, stream));
 }
 
 int olf_frames_pack_dev(olf_ctx* c, const olf_frame_buffers* fb, int n_pairs, uint8_t* d_dst, size_t dst_capacity, uint64_t* d_bytes, void* stream)
@@ -624,217 +472,11 @@ int olf_frames_pack_dev(olf_ctx* c, const olf_frame_buffers* fb, int n_pairs, ui
         set_error("olf_frames_pack_dev: bad argument"); return OLF_ERR_INVALID;
     }
     OLF_TRY(check_device(c, "olf_frames_pack_dev"));
-    OLF_TRY(join_if_pending(c, stream ? (hipStream_t)stream : c->stream));      // (the packer reads every output of the frame call, the line path's too)
+    OLF_TRY(join_if_pending(c, ctx_stream(c, stream)));      // (the packer reads every output of the frame call, the line path's too)
     void* ofs = nullptr;
-    OLF_TRY(scratch_get(c, 3, (size_t)8 * n_pairs * sizeof(int) + 64, &ofs));
+    OLF_TRY(scratch_get(c, SCRATCH_PACK, (size_t)8 * n_pairs * sizeof(int) + 64, &ofs));
     return olf::launch_pack_records(*fb, n_pairs, c->orb.geom.outCap, c->line.geom.outCap, d_dst, dst_capacity, static_cast<int*>(ofs),
-                                    reinterpret_cast<unsigned long long*>(d_bytes), c->ob.status, stream ? (hipStream_t)stream : c->stream);
-}
-
-int olf_debug_copy_bandwidth(olf_ctx* c, size_t bytes, int reps, double* gbytes_per_s)
-{
-    if (!c || !gbytes_per_s || bytes < 16 || reps < 1) { set_error("olf_debug_copy_bandwidth: bad argument"); return OLF_ERR_INVALID; }
-    OLF_TRY(check_device(c, "olf_debug_copy_bandwidth"));
-    void *a = nullptr, *b = nullptr;
-    OLF_HIP_CHECK(hipMalloc(&a, bytes));
-    if (hipMalloc(&b, bytes) != hipSuccess) { (void)hipFree(a); set_error("olf_debug_copy_bandwidth: hipMalloc failed"); return OLF_ERR_HIP; }
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    (void)hipMemsetAsync(a, 1, bytes, c->stream);
-    int rc = olf::launch_copy16(a, b, bytes, c->stream);                    // warm-up
-    (void)hipEventRecord(e0, c->stream);
-    for (int i = 0; i < reps && rc == OLF_OK; ++i) rc = olf::launch_copy16(i & 1 ? b : a, i & 1 ? a : b, bytes, c->stream);
-    (void)hipEventRecord(e1, c->stream);
-    const hipError_t se = hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(a); (void)hipFree(b);
-    if (rc != OLF_OK || se != hipSuccess || !(ms > 0)) { set_error("olf_debug_copy_bandwidth: copy failed"); return OLF_ERR_HIP; }
-    *gbytes_per_s = 2.0 * (double)(bytes / 16 * 16) * reps / (ms * 1e-3) / 1e9;      // bytes read + bytes written
-    return OLF_OK;
-}
-
-int olf_debug_lsd_waves(olf_ctx* c, int waves_per_image, int rob_entries)
-{
-    const bool pow2 = rob_entries > 0 && (rob_entries & (rob_entries - 1)) == 0;
-    if (!c || waves_per_image > 16 || waves_per_image < -1 || (rob_entries != 0 && (!pow2 || rob_entries < 128 || rob_entries > 1024))) {
-        set_error("olf_debug_lsd_waves: bad argument"); return OLF_ERR_INVALID;
-    }
-    c->lsd_force.waves = waves_per_image;
-    c->lsd_force.robEntries = rob_entries;
-    return OLF_OK;
-}
-
-// debug / tests: workgroups per image of the multi-wave growth (1, 2 or 4; 0: chosen from the batch size)
-int olf_debug_lsd_groups(olf_ctx* c, int groups)
-{
-    if (!c || !(groups == 0 || groups == 1 || groups == 2 || groups == 4)) { set_error("olf_debug_lsd_groups: bad argument"); return OLF_ERR_INVALID; }
-    c->lsd_force.groups = groups > 0 ? groups : -1;
-    return OLF_OK;
-}
-
-// debug / tests: cap the one-wave agent's primary pixel log at `entries` (0: the context's own size): images whose logged regions need more move to the spill arena
-int olf_debug_lsd_log_cap(olf_ctx* c, int entries)
-{
-    if (!c || entries < 0) { set_error("olf_debug_lsd_log_cap: bad argument"); return OLF_ERR_INVALID; }
-    OLF_TRY(check_device(c, "olf_debug_lsd_log_cap"));
-    LineGeom& g = c->line.geom;
-    if (entries > 0 && !g.spillArena) {      // a context whose log holds every pixel has no arena of its own
-        const size_t blocks = std::max<size_t>(2, (size_t)c->max_images - (size_t)c->max_images / 4);      // (tests: three quarters of the images may spill)
-        void* q = nullptr;
-        OLF_HIP_CHECK(hipMalloc(&q, blocks * 8 * (size_t)g.Ps));
-        c->allocs.push_back(q);
-        g.spillArena = static_cast<uint32_t*>(q); g.spillBlocks = (int)blocks;
-    }
-    g.logCap = entries > 0 ? std::min(entries, g.regionStride / 2) : g.regionStride / 2;
-    OLF_HIP_CHECK(hipDeviceSynchronize());
-    OLF_HIP_CHECK(hipMemcpy(c->lb.geom, &g, sizeof(LineGeom), hipMemcpyHostToDevice));
-    return OLF_OK;
-}
-
-// debug / tests: deal the growth groups of an image to consecutive workgroups (different XCDs under round-robin placement) instead of to one XCD
-int olf_debug_lsd_scatter(olf_ctx* c, int on)
-{
-    if (!c) { set_error("olf_debug_lsd_scatter: bad argument"); return OLF_ERR_INVALID; }
-    c->lsd_force.scatter = on ? 1 : 0;
-    return OLF_OK;
-}
-
-// debug / tests: the std::sort seed-order kernel (lsd_seedsort.hip) on a caller-supplied key array ((field << 22) | payload, sorted by the
-// 10-bit field ascending exactly as libstdc++'s std::sort would leave it); kthr: only keys whose field is <= kthr are listed (-1: from the
-// image statistics -- not meaningful here, pass n_bins - 1 to list everything); depth_limit: introsort's depth limit (-1: 2 * floor(log2 n))
-int olf_debug_seed_sort(olf_ctx* c, const uint32_t* keys, int n, int kthr, int depth_limit, uint32_t* out, int32_t* out_n)
-{
-    if (!c || !keys || !out || !out_n || n < 0 || n > c->line.geom.Ps || kthr < 0 || kthr > 1023) { set_error("olf_debug_seed_sort: bad argument"); return OLF_ERR_INVALID; }
-    OLF_HIP_CHECK(hipMemcpyAsync(c->lb.keysA, keys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(launch_lsd_seedsort(c->line.geom, c->lb, lsd_plan(c->line.geom, c->lb, c->lsd_force, c->limits, 1), 1, c->stream, n, kthr, depth_limit));
-    int cnt = 0;
-    OLF_HIP_CHECK(hipMemcpyAsync(&cnt, c->lb.keyCount, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    *out_n = cnt;
-    if (cnt < 0 || cnt > n) { set_error("olf_debug_seed_sort: count out of range"); return OLF_ERR_HIP; }
-    if (cnt) OLF_HIP_CHECK(hipMemcpy(out, c->lb.keysB, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-    return OLF_OK;
-}
-
-// debug / tests: the 64-bit seed-order kernel (lsd_wide.hip) on a caller-supplied key array (field << 32 | payload); full = 0: compared by the field alone, the
-// order libstdc++'s std::sort leaves (convention C.9 variant 1); full = 1: compared as whole words (variant 0); kthr: the keys whose field is <= kthr are listed;
-// depth_limit: introsort's depth limit (-1: 2 * floor(log2 n)).  out receives the listed keys' payloads (the pixel addresses) in order.
-int olf_debug_seed_sort_wide(olf_ctx* c, const uint64_t* keys, int n, int64_t kthr, int depth_limit, int full, uint32_t* out, int32_t* out_n)
-{
-    if (!c || !keys || !out || !out_n || n < 0 || n > c->line.geom.Ps || kthr < 0 || kthr > 0xffffffffll || !c->line.geom.wide) {
-        set_error("olf_debug_seed_sort_wide: bad argument (the context must be a wide one: lsd_n_bins > 1024 or 2^22 pixels and more)"); return OLF_ERR_INVALID; }
-    OLF_HIP_CHECK(hipMemcpyAsync(c->lb.keysA, keys, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(launch_lsd_sort_wide(c->line.geom, c->lb, 1, c->stream, n, (long long)kthr, depth_limit, full ? 1 : 0));
-    int cnt = 0;
-    OLF_HIP_CHECK(hipMemcpyAsync(&cnt, c->lb.keyCount, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    *out_n = cnt;
-    if (cnt < 0 || cnt > n) { set_error("olf_debug_seed_sort_wide: count out of range"); return OLF_ERR_HIP; }
-    if (cnt) OLF_HIP_CHECK(hipMemcpy(out, c->lb.keysB, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-    return check_status(c);
-}
-
-// debug / tests: which seed-sort kernel runs (-1: chosen from the batch size; 0: one wave per image; 1 / 2 / 5: 4 / 8 / 2 waves per image)
-int olf_debug_seed_sort_mode(olf_ctx* c, int mode)
-{
-    if (!c || mode < -1 || mode == 3 || mode == 4 || mode > 5) { set_error("olf_debug_seed_sort_mode: bad argument"); return OLF_ERR_INVALID; }
-    c->lsd_force.sortMode = mode;
-    return OLF_OK;
-}
-
-// debug / tests: cap the chunk pool of the multi-wave growth (0: the whole pool) so that the fall-back to the one-wave agent can be exercised
-int olf_debug_lsd_pool(olf_ctx* c, int pool_chunks)
-{
-    if (!c || pool_chunks < 0) { set_error("olf_debug_lsd_pool: bad argument"); return OLF_ERR_INVALID; }
-    c->lsd_force.poolChunks = pool_chunks;
-    return OLF_OK;
-}
-
-// debug: the regions logged by the last growth for `image`, in detection order: (first chunk or list start, pixels, final region angle) triples
-int olf_debug_lsd_regions(olf_ctx* c, int image, int32_t* start_n /* [cap][2] */, double* angle, int cap, int32_t* count)
-{
-    if (!c || !start_n || !angle || !count || image < 0 || image >= c->max_images) return OLF_ERR_INVALID;
-    OLF_HIP_CHECK(hipDeviceSynchronize());
-    int nr = 0;
-    OLF_HIP_CHECK(hipMemcpy(&nr, c->lb.regCount + image, sizeof(int), hipMemcpyDeviceToHost));
-    *count = nr;
-    struct Rec { int start, n; double angle; };
-    std::vector<Rec> r((size_t)std::min(nr, cap));
-    if (!r.empty())
-        OLF_HIP_CHECK(hipMemcpy(r.data(), reinterpret_cast<const Rec*>(c->lb.keysA) + (size_t)image * c->line.geom.maxRegions, r.size() * sizeof(Rec), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < r.size(); ++i) { start_n[2 * i] = r[i].start; start_n[2 * i + 1] = r[i].n; angle[i] = r[i].angle; }
-    return OLF_OK;
-}
-
-// debug: the owner words (seed rank << 10 | ROB slot, 0xffffffff = never claimed) the last multi-region growth left for `image` (Ws*Hs words)
-int olf_debug_lsd_owner(olf_ctx* c, int image, uint32_t* out)
-{
-    if (!c || !out || image < 0 || image >= c->lb.ownerImages) return OLF_ERR_INVALID;
-    OLF_HIP_CHECK(hipDeviceSynchronize());
-    OLF_HIP_CHECK(hipMemcpy(out, c->lb.owner + (size_t)image * c->line.geom.Ps, (size_t)c->line.geom.Ps * 4, hipMemcpyDeviceToHost));
-    return OLF_OK;
-}
-
-int olf_debug_status_n(olf_ctx* c, int32_t* out, int n)
-{
-    if (!c || !out || n < 1 || n > 256) return OLF_ERR_INVALID;
-    OLF_HIP_CHECK(hipDeviceSynchronize());
-    OLF_HIP_CHECK(hipMemcpy(out, c->ob.status, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return OLF_OK;
-}
-
-int olf_debug_fdiv_sweep(olf_ctx* c, uint64_t seed, int blocks, int per_thread, uint64_t* mismatches)
-{
-    if (!c || !mismatches || blocks < 1 || per_thread < 1) { set_error("olf_debug_fdiv_sweep: bad argument"); return OLF_ERR_INVALID; }
-    void* st = nullptr;
-    OLF_TRY(scratch_get(c, 1, 64, &st));
-    OLF_HIP_CHECK(hipMemsetAsync(st, 0, 8, c->stream));
-    OLF_TRY(launch_fdiv_sweep((unsigned long long)seed, blocks, per_thread, (unsigned long long*)st, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(mismatches, st, 8, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
-}
-
-int olf_debug_sqrtq_sweep(olf_ctx* c, int count, uint64_t* mismatches)
-{
-    if (!c || !mismatches || count < 1) { set_error("olf_debug_sqrtq_sweep: bad argument"); return OLF_ERR_INVALID; }
-    void* st = nullptr;
-    OLF_TRY(scratch_get(c, 1, 64, &st));
-    OLF_HIP_CHECK(hipMemsetAsync(st, 0, 8, c->stream));
-    OLF_TRY(launch_sqrtq_sweep(count, (unsigned long long*)st, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(mismatches, st, 8, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
-}
-
-int olf_debug_align_sweep(olf_ctx* c, uint64_t seed, int blocks, int per_thread, uint64_t* out3)
-{
-    if (!c || !out3 || blocks < 1 || per_thread < 1) { set_error("olf_debug_align_sweep: bad argument"); return OLF_ERR_INVALID; }
-    if (c->line.geom.alignTanLo < 0.f) { set_error("olf_debug_align_sweep: the cheap alignment test is off for lsd_ang_th > 80 degrees"); return OLF_ERR_INVALID; }
-    void* st = nullptr;
-    OLF_TRY(scratch_get(c, 1, 64, &st));
-    OLF_HIP_CHECK(hipMemsetAsync(st, 0, 24, c->stream));
-    OLF_TRY(launch_align_sweep(c->lb, (unsigned long long)seed, blocks, per_thread, (unsigned long long*)st, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(out3, st, 24, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
-}
-
-int olf_orb_debug_candidates(olf_ctx* c, int image, int level, int32_t* xys, int cap, int32_t* count)
-{
-    if (!c || !xys || !count || image < 0 || image >= c->max_images || level < 0 || level >= c->orb.geom.nlevels) return OLF_ERR_INVALID;
-    const OrbGeom& g = c->orb.geom;
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    int n = 0;
-    OLF_HIP_CHECK(hipMemcpy(&n, c->ob.candCount + image * g.nlevels + level, sizeof(int), hipMemcpyDeviceToHost));
-    *count = n;
-    std::vector<uint32_t> tmp(std::max(n, 1));
-    OLF_HIP_CHECK(hipMemcpy(tmp.data(), c->ob.cand + (size_t)image * g.candTotal + g.lv[level].candBase, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (int i = 0; i < std::min(n, cap); ++i) {
-        xys[3 * i] = tmp[i] >> 20; xys[3 * i + 1] = (tmp[i] >> 8) & 0xfff; xys[3 * i + 2] = tmp[i] & 0xff;
-    }
-    return OLF_OK;
+                                    reinterpret_cast<unsigned long long*>(d_bytes), c->ob.status, ctx_stream(c, stream));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -845,23 +487,7 @@ int olf_stereo_points_dev(olf_ctx* c, int n_pairs, const olf_keypoint* d_kps, co
     OLF_TRY(check_device(c, "olf_stereo_points_dev"));
     if (n_pairs < 0 || 2 * n_pairs > c->max_images) return OLF_ERR_CAPACITY;
     if (n_pairs == 0) return OLF_OK;
-    return stage_stereo_points(c, n_pairs, d_kps, d_desc, d_counts, d_uright, d_depth, stream ? (hipStream_t)stream : c->stream);
-}
-
-int olf_stereo_points(olf_ctx* c, const uint8_t* images, int n_pairs, olf_keypoint* kps, uint8_t* desc, int32_t* counts, float* uright,
-                      float* depth)
-{
-    if (!c || !images || !kps || !desc || !counts || !uright || !depth) { set_error("olf_stereo_points: null argument"); return OLF_ERR_INVALID; }
-    const int n_images = 2 * n_pairs;
-    if (n_pairs < 0 || n_images > c->max_images) return OLF_ERR_CAPACITY;
-    if (n_pairs == 0) return OLF_OK;
-    olf_frame_buffers h = {}; h.kps = kps; h.desc = desc; h.counts = counts; h.uright = uright; h.depth = depth;
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, (size_t)c->W * c->H * n_images, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_orb_extract_dev(c, c->d_images, n_images, c->d_out.kps, c->d_out.desc, c->d_out.counts, c->stream));
-    OLF_TRY(olf_stereo_points_dev(c, n_pairs, c->d_out.kps, c->d_out.desc, c->d_out.counts, c->d_out.uright, c->d_out.depth, c->stream));
-    OLF_TRY(fb_copy(c, h, FB_KPS, FB_DEPTH, n_images, hipMemcpyDeviceToHost));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return check_status(c);
+    return stage_stereo_points(c, n_pairs, d_kps, d_desc, d_counts, d_uright, d_depth, ctx_stream(c, stream));
 }
 
 int olf_match_bf_dev(olf_ctx* c, const uint8_t* dA, const int32_t* nA, int strideA, int a_step, const uint8_t* dB, const int32_t* nB,
@@ -870,52 +496,15 @@ int olf_match_bf_dev(olf_ctx* c, const uint8_t* dA, const int32_t* nA, int strid
     if (!c || !dA || !dB || !nA || !nB || !d_m12 || strideA < 0 || strideB < 0 || n_sets < 0) { set_error("olf_match_bf_dev: bad argument"); return OLF_ERR_INVALID; }
     OLF_TRY(check_device(c, "olf_match_bf_dev"));
     if (n_sets == 0 || strideA == 0) return OLF_OK;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = ctx_stream(c, stream);
     // line descriptors / counts of a frame call whose line path is still running (deferred join): wait for it; ORB descriptors go ahead
     if (in_pending_line_outputs(c, dA) || in_pending_line_outputs(c, dB) || in_pending_line_outputs(c, nA) || in_pending_line_outputs(c, nB)) OLF_TRY(join_if_pending(c, s));
-    void* ws = nullptr;
-    OLF_TRY(scratch_get(c, 0, (size_t)3 * (strideA + strideB) * n_sets * sizeof(int), &ws));
+    int* ws = nullptr;
+    Carve k;
+    k.add(&ws, (size_t)3 * (strideA + strideB) * n_sets);
+    OLF_TRY(k.bind(c, SCRATCH_KNN));
     StageScope t(c, s, ST_MATCH_BF);
-    return launch_match_bf(dA, nA, strideA, a_step, dB, nB, strideB, b_step, n_sets, nnr, best_lr, (int*)ws, d_m12, s);
-}
-
-// host staging helper: [descA | descB | nA nB | out...]
-int olf_match_bf(olf_ctx* c, const uint8_t* descA, int nA, const uint8_t* descB, int nB, float nnr, int best_lr, int32_t* m12)
-{
-    if (!c || !m12 || nA < 0 || nB < 0 || (nA && !descA) || (nB && !descB)) { set_error("olf_match_bf: bad argument"); return OLF_ERR_INVALID; }
-    if (nA == 0) return OLF_OK;
-    void* st = nullptr;
-    const size_t bA = (size_t)nA * 32, bB = (size_t)std::max(nB, 1) * 32;
-    OLF_TRY(scratch_get(c, 1, bA + bB + 64 + (size_t)nA * 4, &st));
-    uint8_t* dA = (uint8_t*)st; uint8_t* dB = dA + bA; int* dn = (int*)(dB + bB); int* dm = dn + 16;
-    int n[2] = {nA, nB};
-    OLF_HIP_CHECK(hipMemcpyAsync(dA, descA, bA, hipMemcpyHostToDevice, c->stream));
-    if (nB) OLF_HIP_CHECK(hipMemcpyAsync(dB, descB, (size_t)nB * 32, hipMemcpyHostToDevice, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(dn, n, sizeof(n), hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_match_bf_dev(c, dA, dn, nA, 1, dB, dn + 1, std::max(nB, 1), 1, 1, nnr, best_lr, dm, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(m12, dm, (size_t)nA * 4, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
-}
-
-int olf_knn2(olf_ctx* c, const uint8_t* descQ, int nQ, const uint8_t* descT, int nT, int32_t* idx0, int32_t* dist0, int32_t* dist1)
-{
-    if (!c || !idx0 || !dist0 || !dist1 || nQ < 0 || nT < 0 || (nQ && !descQ) || (nT && !descT)) { set_error("olf_knn2: bad argument"); return OLF_ERR_INVALID; }
-    if (nQ == 0) return OLF_OK;
-    void* st = nullptr;
-    const size_t bQ = (size_t)nQ * 32, bT = (size_t)std::max(nT, 1) * 32;
-    OLF_TRY(scratch_get(c, 1, bQ + bT + 64 + (size_t)nQ * 12, &st));
-    uint8_t* dQ = (uint8_t*)st; uint8_t* dT = dQ + bQ; int* dn = (int*)(dT + bT); int* o = dn + 16;
-    int n[2] = {nQ, nT};
-    OLF_HIP_CHECK(hipMemcpyAsync(dQ, descQ, bQ, hipMemcpyHostToDevice, c->stream));
-    if (nT) OLF_HIP_CHECK(hipMemcpyAsync(dT, descT, (size_t)nT * 32, hipMemcpyHostToDevice, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(dn, n, sizeof(n), hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(launch_knn2(dQ, dn, nQ, dT, dn + 1, std::max(nT, 1), 1, o, o + nQ, o + 2 * nQ, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(idx0, o, (size_t)nQ * 4, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(dist0, o + nQ, (size_t)nQ * 4, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(dist1, o + 2 * nQ, (size_t)nQ * 4, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
+    return launch_match_bf(dA, nA, strideA, a_step, dB, nB, strideB, b_step, n_sets, nnr, best_lr, ws, d_m12, s);
 }
 
 int olf_match_candidates_dev(olf_ctx* c, const uint8_t* dQ, int nQ, const uint8_t* dT, int nT, const int32_t* d_offs, const int32_t* d_cand,
@@ -923,41 +512,9 @@ int olf_match_candidates_dev(olf_ctx* c, const uint8_t* dQ, int nQ, const uint8_
 {
     if (!c || nQ < 0 || nT < 0 || (nQ && (!dQ || !d_offs || !d_dist))) { set_error("olf_match_candidates_dev: bad argument"); return OLF_ERR_INVALID; }
     OLF_TRY(check_device(c, "olf_match_candidates_dev"));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = ctx_stream(c, stream);
     StageScope t(c, s, ST_MATCH_BF);
     return launch_match_candidates(dQ, nQ, dT, nT, d_offs, d_cand, d_dist, s);
-}
-
-int olf_match_candidates(olf_ctx* c, const uint8_t* descQ, int nQ, const uint8_t* descT, int nT, const int32_t* offs, const int32_t* cand,
-                         uint16_t* dist)
-{
-    if (!c || nQ < 0 || nT < 0 || (nQ && (!descQ || !offs)) || (nT && !descT)) { set_error("olf_match_candidates: bad argument"); return OLF_ERR_INVALID; }
-    if (nQ == 0) return OLF_OK;
-    const int nnz = offs[nQ];
-    if (nnz < 0 || offs[0] != 0 || (nnz && (!cand || !dist))) { set_error("olf_match_candidates: bad CSR"); return OLF_ERR_INVALID; }
-    if (nnz == 0) return OLF_OK;
-    void* st = nullptr;
-    const size_t bQ = (size_t)nQ * 32, bT = (size_t)std::max(nT, 1) * 32, bO = ((size_t)(nQ + 1) * 4 + 15) & ~(size_t)15, bC = ((size_t)nnz * 4 + 15) & ~(size_t)15;
-    OLF_TRY(scratch_get(c, 1, bQ + bT + bO + bC + (size_t)nnz * 2 + 64, &st));
-    uint8_t* dQ = (uint8_t*)st; uint8_t* dT = dQ + bQ; int* dO = (int*)(dT + bT); int* dC = (int*)((uint8_t*)dO + bO); uint16_t* dD = (uint16_t*)((uint8_t*)dC + bC);
-    OLF_HIP_CHECK(hipMemcpyAsync(dQ, descQ, bQ, hipMemcpyHostToDevice, c->stream));
-    if (nT) OLF_HIP_CHECK(hipMemcpyAsync(dT, descT, (size_t)nT * 32, hipMemcpyHostToDevice, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(dO, offs, (size_t)(nQ + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(dC, cand, (size_t)nnz * 4, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_match_candidates_dev(c, dQ, nQ, dT, nT, dO, dC, dD, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(dist, dD, (size_t)nnz * 2, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
-}
-
-// ---- Frame::mGrid (grid.hip) -----------------------------------------------------------------------------------------------------------
-// mfGridElementWidthInv / mfGridElementHeightInv, src/Frame.cc:186-187: static_cast<float>(FRAME_GRID_COLS) / (mnMaxX - mnMinX), in float
-static bool grid_scales(float minX, float maxX, float minY, float maxY, float* wInv, float* hInv)
-{
-    if (!(maxX > minX) || !(maxY > minY)) return false;
-    *wInv = static_cast<float>(OLF_GRID_COLS) / (maxX - minX);
-    *hInv = static_cast<float>(OLF_GRID_ROWS) / (maxY - minY);
-    return true;
 }
 
 int olf_frame_grid_dev(olf_ctx* c, int n_frames, int img_stride, const olf_keypoint* d_kps, const int32_t* d_counts, float minX, float maxX, float minY,
@@ -971,28 +528,7 @@ int olf_frame_grid_dev(olf_ctx* c, int n_frames, int img_stride, const olf_keypo
     const int cap = c->orb.geom.outCap;
     if (cap > OLF_GRID_MAX_KEYS) { set_error("olf_frame_grid_dev: more than OLF_GRID_MAX_KEYS key points per frame (their cells sit in LDS)"); return OLF_ERR_CAPACITY; }
     return launch_assign_grid(d_kps, (size_t)img_stride * cap, d_counts, img_stride, 0, cap, minX, minY, wInv, hInv, n_frames, d_cell_offsets, d_cell_index,
-                              (size_t)cap, stream ? (hipStream_t)stream : c->stream);
-}
-
-int olf_frame_grid(olf_ctx* c, const olf_keypoint* keys, int n, float minX, float maxX, float minY, float maxY, int32_t* cell_offsets, int32_t* cell_index)
-{
-    float wInv, hInv;
-    if (!c || n < 0 || (n && (!keys || !cell_index)) || !cell_offsets || !grid_scales(minX, maxX, minY, maxY, &wInv, &hInv)) {
-        set_error("olf_frame_grid: bad argument"); return OLF_ERR_INVALID;
-    }
-    if (n > OLF_GRID_MAX_KEYS) { set_error("olf_frame_grid: more than OLF_GRID_MAX_KEYS key points"); return OLF_ERR_CAPACITY; }
-    OLF_TRY(check_device(c, "olf_frame_grid"));
-    void* st = nullptr;
-    const size_t bK = ((size_t)std::max(n, 1) * sizeof(olf_keypoint) + 15) & ~(size_t)15, bO = ((size_t)(OLF_GRID_CELLS + 1) * 4 + 15) & ~(size_t)15;
-    OLF_TRY(scratch_get(c, 1, bK + bO + (size_t)std::max(n, 1) * 4, &st));
-    olf_keypoint* dK = (olf_keypoint*)st; int* dO = (int*)((uint8_t*)st + bK); int* dI = (int*)((uint8_t*)dO + bO);
-    if (n) OLF_HIP_CHECK(hipMemcpyAsync(dK, keys, (size_t)n * sizeof(olf_keypoint), hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(launch_assign_grid(dK, 0, nullptr, 0, n, n, minX, minY, wInv, hInv, 1, dO, dI, (size_t)std::max(n, 1), c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(cell_offsets, dO, (size_t)(OLF_GRID_CELLS + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    const int used = cell_offsets[OLF_GRID_CELLS];
-    if (used > 0) OLF_HIP_CHECK(hipMemcpy(cell_index, dI, (size_t)used * 4, hipMemcpyDeviceToHost));
-    return OLF_OK;
+                              (size_t)cap, ctx_stream(c, stream));
 }
 
 int olf_features_in_area_dev(olf_ctx* c, const olf_keypoint* d_keys, const int32_t* d_cell_offsets, const int32_t* d_cell_index, float minX, float maxX,
@@ -1006,41 +542,7 @@ int olf_features_in_area_dev(olf_ctx* c, const olf_keypoint* d_keys, const int32
     }
     OLF_TRY(check_device(c, "olf_features_in_area_dev"));
     return launch_features_in_area(d_keys, d_cell_offsets, d_cell_index, minX, minY, wInv, hInv, n_queries, d_queries, d_cand_offsets, d_cand_idx,
-                                   cand_capacity, c->ob.status, stream ? (hipStream_t)stream : c->stream);
-}
-
-int olf_features_in_area(olf_ctx* c, const olf_keypoint* keys, int n_keys, const int32_t* cell_offsets, const int32_t* cell_index, float minX, float maxX,
-                         float minY, float maxY, int n_queries, const olf_area_query* queries, int32_t* cand_offsets, int32_t* cand_idx, int cand_capacity)
-{
-    if (!c || n_keys < 0 || (n_keys && !keys) || n_queries < 0 || cand_capacity < 0 || !cand_offsets || (n_queries && !queries) || (cand_capacity && !cand_idx) ||
-        !(maxX > minX) || !(maxY > minY)) {
-        set_error("olf_features_in_area: bad argument"); return OLF_ERR_INVALID;
-    }
-    if (!grid_is_valid(cell_offsets, cell_index, n_keys)) { set_error("olf_features_in_area: the grid does not describe n_keys features"); return OLF_ERR_INVALID; }
-    OLF_TRY(check_device(c, "olf_features_in_area"));
-    const int used = cell_offsets[OLF_GRID_CELLS];
-    auto up16 = [](size_t b) { return (std::max<size_t>(b, 1) + 15) & ~(size_t)15; };
-    const size_t bK = up16((size_t)n_keys * sizeof(olf_keypoint)), bO = up16((size_t)(OLF_GRID_CELLS + 1) * 4), bI = up16((size_t)used * 4),
-                 bQ = up16((size_t)n_queries * sizeof(olf_area_query)), bCO = up16((size_t)(n_queries + 1) * 4), bC = up16((size_t)cand_capacity * 4);
-    void* st = nullptr;
-    OLF_TRY(scratch_get(c, 1, bK + bO + bI + bQ + bCO + bC, &st));
-    uint8_t* p = (uint8_t*)st;
-    olf_keypoint* dK = (olf_keypoint*)p; p += bK;
-    int* dO = (int*)p; p += bO;
-    int* dI = (int*)p; p += bI;
-    olf_area_query* dQ = (olf_area_query*)p; p += bQ;
-    int* dCO = (int*)p; p += bCO;
-    int* dC = (int*)p;
-    if (n_keys) OLF_HIP_CHECK(hipMemcpyAsync(dK, keys, (size_t)n_keys * sizeof(olf_keypoint), hipMemcpyHostToDevice, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(dO, cell_offsets, (size_t)(OLF_GRID_CELLS + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    if (used) OLF_HIP_CHECK(hipMemcpyAsync(dI, cell_index, (size_t)used * 4, hipMemcpyHostToDevice, c->stream));
-    if (n_queries) OLF_HIP_CHECK(hipMemcpyAsync(dQ, queries, (size_t)n_queries * sizeof(olf_area_query), hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_features_in_area_dev(c, dK, dO, dI, minX, maxX, minY, maxY, n_queries, dQ, dCO, dC, cand_capacity, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(cand_offsets, dCO, (size_t)(n_queries + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    const int have = std::min(cand_offsets[n_queries], cand_capacity);
-    if (have > 0) OLF_HIP_CHECK(hipMemcpy(cand_idx, dC, (size_t)have * 4, hipMemcpyDeviceToHost));
-    return check_status(c);
+                                   cand_capacity, c->ob.status, ctx_stream(c, stream));
 }
 
 int olf_ctx_device_buffers(const olf_ctx* c, olf_frame_buffers* out)
@@ -1055,7 +557,7 @@ int olf_cvt_gray_dev(olf_ctx* c, const uint8_t* d_src, int code, int n_images, u
     if (!c || !d_src || !d_gray || code < 0 || code > 3 || n_images < 0) { set_error("olf_cvt_gray_dev: bad argument"); return OLF_ERR_INVALID; }
     OLF_TRY(check_device(c, "olf_cvt_gray_dev"));
     if (n_images == 0) return OLF_OK;
-    return launch_cvt_gray(d_src, d_gray, c->W, c->H, code, n_images, stream ? (hipStream_t)stream : c->stream);
+    return launch_cvt_gray(d_src, d_gray, c->W, c->H, code, n_images, ctx_stream(c, stream));
 }
 
 int olf_init_undistort_rectify_map_dev(olf_ctx* c, const double* K, const double* D, int n_dist, const double* R, const double* P, int w, int h,
@@ -1078,22 +580,7 @@ int olf_init_undistort_rectify_map_dev(olf_ctx* c, const double* K, const double
     ir[6] = (m[3] * m[7] - m[4] * m[6]) * d; ir[7] = (m[1] * m[6] - m[0] * m[7]) * d; ir[8] = (m[0] * m[4] - m[1] * m[3]) * d;
     double k[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int i = 0; i < n_dist; ++i) k[i] = D[i];
-    return launch_init_rectify_map(ir, k, K[0], K[4], K[2], K[5], w, h, d_map1, d_map2, stream ? (hipStream_t)stream : c->stream);
-}
-
-int olf_init_undistort_rectify_map(olf_ctx* c, const double* K, const double* D, int n_dist, const double* R, const double* P, int w, int h, float* map1, float* map2)
-{
-    if (!c || !map1 || !map2 || w < 1 || h < 1) { set_error("olf_init_undistort_rectify_map: bad argument"); return OLF_ERR_INVALID; }
-    void* st = nullptr;
-    const size_t bm = (size_t)w * h * sizeof(float);
-    OLF_TRY(scratch_get(c, 2, 2 * bm + 64, &st));
-    float* d1 = static_cast<float*>(st);
-    float* d2 = d1 + (size_t)w * h;
-    OLF_TRY(olf_init_undistort_rectify_map_dev(c, K, D, n_dist, R, P, w, h, d1, d2, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(map1, d1, bm, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(map2, d2, bm, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
+    return launch_init_rectify_map(ir, k, K[0], K[4], K[2], K[5], w, h, d_map1, d_map2, ctx_stream(c, stream));
 }
 
 int olf_remap_linear_dev(olf_ctx* c, const uint8_t* d_src, int sw, int sh, const float* d_mapx, const float* d_mapy, int dw, int dh, int n_images,
@@ -1102,77 +589,7 @@ int olf_remap_linear_dev(olf_ctx* c, const uint8_t* d_src, int sw, int sh, const
     if (!c || !d_src || !d_mapx || !d_mapy || !d_dst || sw < 1 || sh < 1 || dw < 1 || dh < 1 || n_images < 0) { set_error("olf_remap_linear_dev: bad argument"); return OLF_ERR_INVALID; }
     OLF_TRY(check_device(c, "olf_remap_linear_dev"));
     if (n_images == 0) return OLF_OK;
-    return launch_remap_linear(d_src, sw, sh, d_mapx, d_mapy, dw, dh, d_dst, n_images, stream ? (hipStream_t)stream : c->stream);
-}
-
-int olf_cvt_gray(olf_ctx* c, const uint8_t* src, int code, int n_images, uint8_t* gray)
-{
-    if (!c || !src || !gray || code < 0 || code > 3 || n_images < 0) { set_error("olf_cvt_gray: bad argument"); return OLF_ERR_INVALID; }
-    if (n_images == 0) return OLF_OK;
-    const size_t npx = (size_t)c->W * c->H * n_images, cn = code >= 2 ? 4 : 3;
-    void* st = nullptr;
-    OLF_TRY(scratch_get(c, 2, npx * (cn + 1) + 64, &st));
-    uint8_t* ds = (uint8_t*)st; uint8_t* dd = ds + ((npx * cn + 15) & ~(size_t)15);
-    OLF_HIP_CHECK(hipMemcpyAsync(ds, src, npx * cn, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_cvt_gray_dev(c, ds, code, n_images, dd, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(gray, dd, npx, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
-}
-
-int olf_remap_linear(olf_ctx* c, const uint8_t* src, int sw, int sh, const float* mapx, const float* mapy, int dw, int dh, int n_images, uint8_t* dst)
-{
-    if (!c || !src || !mapx || !mapy || !dst || sw < 1 || sh < 1 || dw < 1 || dh < 1 || n_images < 0) { set_error("olf_remap_linear: bad argument"); return OLF_ERR_INVALID; }
-    if (n_images == 0) return OLF_OK;
-    const size_t bs = ((size_t)sw * sh * n_images + 15) & ~(size_t)15, bm = (size_t)dw * dh * 4, bd = (size_t)dw * dh * n_images;
-    void* st = nullptr;
-    OLF_TRY(scratch_get(c, 2, bs + 2 * bm + bd + 64, &st));
-    uint8_t* ds = (uint8_t*)st; float* mx = (float*)(ds + bs); float* my = mx + (size_t)dw * dh; uint8_t* dd = (uint8_t*)(my + (size_t)dw * dh);
-    OLF_HIP_CHECK(hipMemcpyAsync(ds, src, (size_t)sw * sh * n_images, hipMemcpyHostToDevice, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(mx, mapx, bm, hipMemcpyHostToDevice, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(my, mapy, bm, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_remap_linear_dev(c, ds, sw, sh, mx, my, dw, dh, n_images, dd, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(dst, dd, bd, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
-}
-
-int olf_hamming_matrix(olf_ctx* c, const uint8_t* descA, int nA, const uint8_t* descB, int nB, uint16_t* out)
-{
-    if (!c || !out || nA < 0 || nB < 0 || (nA && !descA) || (nB && !descB)) { set_error("olf_hamming_matrix: bad argument"); return OLF_ERR_INVALID; }
-    if (nA == 0 || nB == 0) return OLF_OK;
-    void* st = nullptr;
-    const size_t bA = (size_t)nA * 32, bB = (size_t)nB * 32, bO = (size_t)nA * nB * 2;
-    OLF_TRY(scratch_get(c, 1, bA + bB + bO, &st));
-    uint8_t* dA = (uint8_t*)st; uint8_t* dB = dA + bA; uint16_t* dO = (uint16_t*)(dB + bB);
-    OLF_HIP_CHECK(hipMemcpyAsync(dA, descA, bA, hipMemcpyHostToDevice, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(dB, descB, bB, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(launch_hamming_matrix(dA, nA, dB, nB, dO, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(out, dO, bO, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
-}
-
-int olf_distinctive_descriptors(olf_ctx* c, const uint8_t* desc, const int32_t* offs, int n_points, int32_t* best)
-{
-    if (!c || !offs || !best || n_points < 0) { set_error("olf_distinctive_descriptors: bad argument"); return OLF_ERR_INVALID; }
-    if (n_points == 0) return OLF_OK;
-    const int total = offs[n_points];
-    if (offs[0] != 0 || total < 0 || (total > 0 && !desc)) { set_error("olf_distinctive_descriptors: bad offsets"); return OLF_ERR_INVALID; }
-    for (int i = 0; i < n_points; ++i) {
-        if (offs[i + 1] < offs[i]) { set_error("olf_distinctive_descriptors: offsets must not decrease"); return OLF_ERR_INVALID; }
-        if (offs[i + 1] - offs[i] > 1024) { set_error("olf_distinctive_descriptors: more than 1024 observations of one landmark"); return OLF_ERR_CAPACITY; }
-    }
-    void* st = nullptr;
-    const size_t bD = ((size_t)total * 32 + 15) & ~(size_t)15, bO = (size_t)(n_points + 1) * 4;
-    OLF_TRY(scratch_get(c, 1, bD + bO + (size_t)n_points * 4 + 64, &st));
-    uint8_t* dD = (uint8_t*)st; int* dO = (int*)(dD + bD); int* dB = dO + n_points + 1;
-    if (total) OLF_HIP_CHECK(hipMemcpyAsync(dD, desc, (size_t)total * 32, hipMemcpyHostToDevice, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(dO, offs, bO, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(launch_distinctive(dD, dO, n_points, dB, c->stream));
-    OLF_HIP_CHECK(hipMemcpyAsync(best, dB, (size_t)n_points * 4, hipMemcpyDeviceToHost, c->stream));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
+    return launch_remap_linear(d_src, sw, sh, d_mapx, d_mapy, dw, dh, d_dst, n_images, ctx_stream(c, stream));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1184,67 +601,12 @@ int olf_line_extract_dev(olf_ctx* c, const uint8_t* d_images, int n_images, olf_
     OLF_TRY(check_device(c, "olf_line_extract_dev"));
     if (n_images < 0 || n_images > c->max_images) return OLF_ERR_CAPACITY;
     if (n_images == 0) return OLF_OK;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = ctx_stream(c, stream);
     const LsdPlan plan = lsd_plan(c->line.geom, c->lb, c->lsd_force, c->limits, n_images);
     OLF_TRY(stage_lsd_front(c, plan, d_images, n_images, s, true));
     OLF_TRY(stage_lsd_grow(c, plan, n_images, s));
     OLF_TRY(stage_lsd_rect(c, plan, n_images, s));
     return stage_line_lbd(c, d_images, n_images, d_kls, d_ldesc, d_lcounts, s);
-}
-
-int olf_line_extract(olf_ctx* c, const uint8_t* images, int n_images, olf_keyline* kls, uint8_t* ldesc, int32_t* lcounts)
-{
-    if (!c || !images || !kls || !ldesc || !lcounts) { set_error("olf_line_extract: null argument"); return OLF_ERR_INVALID; }
-    if (n_images < 0 || n_images > c->max_images) return OLF_ERR_CAPACITY;
-    if (n_images == 0) return OLF_OK;
-    olf_frame_buffers h = {}; h.kls = kls; h.ldesc = ldesc; h.lcounts = lcounts;
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, (size_t)c->W * c->H * n_images, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_line_extract_dev(c, c->d_images, n_images, c->d_out.kls, c->d_out.ldesc, c->d_out.lcounts, c->stream));
-    OLF_TRY(fb_copy(c, h, FB_KLS, FB_LCOUNTS, n_images, hipMemcpyDeviceToHost));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return check_status(c);
-}
-
-int olf_line_extract_strided(olf_ctx* c, const uint8_t* image, size_t row_stride, olf_keyline* kls, uint8_t* ldesc, int32_t* lcount)
-{
-    if (!c || !image || !kls || !ldesc || !lcount || row_stride < (size_t)c->W) { set_error("olf_line_extract_strided: bad argument"); return OLF_ERR_INVALID; }
-    olf_frame_buffers h = {}; h.kls = kls; h.ldesc = ldesc; h.lcounts = lcount;
-    OLF_HIP_CHECK(hipMemcpy2DAsync(c->d_images, c->W, image, row_stride, c->W, c->H, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_line_extract_dev(c, c->d_images, 1, c->d_out.kls, c->d_out.ldesc, c->d_out.lcounts, c->stream));
-    OLF_TRY(fb_copy(c, h, FB_KLS, FB_LCOUNTS, 1, hipMemcpyDeviceToHost));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return check_status(c);
-}
-
-int olf_lbd_compute(olf_ctx* c, const uint8_t* images, int n_images, const olf_keyline* kls, const int32_t* lcounts, uint8_t* ldesc)
-{
-    if (!c || !images || !kls || !lcounts || !ldesc) { set_error("olf_lbd_compute: null argument"); return OLF_ERR_INVALID; }
-    if (n_images < 0 || n_images > c->max_images) return OLF_ERR_CAPACITY;
-    if (n_images == 0) return OLF_OK;
-    for (int i = 0; i < n_images; ++i)
-        if (lcounts[i] < 0 || lcounts[i] > c->line.geom.outCap) { set_error("olf_lbd_compute: count exceeds capacity"); return OLF_ERR_CAPACITY; }
-    olf_frame_buffers h = {}; h.kls = const_cast<olf_keyline*>(kls); h.ldesc = ldesc; h.lcounts = const_cast<int32_t*>(lcounts);
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, (size_t)c->W * c->H * n_images, hipMemcpyHostToDevice, c->stream));
-    // BinaryDescriptor::compute on the caller's key lines: no LSD, no selection
-    OLF_TRY(fb_copy(c, h, FB_KLS, FB_KLS, n_images, hipMemcpyHostToDevice));
-    OLF_TRY(fb_copy(c, h, FB_LCOUNTS, FB_LCOUNTS, n_images, hipMemcpyHostToDevice));
-    OLF_TRY(launch_lbd_dense(c->line.geom, c->lb, c->d_images, c->W, n_images, c->stream));
-    OLF_TRY(launch_lbd_desc(c->line.geom, c->lb, n_images, c->d_out.kls, c->d_out.ldesc, c->d_out.lcounts, c->stream));
-    OLF_TRY(fb_copy(c, h, FB_LDESC, FB_LDESC, n_images, hipMemcpyDeviceToHost));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
-}
-
-int olf_lsd_debug_scaled(olf_ctx* c, int image, uint8_t* dst, int32_t* ws, int32_t* hs)
-{
-    if (!c || !dst || image < 0 || image >= c->max_images) return OLF_ERR_INVALID;
-    if (c->scaled_aliased) { set_error("olf_lsd_debug_scaled: a batch context does not keep the enlarged image (use a context of at most 2048 images)"); return OLF_ERR_INVALID; }
-    const LineGeom& g = c->line.geom;
-    OLF_HIP_CHECK(hipDeviceSynchronize());
-    OLF_HIP_CHECK(hipMemcpy2D(dst, g.Ws, c->lb.scaled + (size_t)image * g.pitchS * g.Hs, g.pitchS, g.Ws, g.Hs, hipMemcpyDeviceToHost));
-    if (ws) *ws = g.Ws;
-    if (hs) *hs = g.Hs;
-    return OLF_OK;
 }
 
 int olf_stereo_lines_dev(olf_ctx* c, int n_pairs, const olf_keyline* d_kls, const uint8_t* d_ldesc, const int32_t* d_lcounts, int32_t* d_m12,
@@ -1254,28 +616,10 @@ int olf_stereo_lines_dev(olf_ctx* c, int n_pairs, const olf_keyline* d_kls, cons
     OLF_TRY(check_device(c, "olf_stereo_lines_dev"));
     if (n_pairs < 0 || 2 * n_pairs > c->max_images) return OLF_ERR_CAPACITY;
     if (n_pairs == 0) return OLF_OK;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = ctx_stream(c, stream);
     // key lines / descriptors of a frame call whose line path is still running (deferred join): this stream waits for it first
     if (s != c->stream2 && (in_pending_line_outputs(c, d_kls) || in_pending_line_outputs(c, d_ldesc) || in_pending_line_outputs(c, d_lcounts))) OLF_TRY(join_if_pending(c, s));
     return stage_stereo_lines(c, n_pairs, d_kls, d_ldesc, d_lcounts, d_m12, d_disp, d_le, s);
-}
-
-int olf_stereo_lines(olf_ctx* c, int n_pairs, const olf_keyline* kls, const uint8_t* ldesc, const int32_t* lcounts, int32_t* m12, float* disp,
-                     double* le)
-{
-    if (!c || !kls || !ldesc || !lcounts || !m12 || !disp || !le) { set_error("olf_stereo_lines: null argument"); return OLF_ERR_INVALID; }
-    if (n_pairs < 0 || 2 * n_pairs > c->max_images) return OLF_ERR_CAPACITY;
-    if (n_pairs == 0) return OLF_OK;
-    const size_t cap = c->line.geom.outCap, ni = 2 * (size_t)n_pairs;
-    for (size_t i = 0; i < ni; ++i)
-        if (lcounts[i] < 0 || lcounts[i] > (int)cap) { set_error("olf_stereo_lines: count exceeds capacity"); return OLF_ERR_CAPACITY; }
-    olf_frame_buffers h = {}; h.kls = const_cast<olf_keyline*>(kls); h.ldesc = const_cast<uint8_t*>(ldesc); h.lcounts = const_cast<int32_t*>(lcounts);
-    h.lmatches12 = m12; h.ldisp = disp; h.lle = le;
-    OLF_TRY(fb_copy(c, h, FB_KLS, FB_LCOUNTS, ni, hipMemcpyHostToDevice));
-    OLF_TRY(olf_stereo_lines_dev(c, n_pairs, c->d_out.kls, c->d_out.ldesc, c->d_out.lcounts, c->d_out.lmatches12, c->d_out.ldisp, c->d_out.lle, c->stream));
-    OLF_TRY(fb_copy(c, h, FB_LMATCHES12, FB_LLE, ni, hipMemcpyDeviceToHost));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OLF_OK;
 }
 
 int olf_stereo_frames_dev(olf_ctx* c, const uint8_t* d_images, int n_pairs, const olf_frame_buffers* o, void* stream)
@@ -1286,7 +630,7 @@ int olf_stereo_frames_dev(olf_ctx* c, const uint8_t* d_images, int n_pairs, cons
     OLF_TRY(check_device(c, "olf_stereo_frames_dev"));
     if (n_pairs < 0 || 2 * n_pairs > c->max_images) return OLF_ERR_CAPACITY;
     if (n_pairs == 0) return OLF_OK;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream, ls = c->stream2;
+    hipStream_t s = ctx_stream(c, stream), ls = c->stream2;
     const int n_images = 2 * n_pairs;
     const LineGeom& lg = c->line.geom;
     const LsdPlan plan = lsd_plan(lg, c->lb, c->lsd_force, c->limits, n_images);
@@ -1399,29 +743,7 @@ int olf_ctx_set_deferred_join(olf_ctx* c, int on)
 int olf_stereo_frames_join_dev(olf_ctx* c, void* stream)
 {
     if (!c) return OLF_ERR_INVALID;
-    return join_if_pending(c, stream ? (hipStream_t)stream : c->stream);
-}
-
-int olf_stereo_frames(olf_ctx* c, const uint8_t* images, int n_pairs, const olf_frame_buffers* o)
-{
-    if (!c || !images || !o) { set_error("olf_stereo_frames: null argument"); return OLF_ERR_INVALID; }
-    if (n_pairs < 0 || 2 * n_pairs > c->max_images) return OLF_ERR_CAPACITY;
-    if (n_pairs == 0) return OLF_OK;
-    const size_t ni = 2 * (size_t)n_pairs;
-    c->input_event = nullptr;           // (the upload below is on the context's stream: the line stream must fork from it, whatever event an earlier caller left)
-    OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, (size_t)c->W * c->H * ni, hipMemcpyHostToDevice, c->stream));
-    OLF_TRY(olf_stereo_frames_dev(c, c->d_images, n_pairs, &c->d_out, c->stream));
-    OLF_TRY(olf_stereo_frames_join_dev(c, c->stream));      // (a context with the deferred join on: the copies below read the line outputs)
-    if (c->d_outslab && (int)ni == c->max_images) {
-        // one copy for all eleven arrays, then host copies out of the pinned slab (the arrays are laid out for exactly this many images)
-        OLF_HIP_CHECK(hipMemcpyAsync(c->h_outslab, c->d_outslab, c->outslab_bytes, hipMemcpyDeviceToHost, c->stream));
-        OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-        for (int k = 0; k < FB_FIELDS; ++k) memcpy(fb_field(*o, k), c->h_outslab + c->outslab_off[k], fb_bytes(c, k, ni));
-        return check_status(c);
-    }
-    OLF_TRY(fb_copy(c, *o, 0, FB_FIELDS - 1, ni, hipMemcpyDeviceToHost));
-    OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return check_status(c);
+    return join_if_pending(c, ctx_stream(c, stream));
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@
 #include <fstream>
 #include <sstream>
 #include "../../include/orbline.h"
-#include "olf_internal.hpp"
+#include "staging.hpp"
 
 using namespace olf;
 
@@ -138,7 +138,7 @@ int olf_bow_words_dev(olf_ctx* c, const olf_voc* v, const uint8_t* d_desc, int n
     if (!c || !v || !d_desc || !d_word || !d_weight || !d_node || n < 0) { set_error("olf_bow_words_dev: bad argument"); return OLF_ERR_INVALID; }
     if (v->n_words == 0) { set_error("olf_bow_words_dev: empty vocabulary"); return OLF_ERR_INVALID; }
     return launch_bow_descend(v->d_slotDesc, v->d_childOff, v->d_slotNode, v->d_nodeWord, v->d_nodeWeight, d_desc, n, v->L - levelsup, d_word, d_weight,
-                              d_node, stream ? (hipStream_t)stream : ctx_stream(c));
+                              d_node, ctx_stream(c, stream));
 }
 
 int olf_bow_assemble(const olf_voc* v, const int32_t* word, const double* weight, const int32_t* node, int n, int32_t* bow_ids, double* bow_vals,
@@ -196,16 +196,13 @@ int olf_search_by_bow_batch_dev(olf_ctx* c, const olf_voc* v, int n_frames, int 
     if (n_frames < 2) return OLF_OK;
     const int cap = olf_orb_capacity(c);
     if (cap > 4096) { set_error("olf_search_by_bow_batch_dev: more than 4096 features per frame (the per-frame node sort runs in 32 KB of LDS)"); return OLF_ERR_CAPACITY; }
-    void* st = nullptr;
-    const size_t bn = (((size_t)n_frames * cap * 4) + 63) & ~(size_t)63, bs = (size_t)n_frames * cap * 8;
-    const int rc = ctx_scratch(c, 2, bn + bs + (size_t)n_frames * 4 + 64, &st);
-    if (rc != OLF_OK) return rc;
-    int* d_nodes = (int*)st;
-    unsigned long long* d_sorted = (unsigned long long*)((uint8_t*)st + bn);
-    int* d_m = (int*)((uint8_t*)st + bn + bs);
+    int *d_nodes, *d_m; unsigned long long* d_sorted;
+    Carve k;
+    k.add(&d_nodes, (size_t)n_frames * cap); k.add(&d_sorted, (size_t)n_frames * cap); k.add(&d_m, n_frames);
+    OLF_TRY(k.bind(c, SCRATCH_BATCH));
     return launch_search_by_bow_batch(v->d_slotDesc, v->d_childOff, v->d_slotNode, v->d_nodeWeight, v->L - levelsup, n_frames, img_stride, cap, d_kps, d_desc,
                                       d_counts, d_mp_valid, d_mp_bad, nnratio, check_orientation ? 1 : 0, d_nodes, d_sorted, d_m, d_matches, d_nmatches,
-                                      stream ? (hipStream_t)stream : ctx_stream(c));
+                                      ctx_stream(c, stream));
 }
 
 int olf_bow_transform(olf_ctx* c, const olf_voc* v, const uint8_t* desc, int n, int levelsup, int32_t* bow_ids, double* bow_vals, int* n_bow,
@@ -213,21 +210,16 @@ int olf_bow_transform(olf_ctx* c, const olf_voc* v, const uint8_t* desc, int n, 
 {
     if (!c || !v || !n_bow || !n_fv || !fv_offs || n < 0 || (n > 0 && !desc)) { set_error("olf_bow_transform: bad argument"); return OLF_ERR_INVALID; }
     if (v->n_words == 0 || n == 0) { *n_bow = 0; *n_fv = 0; fv_offs[0] = 0; return OLF_OK; }      // empty vocabulary -> empty vectors (:1137-1140)
-    void* st = nullptr;
-    const size_t bd = ((size_t)n * 32 + 15) & ~(size_t)15, bw = (size_t)n * 8;
-    int rc = ctx_scratch(c, 2, bd + bw + (size_t)n * 8 + 64, &st);
-    if (rc != OLF_OK) return rc;
-    uint8_t* d_desc = (uint8_t*)st; double* d_weight = (double*)(d_desc + bd); int* d_word = (int*)(d_weight + n); int* d_node = d_word + n;
-    hipStream_t s = ctx_stream(c);
-    OLF_HIP_CHECK(hipMemcpyAsync(d_desc, desc, (size_t)n * 32, hipMemcpyHostToDevice, s));
-    rc = olf_bow_words_dev(c, v, d_desc, n, levelsup, d_word, d_weight, d_node, s);
-    if (rc != OLF_OK) return rc;
+    HostCall h(c, "olf_bow_transform");
+    uint8_t* d_desc; double* d_weight; int *d_word, *d_node;
+    h.add(&d_desc, (size_t)n * 32); h.add(&d_weight, n); h.add(&d_word, n); h.add(&d_node, n);
+    OLF_TRY(h.bind(SCRATCH_BATCH));
+    OLF_TRY(h.up(d_desc, desc, (size_t)n * 32));
+    OLF_TRY(olf_bow_words_dev(c, v, d_desc, n, levelsup, d_word, d_weight, d_node, h.stream()));
     std::vector<int32_t> word(n), node(n);
     std::vector<double> weight(n);
-    OLF_HIP_CHECK(hipMemcpyAsync(word.data(), d_word, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipMemcpyAsync(node.data(), d_node, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipMemcpyAsync(weight.data(), d_weight, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    OLF_HIP_CHECK(hipStreamSynchronize(s));
+    OLF_TRY(h.down(word.data(), d_word, (size_t)n * 4)); OLF_TRY(h.down(node.data(), d_node, (size_t)n * 4)); OLF_TRY(h.down(weight.data(), d_weight, (size_t)n * 8));
+    OLF_TRY(h.finish());
     return olf_bow_assemble(v, word.data(), weight.data(), node.data(), n, bow_ids, bow_vals, n_bow, fv_nodes, fv_offs, fv_idx, n_fv);
 }
 

@@ -20,6 +20,7 @@
 #include "grid_walk.hpp"
 #include "device_math.hpp"
 #include "search_math.hpp"
+#include "staging.hpp"
 #include "../../include/orbline.h"
 
 namespace olf {
@@ -335,15 +336,14 @@ namespace {
 int local_args(olf_ctx* c, const char* who, const olf_track_batch* in, int n_frames, const olf_local_map* map, bool search, LocalArgs& A)
 {
     const std::string w(who);
-    if (!c || !in || !map || n_frames < 0 || map->n_mp < 0 || !in->Tcw || !(in->maxX > in->minX) || !(in->maxY > in->minY) ||
+    if (!c || !in || !map || n_frames < 0 || map->n_mp < 0 || !in->Tcw || !grid_scales(in->minX, in->maxX, in->minY, in->maxY, &A.wInv, &A.hInv) ||
         (map->n_mp && (!map->world || !map->normal || !map->maxd || !map->mind || !map->bad)) ||
         (map->list_offsets && (map->n_entries < 0 || (map->n_entries && !map->list_index))) ||
         (search && (!in->kps || !in->desc || !in->counts || in->img_stride < 1 || !in->uright || !in->cell_offsets || !in->cell_index ||
                     (map->n_mp && (!map->desc || !map->obs))))) {
         set_error(w + ": bad argument"); return OLF_ERR_INVALID;
     }
-    const int rcd = ctx_check_device(c, who);
-    if (rcd != OLF_OK) return rcd;
+    OLF_TRY(ctx_check_device(c, who));
     const int cap = olf_orb_capacity(c);
     if (cap > OLF_GRID_MAX_KEYS) { set_error(w + ": more than OLF_GRID_MAX_KEYS key points per frame (a kept candidate holds 13 index bits)"); return OLF_ERR_CAPACITY; }
     const long long ne = map->list_offsets ? (long long)map->n_entries : (long long)n_frames * map->n_mp;
@@ -351,18 +351,12 @@ int local_args(olf_ctx* c, const char* who, const olf_track_batch* in, int n_fra
     A.in = *in; A.map = *map;
     A.frame_mp = nullptr;
     A.n_frames = n_frames; A.n_entries = (int)ne; A.cap = cap;
-    A.nlevels = std::min(ctx_orb_levels(c), (int)OLF_MAX_LEVELS);
+    A.nlevels = ctx_level_scales(c, A.sf);
     A.mpW = (map->n_mp + 31) / 32; A.capW = (cap + 63) / 64;
     A.cosLimit = 0.f; A.th = 1.f; A.nnratio = 0.f; A.d_th = nullptr;
-    // mfGridElementWidthInv / mfGridElementHeightInv, src/Frame.cc:186-187
-    A.wInv = static_cast<float>(OLF_GRID_COLS) / (in->maxX - in->minX);
-    A.hInv = static_cast<float>(OLF_GRID_ROWS) / (in->maxY - in->minY);
-    for (int l = 0; l < OLF_MAX_LEVELS; ++l) { A.sf[l] = 1.f; A.thr[l] = 0.f; }
-    olf_orb_scale_tables(c, A.sf, nullptr, nullptr, nullptr, nullptr);
+    for (int l = 0; l < OLF_MAX_LEVELS; ++l) A.thr[l] = 0.f;
     return ctx_level_thresholds(c, A.thr);
 }
-
-size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 // the held / blocked bitmaps, then the frustum pass
 int launch_frustum(olf_ctx* c, const LocalArgs& A, unsigned* held, unsigned long long* blk0, uint8_t* in_view, int* level, float* view_cos, float* proj3, hipStream_t s)
@@ -385,16 +379,16 @@ int olf_is_in_frustum_batch_dev(olf_ctx* c, const olf_track_batch* in, int n_fra
                                 float viewing_cos_limit, uint8_t* d_in_view, int32_t* d_level, float* d_view_cos, float* d_proj3, void* stream)
 {
     LocalArgs A;
-    const int rc = local_args(c, "olf_is_in_frustum_batch_dev", in, n_frames, map, false, A);
-    if (rc != OLF_OK) return rc;
+    OLF_TRY(local_args(c, "olf_is_in_frustum_batch_dev", in, n_frames, map, false, A));
     if (d_frame_mp && in->counts && in->img_stride < 1) { set_error("olf_is_in_frustum_batch_dev: bad argument"); return OLF_ERR_INVALID; }
     if (n_frames == 0 || A.n_entries == 0) return OLF_OK;
     if (!d_in_view || !d_level || !d_view_cos || !d_proj3) { set_error("olf_is_in_frustum_batch_dev: bad argument"); return OLF_ERR_INVALID; }
     A.frame_mp = d_frame_mp; A.cosLimit = viewing_cos_limit;
-    void* st = nullptr;
-    const int rs = ctx_scratch(c, 2, (size_t)n_frames * A.mpW * 4 + 64, &st);
-    if (rs != OLF_OK) return rs;
-    return launch_frustum(c, A, (unsigned*)st, nullptr, d_in_view, d_level, d_view_cos, d_proj3, stream ? (hipStream_t)stream : ctx_stream(c));
+    unsigned* held;
+    Carve k;
+    k.add(&held, (size_t)n_frames * A.mpW);
+    OLF_TRY(k.bind(c, SCRATCH_BATCH));
+    return launch_frustum(c, A, held, nullptr, d_in_view, d_level, d_view_cos, d_proj3, ctx_stream(c, stream));
 }
 
 int olf_search_local_map_batch_dev(olf_ctx* c, const olf_track_batch* in, int n_frames, const olf_local_map* map, const int32_t* d_frame_mp,
@@ -402,28 +396,19 @@ int olf_search_local_map_batch_dev(olf_ctx* c, const olf_track_batch* in, int n_
                                    void* stream)
 {
     LocalArgs A;
-    const int rc = local_args(c, "olf_search_local_map_batch_dev", in, n_frames, map, true, A);
-    if (rc != OLF_OK) return rc;
+    OLF_TRY(local_args(c, "olf_search_local_map_batch_dev", in, n_frames, map, true, A));
     if (!d_matches || !d_nmatches) { set_error("olf_search_local_map_batch_dev: bad argument"); return OLF_ERR_INVALID; }
     if (n_frames == 0) return OLF_OK;
     A.frame_mp = d_frame_mp; A.cosLimit = viewing_cos_limit; A.th = th; A.d_th = d_th; A.nnratio = nnratio;
     // scratch, 37 bytes per entry: the kept candidates (16), mTrackProjX / Y / XR (12), mnTrackScaleLevel (4), mTrackViewCos (4), mbTrackInView (1); then the bitmaps
     const size_t ne = (size_t)A.n_entries;
-    const size_t bl = ne * 16, bp = up16(ne * 12), b4 = up16(ne * 4), bv = up16(ne), bh = up16((size_t)n_frames * A.mpW * 4), bb = (size_t)n_frames * A.capW * 8;
-    void* st = nullptr;
-    const int rs = ctx_scratch(c, 2, bl + bp + 2 * b4 + bv + bh + bb + 64, &st);
-    if (rs != OLF_OK) return rs;
-    uint8_t* p = (uint8_t*)st;
-    uint4* lists = (uint4*)p; p += bl;
-    float* proj3 = (float*)p; p += bp;
-    int* level = (int*)p; p += b4;
-    float* view_cos = (float*)p; p += b4;
-    uint8_t* in_view = p; p += bv;
-    unsigned* held = (unsigned*)p; p += bh;
-    unsigned long long* blk0 = (unsigned long long*)p;
-    hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
-    const int rf = launch_frustum(c, A, held, blk0, in_view, level, view_cos, proj3, s);
-    if (rf != OLF_OK) return rf;
+    uint4* lists; float *proj3, *view_cos; int* level; uint8_t* in_view; unsigned* held; unsigned long long* blk0;
+    Carve k;
+    k.add(&lists, ne); k.add(&proj3, 3 * ne); k.add(&level, ne); k.add(&view_cos, ne); k.add(&in_view, ne);
+    k.add(&held, (size_t)n_frames * A.mpW); k.add(&blk0, (size_t)n_frames * A.capW);
+    OLF_TRY(k.bind(c, SCRATCH_BATCH));
+    hipStream_t s = ctx_stream(c, stream);
+    OLF_TRY(launch_frustum(c, A, held, blk0, in_view, level, view_cos, proj3, s));
     if (A.n_entries) hipLaunchKernelGGL(k_local_lists, dim3((A.n_entries + 3) / 4), dim3(256), 0, s, A, in_view, level, view_cos, proj3, blk0, lists);
     const size_t lds = (size_t)A.cap * 4 + (size_t)A.capW * 8;
     hipLaunchKernelGGL(k_local_walk, dim3(n_frames), dim3(256), lds, s, A, lists, level, view_cos, proj3, blk0, d_matches, d_nmatches);

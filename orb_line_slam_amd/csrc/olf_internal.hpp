@@ -1,4 +1,5 @@
-// olf_internal.hpp -- internal layout of the device context behind the C ABI (include/orbline.h).
+// olf_internal.hpp -- what every translation unit of the library shares: the geometry and device buffers of the ORB side, the launchers, the ctx_*
+// accessors and the scratch slots.  The context itself (struct olf_ctx) is ctx.hpp, seen by api.cpp, api_host.cpp and api_debug.cpp only.
 //
 // One olf_ctx serves a fixed image size (w x h), a fixed parameter block and up to max_images
 // images per call (a stereo pair = 2 images: index 2*pair + side).  All buffers are allocated once
@@ -28,18 +29,40 @@
         }                                                                                   \
     } while (0)
 
+#define OLF_TRY(expr)                  \
+    do {                               \
+        int _rc = (expr);              \
+        if (_rc != OLF_OK) return _rc; \
+    } while (0)
+
 struct olf_ctx;
 
 namespace olf {
 
 void set_error(const std::string& s);
 
-// what the entry points outside api.cpp need of a context (api.cpp)
-hipStream_t ctx_stream(olf_ctx* c);
-int ctx_scratch(olf_ctx* c, int slot, size_t bytes, void** out);
+// The context's four grow-on-demand scratch slabs.  An entry carves its slot (staging.hpp) and the slab is in use until the last kernel or copy the
+// entry enqueued has run, so two entries may share a slot only when their work is ordered: on one stream, or with a synchronise between them.
+//   SCRATCH_KNN    olf_match_bf_dev: the k-NN tables of launch_match_bf.
+//   SCRATCH_STAGE  the descriptor-sized host-pointer entries (api_host.cpp: olf_match_bf, olf_knn2, olf_match_candidates, olf_frame_grid,
+//                  olf_features_in_area, olf_hamming_matrix, olf_distinctive_descriptors) and the olf_debug_*_sweep counters.  Every one of them ends in
+//                  a synchronise on the context's stream.
+//   SCRATCH_BATCH  the batched matchers (olf_search_by_bow_batch_dev, olf_search_by_projection_batch_dev, olf_is_in_frustum_batch_dev,
+//                  olf_search_local_map_batch_dev) and the image-sized host-pointer entries (olf_cvt_gray, olf_remap_linear,
+//                  olf_init_undistort_rectify_map, olf_bow_transform).  The matchers do not synchronise: the caller keeps them on one stream.
+//   SCRATCH_PACK   olf_frames_pack_dev: the record's row offsets.
+// Live at the same time: STAGE over KNN inside olf_match_bf (it stages, then calls olf_match_bf_dev); KNN, BATCH and PACK in a pipeline step that
+// enqueues SearchByBoW, the line match and the packer behind one frame call without a synchronise (bench.py).  A slot number is a
+// context's memory: moving an entry to another slot changes what a context allocates.
+enum ScratchSlot { SCRATCH_KNN, SCRATCH_STAGE, SCRATCH_BATCH, SCRATCH_PACK, SCRATCH_SLOTS };
+
+// what the entry points outside api*.cpp need of a context (api.cpp; the context itself is ctx.hpp, which no .hip file includes)
+hipStream_t ctx_stream(olf_ctx* c, void* stream = nullptr);      // the caller's stream, or the context's own when the caller passes none
+int ctx_scratch(olf_ctx* c, ScratchSlot slot, size_t bytes, void** out);
 int* ctx_status(olf_ctx* c);
 int ctx_check_device(const olf_ctx* c, const char* who);
-int ctx_orb_levels(const olf_ctx* c);
+int ctx_check_status(olf_ctx* c);                      // reads the device's capacity flags: OLF_OK, or OLF_ERR_CAPACITY with the flags cleared and named
+int ctx_level_scales(const olf_ctx* c, float* sf);     // mvScaleFactors into sf[0 .. OLF_MAX_LEVELS), 1.0 above the context's levels; returns the level count
 int ctx_level_thresholds(olf_ctx* c, float* thr);      // the table of olf_predict_scale_thresholds for the context's levels, built once
 
 #ifdef __HIPCC__
@@ -116,7 +139,7 @@ struct OrbGeom {
 
 // Host-side derivation of every table of ORBextractor::ORBextractor (src/ORBextractor.cc:412-472),
 // of the level sizes (:1113-1114), of the cell grid (:775-789) and of the cv::resize
-// coefficient tables.  Pure host code, shared by api.cpp.
+// coefficient tables.  Pure host code (host_tables.cpp), held by the context.
 struct OrbHostTables {
     std::vector<float> sf, inv_sf, sigma2, inv_sigma2;
     std::vector<int> nPerLevel;
@@ -190,6 +213,14 @@ int launch_hamming_matrix(const uint8_t* a, int nA, const uint8_t* b, int nB, ui
 
 
 // grid.hip
+// mfGridElementWidthInv / mfGridElementHeightInv, src/Frame.cc:186-187: static_cast<float>(FRAME_GRID_COLS) / (mnMaxX - mnMinX), in float; false for empty bounds
+inline bool grid_scales(float minX, float maxX, float minY, float maxY, float* wInv, float* hInv)
+{
+    if (!(maxX > minX) || !(maxY > minY)) return false;
+    *wInv = static_cast<float>(OLF_GRID_COLS) / (maxX - minX);
+    *hInv = static_cast<float>(OLF_GRID_ROWS) / (maxY - minY);
+    return true;
+}
 int launch_assign_grid(const olf_keypoint* d_kps, size_t frame_stride, const int* d_counts, int count_stride, int n_fixed, int n_limit, float minX,
                        float minY, float wInv, float hInv, int n_frames, int* d_cell_offsets, int* d_cell_index, size_t index_stride, hipStream_t s);
 int launch_features_in_area(const olf_keypoint* d_keys, const int* d_cell_offsets, const int* d_cell_index, float minX, float minY, float wInv, float hInv,

@@ -20,8 +20,6 @@
 #include "predict_scale.hpp"
 #include "search_math.hpp"
 
-#define OLF_TRY(expr) do { const int _rc = (expr); if (_rc != OLF_OK) return _rc; } while (0)
-
 namespace {
 using namespace olf;
 constexpr int TH_HIGH = 100, TH_LOW = 50;                             // src/ORBmatcher.cc:39-40 (HISTO_LENGTH: search_math.hpp)

@@ -18,6 +18,7 @@
 #include "grid_walk.hpp"
 #include "device_math.hpp"
 #include "search_math.hpp"
+#include "staging.hpp"
 #include "../../include/orbline.h"
 
 namespace olf {
@@ -302,34 +303,26 @@ extern "C" {
 int olf_search_by_projection_batch_dev(olf_ctx* c, const olf_track_batch* in, int n_frames, float th, const float* d_th, int bMono, int check_orientation,
                                        int32_t* d_matches, int32_t* d_match12, int32_t* d_nmatches, void* stream)
 {
+    TrackArgs A;
     if (!c || !in || n_frames < 0 || !d_matches || !d_nmatches || !in->kps || !in->desc || !in->counts || in->img_stride < 1 || !in->uright ||
-        !in->cell_offsets || !in->cell_index || !in->Tcw || !in->mp_world || !(in->maxX > in->minX) || !(in->maxY > in->minY)) {
+        !in->cell_offsets || !in->cell_index || !in->Tcw || !in->mp_world || !grid_scales(in->minX, in->maxX, in->minY, in->maxY, &A.wInv, &A.hInv)) {
         set_error("olf_search_by_projection_batch_dev: bad argument"); return OLF_ERR_INVALID;
     }
-    const int rcd = ctx_check_device(c, "olf_search_by_projection_batch_dev");
-    if (rcd != OLF_OK) return rcd;
+    OLF_TRY(ctx_check_device(c, "olf_search_by_projection_batch_dev"));
     const int cap = olf_orb_capacity(c);
     if (cap > OLF_GRID_MAX_KEYS) {
         set_error("olf_search_by_projection_batch_dev: more than OLF_GRID_MAX_KEYS key points per frame (a list entry holds 13 index bits)"); return OLF_ERR_CAPACITY;
     }
     if (n_frames < 2) return OLF_OK;
     const int n_pairs = n_frames - 1;
-    TrackArgs A;
     A.in = *in;
     A.cap = cap; A.bMono = bMono ? 1 : 0; A.th = th; A.d_th = d_th;
-    // mfGridElementWidthInv / mfGridElementHeightInv, src/Frame.cc:186-187
-    A.wInv = static_cast<float>(OLF_GRID_COLS) / (in->maxX - in->minX);
-    A.hInv = static_cast<float>(OLF_GRID_ROWS) / (in->maxY - in->minY);
-    for (int l = 0; l < OLF_MAX_LEVELS; ++l) A.sf[l] = 1.f;
-    A.nlevels = std::min(ctx_orb_levels(c), (int)OLF_MAX_LEVELS);
-    olf_orb_scale_tables(c, A.sf, nullptr, nullptr, nullptr, nullptr);
-    void* st = nullptr;
-    const size_t bl = (size_t)n_pairs * cap * sizeof(uint4);
-    const int rc = ctx_scratch(c, 2, bl + (size_t)n_pairs * 4 + 64, &st);
-    if (rc != OLF_OK) return rc;
-    uint4* lists = (uint4*)st;
-    int* pairBad = (int*)((uint8_t*)st + bl);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx_stream(c);
+    A.nlevels = ctx_level_scales(c, A.sf);
+    uint4* lists; int* pairBad;
+    Carve k;
+    k.add(&lists, (size_t)n_pairs * cap); k.add(&pairBad, n_pairs);
+    OLF_TRY(k.bind(c, SCRATCH_BATCH));
+    hipStream_t s = ctx_stream(c, stream);
     OLF_HIP_CHECK(hipMemsetAsync(pairBad, 0, (size_t)n_pairs * 4, s));
     hipLaunchKernelGGL(k_track_lists, dim3((cap + 3) / 4, n_pairs), dim3(256), 0, s, A, lists, pairBad, ctx_status(c));
     const size_t lds = (size_t)cap * 4 + (((size_t)cap * 2 + 3) & ~(size_t)3);
@@ -344,12 +337,11 @@ int olf_unproject_stereo_dev(olf_ctx* c, int n_frames, int img_stride, const olf
     if (!c || n_frames < 0 || img_stride < 1 || !d_kps || !d_counts || !d_depth || !d_Twc || !d_world) {
         set_error("olf_unproject_stereo_dev: bad argument"); return OLF_ERR_INVALID;
     }
-    const int rcd = ctx_check_device(c, "olf_unproject_stereo_dev");
-    if (rcd != OLF_OK) return rcd;
+    OLF_TRY(ctx_check_device(c, "olf_unproject_stereo_dev"));
     if (n_frames == 0) return OLF_OK;
     const int cap = olf_orb_capacity(c);
     const float invfx = 1.0f / fx, invfy = 1.0f / fy;             // src/Frame.cc:188-189
-    hipLaunchKernelGGL(k_unproject_stereo, dim3((cap + 255) / 256, n_frames), dim3(256), 0, stream ? (hipStream_t)stream : ctx_stream(c), d_kps, d_counts,
+    hipLaunchKernelGGL(k_unproject_stereo, dim3((cap + 255) / 256, n_frames), dim3(256), 0, ctx_stream(c, stream), d_kps, d_counts,
                        d_depth, cap, img_stride, cx, cy, invfx, invfy, d_Twc, d_world);
     OLF_HIP_CHECK(hipGetLastError());
     return OLF_OK;

@@ -112,6 +112,18 @@ def test_device_fast_atan2_equals_oracle(hostmath, oracle):
         assert a.view(np.uint32) == b.view(np.uint32), (y, x, a, b)
 
 
+def test_scratch_carve_layout(tmp_path):
+    """csrc/carve.hpp, the arithmetic under every scratch slab the entry points cut (staging.hpp): tests/staging_layout.cpp lays out some hundred and
+    fifty request lists -- counts of 0, 1 and odd counts of 1- to 28-byte elements, the shapes the entries cut, one list of more than 4 GB -- and checks
+    alignment, order, disjointness, distinct addresses of empty regions and that the total covers the last region.  Its own process, under
+    AddressSanitizer and UBSan: the regions of every list that fits are written at both ends inside a block of exactly the total."""
+    exe = str(tmp_path / "staging_layout")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
+                    os.path.join(ROOT, "tests", "staging_layout.cpp")], check=True)
+    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    assert out.returncode == 0 and b"STAGING_LAYOUT_OK" in out.stdout, out.stdout.decode()[-3000:]
+
+
 def test_synth_is_deterministic_and_has_disparity():
     from orb_line_slam_amd import synth
     l1, r1 = synth.stereo_pair(7, 640, 480)
