@@ -567,6 +567,84 @@ int olf_search_local_map_batch_dev(olf_ctx* ctx, const olf_track_batch* in, int 
                                    float viewing_cos_limit, float th, const float* d_th, float nnratio, int32_t* d_matches, int32_t* d_nmatches,
                                    void* stream);
 
+/* ---- the line half of tracking: Frame::isInFrustum_l, SearchLocalPointsAndLines' line half, the f2f line tracking (csrc/line_batch.hip) --------------------
+ * Host forms first (host arithmetic, no device work, no context): they are the definition the device entries below equal, bit for bit.
+ *
+ * bool Frame::isInFrustum_l(MapLine *pML, float viewingCosLimit), src/Frame.cc:446-515, for n_ml map lines.  world6 [n_ml][6]: GetWorldPos(), start point
+ * then end point, as float (Converter::toCvMat).  Per end point, the start point first: mRcw * p + mtcw (C.12), PcZ < 0 fails, invz = 1.0f / PcZ,
+ * u = fx * PcX * invz + cx, the CLOSED image bounds -- the first half of olf_is_in_frustum.  f supplies mTcw, the calibration and the bounds.  Outputs per
+ * line: in_view (mbTrackInView) and proj4 = (mTrackProjsX, mTrackProjsY, mTrackProjeX, mTrackProjeY); a line that fails only gets in_view = 0.
+ * mnTrackangle (:512) is read by commented-out code only (src/Tracking.cc:1991-1997) and is not produced. */
+int olf_is_in_frustum_l(const olf_frame_view* f, int n_ml, const float* world6, uint8_t* in_view, float* proj4);
+/* The loop of Tracking::SearchLocalPointsAndLines over matches_12 (src/Tracking.cc:1974-2016) and n_inliers_ls (:2021-2023) for one frame.  The first four
+ * arrays run over mvpLocalMapLines_InFrustum (n_in_view lines, the reference's i1): m12 (in / out: matches_12 of match(), :1970; the loop sets entries
+ * to -1, :2010), map_index (the line's index into the map of n_ml lines), proj4 (of olf_is_in_frustum_l).  kls = mvKeysUn_Line, ldisp [n_lines][2] =
+ * mvDisparity_l, frame_ml [n_lines] (in / out) = mvpMapLines as map indices, negative = NULL, on entry without its bad lines (:1897-1913); obs [n_ml] =
+ * Observations() > 0.  deltaWidth = (double)(maxX - minX) * 0.1 with the subtraction in float; the coordinate differences are formed in float, widened
+ * and compared with a strict '>'.  *n_inliers = n_inliers_ls.  An index outside its array is OLF_ERR_INVALID. */
+int olf_local_lines_assign(int n_in_view, int32_t* m12, const int32_t* map_index, const float* proj4, const olf_keyline* kls, int n_lines, const float* ldisp,
+                           float minX, float maxX, float minY, float maxY, int n_ml, const uint8_t* obs, int32_t* frame_ml, int32_t* n_inliers);
+/* The f2f line tracking behind match(desc_last, desc_cur, nnr, matches_12) for one pair: Tracking::TrackWithMotionModelWithLine, src/Tracking.cc:1305-1349
+ * (skip_null = 1: a last line that holds nothing is passed over, :1316; gates = 1, delta_angle = M_PI / 8.0, pos_frac = 0.1) and
+ * TrackReferenceKeyFrameWithLine, :976-1020 (skip_null = 0: it is assigned as NULL and counted, :1018-1019; gates = 0: `if(false)`, :993).  m12 [n_last]
+ * (in / out; the gates set entries to -1), last_ml [n_last]: the last frame's (key frame's) mvpMapLines as ids, negative = NULL; cur_ml [n_cur] (out):
+ * filled with -1 (:1306, :977), then the ids assigned -- i1 runs upwards, the last assignment stays; *n_inliers counts assignments (:1348).  The angle
+ * gate: the float difference of the angles, widened, +- 2 * M_PI in double, fabs(theta) > delta_angle; the position gate as above with pos_frac. */
+int olf_track_lines_assign(int n_last, int32_t* m12, const olf_keyline* kls_last, const int32_t* last_ml, int n_cur, const olf_keyline* kls_cur,
+                           const float* ldisp_cur, float minX, float maxX, float minY, float maxY, int skip_null, int gates, double delta_angle, double pos_frac,
+                           int32_t* cur_ml, int32_t* n_inliers);
+
+/* The frames of a batch in the role the line searches read them in.  Device pointers; frame j = image j * img_stride of the extractor-layout arrays
+ * (img_stride 2 = the left images of a stereo batch); the per-frame planes are [n_frames][olf_line_capacity()].  ldesc 16-byte aligned. */
+typedef struct olf_line_batch {
+    const olf_keyline* kls; const uint8_t* ldesc; const int32_t* lcounts; int32_t img_stride;   /* mvKeysUn_Line (the caller's responsibility, as kps is), mDescriptors_Line, N_l */
+    const float*   ldisp;             /* [n_frames][capacity][2] mvDisparity_l            (olf_frame_buffers.ldisp)                  */
+    const float*   Tcw;               /* [n_frames][16] mTcw, row-major                                                              */
+    float fx, fy, cx, cy, minX, maxX, minY, maxY;
+} olf_line_batch;
+/* The map lines the frames of a batch are matched against, as arrays of n_ml lines (device pointers), and optionally each frame's mvpLocalMapLines as a
+ * list of indices into them: list_offsets / list_index / n_entries have the semantics of olf_local_map, and a NULL list_offsets means every frame sees
+ * all lines in index order.  A line a frame holds must be one of the n_ml lines; it need not be in the frame's list. */
+typedef struct olf_local_line_map {
+    const float*   world;         /* [n_ml][6] GetWorldPos(): start, then end                                                      */
+    const uint8_t* desc;          /* [n_ml][32] GetDescriptor(), 16-byte aligned                                                   */
+    const uint8_t* obs;           /* [n_ml] Observations() > 0                                                                     */
+    const uint8_t* bad;           /* [n_ml] isBad()                                                                                */
+    int32_t        n_ml;
+    const int32_t* list_offsets;  /* [n_frames + 1], non-decreasing from >= 0, or NULL                                             */
+    const int32_t* list_index;    /* [n_entries]                                                                                   */
+    int32_t        n_entries;
+} olf_local_line_map;
+/* Frame::isInFrustum_l (src/Frame.cc:446-515) for every entry of every frame, with the two skips Tracking::SearchLocalPointsAndLines makes first
+ * (src/Tracking.cc:1953-1956): the line is held by the frame (mnLastFrameSeen == mCurrentFrame.mnId) or is bad.  Arithmetic: that of olf_is_in_frustum_l.
+ * `in`: Tcw, the calibration and the bounds are read -- and lcounts (with img_stride) when d_frame_ml is given and lcounts is not NULL.
+ * d_frame_ml [n_frames][capacity] (or NULL: the frames hold nothing): mvpMapLines on entry as indices into the map, negative = none.  A held line that is
+ * bad is dropped first (:1902-1905).  Outputs per entry: d_in_view (uint8) and d_proj4 (4 floats, 16-byte aligned); an entry that is skipped or fails only
+ * gets in view = 0.  MapLine::IncreaseVisible (:1908, :1961) is the caller's.  A list index outside [0, n_ml) is left out (in view = 0) and a d_frame_ml
+ * value >= n_ml counts as "holds nothing"; either sets bit 1024 of the context's status word (olf_ctx_synchronize / olf_ctx_poll_status).  Accesses are never
+ * out of bounds.  Uses the batch scratch slot (one bit per (frame, map line) when d_frame_ml is given, nothing otherwise) and does not synchronise, as the point entries.  Contexts whose olf_line_capacity() exceeds 4096:
+ * OLF_ERR_CAPACITY; maxX <= minX, maxY <= minY or a NULL required pointer: OLF_ERR_INVALID; n_frames == 0 writes nothing. */
+int olf_is_in_frustum_l_batch_dev(olf_ctx* ctx, const olf_line_batch* in, int n_frames, const olf_local_line_map* map, const int32_t* d_frame_ml,
+                                  uint8_t* d_in_view, float* d_proj4, void* stream);
+/* The line half of Tracking::SearchLocalPointsAndLines (src/Tracking.cc:1897-1913, :1945-2023) for every frame: the pass above; the in-view lines of a frame
+ * in list order are mvpLocalMapLines_InFrustum (:1963); match(mvpLocalMapLines_InFrustum, mCurrentFrame, nnr, matches_12) (:1970), which is matchNNR only
+ * (src/LineMatcher.cpp:64-73): kNN(2) of the in-view map line descriptors against the frame's own, the ratio test d0 < d1 * nnr, a frame with fewer than
+ * two lines matches nothing; the loop :1976-2016; n_inliers_ls (:2021-2023).  nnr = Config::minRatio12L().  Outputs per entry: d_in_view, d_proj4 as
+ * above, d_m12: the value matches_12 holds at the end for the entry's place in mvpLocalMapLines_InFrustum, -1 for entries not in view.  Per frame:
+ * d_frame_ml_out [n_frames][capacity]: mvpMapLines at the end as map indices (lines held on entry stay, bad ones are gone; -1 from N_l on; may be
+ * d_frame_ml itself); d_ninliers [n_frames].  Results equal a loop of olf_is_in_frustum_l, olf_match_bf and olf_local_lines_assign over the frames and do
+ * not depend on scheduling.  Errors and malformed indices as above.  Scratch: 17 bytes per entry, 8 per (frame, line), one bit per (frame, map line) when d_frame_ml is given. */
+int olf_search_local_lines_batch_dev(olf_ctx* ctx, const olf_line_batch* in, int n_frames, const olf_local_line_map* map, const int32_t* d_frame_ml, float nnr,
+                                     uint8_t* d_in_view, float* d_proj4, int32_t* d_m12, int32_t* d_frame_ml_out, int32_t* d_ninliers, void* stream);
+/* The f2f line tracking of Tracking::TrackWithMotionModelWithLine (src/Tracking.cc:1305-1349) / TrackReferenceKeyFrameWithLine (:976-1020) for the
+ * n_frames - 1 pairs of consecutive frames of a batch: pair j has last = frame j and current = frame j + 1.  match(desc_last, desc_cur, nnr, matches_12)
+ * with best_lr = Config::bestLRMatches() (the kNN of olf_match_bf_dev), then olf_track_lines_assign's loop with the same flags and parameters.
+ * d_last_ml [n_frames - 1][capacity]: mvpMapLines of pair j's last frame as ids, negative = NULL.  d_enable (or NULL) [n_frames - 1]: 0 leaves the pair's
+ * three output rows untouched.  Outputs per pair: d_m12 [capacity] (-1 from the last frame's N_l on), d_cur_ml [capacity] (the ids copied from
+ * d_last_ml, -1 = NULL), d_ninliers.  n_frames < 2: nothing is written.  Errors as above. */
+int olf_track_lines_batch_dev(olf_ctx* ctx, const olf_line_batch* in, int n_frames, const int32_t* d_last_ml, float nnr, int best_lr, int skip_null, int gates,
+                              double delta_angle, double pos_frac, const int32_t* d_enable, int32_t* d_m12, int32_t* d_cur_ml, int32_t* d_ninliers, void* stream);
+
 /* measurement: rate of a plain 16-byte-per-thread device copy kernel over `bytes` (read + written bytes per second): the practical HBM
  * ceiling bench.py reports next to the specification's 8 TB/s */
 int olf_debug_copy_bandwidth(olf_ctx* ctx, size_t bytes, int reps, double* gbytes_per_s);

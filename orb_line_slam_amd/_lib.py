@@ -79,6 +79,18 @@ class LocalMapC(C.Structure):
                 [(n, C.c_void_p) for n in ("list_offsets", "list_index")] + [("n_entries", C.c_int32)])
 
 
+class LineBatchC(C.Structure):
+    """olf_line_batch (include/orbline.h): device pointers of a batch of frames as the line searches read them"""
+    _fields_ = ([(n, C.c_void_p) for n in ("kls", "ldesc", "lcounts")] + [("img_stride", C.c_int32)] + [(n, C.c_void_p) for n in ("ldisp", "Tcw")] +
+                [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "minX", "maxX", "minY", "maxY")])
+
+
+class LocalLineMapC(C.Structure):
+    """olf_local_line_map (include/orbline.h): the map lines of a batch as device arrays, and optionally each frame's list of indices into them"""
+    _fields_ = ([(n, C.c_void_p) for n in ("world", "desc", "obs", "bad")] + [("n_ml", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("list_offsets", "list_index")] + [("n_entries", C.c_int32)])
+
+
 # Frame::mGrid as two int32 arrays (include/orbline_types.h) and one Frame::GetFeaturesInArea call
 GRID_COLS, GRID_ROWS, GRID_CELLS, GRID_MAX_KEYS = 64, 48, 3072, 8192
 AREA_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("r", "<f4"), ("min_level", "<i4"), ("max_level", "<i4")])
@@ -194,6 +206,15 @@ def lib():
         L.olf_is_in_frustum_batch_dev.argtypes = [C.c_void_p, C.POINTER(TrackBatchC), C.c_int, C.POINTER(LocalMapC), C.c_void_p, C.c_float] + [C.c_void_p] * 5
         L.olf_search_local_map_batch_dev.argtypes = [C.c_void_p, C.POINTER(TrackBatchC), C.c_int, C.POINTER(LocalMapC), C.c_void_p, C.c_float, C.c_float,
                                                      C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.olf_is_in_frustum_l.argtypes = [V, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.olf_local_lines_assign.argtypes = ([C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_float] * 4 +
+                                             [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+        L.olf_track_lines_assign.argtypes = ([C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_float] * 4 +
+                                             [C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p])
+        L.olf_is_in_frustum_l_batch_dev.argtypes = [C.c_void_p, C.POINTER(LineBatchC), C.c_int, C.POINTER(LocalLineMapC)] + [C.c_void_p] * 4
+        L.olf_search_local_lines_batch_dev.argtypes = [C.c_void_p, C.POINTER(LineBatchC), C.c_int, C.POINTER(LocalLineMapC), C.c_void_p, C.c_float] + [C.c_void_p] * 6
+        L.olf_track_lines_batch_dev.argtypes = ([C.c_void_p, C.POINTER(LineBatchC), C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double] +
+                                                [C.c_void_p] * 5)
         L.olf_debug_copy_bandwidth.argtypes =[C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
         L.olf_debug_fdiv_sweep.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         L.olf_debug_sqrtq_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]

@@ -37,7 +37,7 @@ int check_status(olf_ctx* c)
     if (st[0]) {
         (void)hipMemset(c->ob.status, 0, 16);
         set_error("device capacity overflow, flags=" + std::to_string(st[0]) +
-                  " (1/2/4: ORB corner / candidate / key point buffers, 8: LSD regions, segments or pixel-list pool, 16: LSD growth watchdog, 32: frame record buffer, 64: LSD seed sort, final-range list of the grid-wide top levels, 128: candidate list of olf_features_in_area_dev, 256: olf_search_by_projection_batch_dev skipped a pair whose last frame holds an octave outside the context's levels, 512: olf_is_in_frustum_batch_dev / olf_search_local_map_batch_dev met a list index or a d_frame_mp value outside the map)");
+                  " (1/2/4: ORB corner / candidate / key point buffers, 8: LSD regions, segments or pixel-list pool, 16: LSD growth watchdog, 32: frame record buffer, 64: LSD seed sort, final-range list of the grid-wide top levels, 128: candidate list of olf_features_in_area_dev, 256: olf_search_by_projection_batch_dev skipped a pair whose last frame holds an octave outside the context's levels, 512: olf_is_in_frustum_batch_dev / olf_search_local_map_batch_dev met a list index or a d_frame_mp value outside the map, 1024: olf_is_in_frustum_l_batch_dev / olf_search_local_lines_batch_dev met a list index or a d_frame_ml value outside the map)");
         return OLF_ERR_CAPACITY;
     }
     return OLF_OK;
@@ -121,6 +121,11 @@ int launch_depth_mask(const float* depth, uint8_t* mask, size_t n, hipStream_t s
 }
 
 namespace olf {
+int ctx_join_line_outputs(olf_ctx* c, hipStream_t s, const void* p0, const void* p1, const void* p2, const void* p3)
+{
+    if (in_pending_line_outputs(c, p0) || in_pending_line_outputs(c, p1) || in_pending_line_outputs(c, p2) || in_pending_line_outputs(c, p3)) return join_if_pending(c, s);
+    return OLF_OK;
+}
 hipStream_t ctx_stream(olf_ctx* c, void* stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
 int ctx_scratch(olf_ctx* c, ScratchSlot slot, size_t bytes, void** out) { return scratch_get(c, slot, bytes, out); }
 int* ctx_status(olf_ctx* c) { return c->ob.status; }

@@ -317,9 +317,21 @@ __device__ __forceinline__ uint32_t spread4(uint32_t nib) { return (nib * 0x0020
 // -2 * 4096 and an accumulator that starts at ((|a| + |b|) << 12) + train index ends as the finished (distance << 12 | index) key --
 // no instruction builds it.  SHIFT = 16 (up to 65535 rows): bytes {0, 1} / {0, -2}, the accumulator is the distance and the key is one
 // shift-add.
-template <int SHIFT>
+//
+// Where a workgroup's queries come from and where their results go is a template parameter: tile() = the 256-query tile of this workgroup, row(iq) = the
+// descriptor of query iq of the set, out(iq) = its place in idx0 / dist0 / dist1.  KnnRows is the dense form (set s = rows [s * strideQ, +nq)), KnnIndexed
+// fetches through an index (olf_search_local_lines_batch_dev: the in-view map lines of a frame are never gathered into a matrix).
+struct KnnRows {
+    const uint8_t* q;
+    int set, strideQ;
+    __device__ __forceinline__ int tile() const { return blockIdx.x; }
+    __device__ __forceinline__ const uint4* row(int iq) const { return reinterpret_cast<const uint4*>(q + ((size_t)set * strideQ + iq) * OLF_DESC_BYTES); }
+    __device__ __forceinline__ size_t out(int iq) const { return (size_t)set * strideQ + iq; }
+};
+
+template <int SHIFT, class Queries>
 __device__ __forceinline__ void knn2_body(uint8_t (*s_a)[KM_ROWS * KM_STRIDE], int (*s_pa)[KM_ROWS], const int set, const int nq, const int nt,
-                                          const uint8_t* __restrict__ q, int strideQ, const uint8_t* __restrict__ t, int strideT,
+                                          const Queries Q, const uint8_t* __restrict__ t, int strideT,
                                           int* __restrict__ idx0, int* __restrict__ dist0, int* __restrict__ dist1)
 {
     constexpr bool FUSED = SHIFT == 12;
@@ -331,10 +343,10 @@ __device__ __forceinline__ void knn2_body(uint8_t (*s_a)[KM_ROWS * KM_STRIDE], i
     int pb[2];
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
-        const int iq = blockIdx.x * 256 + wv * 64 + cb * 32 + col;
+        const int iq = Q.tile() * 256 + wv * 64 + cb * 32 + col;
         uint4 d0 = make_uint4(0, 0, 0, 0), d1 = d0;
         if (iq < nq) {
-            const uint4* qp = reinterpret_cast<const uint4*>(q + ((size_t)set * strideQ + iq) * OLF_DESC_BYTES);
+            const uint4* qp = Q.row(iq);
             d0 = qp[0]; d1 = qp[1];
         }
         const uint32_t d[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
@@ -412,9 +424,9 @@ __device__ __forceinline__ void knn2_body(uint8_t (*s_a)[KM_ROWS * KM_STRIDE], i
         unsigned m0 = min(k0[cb], o0), m1 = min(max(k0[cb], o0), min(k1[cb], o1));
         if (m0 >= ((unsigned)KM_PAD_DIST << SHIFT)) m0 = 0xffffffffu;          // padding rows are not candidates
         if (m1 >= ((unsigned)KM_PAD_DIST << SHIFT)) m1 = 0xffffffffu;
-        const int iq = blockIdx.x * 256 + wv * 64 + cb * 32 + col;
+        const int iq = Q.tile() * 256 + wv * 64 + cb * 32 + col;
         if (g == 0 && iq < nq) {
-            const size_t o = (size_t)set * strideQ + iq;
+            const size_t o = Q.out(iq);
             idx0[o] = m0 == 0xffffffffu ? -1 : (int)(m0 & ((1u << SHIFT) - 1u));
             dist0[o] = m0 == 0xffffffffu ? 0x7fffffff : (int)(m0 >> SHIFT);
             dist1[o] = m1 == 0xffffffffu ? 0x7fffffff : (int)(m1 >> SHIFT);
@@ -431,8 +443,46 @@ __global__ __launch_bounds__(256) void k_knn2(const uint8_t* __restrict__ q, con
     const int set = blockIdx.y;
     const int nq = nQ[set * qSetStep], nt = nT[set * tSetStep];
     if (blockIdx.x * 256 >= nq) return;                      // whole block beyond the query set
-    if (nt <= 4096) knn2_body<12>(s_a, s_pa, set, nq, nt, q, strideQ, t, strideT, idx0, dist0, dist1);
-    else knn2_body<16>(s_a, s_pa, set, nq, nt, q, strideQ, t, strideT, idx0, dist0, dist1);
+    const KnnRows Q = {q, set, strideQ};
+    if (nt <= 4096) knn2_body<12>(s_a, s_pa, set, nq, nt, Q, t, strideT, idx0, dist0, dist1);
+    else knn2_body<16>(s_a, s_pa, set, nq, nt, Q, t, strideT, idx0, dist0, dist1);
+}
+
+// The queries of set s are rows of one shared matrix picked through an index: query r of the set is entry ent = rank_entry[qbase[s] + r], its descriptor
+// row qidx[ent] of q (qidx == NULL: row ent - qbase[s]), and its results go to place qbase[s] + r.  The number of queries of a set is known on the device
+// only, so the grid is an upper bound of 256-query tiles and a workgroup finds its (set, tile) in tile_prefix [n_sets + 1], the running sum of
+// ceil(nq[s] / 256), or leaves.  Train sets of up to 4096 rows (the fused key).
+struct KnnIndexed {
+    const uint8_t* q;
+    const int *rank_entry, *qidx;
+    int base, tile_;
+    __device__ __forceinline__ int tile() const { return tile_; }
+    __device__ __forceinline__ const uint4* row(int iq) const
+    {
+        const int ent = rank_entry[base + iq];
+        return reinterpret_cast<const uint4*>(q + (size_t)(qidx ? qidx[ent] : ent - base) * OLF_DESC_BYTES);
+    }
+    __device__ __forceinline__ size_t out(int iq) const { return (size_t)(base + iq); }
+};
+
+__global__ __launch_bounds__(256) void k_knn2_indexed(const uint8_t* __restrict__ q, const int* __restrict__ rank_entry, const int* __restrict__ qidx,
+                                                      const int* __restrict__ qbase, const int* __restrict__ nQ, const int* __restrict__ tile_prefix, int n_sets,
+                                                      const uint8_t* __restrict__ t, const int* __restrict__ nT, int strideT, int tSetStep, int tCap,
+                                                      int* __restrict__ idx0, int* __restrict__ dist0, int* __restrict__ dist1)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_a[2][KM_ROWS * KM_STRIDE];
+    __shared__ __attribute__((aligned(16))) int s_pa[2][KM_ROWS];
+    const int b = blockIdx.x;
+    if (b >= tile_prefix[n_sets]) return;                    // (block-uniform, as everything up to the body)
+    int lo = 0, hi = n_sets;                                 // the last set whose tiles start at or before b
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (tile_prefix[mid] <= b) lo = mid; else hi = mid;
+    }
+    const int set = lo;
+    const int nq = nQ[set], nt = min(max(nT[set * tSetStep], 0), tCap);
+    const KnnIndexed Q = {q, rank_entry, qidx, qbase[set], b - tile_prefix[set]};
+    knn2_body<12>(s_a, s_pa, set, nq, nt, Q, t, strideT, idx0, dist0, dist1);
 }
 
 static void launch_knn2_kernel(dim3 grid, hipStream_t s, const uint8_t* q, const int* nQ, int strideQ, int qStep, const uint8_t* t, const int* nT,
@@ -576,6 +626,17 @@ int launch_match_bf(const uint8_t* dA, const int* nA, int strideA, int aStep, co
         launch_knn2_kernel(dim3((strideB + 255) / 256, n_sets), s, dB, nB, strideB, bStep, dA, nA, strideA, aStep, idxBA, d0BA, d1BA);
     hipLaunchKernelGGL(k_ratio_mutual, dim3((strideA + 255) / 256, n_sets), dim3(256), 0, s, nA, strideA, aStep, nB, strideB, bStep, idxAB, d0AB,
                        d1AB, idxBA, d0BA, d1BA, nnr, best_lr, m12);
+    OLF_HIP_CHECK(hipGetLastError());
+    return OLF_OK;
+}
+
+int launch_knn2_indexed(const uint8_t* q, const int* rank_entry, const int* qidx, const int* qbase, const int* nQ, const int* tile_prefix, int n_sets,
+                        int max_tiles, const uint8_t* t, const int* nT, int strideT, int tStep, int tCap, int* idx0, int* dist0, int* dist1, hipStream_t s)
+{
+    if (tCap > 4096) { set_error("knn2 (indexed): more than 4096 train descriptors per set"); return OLF_ERR_CAPACITY; }      // 12-bit index in the fused keys
+    if (n_sets <= 0 || max_tiles <= 0) return OLF_OK;
+    hipLaunchKernelGGL(k_knn2_indexed, dim3(max_tiles), dim3(256), 0, s, q, rank_entry, qidx, qbase, nQ, tile_prefix, n_sets, t, nT, strideT, tStep, tCap, idx0,
+                       dist0, dist1);
     OLF_HIP_CHECK(hipGetLastError());
     return OLF_OK;
 }

@@ -48,7 +48,7 @@ void set_error(const std::string& s);
 //                  olf_features_in_area, olf_hamming_matrix, olf_distinctive_descriptors) and the olf_debug_*_sweep counters.  Every one of them ends in
 //                  a synchronise on the context's stream.
 //   SCRATCH_BATCH  the batched matchers (olf_search_by_bow_batch_dev, olf_search_by_projection_batch_dev, olf_is_in_frustum_batch_dev,
-//                  olf_search_local_map_batch_dev) and the image-sized host-pointer entries (olf_cvt_gray, olf_remap_linear,
+//                  olf_search_local_map_batch_dev, and the line entries of line_batch.hip) and the image-sized host-pointer entries (olf_cvt_gray, olf_remap_linear,
 //                  olf_init_undistort_rectify_map, olf_bow_transform).  The matchers do not synchronise: the caller keeps them on one stream.
 //   SCRATCH_PACK   olf_frames_pack_dev: the record's row offsets.
 // Live at the same time: STAGE over KNN inside olf_match_bf (it stages, then calls olf_match_bf_dev); KNN, BATCH and PACK in a pipeline step that
@@ -62,6 +62,8 @@ int ctx_scratch(olf_ctx* c, ScratchSlot slot, size_t bytes, void** out);
 int* ctx_status(olf_ctx* c);
 int ctx_check_device(const olf_ctx* c, const char* who);
 int ctx_check_status(olf_ctx* c);                      // reads the device's capacity flags: OLF_OK, or OLF_ERR_CAPACITY with the flags cleared and named
+// line outputs of a frame call whose line path is still running (olf_ctx_set_deferred_join): when one of the pointers lies in them, stream s waits for it first
+int ctx_join_line_outputs(olf_ctx* c, hipStream_t s, const void* p0, const void* p1, const void* p2, const void* p3);
 int ctx_level_scales(const olf_ctx* c, float* sf);     // mvScaleFactors into sf[0 .. OLF_MAX_LEVELS), 1.0 above the context's levels; returns the level count
 int ctx_level_thresholds(olf_ctx* c, float* thr);      // the table of olf_predict_scale_thresholds for the context's levels, built once
 
@@ -207,6 +209,10 @@ int launch_match_bf(const uint8_t* dA, const int* nA, int strideA, int aStep, co
                     int n_sets, float nnr, int best_lr, int* ws, int* m12, hipStream_t s);
 int launch_knn2(const uint8_t* dA, const int* nA, int strideA, const uint8_t* dB, const int* nB, int strideB, int n_sets, int* idx0,
                 int* dist0, int* dist1, hipStream_t s);
+// kNN(2) of queries fetched through an index (k_knn2_indexed): set s has nQ[s] queries, query r = row qidx[rank_entry[qbase[s] + r]] of q, against the nT[s * tStep]
+// (<= tCap <= 4096) rows at t + s * strideT * 32; results at place qbase[s] + r.  tile_prefix [n_sets + 1]: running sum of ceil(nQ[s] / 256), <= max_tiles
+int launch_knn2_indexed(const uint8_t* q, const int* rank_entry, const int* qidx, const int* qbase, const int* nQ, const int* tile_prefix, int n_sets,
+                        int max_tiles, const uint8_t* t, const int* nT, int strideT, int tStep, int tCap, int* idx0, int* dist0, int* dist1, hipStream_t s);
 int launch_match_candidates(const uint8_t* q, int nQ, const uint8_t* t, int nT, const int* offs, const int* cand, uint16_t* out, hipStream_t s);
 int launch_distinctive(const uint8_t* desc, const int* offs, int n_points, int* best, hipStream_t s);
 int launch_hamming_matrix(const uint8_t* a, int nA, const uint8_t* b, int nB, uint16_t* out, hipStream_t s);

@@ -484,6 +484,82 @@ int olf_is_in_frustum(const olf_frame_view* f, int n_mp, const float* world, con
     return OLF_OK;
 }
 
+// bool Frame::isInFrustum_l(MapLine *pML, float viewingCosLimit), src/Frame.cc:446-515: both end points through project_closed (search_math.hpp), the start
+// point first.  mnTrackangle (:512) is read by commented-out code only (src/Tracking.cc:1991-1997) and is not produced.
+int olf_is_in_frustum_l(const olf_frame_view* f, int n_ml, const float* world6, uint8_t* in_view, float* proj4)
+{
+    if (!f || !f->Tcw || n_ml < 0 || (n_ml && (!world6 || !in_view || !proj4))) { set_error("olf_is_in_frustum_l: bad argument"); return OLF_ERR_INVALID; }
+    const float cam[4] = {f->fx, f->fy, f->cx, f->cy}, bounds[4] = {f->minX, f->maxX, f->minY, f->maxY};
+    for (int i = 0; i < n_ml; ++i) {
+        in_view[i] = 0;
+        float s[2], e[2];
+        if (!project_closed(f->Tcw, world6 + 6 * (size_t)i, cam, bounds, s)) continue;
+        if (!project_closed(f->Tcw, world6 + 6 * (size_t)i + 3, cam, bounds, e)) continue;
+        in_view[i] = 1;                                       // mbTrackInView; mTrackProjsX, mTrackProjsY, mTrackProjeX, mTrackProjeY
+        float* p = proj4 + 4 * (size_t)i;
+        p[0] = s[0]; p[1] = s[1]; p[2] = e[0]; p[3] = e[1];
+    }
+    return OLF_OK;
+}
+
+// The loop of Tracking::SearchLocalPointsAndLines over matches_12 (src/Tracking.cc:1974-2016) and n_inliers_ls (:2021-2023) for one frame.
+int olf_local_lines_assign(int n_in_view, int32_t* m12, const int32_t* map_index, const float* proj4, const olf_keyline* kls, int n_lines, const float* ldisp,
+                           float minX, float maxX, float minY, float maxY, int n_ml, const uint8_t* obs, int32_t* frame_ml, int32_t* n_inliers)
+{
+    if (n_in_view < 0 || n_lines < 0 || n_ml < 0 || !n_inliers || (n_in_view && (!m12 || !map_index || !proj4 || !obs)) || (n_lines && (!kls || !ldisp || !frame_ml))) {
+        set_error("olf_local_lines_assign: bad argument"); return OLF_ERR_INVALID;
+    }
+    for (int i1 = 0; i1 < n_in_view; ++i1)
+        if (m12[i1] >= n_lines || map_index[i1] < 0 || map_index[i1] >= n_ml) { set_error("olf_local_lines_assign: index out of range"); return OLF_ERR_INVALID; }
+    for (int i2 = 0; i2 < n_lines; ++i2)
+        if (frame_ml[i2] >= n_ml) { set_error("olf_local_lines_assign: a held map line outside the map"); return OLF_ERR_INVALID; }
+    const double deltaWidth = (double)(maxX - minX) * 0.1, deltaHeight = (double)(maxY - minY) * 0.1;
+    for (int i1 = 0; i1 < n_in_view; ++i1) {
+        const int i2 = m12[i1];
+        if (i2 < 0) continue;
+        if (line_is_mono(ldisp, i2)) continue;
+        if (frame_ml[i2] >= 0 && obs[frame_ml[i2]]) continue;               // mvpMapLines[i2]->Observations() > 0, :1981-1983
+        const float* p = proj4 + 4 * (size_t)i1;                            // mTrackProjsX, sY, eX, eY of mvpLocalMapLines_InFrustum[i1]
+        if (line_moved(kls[i2], p[0], p[1], p[2], p[3], deltaWidth, deltaHeight)) { m12[i1] = -1; continue; }
+        frame_ml[i2] = map_index[i1];
+    }
+    int n = 0;
+    for (int i2 = 0; i2 < n_lines; ++i2) n += frame_ml[i2] >= 0 ? 1 : 0;
+    *n_inliers = n;
+    return OLF_OK;
+}
+
+// The frame-to-frame line tracking of Tracking::TrackWithMotionModelWithLine (src/Tracking.cc:1305-1349; skip_null = 1, gates = 1, pos_frac = 0.1) and
+// of TrackReferenceKeyFrameWithLine (:976-1020; skip_null = 0, gates = 0: `if(false)`, 0.3 unused) behind match(): the fill with NULL, the loop, n_inliers_ls.
+int olf_track_lines_assign(int n_last, int32_t* m12, const olf_keyline* kls_last, const int32_t* last_ml, int n_cur, const olf_keyline* kls_cur,
+                           const float* ldisp_cur, float minX, float maxX, float minY, float maxY, int skip_null, int gates, double delta_angle, double pos_frac,
+                           int32_t* cur_ml, int32_t* n_inliers)
+{
+    if (n_last < 0 || n_cur < 0 || !n_inliers || (n_last && (!m12 || !last_ml || (gates && !kls_last))) || (n_cur && (!ldisp_cur || !cur_ml || (gates && !kls_cur)))) {
+        set_error("olf_track_lines_assign: bad argument"); return OLF_ERR_INVALID;
+    }
+    for (int i1 = 0; i1 < n_last; ++i1)
+        if (m12[i1] >= n_cur) { set_error("olf_track_lines_assign: index out of range"); return OLF_ERR_INVALID; }
+    std::fill(cur_ml, cur_ml + n_cur, -1);
+    const double deltaWidth = (double)(maxX - minX) * pos_frac, deltaHeight = (double)(maxY - minY) * pos_frac;
+    int n = 0;
+    for (int i1 = 0; i1 < n_last; ++i1) {
+        if (skip_null && last_ml[i1] < 0) continue;
+        const int i2 = m12[i1];
+        if (i2 < 0) continue;
+        if (line_is_mono(ldisp_cur, i2)) continue;
+        if (gates) {
+            if (line_turned(kls_cur[i2].angle, kls_last[i1].angle, delta_angle)) { m12[i1] = -1; continue; }
+            const olf_keyline& l = kls_last[i1];
+            if (line_moved(kls_cur[i2], l.startPointX, l.startPointY, l.endPointX, l.endPointY, deltaWidth, deltaHeight)) { m12[i1] = -1; continue; }
+        }
+        cur_ml[i2] = last_ml[i1] < 0 ? -1 : last_ml[i1];
+        ++n;
+    }
+    *n_inliers = n;
+    return OLF_OK;
+}
+
 // The ratios at which predict_scale steps, found on predict_scale itself: thr[k - 1] = the smallest positive float whose level is >= k.  The level is a
 // non-decreasing function of the ratio wherever ceil(logf(ratio) / logSF) is (a property of the libm in use, checked around every threshold below), so
 // "the number of thresholds <= ratio" is the level.

@@ -4,6 +4,8 @@
 #pragma once
 #include <cmath>
 #include <hip/hip_runtime.h>
+#include "device_math.hpp"
+#include "../../include/orbline_types.h"
 
 namespace olf {
 
@@ -29,6 +31,41 @@ __host__ __device__ __forceinline__ void camera_centre(const float* Tcw, float* 
         Ow[r] = (float)(-acc);
     }
 }
+
+// One endpoint of Frame::isInFrustum_l (src/Frame.cc:456-479, :480-503) -- the first half of Frame::isInFrustum (:394-412): mRcw * p + mtcw under C.12, the
+// depth gate, the projection and the CLOSED image bounds.  cam = fx, fy, cx, cy; bounds = mnMinX, mnMaxX, mnMinY, mnMaxY.  false: uv is not written.
+// (The point forms, olf_is_in_frustum and k_local_frustum, keep their own spelling of these six lines: they go on to use PcZ's reciprocal for
+// mTrackProjXR, and k_local_frustum is held to the instructions it compiled to when it was measured.)
+__host__ __device__ __forceinline__ bool project_closed(const float* Tcw, const float* P, const float* cam, const float* bounds, float* uv)
+{
+    float Pc[3];
+    rot_apply(Tcw, P, 1.0f, Pc);
+    const float PcX = Pc[0], PcY = Pc[1], PcZ = Pc[2];
+    if (PcZ < 0.0f) return false;
+    const float invz = f_div(1.0f, PcZ);
+    const float u = cam[0] * PcX * invz + cam[2], v = cam[1] * PcY * invz + cam[3];
+    if (u < bounds[0] || u > bounds[1]) return false;
+    if (v < bounds[2] || v > bounds[3]) return false;
+    uv[0] = u; uv[1] = v;
+    return true;
+}
+
+// The gates of the line trackers (src/Tracking.cc:1324-1344, :995-1015, :2000-2012), literally: the differences are formed in float, widened to double and
+// compared with a strict '>'; deltaWidth = (mnMaxX - mnMinX) * frac is a float difference times a double.
+__host__ __device__ __forceinline__ bool line_turned(float angle_cur, float angle_last, double delta_angle)
+{
+    double theta = (double)f_sub(angle_cur, angle_last);
+    if (theta < -M_PI) theta += 2 * M_PI;
+    else if (theta > M_PI) theta -= 2 * M_PI;
+    return fabs(theta) > delta_angle;
+}
+__host__ __device__ __forceinline__ bool line_moved(const olf_keyline& cur, float sX, float sY, float eX, float eY, double delta_width, double delta_height)
+{
+    return (double)fabsf(f_sub(cur.startPointX, sX)) > delta_width || (double)fabsf(f_sub(cur.endPointX, eX)) > delta_width ||
+           (double)fabsf(f_sub(cur.startPointY, sY)) > delta_height || (double)fabsf(f_sub(cur.endPointY, eY)) > delta_height;
+}
+// mvDisparity_l[i2].first < 0 || .second < 0 (:1319, :990, :1979): a line without a stereo match takes no map line
+__host__ __device__ __forceinline__ bool line_is_mono(const float* ldisp, int i2) { return ldisp[2 * (size_t)i2] < 0 || ldisp[2 * (size_t)i2 + 1] < 0; }
 
 // the rotation bin of a match (src/ORBmatcher.cc:1434-1441 and its siblings); angles outside [0, 360) give a bin outside [0, HISTO_LENGTH)
 __host__ __device__ __forceinline__ int rot_bin(float angle1, float angle2)

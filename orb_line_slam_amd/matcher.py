@@ -490,6 +490,125 @@ def search_local_map_batch(n_frames, kps, desc, counts, uright, cell_offsets, ce
     return out
 
 
+class LocalLineMapDev:
+    """olf_local_line_map (include/orbline.h): the map lines a batch of frames is matched against, as device tensors over n_ml lines -- world [n_ml, 6]
+    float32 (GetWorldPos(): start, then end), desc [n_ml, 32] uint8, obs / bad [n_ml] uint8 -- and optionally every frame's mvpLocalMapLines as
+    (list_offsets [n_frames + 1], list_index [n_entries]) int32.  Without lists every frame sees all lines in index order."""
+
+    def __init__(self, world, desc, obs, bad, list_offsets=None, list_index=None, n_ml=None):
+        self.world, self.desc, self.obs, self.bad = world, desc, obs, bad
+        self.list_offsets, self.list_index = list_offsets, list_index
+        self.n_ml = int(bad.shape[0]) if n_ml is None else int(n_ml)
+
+    def n_entries(self, n_frames):
+        if self.list_offsets is None:
+            return int(n_frames) * self.n_ml
+        return 0 if self.list_index is None else int(self.list_index.shape[0])
+
+    def c(self, n_frames):
+        import torch
+        m = _lib.LocalLineMapC()
+        m.world = _dev(self.world, torch.float32, "world")
+        m.desc, m.obs, m.bad = (_dev(getattr(self, k), torch.uint8, k) for k in ("desc", "obs", "bad"))
+        m.n_ml = self.n_ml
+        m.list_offsets, m.list_index = _dev(self.list_offsets, torch.int32, "list_offsets"), _dev(self.list_index, torch.int32, "list_index")
+        m.n_entries = self.n_entries(n_frames)
+        return m
+
+
+def _line_batch_c(kls, ldesc, lcounts, img_stride, ldisp, Tcw, camera, bounds):
+    import torch
+    lb = _lib.LineBatchC()
+    lb.kls, lb.ldesc, lb.lcounts, lb.img_stride = _dev(kls, None, "kls"), _dev(ldesc, torch.uint8, "ldesc"), _dev(lcounts, torch.int32, "lcounts"), int(img_stride)
+    lb.ldisp, lb.Tcw = _dev(ldisp, torch.float32, "ldisp"), _dev(Tcw, torch.float32, "Tcw")
+    lb.fx, lb.fy, lb.cx, lb.cy = (float(v) for v in camera[:4])
+    lb.minX, lb.maxX, lb.minY, lb.maxY = (float(v) for v in bounds)
+    return lb
+
+
+def is_in_frustum_l_batch(n_frames, Tcw, local_lines, camera, bounds, frame_ml=None, lcounts=None, img_stride=2, out=None, context=None):
+    """Frame::isInFrustum_l (src/Frame.cc:446-515) for every (frame, local map line) of a device-resident batch, with the bad / already-held skips of
+    Tracking::SearchLocalPointsAndLines (src/Tracking.cc:1953-1956): olf_is_in_frustum_l_batch_dev (include/orbline.h).  Tcw [n_frames, 4, 4];
+    local_lines: a LocalLineMapDev; camera = (fx, fy, cx, cy[, mbf]); bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY); frame_ml int32 [n_frames, capacity]: the
+    frames' mvpMapLines as map indices (negative: none), lcounts (extractor layout, with img_stride): their N_l.  Runs on torch's current stream.
+    Returns (in_view uint8, proj4 float32 [.., 4]) over the entries; entries not in view keep what `out` held (zeros by default) in proj4."""
+    import ctypes as C
+    import torch
+    ctx = _ctx(context)
+    ne = local_lines.n_entries(n_frames)
+    lb = _line_batch_c(None, None, lcounts, img_stride, None, Tcw, camera, bounds)
+    lm = local_lines.c(n_frames)
+    if out is None:
+        out = (torch.zeros((ne,), dtype=torch.uint8, device="cuda"), torch.zeros((ne, 4), dtype=torch.float32, device="cuda"))
+    v, p = out
+    with _torch_stream() as s:
+        check(lib().olf_is_in_frustum_l_batch_dev(ctx.handle, C.byref(lb), int(n_frames), C.byref(lm), _dev(frame_ml, torch.int32, "frame_ml"),
+                                                  _dev(v, torch.uint8, "in_view"), _dev(p, torch.float32, "proj4"), s), "olf_is_in_frustum_l_batch_dev")
+    return out
+
+
+def search_local_lines_batch(n_frames, kls, ldesc, lcounts, ldisp, Tcw, local_lines, camera, bounds, nnr, frame_ml=None, img_stride=2, out=None, context=None):
+    """The line half of Tracking::SearchLocalPointsAndLines (src/Tracking.cc:1897-1913, :1945-2023) for a device-resident batch: the frustum pass, the
+    compaction into mvpLocalMapLines_InFrustum, match() against every frame's own lines, the loop :1976-2016 and n_inliers_ls --
+    olf_search_local_lines_batch_dev (include/orbline.h describes every array; csrc/line_batch.hip).  kls / ldesc / lcounts in the extractor's layout,
+    ldisp [n_frames, capacity, 2] (mvDisparity_l); nnr = Config::minRatio12L().  out = (in_view, proj4, m12, frame_ml_out, ninliers).  Runs on torch's
+    current stream.  Returns (in_view [n_entries] uint8, proj4 [n_entries, 4], m12 [n_entries]: matches_12 at the end per entry, -1 not in view;
+    frame_ml_out [n_frames, capacity]: mvpMapLines at the end as map indices; ninliers [n_frames])."""
+    import ctypes as C
+    import torch
+    ctx = _ctx(context)
+    ne = local_lines.n_entries(n_frames)
+    lb = _line_batch_c(kls, ldesc, lcounts, img_stride, ldisp, Tcw, camera, bounds)
+    lm = local_lines.c(n_frames)
+    if out is None:
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda")
+        out = (z((ne,), torch.uint8), z((ne, 4), torch.float32), torch.full((ne,), -1, dtype=torch.int32, device="cuda"),
+               torch.full((int(n_frames), ctx.line_capacity), -1, dtype=torch.int32, device="cuda"), z((int(n_frames),), torch.int32))
+    v, p, m, fo, n = out
+    with _torch_stream() as s:
+        check(lib().olf_search_local_lines_batch_dev(ctx.handle, C.byref(lb), int(n_frames), C.byref(lm), _dev(frame_ml, torch.int32, "frame_ml"), float(nnr),
+                                                     _dev(v, torch.uint8, "in_view"), _dev(p, torch.float32, "proj4"), _dev(m, torch.int32, "m12"),
+                                                     _dev(fo, torch.int32, "frame_ml_out"), _dev(n, torch.int32, "ninliers"), s),
+              "olf_search_local_lines_batch_dev")
+    return out
+
+
+def track_lines_batch(n_frames, kls, ldesc, lcounts, ldisp, last_ml, bounds, nnr, best_lr=True, skip_null=True, gates=True, delta_angle=np.pi / 8.0, pos_frac=0.1,
+                      enable=None, img_stride=2, out=None, context=None):
+    """The f2f line tracking of Tracking::TrackWithMotionModelWithLine (src/Tracking.cc:1305-1349; the defaults) or TrackReferenceKeyFrameWithLine
+    (:976-1020: skip_null=False, gates=False) for the n_frames - 1 consecutive pairs of a device-resident batch: olf_track_lines_batch_dev
+    (include/orbline.h).  last_ml int32 [n_frames - 1, capacity]: mvpMapLines of every pair's last frame as ids (negative: NULL); enable int32
+    [n_frames - 1] (0: the pair's rows of `out` keep what they hold).  out = (m12, cur_ml, ninliers).  Runs on torch's current stream.  Returns
+    (m12 [n_frames - 1, capacity], cur_ml [n_frames - 1, capacity]: the ids the current frame's lines received, -1 none; ninliers [n_frames - 1])."""
+    import ctypes as C
+    import torch
+    ctx = _ctx(context)
+    n_pairs = max(int(n_frames) - 1, 0)
+    lb = _line_batch_c(kls, ldesc, lcounts, img_stride, ldisp, None, (0.0, 0.0, 0.0, 0.0), bounds)
+    if out is None:
+        full = lambda shape: torch.full(shape, -1, dtype=torch.int32, device="cuda")
+        out = (full((n_pairs, ctx.line_capacity)), full((n_pairs, ctx.line_capacity)), torch.zeros((n_pairs,), dtype=torch.int32, device="cuda"))
+    m, cm, n = out
+    with _torch_stream() as s:
+        check(lib().olf_track_lines_batch_dev(ctx.handle, C.byref(lb), int(n_frames), _dev(last_ml, torch.int32, "last_ml"), float(nnr), int(bool(best_lr)),
+                                              int(bool(skip_null)), int(bool(gates)), float(delta_angle), float(pos_frac), _dev(enable, torch.int32, "enable"),
+                                              _dev(m, torch.int32, "m12"), _dev(cm, torch.int32, "cur_ml"), _dev(n, torch.int32, "ninliers"), s),
+              "olf_track_lines_batch_dev")
+    return out
+
+
+def isInFrustum_l(F, lines):
+    """bool Frame::isInFrustum_l(MapLine *pML, float viewingCosLimit), src/Frame.cc:446-515, for map lines given as world positions [n, 6] float32 (start,
+    then end) -> olf_is_in_frustum_l (host arithmetic in the library).  F: a FrameView (mTcw, the calibration, the bounds).  Returns (mbTrackInView [n]
+    bool, proj4 [n, 4] float32 = mTrackProjsX, mTrackProjsY, mTrackProjeX, mTrackProjeY; rows not in view are zero)."""
+    keep = []
+    f = _view_c(F, keep)
+    w = np.ascontiguousarray(lines, np.float32).reshape(-1, 6)
+    inview, proj4 = np.zeros(len(w), np.uint8), np.zeros((len(w), 4), np.float32)
+    check(lib().olf_is_in_frustum_l(f, len(w), ptr(w), ptr(inview), ptr(proj4)), "olf_is_in_frustum_l")
+    return inview.astype(bool), proj4
+
+
 class MapPointView:
     """The MapPoint members read by SearchByProjection(Frame&, const vector<MapPoint*>&, th) (src/ORBmatcher.cc:47-131), gathered by the
     host (mutex-guarded in the reference, src/MapPoint.cc:321-325) into SoA buffers:

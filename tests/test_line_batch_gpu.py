@@ -1,0 +1,320 @@
+"""GPU parity: olf_is_in_frustum_l_batch_dev, olf_search_local_lines_batch_dev and olf_track_lines_batch_dev -- the line half of tracking for a
+device-resident batch (Frame::isInFrustum_l, src/Frame.cc:446-515; Tracking::SearchLocalPointsAndLines, src/Tracking.cc:1897-1913, :1945-2023; the f2f line
+tracking, :1305-1349 / :976-1020).  Every expectation is the oracle-built one of line_scenes.py (oracle.is_in_frustum per end point, oracle.match_bf, the
+reference's loops restated line for line), compared bit for bit with nothing left out; test_line_track_cpu.py asserts the floors on those expectations.
+Frames are synthetic (no extractor), 320 x 240."""
+import ctypes as C
+import numpy as np
+import pytest
+import line_scenes as ls
+import orb_line_slam_amd as ola
+from orb_line_slam_amd import _lib, matcher
+from orb_line_slam_amd._lib import KEYLINE_DTYPE, OLF_ERR_CAPACITY, OLF_ERR_INVALID, lib
+
+pytestmark = pytest.mark.gpu
+
+LINE_CAP = 330                                               # no multiple of 64, of 32 or of 256
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import torch  # noqa: F401  (the device tensors below)
+    p = _lib.default_params()
+    p.line.lsd_nfeatures = LINE_CAP
+    c = _lib.Context(p, ls.W, ls.H, 2)
+    assert c.line_capacity == LINE_CAP
+    yield c
+    c.close()
+
+
+def up(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+class DeviceLines:
+    """frames (and a map, mvpMapLines, per-frame lists) as the device arrays of the entries; rows nothing may read hold live-looking values"""
+
+    def __init__(self, ctx, frames, mp=None, lists=None, img_stride=1, frame_ml="own"):
+        self.ctx, self.n, self.st, cap = ctx, len(frames), img_stride, ctx.line_capacity
+        self.cap = cap
+        nf, ni = max(self.n, 1), max(self.n * img_stride, 1)
+        rng = np.random.default_rng(5)
+        kls = np.zeros((ni, cap), KEYLINE_DTYPE)
+        kls["startPointX"] = kls["endPointX"] = 1e9
+        desc = rng.integers(0, 256, (ni, cap, 32), dtype=np.uint8)
+        cnt = np.full(ni, 17, np.int32)
+        disp, Tcw = np.full((nf, cap, 2), 5.0, ls.f32), np.zeros((nf, 4, 4), ls.f32)
+        fml = np.full((nf, cap), 3, np.int32)                 # (past N_l: a live index nothing may read)
+        for j, fr in enumerate(frames):
+            m = len(fr.kls)
+            assert m <= cap
+            kls[j * img_stride, :m], desc[j * img_stride, :m], cnt[j * img_stride] = fr.kls, fr.ldesc, m
+            disp[j, :m] = fr.ldisp
+            if hasattr(fr, "Tcw"):
+                Tcw[j] = fr.Tcw
+            if isinstance(frame_ml, str):
+                fml[j, :m] = fr.frame_ml if hasattr(fr, "frame_ml") else fr.ml
+            elif frame_ml is not None:
+                fml[j, :m] = frame_ml[j]
+        self.kls, self.ldesc, self.lcounts = up(kls.view(np.uint8).reshape(ni, cap, 68)), up(desc), up(cnt)
+        self.ldisp, self.Tcw = up(disp), up(Tcw)
+        self.frame_ml = up(fml) if frame_ml is not None else None
+        self.map = None
+        if mp is not None:
+            lo = li = None
+            if lists is not None:
+                lo = up(np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int32))
+                li = up(np.concatenate([np.asarray(x, np.int32) for x in lists] + [np.zeros(0, np.int32)]).astype(np.int32))
+            self.map = matcher.LocalLineMapDev(up(mp.world), up(mp.desc), up(mp.obs.astype(np.uint8)), up(mp.bad.astype(np.uint8)), lo, li, n_ml=mp.n)
+            self.bounds = mp.bounds
+
+    def frustum(self, **kw):
+        return matcher.is_in_frustum_l_batch(self.n, self.Tcw, self.map, ls.CAM, self.bounds, frame_ml=self.frame_ml, lcounts=self.lcounts, img_stride=self.st,
+                                             context=self.ctx, **kw)
+
+    def search(self, nnr=ls.NNR, **kw):
+        return matcher.search_local_lines_batch(self.n, self.kls, self.ldesc, self.lcounts, self.ldisp, self.Tcw, self.map, ls.CAM, self.bounds, nnr,
+                                                frame_ml=self.frame_ml, img_stride=self.st, context=self.ctx, **kw)
+
+    def track(self, mode, best_lr, **kw):
+        return matcher.track_lines_batch(self.n, self.kls, self.ldesc, self.lcounts, self.ldisp, self.frame_ml[:max(self.n - 1, 0)].contiguous(), ls.BOUNDS, ls.NNR,
+                                         best_lr=best_lr, img_stride=self.st, context=self.ctx, **ls.F2F_MODES[mode], **kw)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def cat(exp, key):
+    return np.concatenate([e[key] for e in exp])
+
+
+def assert_local(res, frames, exp, cap):
+    v, p, m, fo, n = (x.cpu().numpy() for x in res)
+    assert np.array_equal(v.astype(bool), cat(exp, "in_view")) and np.array_equal(bits(p), bits(cat(exp, "proj4")))
+    assert np.array_equal(m, cat(exp, "m12"))
+    for j, (fr, e) in enumerate(zip(frames, exp)):
+        N = len(fr.kls)
+        assert np.array_equal(fo[j, :N], e["frame_ml"]) and np.all(fo[j, N:] == -1) and fo.shape[1] == cap
+        assert int(n[j]) == e["n_inliers"]
+
+
+# ---- 1: the frustum pass alone ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(ls.LOCAL_CASES))
+def test_frustum(oracle, ctx, name):
+    frames, mp, lists, exp = ls.local_case(oracle, name)
+    db = DeviceLines(ctx, frames, mp, lists)
+    v, p = (x.cpu().numpy() for x in db.frustum())
+    assert np.array_equal(v.astype(bool), cat(exp, "in_view")) and np.array_equal(bits(p), bits(cat(exp, "proj4")))
+    assert v.sum() >= 500
+    v2, p2 = (x.cpu().numpy() for x in db.frustum())          # the same call again on the same stream: nothing is left in scratch
+    assert np.array_equal(v2, v) and np.array_equal(bits(p2), bits(p))
+
+
+def test_frustum_holds_nothing(oracle, ctx):
+    """d_frame_ml = NULL: only bad lines are skipped"""
+    frames, mp, lists, _ = ls.local_case(oracle, "lists_a")
+    none = [np.full(len(fr.kls), -1, np.int32) for fr in frames]
+    exp = [ls.expect_frustum_frame(oracle, fr, mp, lists[j], none[j]) for j, fr in enumerate(frames)]
+    v, p = (x.cpu().numpy() for x in DeviceLines(ctx, frames, mp, lists, frame_ml=None).frustum())
+    assert np.array_equal(v.astype(bool), np.concatenate([e[0] for e in exp])) and np.array_equal(bits(p), bits(np.concatenate([e[1] for e in exp])))
+
+
+# ---- 2: the whole line half ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,img_stride", [("lists_a", 1), ("lists_b", 2), ("no_lists", 1), ("shrunk", 2)])
+def test_search_local_lines(oracle, ctx, name, img_stride):
+    frames, mp, lists, exp = ls.local_case(oracle, name)
+    ctx.poll_status()
+    db = DeviceLines(ctx, frames, mp, lists, img_stride=img_stride)
+    res = db.search()
+    assert_local(res, frames, exp, ctx.line_capacity)
+    res2 = db.search()                                       # the same call again on the same stream: nothing is left in scratch
+    for a, b in zip(res, res2):
+        assert np.array_equal(a.cpu().numpy().view(np.uint8), b.cpu().numpy().view(np.uint8))
+    ctx.poll_status()
+
+
+def test_search_in_place(oracle, ctx):
+    """d_frame_ml_out may be d_frame_ml"""
+    import torch
+    frames, mp, lists, exp = ls.local_case(oracle, "lists_a")
+    db = DeviceLines(ctx, frames, mp, lists)
+    ne = db.map.n_entries(db.n)
+    out = (torch.zeros(ne, dtype=torch.uint8, device="cuda"), torch.zeros((ne, 4), dtype=torch.float32, device="cuda"),
+           torch.full((ne,), 9, dtype=torch.int32, device="cuda"), db.frame_ml, torch.full((db.n,), 9, dtype=torch.int32, device="cuda"))
+    assert_local(db.search(out=out), frames, exp, ctx.line_capacity)
+
+
+def test_malformed_indices(oracle, ctx):
+    """a list index outside the map is left out (in view = 0), a held value beyond the map holds nothing; bit 1024 reports either, nothing else changes"""
+    frames, mp, lists, exp = ls.local_case(oracle, "lists_a")
+    ctx.poll_status()
+    bad_lists = [x.copy() for x in lists]
+    bad_lists[1] = np.concatenate([lists[1][:50], [mp.n, -1, 2 ** 30], lists[1][50:]]).astype(np.int32)
+    res = DeviceLines(ctx, frames, mp, bad_lists).search()
+    exp1 = [ls.expect_local_frame(oracle, fr, mp, bad_lists[j], fr.frame_ml) for j, fr in enumerate(frames)]
+    assert not exp1[1]["in_view"][50:53].any() and np.array_equal(np.delete(exp1[1]["m12"], [50, 51, 52]), exp[1]["m12"])
+    assert_local(res, frames, exp1, ctx.line_capacity)
+    with pytest.raises(ola.OlfError) as e:
+        ctx.poll_status()
+    assert e.value.code == OLF_ERR_CAPACITY and "flags=1024" in str(e.value)
+    ctx.poll_status()
+    fml = [fr.frame_ml.copy() for fr in frames]
+    hold = np.flatnonzero(fml[0] >= 0)[:7]
+    fml[0][hold] = mp.n + np.arange(7) * 1000
+    exp2 = [ls.expect_local_frame(oracle, fr, mp, lists[j], fml[j]) for j, fr in enumerate(frames)]
+    assert not np.array_equal(exp2[0]["frame_ml"], exp[0]["frame_ml"])
+    assert_local(DeviceLines(ctx, frames, mp, lists, frame_ml=fml).search(), frames, exp2, ctx.line_capacity)
+    with pytest.raises(ola.OlfError) as e:
+        ctx.poll_status()
+    assert "flags=1024" in str(e.value)
+
+
+# ---- 3: frame-to-frame -------------------------------------------------------------------------------------------------------------------------------------
+def assert_pair(res, j, frames, e, cap):
+    m, cm, n = (x.cpu().numpy() for x in res)
+    nl, nc = len(frames[j].kls), len(frames[j + 1].kls)
+    assert np.array_equal(m[j, :nl], e["m12"]) and np.all(m[j, nl:] == -1) and m.shape[1] == cap
+    assert np.array_equal(cm[j, :nc], e["cur_ml"]) and np.all(cm[j, nc:] == -1)
+    assert int(n[j]) == e["n_inliers"]
+
+
+@pytest.mark.parametrize("best_lr", [False, True])
+@pytest.mark.parametrize("mode", list(ls.F2F_MODES))
+def test_track_lines(oracle, ctx, mode, best_lr):
+    import torch
+    frames, exp = ls.f2f_case(oracle, mode, best_lr)
+    db = DeviceLines(ctx, frames, img_stride=2 if best_lr else 1)
+    res = db.track(mode, best_lr)
+    for j, e in enumerate(exp):
+        assert_pair(res, j, frames, e, ctx.line_capacity)
+    res2 = db.track(mode, best_lr)                           # the same call again on the same stream: nothing is left in scratch
+    for a, b in zip(res, res2):
+        assert np.array_equal(a.cpu().numpy(), b.cpu().numpy())
+    # pair 1 disabled: its three rows keep what they held
+    full = lambda shape: torch.full(shape, -77, dtype=torch.int32, device="cuda")
+    out = (full((3, ctx.line_capacity)), full((3, ctx.line_capacity)), full((3,)))
+    res = db.track(mode, best_lr, enable=up(np.array([1, 0, 5], np.int32)), out=out)
+    for j in (0, 2):
+        assert_pair(res, j, frames, exp[j], ctx.line_capacity)
+    assert all(bool((x[1] == -77).all()) for x in res)
+
+
+def test_track_short_frames(oracle, ctx):
+    """a pair with 0 or 1 lines on either side matches nothing; n_frames < 2 writes nothing"""
+    import torch
+    frames = ls.f2f_scene(31)
+    for fr, n in zip(frames, (1, 140, 0, 2)):
+        fr.kls, fr.ldesc, fr.ldisp, fr.ml = fr.kls[:n], fr.ldesc[:n], fr.ldisp[:n], fr.ml[:n]
+    db = DeviceLines(ctx, frames)
+    for best_lr in (False, True):
+        exp = [ls.expect_f2f_pair(oracle, frames[j], frames[j + 1], ls.NNR, best_lr, **ls.F2F_MODES["reference_kf"]) for j in range(3)]
+        res = db.track("reference_kf", best_lr)
+        for j, e in enumerate(exp):
+            assert_pair(res, j, frames, e, ctx.line_capacity)
+        assert not best_lr or all(e["n_inliers"] == 0 for e in exp[:2])
+    one = DeviceLines(ctx, frames[:1])
+    out = tuple(torch.full(s, -77, dtype=torch.int32, device="cuda") for s in ((1, ctx.line_capacity), (1, ctx.line_capacity), (1,)))
+    lb = matcher._line_batch_c(one.kls, one.ldesc, one.lcounts, 1, one.ldisp, None, (0, 0, 0, 0), ls.BOUNDS)
+    torch.cuda.synchronize()
+    for nf in (0, 1):
+        assert lib().olf_track_lines_batch_dev(ctx.handle, C.byref(lb), nf, one.frame_ml.data_ptr(), ls.NNR, 1, 1, 1, 0.4, 0.1, None, *(x.data_ptr() for x in out), None) == 0
+    ctx.synchronize()
+    assert all(bool((x == -77).all()) for x in out)
+
+
+# ---- 4: the contract -----------------------------------------------------------------------------------------------------------------------------------------
+def test_no_frames_and_no_entries(oracle, ctx):
+    import torch
+    frames, mp, lists, exp = ls.local_case(oracle, "lists_a")
+    db = DeviceLines(ctx, frames, mp, lists)
+    lb = matcher._line_batch_c(db.kls, db.ldesc, db.lcounts, 1, db.ldisp, db.Tcw, ls.CAM, ls.BOUNDS)
+    lm = db.map.c(0)
+    ne = db.map.n_entries(5)
+    outs = (torch.full((ne,), 7, dtype=torch.uint8, device="cuda"), torch.full((ne, 4), 7.0, dtype=torch.float32, device="cuda"),
+            torch.full((ne,), 7, dtype=torch.int32, device="cuda"), torch.full((5, ctx.line_capacity), 7, dtype=torch.int32, device="cuda"),
+            torch.full((5,), 7, dtype=torch.int32, device="cuda"))
+    torch.cuda.synchronize()
+    assert lib().olf_search_local_lines_batch_dev(ctx.handle, C.byref(lb), 0, C.byref(lm), db.frame_ml.data_ptr(), ls.NNR, *(x.data_ptr() for x in outs), None) == 0
+    assert lib().olf_is_in_frustum_l_batch_dev(ctx.handle, C.byref(lb), 0, C.byref(lm), db.frame_ml.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), None) == 0
+    ctx.synchronize()
+    assert all(bool((x == 7).all()) for x in outs)
+    # a map without lines: the frames keep what they hold (their bad lines gone), nothing matches
+    empty = ls.LineMap()
+    empty.world, empty.desc, empty.obs, empty.bad, empty.n, empty.bounds = np.zeros((0, 6), ls.f32), np.zeros((0, 32), np.uint8), np.zeros(0, bool), np.zeros(0, bool), 0, ls.BOUNDS
+    none = [np.full(len(fr.kls), -1, np.int32) for fr in frames]
+    res = DeviceLines(ctx, frames, empty, frame_ml=none).search()
+    fo, n = res[3].cpu().numpy(), res[4].cpu().numpy()
+    assert (fo == -1).all() and (n == 0).all() and res[0].numel() == 0
+
+
+def test_error_codes(oracle, ctx):
+    import torch
+    frames, mp, lists, _ = ls.local_case(oracle, "lists_a")
+    db = DeviceLines(ctx, frames[:2], mp, lists[:2])
+    full = dict(kls=db.kls, ldesc=db.ldesc, lcounts=db.lcounts, ldisp=db.ldisp, Tcw=db.Tcw)
+    ne, cap = db.map.n_entries(2), ctx.line_capacity
+    v, p = torch.zeros(ne, dtype=torch.uint8, device="cuda"), torch.zeros((ne, 4), dtype=torch.float32, device="cuda")
+    m, fo, n = torch.zeros(ne, dtype=torch.int32, device="cuda"), torch.zeros((2, cap), dtype=torch.int32, device="cuda"), torch.zeros(2, dtype=torch.int32, device="cuda")
+
+    def fill(skip=None, bounds=ls.BOUNDS):
+        t = _lib.LineBatchC()
+        for k, x in full.items():
+            setattr(t, k, None if k == skip else x.data_ptr())
+        t.img_stride = 1
+        t.fx, t.fy, t.cx, t.cy = ls.CAM[:4]
+        t.minX, t.maxX, t.minY, t.maxY = bounds
+        return t
+
+    def lmap(skip=None):
+        lm = db.map.c(2)
+        if skip:
+            setattr(lm, skip, None)
+        return lm
+
+    P = lambda x: None if x is None else x.data_ptr()
+
+    def search(t, lm, outs=(v, p, m, fo, n), h=ctx.handle):
+        return lib().olf_search_local_lines_batch_dev(h, C.byref(t), 2, C.byref(lm), db.frame_ml.data_ptr(), ls.NNR, *(P(x) for x in outs), None)
+
+    def frustum(t, lm, outs=(v, p)):
+        return lib().olf_is_in_frustum_l_batch_dev(ctx.handle, C.byref(t), 2, C.byref(lm), db.frame_ml.data_ptr(), *(P(x) for x in outs), None)
+
+    fo2 = torch.zeros_like(fo)
+
+    def track(t, outs=(fo, fo2, n), last=db.frame_ml, h=ctx.handle):
+        return lib().olf_track_lines_batch_dev(h, C.byref(t), 2, P(last), ls.NNR, 1, 1, 1, 0.4, 0.1, None, *(P(x) for x in outs), None)
+    torch.cuda.synchronize()                                # (stream NULL = the context's own stream)
+    assert search(fill(), lmap()) == 0 and frustum(fill(), lmap()) == 0 and track(fill()) == 0
+    for k in full:
+        assert search(fill(skip=k), lmap()) == OLF_ERR_INVALID, k
+    for k in ("kls", "ldesc", "lcounts", "ldisp"):
+        assert track(fill(skip=k)) == OLF_ERR_INVALID, k
+    for k in ("world", "desc", "obs", "bad"):
+        assert search(fill(), lmap(skip=k)) == OLF_ERR_INVALID, k
+    for k in ("world", "bad"):
+        assert frustum(fill(), lmap(skip=k)) == OLF_ERR_INVALID, k
+    assert frustum(fill(skip="Tcw"), lmap()) == OLF_ERR_INVALID
+    for i in range(2):
+        assert frustum(fill(), lmap(), tuple(None if k == i else x for k, x in enumerate((v, p)))) == OLF_ERR_INVALID
+    for i in range(5):
+        assert search(fill(), lmap(), tuple(None if k == i else x for k, x in enumerate((v, p, m, fo, n)))) == OLF_ERR_INVALID, i
+    for i in range(3):
+        assert track(fill(), tuple(None if k == i else x for k, x in enumerate((fo, fo2, n)))) == OLF_ERR_INVALID, i
+    assert track(fill(), last=None) == OLF_ERR_INVALID
+    assert search(fill(), lmap(), h=None) == OLF_ERR_INVALID and track(fill(), h=None) == OLF_ERR_INVALID
+    for b in ((320.0, 320.0, 0.0, 240.0), (0.0, 320.0, 240.0, 0.0)):
+        assert search(fill(bounds=b), lmap()) == OLF_ERR_INVALID and frustum(fill(bounds=b), lmap()) == OLF_ERR_INVALID and track(fill(bounds=b)) == OLF_ERR_INVALID
+    lm = lmap()
+    lm.list_index = None                                     # lists without their indices
+    assert search(fill(), lm) == OLF_ERR_INVALID
+    ctx.synchronize()
+    big_p = _lib.default_params()
+    big_p.line.lsd_nfeatures = 4097
+    big = _lib.Context(big_p, ls.W, ls.H, 1)
+    try:
+        assert big.line_capacity > 4096
+        assert search(fill(), lmap(), h=big.handle) == OLF_ERR_CAPACITY and track(fill(), h=big.handle) == OLF_ERR_CAPACITY      # (refused before anything is read)
+    finally:
+        big.close()
