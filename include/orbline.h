@@ -567,6 +567,28 @@ int olf_search_local_map_batch_dev(olf_ctx* ctx, const olf_track_batch* in, int 
                                    float viewing_cos_limit, float th, const float* d_th, float nnratio, int32_t* d_matches, int32_t* d_nmatches,
                                    void* stream);
 
+/* ---- ORBmatcher::SearchForTriangulation for a list of key-frame pairs on the device (csrc/triangulation_batch.hip) ----------------------------------
+ * int ORBmatcher::SearchForTriangulation(KeyFrame *pKF1, KeyFrame *pKF2, cv::Mat F12, vector<pair<size_t,size_t>> &vMatchedPairs, const bool bOnlyStereo,
+ * const cv::Mat Cw) (src/ORBmatcher.cc:659-825), the matcher of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:268), for n_pairs pairs of the
+ * n_frames frames of a batch, Frame::ComputeBoW of every frame included: each frame's FeatureVector is built once per call, whatever the number of pairs
+ * it is part of (voc, levelsup: as olf_search_by_bow_batch_dev; 4 in the reference).  Results equal olf_search_for_triangulation pair by pair.
+ * `in`: only kps, desc, counts, img_stride, uright, Tcw, mp_valid and fx, fy, cx, cy are read (frame j = image j * img_stride).  mp_valid keeps its
+ * meaning -- the features that hold a map point, which this search skips on both sides -- so NULL (every feature holds one) searches nothing: rows -1,
+ * counts 0.  mvScaleFactors are the context's.  d_pairs [n_pairs][2] = (kf1, kf2) frame indices, any order, a frame in any number of pairs.
+ * d_F12 [n_pairs][9] row-major, used as x1^T F12 x2 (LocalMapping::ComputeF12 stays the caller's).  d_Cw [n_pairs][3] = pKF1->GetCameraCenter(), or NULL:
+ * -Rcw.t() * tcw of kf1's Tcw.  d_matches12 [n_pairs][capacity]: row p holds per feature idx1 of kf1 the matched feature idx2 of kf2 or -1 (-1 from N1
+ * on); vMatchedPairs is the list of (idx1, d_matches12[p][idx1] >= 0) in idx1 order.  d_nmatches [n_pairs]: the return values.
+ * A pair whose index lies outside [0, n_frames), or with kf1 == kf2, ends with nmatches = -1 and its row untouched, and sets bit 2048 of the context's
+ * status word (olf_ctx_synchronize / olf_ctx_poll_status report it).  So does, with bit 256, a pair in which a candidate of key frame 2 holds an octave
+ * outside the context's levels.  A candidate here is a feature of kf2 without a map point that passes only_stereo and shares its vocabulary node with a
+ * searched feature of kf1: the test is made for every one of them, whereas olf_search_for_triangulation makes it only for those within TH_LOW of a query,
+ * so this entry can refuse a pair the host form accepts.  The other pairs of the call are unaffected by either.
+ * n_pairs == 0 or n_frames == 0: nothing is written.  Contexts above 4096 features per frame: OLF_ERR_CAPACITY (16 index bits in the sort key of the
+ * FeatureVector stage); a NULL required pointer or a negative count: OLF_ERR_INVALID, before any launch.  Scratch: 12 bytes per (frame, feature). */
+int olf_search_for_triangulation_batch_dev(olf_ctx* ctx, const olf_voc* voc, const olf_track_batch* in, int n_frames, int n_pairs,
+                                           const int32_t* d_pairs, const float* d_F12, const float* d_Cw, int only_stereo, int check_orientation,
+                                           int levelsup, int32_t* d_matches12, int32_t* d_nmatches, void* stream);
+
 /* ---- the line half of tracking: Frame::isInFrustum_l, SearchLocalPointsAndLines' line half, the f2f line tracking (csrc/line_batch.hip) --------------------
  * Host forms first (host arithmetic, no device work, no context): they are the definition the device entries below equal, bit for bit.
  *

@@ -82,13 +82,6 @@ __global__ __launch_bounds__(256) void k_bow_sort_nodes(const int* __restrict__ 
 
 constexpr int BM_WAVES = 8;
 
-__device__ __forceinline__ int bm_lower_bound(const unsigned long long* a, int n, unsigned long long key)      // first position with a[p] >= key
-{
-    int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < key) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
 // (BM_WAVES waves per frame pair: the pair's ~100 shared nodes are claimed one at a time by whichever wave is free; the walk inside a node is serial, so the
 // kernel's time is the longest chain of nodes one wave ends up with: 4 waves 3.60 ms per 3071 pairs, 8 waves 3.07, 16 waves 4.72 -- profiles/r4at_bow_waves_ab.txt)
 __global__ __launch_bounds__(64 * BM_WAVES) void k_search_by_bow(const unsigned long long* __restrict__ sortedAll, const int* __restrict__ mAll, const olf_keypoint* __restrict__ kps,
@@ -190,18 +183,29 @@ __global__ __launch_bounds__(64 * BM_WAVES) void k_search_by_bow(const unsigned 
     if (threadIdx.x == 0) nmatches[p] = s_n;
 }
 
+// Frame::ComputeBoW's FeatureVector of n_frames frames: d_sorted[f][0 .. d_m[f]) = (node << 16 | index) ascending.  The stage olf_search_by_bow_batch_dev and
+// olf_search_for_triangulation_batch_dev (triangulation_batch.hip) share; cap <= 4096 is the caller's check (16 index bits, 32 KB of LDS for the sort).
+int launch_bow_feature_vectors(const uint8_t* slotDesc, const int* childOff, const int* slotNode, const double* nodeWeight, int nid_level, int n_frames,
+                               int img_stride, int cap, const uint8_t* d_desc, const int* d_counts, int* d_nodes, unsigned long long* d_sorted, int* d_m,
+                               hipStream_t s)
+{
+    int P = 64;
+    while (P < cap) P <<= 1;
+    hipLaunchKernelGGL(k_bow_descend_nodes, dim3((cap + 255) / 256, n_frames), dim3(256), 0, s, reinterpret_cast<const uint4*>(slotDesc), childOff, slotNode,
+                       nodeWeight, reinterpret_cast<const uint4*>(d_desc), d_counts, cap, img_stride, nid_level, d_nodes);
+    hipLaunchKernelGGL(k_bow_sort_nodes, dim3(n_frames), dim3(256), (size_t)P * 8, s, d_nodes, cap, P, d_sorted, d_m);
+    OLF_HIP_CHECK(hipGetLastError());
+    return OLF_OK;
+}
+
 int launch_search_by_bow_batch(const uint8_t* slotDesc, const int* childOff, const int* slotNode, const double* nodeWeight, int nid_level, int n_frames,
                                int img_stride, int cap, const olf_keypoint* d_kps, const uint8_t* d_desc, const int* d_counts, const uint8_t* d_mp_valid,
                                const uint8_t* d_mp_bad, float nnratio, int check_ori, int* d_nodes, unsigned long long* d_sorted, int* d_m, int* d_matches,
                                int* d_nmatches, hipStream_t s)
 {
     if (n_frames < 2) return OLF_OK;
-    int P = 64;
-    while (P < cap) P <<= 1;
     if (cap > 4096) { set_error("olf_search_by_bow_batch_dev: more than 4096 features per frame (the per-frame node sort runs in 32 KB of LDS)"); return OLF_ERR_CAPACITY; }
-    hipLaunchKernelGGL(k_bow_descend_nodes, dim3((cap + 255) / 256, n_frames), dim3(256), 0, s, reinterpret_cast<const uint4*>(slotDesc), childOff, slotNode,
-                       nodeWeight, reinterpret_cast<const uint4*>(d_desc), d_counts, cap, img_stride, nid_level, d_nodes);
-    hipLaunchKernelGGL(k_bow_sort_nodes, dim3(n_frames), dim3(256), (size_t)P * 8, s, d_nodes, cap, P, d_sorted, d_m);
+    OLF_TRY(launch_bow_feature_vectors(slotDesc, childOff, slotNode, nodeWeight, nid_level, n_frames, img_stride, cap, d_desc, d_counts, d_nodes, d_sorted, d_m, s));
     hipLaunchKernelGGL(k_search_by_bow, dim3(n_frames - 1), dim3(64 * BM_WAVES), (size_t)cap * 4 + ((cap + 3) & ~3), s, d_sorted, d_m, d_kps,
                        reinterpret_cast<const uint4*>(d_desc), d_counts, cap, img_stride, d_mp_valid, d_mp_bad, nnratio, check_ori, d_matches, d_nmatches);
     OLF_HIP_CHECK(hipGetLastError());

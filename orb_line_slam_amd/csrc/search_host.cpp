@@ -727,11 +727,9 @@ int olf_search_for_triangulation(olf_ctx* c, const olf_frame_view* kf1, const ol
     for (int i = 0; i < kf1->n; ++i) matches12[i] = -1;
     *nmatches = 0;
     // Compute epipole in second image (:666-676)
-    float cw[3], C2[3];
+    float cw[3], ex, ey;
     if (Cw) std::memcpy(cw, Cw, sizeof(cw)); else camera_centre(kf1->Tcw, cw);
-    rot_apply(kf2->Tcw, cw, 1.0f, C2);
-    const float invz = 1.0f / C2[2];
-    const float ex = kf2->fx * C2[0] * invz + kf2->cx, ey = kf2->fy * C2[1] * invz + kf2->cy;
+    tri_epipole(kf2->Tcw, cw, kf2->fx, kf2->fy, kf2->cx, kf2->cy, ex, ey);
     Batch q;
     bool oob = false;
     for_common_nodes(*kf1, *kf2, [&](int a, int b) {
@@ -766,20 +764,12 @@ int olf_search_for_triangulation(olf_ctx* c, const olf_frame_view* kf1, const ol
             if (dist > TH_LOW || dist > bestDist) continue;
             const olf_keypoint& kp2 = kf2->keys[idx2];
             if (kp2.octave < 0 || kp2.octave >= kf2->n_levels) { set_error("olf_search_for_triangulation: octave outside mvScaleFactors"); return OLF_ERR_INVALID; }
-            if (!bStereo1 && !bStereo2) {
-                const float distex = ex - kp2.x, distey = ey - kp2.y;
-                if (distex * distex + distey * distey < 100 * kf2->scale_factors[kp2.octave]) continue;
-            }
-            // CheckDistEpipolarLine (:142-161), mvLevelSigma2[l] = mvScaleFactor[l]^2
-            const float ea = kp1.x * F12[0] + kp1.y * F12[3] + F12[6];
-            const float eb = kp1.x * F12[1] + kp1.y * F12[4] + F12[7];
-            const float ec = kp1.x * F12[2] + kp1.y * F12[5] + F12[8];
-            const float num = ea * kp2.x + eb * kp2.y + ec;
-            const float den = ea * ea + eb * eb;
-            if (den == 0) continue;
-            const float dsqr = num * num / den;
-            const float sigma2 = kf2->scale_factors[kp2.octave] * kf2->scale_factors[kp2.octave];
-            if (dsqr < 3.84 * sigma2) { bestIdx2 = idx2; bestDist = dist; }
+            const float sf2 = kf2->scale_factors[kp2.octave];
+            if (!bStereo1 && !bStereo2 && tri_near_epipole(ex, ey, kp2.x, kp2.y, sf2)) continue;
+            // CheckDistEpipolarLine (:142-161): search_math.hpp
+            float l[3];
+            tri_epiline(F12, kp1.x, kp1.y, l);
+            if (tri_epiline_ok(l, kp2.x, kp2.y, sf2)) { bestIdx2 = idx2; bestDist = dist; }
         }
         if (bestIdx2 >= 0) {
             matches12[idx1] = bestIdx2;

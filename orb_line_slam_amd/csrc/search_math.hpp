@@ -1,5 +1,5 @@
-// search_math.hpp -- the arithmetic the host searches (search_host.cpp) and the batched device matchers (track_batch.hip, local_batch.hip, bow_match.hip)
-// both run: the cv::Mat products of convention C.12 and the rotation histogram of ORBmatcher.  One text for both sides; every file that includes it is
+// search_math.hpp -- the arithmetic the host searches (search_host.cpp) and the batched device matchers (track_batch.hip, local_batch.hip, bow_match.hip,
+// triangulation_batch.hip) both run: the cv::Mat products of convention C.12, the rotation histogram of ORBmatcher and the gate of SearchForTriangulation.  One text for both sides; every file that includes it is
 // built with -ffp-contract=off.
 #pragma once
 #include <cmath>
@@ -66,6 +66,48 @@ __host__ __device__ __forceinline__ bool line_moved(const olf_keyline& cur, floa
 }
 // mvDisparity_l[i2].first < 0 || .second < 0 (:1319, :990, :1979): a line without a stereo match takes no map line
 __host__ __device__ __forceinline__ bool line_is_mono(const float* ldisp, int i2) { return ldisp[2 * (size_t)i2] < 0 || ldisp[2 * (size_t)i2 + 1] < 0; }
+
+// a frame's FeatureVector as bow_match.hip sorts it, (node << 16 | feature index) ascending: the first position with a[p] >= key
+__host__ __device__ __forceinline__ int bm_lower_bound(const unsigned long long* a, int n, unsigned long long key)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < key) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+// The candidate gate of ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:659-825), one text for olf_search_for_triangulation (search_host.cpp) and
+// k_search_for_triangulation (triangulation_batch.hip).
+// The epipole in the second image (:666-676): C2 = R2w * Cw + t2w under C.12, invz = 1.0f / C2z as one float division, ex = fx * C2x * invz + cx.
+__host__ __device__ __forceinline__ void tri_epipole(const float* Tcw2, const float* Cw, float fx, float fy, float cx, float cy, float& ex, float& ey)
+{
+    float C2[3];
+    rot_apply(Tcw2, Cw, 1.0f, C2);
+    const float invz = f_div(1.0f, C2[2]);
+    ex = fx * C2[0] * invz + cx; ey = fy * C2[1] * invz + cy;
+}
+// distex * distex + distey * distey < 100 * pKF2->mvScaleFactors[kp2.octave] (:749-755, both features mono): the candidate lies too close to the epipole
+__host__ __device__ __forceinline__ bool tri_near_epipole(float ex, float ey, float x2, float y2, float sf)
+{
+    const float distex = ex - x2, distey = ey - y2;
+    return distex * distex + distey * distey < 100 * sf;
+}
+// ORBmatcher::CheckDistEpipolarLine (:142-161): the line l = x1^T F12 of key point 1 in image 2 (F12 row-major) ...
+__host__ __device__ __forceinline__ void tri_epiline(const float* F12, float x1, float y1, float* l)
+{
+    l[0] = x1 * F12[0] + y1 * F12[3] + F12[6];
+    l[1] = x1 * F12[1] + y1 * F12[4] + F12[7];
+    l[2] = x1 * F12[2] + y1 * F12[5] + F12[8];
+}
+// ... and the test of key point 2 against it: den == 0 fails, dsqr = num * num / den in float, dsqr < 3.84 * sigma2 in double, mvLevelSigma2[l] = mvScaleFactor[l]^2
+__host__ __device__ __forceinline__ bool tri_epiline_ok(const float* l, float x2, float y2, float sf)
+{
+    const float num = l[0] * x2 + l[1] * y2 + l[2];
+    const float den = l[0] * l[0] + l[1] * l[1];
+    if (den == 0) return false;
+    const float dsqr = f_div(num * num, den);
+    const float sigma2 = sf * sf;
+    return dsqr < 3.84 * sigma2;
+}
 
 // the rotation bin of a match (src/ORBmatcher.cc:1434-1441 and its siblings); angles outside [0, 360) give a bin outside [0, HISTO_LENGTH)
 __host__ __device__ __forceinline__ int rot_bin(float angle1, float angle2)

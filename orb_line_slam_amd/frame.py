@@ -202,6 +202,23 @@ class StereoFrontEnd:
                                                   bMono=bMono, checkOri=checkOri, img_stride=2, mp_valid=mp_valid, mp_obs=mp_obs, outlier=outlier,
                                                   mp_desc=mp_desc, d_th=d_th, match12=match12, out=out, context=self.ctx)
 
+    def search_for_triangulation_batch(self, voc, Tcw, pairs, F12, camera, Cw=None, mp_valid=None, bOnlyStereo=False, checkOri=True, levelsup=4, out=None):
+        """ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:659-825) for a list of pairs of the left frames of the last frames() call, on the
+        context's device buffers (olf_search_for_triangulation_batch_dev; nothing is downloaded).  voc: an ORBVocabulary; Tcw [n_pairs, 4, 4] float32
+        (numpy or device tensor), one per stereo pair; pairs int32 [n, 2] = (kf1, kf2) frame indices and F12 float32 [n, 3, 3] (numpy or device
+        tensors); camera = (fx, fy, cx, cy); mp_valid e.g. stereo_points_mask().  The other arguments and the result (matches12, nmatches: device
+        tensors over the listed pairs) are those of matcher.search_for_triangulation_batch."""
+        import torch
+        from . import matcher
+        fb, n = self._last_frames("search_for_triangulation_batch")
+        dev = lambda a, dt: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dt) if isinstance(a, np.ndarray) else a).cuda().contiguous()
+        Tcw = dev(Tcw, np.float32)
+        if tuple(Tcw.shape) != (n, 4, 4):
+            raise ValueError("search_for_triangulation_batch: Tcw has one 4 x 4 matrix per stereo pair of the last frames() call")
+        return matcher.search_for_triangulation_batch(voc, n, fb.kps, fb.desc, fb.counts, fb.uright, Tcw, dev(pairs, np.int32), dev(F12, np.float32), camera,
+                                                      Cw=dev(Cw, np.float32), mp_valid=mp_valid, bOnlyStereo=bOnlyStereo, checkOri=checkOri,
+                                                      levelsup=levelsup, img_stride=2, out=out, context=self.ctx)
+
     def search_local_map_batch(self, Tcw, local_map, camera, th=1.0, nnratio=0.8, viewingCosLimit=0.5, bounds=None, frame_mp=None, d_th=None, out=None):
         """The point half of Tracking::SearchLocalPointsAndLines (src/Tracking.cc:1877-1942) for the left frames of the last frames() call, on the
         context's device buffers: olf_frame_grid_dev, then olf_search_local_map_batch_dev -- nothing is downloaded.  Tcw [n_pairs, 4, 4] float32

@@ -382,6 +382,38 @@ def search_by_projection_batch(n_frames, kps, desc, counts, uright, cell_offsets
     return m, m12, n
 
 
+def search_for_triangulation_batch(voc, n_frames, kps, desc, counts, uright, Tcw, pairs, F12, camera, Cw=None, mp_valid=None, bOnlyStereo=False,
+                                   checkOri=True, levelsup=4, img_stride=2, out=None, context=None):
+    """ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, Cw) (src/ORBmatcher.cc:659-825; LocalMapping::CreateNewMapPoints,
+    src/LocalMapping.cc:268) for a list of key-frame pairs of a device-resident batch, Frame::ComputeBoW of every frame included:
+    olf_search_for_triangulation_batch_dev (include/orbline.h describes every array; csrc/triangulation_batch.hip).  voc: an ORBVocabulary.  The arrays
+    are torch device tensors (or raw device addresses): kps / desc / counts in the extractor's layout (frame j = image j * img_stride), uright and
+    mp_valid [n_frames, capacity], Tcw [n_frames, 4, 4]; pairs int32 [n_pairs, 2] = (kf1, kf2) frame indices; F12 float32 [n_pairs, 3, 3], used as
+    x1^T F12 x2; Cw float32 [n_pairs, 3] (None: kf1's camera centre from its Tcw); camera = (fx, fy, cx, cy).  mp_valid marks the features that hold a
+    map point -- the search takes the others -- so None searches nothing.  out = (matches12, nmatches): int32 tensors to write into (rows of refused
+    pairs keep what they hold); by default they are made here, filled with -1 and 0.  Runs on torch's current stream.
+    Returns (matches12 [n_pairs, capacity]: idx2 per idx1 or -1, nmatches [n_pairs]) as device tensors."""
+    import ctypes as C
+    import torch
+    ctx = _ctx(context)
+    n_pairs = int(pairs.shape[0])
+    tb = _lib.TrackBatchC()
+    tb.kps, tb.desc, tb.counts, tb.img_stride = _dev(kps, None, "kps"), _dev(desc, torch.uint8, "desc"), _dev(counts, torch.int32, "counts"), int(img_stride)
+    tb.uright, tb.Tcw, tb.mp_valid = _dev(uright, torch.float32, "uright"), _dev(Tcw, torch.float32, "Tcw"), _dev(mp_valid, torch.uint8, "mp_valid")
+    tb.fx, tb.fy, tb.cx, tb.cy = (float(v) for v in camera)
+    if tuple(pairs.shape) != (n_pairs, 2) or F12.numel() != 9 * n_pairs or (Cw is not None and Cw.numel() != 3 * n_pairs):
+        raise ValueError("search_for_triangulation_batch: pairs [n_pairs, 2], F12 [n_pairs, 3, 3], Cw [n_pairs, 3]")
+    if out is None:
+        out = (torch.full((n_pairs, ctx.orb_capacity), -1, dtype=torch.int32, device="cuda"), torch.zeros((n_pairs,), dtype=torch.int32, device="cuda"))
+    m, n = out
+    with _torch_stream() as s:
+        check(lib().olf_search_for_triangulation_batch_dev(ctx.handle, voc._h, C.byref(tb), int(n_frames), n_pairs, _dev(pairs, torch.int32, "pairs"),
+                                                           _dev(F12, torch.float32, "F12"), _dev(Cw, torch.float32, "Cw"), int(bool(bOnlyStereo)),
+                                                           int(bool(checkOri)), int(levelsup), _dev(m, torch.int32, "matches12"),
+                                                           _dev(n, torch.int32, "nmatches"), s), "olf_search_for_triangulation_batch_dev")
+    return out
+
+
 def unproject_stereo(n_frames, kps, counts, depth, camera, Twc, img_stride=2, out=None, context=None):
     """Frame::UnprojectStereo (src/Frame.cc:1073-1087) for every feature of n_frames device-resident frames: olf_unproject_stereo_dev.  kps / counts in
     the extractor's layout, depth [n_frames, capacity] (mvDepth), camera = (fx, fy, cx, cy), Twc [n_frames, 4, 4] camera-to-world (rows of mRwc | mOw).
