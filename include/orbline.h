@@ -589,6 +589,37 @@ int olf_search_for_triangulation_batch_dev(olf_ctx* ctx, const olf_voc* voc, con
                                            const int32_t* d_pairs, const float* d_F12, const float* d_Cw, int only_stereo, int check_orientation,
                                            int levelsup, int32_t* d_matches12, int32_t* d_nmatches, void* stream);
 
+/* ---- the search part of ORBmatcher::Fuse for a batch of key frames on the device (csrc/fuse_batch.hip) ------------------------------------------------
+ * int ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint*> &vpMapPoints, const float th) (src/ORBmatcher.cc:827-948), called per target key frame by
+ * LocalMapping::SearchInNeighbors (src/LocalMapping.cc:454-534, calls at :489 and :514), and int ORBmatcher::Fuse(KeyFrame *pKF, cv::Mat Scw,
+ * const vector<MapPoint*> &vpPoints, float th, vector<MapPoint*> &vpReplacePoint) (:977-1102), called per corrected key frame by
+ * LoopClosing::SearchAndFuse (src/LoopClosing.cc:605): for every key frame of a batch and every point of its list the most similar key point inside the
+ * projection window.  Results equal olf_fuse_search / olf_fuse_search_sim3 key frame by key frame; the map mutation that follows (:950-972, :1086-1099)
+ * stays the caller's (INTEGRATION.md says when a result goes stale).
+ * `in`: kps, desc, counts, img_stride, uright, the grids of olf_frame_grid_dev, Tcw, the calibration with mbf and the bounds are read (frame j = image
+ * j * img_stride; a count beyond the capacity is read as the capacity); mvScaleFactors and the PredictScale thresholds are the context's.
+ * `map`: the points and every key frame's list as entries, exactly as olf_search_local_map_batch_dev reads olf_local_map (list_offsets == NULL: every key
+ * frame sees all n_mp points -- all target key frames against the current key frame's points, all corrected key frames against mvpLoopMapPoints);
+ * world, normal, maxd, mind (unscaled), desc and bad are read, obs is not.
+ * d_frame_mp [n_frames][capacity] (or NULL: the key frames hold nothing): mvpMapPoints as indices into the map, negative = none.  An entry whose point the
+ * key frame holds is skipped: pMP->IsInKeyFrame(pKF) (:851) in the plain form, spAlreadyFound.count(pMP) with spAlreadyFound = pKF->GetMapPoints() (:992,
+ * :1007) in the Sim3 form; so is a bad point, in both.
+ * d_Scw: NULL gives the plain form -- the pose is in->Tcw, the stereo / mono chi-square gate is on, "nothing" is -1 / 256; [n_frames][16] (row-major)
+ * gives the Sim3 form -- the pose is decomposed as :985-989 does, there is no chi-square gate, "nothing" is -1 / INT_MAX, in->Tcw is not read.
+ * d_Ow [n_frames][3] = pKF->GetCameraCenter(), or NULL: -Rcw.t() * tcw of Tcw; plain form only, the Sim3 form ignores it.
+ * d_best_idx / d_best_dist: per entry, indexed like every per-entry array of olf_local_map; entries outside every list get the "nothing" pair.
+ * d_nfused [n_frames] (or NULL): the number of the frame's entries with best_idx >= 0 && best_dist <= TH_LOW (50) -- what Fuse would return before any
+ * map mutation; 0 without entries.
+ * Errors, before any launch: a NULL required pointer, a negative count, maxX <= minX or maxY <= minY: OLF_ERR_INVALID; contexts above OLF_GRID_MAX_KEYS:
+ * OLF_ERR_CAPACITY.  A list index or a d_frame_mp value outside the map is left out and sets bit 512 of the context's status word (olf_ctx_synchronize /
+ * olf_ctx_poll_status), as in olf_search_local_map_batch_dev.  In the plain form a candidate that passes the level gate with an octave outside the
+ * context's levels -- that can only be octave -1 under predicted level 0 -- is left out of its window and sets bit 256; every other candidate and entry is
+ * unaffected.  olf_fuse_search refuses the whole call there (OLF_ERR_INVALID): this entry answers for the rest of the batch.  n_frames == 0 writes nothing.
+ * Scratch: 16 bytes per entry, 64 bytes per key frame and, with d_frame_mp, one bit per (frame, map point). */
+int olf_fuse_search_batch_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const olf_local_map* map, const int32_t* d_frame_mp,
+                              const float* d_Scw, const float* d_Ow, float th, int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_nfused,
+                              void* stream);
+
 /* ---- the line half of tracking: Frame::isInFrustum_l, SearchLocalPointsAndLines' line half, the f2f line tracking (csrc/line_batch.hip) --------------------
  * Host forms first (host arithmetic, no device work, no context): they are the definition the device entries below equal, bit for bit.
  *

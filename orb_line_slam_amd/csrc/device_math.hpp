@@ -14,6 +14,7 @@
 //                     tests/test_device_math.py sweeps it against the box's libm.
 //  * ham256         : the 256-bit Hamming distance of every matcher (device only)
 #pragma once
+#include <math.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -33,6 +34,8 @@ OLF_HD float f_div(float a, float b) { return __fdiv_rn(a, b); }
 OLF_HD double d_mul(double a, double b) { return __dmul_rn(a, b); }
 OLF_HD double d_add(double a, double b) { return __dadd_rn(a, b); }
 OLF_HD double d_sub(double a, double b) { return __dsub_rn(a, b); }
+OLF_HD double d_div(double a, double b) { return __ddiv_rn(a, b); }
+OLF_HD double d_sqrt(double a) { return __dsqrt_rn(a); }
 #else   // host: the translation unit is compiled with -ffp-contract=off
 OLF_HD float f_mul(float a, float b) { return a * b; }
 OLF_HD float f_add(float a, float b) { return a + b; }
@@ -41,6 +44,8 @@ OLF_HD float f_div(float a, float b) { return a / b; }
 OLF_HD double d_mul(double a, double b) { return a * b; }
 OLF_HD double d_add(double a, double b) { return a + b; }
 OLF_HD double d_sub(double a, double b) { return a - b; }
+OLF_HD double d_div(double a, double b) { return a / b; }
+OLF_HD double d_sqrt(double a) { return sqrt(a); }
 #endif
 
 OLF_HD float dev_fastAtan2(float y, float x)

@@ -1,7 +1,8 @@
 // entry_lists.hpp -- how the per-entry arrays of a local map are indexed (olf_local_map / olf_local_line_map, include/orbline.h): with list_offsets, entry e
 // in [list_offsets[j], list_offsets[j + 1]) is item list_index[e] for frame j; without, entry e = j * n_items + i is item i for frame j.  The offsets are
-// device data: whatever they hold, a range stays inside [0, n_entries).
+// device data: whatever they hold, a range stays inside [0, n_entries).  Also the scatter of what a frame already holds into one bit per (frame, item).
 #pragma once
+#include <stdint.h>
 #include <hip/hip_runtime.h>
 
 namespace olf {
@@ -35,5 +36,16 @@ struct EntryLists {
         e = min(max(offsets[j + 1], b), n_entries);
     }
 };
+
+// One feature's item into its frame's held bitmap (one bit per item; held_row: the frame's (n_items + 31) / 32 words, zeroed before).  v is the feature's
+// entry of mvpMapPoints as an index into the map: negative = none; v >= n_items is left out and sets `bit` of *status; a bad item is dropped
+// from its feature.  Returns v where the frame holds a live item now, -1 otherwise.
+__device__ __forceinline__ int held_mark(int v, int n_items, const uint8_t* __restrict__ bad, unsigned* __restrict__ held_row, int* __restrict__ status, int bit)
+{
+    if (v >= n_items) { atomicOr(status, bit); return -1; }
+    if (v < 0 || bad[v]) return -1;
+    atomicOr(&held_row[v >> 5], 1u << (v & 31));
+    return v;
+}
 
 }  // namespace olf

@@ -18,6 +18,7 @@
 //                    the scan -- there is no capacity and no approximate case
 #include <algorithm>
 #include "grid_walk.hpp"
+#include "entry_lists.hpp"
 #include "device_math.hpp"
 #include "search_math.hpp"
 #include "staging.hpp"
@@ -115,12 +116,9 @@ __global__ __launch_bounds__(256) void k_local_held(LocalArgs A, unsigned* __res
     const int j = blockIdx.y, idx = blockIdx.x * 256 + threadIdx.x;
     bool blocked = false;
     if (idx < lb_count(A, j)) {
-        const int v = A.frame_mp[(size_t)j * A.cap + idx];
-        if (v >= A.map.n_mp) atomicOr(status, LB_STATUS_INDEX);
-        else if (v >= 0 && !A.map.bad[v]) {                          // (a bad point is dropped from its feature, src/Tracking.cc:1885-1888)
-            atomicOr(&held[(size_t)j * A.mpW + (v >> 5)], 1u << (v & 31));
-            blocked = blk0 && A.map.obs[v] != 0;
-        }
+        // (a bad point is dropped from its feature, src/Tracking.cc:1885-1888)
+        const int v = held_mark(A.frame_mp[(size_t)j * A.cap + idx], A.map.n_mp, A.map.bad, held + (size_t)j * A.mpW, status, LB_STATUS_INDEX);
+        blocked = v >= 0 && blk0 && A.map.obs[v] != 0;
     }
     const unsigned long long m = wave_vote(blocked);
     if (blk0 && (threadIdx.x & 63) == 0 && (idx >> 6) < A.capW) blk0[(size_t)j * A.capW + (idx >> 6)] = m;

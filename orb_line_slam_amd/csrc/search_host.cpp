@@ -415,17 +415,7 @@ void for_common_nodes(const olf_frame_view& A, const olf_frame_view& B, F&& f)
 
 bool bad_fv(const olf_frame_view* v) { return v->fv_n < 0 || (v->fv_n && (!v->fv_nodes || !v->fv_offsets || !v->fv_features)); }
 
-// alpha * R * v (+ t), cv::gemm.  transposed: R9 holds the transpose of the matrix the reference multiplies with .t() -> generic path
-void r3_apply(const float* R9, const float* v, const float* t3, float* out, double alpha = 1.0, bool transposed = false)
-{
-    for (int r = 0; r < 3; ++r) {
-        double acc = 0;
-        if (transposed) for (int k = 0; k < 3; ++k) acc += (double)R9[3 * r + k] * (double)v[k];
-        else acc = (double)dot3_small(R9 + 3 * r, v);
-        out[r] = (float)(alpha * acc + (t3 ? (double)t3[r] : 0.0));
-    }
-}
-
+// (r3_apply: search_math.hpp)
 // (predict_scale: predict_scale.hpp)
 float log_scale_factor(const olf_frame_view& f) { return olf::log_scale_factor(f.scale_factors, f.n_levels); }
 
@@ -805,30 +795,22 @@ int fuse_core(olf_ctx* c, const char* who, const olf_frame_view* kf, const float
     const Grid grid(*kf);
     if (!grid.ok) return bad_grid();
     Batch q;
-    struct Meta { float u, v, ur; int level; };
+    struct Meta { float uvr[3]; int level; };
     std::vector<Meta> meta;
     int taken = 0;
+    const float cam[5] = {kf->fx, kf->fy, kf->cx, kf->cy, kf->mbf}, bounds[4] = {kf->minX, kf->maxX, kf->minY, kf->maxY};
     for (int i = 0; i < n_mp; ++i) {
         if (best_idx) { best_idx[i] = -1; best_dist[i] = none_dist; }
         if (skip && skip[i]) continue;
-        const float* p3Dw = world + 3 * (size_t)i;
-        float p3Dc[3], u, v, invz;
-        r3_apply(Rcw9, p3Dw, tcw3, p3Dc);
-        if (!project_in_image(*kf, p3Dc, u, v, invz)) continue;
-        const float ur = u - kf->mbf * invz;
-        const float maxDistance = 1.2f * maxd[i], minDistance = 0.8f * mind[i];
-        float PO[3]; double nrm = 0, dot = 0;
-        for (int k = 0; k < 3; ++k) { PO[k] = p3Dw[k] - Ow3[k]; nrm += (double)PO[k] * (double)PO[k]; dot += (double)PO[k] * (double)normal[3 * (size_t)i + k]; }
-        const float dist3D = (float)std::sqrt(nrm);
-        // Depth must be inside the scale pyramid of the image
-        if (dist3D < minDistance || dist3D > maxDistance) continue;
-        // Viewing angle must be less than 60 deg
-        if (dot < 0.5 * dist3D) continue;
-        const int nPredictedLevel = predict_scale(maxd[i], dist3D, logSF, kf->n_levels);
-        const float radius = th * kf->scale_factors[nPredictedLevel];
-        if (!grid.area(u, v, radius, -1, -1, q.cand)) continue;
+        // the gates on the point (fuse_point_gate, search_math.hpp)
+        Meta m;
+        float dist3D;
+        if (!fuse_point_gate(Rcw9, tcw3, Ow3, world + 3 * (size_t)i, normal + 3 * (size_t)i, maxd[i], mind[i], cam, bounds, m.uvr, dist3D)) continue;
+        m.level = predict_scale(maxd[i], dist3D, logSF, kf->n_levels);
+        const float radius = th * kf->scale_factors[m.level];
+        if (!grid.area(m.uvr[0], m.uvr[1], radius, -1, -1, q.cand)) continue;
         q.add(i, desc + 32 * (size_t)i);
-        meta.push_back({u, v, ur, nPredictedLevel});
+        meta.push_back(m);
     }
     const int rc = q.run(c, kf->desc, kf->n);
     if (rc != OLF_OK) return rc;
@@ -840,21 +822,10 @@ int fuse_core(olf_ctx* c, const char* who, const olf_frame_view* kf, const float
             if (matched && matched[idx]) continue;
             const olf_keypoint& kp = kf->keys[idx];
             const int kpLevel = kp.octave;
-            if (kpLevel < m.level - 1 || kpLevel > m.level) continue;
+            if (!fuse_level_ok(kpLevel, m.level)) continue;
             if (stereo_gate) {
                 if (kpLevel < 0 || kpLevel >= kf->n_levels) { set_error(std::string(who) + ": octave outside mvScaleFactors"); return OLF_ERR_INVALID; }
-                const float sigma2 = kf->scale_factors[kpLevel] * kf->scale_factors[kpLevel];
-                const float invSigma2 = 1.0f / sigma2;                        // mvInvLevelSigma2, src/ORBextractor.cc:434-436
-                const float ex = m.u - kp.x, ey = m.v - kp.y;
-                if (kf->uright[idx] >= 0) {
-                    // Check reprojection error in stereo
-                    const float er = m.ur - kf->uright[idx];
-                    const float e2 = ex * ex + ey * ey + er * er;
-                    if (e2 * invSigma2 > 7.8) continue;
-                } else {
-                    const float e2 = ex * ex + ey * ey;
-                    if (e2 * invSigma2 > 5.99) continue;
-                }
+                if (!fuse_chi2_ok(m.uvr, kp.x, kp.y, kf->uright[idx], kf->scale_factors[kpLevel])) continue;
             }
             const int dist = q.dist[p];
             if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
@@ -866,18 +837,7 @@ int fuse_core(olf_ctx* c, const char* who, const olf_frame_view* kf, const float
     return OLF_OK;
 }
 
-// Decompose Scw (src/ORBmatcher.cc:301-305, :985-989): scw = sqrt(row0 . row0); Rcw = sRcw / scw, tcw = Scw.col(3) / scw (a cv::Mat divided by a
-// scalar is a scaling by the double 1/scw rounded to float); Ow = -Rcw.t() * tcw
-void sim3_decompose(const float* Scw, float* R, float* t, float* ow)
-{
-    double d = 0;
-    for (int k = 0; k < 3; ++k) d += (double)Scw[k] * (double)Scw[k];
-    const float scw = (float)std::sqrt(d);
-    const float inv = (float)(1.0 / (double)scw);
-    float Rt[9];
-    for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) { R[3 * r + k] = Scw[4 * r + k] * inv; Rt[3 * k + r] = R[3 * r + k]; } t[r] = Scw[4 * r + 3] * inv; }
-    r3_apply(Rt, t, nullptr, ow, -1.0, true);
-}
+// (sim3_decompose: search_math.hpp)
 }  // namespace
 
 extern "C" {

@@ -1,6 +1,6 @@
 // search_math.hpp -- the arithmetic the host searches (search_host.cpp) and the batched device matchers (track_batch.hip, local_batch.hip, bow_match.hip,
-// triangulation_batch.hip) both run: the cv::Mat products of convention C.12, the rotation histogram of ORBmatcher and the gate of SearchForTriangulation.  One text for both sides; every file that includes it is
-// built with -ffp-contract=off.
+// triangulation_batch.hip, fuse_batch.hip) both run: the cv::Mat products of convention C.12, the rotation histogram of ORBmatcher, the gate of
+// SearchForTriangulation and the gates of the two Fuse forms.  One text for both sides; every file that includes it is built with -ffp-contract=off.
 #pragma once
 #include <cmath>
 #include <hip/hip_runtime.h>
@@ -107,6 +107,88 @@ __host__ __device__ __forceinline__ bool tri_epiline_ok(const float* l, float x2
     const float dsqr = f_div(num * num, den);
     const float sigma2 = sf * sf;
     return dsqr < 3.84 * sigma2;
+}
+
+// alpha * R * v (+ t), cv::gemm on a 3x3 R9 (row-major).  transposed: R9 holds the transpose of the matrix the reference multiplies with .t() -> generic path
+__host__ __device__ __forceinline__ void r3_apply(const float* R9, const float* v, const float* t3, float* out, double alpha = 1.0, bool transposed = false)
+{
+    for (int r = 0; r < 3; ++r) {
+        double acc = 0;
+        if (transposed) for (int k = 0; k < 3; ++k) acc += (double)R9[3 * r + k] * (double)v[k];
+        else acc = (double)dot3_small(R9 + 3 * r, v);
+        out[r] = (float)(alpha * acc + (t3 ? (double)t3[r] : 0.0));
+    }
+}
+
+// The search part of the two ORBmatcher::Fuse forms (src/ORBmatcher.cc:827-948, :977-1102), one text for fuse_core (search_host.cpp) and the kernels of
+// fuse_batch.hip: the Sim3 decomposition, the gates on a map point, the gates on a key point of its window.
+// Decompose Scw (:301-305, :985-989): scw = sqrt(row0 . row0); Rcw = sRcw / scw, tcw = Scw.col(3) / scw (a cv::Mat divided by a scalar is a scaling by
+// the double 1/scw rounded to float); Ow = -Rcw.t() * tcw
+__host__ __device__ __forceinline__ void sim3_decompose(const float* Scw, float* R, float* t, float* ow)
+{
+    double d = 0;
+    for (int k = 0; k < 3; ++k) d += (double)Scw[k] * (double)Scw[k];
+    const float scw = (float)d_sqrt(d);
+    const float inv = (float)d_div(1.0, (double)scw);
+    float Rt[9];
+    for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) { R[3 * r + k] = Scw[4 * r + k] * inv; Rt[3 * k + r] = R[3 * r + k]; } t[r] = Scw[4 * r + 3] * inv; }
+    r3_apply(Rt, t, nullptr, ow, -1.0, true);
+}
+// A map point against a key frame (:855-894, :1011-1050): p3Dc = Rcw * p + tcw (C.12), the depth gate, invz = 1 / z (one rounding to float: the double
+// quotient rounded again gives the same float), x = p3Dc[0] * invz, u = fx * x + cx, KeyFrame::IsInImage (HALF-OPEN), ur = u - mbf * invz, the distance
+// interval, the 60 degree gate in double.  cam = fx, fy, cx, cy, mbf; bounds = mnMinX, mnMaxX, mnMinY, mnMaxY.  true: uvr = (u, v, ur) and dist3D are
+// written; the level is the caller's (predict_scale on the host, fuse_level below on the device).
+__host__ __device__ __forceinline__ bool fuse_point_gate(const float* Rcw9, const float* tcw3, const float* Ow3, const float* p3Dw, const float* normal,
+                                                         float maxd, float mind, const float* cam, const float* bounds, float* uvr, float& dist3D)
+{
+    float p3Dc[3];
+    r3_apply(Rcw9, p3Dw, tcw3, p3Dc);
+    // Depth must be positive
+    if (p3Dc[2] < 0.0f) return false;
+    const float invz = f_div(1.0f, p3Dc[2]);
+    const float x = p3Dc[0] * invz, y = p3Dc[1] * invz;
+    const float u = cam[0] * x + cam[2], v = cam[1] * y + cam[3];
+    // Point must be inside the image
+    if (!(u >= bounds[0] && u < bounds[1] && v >= bounds[2] && v < bounds[3])) return false;
+    const float ur = u - cam[4] * invz;
+    const float maxDistance = 1.2f * maxd, minDistance = 0.8f * mind;
+    float PO[3]; double nrm = 0, dot = 0;
+    for (int k = 0; k < 3; ++k) { PO[k] = p3Dw[k] - Ow3[k]; nrm += (double)PO[k] * (double)PO[k]; dot += (double)PO[k] * (double)normal[k]; }
+    dist3D = (float)d_sqrt(nrm);
+    // Depth must be inside the scale pyramid of the image
+    if (dist3D < minDistance || dist3D > maxDistance) return false;
+    // Viewing angle must be less than 60 deg
+    if (dot < 0.5 * dist3D) return false;
+    uvr[0] = u; uvr[1] = v; uvr[2] = ur;
+    return true;
+}
+// MapPoint::PredictScale from the table of olf_predict_scale_thresholds: the number of thresholds <= mfMaxDistance / dist3D
+__host__ __device__ __forceinline__ int fuse_level(float maxd, float dist3D, const float* thr, int nlevels)
+{
+    const float ratio = f_div(maxd, dist3D);
+    int lv = 0;
+    for (int k = 0; k + 1 < nlevels; ++k) lv += thr[k] <= ratio ? 1 : 0;
+    return lv;
+}
+// the level gate on a key point of the window (:905-908, :1061-1064)
+__host__ __device__ __forceinline__ bool fuse_level_ok(int kpLevel, int nPredictedLevel) { return !(kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel); }
+// the chi-square gate of the plain form (:910-933): invSigma2 = 1.0f / (sf * sf) (mvInvLevelSigma2, src/ORBextractor.cc:434-436), e2 summed in float left
+// to right, the product compared in double; a key point with mvuRight >= 0 -- 0 included -- takes the stereo test.  sf = mvScaleFactors[kpLevel]
+__host__ __device__ __forceinline__ bool fuse_chi2_ok(const float* uvr, float kpx, float kpy, float kpur, float sf)
+{
+    const float sigma2 = sf * sf;
+    const float invSigma2 = f_div(1.0f, sigma2);
+    const float ex = uvr[0] - kpx, ey = uvr[1] - kpy;
+    if (kpur >= 0) {
+        // Check reprojection error in stereo
+        const float er = uvr[2] - kpur;
+        const float e2 = ex * ex + ey * ey + er * er;
+        if (e2 * invSigma2 > 7.8) return false;
+    } else {
+        const float e2 = ex * ex + ey * ey;
+        if (e2 * invSigma2 > 5.99) return false;
+    }
+    return true;
 }
 
 // the rotation bin of a match (src/ORBmatcher.cc:1434-1441 and its siblings); angles outside [0, 360) give a bin outside [0, HISTO_LENGTH)

@@ -522,6 +522,34 @@ def search_local_map_batch(n_frames, kps, desc, counts, uright, cell_offsets, ce
     return out
 
 
+def fuse_search_batch(n_frames, kps, desc, counts, uright, cell_offsets, cell_index, Tcw, local_map, camera, bounds, th=3.0, Scw=None, Ow=None,
+                      frame_mp=None, img_stride=2, out=None, context=None):
+    """The search part of ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:827-948; LocalMapping::SearchInNeighbors, src/LocalMapping.cc:489,
+    :514) -- or, with Scw, of Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:977-1102; LoopClosing::SearchAndFuse, src/LoopClosing.cc:605) -- for every key
+    frame of a device-resident batch: olf_fuse_search_batch_dev (include/orbline.h describes every array; csrc/fuse_batch.hip).  The frame arrays are those
+    of search_local_map_batch; local_map: a LocalMapDev (obs is not read and may be None) whose lists, if any, are the points each key frame is searched
+    for; Scw float32 [n_frames, 4, 4]: the Sim3 poses (Tcw is then not read and may be None); Ow float32 [n_frames, 3]: GetCameraCenter() (None: from
+    Tcw; plain form only); frame_mp int32 [n_frames, capacity]: the key frames' mvpMapPoints as map indices (negative: none) -- a point its key frame
+    holds is skipped.  out = (best_idx, best_dist, nfused): int32 tensors to write into.  Runs on torch's current stream.
+    Returns (best_idx, best_dist) over the entries (LocalMapDev.n_entries; -1 / 256, or -1 / INT_MAX with Scw, where nothing was found) and nfused
+    [n_frames]: the entries per key frame with best_idx >= 0 and best_dist <= TH_LOW."""
+    import ctypes as C
+    import torch
+    ctx = _ctx(context)
+    tb = _track_batch_c(kps, desc, counts, img_stride, uright, cell_offsets, cell_index, Tcw, camera, bounds)
+    lm = local_map.c(n_frames)
+    if out is None:
+        ne = local_map.n_entries(n_frames)
+        out = (torch.full((ne,), -1, dtype=torch.int32, device="cuda"),
+               torch.full((ne,), 256 if Scw is None else INT_MAX, dtype=torch.int32, device="cuda"), torch.zeros((int(n_frames),), dtype=torch.int32, device="cuda"))
+    bi, bd, nf = out
+    with _torch_stream() as s:
+        check(lib().olf_fuse_search_batch_dev(ctx.handle, C.byref(tb), int(n_frames), C.byref(lm), _dev(frame_mp, torch.int32, "frame_mp"),
+                                              _dev(Scw, torch.float32, "Scw"), _dev(Ow, torch.float32, "Ow"), float(th), _dev(bi, torch.int32, "best_idx"),
+                                              _dev(bd, torch.int32, "best_dist"), _dev(nf, torch.int32, "nfused"), s), "olf_fuse_search_batch_dev")
+    return out
+
+
 class LocalLineMapDev:
     """olf_local_line_map (include/orbline.h): the map lines a batch of frames is matched against, as device tensors over n_ml lines -- world [n_ml, 6]
     float32 (GetWorldPos(): start, then end), desc [n_ml, 32] uint8, obs / bad [n_ml] uint8 -- and optionally every frame's mvpLocalMapLines as
