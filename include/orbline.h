@@ -589,6 +589,37 @@ int olf_search_for_triangulation_batch_dev(olf_ctx* ctx, const olf_voc* voc, con
                                            const int32_t* d_pairs, const float* d_F12, const float* d_Cw, int only_stereo, int check_orientation,
                                            int levelsup, int32_t* d_matches12, int32_t* d_nmatches, void* stream);
 
+/* ---- ORBmatcher::SearchByBoW for a list of key-frame pairs on the device, both overloads (csrc/bow_match.hip) ------------------------------------------
+ * The matcher of Tracking::TrackReferenceKeyFrame (src/Tracking.cc:963-970), Tracking::Relocalization (:2240-2261: one frame against every candidate key
+ * frame) and LoopClosing::ComputeSim3 (src/LoopClosing.cc:271: the current key frame against every loop candidate) for n_pairs pairs of the n_frames
+ * frames of a batch, Frame::ComputeBoW (src/Frame.cc:585-597) of every frame included: each frame's FeatureVector is built once per call, whatever the
+ * number of pairs it is part of (voc, levelsup: as olf_search_by_bow_batch_dev; 4 in the reference).
+ * `in`: only kps (angles), desc, counts, img_stride and mp_valid are read, everything else may be NULL or zero (frame j = image j * img_stride; a count
+ * beyond the capacity is read as the capacity).  mp_valid keeps its meaning, mvpMapPoints[i] != NULL (NULL: every feature holds one); d_mp_bad
+ * [n_frames][capacity] is isBad() of the held point (NULL: none is bad).  d_pairs [n_pairs][2] = (first, second) frame indices, any order, duplicates
+ * allowed, a frame in any number of pairs.
+ * form OLF_BOW_KF_FRAME: SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches) (src/ORBmatcher.cc:161-290), first = pKF, second = F.
+ * F starts without matches (:165) and its own mp_valid / bad flags are not read; a key-frame feature is searched when it holds a point that is not bad
+ * (:193-199); a feature of F that holds a match from this call is passed over (:211-212); accept iff bestDist1 <= TH_LOW and (float)bestDist1 <
+ * nnratio * (float)bestDist2 (:230-232).  Row p of d_matches [n_pairs][capacity] is indexed by the feature of F and holds the key-frame feature whose
+ * point it received (-1: none; -1 from N_F on).  With the pairs (j, j + 1) rows and counts equal olf_search_by_bow_batch_dev's.
+ * form OLF_BOW_KF_KF: SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (:524-657).  A feature of pKF1 is searched when it
+ * holds a good point (:558-564); a feature of pKF2 is a candidate when it holds a good point and is not yet in vbMatched2 (:578-582); accept iff
+ * bestDist1 < TH_LOW (strict, :600) and the same ratio test.  Row p is indexed by idx1 and holds idx2 or -1 (-1 from N1 on); the rotation histogram
+ * drops by idx1 (:640-652).  Results equal olf_search_by_bow_kf pair by pair.
+ * Both: d_nmatches [n_pairs] = the return values after the rotation check (ComputeThreeMaxima, only with check_orientation); on equal distances the
+ * earlier candidate of the reference's scan stays.  Results do not depend on scheduling.
+ * A pair whose index lies outside [0, n_frames), or with first == second, ends with nmatches = -1 and its row untouched, and sets bit 2048 of the context's
+ * status word (olf_ctx_synchronize / olf_ctx_poll_status report it), as in olf_search_for_triangulation_batch_dev; the other pairs are unaffected.
+ * Errors, before any launch: a NULL required pointer, a negative count, an unknown form or an empty vocabulary: OLF_ERR_INVALID; contexts above 4096
+ * features per frame: OLF_ERR_CAPACITY (16 index bits in the sort key of the FeatureVector stage).  n_pairs == 0 or n_frames == 0: nothing is written.
+ * Scratch: 12 bytes per (frame, feature).  The call does not synchronise. */
+#define OLF_BOW_KF_FRAME 0   /* SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches),  src/ORBmatcher.cc:161-290 */
+#define OLF_BOW_KF_KF    1   /* SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12), src/ORBmatcher.cc:524-657 */
+int olf_search_by_bow_pairs_dev(olf_ctx* ctx, const olf_voc* voc, const olf_track_batch* in, int n_frames, int n_pairs, const int32_t* d_pairs,
+                                const uint8_t* d_mp_bad, int form, float nnratio, int check_orientation, int levelsup,
+                                int32_t* d_matches, int32_t* d_nmatches, void* stream);
+
 /* ---- the search part of ORBmatcher::Fuse for a batch of key frames on the device (csrc/fuse_batch.hip) ------------------------------------------------
  * int ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint*> &vpMapPoints, const float th) (src/ORBmatcher.cc:827-948), called per target key frame by
  * LocalMapping::SearchInNeighbors (src/LocalMapping.cc:454-534, calls at :489 and :514), and int ORBmatcher::Fuse(KeyFrame *pKF, cv::Mat Scw,

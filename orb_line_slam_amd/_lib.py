@@ -232,6 +232,8 @@ def lib():
         L.olf_search_by_bow_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.olf_search_for_triangulation_batch_dev.argtypes = ([C.c_void_p, C.c_void_p, C.POINTER(TrackBatchC), C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 +
                                                              [C.c_void_p] * 3)
+        L.olf_search_by_bow_pairs_dev.argtypes = ([C.c_void_p, C.c_void_p, C.POINTER(TrackBatchC), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
+                                                   C.c_int, C.c_int] + [C.c_void_p] * 3)
         L.olf_fuse_search_batch_dev.argtypes = ([C.c_void_p, C.POINTER(TrackBatchC), C.c_int, C.POINTER(LocalMapC)] + [C.c_void_p] * 3 + [C.c_float] +
                                                 [C.c_void_p] * 4)
         L.olf_bow_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,

@@ -32,6 +32,8 @@ int launch_bow_feature_vectors(const uint8_t* slotDesc, const int* childOff, con
 int launch_search_for_triangulation_batch(const olf_track_batch& in, int n_frames, int cap, const float* sf, int nlevels, int n_pairs, const int* d_pairs,
                                           const float* d_F12, const float* d_Cw, int only_stereo, int check_ori, const unsigned long long* d_sorted,
                                           const int* d_m, int* d_status, int* d_matches12, int* d_nmatches, hipStream_t s);
+int launch_search_by_bow_pairs(const olf_track_batch& in, int n_frames, int cap, int n_pairs, const int* d_pairs, const uint8_t* d_mp_bad, int form, float nnratio,
+                               int check_ori, const unsigned long long* d_sorted, const int* d_m, int* d_status, int* d_matches, int* d_nmatches, hipStream_t s);
 }
 
 extern "C" {
@@ -239,6 +241,34 @@ int olf_search_for_triangulation_batch_dev(olf_ctx* c, const olf_voc* v, const o
                                        in->counts, d_nodes, d_sorted, d_m, s));
     return launch_search_for_triangulation_batch(*in, n_frames, cap, sf, nlevels, n_pairs, d_pairs, d_F12, d_Cw, only_stereo ? 1 : 0, check_orientation ? 1 : 0,
                                                  d_sorted, d_m, ctx_status(c), d_matches12, d_nmatches, s);
+}
+
+int olf_search_by_bow_pairs_dev(olf_ctx* c, const olf_voc* v, const olf_track_batch* in, int n_frames, int n_pairs, const int32_t* d_pairs,
+                                const uint8_t* d_mp_bad, int form, float nnratio, int check_orientation, int levelsup, int32_t* d_matches, int32_t* d_nmatches,
+                                void* stream)
+{
+    if (!c || !v || !in || n_frames < 0 || n_pairs < 0 || levelsup < 0 || !in->kps || !in->desc || !in->counts || in->img_stride < 1 ||
+        (form != OLF_BOW_KF_FRAME && form != OLF_BOW_KF_KF) || (n_pairs > 0 && (!d_pairs || !d_matches || !d_nmatches))) {
+        set_error("olf_search_by_bow_pairs_dev: bad argument"); return OLF_ERR_INVALID;
+    }
+    if (v->n_words == 0) { set_error("olf_search_by_bow_pairs_dev: empty vocabulary"); return OLF_ERR_INVALID; }
+    OLF_TRY(ctx_check_device(c, "olf_search_by_bow_pairs_dev"));
+    const int cap = olf_orb_capacity(c);
+    if (cap > 4096) {
+        set_error("olf_search_by_bow_pairs_dev: more than 4096 features per frame (the sort key of the per-frame node sort holds 16 index bits)");
+        return OLF_ERR_CAPACITY;
+    }
+    if (n_pairs == 0 || n_frames == 0) return OLF_OK;
+    int *d_nodes, *d_m; unsigned long long* d_sorted;
+    Carve k;
+    k.add(&d_nodes, (size_t)n_frames * cap); k.add(&d_sorted, (size_t)n_frames * cap); k.add(&d_m, n_frames);
+    OLF_TRY(k.bind(c, SCRATCH_BATCH));
+    hipStream_t s = ctx_stream(c, stream);
+    // every frame's FeatureVector once per call, whatever the number of pairs it is part of
+    OLF_TRY(launch_bow_feature_vectors(v->d_slotDesc, v->d_childOff, v->d_slotNode, v->d_nodeWeight, v->L - levelsup, n_frames, in->img_stride, cap, in->desc,
+                                       in->counts, d_nodes, d_sorted, d_m, s));
+    return launch_search_by_bow_pairs(*in, n_frames, cap, n_pairs, d_pairs, d_mp_bad, form, nnratio, check_orientation ? 1 : 0, d_sorted, d_m, ctx_status(c),
+                                      d_matches, d_nmatches, s);
 }
 
 int olf_bow_transform(olf_ctx* c, const olf_voc* v, const uint8_t* desc, int n, int levelsup, int32_t* bow_ids, double* bow_vals, int* n_bow,

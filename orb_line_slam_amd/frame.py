@@ -219,6 +219,18 @@ class StereoFrontEnd:
                                                       Cw=dev(Cw, np.float32), mp_valid=mp_valid, bOnlyStereo=bOnlyStereo, checkOri=checkOri,
                                                       levelsup=levelsup, img_stride=2, out=out, context=self.ctx)
 
+    def search_by_bow_pairs(self, voc, pairs, mp_valid=None, mp_bad=None, form=0, nnratio=0.7, checkOri=True, levelsup=4, out=None):
+        """ORBmatcher::SearchByBoW (src/ORBmatcher.cc:161-290, or :524-657 with form=matcher.BOW_KF_KF) for a list of pairs of the left frames of the
+        last frames() call, on the context's device buffers (olf_search_by_bow_pairs_dev; nothing is downloaded).  voc: an ORBVocabulary; pairs int32
+        [n, 2] = (first, second) frame indices (numpy or device tensor); mp_valid e.g. stereo_points_mask().  The other arguments and the result
+        (matches, nmatches: device tensors over the listed pairs) are those of matcher.search_by_bow_pairs."""
+        import torch
+        from . import matcher
+        fb, n = self._last_frames("search_by_bow_pairs")
+        pairs = torch.as_tensor(np.ascontiguousarray(pairs, np.int32) if isinstance(pairs, np.ndarray) else pairs).cuda().contiguous()
+        return matcher.search_by_bow_pairs(voc, n, fb.kps, fb.desc, fb.counts, pairs, mp_valid=mp_valid, mp_bad=mp_bad, form=form, nnratio=nnratio,
+                                           checkOri=checkOri, levelsup=levelsup, img_stride=2, out=out, context=self.ctx)
+
     def search_local_map_batch(self, Tcw, local_map, camera, th=1.0, nnratio=0.8, viewingCosLimit=0.5, bounds=None, frame_mp=None, d_th=None, out=None):
         """The point half of Tracking::SearchLocalPointsAndLines (src/Tracking.cc:1877-1942) for the left frames of the last frames() call, on the
         context's device buffers: olf_frame_grid_dev, then olf_search_local_map_batch_dev -- nothing is downloaded.  Tcw [n_pairs, 4, 4] float32

@@ -414,6 +414,39 @@ def search_for_triangulation_batch(voc, n_frames, kps, desc, counts, uright, Tcw
     return out
 
 
+BOW_KF_FRAME, BOW_KF_KF = 0, 1      # OLF_BOW_KF_FRAME, OLF_BOW_KF_KF (include/orbline.h): the two SearchByBoW overloads of search_by_bow_pairs
+
+
+def search_by_bow_pairs(voc, n_frames, kps, desc, counts, pairs, mp_valid=None, mp_bad=None, form=BOW_KF_FRAME, nnratio=0.7, checkOri=True, levelsup=4,
+                        img_stride=2, out=None, context=None):
+    """ORBmatcher::SearchByBoW for a list of pairs of a device-resident batch, Frame::ComputeBoW of every frame included: olf_search_by_bow_pairs_dev
+    (include/orbline.h describes every array; csrc/bow_match.hip).  form BOW_KF_FRAME: SearchByBoW(pKF, F, vpMapPointMatches) (src/ORBmatcher.cc:161-290;
+    Tracking::TrackReferenceKeyFrame, Tracking::Relocalization), pairs = (pKF, F); form BOW_KF_KF: SearchByBoW(pKF1, pKF2, vpMatches12) (:524-657;
+    LoopClosing::ComputeSim3), pairs = (pKF1, pKF2).  voc: an ORBVocabulary.  The arrays are torch device tensors (or raw device addresses): kps / desc /
+    counts in the extractor's layout (frame j = image j * img_stride), mp_valid and mp_bad uint8 [n_frames, capacity] (None: every feature holds a
+    point / no point is bad), pairs int32 [n_pairs, 2], any order, duplicates allowed.  out = (matches, nmatches): int32 tensors to write into (rows of
+    refused pairs keep what they hold); by default they are made here, filled with -1 and 0.  Runs on torch's current stream.
+    Returns (matches [n_pairs, capacity], nmatches [n_pairs]) as device tensors: row p is indexed by the feature of F and holds the pKF feature whose
+    point it received (BOW_KF_FRAME), or is indexed by idx1 and holds idx2 (BOW_KF_KF); -1 = none."""
+    import ctypes as C
+    import torch
+    ctx = _ctx(context)
+    n_pairs = int(pairs.shape[0])
+    if tuple(pairs.shape) != (n_pairs, 2):
+        raise ValueError("search_by_bow_pairs: pairs [n_pairs, 2]")
+    tb = _lib.TrackBatchC()
+    tb.kps, tb.desc, tb.counts, tb.img_stride = _dev(kps, None, "kps"), _dev(desc, torch.uint8, "desc"), _dev(counts, torch.int32, "counts"), int(img_stride)
+    tb.mp_valid = _dev(mp_valid, torch.uint8, "mp_valid")
+    if out is None:
+        out = (torch.full((n_pairs, ctx.orb_capacity), -1, dtype=torch.int32, device="cuda"), torch.zeros((n_pairs,), dtype=torch.int32, device="cuda"))
+    m, n = out
+    with _torch_stream() as s:
+        check(lib().olf_search_by_bow_pairs_dev(ctx.handle, voc._h, C.byref(tb), int(n_frames), n_pairs, _dev(pairs, torch.int32, "pairs"),
+                                                _dev(mp_bad, torch.uint8, "mp_bad"), int(form), float(nnratio), int(bool(checkOri)), int(levelsup),
+                                                _dev(m, torch.int32, "matches"), _dev(n, torch.int32, "nmatches"), s), "olf_search_by_bow_pairs_dev")
+    return out
+
+
 def unproject_stereo(n_frames, kps, counts, depth, camera, Twc, img_stride=2, out=None, context=None):
     """Frame::UnprojectStereo (src/Frame.cc:1073-1087) for every feature of n_frames device-resident frames: olf_unproject_stereo_dev.  kps / counts in
     the extractor's layout, depth [n_frames, capacity] (mvDepth), camera = (fx, fy, cx, cy), Twc [n_frames, 4, 4] camera-to-world (rows of mRwc | mOw).
