@@ -651,6 +651,36 @@ int olf_fuse_search_batch_dev(olf_ctx* ctx, const olf_track_batch* in, int n_fra
                               const float* d_Scw, const float* d_Ow, float th, int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_nfused,
                               void* stream);
 
+/* ---- ORBmatcher::SearchBySim3 for a list of key-frame pairs on the device (csrc/sim3_batch.hip) ---------------------------------------------------------
+ * int ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12, const float &s12, const cv::Mat &R12, const cv::Mat &t12,
+ * const float th) (src/ORBmatcher.cc:1104-1328), called per loop candidate by LoopClosing::ComputeSim3 (src/LoopClosing.cc:329) on the candidate's own
+ * copy of the matches (:319): n_pairs pairs of the n_frames key frames of a batch, each with its own similarity.  Results equal olf_search_by_sim3 pair by
+ * pair and do not depend on scheduling; INTEGRATION.md says why the candidates of one round are independent and when a row goes stale.
+ * `in`: kps, desc, counts, img_stride, the grids of olf_frame_grid_dev, Tcw, mp_world, mp_valid (NULL: every feature holds a point), mp_desc (NULL: the
+ * frame's own descriptors), fx, fy, cx, cy and the bounds are read (frame j = image j * img_stride; a count beyond the capacity is read as the capacity);
+ * mvScaleFactors and the PredictScale thresholds are the context's.
+ * d_mp_bad (or NULL: none is bad), d_mp_maxd, d_mp_mind [n_frames][capacity]: isBad(), mfMaxDistance and mfMinDistance of the point a feature holds, per
+ * feature like mp_world; the distances unscaled as in olf_local_map -- the search applies 1.2 and 0.8 (GetMaxDistanceInvariance, :1179-1180).
+ * d_pairs [n_pairs][2] = (kf1, kf2) frame indices, any order, duplicates allowed, a frame in any number of pairs and on either side.  d_s12 [n_pairs],
+ * d_R12 [n_pairs][9] row-major, d_t12 [n_pairs][3]: the similarity of each pair, as the Sim3Solver hands it over (:325-327).
+ * d_matches12 [n_pairs][capacity], in / out, the codes of olf_search_by_sim3: in -- -1 = NULL, >= 0 = pMP->GetIndexInKeyFrame(pKF2), -2 = a point pKF2
+ * does not observe; a value >= N2 marks feature i1 as matched and nothing in kf2 (:1141) and never indexes anything; out -- additionally the agreed
+ * matches.  Positions from N1 on are left as they are.
+ * d_vn_match1, d_vn_match2 [n_pairs][capacity] (either may be NULL: the row then lives in context scratch): vnMatch1 / vnMatch2, -1 from N on.
+ * d_nfound [n_pairs]: the return values.
+ * A pair whose index lies outside [0, n_frames), or with kf1 == kf2, ends with nfound = -1 and its three rows untouched, and sets bit 2048 of the context's
+ * status word (olf_ctx_synchronize / olf_ctx_poll_status report it), as in olf_search_for_triangulation_batch_dev and olf_search_by_bow_pairs_dev; the other
+ * pairs are unaffected.  A window candidate that passes the level gate with an octave outside the context's levels -- that can only be octave -1 under
+ * predicted level 0 -- is left out of its window and sets bit 256, as in olf_fuse_search_batch_dev (olf_search_by_sim3 takes it).
+ * Errors, before any launch: a NULL required pointer (the per-pair arrays only when n_pairs > 0), a negative count, maxX <= minX or maxY <= minY:
+ * OLF_ERR_INVALID; contexts above OLF_GRID_MAX_KEYS (or 2 * n_pairs * capacity beyond 2^31): OLF_ERR_CAPACITY.  n_pairs == 0 or n_frames == 0 writes
+ * nothing.  The call does not synchronise.
+ * Scratch: 128 bytes and one bit per feature of the capacity per pair, 12 bytes per (pair, direction, feature), and 4 bytes per (pair, feature) for each
+ * of d_vn_match1 / d_vn_match2 that is NULL. */
+int olf_search_by_sim3_pairs_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const uint8_t* d_mp_bad, const float* d_mp_maxd,
+                                 const float* d_mp_mind, int n_pairs, const int32_t* d_pairs, const float* d_s12, const float* d_R12, const float* d_t12,
+                                 float th, int32_t* d_matches12, int32_t* d_vn_match1, int32_t* d_vn_match2, int32_t* d_nfound, void* stream);
+
 /* ---- the line half of tracking: Frame::isInFrustum_l, SearchLocalPointsAndLines' line half, the f2f line tracking (csrc/line_batch.hip) --------------------
  * Host forms first (host arithmetic, no device work, no context): they are the definition the device entries below equal, bit for bit.
  *

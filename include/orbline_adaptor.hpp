@@ -354,6 +354,16 @@ public:
         olf_detail::check(olf_search_by_sim3(ctx, &KF1, &KF2, vpMatches12.data(), s12, R12, t12, th, v1.data(), v2.data(), &n), "olf_search_by_sim3");
         return n;
     }
+    // SearchBySim3 for callers that hold a device batch: the candidates of one LoopClosing::ComputeSim3 round as pairs (current, candidate), each with its
+    // own (s, R, t) -- olf_search_by_sim3_pairs_dev (include/orbline.h describes every array; all of them device pointers).  d_vpMatches12 is in / out as
+    // vpMatches12 above, one row per pair; d_nFound receives the return values.  Enqueued on `stream`, not synchronised.
+    void SearchBySim3(olf_ctx* ctx, const olf_track_batch& batch, int n_frames, const uint8_t* d_mp_bad, const float* d_mfMaxDistance,
+                      const float* d_mfMinDistance, int n_pairs, const int32_t* d_pairs, const float* d_s12, const float* d_R12, const float* d_t12, float th,
+                      int32_t* d_vpMatches12, int32_t* d_nFound, void* stream, int32_t* d_vnMatch1 = nullptr, int32_t* d_vnMatch2 = nullptr) const
+    {
+        olf_detail::check(olf_search_by_sim3_pairs_dev(ctx, &batch, n_frames, d_mp_bad, d_mfMaxDistance, d_mfMinDistance, n_pairs, d_pairs, d_s12, d_R12, d_t12,
+                                                       th, d_vpMatches12, d_vnMatch1, d_vnMatch2, d_nFound, stream), "olf_search_by_sim3_pairs_dev");
+    }
     float mfNNratio;
     bool mbCheckOrientation;
 };

@@ -418,16 +418,7 @@ bool bad_fv(const olf_frame_view* v) { return v->fv_n < 0 || (v->fv_n && (!v->fv
 // (r3_apply: search_math.hpp)
 // (predict_scale: predict_scale.hpp)
 float log_scale_factor(const olf_frame_view& f) { return olf::log_scale_factor(f.scale_factors, f.n_levels); }
-
-// pinhole projection + IsInImage (half-open, KeyFrame::IsInImage)
-bool project_in_image(const olf_frame_view& K, const float* p3Dc, float& u, float& v, float& invz)
-{
-    if (p3Dc[2] < 0.0f) return false;
-    invz = (float)(1.0 / p3Dc[2]);
-    const float x = p3Dc[0] * invz, y = p3Dc[1] * invz;
-    u = K.fx * x + K.cx; v = K.fy * y + K.cy;
-    return u >= K.minX && u < K.maxX && v >= K.minY && v < K.maxY;
-}
+// (sim3_pair_transforms, sim3_point_gate: search_math.hpp)
 }  // namespace
 
 extern "C" {
@@ -892,9 +883,7 @@ int olf_search_by_sim3(olf_ctx* c, const olf_frame_view* kf1, const olf_frame_vi
     const int N1 = kf1->n, N2 = kf2->n;
     // Transformation between cameras (:1123-1125)
     float sR12[9], sR21[9], t21[3];
-    const float inv = (float)(1.0 / (double)s12);
-    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) { sR12[3 * r + k] = s12 * R12[3 * r + k]; sR21[3 * r + k] = inv * R12[3 * k + r]; }
-    r3_apply(sR21, t12, nullptr, t21, -1.0);
+    sim3_pair_transforms(s12, R12, t12, sR12, sR21, t21);
     std::vector<uint8_t> already1((size_t)N1, 0), already2((size_t)N2, 0);
     for (int i = 0; i < N1; i++) {
         if (matches12[i] != -1) {
@@ -918,15 +907,11 @@ int olf_search_by_sim3(olf_ctx* c, const olf_frame_view* kf1, const olf_frame_vi
         for (int i = 0; i < src.n; ++i) {
             if (!src.mp_valid[i] || already[i]) continue;
             if (src.mp_bad[i]) continue;
-            float pa[3], pb[3], u, v, invz;
-            rot_apply(src.Tcw, src.mp_world + 3 * (size_t)i, 1.0f, pa);
-            r3_apply(sR, pa, t, pb);
-            if (!project_in_image(dst, pb, u, v, invz)) continue;
-            const float maxDistance = 1.2f * src.mp_maxd[i], minDistance = 0.8f * src.mp_mind[i];
-            double nrm = 0;
-            for (int k = 0; k < 3; ++k) nrm += (double)pb[k] * (double)pb[k];
-            const float dist3D = (float)std::sqrt(nrm);
-            if (dist3D < minDistance || dist3D > maxDistance) continue;
+            // (the projection and the gates on the point: sim3_point_gate, search_math.hpp)
+            const float cam[4] = {dst.fx, dst.fy, dst.cx, dst.cy}, bounds[4] = {dst.minX, dst.maxX, dst.minY, dst.maxY};
+            float uv[2], dist3D;
+            if (!sim3_point_gate(src.Tcw, src.mp_world + 3 * (size_t)i, sR, t, src.mp_maxd[i], src.mp_mind[i], cam, bounds, uv, dist3D)) continue;
+            const float u = uv[0], v = uv[1];
             const int nPredictedLevel = predict_scale(src.mp_maxd[i], dist3D, logSF, dst.n_levels);
             const float radius = th * dst.scale_factors[nPredictedLevel];
             if (!grid.area(u, v, radius, -1, -1, q.cand)) continue;

@@ -1,6 +1,7 @@
 // search_math.hpp -- the arithmetic the host searches (search_host.cpp) and the batched device matchers (track_batch.hip, local_batch.hip, bow_match.hip,
-// triangulation_batch.hip, fuse_batch.hip) both run: the cv::Mat products of convention C.12, the rotation histogram of ORBmatcher, the gate of
-// SearchForTriangulation and the gates of the two Fuse forms.  One text for both sides; every file that includes it is built with -ffp-contract=off.
+// triangulation_batch.hip, fuse_batch.hip, sim3_batch.hip) both run: the cv::Mat products of convention C.12, the rotation histogram of ORBmatcher, the
+// gate of SearchForTriangulation, the gates of the two Fuse forms and the transforms and point gate of SearchBySim3.  One text for both sides; every file
+// that includes it is built with -ffp-contract=off.
 #pragma once
 #include <cmath>
 #include <hip/hip_runtime.h>
@@ -188,6 +189,43 @@ __host__ __device__ __forceinline__ bool fuse_chi2_ok(const float* uvr, float kp
         const float e2 = ex * ex + ey * ey;
         if (e2 * invSigma2 > 5.99) return false;
     }
+    return true;
+}
+
+// ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1104-1328), one text for olf_search_by_sim3 (search_host.cpp) and the kernels of sim3_batch.hip.
+// Transformation between cameras (:1121-1123): sR12 = s12 * R12; sR21 = (1.0 / s12) * R12.t() -- the double reciprocal rounded to float scales the
+// transpose; t21 = -sR21 * t12 (a plain product, cv::gemm's small-matrix path, alpha = -1 applied in double).  All row-major.
+__host__ __device__ __forceinline__ void sim3_pair_transforms(float s12, const float* R12, const float* t12, float* sR12, float* sR21, float* t21)
+{
+    const float inv = (float)d_div(1.0, (double)s12);
+    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) { sR12[3 * r + k] = s12 * R12[3 * r + k]; sR21[3 * r + k] = inv * R12[3 * k + r]; }
+    r3_apply(sR21, t12, nullptr, t21, -1.0);
+}
+// A map point of the source key frame against the other one (:1160-1185, :1240-1265): p3Dc1 = Rsw * p3Dw + tsw (C.12), p3Dc2 = sR * p3Dc1 + t, the depth
+// gate (z == 0 fails through the infinite quotient), invz = 1.0 / z (the double quotient rounded to float), x = p3Dc2[0] * invz, u = fx * x + cx,
+// KeyFrame::IsInImage (HALF-OPEN), dist3D = cv::norm(p3Dc2) (a double sum, its double root, one rounding), the CLOSED distance interval.
+// Tsw = the source key frame's 4 x 4 pose; cam = fx, fy, cx, cy; bounds = mnMinX, mnMaxX, mnMinY, mnMaxY.  true: uv = (u, v) and dist3D are written;
+// the level is the caller's (predict_scale on the host, fuse_level on the device).
+__host__ __device__ __forceinline__ bool sim3_point_gate(const float* Tsw, const float* p3Dw, const float* sR9, const float* t3, float maxd, float mind,
+                                                         const float* cam, const float* bounds, float* uv, float& dist3D)
+{
+    float pa[3], pb[3];
+    rot_apply(Tsw, p3Dw, 1.0f, pa);
+    r3_apply(sR9, pa, t3, pb);
+    // Depth must be positive
+    if (pb[2] < 0.0f) return false;
+    const float invz = (float)d_div(1.0, (double)pb[2]);
+    const float x = pb[0] * invz, y = pb[1] * invz;
+    const float u = cam[0] * x + cam[2], v = cam[1] * y + cam[3];
+    // Point must be inside the image
+    if (!(u >= bounds[0] && u < bounds[1] && v >= bounds[2] && v < bounds[3])) return false;
+    const float maxDistance = 1.2f * maxd, minDistance = 0.8f * mind;
+    double nrm = 0;
+    for (int k = 0; k < 3; ++k) nrm += (double)pb[k] * (double)pb[k];
+    dist3D = (float)d_sqrt(nrm);
+    // Depth must be inside the scale invariance region
+    if (dist3D < minDistance || dist3D > maxDistance) return false;
+    uv[0] = u; uv[1] = v;
     return true;
 }
 

@@ -583,6 +583,44 @@ def fuse_search_batch(n_frames, kps, desc, counts, uright, cell_offsets, cell_in
     return out
 
 
+def search_by_sim3_pairs(n_frames, kps, desc, counts, cell_offsets, cell_index, Tcw, mp_world, mp_maxd, mp_mind, pairs, s12, R12, t12, camera, bounds,
+                         matches12=None, th=7.5, mp_valid=None, mp_bad=None, mp_desc=None, img_stride=2, out=None, context=None):
+    """ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cc:1104-1328; LoopClosing::ComputeSim3,
+    src/LoopClosing.cc:329) for a list of key-frame pairs of a device-resident batch, each with its own similarity: olf_search_by_sim3_pairs_dev
+    (include/orbline.h describes every array; csrc/sim3_batch.hip).  The arrays are torch device tensors (or raw device addresses): kps / desc / counts in
+    the extractor's layout (frame j = image j * img_stride), the grids of olf_frame_grid_dev, Tcw [n_frames, 4, 4]; per feature [n_frames, capacity]:
+    mp_world [.., 3], mp_maxd / mp_mind float32 (unscaled), mp_valid / mp_bad uint8 (None: every feature holds a point / no point is bad), mp_desc
+    [.., 32] uint8 (None: the frame's own descriptors); pairs int32 [n_pairs, 2] = (kf1, kf2), any order, duplicates allowed; s12 [n_pairs], R12
+    [n_pairs, 3, 3], t12 [n_pairs, 3] float32; camera = (fx, fy, cx, cy[, mbf]); bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY).  matches12 int32
+    [n_pairs, capacity] is vpMatches12 on entry (-1 NULL, >= 0 the index in kf2, -2 a point kf2 does not observe) and is written in place; None: no
+    pre-matches, a tensor of -1 is made here.  out = (vn_match1, vn_match2, nfound): int32 tensors to write into, either of the first two None to keep that
+    row in context scratch (rows of refused pairs keep what they hold); by default all three are made here.  Runs on torch's current stream.
+    Returns (matches12, vn_match1, vn_match2, nfound) as device tensors: row p of matches12 holds per feature of kf1 the agreed feature of kf2 beside the
+    pre-matches, vn_match1 / vn_match2 [n_pairs, capacity] the reference's vnMatch1 / vnMatch2 (-1 from N on), nfound [n_pairs] the return values."""
+    import ctypes as C
+    import torch
+    ctx = _ctx(context)
+    n_pairs, cap = int(pairs.shape[0]), ctx.orb_capacity
+    if tuple(pairs.shape) != (n_pairs, 2) or s12.numel() != n_pairs or R12.numel() != 9 * n_pairs or t12.numel() != 3 * n_pairs:
+        raise ValueError("search_by_sim3_pairs: pairs [n_pairs, 2], s12 [n_pairs], R12 [n_pairs, 3, 3], t12 [n_pairs, 3]")
+    cam = tuple(camera) + (0.0,) * (5 - len(tuple(camera)))
+    tb = _track_batch_c(kps, desc, counts, img_stride, None, cell_offsets, cell_index, Tcw, cam, bounds)
+    tb.mp_world, tb.mp_valid, tb.mp_desc = _dev(mp_world, torch.float32, "mp_world"), _dev(mp_valid, torch.uint8, "mp_valid"), _dev(mp_desc, torch.uint8, "mp_desc")
+    mk = lambda *shape: torch.full(shape, -1, dtype=torch.int32, device="cuda")
+    if matches12 is None:
+        matches12 = mk(n_pairs, cap)
+    if out is None:
+        out = (mk(n_pairs, cap), mk(n_pairs, cap), torch.zeros((n_pairs,), dtype=torch.int32, device="cuda"))
+    v1, v2, nf = out
+    with _torch_stream() as s:
+        check(lib().olf_search_by_sim3_pairs_dev(ctx.handle, C.byref(tb), int(n_frames), _dev(mp_bad, torch.uint8, "mp_bad"), _dev(mp_maxd, torch.float32, "mp_maxd"),
+                                                 _dev(mp_mind, torch.float32, "mp_mind"), n_pairs, _dev(pairs, torch.int32, "pairs"), _dev(s12, torch.float32, "s12"),
+                                                 _dev(R12, torch.float32, "R12"), _dev(t12, torch.float32, "t12"), float(th), _dev(matches12, torch.int32, "matches12"),
+                                                 _dev(v1, torch.int32, "vn_match1"), _dev(v2, torch.int32, "vn_match2"), _dev(nf, torch.int32, "nfound"), s),
+              "olf_search_by_sim3_pairs_dev")
+    return matches12, v1, v2, nf
+
+
 class LocalLineMapDev:
     """olf_local_line_map (include/orbline.h): the map lines a batch of frames is matched against, as device tensors over n_ml lines -- world [n_ml, 6]
     float32 (GetWorldPos(): start, then end), desc [n_ml, 32] uint8, obs / bad [n_ml] uint8 -- and optionally every frame's mvpLocalMapLines as

@@ -1,0 +1,256 @@
+"""GPU parity: olf_search_by_sim3_pairs_dev -- ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1104-1328, LoopClosing::ComputeSim3) for a list of key-frame
+pairs of a device-resident batch.  Every expectation comes from the CPU oracle pair by pair (oracle.search_by_sim3, tests/sim3_pairs_scenes.py);
+equality is exact on nfound, vn_match1, vn_match2 and matches12.  The scenarios assert, without a GPU, that their cases really occur."""
+import ctypes as C
+import numpy as np
+import pytest
+import orb_line_slam_amd as ola
+from orb_line_slam_amd import _lib, matcher
+from orb_line_slam_amd._lib import KEYPOINT_DTYPE, OLF_ERR_CAPACITY, lib
+import sim3_pairs_scenes as S
+from sim3_pairs_scenes import BOUNDS, CAM, FILL_M12, FILL_VN, f32
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import torch  # noqa: F401  (the device tensors below)
+    p = _lib.default_params()
+    p.orb.nfeatures = 1400
+    c = _lib.Context(p, S.W, S.H, 2)
+    assert c.orb_capacity >= 1400
+    sf = np.zeros(c.nlevels, np.float32)
+    lib().olf_orb_scale_tables(c.handle, sf.ctypes.data_as(C.c_void_p), None, None, None, None)
+    assert np.array_equal(sf, S.SF8)
+    yield c
+    c.close()
+
+
+def _up(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+class DeviceBatch:
+    """key frames as the device arrays of the entry; rows nothing may read hold values that would change a result"""
+
+    def __init__(self, ctx, kfs, img_stride=1, counts=None, own_desc=False):
+        import torch
+        self.ctx, self.n, self.st, cap = ctx, len(kfs), img_stride, ctx.orb_capacity
+        nf, ni = max(self.n, 1), max(self.n * img_stride, 1)
+        rng = np.random.default_rng(5)
+        kps = np.zeros((ni, cap), KEYPOINT_DTYPE)
+        kps["x"], kps["y"], kps["octave"] = 160.0, 120.0, 3       # images between the frames, features past the count: in the middle of every window
+        desc = rng.integers(0, 256, (ni, cap, 32), dtype=np.uint8)
+        cnt = np.full(ni, 17, np.int32)
+        Tcw = np.zeros((nf, 4, 4), f32)
+        world, valid, bad = np.full((nf, cap, 3), 5.0, f32), np.ones((nf, cap), np.uint8), np.zeros((nf, cap), np.uint8)
+        maxd, mind = np.full((nf, cap), 1e3, f32), np.full((nf, cap), 1e-3, f32)
+        mdesc = rng.integers(0, 256, (nf, cap, 32), dtype=np.uint8)
+        for j, kf in enumerate(kfs):
+            m = kf.N
+            assert m <= cap
+            kps[j * img_stride, :m], desc[j * img_stride, :m] = kf.mvKeysUn, kf.mDescriptors
+            cnt[j * img_stride] = m if counts is None or counts[j] is None else counts[j]
+            Tcw[j] = kf.mTcw
+            world[j, :m], valid[j, :m], bad[j, :m] = kf.mp_world, kf.mp_valid, kf.mp_bad
+            maxd[j, :m], mind[j, :m], mdesc[j, :m] = kf.mp_maxd, kf.mp_mind, kf.mp_desc
+        self.kps, self.desc, self.counts = _up(kps.view(np.uint8).reshape(ni, cap, 28)), _up(desc), _up(cnt)
+        self.Tcw, self.world, self.valid, self.bad = _up(Tcw), _up(world), _up(valid), _up(bad)
+        self.maxd, self.mind, self.mdesc = _up(maxd), _up(mind), None if own_desc else _up(mdesc)
+        self.offs = torch.full((nf, _lib.GRID_CELLS + 1), -5, dtype=torch.int32, device="cuda")
+        self.idx = torch.full((nf, cap), -5, dtype=torch.int32, device="cuda")
+        if self.n:
+            with matcher._torch_stream() as s:
+                _lib.check(lib().olf_frame_grid_dev(ctx.handle, self.n, img_stride, self.kps.data_ptr(), self.counts.data_ptr(), *BOUNDS, self.offs.data_ptr(),
+                                                    self.idx.data_ptr(), s), "olf_frame_grid_dev")
+
+    def rows(self, m12s):
+        """vpMatches12 on entry over the capacity: positions from N1 on hold a value the call must leave"""
+        cap = self.ctx.orb_capacity
+        out = np.full((max(len(m12s), 1), cap), FILL_M12, np.int32)
+        for p, m in enumerate(m12s):
+            out[p, :len(m)] = m
+        return out
+
+    def search(self, pairs, sims, m12s, th, vn=(True, True), n_frames=None):
+        """(matches12, vn_match1, vn_match2, nfound) as numpy arrays (None for a vn row left to the context); the outputs start from a fill no result equals"""
+        import torch
+        cap, n = self.ctx.orb_capacity, len(pairs)
+        m12 = _up(self.rows(m12s))
+        out = tuple(torch.full((max(n, 1), cap), FILL_VN, dtype=torch.int32, device="cuda") if v else None for v in vn) + \
+            (torch.full((max(n, 1),), FILL_VN, dtype=torch.int32, device="cuda"),)
+        pr = _up(np.asarray(pairs, np.int32).reshape(n, 2))
+        s12 = _up(np.asarray([x[0] for x in sims], f32).reshape(n))
+        R12 = _up(np.asarray([x[1] for x in sims], f32).reshape(n, 3, 3))
+        t12 = _up(np.asarray([x[2] for x in sims], f32).reshape(n, 3))
+        matcher.search_by_sim3_pairs(self.n if n_frames is None else n_frames, self.kps, self.desc, self.counts, self.offs, self.idx, self.Tcw, self.world,
+                                     self.maxd, self.mind, pr, s12, R12, t12, CAM, BOUNDS, matches12=m12, th=th, mp_valid=self.valid, mp_bad=self.bad,
+                                     mp_desc=self.mdesc, img_stride=self.st, out=out, context=self.ctx)
+        torch.cuda.synchronize()
+        return (m12.cpu().numpy(),) + tuple(None if o is None else o.cpu().numpy() for o in out)
+
+
+def assert_equal(res, exp, names=("matches12", "vn_match1", "vn_match2", "nfound")):
+    for r, e, name in zip(res, exp, names):
+        if r is not None:
+            r = r[:len(e)]
+            assert np.array_equal(r, e), (name, np.argwhere(r != e)[:10])
+
+
+@pytest.fixture(scope="module")
+def batch(ctx):
+    s = S.scenario_batch(ctx.orb_capacity)
+    return s, DeviceBatch(ctx, s.kfs)
+
+
+@pytest.mark.parametrize("th", [7.5, 10.0])
+def test_batch_parity(ctx, batch, th):
+    """1: seven key frames of (0, 1, 63, 64, 65, 300, 900) key points, fifteen pairs, s12 in {0.5, 1, 1.37, 2}, pre-matches of all three kinds"""
+    s, dev = batch
+    assert_equal(dev.search(s.pairs, s.sims, s.m12s, th), s.exp[th])
+    ctx.poll_status()
+
+
+def test_hand_built_gates(ctx):
+    """2: the image bounds, the depth gate, the distance interval to the ulp, the octave gate, TH_HIGH, the scan-order tie and a pre-match that takes a
+    key point of kf2 out of the second pass -- all cases as the pairs (2k, 2k + 1) of one call"""
+    cases = S.scenario_gates(ctx.orb_capacity)
+    kfs = [k for c in cases for k in (c.kf1, c.kf2)]
+    pairs = [(2 * k, 2 * k + 1) for k in range(len(cases))]
+    res = DeviceBatch(ctx, kfs).search(pairs, [S.IDENT] * len(cases), [c.m12 for c in cases], 7.5)
+    for k, c in enumerate(cases):
+        assert list(res[1][k, :c.kf1.N]) == c.want_v1, c.name
+        assert_equal(tuple(r[k:k + 1] for r in res), tuple(np.asarray(e)[None] for e in c.exp))
+    ctx.poll_status()
+
+
+def test_equals_the_host_form(ctx, batch):
+    """3: olf_search_by_sim3 on the same views, with its own grid and with a supplied one, gives the rows of the entry"""
+    s, dev = batch
+    res = dev.search(s.pairs, s.sims, s.m12s, 7.5)
+    m = ola.ORBmatcher(0.75, True, context=ctx)
+    for p in (0, 1, 3, 6, 9, 11):
+        a, b = s.pairs[p]
+        k1, k2 = s.kfs[a], s.kfs[b]
+        for supplied in (False, True):
+            for k in (k1, k2):
+                k.attach_grid(*(ola.assign_features_to_grid(k.mvKeysUn, BOUNDS, context=ctx) if supplied and k.N else (None, None)))
+            m12 = s.m12s[p].copy()
+            n, v1, v2 = m.SearchBySim3(k1, k2, m12, float(s.sims[p][0]), s.sims[p][1], s.sims[p][2], 7.5)
+            assert n == res[3][p] and np.array_equal(v1, res[1][p, :k1.N]) and np.array_equal(v2, res[2][p, :k2.N]) and np.array_equal(m12, res[0][p, :k1.N])
+        for k in (k1, k2):
+            k.attach_grid(None, None)
+    ctx.poll_status()
+
+
+def test_order_and_repetition(ctx, batch):
+    """4: the same call twice; the pair list permuted; vn_match1 / vn_match2 left to the context"""
+    s, dev = batch
+    first = dev.search(s.pairs, s.sims, s.m12s, 7.5)
+    assert_equal(first, s.exp[7.5])
+    assert_equal(dev.search(s.pairs, s.sims, s.m12s, 7.5), first)
+    perm = np.random.default_rng(4).permutation(len(s.pairs))
+    pick = lambda a: [a[i] for i in perm]
+    assert_equal(dev.search(pick(s.pairs), pick(s.sims), pick(s.m12s), 7.5), tuple(e[perm] for e in s.exp[7.5]))
+    for vn in ((False, False), (True, False), (False, True)):
+        res = dev.search(s.pairs, s.sims, s.m12s, 7.5, vn=vn)
+        assert res[1 + vn.index(False)] is None
+        assert_equal(res, s.exp[7.5])
+    ctx.poll_status()
+
+
+def test_malformed_pairs(ctx, batch):
+    """5: an index -1, an index n_frames and kf1 == kf2 give nfound = -1, leave their rows as they were and set bit 2048; the pairs beside them are not
+    affected; n_pairs == 0 writes nothing"""
+    s, dev = batch
+    bad = {2: (-1, 5), 5: (5, len(s.kfs)), 9: (6, 6)}
+    pairs = [bad.get(p, ab) for p, ab in enumerate(s.pairs)]
+    res = dev.search(pairs, s.sims, s.m12s, 7.5)
+    rows0 = dev.rows(s.m12s)
+    good = [p for p in range(len(pairs)) if p not in bad]
+    assert_equal(tuple(r[good] for r in res), tuple(e[good] for e in s.exp[7.5]))
+    for p in bad:
+        assert res[3][p] == -1
+        assert res[0][p].tobytes() == rows0[p].tobytes() and (res[1][p] == FILL_VN).all() and (res[2][p] == FILL_VN).all()
+    with pytest.raises(ola.OlfError) as e:
+        ctx.poll_status()
+    assert e.value.code == OLF_ERR_CAPACITY and "flags=2048" in str(e.value)
+    ctx.poll_status()                                         # reported once, then clear
+    res = dev.search([], [], [], 7.5)
+    assert (res[0] == FILL_M12).all() and (res[1] == FILL_VN).all() and (res[2] == FILL_VN).all() and (res[3] == FILL_VN).all()
+    res = dev.search(s.pairs[:2], s.sims[:2], s.m12s[:2], 7.5, n_frames=0)
+    assert (res[1] == FILL_VN).all() and (res[2] == FILL_VN).all() and (res[3] == FILL_VN).all() and res[0].tobytes() == dev.rows(s.m12s[:2]).tobytes()
+    ctx.poll_status()
+
+
+def test_octave_outside_the_levels(ctx, oracle):
+    """a candidate with octave -1 under predicted level 0 is left out of its window and sets bit 256; without it the second candidate wins"""
+    rng = np.random.default_rng(808)
+    pd = rng.integers(0, 256, (1, 32), dtype=np.uint8)
+    p = [[0.0, 0.0, 8.0]]
+    d2 = np.concatenate([pd, S.flip(rng, pd, 6)])
+    kfs = []
+    for keys2, desc2 in (([(160.5, 120.0, 0)], d2[1:]), ([(160.25, 120.0, -1), (160.5, 120.0, 0)], d2)):
+        kf1 = S.key_frame([(160.0, 120.0, 0)], pd)
+        S.hold(kf1, [0], p, [8 * 0.9], [1.0], pd)          # (a ratio below 1: level 0)
+        kfs += [kf1, S.key_frame(keys2, desc2)]
+    m12 = np.full(1, -1, np.int64)
+    exp = S.expect_pair(oracle, kfs[0], kfs[1], m12, S.IDENT, 7.5, ctx.orb_capacity)
+    assert exp[1][0] == 0
+    res = DeviceBatch(ctx, kfs).search([(0, 1), (2, 3)], [S.IDENT] * 2, [m12, m12], 7.5)
+    assert res[1][0, 0] == 0 and res[1][1, 0] == 1 and (res[2][:, :2] == -1).all() and list(res[3]) == [0, 0]
+    with pytest.raises(ola.OlfError) as e:
+        ctx.poll_status()
+    assert "flags=256" in str(e.value)
+    ctx.poll_status()
+
+
+def test_layout(ctx, batch, oracle):
+    """6: img_stride 1 and 2 give the same rows; a count above the capacity is read as the capacity and one below N cuts the key frame; the frames' own
+    descriptors stand in for a NULL mp_desc; a caller's stream is honoured"""
+    import torch
+    s, dev = batch
+    cap = ctx.orb_capacity
+    assert_equal(DeviceBatch(ctx, s.kfs, img_stride=2).search(s.pairs, s.sims, s.m12s, 7.5), s.exp[7.5])
+    # counts: the last key frame fills the capacity, so that the rows a count beyond it reaches are defined; key frame 4 is cut to 40
+    c = S.scenario_counts(cap)
+    assert_equal(DeviceBatch(ctx, c.kfs, img_stride=2, counts=c.counts).search(c.pairs, c.sims, c.m12s, 7.5), c.exp)
+    # mp_desc NULL: GetDescriptor() is the feature's own descriptor
+    own = []
+    for k in s.kfs:
+        k = S.cut(k, k.N)
+        k.mp_desc = k.mDescriptors.copy()
+        own.append(k)
+    sub = list(range(6))
+    pick = lambda a: [a[i] for i in sub]
+    exp_o = S.expect(oracle, own, pick(s.pairs), pick(s.m12s), pick(s.sims), 7.5, cap)
+    assert not np.array_equal(exp_o[1], s.exp[7.5][1][sub])
+    assert_equal(DeviceBatch(ctx, own, own_desc=True).search(pick(s.pairs), pick(s.sims), pick(s.m12s), 7.5), exp_o)
+    # a stream of the caller's
+    st = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(st):
+        res = dev.search(s.pairs, s.sims, s.m12s, 7.5)
+    assert_equal(res, s.exp[7.5])
+    ctx.poll_status()
+
+
+def test_capacity(ctx, batch):
+    """7: a context above OLF_GRID_MAX_KEYS is refused before anything is read"""
+    s, dev = batch
+    p = _lib.default_params()
+    p.orb.nfeatures = _lib.GRID_MAX_KEYS + 1
+    big = _lib.Context(p, S.W, S.H, 1)
+    try:
+        assert big.orb_capacity > _lib.GRID_MAX_KEYS
+        with pytest.raises(ola.OlfError) as e:
+            matcher.search_by_sim3_pairs(dev.n, dev.kps, dev.desc, dev.counts, dev.offs, dev.idx, dev.Tcw, dev.world, dev.maxd, dev.mind,
+                                         _up(np.asarray(s.pairs[:1], np.int32)), _up(np.ones(1, f32)), _up(np.eye(3, dtype=f32)[None]), _up(np.zeros((1, 3), f32)),
+                                         CAM, BOUNDS, matches12=_up(np.full((1, 8), -1, np.int32)), out=(None, None, _up(np.zeros(1, np.int32))), img_stride=1,
+                                         context=big)
+        assert e.value.code == OLF_ERR_CAPACITY
+    finally:
+        big.close()
+    ctx.poll_status()
