@@ -681,6 +681,65 @@ int olf_search_by_sim3_pairs_dev(olf_ctx* ctx, const olf_track_batch* in, int n_
                                  const float* d_mp_mind, int n_pairs, const int32_t* d_pairs, const float* d_s12, const float* d_R12, const float* d_t12,
                                  float th, int32_t* d_matches12, int32_t* d_vn_match1, int32_t* d_vn_match2, int32_t* d_nfound, void* stream);
 
+/* ---- the two key-frame forms of ORBmatcher::SearchByProjection for batches on the device (csrc/projection_batch.hip) ------------------------------------
+ * Both are ordered greedy searches -- a key point that takes a point is closed to every later point -- solved as olf_search_by_projection_batch_dev and
+ * olf_search_local_map_batch_dev solve theirs: at most 4 best candidates are kept per query, one wave walks the queries in the reference's order, and a
+ * query that runs out of kept candidates is recomputed on the spot.  There is no capacity to exceed, and results do not depend on scheduling.
+ *
+ * int ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint*> &sAlreadyFound, const float th, const int ORBdist)
+ * (src/ORBmatcher.cc:1620-1747), called up to twice per candidate key frame by Tracking::Relocalization (src/Tracking.cc:2322, :2336) on the candidate's
+ * own copy of the frame's map points and its own PnP pose: n_pairs pairs of the n_frames frames of a batch.  Rows and counts equal
+ * olf_search_by_projection_kf pair by pair; INTEGRATION.md says why the candidates of one round are independent, how the second call is formed from the
+ * first one's row and when a row goes stale.
+ * `in`: kps, desc, counts, img_stride, the grids of olf_frame_grid_dev (of the current frames), fx, fy, cx, cy and the bounds are read; mp_world, mp_valid
+ * (NULL: every feature holds a point) and mp_desc (NULL: the frame's own descriptors) in the key-frame role; Tcw only when d_Tcw is NULL; uright is not
+ * read (the reference has no mvuRight gate here).  Frame j = image j * img_stride; a count beyond the capacity is read as the capacity.  mvScaleFactors
+ * and the PredictScale thresholds are the context's.
+ * d_mp_bad (or NULL: none is bad), d_mp_maxd, d_mp_mind [n_frames][capacity]: as olf_search_by_sim3_pairs_dev (unscaled; the search applies 1.2 and 0.8,
+ * :1667-1668).  d_pairs [n_pairs][2] = (current frame, key frame), any order, duplicates allowed, a frame in any number of pairs and in either role.
+ * d_Tcw [n_pairs][16] (or NULL: in->Tcw of the current frame): the pose of the current frame under this candidate, row-major.
+ * d_cur_valid [n_pairs][capacity] (or NULL: none): CurrentFrame.mvpMapPoints[i2] != NULL on entry, per candidate -- such a feature is passed over (:1693).
+ * d_already_found [n_pairs][capacity] (or NULL: none): sAlreadyFound.count(pKF's i-th point), indexed by the key-frame feature (:1648).
+ * d_th [n_pairs] / d_orb_dist [n_pairs] (or NULL) replace th / orb_dist per pair; d_th[p] <= 0 skips the pair and leaves its row and count untouched.
+ * Arithmetic: x3Dc = Rcw * x3Dw + tcw under C.12 and invzc = (float)(1.0 / z) with NO sign test -- the reference has none, so a point behind the camera
+ * that lands inside the image is searched --, the CLOSED image bounds, dist3D from a double sum, the CLOSED interval [0.8f * mind, 1.2f * maxd], the
+ * window over the levels nPredictedLevel - 1 .. nPredictedLevel + 1 with radius th * mvScaleFactors[nPredictedLevel], the best distance with `<` in
+ * scan order, accepted iff <= orb_dist (a distance of 256 never registers), then with check_orientation the rotation histogram (ComputeThreeMaxima).
+ * d_matches [n_pairs][capacity]: row p is indexed by the current frame's feature and holds the key-frame feature whose point it received in this call,
+ * after the rotation check (-1: none; -1 from N on).  d_nmatches [n_pairs]: the return values.  The inputs are not written.
+ * A pair whose index lies outside [0, n_frames), or with both indices equal, ends with nmatches = -1 and its row untouched, and sets bit 2048 of the
+ * context's status word (olf_ctx_synchronize / olf_ctx_poll_status report it), as in the other pair entries; the other pairs are unaffected.
+ * Errors, before any launch: a NULL required pointer (the per-pair arrays only when n_pairs > 0), a negative count, img_stride < 1, maxX <= minX or
+ * maxY <= minY: OLF_ERR_INVALID; contexts above OLF_GRID_MAX_KEYS (or n_pairs * capacity beyond 2^31): OLF_ERR_CAPACITY.  n_pairs == 0 or
+ * n_frames == 0 writes nothing.  The call does not synchronise.  Scratch: 32 bytes per (pair, feature). */
+int olf_search_by_projection_kf_pairs_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const uint8_t* d_mp_bad, const float* d_mp_maxd,
+                                          const float* d_mp_mind, int n_pairs, const int32_t* d_pairs, const float* d_Tcw, const uint8_t* d_cur_valid,
+                                          const uint8_t* d_already_found, float th, const float* d_th, int orb_dist, const int32_t* d_orb_dist,
+                                          int check_orientation, int32_t* d_matches, int32_t* d_nmatches, void* stream);
+/* int ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*> &vpPoints, vector<MapPoint*> &vpMatched, int th)
+ * (src/ORBmatcher.cc:292-405), called by LoopClosing::ComputeSim3 (src/LoopClosing.cc:381), for every key frame of a batch against its list of points.
+ * Rows and counts equal olf_search_by_projection_sim3 key frame by key frame.
+ * `in`: kps, desc, counts, img_stride, the grids of olf_frame_grid_dev, the calibration with mbf and the bounds are read; Tcw and uright are not.
+ * `map`: the points and every key frame's list as entries, exactly as olf_fuse_search_batch_dev reads olf_local_map (list_offsets == NULL: every key
+ * frame sees all n_mp points in index order); world, normal, maxd, mind (unscaled), desc and bad are read, obs is not.
+ * d_Scw [n_frames][16] row-major: the Sim3 pose of each key frame, decomposed as :301-305 does.
+ * d_frame_matched [n_frames][capacity], in / out: vpMatched as map indices.  In: -1 = NULL; >= 0 = the map index held -- that key point is closed (:378)
+ * and that point is in spAlreadyFound (:307-308, :321); -2 (any other negative value) = a point outside the map -- that key point is closed only.  Out:
+ * additionally the map index each key point received in this call; nothing else is written, positions from N on are left as they are.
+ * d_th [n_frames] (or NULL) replaces th per key frame; an entry <= 0 skips the key frame and leaves its row and count untouched.  The reference's th is
+ * an int (10 at the call site); the radius is th * mvScaleFactors[nPredictedLevel] in float.
+ * Gates: those of olf_search_by_projection_sim3 -- the point gate of the Sim3 Fuse without a chi-square gate (depth, the HALF-OPEN image bounds, the
+ * distance interval, the 60 degree gate), the predicted level from the thresholds, the unrestricted window, the level gate per candidate
+ * (nPredictedLevel - 1 <= octave <= nPredictedLevel), the best distance with `<` in scan order, taken at once iff <= TH_LOW (50).  A candidate with
+ * octave -1 under predicted level 0 passes the level gate as in the host form; no status bit is set.
+ * d_nmatches [n_frames]: the return values (0 without entries).
+ * A list index or a d_frame_matched value >= n_mp is left out -- the value still closes its key point -- and sets bit 512 of the context's status word, as
+ * in olf_fuse_search_batch_dev.  Errors follow that entry: a NULL required pointer, a negative count, maxX <= minX or maxY <= minY: OLF_ERR_INVALID;
+ * contexts above OLF_GRID_MAX_KEYS (or 2^31 entries): OLF_ERR_CAPACITY; before any launch.  n_frames == 0 writes nothing.  The call does not synchronise.
+ * Scratch: 32 bytes per entry, 64 bytes per key frame and one bit per (key frame, map point). */
+int olf_search_by_projection_sim3_batch_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const olf_local_map* map, const float* d_Scw,
+                                            int32_t* d_frame_matched, float th, const float* d_th, int32_t* d_nmatches, void* stream);
+
 /* ---- the line half of tracking: Frame::isInFrustum_l, SearchLocalPointsAndLines' line half, the f2f line tracking (csrc/line_batch.hip) --------------------
  * Host forms first (host arithmetic, no device work, no context): they are the definition the device entries below equal, bit for bit.
  *

@@ -364,6 +364,27 @@ public:
         olf_detail::check(olf_search_by_sim3_pairs_dev(ctx, &batch, n_frames, d_mp_bad, d_mfMaxDistance, d_mfMinDistance, n_pairs, d_pairs, d_s12, d_R12, d_t12,
                                                        th, d_vpMatches12, d_vnMatch1, d_vnMatch2, d_nFound, stream), "olf_search_by_sim3_pairs_dev");
     }
+    // SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) for callers that hold a device batch: the candidates of one
+    // Tracking::Relocalization round as pairs (current frame, candidate key frame), each with its own pose, mvpMapPoints mask and sAlreadyFound --
+    // olf_search_by_projection_kf_pairs_dev (include/orbline.h describes every array; all of them device pointers).  Row p of d_matches is indexed by
+    // the current frame's feature; d_nmatches receives the return values.  Enqueued on `stream`, not synchronised.
+    void SearchByProjection(olf_ctx* ctx, const olf_track_batch& batch, int n_frames, const uint8_t* d_mp_bad, const float* d_mfMaxDistance,
+                            const float* d_mfMinDistance, int n_pairs, const int32_t* d_pairs, const float* d_Tcw, const uint8_t* d_mvpMapPoints,
+                            const uint8_t* d_sAlreadyFound, float th, int ORBdist, int32_t* d_matches, int32_t* d_nmatches, void* stream,
+                            const float* d_th = nullptr, const int32_t* d_ORBdist = nullptr) const
+    {
+        olf_detail::check(olf_search_by_projection_kf_pairs_dev(ctx, &batch, n_frames, d_mp_bad, d_mfMaxDistance, d_mfMinDistance, n_pairs, d_pairs, d_Tcw,
+                                                                d_mvpMapPoints, d_sAlreadyFound, th, d_th, ORBdist, d_ORBdist, mbCheckOrientation ? 1 : 0,
+                                                                d_matches, d_nmatches, stream), "olf_search_by_projection_kf_pairs_dev");
+    }
+    // SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) for callers that hold a device batch: every key frame against its list of `map` under its
+    // own Sim3 pose -- olf_search_by_projection_sim3_batch_dev.  d_vpMatched is in / out as map indices, one row per key frame.
+    void SearchByProjection(olf_ctx* ctx, const olf_track_batch& batch, int n_frames, const olf_local_map& map, const float* d_Scw, int32_t* d_vpMatched,
+                            float th, int32_t* d_nmatches, void* stream, const float* d_th = nullptr) const
+    {
+        olf_detail::check(olf_search_by_projection_sim3_batch_dev(ctx, &batch, n_frames, &map, d_Scw, d_vpMatched, th, d_th, d_nmatches, stream),
+                          "olf_search_by_projection_sim3_batch_dev");
+    }
     float mfNNratio;
     bool mbCheckOrientation;
 };

@@ -238,6 +238,10 @@ def lib():
                                                 [C.c_void_p] * 4)
         L.olf_search_by_sim3_pairs_dev.argtypes = ([C.c_void_p, C.POINTER(TrackBatchC), C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4 + [C.c_float] +
                                                    [C.c_void_p] * 5)
+        L.olf_search_by_projection_kf_pairs_dev.argtypes = ([C.c_void_p, C.POINTER(TrackBatchC), C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4 +
+                                                            [C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3)
+        L.olf_search_by_projection_sim3_batch_dev.argtypes = ([C.c_void_p, C.POINTER(TrackBatchC), C.c_int, C.POINTER(LocalMapC)] + [C.c_void_p] * 2 +
+                                                              [C.c_float] + [C.c_void_p] * 3)
         L.olf_bow_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.olf_profile_enable.argtypes = [C.c_void_p, C.c_int]

@@ -584,28 +584,17 @@ int olf_search_by_projection_kf(olf_ctx* c, const olf_frame_view* cur, const olf
     const Grid grid(*cur);
     if (!grid.ok) return bad_grid();
     Batch q;
+    const float cam[4] = {cur->fx, cur->fy, cur->cx, cur->cy}, bounds[4] = {cur->minX, cur->maxX, cur->minY, cur->maxY};
     for (int i = 0; i < kf->n; ++i) {
         if (!kf->mp_valid[i]) continue;
         if (kf->mp_bad[i] || (already_found && already_found[i])) continue;
-        const float* x3Dw = kf->mp_world + 3 * (size_t)i;
-        float x3Dc[3];
-        rot_apply(cur->Tcw, x3Dw, 1.0f, x3Dc);
-        const float xc = x3Dc[0], yc = x3Dc[1];
-        const float invzc = (float)(1.0 / x3Dc[2]);
-        const float u = cur->fx * xc * invzc + cur->cx, v = cur->fy * yc * invzc + cur->cy;
-        if (u < cur->minX || u > cur->maxX) continue;
-        if (v < cur->minY || v > cur->maxY) continue;
-        // Compute predicted scale level
-        double nrm = 0;
-        for (int k = 0; k < 3; ++k) { const float po = x3Dw[k] - Ow[k]; nrm += (double)po * (double)po; }
-        const float dist3D = (float)std::sqrt(nrm);
-        const float maxDistance = 1.2f * kf->mp_maxd[i], minDistance = 0.8f * kf->mp_mind[i];
-        // Depth must be inside the scale pyramid of the image
-        if (dist3D < minDistance || dist3D > maxDistance) continue;
+        // the gates on the point (reloc_point_gate, search_math.hpp)
+        float uv[2], dist3D;
+        if (!reloc_point_gate(cur->Tcw, Ow, kf->mp_world + 3 * (size_t)i, kf->mp_maxd[i], kf->mp_mind[i], cam, bounds, uv, dist3D)) continue;
         const int nPredictedLevel = predict_scale(kf->mp_maxd[i], dist3D, logSF, cur->n_levels);
         // Search in a window
         const float radius = th * cur->scale_factors[nPredictedLevel];
-        if (!grid.area(u, v, radius, nPredictedLevel - 1, nPredictedLevel + 1, q.cand)) continue;
+        if (!grid.area(uv[0], uv[1], radius, nPredictedLevel - 1, nPredictedLevel + 1, q.cand)) continue;
         q.add(i, kf->mp_desc + 32 * (size_t)i);
     }
     OLF_TRY(q.run(c, cur->desc, cur->n));

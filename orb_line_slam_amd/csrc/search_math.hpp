@@ -1,7 +1,7 @@
 // search_math.hpp -- the arithmetic the host searches (search_host.cpp) and the batched device matchers (track_batch.hip, local_batch.hip, bow_match.hip,
-// triangulation_batch.hip, fuse_batch.hip, sim3_batch.hip) both run: the cv::Mat products of convention C.12, the rotation histogram of ORBmatcher, the
-// gate of SearchForTriangulation, the gates of the two Fuse forms and the transforms and point gate of SearchBySim3.  One text for both sides; every file
-// that includes it is built with -ffp-contract=off.
+// triangulation_batch.hip, fuse_batch.hip, sim3_batch.hip, projection_batch.hip) both run: the cv::Mat products of convention C.12, the rotation histogram
+// of ORBmatcher, the gate of SearchForTriangulation, the gates of the two Fuse forms, the transforms and point gate of SearchBySim3 and the point gate of
+// the relocalisation SearchByProjection.  One text for both sides; every file that includes it is built with -ffp-contract=off.
 #pragma once
 #include <cmath>
 #include <hip/hip_runtime.h>
@@ -224,6 +224,34 @@ __host__ __device__ __forceinline__ bool sim3_point_gate(const float* Tsw, const
     for (int k = 0; k < 3; ++k) nrm += (double)pb[k] * (double)pb[k];
     dist3D = (float)d_sqrt(nrm);
     // Depth must be inside the scale invariance region
+    if (dist3D < minDistance || dist3D > maxDistance) return false;
+    uv[0] = u; uv[1] = v;
+    return true;
+}
+
+// ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1620-1747), one text for
+// olf_search_by_projection_kf (search_host.cpp) and k_proj_gate (projection_batch.hip).  A map point of the key frame against the current frame
+// (:1651-1677): x3Dc = Rcw * x3Dw + tcw (C.12), invzc = 1.0 / z (the double quotient rounded to float) WITH NO SIGN TEST -- the reference has none, so a
+// point behind the camera that lands inside the bounds goes on --, u = fx * xc * invzc + cx, the CLOSED image bounds, dist3D = cv::norm(x3Dw - Ow)
+// (float differences, a double sum, its double root, one rounding), the CLOSED distance interval.  cam = fx, fy, cx, cy; bounds = mnMinX, mnMaxX,
+// mnMinY, mnMaxY; Ow3 = -Rcw.t() * tcw (camera_centre).  true: uv = (u, v) and dist3D are written; the level is the caller's (predict_scale on the
+// host, fuse_level on the device).
+__host__ __device__ __forceinline__ bool reloc_point_gate(const float* Tcw, const float* Ow3, const float* x3Dw, float maxd, float mind, const float* cam,
+                                                          const float* bounds, float* uv, float& dist3D)
+{
+    float x3Dc[3];
+    rot_apply(Tcw, x3Dw, 1.0f, x3Dc);
+    const float xc = x3Dc[0], yc = x3Dc[1];
+    const float invzc = (float)d_div(1.0, (double)x3Dc[2]);
+    const float u = cam[0] * xc * invzc + cam[2], v = cam[1] * yc * invzc + cam[3];
+    if (u < bounds[0] || u > bounds[1]) return false;
+    if (v < bounds[2] || v > bounds[3]) return false;
+    // Compute predicted scale level
+    double nrm = 0;
+    for (int k = 0; k < 3; ++k) { const float po = x3Dw[k] - Ow3[k]; nrm += (double)po * (double)po; }
+    dist3D = (float)d_sqrt(nrm);
+    const float maxDistance = 1.2f * maxd, minDistance = 0.8f * mind;
+    // Depth must be inside the scale pyramid of the image
     if (dist3D < minDistance || dist3D > maxDistance) return false;
     uv[0] = u; uv[1] = v;
     return true;

@@ -621,6 +621,68 @@ def search_by_sim3_pairs(n_frames, kps, desc, counts, cell_offsets, cell_index, 
     return matches12, v1, v2, nf
 
 
+def search_by_projection_kf_pairs(n_frames, kps, desc, counts, cell_offsets, cell_index, mp_world, mp_maxd, mp_mind, pairs, camera, bounds, th=10.0,
+                                  ORBdist=100, Tcw=None, pair_Tcw=None, cur_valid=None, already_found=None, d_th=None, d_orb_dist=None, checkOri=True,
+                                  mp_valid=None, mp_bad=None, mp_desc=None, img_stride=2, out=None, context=None):
+    """ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1620-1747; Tracking::Relocalization,
+    src/Tracking.cc:2322, :2336) for a list of (current frame, key frame) pairs of a device-resident batch, each with its own pose:
+    olf_search_by_projection_kf_pairs_dev (include/orbline.h describes every array; csrc/projection_batch.hip).  The arrays are torch device tensors (or
+    raw device addresses): kps / desc / counts in the extractor's layout (frame j = image j * img_stride), the grids of olf_frame_grid_dev; per feature
+    [n_frames, capacity] in the key-frame role: mp_world [.., 3], mp_maxd / mp_mind float32 (unscaled), mp_valid / mp_bad uint8 (None: every feature
+    holds a point / no point is bad), mp_desc [.., 32] uint8 (None: the frame's own descriptors); pairs int32 [n_pairs, 2] = (current frame, key frame).
+    pair_Tcw float32 [n_pairs, 4, 4]: the current frame's pose under each candidate (None: Tcw [n_frames, 4, 4] of the current frame); cur_valid uint8
+    [n_pairs, capacity]: CurrentFrame.mvpMapPoints[i2] != NULL on entry; already_found uint8 [n_pairs, capacity]: sAlreadyFound over the key frame's
+    features; d_th float32 / d_orb_dist int32 [n_pairs]: per-pair values that replace th / ORBdist (d_th <= 0 skips a pair).  camera = (fx, fy, cx,
+    cy[, mbf]); bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY).  out = (matches, nmatches): int32 tensors to write into (rows of skipped and refused pairs
+    keep what they hold); by default they are made here, filled with -1 and 0.  Runs on torch's current stream.
+    Returns (matches [n_pairs, capacity], nmatches [n_pairs]) as device tensors: row p is indexed by the current frame's feature and holds the key-frame
+    feature whose point it received in this call (-1: none)."""
+    import ctypes as C
+    import torch
+    ctx = _ctx(context)
+    n_pairs, cap = int(pairs.shape[0]), ctx.orb_capacity
+    if tuple(pairs.shape) != (n_pairs, 2) or (pair_Tcw is not None and pair_Tcw.numel() != 16 * n_pairs):
+        raise ValueError("search_by_projection_kf_pairs: pairs [n_pairs, 2], pair_Tcw [n_pairs, 4, 4]")
+    cam = tuple(camera) + (0.0,) * (5 - len(tuple(camera)))
+    tb = _track_batch_c(kps, desc, counts, img_stride, None, cell_offsets, cell_index, Tcw, cam, bounds)
+    tb.mp_world, tb.mp_valid, tb.mp_desc = _dev(mp_world, torch.float32, "mp_world"), _dev(mp_valid, torch.uint8, "mp_valid"), _dev(mp_desc, torch.uint8, "mp_desc")
+    if out is None:
+        out = (torch.full((n_pairs, cap), -1, dtype=torch.int32, device="cuda"), torch.zeros((n_pairs,), dtype=torch.int32, device="cuda"))
+    m, n = out
+    with _torch_stream() as s:
+        check(lib().olf_search_by_projection_kf_pairs_dev(ctx.handle, C.byref(tb), int(n_frames), _dev(mp_bad, torch.uint8, "mp_bad"),
+                                                          _dev(mp_maxd, torch.float32, "mp_maxd"), _dev(mp_mind, torch.float32, "mp_mind"), n_pairs,
+                                                          _dev(pairs, torch.int32, "pairs"), _dev(pair_Tcw, torch.float32, "pair_Tcw"),
+                                                          _dev(cur_valid, torch.uint8, "cur_valid"), _dev(already_found, torch.uint8, "already_found"),
+                                                          float(th), _dev(d_th, torch.float32, "d_th"), int(ORBdist), _dev(d_orb_dist, torch.int32, "d_orb_dist"),
+                                                          int(bool(checkOri)), _dev(m, torch.int32, "matches"), _dev(n, torch.int32, "nmatches"), s),
+              "olf_search_by_projection_kf_pairs_dev")
+    return m, n
+
+
+def search_by_projection_sim3_batch(n_frames, kps, desc, counts, cell_offsets, cell_index, local_map, Scw, frame_matched, camera, bounds, th=10.0, d_th=None,
+                                    img_stride=2, out=None, context=None):
+    """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:292-405; LoopClosing::ComputeSim3, src/LoopClosing.cc:381) for
+    every key frame of a device-resident batch against its list of points: olf_search_by_projection_sim3_batch_dev (include/orbline.h describes every
+    array; csrc/projection_batch.hip).  The frame arrays are those of fuse_search_batch (uright and Tcw are not read); local_map: a LocalMapDev (obs is
+    not read and may be None) whose lists, if any, are the points each key frame is searched for; Scw float32 [n_frames, 4, 4]: the Sim3 poses;
+    frame_matched int32 [n_frames, capacity]: vpMatched as map indices, written in place (in: -1 NULL, >= 0 the map index held, -2 a point outside
+    the map; out: additionally the map index each key point received); d_th float32 [n_frames]: per-key-frame radii (<= 0 skips a key frame);
+    camera = (fx, fy, cx, cy, mbf).  out = nmatches: an int32 tensor [n_frames] to write into; by default made here, zero.  Runs on torch's current stream.
+    Returns (frame_matched, nmatches) as device tensors."""
+    import ctypes as C
+    import torch
+    ctx = _ctx(context)
+    tb = _track_batch_c(kps, desc, counts, img_stride, None, cell_offsets, cell_index, None, camera, bounds)
+    lm = local_map.c(n_frames)
+    n = torch.zeros((int(n_frames),), dtype=torch.int32, device="cuda") if out is None else out
+    with _torch_stream() as s:
+        check(lib().olf_search_by_projection_sim3_batch_dev(ctx.handle, C.byref(tb), int(n_frames), C.byref(lm), _dev(Scw, torch.float32, "Scw"),
+                                                            _dev(frame_matched, torch.int32, "frame_matched"), float(th), _dev(d_th, torch.float32, "d_th"),
+                                                            _dev(n, torch.int32, "nmatches"), s), "olf_search_by_projection_sim3_batch_dev")
+    return frame_matched, n
+
+
 class LocalLineMapDev:
     """olf_local_line_map (include/orbline.h): the map lines a batch of frames is matched against, as device tensors over n_ml lines -- world [n_ml, 6]
     float32 (GetWorldPos(): start, then end), desc [n_ml, 32] uint8, obs / bad [n_ml] uint8 -- and optionally every frame's mvpLocalMapLines as
