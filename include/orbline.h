@@ -38,7 +38,10 @@ int olf_default_params(olf_params* p);
 /* A context belongs to the device that is current when it is created (calls made with another device current return OLF_ERR_INVALID) and
  * to ONE host thread.  Its scratch buffers are shared by every call, so at most one stream may have work of a context in flight at a time:
  * the *_dev entry points accept any stream, but work enqueued on a second stream must be ordered after the first (event / synchronise) by
- * the caller. */
+ * the caller.
+ * Image size: at most 4131 pixels wide and high (FAST candidates are packed with 12 bits per coordinate relative to the 16-pixel border, and the largest
+ * coordinate is the side - 36), and large enough that every pyramid level keeps 62 x 62 pixels; anything else is OLF_ERR_INVALID, before any device allocation or
+ * launch, and olf_last_error() names which limit was missed. */
 int  olf_ctx_create(const olf_params* p, int width, int height, int max_images, olf_ctx** out);
 void olf_ctx_destroy(olf_ctx* ctx);
 /* Capacity overflows (more corners / key points / segments than a fixed-size device buffer holds) are never silent: the blocking

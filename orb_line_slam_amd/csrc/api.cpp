@@ -224,6 +224,7 @@ int olf_ctx_create(const olf_params* p, int width, int height, int max_images, o
     int rc = c->orb.build(p->orb, width, height);
     if (rc != OLF_OK) {
         set_error(rc == OLF_ERR_CAPACITY ? "olf_ctx_create: more than 32760 key points on one pyramid level (nfeatures too large for this scale factor / level count)"
+                  : (width > kMaxOrbSide || height > kMaxOrbSide) ? "olf_ctx_create: image wider or higher than 4131 pixels (FAST candidates are packed with 12 bits per coordinate)"
                                          : "olf_ctx_create: image size / ORB parameters not supported (every pyramid level needs at least 62 x 62 pixels and a landscape cell grid)");
         delete c; return rc;
     }

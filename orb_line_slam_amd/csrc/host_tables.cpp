@@ -91,6 +91,7 @@ int OrbHostTables::build(const olf_orb_params& p, int W, int H)
 {
     const int nlevels = p.nlevels;
     if (nlevels < 1 || nlevels > OLF_MAX_LEVELS || p.nfeatures < 1 || !(p.scale_factor > 1.0f)) return OLF_ERR_INVALID;
+    if (W > kMaxOrbSide || H > kMaxOrbSide) return OLF_ERR_INVALID;      // the packed candidate word holds 12 bits per coordinate (olf_internal.hpp)
     const double scaleFactor = p.scale_factor;   // the member is a double (include/ORBextractor.h:103)
     sf.assign(nlevels, 1.f); sigma2.assign(nlevels, 1.f); inv_sf.resize(nlevels); inv_sigma2.resize(nlevels);
     for (int i = 1; i < nlevels; ++i) {
@@ -117,6 +118,10 @@ int OrbHostTables::build(const olf_orb_params& p, int W, int H)
     g.nlevels = nlevels; g.W = W; g.H = H; g.in_pitch = W;
     g.iniTh = std::min(std::max(p.ini_th_fast, 1), 255);
     g.minTh = std::min(std::max(p.min_th_fast, 1), 255);
+    // iniThFAST < minThFAST (both are free keys of the settings file): a cell keeps every corner that reaches iniThFAST, because the retry at minThFAST
+    // (src/ORBextractor.cc:811-818) finds nothing where the first pass found nothing.  k_fast_score keeps what reaches minTh, k_cells_sort then drops what is
+    // below iniTh in a cell that has a corner at iniTh: with minTh = iniTh that is the reference's result.
+    g.minTh = std::min(g.minTh, g.iniTh);
     {
         int v, v0, vmax = cv_floor(kHalfPatch * std::sqrt(2.f) / 2 + 1);
         int vmin = cv_ceil(kHalfPatch * std::sqrt(2.f) / 2);

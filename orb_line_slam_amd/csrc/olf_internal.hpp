@@ -101,6 +101,10 @@ __device__ __forceinline__ bool wave_bit(unsigned long long m) { return __builti
 constexpr int kEdge = 19;          // EDGE_THRESHOLD   src/ORBextractor.cc:76
 constexpr int kMinBorder = 16;     // EDGE_THRESHOLD-3 src/ORBextractor.cc:775
 constexpr int kHalfPatch = 15;     // HALF_PATCH_SIZE  src/ORBextractor.cc:75
+// A FAST candidate is one 32-bit word, 12 bits per coordinate relative to kMinBorder and 8 of score (k_fast_score, k_cells_sort, k_octree, k_describe): the
+// largest coordinate of a level, side - 2 * kMinBorder - 4, must not exceed 4095.  Level 0 is the largest level; a larger image is refused at context creation.
+constexpr int kMaxOrbSide = 4095 + 2 * kMinBorder + 4;
+static_assert(kMaxOrbSide == 4131, "olf_ctx_create's message and include/orbline.h state this limit");
 
 // Geometry of one pyramid level; identical for every image of the context.
 struct LevelGeom {
