@@ -825,6 +825,77 @@ int olf_track_lines_batch_dev(olf_ctx* ctx, const olf_line_batch* in, int n_fram
  * ceiling bench.py reports next to the specification's 8 TB/s */
 int olf_debug_copy_bandwidth(olf_ctx* ctx, size_t bytes, int reps, double* gbytes_per_s);
 
+/* ---- place recognition: KeyFrameDatabase (src/KeyFrameDatabase.cc) and TemplatedVocabulary::score with L1 scoring -------------------------------
+ * A database holds the BoW vectors of its key frames for the point and (optionally) the line vocabulary.  A key frame is a SLOT: olf_kfdb_add hands out
+ * 0, 1, 2, ... in the order of the add calls, a slot is never reused until olf_kfdb_clear and an erased slot stays as an empty column of the tables.  The
+ * slot order stands for two orders of the reference: the insertion order of a word's posting list (mvInvertedFile[w].push_back, :51-54) and the address
+ * order of the std::set the WithLine forms iterate (:307, :582; DESIGN 2, convention C.15).
+ * The data-parallel part (common-word counts, smallest common word and L1 scores of Q queries against every slot) runs on the device; the sequential,
+ * stateful part (thresholds, covisibility accumulation, the per-key-frame members mRelocScore / mRelocScore_l / mRelocScore_pl that survive a query) is
+ * host code behind olf_kfdb_select.
+ * Limits (OLF_ERR_CAPACITY, checked before anything is launched): OLF_KFDB_MAX_WORDS words per BoW vector, OLF_KFDB_MAX_SLOTS slots,
+ * OLF_KFDB_MAX_CELLS = Q x slots table entries per call, 2^31 - 1 words in a database per vocabulary. */
+#define OLF_KFDB_MAX_WORDS 4096
+#define OLF_KFDB_MAX_SLOTS (1 << 20)
+#define OLF_KFDB_MAX_CELLS (1 << 26)
+#define OLF_SCORING_L1_NORM 0                  /* DBoW2::ScoringType, Thirdparty/DBoW2/DBoW2/BowVector.h:45-53 */
+#define OLF_KFDB_LOOP            0             /* DetectLoopCandidates                    src/KeyFrameDatabase.cc:107-228 */
+#define OLF_KFDB_LOOP_LINE       1             /* DetectLoopCandidatesWithLine            :230-400 */
+#define OLF_KFDB_RELOC           2             /* DetectRelocalizationCandidates          :402-512 */
+#define OLF_KFDB_RELOC_LINE      3             /* DetectRelocalizationCandidatesWithLine  :514-667 */
+typedef struct olf_kfdb olf_kfdb;
+/* n BoW vectors as CSR: vector i is ids / vals [off[i], off[i + 1]), ids ascending and distinct (a DBoW2::BowVector is a std::map) */
+typedef struct olf_bow_csr { const int32_t* off; const int32_t* ids; const double* vals; } olf_bow_csr;
+/* one vocabulary's tables, [n_queries][n_slots] row-major: common = number of common words (mnLoopWords / mnRelocWords as the walk :117-135 leaves them
+ * for a key frame that is not connected), first = the smallest common word id or -1 (the walk's first encounter), score = L1Scoring::score(query, slot)
+ * (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68) bit for bit where common > 0 and -0.0 elsewhere */
+typedef struct olf_kfdb_tables { int32_t* common; int32_t* first; double* score; } olf_kfdb_tables;
+
+/* KeyFrameDatabase::KeyFrameDatabase (:33-44).  n_words_p / n_words_l: the vocabularies' sizes; n_words_l == 0: no line vocabulary, the WithLine forms
+ * return empty lists (:232, :516).  A scoring other than OLF_SCORING_L1_NORM (what both of the reference's vocabularies use): OLF_ERR_INVALID.  ctx may be
+ * NULL: such a database keeps no device copy and serves add / erase / clear / size / select / state only. */
+int olf_kfdb_create(olf_ctx* ctx, int n_words_p, int n_words_l, int scoring_p, int scoring_l, olf_kfdb** out);
+void olf_kfdb_destroy(olf_kfdb* db);
+/* KeyFrameDatabase::add (:46-55): the key frame's mBowVec and mBowVec_l as host arrays (ids ascending, distinct, in [0, n_words)); *slot: its slot.
+ * Must not overlap a tables call of the same database that is still running (the device arrays may move). */
+int olf_kfdb_add(olf_kfdb* db, const int32_t* ids_p, const double* vals_p, int n_p, const int32_t* ids_l, const double* vals_l, int n_l, int32_t* slot);
+/* KeyFrameDatabase::erase (:57-90): the slot becomes an empty column.  Erasing an erased slot is a no-op; the per-slot state stays (it is the key frame's). */
+int olf_kfdb_erase(olf_kfdb* db, int32_t slot);
+/* KeyFrameDatabase::clear (:92-98); the slot numbers start again at 0, the per-slot state and the query id bounds are reset */
+int olf_kfdb_clear(olf_kfdb* db);
+/* *n_slots: slots handed out since the last clear (the row length of the tables); *n_live: those not erased */
+int olf_kfdb_size(const olf_kfdb* db, int32_t* n_slots, int32_t* n_live);
+/* the members that survive a query, [n_slots] each (NULL: not wanted): mRelocScore, mRelocScore_l, mRelocScore_pl; 0 until written (src/KeyFrame.cc:35-37) */
+int olf_kfdb_state(const olf_kfdb* db, float* reloc_score, float* reloc_score_l, float* reloc_score_pl);
+/* The walks :117-135, :246-284, :410-425, :528-560 without the connected-key-frame test, and mpVoc->score (:164, :334-335, :452, :605-606), for n_queries
+ * queries against every slot.  qp / ql: the queries' mBowVec / mBowVec_l; off are HOST arrays [n_queries + 1] (the limits are checked from them), ids and
+ * vals device arrays.  d_tp / d_tl: device tables [n_queries][n_slots].  ql and d_tl may be NULL (both or neither): the line tables are not computed.
+ * Enqueued on `stream` (NULL: the context's own); no synchronise. */
+int olf_kfdb_tables_dev(olf_kfdb* db, int n_queries, const olf_bow_csr* qp, const olf_bow_csr* ql, const olf_kfdb_tables* d_tp, const olf_kfdb_tables* d_tl,
+                        void* stream);
+/* The rest of the four Detect members for n_queries queries, one after the other in list order (query q + 1 sees the state query q left).  Host only.
+ * form: OLF_KFDB_*.  query_ids: pKF->mnId / F->mnId, > 0 and strictly greater than any id an earlier query of the same family (loop, relocalisation) of
+ * this database had, else OLF_ERR_INVALID with nothing changed.  np, nl [n_queries]: N and N_l (WithLine forms; else NULL).  min_score [n_queries]
+ * (loop forms; else NULL).  conn_off [n_queries + 1] / conn_slots: GetConnectedKeyFrames() of each query as slots (loop forms; NULL: none; values
+ * outside [0, n_slots) are key frames outside the database and ignored).  nb_off [n_slots + 1] / nb_slots: GetBestCovisibilityKeyFrames(10) of every
+ * slot in order, a negative value = a neighbour that is not in the database (skipped); values >= n_slots: OLF_ERR_INVALID.  n_slots must be the
+ * database's.  tp, tl: host copies of the tables (tl NULL in the plain forms).  Out: cand_off [n_queries + 1] and cand_slots [cand_capacity], the
+ * candidates of each query in the reference's order; more than cand_capacity candidates: OLF_ERR_CAPACITY with nothing changed. */
+int olf_kfdb_select(olf_kfdb* db, int form, int n_queries, const int64_t* query_ids, const int32_t* np, const int32_t* nl, const float* min_score,
+                    const int32_t* conn_off, const int32_t* conn_slots, const int32_t* nb_off, const int32_t* nb_slots, int n_slots,
+                    const olf_kfdb_tables* tp, const olf_kfdb_tables* tl, int32_t* cand_off, int32_t* cand_slots, int cand_capacity);
+/* tables, download, select: every pointer a host pointer (qp->off included); the arguments of the two entries above */
+int olf_kfdb_detect(olf_kfdb* db, int form, int n_queries, const int64_t* query_ids, const olf_bow_csr* qp, const olf_bow_csr* ql, const int32_t* np,
+                    const int32_t* nl, const float* min_score, const int32_t* conn_off, const int32_t* conn_slots, const int32_t* nb_off,
+                    const int32_t* nb_slots, int32_t* cand_off, int32_t* cand_slots, int cand_capacity);
+/* The minScore loop of LoopClosing::DetectLoop (src/LoopClosing.cc:126-144): d_score[i] = L1Scoring::score(a_i, b_i) for n_pairs pairs d_pairs [n_pairs][2]
+ * (device).  b_i is a slot of the database's vocabulary `line` (0 points, 1 lines); a_i is a slot too when d_queries is NULL, else vector a_i of the
+ * n_queries device vectors d_queries (off a DEVICE array here).  A pair with an index out of range scores NaN. */
+int olf_bow_score_pairs_dev(olf_kfdb* db, int line, int n_pairs, const int32_t* d_pairs, const olf_bow_csr* d_queries, int n_queries, double* d_score,
+                            void* stream);
+/* TemplatedVocabulary::score (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1199-1203) with L1 scoring for two host vectors, on the device */
+int olf_bow_score(olf_ctx* ctx, const int32_t* ids_a, const double* vals_a, int n_a, const int32_t* ids_b, const double* vals_b, int n_b, double* score);
+
 #ifdef __cplusplus
 }
 #endif

@@ -436,6 +436,19 @@ public:
         for (int a = 0; a < nf; ++a)
             fv.insert(fv.end(), typename FeatVec::value_type(nodes[a], typename FeatVec::mapped_type(idx.begin() + offs[a], idx.begin() + offs[a + 1])));
     }
+    // double score(const BowVector& a, const BowVector& b) const, :1199-1203, with L1 scoring (ScoringObject.cpp:23-68; the only scoring built)
+    template <class BowVec>
+    double score(olf_ctx* ctx, const BowVec& a, const BowVec& b) const
+    {
+        std::vector<int32_t> ia, ib;
+        std::vector<double> va, vb;
+        for (typename BowVec::const_iterator it = a.begin(); it != a.end(); ++it) { ia.push_back((int32_t)it->first); va.push_back(it->second); }
+        for (typename BowVec::const_iterator it = b.begin(); it != b.end(); ++it) { ib.push_back((int32_t)it->first); vb.push_back(it->second); }
+        double s = 0;
+        olf_detail::check(olf_bow_score(ctx, ia.data(), va.data(), (int)ia.size(), ib.data(), vb.data(), (int)ib.size(), &s), "olf_bow_score");
+        return s;
+    }
+    int scoring() const { int sc = 0; return voc_ && olf_voc_info(voc_, nullptr, nullptr, &sc, nullptr, nullptr, nullptr) == OLF_OK ? sc : 0; }
     olf_voc* handle() const { return voc_; }
 private:
     olf_voc* voc_;

@@ -10,6 +10,7 @@
 //   GridStructure / GridWindow / getLineCoords                                       include/gridStructure.h:33-58
 //   StereoFrameFeatures(frame, imLeft, imRight)  = the feature part of Frame::Frame  src/Frame.cc:164-171,199-207
 //   FrameGrid(frame)                             = AssignFeaturesToGrid()            src/Frame.cc:215            (:334-349)
+//   KeyFrameDatabaseOf<KeyFrame, Frame>          = KeyFrameDatabase                  include/KeyFrameDatabase.h:60-98 (add, erase, clear, the four Detect members)
 //   and every other ORBmatcher call of the reference: SearchByProjection(cur, pKF, sFound, th, ORBdist) Tracking.cc:2322,2336;
 //   SearchForTriangulation LocalMapping.cc:268; Fuse(pKF, vpMapPoints[, th]) LocalMapping.cc:489,514; SearchByBoW(pKF1, pKF2, vpMatches12)
 //   LoopClosing.cc:271; SearchBySim3 LoopClosing.cc:329; SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) LoopClosing.cc:381;
@@ -30,6 +31,7 @@
 #include <set>
 #include <unordered_set>
 #include <limits>
+#include <mutex>
 #include <type_traits>
 #include "orbline_adaptor.hpp"
 
@@ -692,5 +694,101 @@ void StereoFrameFeatures(FrameT& F, const MatT& imLeft, const MatT& imRight, con
         for (int c = 0; c < 3; ++c) F.mvle_l[i][c] = lle[3 * i + c];
     }
 }
+
+// ---- class KeyFrameDatabase (include/KeyFrameDatabase.h:60-98, src/KeyFrameDatabase.cc) ---------------------------------------------------------------
+// The reference's member signatures over the reference's own types; inside the reference tree
+//     typedef KeyFrameDatabaseOf<KeyFrame, Frame> KeyFrameDatabase;
+// takes the place of the class.  Reads of a key frame / frame: mBowVec, mBowVec_l, mnId, N, N_l, GetConnectedKeyFrames(), GetBestCovisibilityKeyFrames(10) --
+// the members the reference's functions read; the covisibility graph and isBad() stay with the caller's classes.  The per-key-frame members the reference
+// writes (mnLoopQuery .. mRelocScore_pl) are kept inside the database instead (per slot), so a key frame that is erased and added again starts from the
+// constructor's zeros.  Query ids (pKF->mnId, F->mnId) must be > 0 and increase within a family, as the reference's counters make them; anything else
+// throws.  The object owns a context and serialises its members with a mutex, as the reference's mMutex does.
+template <class KeyFrameT, class FrameT>
+class KeyFrameDatabaseOf {
+public:
+    explicit KeyFrameDatabaseOf(const ORBVocabulary& voc) : db_(nullptr) { create((int)voc.size(), 0, voc.scoring(), 0); }
+    KeyFrameDatabaseOf(const ORBVocabulary& voc, const LineVocabulary& voc_l) : db_(nullptr) { create((int)voc.size(), (int)voc_l.size(), voc.scoring(), voc_l.scoring()); }
+    ~KeyFrameDatabaseOf() { olf_kfdb_destroy(db_); }
+    KeyFrameDatabaseOf(const KeyFrameDatabaseOf&) = delete;
+    KeyFrameDatabaseOf& operator=(const KeyFrameDatabaseOf&) = delete;
+
+    void add(KeyFrameT* pKF)                                                  // :46-55
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        Vec p(pKF->mBowVec), l(pKF->mBowVec_l);
+        int32_t slot = -1;
+        olf_detail::check(olf_kfdb_add(db_, p.ids.data(), p.vals.data(), (int)p.ids.size(), l.ids.data(), l.vals.data(), (int)l.ids.size(), &slot), "olf_kfdb_add");
+        slot_of_[pKF] = slot;
+        kf_of_.resize(slot + 1, nullptr);
+        kf_of_[slot] = pKF;
+    }
+    void erase(KeyFrameT* pKF)                                                // :57-90
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        typename std::map<KeyFrameT*, int32_t>::iterator it = slot_of_.find(pKF);
+        if (it == slot_of_.end()) return;
+        olf_detail::check(olf_kfdb_erase(db_, it->second), "olf_kfdb_erase");
+        kf_of_[it->second] = nullptr;
+        slot_of_.erase(it);
+    }
+    void clear()                                                              // :92-98
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        olf_detail::check(olf_kfdb_clear(db_), "olf_kfdb_clear");
+        slot_of_.clear(); kf_of_.clear();
+    }
+    std::vector<KeyFrameT*> DetectLoopCandidates(KeyFrameT* pKF, float minScore) { return detect(OLF_KFDB_LOOP, *pKF, minScore, connected(pKF)); }                 // :107-228
+    std::vector<KeyFrameT*> DetectLoopCandidatesWithLine(KeyFrameT* pKF, float minScore) { return detect(OLF_KFDB_LOOP_LINE, *pKF, minScore, connected(pKF)); }    // :230-400
+    std::vector<KeyFrameT*> DetectRelocalizationCandidates(FrameT* F) { return detect(OLF_KFDB_RELOC, *F, 0.f, std::vector<KeyFrameT*>()); }                        // :402-512
+    std::vector<KeyFrameT*> DetectRelocalizationCandidatesWithLine(FrameT* F) { return detect(OLF_KFDB_RELOC_LINE, *F, 0.f, std::vector<KeyFrameT*>()); }           // :514-667
+    olf_kfdb* handle() const { return db_; }
+
+private:
+    struct Vec {
+        std::vector<int32_t> ids; std::vector<double> vals;
+        template <class BowVec> explicit Vec(const BowVec& v) { for (typename BowVec::const_iterator it = v.begin(); it != v.end(); ++it) { ids.push_back((int32_t)it->first); vals.push_back(it->second); } }
+    };
+    void create(int nw_p, int nw_l, int sc_p, int sc_l) { olf_detail::check(olf_kfdb_create(ctx_.get(640, 480), nw_p, nw_l, sc_p, sc_l, &db_), "olf_kfdb_create"); }
+    static std::vector<KeyFrameT*> connected(KeyFrameT* pKF)
+    {
+        const std::set<KeyFrameT*> s = pKF->GetConnectedKeyFrames();
+        return std::vector<KeyFrameT*>(s.begin(), s.end());
+    }
+    template <class QueryT>
+    std::vector<KeyFrameT*> detect(int form, QueryT& Q, float minScore, const std::vector<KeyFrameT*>& conn)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int n = (int)kf_of_.size();
+        Vec p(Q.mBowVec), l(Q.mBowVec_l);
+        const int32_t offp[2] = {0, (int32_t)p.ids.size()}, offl[2] = {0, (int32_t)l.ids.size()};
+        const olf_bow_csr qp = {offp, p.ids.data(), p.vals.data()}, ql = {offl, l.ids.data(), l.vals.data()};
+        std::vector<int32_t> conn_slots, nb_off(n + 1, 0), nb_slots;
+        for (size_t i = 0; i < conn.size(); ++i) { typename std::map<KeyFrameT*, int32_t>::const_iterator it = slot_of_.find(conn[i]); if (it != slot_of_.end()) conn_slots.push_back(it->second); }
+        const int32_t conn_off[2] = {0, (int32_t)conn_slots.size()};
+        conn_slots.push_back(-1);                                           // (never a null pointer)
+        for (int k = 0; k < n; ++k) {
+            if (kf_of_[k]) {
+                const std::vector<KeyFrameT*> nb = kf_of_[k]->GetBestCovisibilityKeyFrames(10);
+                for (size_t i = 0; i < nb.size(); ++i) { typename std::map<KeyFrameT*, int32_t>::const_iterator it = slot_of_.find(nb[i]); nb_slots.push_back(it != slot_of_.end() ? it->second : -1); }
+            }
+            nb_off[k + 1] = (int32_t)nb_slots.size();
+        }
+        nb_slots.push_back(-1);
+        const int64_t id = (int64_t)Q.mnId;
+        const int32_t np = (int32_t)Q.N, nl = (int32_t)Q.N_l;
+        std::vector<int32_t> cand((size_t)(n > 0 ? n : 1));
+        int32_t cand_off[2] = {0, 0};
+        olf_detail::check(olf_kfdb_detect(db_, form, 1, &id, &qp, &ql, &np, &nl, &minScore, conn_off, conn_slots.data(), nb_off.data(), nb_slots.data(), cand_off,
+                                          cand.data(), (int)cand.size()), "olf_kfdb_detect");
+        std::vector<KeyFrameT*> out;
+        for (int i = 0; i < cand_off[1]; ++i) out.push_back(kf_of_[cand[i]]);
+        return out;
+    }
+    olf_detail::Ctx ctx_;
+    olf_kfdb* db_;
+    std::map<KeyFrameT*, int32_t> slot_of_;
+    std::vector<KeyFrameT*> kf_of_;
+    std::mutex mMutex;
+};
 
 }  // namespace ORB_SLAM2

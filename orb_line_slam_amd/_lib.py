@@ -91,6 +91,20 @@ class LocalLineMapC(C.Structure):
                 [(n, C.c_void_p) for n in ("list_offsets", "list_index")] + [("n_entries", C.c_int32)])
 
 
+class BowCsrC(C.Structure):
+    """olf_bow_csr (include/orbline.h): n BoW vectors as offsets, ascending word ids and values"""
+    _fields_ = [(n, C.c_void_p) for n in ("off", "ids", "vals")]
+
+
+class KfdbTablesC(C.Structure):
+    """olf_kfdb_tables (include/orbline.h): one vocabulary's [n_queries][n_slots] common / first / score tables"""
+    _fields_ = [(n, C.c_void_p) for n in ("common", "first", "score")]
+
+
+KFDB_MAX_WORDS, KFDB_MAX_SLOTS, KFDB_MAX_CELLS = 4096, 1 << 20, 1 << 26
+KFDB_LOOP, KFDB_LOOP_LINE, KFDB_RELOC, KFDB_RELOC_LINE = range(4)
+
+
 # Frame::mGrid as two int32 arrays (include/orbline_types.h) and one Frame::GetFeaturesInArea call
 GRID_COLS, GRID_ROWS, GRID_CELLS, GRID_MAX_KEYS = 64, 48, 3072, 8192
 AREA_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("r", "<f4"), ("min_level", "<i4"), ("max_level", "<i4")])
@@ -244,6 +258,20 @@ def lib():
                                                               [C.c_float] + [C.c_void_p] * 3)
         L.olf_bow_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        P = C.c_void_p
+        L.olf_kfdb_create.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(P)]
+        L.olf_kfdb_destroy.argtypes = [P]
+        L.olf_kfdb_destroy.restype = None
+        L.olf_kfdb_add.argtypes = [P, P, P, C.c_int, P, P, C.c_int, C.POINTER(C.c_int32)]
+        L.olf_kfdb_erase.argtypes = [P, C.c_int32]
+        L.olf_kfdb_clear.argtypes = [P]
+        L.olf_kfdb_size.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.olf_kfdb_state.argtypes = [P, P, P, P]
+        L.olf_kfdb_tables_dev.argtypes = [P, C.c_int, C.POINTER(BowCsrC), C.POINTER(BowCsrC), C.POINTER(KfdbTablesC), C.POINTER(KfdbTablesC), P]
+        L.olf_kfdb_select.argtypes = ([P, C.c_int, C.c_int] + [P] * 8 + [C.c_int, C.POINTER(KfdbTablesC), C.POINTER(KfdbTablesC), P, P, C.c_int])
+        L.olf_kfdb_detect.argtypes = ([P, C.c_int, C.c_int, P, C.POINTER(BowCsrC), C.POINTER(BowCsrC)] + [P] * 9 + [C.c_int])
+        L.olf_bow_score_pairs_dev.argtypes = [P, C.c_int, C.c_int, P, C.POINTER(BowCsrC), C.c_int, P, P]
+        L.olf_bow_score.argtypes = [P, P, P, C.c_int, P, P, C.c_int, C.POINTER(C.c_double)]
         L.olf_profile_enable.argtypes = [C.c_void_p, C.c_int]
         L.olf_profile_reset.argtypes = [C.c_void_p]
         L.olf_profile_stage_name.restype = C.c_char_p

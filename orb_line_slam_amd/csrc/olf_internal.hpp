@@ -241,4 +241,12 @@ int launch_features_in_area(const olf_keypoint* d_keys, const int* d_cell_offset
 // a caller-supplied Frame::mGrid (layout: orbline_types.h) for n features, checked in O(OLF_GRID_CELLS + n): offsets monotone from 0, last <= n, indices in [0, n)
 bool grid_is_valid(const int32_t* cell_offsets, const int32_t* cell_index, int n);
 
+// kfdb.hip
+// the tables of olf_kfdb_tables_dev for one vocabulary: n_queries CSR queries (d_qoff [n_queries + 1] on the device) against slots [d_beg[k], d_beg[k] + d_len[k])
+int launch_kfdb_tables(const int* d_qoff, const int* d_qids, const double* d_qvals, int n_queries, const int* d_beg, const int* d_len, const int* d_ids,
+                       const double* d_vals, int n_slots, int* d_common, int* d_first, double* d_score, hipStream_t s);
+// d_score[i] = L1 score(a_i, b_i); a_len == nullptr: the first operands are a CSR (a_beg [n_a + 1]), else slots as the second operands are
+int launch_bow_score_pairs(const int* d_pairs, int n_pairs, const int* a_beg, const int* a_len, int n_a, const int* a_ids, const double* a_vals,
+                           const int* b_beg, const int* b_len, int n_b, const int* b_ids, const double* b_vals, double* d_score, hipStream_t s);
+
 }  // namespace olf

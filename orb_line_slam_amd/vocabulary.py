@@ -78,5 +78,16 @@ class ORBVocabulary:
         fv = {int(nodes[a]): idx[offs[a]:offs[a + 1]].tolist() for a in range(nf.value)}
         return bow, fv
 
+    def score(self, a, b):
+        """double score(const BowVector&, const BowVector&), TemplatedVocabulary.h:1199-1203, for L1 scoring (ScoringObject.cpp:23-68): the only scoring
+        the reference's two vocabularies use, and the only one built"""
+        from .database import bow_arrays
+        if self._h.value and self.info()["scoring"] != L1_NORM:
+            raise NotImplementedError("ORBVocabulary.score: only L1_NORM scoring is built")
+        (ia, va), (ib, vb) = bow_arrays(a), bow_arrays(b)
+        out = C.c_double()
+        check(lib().olf_bow_score(self._ctx().handle, ptr(ia), ptr(va), len(ia), ptr(ib), ptr(vb), len(ib), C.byref(out)), "olf_bow_score")
+        return out.value
+
 
 LineVocabulary = ORBVocabulary
