@@ -36,8 +36,10 @@ int check_status(olf_ctx* c)
     OLF_HIP_CHECK(hipMemcpy(st, c->ob.status, sizeof(st), hipMemcpyDeviceToHost));
     if (st[0]) {
         (void)hipMemset(c->ob.status, 0, 16);
-        set_error("device capacity overflow, flags=" + std::to_string(st[0]) +
-                  " (1/2/4: ORB corner / candidate / key point buffers, 8: LSD regions, segments or pixel-list pool, 16: LSD growth watchdog, 32: frame record buffer, 64: LSD seed sort, final-range list of the grid-wide top levels, 128: candidate list of olf_features_in_area_dev, 256: olf_search_by_projection_batch_dev / olf_search_for_triangulation_batch_dev skipped a pair that holds an octave outside the context's levels, 512: olf_is_in_frustum_batch_dev / olf_search_local_map_batch_dev met a list index or a d_frame_mp value outside the map, 1024: olf_is_in_frustum_l_batch_dev / olf_search_local_lines_batch_dev met a list index or a d_frame_ml value outside the map, 2048: olf_search_for_triangulation_batch_dev skipped a pair whose frame indices are outside the batch or equal)");
+        std::string what;                                           // the set bits, each with its row of kStatusText
+        for (const StatusText& t : kStatusText)
+            if (st[0] & t.bit) what += (what.empty() ? "" : ", ") + std::to_string(t.bit) + ": " + t.text;
+        set_error("device capacity overflow, flags=" + std::to_string(st[0]) + " (" + what + ")");
         return OLF_ERR_CAPACITY;
     }
     return OLF_OK;

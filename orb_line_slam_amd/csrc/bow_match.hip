@@ -237,8 +237,6 @@ int launch_search_by_bow_batch(const uint8_t* slotDesc, const int* childOff, con
     return OLF_OK;
 }
 
-constexpr int BM_STATUS_PAIR = 2048;                // status bit: a pair was skipped, its frame indices are outside the batch or equal (as TRI_STATUS_PAIR)
-
 struct BowPairsArgs {
     const olf_keypoint* kps; const uint4* desc; const int* counts; const uint8_t* mpValid; const uint8_t* mpBad;
     const int* pairs;
@@ -260,8 +258,8 @@ __global__ __launch_bounds__(64 * BM_WAVES) void k_search_by_bow_pairs(BowPairsA
     uint8_t* binOf = reinterpret_cast<uint8_t*>(s_mem + cap);
     uint8_t* taken = binOf + ((cap + 3) & ~3);
     const int f1 = A.pairs[2 * (size_t)p], f2 = A.pairs[2 * (size_t)p + 1];
-    if (f1 < 0 || f1 >= A.n_frames || f2 < 0 || f2 >= A.n_frames || f1 == f2) {       // (block-uniform)
-        if (tid == 0) { nmatches[p] = -1; atomicOr(status, BM_STATUS_PAIR); }
+    if (!pair_in_batch(f1, f2, A.n_frames)) {                        // (block-uniform)
+        if (tid == 0) { nmatches[p] = -1; atomicOr(status, STATUS_PAIR); }
         return;
     }
     const size_t st = (size_t)A.img_stride;

@@ -14,42 +14,29 @@
 //   k_fuse_gate    one thread per entry: bad / held, then fuse_point_gate and the level from the table of olf_predict_scale_thresholds; writes
 //                  (u, v, ur, level or -1), 16 bytes, and the "nothing" pair of the entry
 //   k_fuse_search  one wave per entry that passed: walks the window (grid_walk, grid_walk.hpp) with the level gate; every lane keeps its smallest key and
-//                  that key's feature; one wave_min_i32, the owner lane's feature fetched as Best4::drain fetches it, lane 0 writes the pair and counts
+//                  that key's feature; the wave's minimum with its owner lane's feature (wave_min_fetch, grid_walk.hpp), lane 0 writes the pair and counts
 //                  the entry for its frame when it lies within TH_LOW (an integer atomic: the count does not depend on scheduling)
-#include "grid_walk.hpp"
+#include "batch_frames.hpp"
 #include "entry_lists.hpp"
 #include "device_math.hpp"
-#include "search_math.hpp"
 #include "staging.hpp"
-#include "../../include/orbline.h"
 
 namespace olf {
 
 constexpr int FB_TH_LOW = 50;                       // src/ORBmatcher.cc:40
 constexpr int FB_NOKEY = 0x7fffffff;                // above every key: distance <= 256, so a key is below 257 << 20
 constexpr int FB_POS_BITS = 20;                     // scan positions: at most OLF_GRID_COLS ranges of at most OLF_GRID_MAX_KEYS indices, malformed grids included
-constexpr int FB_POSE = 16;                         // floats per key frame in scratch: Rcw (9), tcw (3), Ow (3), one of padding
-constexpr int FB_STATUS_OCTAVE = 256;               // status bit: a candidate with an octave outside the context's levels was left out
-constexpr int FB_STATUS_INDEX = 512;                // status bit: a list index or a d_frame_mp value outside the map
 static_assert(OLF_GRID_COLS * OLF_GRID_MAX_KEYS <= (1 << FB_POS_BITS), "key layout");
 
-struct FuseArgs {
-    olf_track_batch in;
+struct FuseArgs : FrameView {
     olf_local_map map;
     EntryLists L;
     const int* frame_mp;
     const float* Scw;              // NULL: the plain form
     const float* Ow;
-    int n_frames, n_entries, cap, nlevels, mpW;     // mpW: 32-bit words of the held bitmap per frame
-    float th, wInv, hInv;
-    float sf[OLF_MAX_LEVELS];      // mvScaleFactors
-    float thr[OLF_MAX_LEVELS];     // olf_predict_scale_thresholds
+    int n_frames, n_entries, mpW;  // mpW: 32-bit words of the held bitmap per frame
+    float th;
 };
-
-__device__ __forceinline__ int fb_count(const FuseArgs& A, int j)      // (the clamping of lb_count, local_batch.hip)
-{
-    return min(max(A.in.counts[(size_t)j * A.in.img_stride], 0), A.cap);
-}
 
 __global__ __launch_bounds__(256) void k_fuse_pose(FuseArgs A, float* __restrict__ pose)
 {
@@ -63,16 +50,13 @@ __global__ __launch_bounds__(256) void k_fuse_pose(FuseArgs A, float* __restrict
         if (A.Ow) for (int k = 0; k < 3; ++k) ow[k] = A.Ow[3 * (size_t)j + k];
         else camera_centre(T, ow);
     }
-    float* o = pose + (size_t)FB_POSE * j;
-    for (int k = 0; k < 9; ++k) o[k] = R[k];
-    for (int k = 0; k < 3; ++k) { o[9 + k] = t[k]; o[12 + k] = ow[k]; }
-    o[15] = 0.f;
+    pose_store(pose + (size_t)POSE_FLOATS * j, R, t, ow);
 }
 
 __global__ __launch_bounds__(256) void k_fuse_held(FuseArgs A, unsigned* __restrict__ held, int* __restrict__ status)
 {
     const int j = blockIdx.y, idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx < fb_count(A, j)) held_mark(A.frame_mp[(size_t)j * A.cap + idx], A.map.n_mp, A.map.bad, held + (size_t)j * A.mpW, status, FB_STATUS_INDEX);
+    if (idx < A.count(j)) held_mark(A.frame_mp[(size_t)j * A.cap + idx], A.map.n_mp, A.map.bad, held + (size_t)j * A.mpW, status, STATUS_POINT_INDEX);
 }
 
 __global__ __launch_bounds__(256) void k_fuse_gate(FuseArgs A, const float* __restrict__ pose, const unsigned* __restrict__ held, float4* __restrict__ gate,
@@ -86,12 +70,12 @@ __global__ __launch_bounds__(256) void k_fuse_gate(FuseArgs A, const float* __re
     int i = -1;
     const int j = A.L.frame_of(e, i);
     if (j >= 0) {
-        if ((unsigned)i >= (unsigned)A.map.n_mp) atomicOr(status, FB_STATUS_INDEX);
+        if ((unsigned)i >= (unsigned)A.map.n_mp) atomicOr(status, STATUS_POINT_INDEX);
         // if(!pMP) continue; if(pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue (:848-852); if(pMP->isBad() || spAlreadyFound.count(pMP)) continue (:1007)
         else if (!A.map.bad[i] && !(held && ((held[(size_t)j * A.mpW + (i >> 5)] >> (i & 31)) & 1u))) {
             const olf_track_batch& in = A.in;
             const float cam[5] = {in.fx, in.fy, in.cx, in.cy, in.mbf}, bounds[4] = {in.minX, in.maxX, in.minY, in.maxY};
-            const float* P = pose + (size_t)FB_POSE * j;
+            const float* P = pose + (size_t)POSE_FLOATS * j;
             float uvr[3], dist3D;
             if (fuse_point_gate(P, P + 9, P + 12, A.map.world + 3 * (size_t)i, A.map.normal + 3 * (size_t)i, A.map.maxd[i], A.map.mind[i], cam, bounds, uvr, dist3D))
                 g = make_float4(uvr[0], uvr[1], uvr[2], __int_as_float(fuse_level(A.map.maxd[i], dist3D, A.thr, A.nlevels)));
@@ -110,12 +94,9 @@ __global__ __launch_bounds__(256) void k_fuse_search(FuseArgs A, const float4* _
     if (level < 0) return;                                            // (the entry keeps the "nothing" pair)
     int i = -1;
     const int j = A.L.frame_of(e, i);                                 // (passed the gate: j is a frame and i a map point)
-    const olf_track_batch& in = A.in;
-    const size_t cap = (size_t)A.cap, f = (size_t)j, st = (size_t)in.img_stride;
-    const olf_keypoint* keys = in.kps + f * st * cap;
-    const uint4* kd = reinterpret_cast<const uint4*>(in.desc + 32 * f * st * cap);
-    const float* kur = in.uright + f * cap;
-    const GridView G = {keys, in.cell_offsets + f * (OLF_GRID_CELLS + 1), in.cell_index + f * cap, fb_count(A, j), A.cap, in.minX, in.minY, A.wInv, A.hInv};
+    const olf_keypoint* keys = A.keys(j);
+    const uint4* kd = A.desc(j);
+    const float* kur = A.uright(j);
     const uint4* md = reinterpret_cast<const uint4*>(A.map.desc) + 2 * (size_t)i;
     const uint4 a0 = md[0], a1 = md[1];
     const float uvr[3] = {g.x, g.y, g.z};
@@ -127,7 +108,7 @@ __global__ __launch_bounds__(256) void k_fuse_search(FuseArgs A, const float4* _
     int bestKey = FB_NOKEY, bestJ = -1;
     bool badOct = false;
     // GetFeaturesInArea(u, v, radius) and the level gate (:905-908) in one: the walk leaves out what the gate would, and keeps the order of the rest
-    grid_walk(G, uvr[0], uvr[1], radius, level - 1, level, lane, [&](bool take, int j2, int pos) {
+    grid_walk(A.grid(j), uvr[0], uvr[1], radius, level - 1, level, lane, [&](bool take, int j2, int pos) {
         if (!take) return;
         if (plain) {
             const olf_keypoint& kp = keys[j2];
@@ -140,15 +121,11 @@ __global__ __launch_bounds__(256) void k_fuse_search(FuseArgs A, const float4* _
         const int key = (dist << FB_POS_BITS) | pos;
         if (key < bestKey) { bestKey = key; bestJ = j2; }
     });
-    const int m = wave_min_i32(bestKey);
+    int m, idx = -1;
+    wave_min_fetch(bestKey, bestJ, FB_NOKEY, m, idx);
     const bool anyBad = wave_vote(badOct) != 0;
-    int idx = -1;
-    if (m != FB_NOKEY) {
-        const int owner = __ffsll((long long)wave_vote(bestKey == m)) - 1;       // (the keys are distinct: they end in the scan position)
-        idx = __shfl(bestJ, owner, 64);
-    }
     if (lane == 0) {
-        if (anyBad) atomicOr(status, FB_STATUS_OCTAVE);
+        if (anyBad) atomicOr(status, STATUS_OCTAVE);
         if (idx >= 0) {
             const int dist = m >> FB_POS_BITS;
             best_idx[e] = idx; best_dist[e] = dist;
@@ -166,29 +143,17 @@ extern "C" {
 int olf_fuse_search_batch_dev(olf_ctx* c, const olf_track_batch* in, int n_frames, const olf_local_map* map, const int32_t* d_frame_mp, const float* d_Scw,
                               const float* d_Ow, float th, int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_nfused, void* stream)
 {
-    const char* who = "olf_fuse_search_batch_dev";
     FuseArgs A;
-    if (!c || !in || !map || n_frames < 0 || map->n_mp < 0 || !d_best_idx || !d_best_dist || (!d_Scw && !in->Tcw) ||
-        !grid_scales(in->minX, in->maxX, in->minY, in->maxY, &A.wInv, &A.hInv) || !in->kps || !in->desc || !in->counts || in->img_stride < 1 || !in->uright ||
-        !in->cell_offsets || !in->cell_index ||
-        (map->n_mp && (!map->world || !map->normal || !map->maxd || !map->mind || !map->desc || !map->bad)) ||
-        (map->list_offsets && (map->n_entries < 0 || (map->n_entries && !map->list_index)))) {
-        set_error(std::string(who) + ": bad argument"); return OLF_ERR_INVALID;
-    }
-    OLF_TRY(ctx_check_device(c, who));
-    const int cap = olf_orb_capacity(c);
-    if (cap > OLF_GRID_MAX_KEYS) { set_error(std::string(who) + ": more than OLF_GRID_MAX_KEYS key points per frame"); return OLF_ERR_CAPACITY; }
-    const long long ne = map->list_offsets ? (long long)map->n_entries : (long long)n_frames * map->n_mp;
-    if (ne > 0x7fffffffLL - 256) { set_error(std::string(who) + ": more than 2^31 entries"); return OLF_ERR_CAPACITY; }
+    OLF_TRY(batch_frames(c, "olf_fuse_search_batch_dev", map && d_best_idx && d_best_dist, in, NEED_GRID | NEED_URIGHT | (d_Scw ? 0 : NEED_TCW), n_frames, map,
+                         MAP_DESC, 0, "entries", A, &A.n_entries));
     if (n_frames == 0) return OLF_OK;
-    A.in = *in; A.map = *map;
-    A.L = {map->list_offsets, map->list_index, map->n_mp, n_frames, (int)ne};
+    const int cap = A.cap;
+    A.map = *map;
+    A.L = {map->list_offsets, map->list_index, map->n_mp, n_frames, A.n_entries};
     A.frame_mp = d_frame_mp; A.Scw = d_Scw; A.Ow = d_Ow;
-    A.n_frames = n_frames; A.n_entries = (int)ne; A.cap = cap;
-    A.nlevels = ctx_level_scales(c, A.sf);
+    A.n_frames = n_frames;
     A.mpW = (map->n_mp + 31) / 32;
     A.th = th;
-    for (int l = 0; l < OLF_MAX_LEVELS; ++l) A.thr[l] = 0.f;
     OLF_TRY(ctx_level_thresholds(c, A.thr));
     hipStream_t s = ctx_stream(c, stream);
     if (d_nfused) OLF_HIP_CHECK(hipMemsetAsync(d_nfused, 0, (size_t)n_frames * 4, s));
@@ -197,7 +162,7 @@ int olf_fuse_search_batch_dev(olf_ctx* c, const olf_track_batch* in, int n_frame
     float4* gate; float* pose; unsigned* held;
     const size_t bh = d_frame_mp ? (size_t)n_frames * A.mpW : 0;
     Carve k;
-    k.add(&gate, (size_t)A.n_entries); k.add(&pose, (size_t)FB_POSE * n_frames); k.add(&held, bh);
+    k.add(&gate, (size_t)A.n_entries); k.add(&pose, (size_t)POSE_FLOATS * n_frames); k.add(&held, bh);
     OLF_TRY(k.bind(c, SCRATCH_BATCH));
     hipLaunchKernelGGL(k_fuse_pose, dim3((n_frames + 255) / 256), dim3(256), 0, s, A, pose);
     if (bh) OLF_HIP_CHECK(hipMemsetAsync(held, 0, bh * 4, s));

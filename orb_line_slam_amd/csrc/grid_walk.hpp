@@ -1,6 +1,7 @@
 // grid_walk.hpp -- what the device callers of Frame::mGrid share: Frame::GetFeaturesInArea (src/Frame.cc:517-570) by one wave (grid.hip's k_features_in_area and
-// the batched matchers of track_batch.hip and local_batch.hip), the four best entries of such a window, and the matchers' per-item radius.  The matchers' sort
-// keys carry the scan position this walk hands out, so their results rest on every caller running this one text.
+// the batched matchers), the wave's smallest key with its owner's payload, the four best entries of a window (Best4), a window's best entry under a
+// caller's test (window_best), and the matchers' per-item radius.  The matchers' sort keys carry the scan position this walk hands out, so their results rest
+// on every caller running this one text.
 #pragma once
 #include "olf_internal.hpp"
 
@@ -62,6 +63,18 @@ __device__ __forceinline__ int grid_walk(const GridView& G, float x, float y, fl
     return total;
 }
 
+// The wave's smallest key m and, where m < below, the payload of the lane that holds it (both wave-uniform); false: no key lies below `below`.  The keys below
+// Best4::NOKEY are distinct (a matcher's key ends in the scan position), so such a minimum has one owner lane.  Every lane of the wave calls it.
+template <class T>
+__device__ __forceinline__ bool wave_min_fetch(int key, T payload, int below, int& m, T& out)
+{
+    m = wave_min_i32(key);
+    if (m >= below) return false;
+    const int owner = __ffsll((long long)wave_vote(key == m)) - 1;
+    out = (T)__shfl((int)payload, owner, 64);
+    return true;
+}
+
 // The four smallest (key, entry) pairs a wave meets.  Every lane keeps the four smallest keys pushed to it, ascending: one of the window's four smallest is
 // one of its lane's four smallest, so the lanes' registers hold them all, and drain() takes them out by four wave minima.  The keys are distinct (a matcher's
 // key ends in the scan position), so each minimum has one owner lane.
@@ -85,15 +98,29 @@ struct Best4 {
     __device__ __forceinline__ void drain(unsigned (&out)[K])
     {
         for (int k = 0; k < K; ++k) {
-            const int m = wave_min_i32(h0);
-            if (m == NOKEY) break;
-            const bool mine = h0 == m;
-            const int owner = __ffsll((long long)wave_vote(mine)) - 1;
-            out[k] = (unsigned)__shfl((int)e0, owner, 64);
-            if (mine) { h0 = h1; e0 = e1; h1 = h2; e1 = e2; h2 = h3; e2 = e3; h3 = NOKEY; e3 = NONE; }
+            int m;
+            if (!wave_min_fetch(h0, e0, NOKEY, m, out[k])) break;
+            if (h0 == m) { h0 = h1; e0 = e1; h1 = h2; e1 = e2; h2 = h3; e2 = e3; h3 = NOKEY; e3 = NONE; }
         }
     }
 };
+
+// A window again by the whole wave, for the ordered walks' recompute path: the entry of the smallest key among the features that cand(j, pos, key, ent)
+// accepts -- the caller's closed test is part of cand --, or Best4::NONE.  Wave-uniform.
+template <class C>
+__device__ __forceinline__ unsigned window_best(const GridView& G, float x, float y, float r, int minLevel, int maxLevel, int lane, C&& cand)
+{
+    int best = Best4::NOKEY;
+    unsigned bestEnt = Best4::NONE;
+    grid_walk(G, x, y, r, minLevel, maxLevel, lane, [&](bool take, int j, int pos) {
+        int key = Best4::NOKEY, m;
+        unsigned ent = Best4::NONE, e;
+        if (!(take && cand(j, pos, key, ent))) key = Best4::NOKEY;
+        // (later chunks hold later scan positions: a tie is impossible, `<` as in the reference)
+        if (wave_min_fetch(key, ent, best, m, e)) { best = m; bestEnt = e; }
+    });
+    return bestEnt;
+}
 
 // the radius factor of item j of a batch (a pair, a frame): th, or d_th[j] where the caller gives one per item; false: the item is skipped (d_th[j] <= 0)
 __device__ __forceinline__ bool item_radius(float th, const float* d_th, int j, float& out)

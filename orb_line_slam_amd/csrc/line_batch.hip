@@ -27,7 +27,6 @@
 
 namespace olf {
 
-constexpr int LL_STATUS_INDEX = 1024;               // status bit: a list index or a d_frame_ml value outside the map
 constexpr int LL_MAX_LINES = 4096;                  // lines per frame: the fused (distance << 12 | index) key of the kNN
 constexpr int LL_NO_RANK = 0x7f7f7f7f;              // (memset 0x7f) no rank with observations passed the position gate
 // what k_ll_gate found for a rank
@@ -55,7 +54,7 @@ __global__ __launch_bounds__(256) void k_ll_held(LineArgs A, unsigned* __restric
     if (idx >= A.cap) return;
     int v = -1;
     if (A.frame_ml && idx < ll_count(A.in, j, A.cap)) v = A.frame_ml[(size_t)j * A.cap + idx];
-    if (v >= A.map.n_ml) { atomicOr(status, LL_STATUS_INDEX); v = -1; }
+    if (v >= A.map.n_ml) { atomicOr(status, STATUS_LINE_INDEX); v = -1; }
     else if (v < 0 || A.map.bad[v]) v = -1;                            // (a bad line is dropped from its frame line, src/Tracking.cc:1902-1905)
     if (v >= 0) atomicOr(&held[(size_t)j * A.mlW + (v >> 5)], 1u << (v & 31));
     if (frame_ml_out) frame_ml_out[(size_t)j * A.cap + idx] = v;
@@ -70,7 +69,7 @@ __global__ __launch_bounds__(256) void k_ll_frustum(LineArgs A, const unsigned* 
     const int j = A.L.frame_of(e, i);
     in_view[e] = 0;
     if (j < 0) return;
-    if ((unsigned)i >= (unsigned)A.map.n_ml) { atomicOr(status, LL_STATUS_INDEX); return; }
+    if ((unsigned)i >= (unsigned)A.map.n_ml) { atomicOr(status, STATUS_LINE_INDEX); return; }
     if (held && ((held[(size_t)j * A.mlW + (i >> 5)] >> (i & 31)) & 1u)) return;   // mnLastFrameSeen == mCurrentFrame.mnId, :1953 (NULL: the frames hold nothing)
     if (A.map.bad[i]) return;                                                      // :1955
     const olf_line_batch& in = A.in;

@@ -17,12 +17,10 @@
 //                    do not yield two unblocked ones although the window held more is recomputed on the spot by the wave, with the blocked test inside
 //                    the scan -- there is no capacity and no approximate case
 #include <algorithm>
-#include "grid_walk.hpp"
+#include "batch_frames.hpp"
 #include "entry_lists.hpp"
 #include "device_math.hpp"
-#include "search_math.hpp"
 #include "staging.hpp"
-#include "../../include/orbline.h"
 
 namespace olf {
 
@@ -31,27 +29,22 @@ constexpr int LB_K = 4;                             // candidates kept per entry
 // a kept candidate: distance << 18 | (octave == predicted level) << 13 | feature (< OLF_GRID_MAX_KEYS = 2^13); the first word of a list also carries two flags
 constexpr unsigned LB_NONE = Best4::NONE, LB_OBS = 1u << 30, LB_MORE = 1u << 31;
 constexpr int LB_NOKEY = Best4::NOKEY;
-constexpr int LB_STATUS_INDEX = 512;                // status bit: a list index or a d_frame_mp value outside the map
 static_assert(OLF_GRID_MAX_KEYS <= (1 << 13) && LB_K == Best4::K, "candidate layout");
 
-struct LocalArgs {
-    olf_track_batch in;
+struct LocalArgs : FrameView {
     olf_local_map map;
+    EntryLists L;
     const int* frame_mp;
-    int n_frames, n_entries, cap, nlevels;
-    int mpW, capW;                 // per frame: 32-bit words of the held bitmap, 64-bit words of the blocked bitmap
+    int n_frames, n_entries;
+    int mpW, blkW;                 // per frame: 32-bit words of the held bitmap, 64-bit words of the blocked bitmap
     float cosLimit, th, nnratio;
     const float* d_th;
-    float wInv, hInv;
-    float sf[OLF_MAX_LEVELS];      // mvScaleFactors
-    float thr[OLF_MAX_LEVELS];     // olf_predict_scale_thresholds
 };
 
 struct LbFrame {
     const olf_keypoint* k;
     const uint4* d;
     const float* ur;
-    const int *offs, *idx;
     int n;
 };
 
@@ -60,68 +53,19 @@ struct LbQuery {
     int level;
 };
 
-// the frame entry e belongs to (-1: none) and its map index (unchecked)
-__device__ __forceinline__ int lb_frame_of(const LocalArgs& A, int e, int& mi)
-{
-    if (!A.map.list_offsets) {
-        const int j = e / A.map.n_mp;
-        mi = e - j * A.map.n_mp;
-        return j;
-    }
-    const int* o = A.map.list_offsets;
-    int lo = 0, hi = A.n_frames;                    // the last frame whose list starts at or before e
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (o[mid] <= e) lo = mid; else hi = mid;
-    }
-    mi = A.map.list_index[e];
-    return (e >= o[lo] && e < o[lo + 1]) ? lo : -1;
-}
-
-// the entries of frame j, inside [0, n_entries) whatever the offsets hold
-__device__ __forceinline__ void lb_range(const LocalArgs& A, int j, int& b, int& e)
-{
-    if (!A.map.list_offsets) { b = j * A.map.n_mp; e = b + A.map.n_mp; return; }
-    b = min(max(A.map.list_offsets[j], 0), A.n_entries);
-    e = min(max(A.map.list_offsets[j + 1], b), A.n_entries);
-}
-
-__device__ __forceinline__ int lb_count(const LocalArgs& A, int j)
-{
-    return A.in.counts ? min(max(A.in.counts[(size_t)j * A.in.img_stride], 0), A.cap) : A.cap;
-}
-
-__device__ __forceinline__ LbFrame lb_frame(const LocalArgs& A, int j)
-{
-    const olf_track_batch& in = A.in;
-    const size_t cap = (size_t)A.cap, f = (size_t)j, st = (size_t)in.img_stride;
-    LbFrame F;
-    F.k = in.kps + f * st * cap;
-    F.d = reinterpret_cast<const uint4*>(in.desc + 32 * f * st * cap);
-    F.ur = in.uright + f * cap;
-    F.offs = in.cell_offsets + f * (OLF_GRID_CELLS + 1);
-    F.idx = in.cell_index + f * cap;
-    F.n = lb_count(A, j);
-    return F;
-}
-
-// the frame's grid as grid_walk reads it (built at the walk, as tb_grid of track_batch.hip is)
-__device__ __forceinline__ GridView lb_grid(const LbFrame& P, const LocalArgs& A)
-{
-    return {P.k, P.offs, P.idx, P.n, A.cap, A.in.minX, A.in.minY, A.wInv, A.hInv};
-}
+__device__ __forceinline__ LbFrame lb_frame(const LocalArgs& A, int j) { return {A.keys(j), A.desc(j), A.uright(j), A.count(j)}; }
 
 __global__ __launch_bounds__(256) void k_local_held(LocalArgs A, unsigned* __restrict__ held, unsigned long long* __restrict__ blk0, int* __restrict__ status)
 {
     const int j = blockIdx.y, idx = blockIdx.x * 256 + threadIdx.x;
     bool blocked = false;
-    if (idx < lb_count(A, j)) {
+    if (idx < (A.in.counts ? A.count(j) : A.cap)) {                  // (olf_is_in_frustum_batch_dev without counts: every frame holds cap key points)
         // (a bad point is dropped from its feature, src/Tracking.cc:1885-1888)
-        const int v = held_mark(A.frame_mp[(size_t)j * A.cap + idx], A.map.n_mp, A.map.bad, held + (size_t)j * A.mpW, status, LB_STATUS_INDEX);
+        const int v = held_mark(A.frame_mp[(size_t)j * A.cap + idx], A.map.n_mp, A.map.bad, held + (size_t)j * A.mpW, status, STATUS_POINT_INDEX);
         blocked = v >= 0 && blk0 && A.map.obs[v] != 0;
     }
     const unsigned long long m = wave_vote(blocked);
-    if (blk0 && (threadIdx.x & 63) == 0 && (idx >> 6) < A.capW) blk0[(size_t)j * A.capW + (idx >> 6)] = m;
+    if (blk0 && (threadIdx.x & 63) == 0 && (idx >> 6) < A.blkW) blk0[(size_t)j * A.blkW + (idx >> 6)] = m;
 }
 
 // Frame::isInFrustum as olf_is_in_frustum evaluates it (search_host.cpp)
@@ -131,10 +75,10 @@ __global__ __launch_bounds__(256) void k_local_frustum(LocalArgs A, const unsign
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= A.n_entries) return;
     int i = -1;
-    const int j = lb_frame_of(A, e, i);
+    const int j = A.L.frame_of(e, i);
     in_view[e] = 0;
     if (j < 0) return;
-    if ((unsigned)i >= (unsigned)A.map.n_mp) { atomicOr(status, LB_STATUS_INDEX); return; }
+    if ((unsigned)i >= (unsigned)A.map.n_mp) { atomicOr(status, STATUS_POINT_INDEX); return; }
     if (A.map.bad[i]) return;
     if (held && ((held[(size_t)j * A.mpW + (i >> 5)] >> (i & 31)) & 1u)) return;
     const olf_track_batch& in = A.in;
@@ -202,7 +146,7 @@ __global__ __launch_bounds__(256) void k_local_lists(LocalArgs A, const uint8_t*
     const int e = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (e >= A.n_entries) return;                                    // (wave-uniform, as every branch on e below)
     int i = -1;
-    const int j = lb_frame_of(A, e, i);
+    const int j = A.L.frame_of(e, i);
     unsigned out[LB_K] = {LB_NONE, LB_NONE, LB_NONE, LB_NONE};
     int cnt = 0;
     bool obs = false;
@@ -212,10 +156,10 @@ __global__ __launch_bounds__(256) void k_local_lists(LocalArgs A, const uint8_t*
         const LbQuery q = lb_query(A, th, level[e], view_cos[e], proj3 + 3 * (size_t)e);
         const uint4* md = reinterpret_cast<const uint4*>(A.map.desc) + 2 * (size_t)i;
         const uint4 a0 = md[0], a1 = md[1];
-        const unsigned long long* b0 = blk0 + (size_t)j * A.capW;
+        const unsigned long long* b0 = blk0 + (size_t)j * A.blkW;
         obs = A.map.obs[i] != 0;
         Best4 best;
-        grid_walk(lb_grid(P, A), q.u, q.v, q.radius, q.level - 1, q.level, lane, [&](bool take, int j2, int pos) {
+        grid_walk(A.grid(j), q.u, q.v, q.radius, q.level - 1, q.level, lane, [&](bool take, int j2, int pos) {
             int key = LB_NOKEY;
             unsigned ent = LB_NONE;
             const bool ok = take && !((b0[j2 >> 6] >> (j2 & 63)) & 1ull) && lb_candidate(P, q, a0, a1, j2, pos, key, ent);
@@ -233,25 +177,24 @@ __global__ __launch_bounds__(256) void k_local_lists(LocalArgs A, const uint8_t*
 }
 
 // the window of entry e again, with the blocked test inside the scan: the first two candidates of the sorted list that are not blocked now (LB_NONE: none)
-__device__ __forceinline__ void lb_rescan(const LbFrame& P, const LocalArgs& A, const LbQuery& q, int i, int lane, const unsigned* s_blk, unsigned& c1, unsigned& c2)
+__device__ __forceinline__ void lb_rescan(const LbFrame& P, const LocalArgs& A, int j, const LbQuery& q, int i, int lane, const unsigned* s_blk, unsigned& c1, unsigned& c2)
 {
     const uint4* md = reinterpret_cast<const uint4*>(A.map.desc) + 2 * (size_t)i;
     const uint4 a0 = md[0], a1 = md[1];
     int k1 = LB_NOKEY, k2 = LB_NOKEY;
     c1 = c2 = LB_NONE;
-    grid_walk(lb_grid(P, A), q.u, q.v, q.radius, q.level - 1, q.level, lane, [&](bool take, int j2, int pos) {
+    grid_walk(A.grid(j), q.u, q.v, q.radius, q.level - 1, q.level, lane, [&](bool take, int j2, int pos) {
         int key = LB_NOKEY;
         unsigned ent = LB_NONE;
         const bool ok = take && !((s_blk[j2 >> 5] >> (j2 & 31)) & 1u) && lb_candidate(P, q, a0, a1, j2, pos, key, ent);
         if (!ok) key = LB_NOKEY;
         for (int t = 0; t < 2; ++t) {                                // the chunk's two smallest keys, merged into the running two (keys are distinct)
-            const int m = wave_min_i32(key);
-            if (m >= k2) break;
-            const int owner = __ffsll((long long)wave_vote(key == m)) - 1;
-            const unsigned em = (unsigned)__shfl((int)ent, owner, 64);
+            int m;
+            unsigned em;
+            if (!wave_min_fetch(key, ent, k2, m, em)) break;
             if (m < k1) { k2 = k1; c2 = c1; k1 = m; c1 = em; }
             else { k2 = m; c2 = em; }
-            if (lane == owner) key = LB_NOKEY;
+            if (key == m) key = LB_NOKEY;
         }
     });
 }
@@ -268,55 +211,42 @@ __global__ __launch_bounds__(256) void k_local_walk(LocalArgs A, const uint4* __
     float th;
     if (!item_radius(A.th, A.d_th, j, th)) return;
     const LbFrame P = lb_frame(A, j);
-    const unsigned* b0 = reinterpret_cast<const unsigned*>(blk0 + (size_t)j * A.capW);
+    const unsigned* b0 = reinterpret_cast<const unsigned*>(blk0 + (size_t)j * A.blkW);
     for (int i = tid; i < cap; i += 256) s_match[i] = -1;
-    for (int w = tid; w < 2 * A.capW; w += 256) s_blk[w] = b0[w];
+    for (int w = tid; w < 2 * A.blkW; w += 256) s_blk[w] = b0[w];
     if (tid == 0) s_n = 0;
     __syncthreads();
     if (tid < 64) {
-        int n = 0, eb, ee;
-        lb_range(A, j, eb, ee);
-        for (int c0 = eb; c0 < ee; c0 += 64) {
-            const int e = c0 + lane;
-            uint4 L = make_uint4(LB_NONE, LB_NONE, LB_NONE, LB_NONE);
-            int mi = -1;
-            if (e < ee) { L = lists[e]; mi = A.map.list_offsets ? A.map.list_index[e] : e - eb; }
-            unsigned long long todo = wave_vote((L.x & LB_NONE) != LB_NONE);
-            while (todo) {
-                const int l = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                const unsigned x = (unsigned)__shfl((int)L.x, l, 64);
-                const unsigned k[LB_K] = {x & LB_NONE, (unsigned)__shfl((int)L.y, l, 64), (unsigned)__shfl((int)L.z, l, 64), (unsigned)__shfl((int)L.w, l, 64)};
-                const int i = __shfl(mi, l, 64);
-                // the first two kept candidates that are not blocked now
-                unsigned c1 = LB_NONE, c2 = LB_NONE;
-                bool complete = false;                               // the kept candidates decide the entry
-                for (int t = 0; t < LB_K; ++t) {
-                    if (k[t] == LB_NONE) { complete = true; break; }
-                    const unsigned f = k[t] & 0x1fffu;
-                    if (f >= (unsigned)P.n || ((s_blk[f >> 5] >> (f & 31)) & 1u)) continue;
-                    if (c1 == LB_NONE) {
-                        c1 = k[t];
-                        if ((int)(c1 >> 18) > LB_TH_HIGH) { complete = true; break; }      // (bestDist > TH_HIGH: the second best is not looked at, :120)
-                    } else { c2 = k[t]; complete = true; break; }
-                }
-                if (!complete && !(x & LB_MORE)) complete = true;
-                if (!complete && c1 == LB_NONE && (int)(k[LB_K - 1] >> 18) > LB_TH_HIGH) complete = true;      // (whatever follows is no nearer)
-                if (!complete) {
-                    const int e1 = c0 + l;
-                    lb_rescan(P, A, lb_query(A, th, level[e1], view_cos[e1], proj3 + 3 * (size_t)e1), i, lane, s_blk, c1, c2);
-                }
-                if (c1 == LB_NONE) continue;
-                const int bestDist = (int)(c1 >> 18);
-                if (bestDist > LB_TH_HIGH) continue;
-                // Apply ratio to second match (only if best and second are in the same scale level), :119-123 -- without a second: bestLevel2 = -1
-                if (c2 != LB_NONE && ((c1 ^ c2) & (1u << 13)) == 0 && (float)bestDist > A.nnratio * (float)(int)(c2 >> 18)) continue;
-                const unsigned f = c1 & 0x1fffu;
-                s_match[f] = i;                                       // (every lane stores the same values: the next entry's reads are ordered behind them)
-                if (x & LB_OBS) s_blk[f >> 5] |= 1u << (f & 31);
-                ++n;
+        int n = 0, eb, ee, mi = -1;                                  // mi: this lane's list's map index
+        A.L.range(j, eb, ee);
+        walk_lists(lists, eb, ee, lane, [&](int e, bool in) { mi = !in ? -1 : A.L.offsets ? A.L.index[e] : e - eb; },
+                   [&](int e1, int l, unsigned x, const unsigned (&k)[LB_K]) {
+            const int i = __shfl(mi, l, 64);
+            // the first two kept candidates that are not blocked now
+            unsigned c1 = LB_NONE, c2 = LB_NONE;
+            bool complete = false;                                   // the kept candidates decide the entry
+            for (int t = 0; t < LB_K; ++t) {
+                if (k[t] == LB_NONE) { complete = true; break; }
+                const unsigned f = k[t] & 0x1fffu;
+                if (f >= (unsigned)P.n || ((s_blk[f >> 5] >> (f & 31)) & 1u)) continue;
+                if (c1 == LB_NONE) {
+                    c1 = k[t];
+                    if ((int)(c1 >> 18) > LB_TH_HIGH) { complete = true; break; }      // (bestDist > TH_HIGH: the second best is not looked at, :120)
+                } else { c2 = k[t]; complete = true; break; }
             }
-        }
+            if (!complete && !(x & LB_MORE)) complete = true;
+            if (!complete && c1 == LB_NONE && (int)(k[LB_K - 1] >> 18) > LB_TH_HIGH) complete = true;      // (whatever follows is no nearer)
+            if (!complete) lb_rescan(P, A, j, lb_query(A, th, level[e1], view_cos[e1], proj3 + 3 * (size_t)e1), i, lane, s_blk, c1, c2);
+            if (c1 == LB_NONE) return;
+            const int bestDist = (int)(c1 >> 18);
+            if (bestDist > LB_TH_HIGH) return;
+            // Apply ratio to second match (only if best and second are in the same scale level), :119-123 -- without a second: bestLevel2 = -1
+            if (c2 != LB_NONE && ((c1 ^ c2) & (1u << 13)) == 0 && (float)bestDist > A.nnratio * (float)(int)(c2 >> 18)) return;
+            const unsigned f = c1 & 0x1fffu;
+            s_match[f] = i;                                           // (every lane stores the same values: the next entry's reads are ordered behind them)
+            if (x & LB_OBS) s_blk[f >> 5] |= 1u << (f & 31);
+            ++n;
+        });
         if (lane == 0) s_n = n;
     }
     __syncthreads();
@@ -330,29 +260,17 @@ using namespace olf;
 
 namespace {
 
-// the checks and the argument block the two entries share; n_entries is formed here when the map carries no lists
+// the checks and the argument block the two entries share (batch_frames forms n_entries when the map carries no lists)
 int local_args(olf_ctx* c, const char* who, const olf_track_batch* in, int n_frames, const olf_local_map* map, bool search, LocalArgs& A)
 {
-    const std::string w(who);
-    if (!c || !in || !map || n_frames < 0 || map->n_mp < 0 || !in->Tcw || !grid_scales(in->minX, in->maxX, in->minY, in->maxY, &A.wInv, &A.hInv) ||
-        (map->n_mp && (!map->world || !map->normal || !map->maxd || !map->mind || !map->bad)) ||
-        (map->list_offsets && (map->n_entries < 0 || (map->n_entries && !map->list_index))) ||
-        (search && (!in->kps || !in->desc || !in->counts || in->img_stride < 1 || !in->uright || !in->cell_offsets || !in->cell_index ||
-                    (map->n_mp && (!map->desc || !map->obs))))) {
-        set_error(w + ": bad argument"); return OLF_ERR_INVALID;
-    }
-    OLF_TRY(ctx_check_device(c, who));
-    const int cap = olf_orb_capacity(c);
-    if (cap > OLF_GRID_MAX_KEYS) { set_error(w + ": more than OLF_GRID_MAX_KEYS key points per frame (a kept candidate holds 13 index bits)"); return OLF_ERR_CAPACITY; }
-    const long long ne = map->list_offsets ? (long long)map->n_entries : (long long)n_frames * map->n_mp;
-    if (ne > 0x7fffffffLL - 256) { set_error(w + ": more than 2^31 entries"); return OLF_ERR_CAPACITY; }
-    A.in = *in; A.map = *map;
+    OLF_TRY(batch_frames(c, who, map != nullptr, in, search ? NEED_GRID | NEED_URIGHT | NEED_TCW : NEED_TCW, n_frames, map, search ? MAP_DESC | MAP_OBS : 0, 0,
+                         "entries", A, &A.n_entries));
+    A.map = *map;
+    A.L = {map->list_offsets, map->list_index, map->n_mp, n_frames, A.n_entries};
     A.frame_mp = nullptr;
-    A.n_frames = n_frames; A.n_entries = (int)ne; A.cap = cap;
-    A.nlevels = ctx_level_scales(c, A.sf);
-    A.mpW = (map->n_mp + 31) / 32; A.capW = (cap + 63) / 64;
+    A.n_frames = n_frames;
+    A.mpW = (map->n_mp + 31) / 32; A.blkW = (A.cap + 63) / 64;
     A.cosLimit = 0.f; A.th = 1.f; A.nnratio = 0.f; A.d_th = nullptr;
-    for (int l = 0; l < OLF_MAX_LEVELS; ++l) A.thr[l] = 0.f;
     return ctx_level_thresholds(c, A.thr);
 }
 
@@ -362,7 +280,7 @@ int launch_frustum(olf_ctx* c, const LocalArgs& A, unsigned* held, unsigned long
     const size_t bh = (size_t)A.n_frames * A.mpW * 4;
     const bool scatter = A.frame_mp != nullptr;
     if (bh) OLF_HIP_CHECK(hipMemsetAsync(held, 0, bh, s));
-    if (blk0 && !scatter) OLF_HIP_CHECK(hipMemsetAsync(blk0, 0, (size_t)A.n_frames * A.capW * 8, s));
+    if (blk0 && !scatter) OLF_HIP_CHECK(hipMemsetAsync(blk0, 0, (size_t)A.n_frames * A.blkW * 8, s));
     if (scatter) hipLaunchKernelGGL(k_local_held, dim3((A.cap + 255) / 256, A.n_frames), dim3(256), 0, s, A, held, blk0, ctx_status(c));
     if (A.n_entries) hipLaunchKernelGGL(k_local_frustum, dim3((A.n_entries + 255) / 256), dim3(256), 0, s, A, scatter ? held : nullptr, in_view, level, view_cos, proj3, ctx_status(c));
     OLF_HIP_CHECK(hipGetLastError());
@@ -403,12 +321,12 @@ int olf_search_local_map_batch_dev(olf_ctx* c, const olf_track_batch* in, int n_
     uint4* lists; float *proj3, *view_cos; int* level; uint8_t* in_view; unsigned* held; unsigned long long* blk0;
     Carve k;
     k.add(&lists, ne); k.add(&proj3, 3 * ne); k.add(&level, ne); k.add(&view_cos, ne); k.add(&in_view, ne);
-    k.add(&held, (size_t)n_frames * A.mpW); k.add(&blk0, (size_t)n_frames * A.capW);
+    k.add(&held, (size_t)n_frames * A.mpW); k.add(&blk0, (size_t)n_frames * A.blkW);
     OLF_TRY(k.bind(c, SCRATCH_BATCH));
     hipStream_t s = ctx_stream(c, stream);
     OLF_TRY(launch_frustum(c, A, held, blk0, in_view, level, view_cos, proj3, s));
     if (A.n_entries) hipLaunchKernelGGL(k_local_lists, dim3((A.n_entries + 3) / 4), dim3(256), 0, s, A, in_view, level, view_cos, proj3, blk0, lists);
-    const size_t lds = (size_t)A.cap * 4 + (size_t)A.capW * 8;
+    const size_t lds = (size_t)A.cap * 4 + (size_t)A.blkW * 8;
     hipLaunchKernelGGL(k_local_walk, dim3(n_frames), dim3(256), lds, s, A, lists, level, view_cos, proj3, blk0, d_matches, d_nmatches);
     OLF_HIP_CHECK(hipGetLastError());
     return OLF_OK;

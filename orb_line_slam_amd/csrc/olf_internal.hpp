@@ -69,7 +69,29 @@ int ctx_join_line_outputs(olf_ctx* c, hipStream_t s, const void* p0, const void*
 int ctx_level_scales(const olf_ctx* c, float* sf);     // mvScaleFactors into sf[0 .. OLF_MAX_LEVELS), 1.0 above the context's levels; returns the level count
 int ctx_level_thresholds(olf_ctx* c, float* thr);      // the table of olf_predict_scale_thresholds for the context's levels, built once
 
+// The bits of the context's status word (ctx_status) that the batched matchers set, as every entry means them; include/orbline.h says per entry what was
+// left out.  What a bit means is its row of kStatusText, which is also what check_status (api.cpp) tells the caller about a set bit.
+enum StatusBit : int { STATUS_OCTAVE = 256, STATUS_POINT_INDEX = 512, STATUS_LINE_INDEX = 1024, STATUS_PAIR = 2048 };
+struct StatusText { int bit; const char* text; };
+constexpr StatusText kStatusText[] = {
+    {1, "ORB corner buffer"},
+    {2, "ORB candidate buffer"},
+    {4, "ORB key point buffer"},
+    {8, "LSD regions, segments or pixel-list pool"},
+    {16, "LSD growth watchdog"},
+    {32, "frame record buffer"},
+    {64, "LSD seed sort, final-range list of the grid-wide top levels"},
+    {128, "candidate list of olf_features_in_area_dev"},
+    {STATUS_OCTAVE, "a batched matcher left out a pair or a candidate that holds an octave outside the context's levels"},
+    {STATUS_POINT_INDEX, "a batched point entry left out a list index or a per-frame map-point index outside the map"},
+    {STATUS_LINE_INDEX, "a batched line entry left out a list index or a per-frame map-line index outside the map"},
+    {STATUS_PAIR, "a pair entry skipped a pair whose frame indices are outside the batch or equal"},
+};
+
 #ifdef __HIPCC__
+// a pair (f1, f2) of a pair entry is searched when both are frames of the batch and differ; otherwise the entry skips it and sets STATUS_PAIR
+__device__ __forceinline__ bool pair_in_batch(int f1, int f2, int n_frames) { return f1 >= 0 && f1 < n_frames && f2 >= 0 && f2 < n_frames && f1 != f2; }
+
 // Wave-wide vote.  hip's __ballot() converts the predicate to an int first and compares that with 0 (a v_cndmask + v_cmp_ne pair per vote);
 // the wave64 builtin takes the compare's lane mask as it is.
 // sum over the 64 lanes of a wave, wave-uniform result: two quad permutes, the two row mirrors (DPP, no LDS), then the four rows' sums through scalar registers

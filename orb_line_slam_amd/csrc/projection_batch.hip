@@ -5,7 +5,8 @@
 //   loop            int SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*> &vpPoints, vector<MapPoint*> &vpMatched, int th)
 //                   (src/ORBmatcher.cc:292-405; LoopClosing::ComputeSim3, src/LoopClosing.cc:381) for every key frame of a batch against its list of points
 // The arithmetic is that of search_host.cpp (olf_search_by_projection_kf; fuse_core with `matched`), and the gates on a point are the text both sides run
-// (search_math.hpp: reloc_point_gate, sim3_decompose, fuse_point_gate, fuse_level_ok, rot_bin, three_maxima).  No contraction (-ffp-contract=off),
+// (search_math.hpp: reloc_point_gate, sim3_decompose, fuse_point_gate, fuse_level_ok, rot_bin, three_maxima), the frames, list traversal, recompute and
+// histogram rejection those of every ordered walk (batch_frames.hpp, grid_walk.hpp).  No contraction (-ffp-contract=off),
 // correctly rounded divisions and square root.
 //
 // Both are ordered greedy searches: a key point that takes a point is closed to every later point (:1693-1694 with :1714; :378 with :400), and nothing else
@@ -26,27 +27,21 @@
 // k_proj_lists and k_proj_walk are one text for both forms, instantiated on RelocForm / LoopForm: what a work item is, which key points are closed on entry,
 // where a query's descriptor lives, the levels of its window and what a take stores.
 #include <string>
-#include "grid_walk.hpp"
+#include "batch_frames.hpp"
 #include "entry_lists.hpp"
 #include "device_math.hpp"
-#include "search_math.hpp"
 #include "staging.hpp"
-#include "../../include/orbline.h"
 
 namespace olf {
 
-constexpr int PB_TH_LOW = 50, PB_HISTO = HISTO_LENGTH;      // src/ORBmatcher.cc:40-41
+constexpr int PB_TH_LOW = 50;                       // src/ORBmatcher.cc:40
 constexpr int PB_K = 4;                             // entries kept per query (one uint4)
 // a list entry: distance << 18 | rotation bin << 13 | key point (< OLF_GRID_MAX_KEYS = 2^13); the first word of a list also carries a flag
 constexpr unsigned PB_NONE = Best4::NONE, PB_MORE = 1u << 31;
 constexpr int PB_NOKEY = Best4::NOKEY;
-constexpr int PB_POSE = 16;                         // floats per key frame in scratch: Rcw (9), tcw (3), Ow (3), one of padding
-constexpr int PB_STATUS_INDEX = 512;                // status bit: a list index or a d_frame_matched value outside the map
-constexpr int PB_STATUS_PAIR = 2048;                // status bit: a pair was skipped, its frame indices are outside the batch or equal
-static_assert(OLF_GRID_MAX_KEYS <= (1 << 13) && PB_HISTO <= 32 && PB_K == Best4::K, "entry layout");
+static_assert(OLF_GRID_MAX_KEYS <= (1 << 13) && HISTO_LENGTH <= 32 && PB_K == Best4::K, "entry layout");
 
-struct ProjArgs {
-    olf_track_batch in;
+struct ProjArgs : FrameView {      // (capW: the 32-bit words of the closed bitmap)
     // the relocalisation form
     const uint8_t* mp_bad;         // [n_frames][cap] or NULL
     const float *mp_maxd, *mp_mind;
@@ -62,12 +57,9 @@ struct ProjArgs {
     int* frame_matched;
     int mpW;                       // 32-bit words of the spAlreadyFound bitmap per key frame
     // both
-    int n_frames, n_items, n_queries, cap, capW, nlevels;      // n_items: pairs / key frames; capW: 32-bit words of the closed bitmap
+    int n_frames, n_items, n_queries;      // n_items: pairs / key frames
     float th;
     const float* d_th;
-    float wInv, hInv;
-    float sf[OLF_MAX_LEVELS];      // mvScaleFactors
-    float thr[OLF_MAX_LEVELS];     // olf_predict_scale_thresholds
 };
 
 // a pair (relocalisation) or a key frame (loop)
@@ -86,11 +78,6 @@ struct ProjQuery {
     int level;
 };
 
-__device__ __forceinline__ int pb_count(const ProjArgs& A, int j)      // (the clamping of lb_count, local_batch.hip)
-{
-    return min(max(A.in.counts[(size_t)j * A.in.img_stride], 0), A.cap);
-}
-
 // ---- what differs between the two forms ---------------------------------------------------------------------------------------------------------------
 struct RelocForm {
     static constexpr bool kRot = true;              // the rotation histogram (:1716-1734)
@@ -99,10 +86,10 @@ struct RelocForm {
         ProjItem I = {0, 0, 0, 0, 0, 0, 0, 0.f};
         if (!item_radius(A.th, A.d_th, p, I.th)) return I;
         const int fc = A.pairs[2 * (size_t)p], fk = A.pairs[2 * (size_t)p + 1];
-        if (fc < 0 || fc >= A.n_frames || fk < 0 || fk >= A.n_frames || fc == fk) { I.state = 2; return I; }
+        if (!pair_in_batch(fc, fk, A.n_frames)) { I.state = 2; return I; }
         I.state = 1; I.tgt = fc; I.src = fk;
-        I.nT = pb_count(A, fc);
-        I.qb = p * A.cap; I.qe = I.qb + pb_count(A, fk);
+        I.nT = A.count(fc);
+        I.qb = p * A.cap; I.qe = I.qb + A.count(fk);
         I.accept = A.d_orb_dist ? A.d_orb_dist[p] : A.orb_dist;
         return I;
     }
@@ -114,11 +101,9 @@ struct RelocForm {
     // const cv::Mat dMP = pMP->GetDescriptor() (:1684) and pKF->mvKeysUn[i].angle (:1718)
     static __device__ __forceinline__ void source(const ProjArgs& A, const ProjItem& I, int i, ProjQuery& Q)
     {
-        const olf_track_batch& in = A.in;
-        const size_t cap = (size_t)A.cap, st = (size_t)in.img_stride;
-        const uint4* md = reinterpret_cast<const uint4*>(in.mp_desc ? in.mp_desc + 32 * ((size_t)I.src * cap + i) : in.desc + 32 * ((size_t)I.src * st * cap + i));
+        const uint4* md = A.point_desc(I.src, i);
         Q.a0 = md[0]; Q.a1 = md[1];
-        Q.angle = in.kps[(size_t)I.src * st * cap + i].angle;
+        Q.angle = A.keys(I.src)[i].angle;
     }
     // GetFeaturesInArea(u, v, radius, nPredictedLevel - 1, nPredictedLevel + 1) (:1679)
     static __device__ __forceinline__ void window(int level, int& lo, int& hi) { lo = level - 1; hi = level + 1; }
@@ -134,7 +119,7 @@ struct LoopForm {
         ProjItem I = {0, 0, 0, 0, 0, 0, 0, 0.f};
         if (!item_radius(A.th, A.d_th, j, I.th)) return I;
         I.state = 1; I.tgt = j; I.src = j;
-        I.nT = pb_count(A, j);
+        I.nT = A.count(j);
         A.L.range(j, I.qb, I.qe);
         I.accept = PB_TH_LOW;
         return I;
@@ -167,7 +152,7 @@ __global__ __launch_bounds__(256) void k_reloc_gate(ProjArgs A, float4* __restri
     const int p = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= A.cap) return;
     const ProjItem I = RelocForm::item(A, p);
-    if (I.state == 2 && i == 0) { nmatches[p] = -1; atomicOr(status, PB_STATUS_PAIR); }
+    if (I.state == 2 && i == 0) { nmatches[p] = -1; atomicOr(status, STATUS_PAIR); }
     const int q = p * A.cap + i;
     float4 g = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
     if (I.state == 1 && q < I.qe) {
@@ -198,17 +183,14 @@ __global__ __launch_bounds__(256) void k_loop_pose(ProjArgs A, float* __restrict
     if (j >= A.n_frames) return;
     float R[9], t[3], ow[3];
     sim3_decompose(A.Scw + 16 * (size_t)j, R, t, ow);
-    float* o = pose + (size_t)PB_POSE * j;
-    for (int k = 0; k < 9; ++k) o[k] = R[k];
-    for (int k = 0; k < 3; ++k) { o[9 + k] = t[k]; o[12 + k] = ow[k]; }
-    o[15] = 0.f;
+    pose_store(pose + (size_t)POSE_FLOATS * j, R, t, ow);
 }
 
 // set<MapPoint*> spAlreadyFound(vpMatched.begin(), vpMatched.end()) (:307-308)
 __global__ __launch_bounds__(256) void k_loop_held(ProjArgs A, unsigned* __restrict__ held, int* __restrict__ status)
 {
     const int j = blockIdx.y, idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx < pb_count(A, j)) held_mark(A.frame_matched[(size_t)j * A.cap + idx], A.map.n_mp, A.map.bad, held + (size_t)j * A.mpW, status, PB_STATUS_INDEX);
+    if (idx < A.count(j)) held_mark(A.frame_matched[(size_t)j * A.cap + idx], A.map.n_mp, A.map.bad, held + (size_t)j * A.mpW, status, STATUS_POINT_INDEX);
 }
 
 __global__ __launch_bounds__(256) void k_loop_gate(ProjArgs A, const float* __restrict__ pose, const unsigned* __restrict__ held, float4* __restrict__ gate,
@@ -221,12 +203,12 @@ __global__ __launch_bounds__(256) void k_loop_gate(ProjArgs A, const float* __re
     const int j = A.L.frame_of(e, i);
     float th;
     if (j >= 0 && item_radius(A.th, A.d_th, j, th)) {
-        if ((unsigned)i >= (unsigned)A.map.n_mp) atomicOr(status, PB_STATUS_INDEX);
+        if ((unsigned)i >= (unsigned)A.map.n_mp) atomicOr(status, STATUS_POINT_INDEX);
         // Discard Bad MapPoints and already found (:321)
         else if (!A.map.bad[i] && !((held[(size_t)j * A.mpW + (i >> 5)] >> (i & 31)) & 1u)) {
             const olf_track_batch& in = A.in;
             const float cam[5] = {in.fx, in.fy, in.cx, in.cy, in.mbf}, bounds[4] = {in.minX, in.maxX, in.minY, in.maxY};
-            const float* P = pose + (size_t)PB_POSE * j;
+            const float* P = pose + (size_t)POSE_FLOATS * j;
             float uvr[3], dist3D;
             const float maxd = A.map.maxd[i];
             if (fuse_point_gate(P, P + 9, P + 12, A.map.world + 3 * (size_t)i, A.map.normal + 3 * (size_t)i, maxd, A.map.mind[i], cam, bounds, uvr, dist3D)) {
@@ -241,14 +223,6 @@ __global__ __launch_bounds__(256) void k_loop_gate(ProjArgs A, const float* __re
 }
 
 // ---- the ordered part, one text for both forms -------------------------------------------------------------------------------------------------------------
-// the grid of the frame that is searched, as grid_walk reads it
-__device__ __forceinline__ GridView pb_grid(const ProjArgs& A, const ProjItem& I)
-{
-    const olf_track_batch& in = A.in;
-    const size_t f = (size_t)I.tgt;
-    return {in.kps + f * in.img_stride * A.cap, in.cell_offsets + f * (OLF_GRID_CELLS + 1), in.cell_index + f * A.cap, I.nT, A.cap, in.minX, in.minY, A.wInv, A.hInv};
-}
-
 template <class F>
 __device__ __forceinline__ ProjQuery pb_query(const ProjArgs& A, const ProjItem& I, int local, const float4& g)
 {
@@ -271,16 +245,11 @@ __device__ __forceinline__ bool pb_candidate(const ProjItem& I, const ProjQuery&
     int bin = 0;
     if (F::kRot) {
         bin = rot_bin(Q.angle, kp.angle);                              // (:1718-1725)
-        bin = min(max(bin, 0), PB_HISTO - 1);      // (angles outside [0, 360) index past rotHist in the reference; here they land in an end bin)
+        bin = min(max(bin, 0), HISTO_LENGTH - 1);      // (angles outside [0, 360) index past rotHist in the reference; here they land in an end bin)
     }
     key = (dist << 16) | pos;
     ent = ((unsigned)dist << 18) | ((unsigned)bin << 13) | (unsigned)j;
     return true;
-}
-
-__device__ __forceinline__ const uint4* pb_target_desc(const ProjArgs& A, const ProjItem& I)
-{
-    return reinterpret_cast<const uint4*>(A.in.desc + 32 * (size_t)I.tgt * A.in.img_stride * A.cap);
 }
 
 template <class F>
@@ -294,8 +263,8 @@ __global__ __launch_bounds__(256) void k_proj_lists(ProjArgs A, const float4* __
     const int it = F::item_of(A, q, local);                           // (passed the gate: an item that is searched)
     const ProjItem I = F::item(A, it);
     const ProjQuery Q = pb_query<F>(A, I, local, g);
-    const GridView G = pb_grid(A, I);
-    const uint4* kd = pb_target_desc(A, I);
+    const GridView G = A.grid(I.tgt, I.nT);
+    const uint4* kd = A.desc(I.tgt);
     int lo, hi;
     F::window(Q.level, lo, hi);
     unsigned out[PB_K] = {PB_NONE, PB_NONE, PB_NONE, PB_NONE};
@@ -317,24 +286,13 @@ template <class F>
 __device__ __forceinline__ unsigned pb_rescan(const ProjArgs& A, const ProjItem& I, int local, const float4& g, int lane, const unsigned* s_closed)
 {
     const ProjQuery Q = pb_query<F>(A, I, local, g);
-    const GridView G = pb_grid(A, I);
-    const uint4* kd = pb_target_desc(A, I);
+    const GridView G = A.grid(I.tgt, I.nT);
+    const uint4* kd = A.desc(I.tgt);
     int lo, hi;
     F::window(Q.level, lo, hi);
-    int best = PB_NOKEY;
-    unsigned bestEnt = PB_NONE;
-    grid_walk(G, Q.u, Q.v, Q.radius, lo, hi, lane, [&](bool take, int j2, int pos) {
-        int key = PB_NOKEY;
-        unsigned ent = PB_NONE;
-        const bool ok = take && !((s_closed[j2 >> 5] >> (j2 & 31)) & 1u) && pb_candidate<F>(I, Q, G.keys, kd, j2, pos, key, ent);
-        const int m = wave_min_i32(ok ? key : PB_NOKEY);
-        if (m < best) {                                              // (later chunks hold later scan positions: a tie is impossible, `<` as in the reference)
-            const int owner = __ffsll((long long)wave_vote(ok && key == m)) - 1;
-            best = m;
-            bestEnt = (unsigned)__shfl((int)ent, owner, 64);
-        }
+    return window_best(G, Q.u, Q.v, Q.radius, lo, hi, lane, [&](int j2, int pos, int& key, unsigned& ent) {
+        return !((s_closed[j2 >> 5] >> (j2 & 31)) & 1u) && pb_candidate<F>(I, Q, G.keys, kd, j2, pos, key, ent);
     });
-    return bestEnt;
 }
 
 // One workgroup per pair / key frame; dynamic LDS: cap ints (what a key point received in this call, -1: nothing), then capW words (closed bits).
@@ -344,7 +302,7 @@ __global__ __launch_bounds__(256) void k_proj_walk(ProjArgs A, const float4* __r
                                                    int* __restrict__ nmatches)
 {
     extern __shared__ int s_match[];
-    __shared__ int s_hist[PB_HISTO], s_n;
+    __shared__ int s_hist[HISTO_LENGTH], s_n;
     __shared__ unsigned s_reject;
     unsigned* s_closed = reinterpret_cast<unsigned*>(s_match + A.cap);
     const int it = blockIdx.x, tid = threadIdx.x, lane = tid & 63, cap = A.cap;
@@ -358,6 +316,8 @@ __global__ __launch_bounds__(256) void k_proj_walk(ProjArgs A, const float4* __r
     __syncthreads();
     if (tid < 64) {
         int n = 0, myHist = 0;                                       // lane b counts the events of rotation bin b
+        // (the traversal walk_lists states, in this kernel's own text: through walk_lists the relocalisation form's walk took 56.0 us where this takes 53.4,
+        // kernel trace on an MI355X)
         for (int c0 = I.qb; c0 < I.qe; c0 += 64) {
             const int q = c0 + lane;
             uint4 L = pb_empty();
@@ -370,13 +330,8 @@ __global__ __launch_bounds__(256) void k_proj_walk(ProjArgs A, const float4* __r
                 const unsigned x = (unsigned)__shfl((int)L.x, l, 64);
                 const unsigned e[PB_K] = {x & PB_NONE, (unsigned)__shfl((int)L.y, l, 64), (unsigned)__shfl((int)L.z, l, 64), (unsigned)__shfl((int)L.w, l, 64)};
                 const int who = __shfl(local, l, 64);
-                unsigned hit = PB_NONE;
-                bool exhausted = true;
-                for (int k = 0; k < PB_K; ++k) {
-                    if (e[k] == PB_NONE) { exhausted = false; break; }
-                    const unsigned f = e[k] & 0x1fffu;
-                    if (!((s_closed[f >> 5] >> (f & 31)) & 1u)) { hit = e[k]; exhausted = false; break; }
-                }
+                bool exhausted;
+                unsigned hit = first_open(e, exhausted, [&](unsigned f) { return !((s_closed[f >> 5] >> (f & 31)) & 1u); });
                 if (exhausted && (x & PB_MORE)) hit = pb_rescan<F>(A, I, who, gate[c0 + l], lane, s_closed);
                 if (hit != PB_NONE) {
                     // CurrentFrame.mvpMapPoints[bestIdx2] = pMP; nmatches++; rotHist[bin].push_back(bestIdx2) (:1712-1733) / vpMatched[bestIdx] = pMP;
@@ -390,20 +345,13 @@ __global__ __launch_bounds__(256) void k_proj_walk(ProjArgs A, const float4* __r
                 }
             }
         }
-        if (lane < PB_HISTO) s_hist[lane] = myHist;
+        if (lane < HISTO_LENGTH) s_hist[lane] = myHist;
         if (lane == 0) s_n = n;
     }
     __syncthreads();
     if (F::kRot) {
         if (A.checkOri) {
-            if (tid == 0) {
-                int ind1, ind2, ind3;
-                three_maxima(s_hist, ind1, ind2, ind3);
-                unsigned rej = 0;
-                int n = s_n;
-                for (int i = 0; i < PB_HISTO; i++) if (i != ind1 && i != ind2 && i != ind3) { rej |= 1u << i; n -= s_hist[i]; }
-                s_reject = rej; s_n = n;
-            }
+            if (tid == 0) { int n = s_n; s_reject = histo_reject(s_hist, n); s_n = n; }
             __syncthreads();
         }
         const unsigned rej = s_reject;
@@ -427,17 +375,6 @@ using namespace olf;
 
 namespace {
 
-// what both entries fill in the same way (wInv / hInv are the argument check's)
-void pb_common(olf_ctx* c, const olf_track_batch* in, int n_frames, float th, const float* d_th, ProjArgs& A)
-{
-    A.in = *in;
-    A.n_frames = n_frames; A.th = th; A.d_th = d_th;
-    A.cap = olf_orb_capacity(c);
-    A.capW = (A.cap + 31) / 32;
-    A.nlevels = ctx_level_scales(c, A.sf);
-    for (int l = 0; l < OLF_MAX_LEVELS; ++l) A.thr[l] = 0.f;
-}
-
 template <class F>
 void pb_ordered(const ProjArgs& A, const float4* gate, uint4* lists, int* matches, int* nmatches, hipStream_t s)
 {
@@ -455,25 +392,18 @@ int olf_search_by_projection_kf_pairs_dev(olf_ctx* c, const olf_track_batch* in,
                                           const uint8_t* d_already_found, float th, const float* d_th, int orb_dist, const int32_t* d_orb_dist,
                                           int check_orientation, int32_t* d_matches, int32_t* d_nmatches, void* stream)
 {
-    const char* who = "olf_search_by_projection_kf_pairs_dev";
     ProjArgs A = {};
     // (the per-pair arrays of a call without pairs may be NULL: nothing is required of them)
-    if (!c || !in || n_frames < 0 || n_pairs < 0 || !d_mp_maxd || !d_mp_mind || (n_pairs && (!d_pairs || !d_matches || !d_nmatches)) ||
-        !grid_scales(in->minX, in->maxX, in->minY, in->maxY, &A.wInv, &A.hInv) || !in->kps || !in->desc || !in->counts || in->img_stride < 1 ||
-        !in->cell_offsets || !in->cell_index || (!d_Tcw && !in->Tcw) || !in->mp_world) {
-        set_error(std::string(who) + ": bad argument"); return OLF_ERR_INVALID;
-    }
-    OLF_TRY(ctx_check_device(c, who));
-    const int cap = olf_orb_capacity(c);
-    if (cap > OLF_GRID_MAX_KEYS) { set_error(std::string(who) + ": more than OLF_GRID_MAX_KEYS key points per frame"); return OLF_ERR_CAPACITY; }
-    const long long nq = (long long)n_pairs * cap;
-    if (nq > 0x7fffffffLL - 256) { set_error(std::string(who) + ": more than 2^31 queries"); return OLF_ERR_CAPACITY; }
+    const bool ok = n_pairs >= 0 && d_mp_maxd && d_mp_mind && (!n_pairs || (d_pairs && d_matches && d_nmatches));
+    OLF_TRY(batch_frames(c, "olf_search_by_projection_kf_pairs_dev", ok, in, NEED_GRID | NEED_WORLD | (d_Tcw ? 0 : NEED_TCW), n_frames, nullptr, 0, n_pairs, "queries",
+                         A, &A.n_queries));
     if (n_pairs == 0 || n_frames == 0) return OLF_OK;
-    pb_common(c, in, n_frames, th, d_th, A);
+    const int cap = A.cap, nq = A.n_queries;
+    A.n_frames = n_frames; A.th = th; A.d_th = d_th;
     A.mp_bad = d_mp_bad; A.mp_maxd = d_mp_maxd; A.mp_mind = d_mp_mind;
     A.pairs = d_pairs; A.pairTcw = d_Tcw; A.cur_valid = d_cur_valid; A.already = d_already_found;
     A.d_orb_dist = d_orb_dist; A.orb_dist = orb_dist; A.checkOri = check_orientation ? 1 : 0;
-    A.n_items = n_pairs; A.n_queries = (int)nq;
+    A.n_items = n_pairs;
     OLF_TRY(ctx_level_thresholds(c, A.thr));
     hipStream_t s = ctx_stream(c, stream);
     // scratch: 32 bytes per (pair, feature): (u, v, radius, level) and the kept entries
@@ -490,34 +420,24 @@ int olf_search_by_projection_kf_pairs_dev(olf_ctx* c, const olf_track_batch* in,
 int olf_search_by_projection_sim3_batch_dev(olf_ctx* c, const olf_track_batch* in, int n_frames, const olf_local_map* map, const float* d_Scw,
                                             int32_t* d_frame_matched, float th, const float* d_th, int32_t* d_nmatches, void* stream)
 {
-    const char* who = "olf_search_by_projection_sim3_batch_dev";
     ProjArgs A = {};
-    if (!c || !in || !map || n_frames < 0 || map->n_mp < 0 || !d_Scw || !d_frame_matched || !d_nmatches ||
-        !grid_scales(in->minX, in->maxX, in->minY, in->maxY, &A.wInv, &A.hInv) || !in->kps || !in->desc || !in->counts || in->img_stride < 1 ||
-        !in->cell_offsets || !in->cell_index ||
-        (map->n_mp && (!map->world || !map->normal || !map->maxd || !map->mind || !map->desc || !map->bad)) ||
-        (map->list_offsets && (map->n_entries < 0 || (map->n_entries && !map->list_index)))) {
-        set_error(std::string(who) + ": bad argument"); return OLF_ERR_INVALID;
-    }
-    OLF_TRY(ctx_check_device(c, who));
-    const int cap = olf_orb_capacity(c);
-    if (cap > OLF_GRID_MAX_KEYS) { set_error(std::string(who) + ": more than OLF_GRID_MAX_KEYS key points per frame"); return OLF_ERR_CAPACITY; }
-    const long long ne = map->list_offsets ? (long long)map->n_entries : (long long)n_frames * map->n_mp;
-    if (ne > 0x7fffffffLL - 256) { set_error(std::string(who) + ": more than 2^31 entries"); return OLF_ERR_CAPACITY; }
+    OLF_TRY(batch_frames(c, "olf_search_by_projection_sim3_batch_dev", map && d_Scw && d_frame_matched && d_nmatches, in, NEED_GRID, n_frames, map, MAP_DESC, 0,
+                         "entries", A, &A.n_queries));
     if (n_frames == 0) return OLF_OK;
-    pb_common(c, in, n_frames, th, d_th, A);
+    const int cap = A.cap, ne = A.n_queries;
+    A.n_frames = n_frames; A.th = th; A.d_th = d_th;
     A.map = *map;
-    A.L = {map->list_offsets, map->list_index, map->n_mp, n_frames, (int)ne};
+    A.L = {map->list_offsets, map->list_index, map->n_mp, n_frames, ne};
     A.Scw = d_Scw; A.frame_matched = d_frame_matched;
     A.mpW = (map->n_mp + 31) / 32;
-    A.n_items = n_frames; A.n_queries = (int)ne;
+    A.n_items = n_frames;
     OLF_TRY(ctx_level_thresholds(c, A.thr));
     hipStream_t s = ctx_stream(c, stream);
     // scratch: 32 bytes per entry: (u, v, radius, level) and the kept entries; 64 bytes per key frame (the pose) and one bit per (key frame, map point)
     float4* gate; uint4* lists; float* pose; unsigned* held;
     const size_t bh = (size_t)n_frames * A.mpW;
     Carve k;
-    k.add(&gate, (size_t)ne); k.add(&lists, (size_t)ne); k.add(&pose, (size_t)PB_POSE * n_frames); k.add(&held, bh);
+    k.add(&gate, (size_t)ne); k.add(&lists, (size_t)ne); k.add(&pose, (size_t)POSE_FLOATS * n_frames); k.add(&held, bh);
     OLF_TRY(k.bind(c, SCRATCH_BATCH));
     hipLaunchKernelGGL(k_loop_pose, dim3((n_frames + 255) / 256), dim3(256), 0, s, A, pose);
     if (bh) OLF_HIP_CHECK(hipMemsetAsync(held, 0, bh * 4, s));

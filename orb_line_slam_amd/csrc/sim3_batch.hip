@@ -15,15 +15,13 @@
 //                     table of olf_predict_scale_thresholds; writes (u, v, level or -1), 12 bytes
 //   k_sim3_search     one wave per entry, four per workgroup; an entry that failed the gate leaves at once.  The entry index, hence pair, direction, both
 //                     frames, the level and the radius, is wave-uniform (readfirstlane).  The wave walks the window in the other key frame's grid
-//                     (grid_walk, grid_walk.hpp) with the level gate; every lane keeps its smallest key and that key's feature; one wave_min_i32, the
-//                     owner lane's feature fetched as Best4::drain fetches it; lane 0 writes vnMatch when the distance lies within TH_HIGH
+//                     (grid_walk, grid_walk.hpp) with the level gate; every lane keeps its smallest key and that key's feature; the wave's minimum
+//                     with its owner lane's feature (wave_min_fetch, grid_walk.hpp); lane 0 writes vnMatch when the distance lies within TH_HIGH
 //   k_sim3_agree      one thread per (pair, feature of kf1): vnMatch2[vnMatch1[i1]] == i1 writes vpMatches12[i1]; the count goes wave by wave into the
 //                     pair's zeroed counter with an integer atomic, so it does not depend on scheduling
-#include "grid_walk.hpp"
+#include "batch_frames.hpp"
 #include "device_math.hpp"
-#include "search_math.hpp"
 #include "staging.hpp"
-#include "../../include/orbline.h"
 
 namespace olf {
 
@@ -32,28 +30,19 @@ constexpr int SB_NOKEY = 0x7fffffff;                // above every key: distance
 constexpr int SB_POS_BITS = 20;                     // scan positions: at most OLF_GRID_COLS ranges of at most OLF_GRID_MAX_KEYS indices, malformed grids included
 constexpr int SB_XF = 32;                           // floats per pair in scratch: sR12 (9), sR21 (9), t12 (3), t21 (3), valid (1, an int), seven of padding
 constexpr int SB_XF_VALID = 24;
-constexpr int SB_STATUS_OCTAVE = 256;               // status bit: a candidate with an octave outside the context's levels was left out
-constexpr int SB_STATUS_PAIR = 2048;                // status bit: a pair was skipped, its frame indices are outside the batch or equal
 static_assert(OLF_GRID_COLS * OLF_GRID_MAX_KEYS <= (1 << SB_POS_BITS), "key layout");
 
 struct Sim3Gate { float u, v; int level; };         // level -1: nothing to search
 
-struct Sim3Args {
-    olf_track_batch in;
+struct Sim3Args : FrameView {      // (capW: the 32-bit words of vbAlreadyMatched2 per pair)
     const uint8_t* mp_bad;         // [n_frames][cap] or NULL
     const float *mp_maxd, *mp_mind;
     const int* pairs;
     const float *s12, *R12, *t12;
-    int n_frames, n_pairs, cap, nlevels, capW;      // capW: 32-bit words of vbAlreadyMatched2 per pair
-    float th, wInv, hInv;
-    float sf[OLF_MAX_LEVELS];      // mvScaleFactors
-    float thr[OLF_MAX_LEVELS];     // olf_predict_scale_thresholds
+    int n_frames, n_pairs;
+    float th;
 };
 
-__device__ __forceinline__ int sb_count(const Sim3Args& A, int j)      // (the clamping of lb_count, local_batch.hip)
-{
-    return min(max(A.in.counts[(size_t)j * A.in.img_stride], 0), A.cap);
-}
 __device__ __forceinline__ bool sb_valid(const float* __restrict__ xf, int p) { return __float_as_int(xf[(size_t)SB_XF * p + SB_XF_VALID]) != 0; }
 
 __global__ __launch_bounds__(256) void k_sim3_transform(Sim3Args A, float* __restrict__ xf, int* __restrict__ nfound, int* __restrict__ status)
@@ -63,9 +52,9 @@ __global__ __launch_bounds__(256) void k_sim3_transform(Sim3Args A, float* __res
     float* o = xf + (size_t)SB_XF * p;
     for (int k = 0; k < SB_XF; ++k) o[k] = 0.f;
     const int f1 = A.pairs[2 * (size_t)p], f2 = A.pairs[2 * (size_t)p + 1];
-    if (f1 < 0 || f1 >= A.n_frames || f2 < 0 || f2 >= A.n_frames || f1 == f2) {
+    if (!pair_in_batch(f1, f2, A.n_frames)) {
         nfound[p] = -1;
-        atomicOr(status, SB_STATUS_PAIR);
+        atomicOr(status, STATUS_PAIR);
         return;
     }
     float R[9], t[3], sR12[9], sR21[9], t21[3];
@@ -86,10 +75,10 @@ __global__ __launch_bounds__(256) void k_sim3_mark(Sim3Args A, const float* __re
     const size_t row = (size_t)p * A.cap;
     vn1[row + i] = -1; vn2[row + i] = -1;
     const int f1 = A.pairs[2 * (size_t)p], f2 = A.pairs[2 * (size_t)p + 1];
-    if (i >= sb_count(A, f1)) return;
+    if (i >= A.count(f1)) return;
     // vbAlreadyMatched2[idx2] = true for idx2 = pMP->GetIndexInKeyFrame(pKF2) in [0, N2) (:1137-1143)
     const int idx2 = matches12[row + i];
-    if (idx2 >= 0 && idx2 < sb_count(A, f2)) atomicOr(&already2[(size_t)p * A.capW + (idx2 >> 5)], 1u << (idx2 & 31));
+    if (idx2 >= 0 && idx2 < A.count(f2)) atomicOr(&already2[(size_t)p * A.capW + (idx2 >> 5)], 1u << (idx2 & 31));
 }
 
 __global__ __launch_bounds__(256) void k_sim3_gate(Sim3Args A, const float* __restrict__ xf, const int* __restrict__ matches12,
@@ -105,7 +94,7 @@ __global__ __launch_bounds__(256) void k_sim3_gate(Sim3Args A, const float* __re
         const int f1 = A.pairs[2 * (size_t)p], f2 = A.pairs[2 * (size_t)p + 1];
         const int src = dir ? f2 : f1;
         const size_t s = (size_t)src * A.cap + i;
-        if (i < sb_count(A, src)) {
+        if (i < A.count(src)) {
             const olf_track_batch& in = A.in;
             // if(!pMP || vbAlreadyMatched[i]) continue; if(pMP->isBad()) continue (:1154-1158, :1234-1238)
             const bool holds = !in.mp_valid || in.mp_valid[s];
@@ -137,14 +126,11 @@ __global__ __launch_bounds__(256) void k_sim3_search(Sim3Args A, const Sim3Gate*
     const int p = e / per, r = e - p * per, dir = r >= A.cap ? 1 : 0, i = r - dir * A.cap;
     const int f1 = A.pairs[2 * (size_t)p], f2 = A.pairs[2 * (size_t)p + 1];      // (passed the gate: both are frames of the batch)
     const int src = dir ? f2 : f1, dst = dir ? f1 : f2;
-    const olf_track_batch& in = A.in;
-    const size_t cap = (size_t)A.cap, st = (size_t)in.img_stride;
-    const olf_keypoint* keys = in.kps + (size_t)dst * st * cap;
-    const uint4* kd = reinterpret_cast<const uint4*>(in.desc + 32 * (size_t)dst * st * cap);
-    const GridView G = {keys, in.cell_offsets + (size_t)dst * (OLF_GRID_CELLS + 1), in.cell_index + (size_t)dst * cap, sb_count(A, dst), A.cap, in.minX, in.minY,
-                        A.wInv, A.hInv};
+    const olf_keypoint* keys = A.keys(dst);
+    const uint4* kd = A.desc(dst);
+    const GridView G = A.grid(dst);                                   // (here, beside the entry's other loads: FrameView::grid)
     // const cv::Mat dMP = pMP->GetDescriptor() (:1199, :1279)
-    const uint4* md = reinterpret_cast<const uint4*>(in.mp_desc ? in.mp_desc + 32 * ((size_t)src * cap + i) : in.desc + 32 * ((size_t)src * st * cap + i));
+    const uint4* md = A.point_desc(src, i);
     const uint4 a0 = md[0], a1 = md[1];
     // Search in a radius (:1191, :1271)
     const float radius = A.th * A.sf[level];
@@ -159,17 +145,13 @@ __global__ __launch_bounds__(256) void k_sim3_search(Sim3Args A, const Sim3Gate*
         const int key = (dist << SB_POS_BITS) | pos;
         if (key < bestKey) { bestKey = key; bestJ = j2; }
     });
-    const int m = wave_min_i32(bestKey);
+    int m, idx = -1;
+    wave_min_fetch(bestKey, bestJ, SB_NOKEY, m, idx);
     const bool anyBad = wave_vote(badOct) != 0;
-    int idx = -1;
-    if (m != SB_NOKEY) {
-        const int owner = __ffsll((long long)wave_vote(bestKey == m)) - 1;       // (the keys are distinct: they end in the scan position)
-        idx = __shfl(bestJ, owner, 64);
-    }
     if (lane == 0) {
-        if (anyBad) atomicOr(status, SB_STATUS_OCTAVE);
+        if (anyBad) atomicOr(status, STATUS_OCTAVE);
         // if(bestDist<=TH_HIGH) vnMatch[i] = bestIdx (:1223-1226, :1303-1306)
-        if (idx >= 0 && (m >> SB_POS_BITS) <= SB_TH_HIGH) (dir ? vn2 : vn1)[(size_t)p * cap + i] = idx;
+        if (idx >= 0 && (m >> SB_POS_BITS) <= SB_TH_HIGH) (dir ? vn2 : vn1)[(size_t)p * A.cap + i] = idx;
     }
 }
 
@@ -180,7 +162,7 @@ __global__ __launch_bounds__(256) void k_sim3_agree(Sim3Args A, const float* __r
     if (!sb_valid(xf, p)) return;                                     // (block-uniform)
     const size_t row = (size_t)p * A.cap;
     bool ok = false;
-    if (i1 < sb_count(A, A.pairs[2 * (size_t)p])) {
+    if (i1 < A.count(A.pairs[2 * (size_t)p])) {
         // Check agreement (:1312-1325)
         const int idx2 = vn1[row + i1];
         if (idx2 >= 0 && idx2 < A.cap && vn2[row + idx2] == i1) { matches12[row + i1] = idx2; ok = true; }
@@ -199,28 +181,17 @@ int olf_search_by_sim3_pairs_dev(olf_ctx* c, const olf_track_batch* in, int n_fr
                                  int n_pairs, const int32_t* d_pairs, const float* d_s12, const float* d_R12, const float* d_t12, float th,
                                  int32_t* d_matches12, int32_t* d_vn_match1, int32_t* d_vn_match2, int32_t* d_nfound, void* stream)
 {
-    const char* who = "olf_search_by_sim3_pairs_dev";
     Sim3Args A;
+    int ne;
     // (the per-pair arrays of a call without pairs may be NULL: nothing is required of them)
-    if (!c || !in || n_frames < 0 || n_pairs < 0 || !d_mp_maxd || !d_mp_mind ||
-        (n_pairs && (!d_pairs || !d_s12 || !d_R12 || !d_t12 || !d_matches12 || !d_nfound)) || !grid_scales(in->minX, in->maxX, in->minY, in->maxY, &A.wInv, &A.hInv) || !in->kps || !in->desc || !in->counts || in->img_stride < 1 ||
-        !in->cell_offsets || !in->cell_index || !in->Tcw || !in->mp_world) {
-        set_error(std::string(who) + ": bad argument"); return OLF_ERR_INVALID;
-    }
-    OLF_TRY(ctx_check_device(c, who));
-    const int cap = olf_orb_capacity(c);
-    if (cap > OLF_GRID_MAX_KEYS) { set_error(std::string(who) + ": more than OLF_GRID_MAX_KEYS key points per frame"); return OLF_ERR_CAPACITY; }
-    const long long ne = 2LL * n_pairs * cap;
-    if (ne > 0x7fffffffLL - 256) { set_error(std::string(who) + ": more than 2^31 entries"); return OLF_ERR_CAPACITY; }
+    const bool ok = n_pairs >= 0 && d_mp_maxd && d_mp_mind && (!n_pairs || (d_pairs && d_s12 && d_R12 && d_t12 && d_matches12 && d_nfound));
+    OLF_TRY(batch_frames(c, "olf_search_by_sim3_pairs_dev", ok, in, NEED_GRID | NEED_TCW | NEED_WORLD, n_frames, nullptr, 0, 2LL * n_pairs, "entries", A, &ne));
     if (n_pairs == 0 || n_frames == 0) return OLF_OK;
-    A.in = *in;
+    const int cap = A.cap;
     A.mp_bad = d_mp_bad; A.mp_maxd = d_mp_maxd; A.mp_mind = d_mp_mind;
     A.pairs = d_pairs; A.s12 = d_s12; A.R12 = d_R12; A.t12 = d_t12;
-    A.n_frames = n_frames; A.n_pairs = n_pairs; A.cap = cap;
-    A.nlevels = ctx_level_scales(c, A.sf);
-    A.capW = (cap + 31) / 32;
+    A.n_frames = n_frames; A.n_pairs = n_pairs;
     A.th = th;
-    for (int l = 0; l < OLF_MAX_LEVELS; ++l) A.thr[l] = 0.f;
     OLF_TRY(ctx_level_thresholds(c, A.thr));
     hipStream_t s = ctx_stream(c, stream);
     // scratch: 128 bytes and one bit per feature of the capacity per pair; 12 bytes per (pair, direction, feature); 4 bytes per (pair, feature) for each

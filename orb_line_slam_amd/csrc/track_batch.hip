@@ -15,40 +15,33 @@
 //                   there is no capacity to exceed; then the rotation histogram (ComputeThreeMaxima, :1749-1790) and the output rows
 //   k_unproject_stereo  Frame::UnprojectStereo, one thread per feature
 #include <algorithm>
-#include "grid_walk.hpp"
+#include "batch_frames.hpp"
 #include "device_math.hpp"
-#include "search_math.hpp"
 #include "staging.hpp"
-#include "../../include/orbline.h"
 
 namespace olf {
 
-constexpr int TB_TH_HIGH = 100, TB_HISTO = HISTO_LENGTH;      // src/ORBmatcher.cc:39-41
+constexpr int TB_TH_HIGH = 100;                     // src/ORBmatcher.cc:39
 constexpr int TB_K = 4;                             // entries kept per query (one uint4)
 // a list entry: distance << 18 | rotation bin << 13 | CurrentFrame feature (< OLF_GRID_MAX_KEYS = 2^13); the first word of a list also carries two flags
 constexpr unsigned TB_NONE = Best4::NONE, TB_OBS = 1u << 30, TB_MORE = 1u << 31;
 // per CurrentFrame feature in the walk: bit b = an event of rotation bin b landed here, then
 constexpr unsigned TB_SEEN = 1u << 30, TB_BLOCKED = 1u << 31;
 constexpr int TB_NOKEY = Best4::NOKEY;
-constexpr int TB_STATUS_OCTAVE = 256;               // status bit: a pair was skipped, its last frame holds an octave outside the context's levels
-static_assert(OLF_GRID_MAX_KEYS <= (1 << 13) && TB_HISTO <= 30 && TB_K == Best4::K, "entry and word layouts");
+static_assert(OLF_GRID_MAX_KEYS <= (1 << 13) && HISTO_LENGTH <= 30 && TB_K == Best4::K, "entry and word layouts");
 
-struct TrackArgs {
-    olf_track_batch in;
-    int cap, nlevels, bMono;
+struct TrackArgs : FrameView {
+    int bMono;
     float th;
     const float* d_th;
-    float wInv, hInv;
-    float sf[OLF_MAX_LEVELS];      // mvScaleFactors
 };
 
 struct TbPair {
     const olf_keypoint *kL, *kC;
     const uint4 *dL, *dC;
     const float *urC, *TcwC, *world;
-    const int *offs, *idx;
     const uint8_t *valid, *obs, *outl;
-    int nL, nC;
+    int nL;
     bool fwd, bwd;
     float th;
 };
@@ -62,21 +55,18 @@ struct TbQuery {
 __device__ __forceinline__ TbPair tb_pair(const TrackArgs& A, int j, float th)
 {
     const olf_track_batch& in = A.in;
-    const size_t cap = (size_t)A.cap, fL = (size_t)j, fC = (size_t)j + 1, st = (size_t)in.img_stride;
+    const size_t cap = (size_t)A.cap, fL = (size_t)j, fC = (size_t)j + 1;
     TbPair P;
-    P.kL = in.kps + fL * st * cap; P.kC = in.kps + fC * st * cap;
-    P.dL = reinterpret_cast<const uint4*>(in.mp_desc ? in.mp_desc + 32 * fL * cap : in.desc + 32 * fL * st * cap);
-    P.dC = reinterpret_cast<const uint4*>(in.desc + 32 * fC * st * cap);
-    P.urC = in.uright + fC * cap;
+    P.kL = A.keys(j); P.kC = A.keys(j + 1);
+    P.dL = A.point_desc(j, 0);
+    P.dC = A.desc(j + 1);
+    P.urC = A.uright(j + 1);
     P.TcwC = in.Tcw + 16 * fC;
     P.world = in.mp_world + 3 * fL * cap;
-    P.offs = in.cell_offsets + fC * (OLF_GRID_CELLS + 1);
-    P.idx = in.cell_index + fC * cap;
     P.valid = in.mp_valid ? in.mp_valid + fL * cap : nullptr;
     P.obs = in.mp_obs ? in.mp_obs + fL * cap : nullptr;
     P.outl = in.outlier ? in.outlier + fL * cap : nullptr;
-    P.nL = min(max(in.counts[fL * st], 0), A.cap);
-    P.nC = min(max(in.counts[fC * st], 0), A.cap);
+    P.nL = A.count(j);
     P.th = th;
     // twc = -Rcw.t() * tcw;  tlc = Rlw * twc + tlw                                   (:1341-1349)
     float twc[3], tlc[3];
@@ -115,13 +105,6 @@ __device__ __forceinline__ TbQuery tb_query(const TbPair& P, const TrackArgs& A,
     return q;
 }
 
-// the CurrentFrame's grid as grid_walk reads it; built at the walk, so that the four floats hold scalar registers only there (held from the start of
-// k_track_lists they cost it four more, and 0.5 ms per call on an MI355X: DESIGN 4.5)
-__device__ __forceinline__ GridView tb_grid(const TbPair& P, const TrackArgs& A)
-{
-    return {P.kC, P.offs, P.idx, P.nC, A.cap, A.in.minX, A.in.minY, A.wInv, A.hInv};
-}
-
 // the state-free tests on one candidate (:1409-1423): the mvuRight gate and the distance.  true: the candidate could be chosen (distance <= TH_HIGH);
 // key orders such candidates as the reference's `dist < bestDist` scan does, ent is the list entry
 __device__ __forceinline__ bool tb_candidate(const TbPair& P, const TrackArgs& A, const TbQuery& q, const uint4& a0, const uint4& a1, float angL, int j, int pos,
@@ -136,7 +119,7 @@ __device__ __forceinline__ bool tb_candidate(const TbPair& P, const TrackArgs& A
     const int dist = ham256(a0, a1, P.dC[2 * (size_t)j], P.dC[2 * (size_t)j + 1]);
     if (dist > TB_TH_HIGH) return false;
     int bin = rot_bin(angL, P.kC[j].angle);                                     // (:1434-1441)
-    bin = min(max(bin, 0), TB_HISTO - 1);      // (angles outside [0, 360) index past rotHist in the reference; here they land in an end bin)
+    bin = min(max(bin, 0), HISTO_LENGTH - 1);      // (angles outside [0, 360) index past rotHist in the reference; here they land in an end bin)
     key = (dist << 16) | pos;
     ent = ((unsigned)dist << 18) | ((unsigned)bin << 13) | (unsigned)j;
     return true;
@@ -153,12 +136,12 @@ __global__ __launch_bounds__(256) void k_track_lists(TrackArgs A, uint4* __restr
     unsigned out[TB_K] = {TB_NONE, TB_NONE, TB_NONE, TB_NONE};
     int cnt = 0;
     if (q.state == 2) {
-        if (lane == 0) { atomicOr(status, TB_STATUS_OCTAVE); pairBad[j] = 1; }
+        if (lane == 0) { atomicOr(status, STATUS_OCTAVE); pairBad[j] = 1; }
     } else if (q.state == 1) {
         const uint4 a0 = P.dL[2 * (size_t)i], a1 = P.dL[2 * (size_t)i + 1];
         const float angL = P.kL[i].angle;
         Best4 best;
-        grid_walk(tb_grid(P, A), q.u, q.v, q.radius, q.minLevel, q.maxLevel, lane, [&](bool take, int j2, int pos) {
+        grid_walk(A.grid(j + 1), q.u, q.v, q.radius, q.minLevel, q.maxLevel, lane, [&](bool take, int j2, int pos) {
             int key = TB_NOKEY;
             unsigned ent = TB_NONE;
             const bool ok = take && tb_candidate(P, A, q, a0, a1, angL, j2, pos, key, ent);
@@ -175,27 +158,16 @@ __global__ __launch_bounds__(256) void k_track_lists(TrackArgs A, uint4* __restr
     }
 }
 
-// the query of last-frame feature i again, with the blocked test inside the scan: the entry the reference would choose now, or TB_NONE
-__device__ __forceinline__ unsigned tb_rescan(const TbPair& P, const TrackArgs& A, int i, int lane, const unsigned* s_word)
+// the query of last-frame feature i of pair j again, with the blocked test inside the scan: the entry the reference would choose now, or TB_NONE
+__device__ __forceinline__ unsigned tb_rescan(const TbPair& P, const TrackArgs& A, int j, int i, int lane, const unsigned* s_word)
 {
     const TbQuery q = tb_query(P, A, i);
     if (q.state != 1) return TB_NONE;
     const uint4 a0 = P.dL[2 * (size_t)i], a1 = P.dL[2 * (size_t)i + 1];
     const float angL = P.kL[i].angle;
-    int best = TB_NOKEY;
-    unsigned bestEnt = TB_NONE;
-    grid_walk(tb_grid(P, A), q.u, q.v, q.radius, q.minLevel, q.maxLevel, lane, [&](bool take, int j2, int pos) {
-        int key = TB_NOKEY;
-        unsigned ent = TB_NONE;
-        const bool ok = take && !(s_word[j2] & TB_BLOCKED) && tb_candidate(P, A, q, a0, a1, angL, j2, pos, key, ent);
-        const int m = wave_min_i32(ok ? key : TB_NOKEY);
-        if (m < best) {                                              // (later chunks hold later scan positions: a tie is impossible, `<` as in the reference)
-            const int owner = __ffsll((long long)wave_vote(ok && key == m)) - 1;
-            best = m;
-            bestEnt = (unsigned)__shfl((int)ent, owner, 64);
-        }
+    return window_best(A.grid(j + 1), q.u, q.v, q.radius, q.minLevel, q.maxLevel, lane, [&](int j2, int pos, int& key, unsigned& ent) {
+        return !(s_word[j2] & TB_BLOCKED) && tb_candidate(P, A, q, a0, a1, angL, j2, pos, key, ent);
     });
-    return bestEnt;
 }
 
 // One workgroup per pair; dynamic LDS: cap words, then cap uint16 (the last frame's index a feature holds).
@@ -203,7 +175,7 @@ __global__ __launch_bounds__(256) void k_track_walk(TrackArgs A, const uint4* __
                                                     int* __restrict__ matches, int* __restrict__ match12, int* __restrict__ nmatches)
 {
     extern __shared__ unsigned s_word[];
-    __shared__ int s_hist[TB_HISTO], s_n;
+    __shared__ int s_hist[HISTO_LENGTH], s_n;
     __shared__ unsigned s_reject;
     unsigned short* s_last = reinterpret_cast<unsigned short*>(s_word + A.cap);
     const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, cap = A.cap;
@@ -217,51 +189,29 @@ __global__ __launch_bounds__(256) void k_track_walk(TrackArgs A, const uint4* __
     if (tid < 64) {
         int n = 0, myHist = 0;                                       // lane b counts the events of rotation bin b
         int* m12 = match12 ? match12 + (size_t)j * cap : nullptr;
-        for (int c0 = 0; c0 < P.nL; c0 += 64) {
-            const int i = c0 + lane;
-            uint4 L = make_uint4(TB_NONE, TB_NONE, TB_NONE, TB_NONE);
-            if (i < P.nL) L = lists[(size_t)j * cap + i];
-            unsigned long long todo = wave_vote((L.x & TB_NONE) != TB_NONE);
-            while (todo) {
-                const int l = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                const unsigned x = (unsigned)__shfl((int)L.x, l, 64);
-                const unsigned e[TB_K] = {x & TB_NONE, (unsigned)__shfl((int)L.y, l, 64), (unsigned)__shfl((int)L.z, l, 64), (unsigned)__shfl((int)L.w, l, 64)};
-                unsigned hit = TB_NONE;
-                bool exhausted = true;
-                for (int k = 0; k < TB_K; ++k) {
-                    if (e[k] == TB_NONE) { exhausted = false; break; }
-                    if (!(s_word[e[k] & 0x1fffu] & TB_BLOCKED)) { hit = e[k]; exhausted = false; break; }
-                }
-                if (exhausted && (x & TB_MORE)) hit = tb_rescan(P, A, c0 + l, lane, s_word);
-                if (hit != TB_NONE) {
-                    // mvpMapPoints[bestIdx2] = pMP; match12.insert(...); nmatches++; rotHist[bin].push_back(bestIdx2)           (:1427-1445, :1574-1590)
-                    const int i2 = (int)(hit & 0x1fffu), bin = (int)((hit >> 13) & 31u);
-                    unsigned w = s_word[i2];
-                    const bool first = !(w & TB_SEEN);
-                    w |= TB_SEEN;
-                    if (x & TB_OBS) w |= TB_BLOCKED;
-                    if (checkOri) { w |= 1u << bin; if (lane == bin) ++myHist; }
-                    s_word[i2] = w;                                  // (every lane stores the same word: the next query's read is ordered behind it)
-                    s_last[i2] = (unsigned short)(c0 + l);
-                    if (first && m12 && lane == 0) m12[i2] = c0 + l;
-                    ++n;
-                }
-            }
-        }
-        if (lane < TB_HISTO) s_hist[lane] = myHist;
+        walk_lists(lists + (size_t)j * cap, 0, P.nL, lane, [](int, bool) {}, [&](int i, int, unsigned x, const unsigned (&e)[TB_K]) {
+            bool exhausted;
+            unsigned hit = first_open(e, exhausted, [&](unsigned f) { return !(s_word[f] & TB_BLOCKED); });
+            if (exhausted && (x & TB_MORE)) hit = tb_rescan(P, A, j, i, lane, s_word);
+            if (hit == TB_NONE) return;
+            // mvpMapPoints[bestIdx2] = pMP; match12.insert(...); nmatches++; rotHist[bin].push_back(bestIdx2)           (:1427-1445, :1574-1590)
+            const int i2 = (int)(hit & 0x1fffu), bin = (int)((hit >> 13) & 31u);
+            unsigned w = s_word[i2];
+            const bool first = !(w & TB_SEEN);
+            w |= TB_SEEN;
+            if (x & TB_OBS) w |= TB_BLOCKED;
+            if (checkOri) { w |= 1u << bin; if (lane == bin) ++myHist; }
+            s_word[i2] = w;                                          // (every lane stores the same word: the next query's read is ordered behind it)
+            s_last[i2] = (unsigned short)i;
+            if (first && m12 && lane == 0) m12[i2] = i;
+            ++n;
+        });
+        if (lane < HISTO_LENGTH) s_hist[lane] = myHist;
         if (lane == 0) s_n = n;
     }
     __syncthreads();
     if (checkOri) {
-        if (tid == 0) {
-            int ind1, ind2, ind3;
-            three_maxima(s_hist, ind1, ind2, ind3);
-            unsigned rej = 0;
-            int n = s_n;
-            for (int i = 0; i < TB_HISTO; i++) if (i != ind1 && i != ind2 && i != ind3) { rej |= 1u << i; n -= s_hist[i]; }
-            s_reject = rej; s_n = n;
-        }
+        if (tid == 0) { int n = s_n; s_reject = histo_reject(s_hist, n); s_n = n; }
         __syncthreads();
     }
     const unsigned rej = s_reject;
@@ -283,7 +233,7 @@ __global__ __launch_bounds__(256) void k_unproject_stereo(const olf_keypoint* __
     if (i >= cap) return;
     const size_t at = (size_t)f * cap + i;
     float o[3] = {0.f, 0.f, 0.f};
-    const int n = min(max(counts[(size_t)f * img_stride], 0), cap);
+    const int n = frame_count(f, counts, img_stride, cap);
     const float z = i < n ? depth[at] : 0.f;
     if (z > 0) {
         const olf_keypoint& kp = kps[(size_t)f * img_stride * cap + i];
@@ -304,20 +254,11 @@ int olf_search_by_projection_batch_dev(olf_ctx* c, const olf_track_batch* in, in
                                        int32_t* d_matches, int32_t* d_match12, int32_t* d_nmatches, void* stream)
 {
     TrackArgs A;
-    if (!c || !in || n_frames < 0 || !d_matches || !d_nmatches || !in->kps || !in->desc || !in->counts || in->img_stride < 1 || !in->uright ||
-        !in->cell_offsets || !in->cell_index || !in->Tcw || !in->mp_world || !grid_scales(in->minX, in->maxX, in->minY, in->maxY, &A.wInv, &A.hInv)) {
-        set_error("olf_search_by_projection_batch_dev: bad argument"); return OLF_ERR_INVALID;
-    }
-    OLF_TRY(ctx_check_device(c, "olf_search_by_projection_batch_dev"));
-    const int cap = olf_orb_capacity(c);
-    if (cap > OLF_GRID_MAX_KEYS) {
-        set_error("olf_search_by_projection_batch_dev: more than OLF_GRID_MAX_KEYS key points per frame (a list entry holds 13 index bits)"); return OLF_ERR_CAPACITY;
-    }
+    OLF_TRY(batch_frames(c, "olf_search_by_projection_batch_dev", d_matches && d_nmatches, in, NEED_GRID | NEED_URIGHT | NEED_TCW | NEED_WORLD, n_frames, nullptr, 0,
+                         0, "", A, nullptr));
     if (n_frames < 2) return OLF_OK;
-    const int n_pairs = n_frames - 1;
-    A.in = *in;
-    A.cap = cap; A.bMono = bMono ? 1 : 0; A.th = th; A.d_th = d_th;
-    A.nlevels = ctx_level_scales(c, A.sf);
+    const int n_pairs = n_frames - 1, cap = A.cap;
+    A.bMono = bMono ? 1 : 0; A.th = th; A.d_th = d_th;
     uint4* lists; int* pairBad;
     Carve k;
     k.add(&lists, (size_t)n_pairs * cap); k.add(&pairBad, n_pairs);

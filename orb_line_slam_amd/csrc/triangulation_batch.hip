@@ -12,26 +12,20 @@
 //                                query and chunk.  A node's segment longer than a wave is walked in chunks, chunk outside, query inside, so the lanes are loaded
 //                                once; the minima of the chunks meet in the query's LDS word, and a later chunk's positions are larger, so the tie rule holds
 //                                across chunks.  Then the rotation histogram in integer counters, ComputeThreeMaxima, and the row.
-#include "olf_internal.hpp"
+#include "batch_frames.hpp"
 #include "device_math.hpp"
-#include "search_math.hpp"
-#include "../../include/orbline.h"
 
 namespace olf {
 
 constexpr int TRI_TH_LOW = 50;                      // src/ORBmatcher.cc:40
 constexpr int TRI_WAVES = 4;
 constexpr int TRI_NOKEY = 0x7fffffff;
-constexpr int TRI_STATUS_OCTAVE = 256;              // status bit: a pair was skipped, a candidate of key frame 2 holds an octave outside the context's levels
-constexpr int TRI_STATUS_PAIR = 2048;               // status bit: a pair was skipped, its frame indices are outside the batch or equal
 
-struct TriArgs {
-    olf_track_batch in;
-    int cap, nlevels, n_frames, onlyStereo, checkOri;
+struct TriArgs : FrameView {       // (no grid is read: capW, wInv, hInv and thr stay zero)
+    int n_frames, onlyStereo, checkOri;
     const int* pairs;
     const float* F12;
     const float* Cw;
-    float sf[OLF_MAX_LEVELS];      // mvScaleFactors
 };
 
 // dynamic LDS: cap words (a query's best key, then its match), then one rotation bin byte per key-frame-1 feature
@@ -44,23 +38,19 @@ __global__ __launch_bounds__(64 * TRI_WAVES) void k_search_for_triangulation(Tri
     const int cap = A.cap, p = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     uint8_t* binOf = reinterpret_cast<uint8_t*>(s_key + cap);
     const int f1 = A.pairs[2 * (size_t)p], f2 = A.pairs[2 * (size_t)p + 1];
-    if (f1 < 0 || f1 >= A.n_frames || f2 < 0 || f2 >= A.n_frames || f1 == f2) {       // (block-uniform)
-        if (tid == 0) { nmatches[p] = -1; atomicOr(status, TRI_STATUS_PAIR); }
+    if (!pair_in_batch(f1, f2, A.n_frames)) {                        // (block-uniform)
+        if (tid == 0) { nmatches[p] = -1; atomicOr(status, STATUS_PAIR); }
         return;
     }
     const olf_track_batch& in = A.in;
-    const size_t st = (size_t)in.img_stride;
     const unsigned long long* SK = sortedAll + (size_t)f1 * cap;
     const unsigned long long* SF = sortedAll + (size_t)f2 * cap;
     // mp_valid == NULL: every feature holds a map point, nothing is searched
     const int mK = in.mp_valid ? mAll[f1] : 0, mF = mAll[f2];
-    const int N1 = min(max(in.counts[(size_t)f1 * st], 0), cap);
-    const olf_keypoint* k1 = in.kps + (size_t)f1 * st * cap;
-    const olf_keypoint* k2 = in.kps + (size_t)f2 * st * cap;
-    const uint4* d1 = reinterpret_cast<const uint4*>(in.desc) + 2 * (size_t)f1 * st * cap;
-    const uint4* d2 = reinterpret_cast<const uint4*>(in.desc) + 2 * (size_t)f2 * st * cap;
-    const float* u1 = in.uright + (size_t)f1 * cap;
-    const float* u2 = in.uright + (size_t)f2 * cap;
+    const int N1 = A.count(f1);
+    const olf_keypoint *k1 = A.keys(f1), *k2 = A.keys(f2);
+    const uint4 *d1 = A.desc(f1), *d2 = A.desc(f2);
+    const float *u1 = A.uright(f1), *u2 = A.uright(f2);
     const uint8_t* v1 = in.mp_valid + (size_t)f1 * cap;      // (read only when mK > 0)
     const uint8_t* v2 = in.mp_valid + (size_t)f2 * cap;
     const float* F12 = A.F12 + 9 * (size_t)p;
@@ -127,7 +117,7 @@ __global__ __launch_bounds__(64 * TRI_WAVES) void k_search_for_triangulation(Tri
     }
     __syncthreads();
     if (s_bad) {
-        if (tid == 0) { nmatches[p] = -1; atomicOr(status, TRI_STATUS_OCTAVE); }
+        if (tid == 0) { nmatches[p] = -1; atomicOr(status, STATUS_OCTAVE); }
         return;
     }
     // a key becomes its match: matches12[idx1] = bestIdx2, and the rotation bin (:767-786)
@@ -170,7 +160,7 @@ int launch_search_for_triangulation_batch(const olf_track_batch& in, int n_frame
                                           const float* d_F12, const float* d_Cw, int only_stereo, int check_ori, const unsigned long long* d_sorted,
                                           const int* d_m, int* d_status, int* d_matches12, int* d_nmatches, hipStream_t s)
 {
-    TriArgs A;
+    TriArgs A = {};
     A.in = in;
     A.cap = cap; A.nlevels = nlevels; A.n_frames = n_frames; A.onlyStereo = only_stereo; A.checkOri = check_ori;
     A.pairs = d_pairs; A.F12 = d_F12; A.Cw = d_Cw;

@@ -10,6 +10,7 @@ import orb_line_slam_amd as ola
 from orb_line_slam_amd import _lib, matcher
 from orb_line_slam_amd._lib import KEYPOINT_DTYPE, OLF_ERR_CAPACITY, lib
 from bow_pairs_scenes import KF_FRAME, KF_KF
+from status_text import describes
 
 pytestmark = pytest.mark.gpu
 
@@ -159,14 +160,14 @@ def test_pair_list_edges_in_one_call(ctx, form):
     assert (m[-1] == -7).all() and nm[-1] == -7              # nothing past either output array
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert e.value.code == OLF_ERR_CAPACITY and "flags=2048" in str(e.value)
+    assert e.value.code == OLF_ERR_CAPACITY and "flags=2048" in str(e.value) and describes(e.value, 2048)
     ctx.poll_status()                                       # reported once, then clear
     for bad in S.EDGE_BAD[:3]:                              # each kind alone: -1, n_frames, equal
         m, nm = dev.search(G, [bad], form, 1)
         assert nm[0] == -1 and (m == -7).all()
         with pytest.raises(ola.OlfError) as e:
             ctx.poll_status()
-        assert "flags=2048" in str(e.value)
+        assert "flags=2048" in str(e.value) and describes(e.value, 2048)
     m, nm = dev.search(G, [(5, 4)], form, 1, n_pairs=0)      # n_pairs = 0 writes nothing
     assert (m == -7).all() and (nm == -7).all()
     ctx.poll_status()

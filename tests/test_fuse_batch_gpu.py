@@ -13,6 +13,7 @@ import pytest
 import orb_line_slam_amd as ola
 from orb_line_slam_amd import _lib, matcher
 from orb_line_slam_amd._lib import KEYPOINT_DTYPE, OLF_ERR_CAPACITY, OLF_ERR_INVALID, lib
+from status_text import describes
 
 pytestmark = pytest.mark.gpu
 
@@ -552,7 +553,7 @@ def test_malformed_input(ctx, oracle):
     assert_equal(dev.search(3.0), exp, 2)
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert e.value.code == OLF_ERR_CAPACITY and "flags=512" in str(e.value)
+    assert e.value.code == OLF_ERR_CAPACITY and "flags=512" in str(e.value) and describes(e.value, 512)
     ctx.poll_status()                                         # reported once, then clear
     # a held index outside the map counts as "holds nothing"
     kf = types.SimpleNamespace(**vars(kfs[1]))
@@ -562,7 +563,7 @@ def test_malformed_input(ctx, oracle):
     assert_equal(DeviceBatch(ctx, [kf], mp).search(3.0), exp1, 1)
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert "flags=512" in str(e.value)
+    assert "flags=512" in str(e.value) and describes(e.value, 512)
     # octave -1 under predicted level 0: the best candidate of the point is the malformed one; without it the second one wins
     rng = np.random.default_rng(808)
     mp1 = _one_point_scene(rng, 0)
@@ -577,7 +578,7 @@ def test_malformed_input(ctx, oracle):
     assert (res[0][0], res[1][0]) == (1, 6) and res[0][1] == exp_good[0][1] and res[1][1] == exp_good[1][1]
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert "flags=256" in str(e.value)
+    assert "flags=256" in str(e.value) and describes(e.value, 256)
     geom = ola.MapPointGeom(mp1.world, mp1.normal, mp1.maxd, mp1.mind, mp1.desc)
     with pytest.raises(ola.OlfError) as e:
         ola.ORBmatcher(0.6, True, context=ctx).FuseSearch(view(malformed), geom, 3.0, np.zeros(3, f32))

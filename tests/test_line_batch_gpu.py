@@ -10,6 +10,7 @@ import line_scenes as ls
 import orb_line_slam_amd as ola
 from orb_line_slam_amd import _lib, matcher
 from orb_line_slam_amd._lib import KEYLINE_DTYPE, OLF_ERR_CAPACITY, OLF_ERR_INVALID, lib
+from status_text import describes
 
 pytestmark = pytest.mark.gpu
 
@@ -158,7 +159,7 @@ def test_malformed_indices(oracle, ctx):
     assert_local(res, frames, exp1, ctx.line_capacity)
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert e.value.code == OLF_ERR_CAPACITY and "flags=1024" in str(e.value)
+    assert e.value.code == OLF_ERR_CAPACITY and "flags=1024" in str(e.value) and describes(e.value, 1024)
     ctx.poll_status()
     fml = [fr.frame_ml.copy() for fr in frames]
     hold = np.flatnonzero(fml[0] >= 0)[:7]
@@ -168,7 +169,7 @@ def test_malformed_indices(oracle, ctx):
     assert_local(DeviceLines(ctx, frames, mp, lists, frame_ml=fml).search(), frames, exp2, ctx.line_capacity)
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert "flags=1024" in str(e.value)
+    assert "flags=1024" in str(e.value) and describes(e.value, 1024)
 
 
 # ---- 3: frame-to-frame -------------------------------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import pytest
 import orb_line_slam_amd as ola
 from orb_line_slam_amd import _lib, matcher
 from orb_line_slam_amd._lib import KEYPOINT_DTYPE, OLF_ERR_CAPACITY, OLF_ERR_INVALID, lib
+from status_text import describes
 
 pytestmark = pytest.mark.gpu
 
@@ -558,7 +559,7 @@ def test_malformed_indices(oracle, ctx):
         assert_frame(res, j, exp[j], cap)
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert e.value.code == OLF_ERR_CAPACITY and "flags=512" in str(e.value)
+    assert e.value.code == OLF_ERR_CAPACITY and "flags=512" in str(e.value) and describes(e.value, 512)
     ctx.poll_status()
     # mvpMapPoints: a value beyond the map holds nothing
     hold = np.flatnonzero(frame_mp[1] >= 0)[:7]
@@ -570,7 +571,7 @@ def test_malformed_indices(oracle, ctx):
     assert_frame(res, 1, exp1, cap)
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert "flags=512" in str(e.value)
+    assert "flags=512" in str(e.value) and describes(e.value, 512)
 
 
 def test_error_codes(ctx):

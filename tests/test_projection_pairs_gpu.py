@@ -12,6 +12,7 @@ from orb_line_slam_amd import _lib, matcher
 from orb_line_slam_amd._lib import KEYPOINT_DTYPE, OLF_ERR_CAPACITY, lib
 import projection_pairs_scenes as S
 from projection_pairs_scenes import BOUNDS, CAM, FILL, f32
+from status_text import describes
 
 pytestmark = pytest.mark.gpu
 
@@ -226,7 +227,7 @@ def test_reloc_malformed_and_skipped_pairs(ctx, reloc):
         assert res[1][p] == FILL and (res[0][p] == FILL).all()
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert e.value.code == OLF_ERR_CAPACITY and "flags=2048" in str(e.value)
+    assert e.value.code == OLF_ERR_CAPACITY and "flags=2048" in str(e.value) and describes(e.value, 2048)
     ctx.poll_status()                                         # reported once, then clear
     res = dev.search([], [], [], [], 10.0, 100, 1)
     assert (res[0] == FILL).all() and (res[1] == FILL).all()
@@ -352,7 +353,7 @@ def test_loop_malformed_indices_and_skipped_frames(ctx, loop, oracle):
             assert np.array_equal(res[0][j], fms[j]) and res[1][j] == FILL, j
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert "flags=512" in str(e.value)
+    assert "flags=512" in str(e.value) and describes(e.value, 512)
     ctx.poll_status()
     res = dev.search(s.Scw, s.lists, s.fms, 10.0, n_frames=0)
     assert np.array_equal(res[0][:7], np.stack(s.fms)) and (res[1] == FILL).all()

@@ -9,6 +9,7 @@ from orb_line_slam_amd import _lib, matcher
 from orb_line_slam_amd._lib import KEYPOINT_DTYPE, OLF_ERR_CAPACITY, lib
 import sim3_pairs_scenes as S
 from sim3_pairs_scenes import BOUNDS, CAM, FILL_M12, FILL_VN, f32
+from status_text import describes
 
 pytestmark = pytest.mark.gpu
 
@@ -176,7 +177,7 @@ def test_malformed_pairs(ctx, batch):
         assert res[0][p].tobytes() == rows0[p].tobytes() and (res[1][p] == FILL_VN).all() and (res[2][p] == FILL_VN).all()
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert e.value.code == OLF_ERR_CAPACITY and "flags=2048" in str(e.value)
+    assert e.value.code == OLF_ERR_CAPACITY and "flags=2048" in str(e.value) and describes(e.value, 2048)
     ctx.poll_status()                                         # reported once, then clear
     res = dev.search([], [], [], 7.5)
     assert (res[0] == FILL_M12).all() and (res[1] == FILL_VN).all() and (res[2] == FILL_VN).all() and (res[3] == FILL_VN).all()
@@ -203,7 +204,7 @@ def test_octave_outside_the_levels(ctx, oracle):
     assert res[1][0, 0] == 0 and res[1][1, 0] == 1 and (res[2][:, :2] == -1).all() and list(res[3]) == [0, 0]
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert "flags=256" in str(e.value)
+    assert "flags=256" in str(e.value) and describes(e.value, 256)
     ctx.poll_status()
 
 

@@ -11,6 +11,7 @@ import pytest
 import orb_line_slam_amd as ola
 from orb_line_slam_amd import _lib, matcher, synth
 from orb_line_slam_amd._lib import KEYPOINT_DTYPE, OLF_ERR_CAPACITY, OLF_ERR_INVALID, lib
+from status_text import describes
 
 pytestmark = pytest.mark.gpu
 
@@ -615,7 +616,7 @@ def test_octave_outside_the_levels(oracle, ctx):
     assert int(out[2][0].item()) == -1 and bool((out[0][0] == 7).all()) and bool((out[1][0] == 7).all())
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert e.value.code == OLF_ERR_CAPACITY and "flags=256" in str(e.value)
+    assert e.value.code == OLF_ERR_CAPACITY and "flags=256" in str(e.value) and describes(e.value, 256)
     ctx.poll_status()                                       # reported once, then clear
     exp = oracle_pair(oracle, sf, fr[1], fr[2], 7.0)
     assert exp[0] >= 100

@@ -9,6 +9,7 @@ import pytest
 import orb_line_slam_amd as ola
 from orb_line_slam_amd import _lib, matcher
 from orb_line_slam_amd._lib import KEYPOINT_DTYPE, OLF_ERR_CAPACITY, lib
+from status_text import describes
 
 pytestmark = pytest.mark.gpu
 
@@ -393,17 +394,17 @@ def test_edges_in_one_call(ctx):
     assert (m[-1] == -7).all() and nm[-1] == -7            # nothing past either output array
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert e.value.code == OLF_ERR_CAPACITY and "flags=%d" % (256 | 2048) in str(e.value)
+    assert e.value.code == OLF_ERR_CAPACITY and "flags=%d" % (256 | 2048) in str(e.value) and describes(e.value, 256, 2048)
     ctx.poll_status()                                       # reported once, then clear
     # each refusal alone sets its own bit
     m, nm = dev.search(G, [(7, 1)], 2)
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert nm[0] == -1 and "flags=2048" in str(e.value)
+    assert nm[0] == -1 and "flags=2048" in str(e.value) and describes(e.value, 2048)
     m, nm = dev.search(G, [(4, 6)], 2)
     with pytest.raises(ola.OlfError) as e:
         ctx.poll_status()
-    assert nm[0] == -1 and "flags=256" in str(e.value)
+    assert nm[0] == -1 and "flags=256" in str(e.value) and describes(e.value, 256)
     # n_pairs = 0 writes nothing; mp_valid = NULL searches nothing
     m, nm = dev.search(G, [(5, 4)], 2, n_pairs=0)
     assert (m == -7).all() and (nm == -7).all()
