@@ -1,11 +1,13 @@
-// search_host.cpp -- host side of the ORBmatcher searches behind the C ABI: the three every-frame ones (olf_search_by_projection,
-// olf_search_by_bow, olf_search_local_map, fed by olf_is_in_frustum) and the relocalisation / LocalMapping / LoopClosing ones
+// search_host.cpp -- host side of the ORBmatcher searches behind the C ABI, and nothing else: the every-frame ones (olf_search_by_projection[_match12],
+// olf_search_for_initialization, olf_search_by_bow, olf_search_local_map) and the relocalisation / LocalMapping / LoopClosing ones
 // (olf_search_by_projection_kf, olf_search_by_bow_kf, olf_search_for_triangulation, olf_fuse_search, olf_fuse_search_sim3,
-// olf_search_by_sim3).  Split of the reference's loops, as SURVEY 8(b) / App. C.7 prescribe:
+// olf_search_by_projection_sim3, olf_search_by_sim3).  The host entries that feed them without searching (olf_is_in_frustum and its kin) are in
+// host_geometry.cpp.  Split of the reference's loops, as SURVEY 8(b) / App. C.7 prescribe:
 //   1. candidate generation on the host, exactly as the reference walks them (Frame::GetFeaturesInArea over the 64 x 48 grid,
 //      src/Frame.cc:517-570; the merge of two DBoW2 feature vectors, src/ORBmatcher.cc:176-203),
 //   2. every DescriptorDistance of the search in one k_match_candidates launch (match.hip),
 //   3. the reference's greedy resolution, which depends on the map points assigned so far, on the host in the reference's order.
+// What the searches share is stated once at the top: Grid (1), bow_queries (1), Batch (2), RotHist (the rejection that ends 3) and the argument tests.
 // Map mutations (MapPoint::Replace / AddObservation in the Fuse functions) stay with the caller: they never feed back into a search.
 // Float expressions are written as the reference writes them (src/ORBmatcher.cc, float unless a double literal promotes them); cv::Mat
 // products of CV_32F operands accumulate in double and round once; the library is built with -ffp-contract=off.
@@ -102,15 +104,67 @@ struct Batch {
     }
 };
 
-// ORBmatcher::ComputeThreeMaxima on the sizes of the reference's rotHist vectors
-void three_maxima(const std::vector<int>* histo, int& ind1, int& ind2, int& ind3)
+// The reference's rotHist (src/ORBmatcher.cc:1434-1441 and its siblings): the matches of a search by rotation bin, and the rejection that ends the
+// search -- every match outside the three fullest bins (ORBmatcher::ComputeThreeMaxima on the sizes of the vectors) is undone, bin by bin and within a
+// bin in the order the matches were made; `undo` takes one index and does the search's own reset.
+struct RotHist {
+    std::vector<int> rotHist[HISTO_LENGTH];
+    void add(float angle1, float angle2, int idx) { rotHist[rot_bin(angle1, angle2)].push_back(idx); }
+    template <class Undo>
+    void reject(int check_orientation, Undo&& undo) const
+    {
+        if (!check_orientation) return;
+        int counts[HISTO_LENGTH], ind1, ind2, ind3;
+        for (int i = 0; i < HISTO_LENGTH; i++) counts[i] = (int)rotHist[i].size();
+        three_maxima(counts, ind1, ind2, ind3);
+        for (int b = 0; b < HISTO_LENGTH; b++) {
+            if (b == ind1 || b == ind2 || b == ind3) continue;
+            for (int idx : rotHist[b]) undo(idx);
+        }
+    }
+};
+
+// merge of two DBoW2 feature vectors: calls f(a, b) for every node present in both; the two ordered maps are walked in step (:176-203, :537-543, :683-689)
+template <class F>
+void for_common_nodes(const olf_frame_view& A, const olf_frame_view& B, F&& f)
 {
-    int counts[HISTO_LENGTH];
-    for (int i = 0; i < HISTO_LENGTH; i++) counts[i] = (int)histo[i].size();
-    olf::three_maxima(counts, ind1, ind2, ind3);
+    int a = 0, b = 0;
+    while (a < A.fv_n && b < B.fv_n) {
+        if (A.fv_nodes[a] == B.fv_nodes[b]) { f(a, b); ++a; ++b; }
+        else if (A.fv_nodes[a] < B.fv_nodes[b]) ++a;
+        else ++b;
+    }
 }
 
-// (rot_bin; dot3_small, rot_apply, camera_centre -- convention C.12: search_math.hpp)
+// The queries of the three searches that walk two feature vectors: every feature of A under a common node that `eligible` lets through, against all of
+// B's features under that node.  false: a feature index of A lies outside A (that feature is left out).
+template <class E>
+bool bow_queries(const olf_frame_view& A, const olf_frame_view& B, Batch& q, E&& eligible)
+{
+    bool inside = true;
+    for_common_nodes(A, B, [&](int a, int b) {
+        for (int p = A.fv_offsets[a]; p < A.fv_offsets[a + 1]; ++p) {
+            const int idxA = A.fv_features[p];
+            if (idxA < 0 || idxA >= A.n) { inside = false; continue; }
+            if (!eligible(idxA)) continue;
+            q.cand.insert(q.cand.end(), B.fv_features + B.fv_offsets[b], B.fv_features + B.fv_offsets[b + 1]);
+            q.add(idxA, A.desc + 32 * (size_t)idxA);
+        }
+    });
+    return inside;
+}
+// the candidates are features of B
+bool cand_inside(const Batch& q, const olf_frame_view& B)
+{
+    for (int idxB : q.cand) if (idxB < 0 || idxB >= B.n) return false;
+    return true;
+}
+
+// (rot_bin; dot3_small, rot_apply, camera_centre -- convention C.12; r3_apply; sim3_decompose, sim3_pair_transforms, sim3_point_gate: search_math.hpp)
+// (predict_scale: predict_scale.hpp)
+float log_scale_factor(const olf_frame_view& f) { return olf::log_scale_factor(f.scale_factors, f.n_levels); }
+
+// ---- the argument tests --------------------------------------------------------------------------------------------------------------------------
 int bad_grid() { set_error("the view's grid_offsets / grid_index do not describe its n features (orbline_types.h: Frame::mGrid as two arrays)"); return OLF_ERR_INVALID; }
 bool bad_view(const olf_frame_view* f, bool needs_pose)
 {
@@ -118,6 +172,16 @@ bool bad_view(const olf_frame_view* f, bool needs_pose)
 }
 // views whose scale tables are indexed by a predicted pyramid level (MapPoint::PredictScale) or by a key point's octave
 bool bad_levels(const olf_frame_view* f) { return f->n_levels < 1 || f->n_levels > OLF_MAX_LEVELS || !f->scale_factors; }
+// a feature vector that is named but not there; and one that is that or has a negative length
+bool fv_missing(const olf_frame_view* v) { return v->fv_n && (!v->fv_nodes || !v->fv_offsets || !v->fv_features); }
+bool bad_fv(const olf_frame_view* v) { return v->fv_n < 0 || fv_missing(v); }
+// the state planes of a key frame whose map points are projected: mp_valid, mp_bad and the points' position, descriptor and distance range
+bool bad_kf_points(const olf_frame_view* k) { return k->n && (!k->mp_valid || !k->mp_bad || !k->mp_world || !k->mp_desc || !k->mp_maxd || !k->mp_mind); }
+// the arrays of a list of map points (the Fuse family)
+bool bad_points(int n_mp, const float* world, const float* normal, const float* maxd, const float* mind, const uint8_t* desc)
+{
+    return n_mp && (!world || !normal || !maxd || !mind || !desc);
+}
 
 // Both SearchByProjection(Frame, Frame) overloads: src/ORBmatcher.cc:1330-1472 and, with match12, :1474-1618.  match12 models the reference's
 // map<int, int>: match12.insert(pair(bestIdx2, i)) keeps the FIRST last-frame index a current feature was matched with (:1577; a feature whose
@@ -169,7 +233,7 @@ int search_by_projection_frames(olf_ctx* c, const olf_frame_view* cur, const olf
     }
     OLF_TRY(q.run(c, cur->desc, cur->n));
 
-    std::vector<int> rotHist[HISTO_LENGTH];
+    RotHist hist;
     int n = 0;
     for (size_t k = 0; k < q.owner.size(); ++k) {
         const int i = q.owner[k];
@@ -192,23 +256,73 @@ int search_by_projection_frames(olf_ctx* c, const olf_frame_view* cur, const olf
             matches[bestIdx2] = i;
             if (match12 && match12[bestIdx2] < 0) match12[bestIdx2] = i;
             n++;
-            if (check_orientation) rotHist[rot_bin(last->keys[i].angle, cur->keys[bestIdx2].angle)].push_back(bestIdx2);
+            if (check_orientation) hist.add(last->keys[i].angle, cur->keys[bestIdx2].angle, bestIdx2);
         }
     }
-    if (check_orientation) {
-        int ind1, ind2, ind3;
-        three_maxima(rotHist, ind1, ind2, ind3);
-        for (int b = 0; b < HISTO_LENGTH; b++) {
-            if (b == ind1 || b == ind2 || b == ind3) continue;
-            for (int j : rotHist[b]) { cur->mp_valid[j] = 0; matches[j] = -1; if (match12) match12[j] = -1; n--; }
-        }
-    }
+    hist.reject(check_orientation, [&](int j) { cur->mp_valid[j] = 0; matches[j] = -1; if (match12) match12[j] = -1; n--; });
     *nmatches = n;
+    return OLF_OK;
+}
+
+// per map point: gates, window, candidates.  Rcw9 / tcw3 / Ow3: camera pose; stereo_gate: the chi-square test of the plain Fuse.
+int fuse_core(olf_ctx* c, const char* who, const olf_frame_view* kf, const float* Rcw9, const float* tcw3, const float* Ow3, int n_mp,
+              const uint8_t* skip, const float* world, const float* normal, const float* maxd, const float* mind, const uint8_t* desc, float th,
+              bool stereo_gate, int none_dist, int32_t* best_idx, int32_t* best_dist, uint8_t* matched = nullptr, int32_t* kf_match = nullptr,
+              int32_t* nmatches = nullptr)
+{
+    // matched != nullptr: SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:292-405) -- key points that hold a match are
+    // skipped (:378), a point whose best distance is <= TH_LOW takes its key point at once (:397-401), so later points see it taken
+    if (bad_levels(kf)) { set_error(std::string(who) + ": n_levels / scale_factors missing"); return OLF_ERR_INVALID; }
+    const float logSF = log_scale_factor(*kf);
+    const Grid grid(*kf);
+    if (!grid.ok) return bad_grid();
+    Batch q;
+    struct Meta { float uvr[3]; int level; };
+    std::vector<Meta> meta;
+    int taken = 0;
+    const float cam[5] = {kf->fx, kf->fy, kf->cx, kf->cy, kf->mbf}, bounds[4] = {kf->minX, kf->maxX, kf->minY, kf->maxY};
+    for (int i = 0; i < n_mp; ++i) {
+        if (best_idx) { best_idx[i] = -1; best_dist[i] = none_dist; }
+        if (skip && skip[i]) continue;
+        // the gates on the point (fuse_point_gate, search_math.hpp)
+        Meta m;
+        float dist3D;
+        if (!fuse_point_gate(Rcw9, tcw3, Ow3, world + 3 * (size_t)i, normal + 3 * (size_t)i, maxd[i], mind[i], cam, bounds, m.uvr, dist3D)) continue;
+        m.level = predict_scale(maxd[i], dist3D, logSF, kf->n_levels);
+        const float radius = th * kf->scale_factors[m.level];
+        if (!grid.area(m.uvr[0], m.uvr[1], radius, -1, -1, q.cand)) continue;
+        q.add(i, desc + 32 * (size_t)i);
+        meta.push_back(m);
+    }
+    const int rc = q.run(c, kf->desc, kf->n);
+    if (rc != OLF_OK) return rc;
+    for (size_t k = 0; k < q.owner.size(); ++k) {
+        const Meta& m = meta[k];
+        int bestDist = none_dist, bestIdx = -1;
+        for (int p = q.offs[k]; p < q.offs[k + 1]; ++p) {
+            const int idx = q.cand[p];
+            if (matched && matched[idx]) continue;
+            const olf_keypoint& kp = kf->keys[idx];
+            const int kpLevel = kp.octave;
+            if (!fuse_level_ok(kpLevel, m.level)) continue;
+            if (stereo_gate) {
+                if (kpLevel < 0 || kpLevel >= kf->n_levels) { set_error(std::string(who) + ": octave outside mvScaleFactors"); return OLF_ERR_INVALID; }
+                if (!fuse_chi2_ok(m.uvr, kp.x, kp.y, kf->uright[idx], kf->scale_factors[kpLevel])) continue;
+            }
+            const int dist = q.dist[p];
+            if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
+        }
+        if (best_idx) { best_idx[q.owner[k]] = bestIdx; best_dist[q.owner[k]] = bestDist; }
+        if (matched && bestDist <= TH_LOW) { matched[bestIdx] = 1; kf_match[bestIdx] = q.owner[k]; ++taken; }
+    }
+    if (nmatches) *nmatches = taken;
     return OLF_OK;
 }
 }  // namespace
 
 extern "C" {
+
+// ---- the every-frame searches ---------------------------------------------------------------------------------------------------------------------
 
 int olf_search_by_projection(olf_ctx* c, const olf_frame_view* cur, const olf_frame_view* last, float th, int bMono, int check_orientation,
                              int32_t* matches, int32_t* nmatches)
@@ -244,7 +358,7 @@ int olf_search_for_initialization(olf_ctx* c, const olf_frame_view* f1, const ol
     OLF_TRY(q.run(c, f2->desc, f2->n));
     // the resolution depends on the matches made so far (vMatchedDistance): replayed in F1 order                             (:431-486)
     std::vector<int> matchedDistance((size_t)f2->n, INT_MAX), matches21((size_t)f2->n, -1);
-    std::vector<int> rotHist[HISTO_LENGTH];
+    RotHist hist;
     int n = 0;
     for (size_t k = 0; k < q.owner.size(); ++k) {
         const int i1 = q.owner[k];
@@ -261,17 +375,10 @@ int olf_search_for_initialization(olf_ctx* c, const olf_frame_view* f1, const ol
             matches21[bestIdx2] = i1;
             matchedDistance[bestIdx2] = bestDist;
             n++;
-            if (check_orientation) rotHist[rot_bin(f1->keys[i1].angle, f2->keys[bestIdx2].angle)].push_back(i1);
+            if (check_orientation) hist.add(f1->keys[i1].angle, f2->keys[bestIdx2].angle, i1);
         }
     }
-    if (check_orientation) {
-        int ind1, ind2, ind3;
-        three_maxima(rotHist, ind1, ind2, ind3);
-        for (int b = 0; b < HISTO_LENGTH; b++) {
-            if (b == ind1 || b == ind2 || b == ind3) continue;
-            for (int idx1 : rotHist[b]) if (matches12[idx1] >= 0) { matches12[idx1] = -1; n--; }
-        }
-    }
+    hist.reject(check_orientation, [&](int idx1) { if (matches12[idx1] >= 0) { matches12[idx1] = -1; n--; } });      // (a later match may already have undone it)
     for (int i1 = 0; i1 < f1->n; ++i1)                                                       // "Update prev matched"          (:516-519)
         if (matches12[i1] >= 0) { prev_matched[2 * i1] = f2->keys[matches12[i1]].x; prev_matched[2 * i1 + 1] = f2->keys[matches12[i1]].y; }
     *nmatches = n;
@@ -281,32 +388,20 @@ int olf_search_for_initialization(olf_ctx* c, const olf_frame_view* f1, const ol
 int olf_search_by_bow(olf_ctx* c, const olf_frame_view* kf, const olf_frame_view* f, float nnratio, int check_orientation, int32_t* matched,
                       int32_t* nmatches)
 {
-    if (!c || bad_view(kf, false) || bad_view(f, false) || !matched || !nmatches || (kf->n && (!kf->mp_valid || !kf->mp_bad)) ||
-        (kf->fv_n && (!kf->fv_nodes || !kf->fv_offsets || !kf->fv_features)) || (f->fv_n && (!f->fv_nodes || !f->fv_offsets || !f->fv_features))) {
+    if (!c || bad_view(kf, false) || bad_view(f, false) || !matched || !nmatches || (kf->n && (!kf->mp_valid || !kf->mp_bad)) || fv_missing(kf) ||
+        fv_missing(f)) {
         set_error("olf_search_by_bow: bad argument"); return OLF_ERR_INVALID;
     }
     for (int i = 0; i < f->n; ++i) matched[i] = -1;
     *nmatches = 0;
-    // the two ordered maps are walked in step; only nodes present in both contribute (:176-203, :273-281)
+    // only nodes present in both contribute (:176-203, :273-281)
     Batch q;
-    int a = 0, b = 0;
-    while (a < kf->fv_n && b < f->fv_n) {
-        if (kf->fv_nodes[a] == f->fv_nodes[b]) {
-            for (int p = kf->fv_offsets[a]; p < kf->fv_offsets[a + 1]; ++p) {
-                const int realIdxKF = kf->fv_features[p];
-                if (realIdxKF < 0 || realIdxKF >= kf->n) { set_error("olf_search_by_bow: feature index outside the key frame"); return OLF_ERR_INVALID; }
-                if (!kf->mp_valid[realIdxKF]) continue;
-                if (kf->mp_bad[realIdxKF]) continue;
-                q.cand.insert(q.cand.end(), f->fv_features + f->fv_offsets[b], f->fv_features + f->fv_offsets[b + 1]);
-                q.add(realIdxKF, kf->desc + 32 * (size_t)realIdxKF);
-            }
-            ++a; ++b;
-        } else if (kf->fv_nodes[a] < f->fv_nodes[b]) ++a;
-        else ++b;
+    if (!bow_queries(*kf, *f, q, [&](int realIdxKF) { return kf->mp_valid[realIdxKF] && !kf->mp_bad[realIdxKF]; })) {
+        set_error("olf_search_by_bow: feature index outside the key frame"); return OLF_ERR_INVALID;
     }
     OLF_TRY(q.run(c, f->desc, f->n));
 
-    std::vector<int> rotHist[HISTO_LENGTH];
+    RotHist hist;
     int n = 0;
     for (size_t k = 0; k < q.owner.size(); ++k) {
         const int realIdxKF = q.owner[k];
@@ -322,19 +417,12 @@ int olf_search_by_bow(olf_ctx* c, const olf_frame_view* kf, const olf_frame_view
         if (bestDist1 <= TH_LOW) {
             if (static_cast<float>(bestDist1) < nnratio * static_cast<float>(bestDist2)) {
                 matched[bestIdxF] = realIdxKF;
-                if (check_orientation) rotHist[rot_bin(kf->keys[realIdxKF].angle, f->keys[bestIdxF].angle)].push_back(bestIdxF);
+                if (check_orientation) hist.add(kf->keys[realIdxKF].angle, f->keys[bestIdxF].angle, bestIdxF);
                 n++;
             }
         }
     }
-    if (check_orientation) {
-        int ind1, ind2, ind3;
-        three_maxima(rotHist, ind1, ind2, ind3);
-        for (int bb = 0; bb < HISTO_LENGTH; bb++) {
-            if (bb == ind1 || bb == ind2 || bb == ind3) continue;
-            for (int j : rotHist[bb]) { matched[j] = -1; n--; }
-        }
-    }
+    hist.reject(check_orientation, [&](int j) { matched[j] = -1; n--; });
     *nmatches = n;
     return OLF_OK;
 }
@@ -396,183 +484,12 @@ int olf_search_local_map(olf_ctx* c, const olf_frame_view* f, int n_mp, const ui
     return OLF_OK;
 }
 
-}  // extern "C"
-
 // ---- LocalMapping / LoopClosing / relocalisation searches ------------------------------------------------------------------------
-
-namespace {
-// merge of two DBoW2 feature vectors: calls f(a, b) for every node present in both (:537-543, :683-689)
-template <class F>
-void for_common_nodes(const olf_frame_view& A, const olf_frame_view& B, F&& f)
-{
-    int a = 0, b = 0;
-    while (a < A.fv_n && b < B.fv_n) {
-        if (A.fv_nodes[a] == B.fv_nodes[b]) { f(a, b); ++a; ++b; }
-        else if (A.fv_nodes[a] < B.fv_nodes[b]) ++a;
-        else ++b;
-    }
-}
-
-bool bad_fv(const olf_frame_view* v) { return v->fv_n < 0 || (v->fv_n && (!v->fv_nodes || !v->fv_offsets || !v->fv_features)); }
-
-// (r3_apply: search_math.hpp)
-// (predict_scale: predict_scale.hpp)
-float log_scale_factor(const olf_frame_view& f) { return olf::log_scale_factor(f.scale_factors, f.n_levels); }
-// (sim3_pair_transforms, sim3_point_gate: search_math.hpp)
-}  // namespace
-
-extern "C" {
-
-int olf_is_in_frustum(const olf_frame_view* f, int n_mp, const float* world, const float* normal, const float* maxd, const float* mind,
-                      float viewing_cos_limit, uint8_t* track_in_view, int32_t* track_scale_level, float* track_view_cos, float* track_proj3)
-{
-    if (!f || !f->Tcw || !f->scale_factors || f->n_levels < 1 || n_mp < 0 ||
-        (n_mp && (!world || !normal || !maxd || !mind || !track_in_view || !track_scale_level || !track_view_cos || !track_proj3))) {
-        set_error("olf_is_in_frustum: bad argument"); return OLF_ERR_INVALID;
-    }
-    float Ow[3];
-    camera_centre(f->Tcw, Ow);                                   // mOw, Frame::UpdatePoseMatrices (src/Frame.cc:380-386)
-    const float logSF = log_scale_factor(*f);
-    for (int i = 0; i < n_mp; ++i) {
-        track_in_view[i] = 0;
-        const float* P = world + 3 * (size_t)i;
-        // 3D in camera coordinates
-        float Pc[3];
-        rot_apply(f->Tcw, P, 1.0f, Pc);
-        const float PcX = Pc[0], PcY = Pc[1], PcZ = Pc[2];
-        // Check positive depth
-        if (PcZ < 0.0f) continue;
-        // Project in image and check it is not outside
-        const float invz = 1.0f / PcZ;
-        const float u = f->fx * PcX * invz + f->cx, v = f->fy * PcY * invz + f->cy;
-        if (u < f->minX || u > f->maxX) continue;
-        if (v < f->minY || v > f->maxY) continue;
-        // Check distance is in the scale invariance region of the MapPoint
-        const float maxDistance = 1.2f * maxd[i], minDistance = 0.8f * mind[i];
-        float PO[3]; double nrm = 0, dot = 0;
-        for (int k = 0; k < 3; ++k) { PO[k] = P[k] - Ow[k]; nrm += (double)PO[k] * (double)PO[k]; dot += (double)PO[k] * (double)normal[3 * (size_t)i + k]; }
-        const float dist = (float)std::sqrt(nrm);
-        if (dist < minDistance || dist > maxDistance) continue;
-        // Check viewing angle
-        const float viewCos = (float)(dot / dist);
-        if (viewCos < viewing_cos_limit) continue;
-        // Predict scale in the image; data used by the tracking
-        track_scale_level[i] = predict_scale(maxd[i], dist, logSF, f->n_levels);
-        track_in_view[i] = 1;
-        track_proj3[3 * (size_t)i] = u; track_proj3[3 * (size_t)i + 1] = v; track_proj3[3 * (size_t)i + 2] = u - f->mbf * invz;
-        track_view_cos[i] = viewCos;
-    }
-    return OLF_OK;
-}
-
-// bool Frame::isInFrustum_l(MapLine *pML, float viewingCosLimit), src/Frame.cc:446-515: both end points through project_closed (search_math.hpp), the start
-// point first.  mnTrackangle (:512) is read by commented-out code only (src/Tracking.cc:1991-1997) and is not produced.
-int olf_is_in_frustum_l(const olf_frame_view* f, int n_ml, const float* world6, uint8_t* in_view, float* proj4)
-{
-    if (!f || !f->Tcw || n_ml < 0 || (n_ml && (!world6 || !in_view || !proj4))) { set_error("olf_is_in_frustum_l: bad argument"); return OLF_ERR_INVALID; }
-    const float cam[4] = {f->fx, f->fy, f->cx, f->cy}, bounds[4] = {f->minX, f->maxX, f->minY, f->maxY};
-    for (int i = 0; i < n_ml; ++i) {
-        in_view[i] = 0;
-        float s[2], e[2];
-        if (!project_closed(f->Tcw, world6 + 6 * (size_t)i, cam, bounds, s)) continue;
-        if (!project_closed(f->Tcw, world6 + 6 * (size_t)i + 3, cam, bounds, e)) continue;
-        in_view[i] = 1;                                       // mbTrackInView; mTrackProjsX, mTrackProjsY, mTrackProjeX, mTrackProjeY
-        float* p = proj4 + 4 * (size_t)i;
-        p[0] = s[0]; p[1] = s[1]; p[2] = e[0]; p[3] = e[1];
-    }
-    return OLF_OK;
-}
-
-// The loop of Tracking::SearchLocalPointsAndLines over matches_12 (src/Tracking.cc:1974-2016) and n_inliers_ls (:2021-2023) for one frame.
-int olf_local_lines_assign(int n_in_view, int32_t* m12, const int32_t* map_index, const float* proj4, const olf_keyline* kls, int n_lines, const float* ldisp,
-                           float minX, float maxX, float minY, float maxY, int n_ml, const uint8_t* obs, int32_t* frame_ml, int32_t* n_inliers)
-{
-    if (n_in_view < 0 || n_lines < 0 || n_ml < 0 || !n_inliers || (n_in_view && (!m12 || !map_index || !proj4 || !obs)) || (n_lines && (!kls || !ldisp || !frame_ml))) {
-        set_error("olf_local_lines_assign: bad argument"); return OLF_ERR_INVALID;
-    }
-    for (int i1 = 0; i1 < n_in_view; ++i1)
-        if (m12[i1] >= n_lines || map_index[i1] < 0 || map_index[i1] >= n_ml) { set_error("olf_local_lines_assign: index out of range"); return OLF_ERR_INVALID; }
-    for (int i2 = 0; i2 < n_lines; ++i2)
-        if (frame_ml[i2] >= n_ml) { set_error("olf_local_lines_assign: a held map line outside the map"); return OLF_ERR_INVALID; }
-    const double deltaWidth = (double)(maxX - minX) * 0.1, deltaHeight = (double)(maxY - minY) * 0.1;
-    for (int i1 = 0; i1 < n_in_view; ++i1) {
-        const int i2 = m12[i1];
-        if (i2 < 0) continue;
-        if (line_is_mono(ldisp, i2)) continue;
-        if (frame_ml[i2] >= 0 && obs[frame_ml[i2]]) continue;               // mvpMapLines[i2]->Observations() > 0, :1981-1983
-        const float* p = proj4 + 4 * (size_t)i1;                            // mTrackProjsX, sY, eX, eY of mvpLocalMapLines_InFrustum[i1]
-        if (line_moved(kls[i2], p[0], p[1], p[2], p[3], deltaWidth, deltaHeight)) { m12[i1] = -1; continue; }
-        frame_ml[i2] = map_index[i1];
-    }
-    int n = 0;
-    for (int i2 = 0; i2 < n_lines; ++i2) n += frame_ml[i2] >= 0 ? 1 : 0;
-    *n_inliers = n;
-    return OLF_OK;
-}
-
-// The frame-to-frame line tracking of Tracking::TrackWithMotionModelWithLine (src/Tracking.cc:1305-1349; skip_null = 1, gates = 1, pos_frac = 0.1) and
-// of TrackReferenceKeyFrameWithLine (:976-1020; skip_null = 0, gates = 0: `if(false)`, 0.3 unused) behind match(): the fill with NULL, the loop, n_inliers_ls.
-int olf_track_lines_assign(int n_last, int32_t* m12, const olf_keyline* kls_last, const int32_t* last_ml, int n_cur, const olf_keyline* kls_cur,
-                           const float* ldisp_cur, float minX, float maxX, float minY, float maxY, int skip_null, int gates, double delta_angle, double pos_frac,
-                           int32_t* cur_ml, int32_t* n_inliers)
-{
-    if (n_last < 0 || n_cur < 0 || !n_inliers || (n_last && (!m12 || !last_ml || (gates && !kls_last))) || (n_cur && (!ldisp_cur || !cur_ml || (gates && !kls_cur)))) {
-        set_error("olf_track_lines_assign: bad argument"); return OLF_ERR_INVALID;
-    }
-    for (int i1 = 0; i1 < n_last; ++i1)
-        if (m12[i1] >= n_cur) { set_error("olf_track_lines_assign: index out of range"); return OLF_ERR_INVALID; }
-    std::fill(cur_ml, cur_ml + n_cur, -1);
-    const double deltaWidth = (double)(maxX - minX) * pos_frac, deltaHeight = (double)(maxY - minY) * pos_frac;
-    int n = 0;
-    for (int i1 = 0; i1 < n_last; ++i1) {
-        if (skip_null && last_ml[i1] < 0) continue;
-        const int i2 = m12[i1];
-        if (i2 < 0) continue;
-        if (line_is_mono(ldisp_cur, i2)) continue;
-        if (gates) {
-            if (line_turned(kls_cur[i2].angle, kls_last[i1].angle, delta_angle)) { m12[i1] = -1; continue; }
-            const olf_keyline& l = kls_last[i1];
-            if (line_moved(kls_cur[i2], l.startPointX, l.startPointY, l.endPointX, l.endPointY, deltaWidth, deltaHeight)) { m12[i1] = -1; continue; }
-        }
-        cur_ml[i2] = last_ml[i1] < 0 ? -1 : last_ml[i1];
-        ++n;
-    }
-    *n_inliers = n;
-    return OLF_OK;
-}
-
-// The ratios at which predict_scale steps, found on predict_scale itself: thr[k - 1] = the smallest positive float whose level is >= k.  The level is a
-// non-decreasing function of the ratio wherever ceil(logf(ratio) / logSF) is (a property of the libm in use, checked around every threshold below), so
-// "the number of thresholds <= ratio" is the level.
-int olf_predict_scale_thresholds(const float* scale_factors, int n_levels, float* thr)
-{
-    if (!scale_factors || n_levels < 1 || n_levels > OLF_MAX_LEVELS || (n_levels > 1 && !thr)) { set_error("olf_predict_scale_thresholds: bad argument"); return OLF_ERR_INVALID; }
-    const float logSF = log_scale_factor(scale_factors, n_levels);
-    if (!(logSF > 0.f)) { set_error("olf_predict_scale_thresholds: the scale factor must exceed 1"); return OLF_ERR_INVALID; }
-    auto level = [&](uint32_t bits) { float r; std::memcpy(&r, &bits, 4); return predict_scale(r, 1.0f, logSF, n_levels); };      // (r / 1.0f == r)
-    constexpr uint32_t kMinPos = 0x00000001u, kMaxFinite = 0x7f7fffffu, kNear = 4096;
-    for (int k = 1; k < n_levels; ++k) {
-        uint32_t lo = kMinPos, hi = kMaxFinite;          // positive floats order as their bit patterns do
-        if (level(lo) >= k || level(hi) < k) { set_error("olf_predict_scale_thresholds: level " + std::to_string(k) + " has no threshold"); return OLF_ERR_INVALID; }
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (level(mid) >= k) hi = mid; else lo = mid;
-        }
-        const int below = level(lo), above = level(hi);
-        for (uint32_t d = 1; d < kNear; ++d) {
-            const bool okLo = lo - kMinPos < d || level(lo - d) == below, okHi = kMaxFinite - hi < d || level(hi + d) == above;
-            if (!okLo || !okHi) { set_error("olf_predict_scale_thresholds: the level is not monotone around the threshold of level " + std::to_string(k)); return OLF_ERR_INVALID; }
-        }
-        std::memcpy(&thr[k - 1], &hi, 4);
-    }
-    return OLF_OK;
-}
 
 int olf_search_by_projection_kf(olf_ctx* c, const olf_frame_view* cur, const olf_frame_view* kf, const uint8_t* already_found, float th,
                                 int orb_dist, int check_orientation, int32_t* matches, int32_t* nmatches)
 {
-    if (!c || bad_view(cur, true) || bad_view(kf, false) || !matches || !nmatches || !cur->scale_factors || !cur->mp_valid ||
-        (kf->n && (!kf->mp_valid || !kf->mp_bad || !kf->mp_world || !kf->mp_desc || !kf->mp_maxd || !kf->mp_mind))) {
+    if (!c || bad_view(cur, true) || bad_view(kf, false) || !matches || !nmatches || !cur->scale_factors || !cur->mp_valid || bad_kf_points(kf)) {
         set_error("olf_search_by_projection_kf: bad argument"); return OLF_ERR_INVALID;
     }
     if (bad_levels(cur)) { set_error("olf_search_by_projection_kf: n_levels / scale_factors missing"); return OLF_ERR_INVALID; }
@@ -598,7 +515,7 @@ int olf_search_by_projection_kf(olf_ctx* c, const olf_frame_view* cur, const olf
         q.add(i, kf->mp_desc + 32 * (size_t)i);
     }
     OLF_TRY(q.run(c, cur->desc, cur->n));
-    std::vector<int> rotHist[HISTO_LENGTH];
+    RotHist hist;
     int n = 0;
     for (size_t k = 0; k < q.owner.size(); ++k) {
         const int i = q.owner[k];
@@ -613,17 +530,10 @@ int olf_search_by_projection_kf(olf_ctx* c, const olf_frame_view* cur, const olf
             cur->mp_valid[bestIdx2] = 1;
             matches[bestIdx2] = i;
             n++;
-            if (check_orientation) rotHist[rot_bin(kf->keys[i].angle, cur->keys[bestIdx2].angle)].push_back(bestIdx2);
+            if (check_orientation) hist.add(kf->keys[i].angle, cur->keys[bestIdx2].angle, bestIdx2);
         }
     }
-    if (check_orientation) {
-        int ind1, ind2, ind3;
-        three_maxima(rotHist, ind1, ind2, ind3);
-        for (int b = 0; b < HISTO_LENGTH; b++) {
-            if (b == ind1 || b == ind2 || b == ind3) continue;
-            for (int j : rotHist[b]) { cur->mp_valid[j] = 0; matches[j] = -1; n--; }
-        }
-    }
+    hist.reject(check_orientation, [&](int j) { cur->mp_valid[j] = 0; matches[j] = -1; n--; });
     *nmatches = n;
     return OLF_OK;
 }
@@ -638,22 +548,11 @@ int olf_search_by_bow_kf(olf_ctx* c, const olf_frame_view* kf1, const olf_frame_
     for (int i = 0; i < kf1->n; ++i) matches12[i] = -1;
     *nmatches = 0;
     Batch q;
-    bool oob = false;
-    for_common_nodes(*kf1, *kf2, [&](int a, int b) {
-        for (int p = kf1->fv_offsets[a]; p < kf1->fv_offsets[a + 1]; ++p) {
-            const int idx1 = kf1->fv_features[p];
-            if (idx1 < 0 || idx1 >= kf1->n) { oob = true; continue; }
-            if (!kf1->mp_valid[idx1]) continue;
-            if (kf1->mp_bad[idx1]) continue;
-            q.cand.insert(q.cand.end(), kf2->fv_features + kf2->fv_offsets[b], kf2->fv_features + kf2->fv_offsets[b + 1]);
-            q.add(idx1, kf1->desc + 32 * (size_t)idx1);
-        }
-    });
-    for (int idx2 : q.cand) if (idx2 < 0 || idx2 >= kf2->n) oob = true;
-    if (oob) { set_error("olf_search_by_bow_kf: feature index outside its key frame"); return OLF_ERR_INVALID; }
+    const bool inside1 = bow_queries(*kf1, *kf2, q, [&](int idx1) { return kf1->mp_valid[idx1] && !kf1->mp_bad[idx1]; });
+    if (!inside1 || !cand_inside(q, *kf2)) { set_error("olf_search_by_bow_kf: feature index outside its key frame"); return OLF_ERR_INVALID; }
     OLF_TRY(q.run(c, kf2->desc, kf2->n));
     std::vector<uint8_t> vbMatched2((size_t)std::max(kf2->n, 0), 0);
-    std::vector<int> rotHist[HISTO_LENGTH];
+    RotHist hist;
     int n = 0;
     for (size_t k = 0; k < q.owner.size(); ++k) {
         const int idx1 = q.owner[k];
@@ -670,19 +569,12 @@ int olf_search_by_bow_kf(olf_ctx* c, const olf_frame_view* kf1, const olf_frame_
             if (static_cast<float>(bestDist1) < nnratio * static_cast<float>(bestDist2)) {
                 matches12[idx1] = bestIdx2;
                 vbMatched2[bestIdx2] = 1;
-                if (check_orientation) rotHist[rot_bin(kf1->keys[idx1].angle, kf2->keys[bestIdx2].angle)].push_back(idx1);
+                if (check_orientation) hist.add(kf1->keys[idx1].angle, kf2->keys[bestIdx2].angle, idx1);
                 n++;
             }
         }
     }
-    if (check_orientation) {
-        int ind1, ind2, ind3;
-        three_maxima(rotHist, ind1, ind2, ind3);
-        for (int b = 0; b < HISTO_LENGTH; b++) {
-            if (b == ind1 || b == ind2 || b == ind3) continue;
-            for (int j : rotHist[b]) { matches12[j] = -1; n--; }
-        }
-    }
+    hist.reject(check_orientation, [&](int j) { matches12[j] = -1; n--; });
     *nmatches = n;
     return OLF_OK;
 }
@@ -701,23 +593,16 @@ int olf_search_for_triangulation(olf_ctx* c, const olf_frame_view* kf1, const ol
     if (Cw) std::memcpy(cw, Cw, sizeof(cw)); else camera_centre(kf1->Tcw, cw);
     tri_epipole(kf2->Tcw, cw, kf2->fx, kf2->fy, kf2->cx, kf2->cy, ex, ey);
     Batch q;
-    bool oob = false;
-    for_common_nodes(*kf1, *kf2, [&](int a, int b) {
-        for (int p = kf1->fv_offsets[a]; p < kf1->fv_offsets[a + 1]; ++p) {
-            const int idx1 = kf1->fv_features[p];
-            if (idx1 < 0 || idx1 >= kf1->n) { oob = true; continue; }
-            // If there is already a MapPoint skip
-            if (kf1->mp_valid[idx1]) continue;
-            const bool bStereo1 = kf1->uright[idx1] >= 0;
-            if (only_stereo) if (!bStereo1) continue;
-            q.cand.insert(q.cand.end(), kf2->fv_features + kf2->fv_offsets[b], kf2->fv_features + kf2->fv_offsets[b + 1]);
-            q.add(idx1, kf1->desc + 32 * (size_t)idx1);
-        }
+    const bool inside1 = bow_queries(*kf1, *kf2, q, [&](int idx1) {
+        // If there is already a MapPoint skip
+        if (kf1->mp_valid[idx1]) return false;
+        const bool bStereo1 = kf1->uright[idx1] >= 0;
+        if (only_stereo) if (!bStereo1) return false;
+        return true;
     });
-    for (int idx2 : q.cand) if (idx2 < 0 || idx2 >= kf2->n) oob = true;
-    if (oob) { set_error("olf_search_for_triangulation: feature index outside its key frame"); return OLF_ERR_INVALID; }
+    if (!inside1 || !cand_inside(q, *kf2)) { set_error("olf_search_for_triangulation: feature index outside its key frame"); return OLF_ERR_INVALID; }
     OLF_TRY(q.run(c, kf2->desc, kf2->n));
-    std::vector<int> rotHist[HISTO_LENGTH];
+    RotHist hist;
     int n = 0;
     for (size_t k = 0; k < q.owner.size(); ++k) {
         const int idx1 = q.owner[k];
@@ -744,89 +629,19 @@ int olf_search_for_triangulation(olf_ctx* c, const olf_frame_view* kf1, const ol
         if (bestIdx2 >= 0) {
             matches12[idx1] = bestIdx2;
             n++;
-            if (check_orientation) rotHist[rot_bin(kp1.angle, kf2->keys[bestIdx2].angle)].push_back(idx1);
+            if (check_orientation) hist.add(kp1.angle, kf2->keys[bestIdx2].angle, idx1);
         }
     }
-    if (check_orientation) {
-        int ind1, ind2, ind3;
-        three_maxima(rotHist, ind1, ind2, ind3);
-        for (int b = 0; b < HISTO_LENGTH; b++) {
-            if (b == ind1 || b == ind2 || b == ind3) continue;
-            for (int j : rotHist[b]) { matches12[j] = -1; n--; }
-        }
-    }
+    hist.reject(check_orientation, [&](int j) { matches12[j] = -1; n--; });
     *nmatches = n;
     return OLF_OK;
 }
-
-}  // extern "C"
-
-namespace {
-// per map point: gates, window, candidates.  Rcw9 / tcw3 / Ow3: camera pose; stereo_gate: the chi-square test of the plain Fuse.
-int fuse_core(olf_ctx* c, const char* who, const olf_frame_view* kf, const float* Rcw9, const float* tcw3, const float* Ow3, int n_mp,
-              const uint8_t* skip, const float* world, const float* normal, const float* maxd, const float* mind, const uint8_t* desc, float th,
-              bool stereo_gate, int none_dist, int32_t* best_idx, int32_t* best_dist, uint8_t* matched = nullptr, int32_t* kf_match = nullptr,
-              int32_t* nmatches = nullptr)
-{
-    // matched != nullptr: SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:292-405) -- key points that hold a match are
-    // skipped (:378), a point whose best distance is <= TH_LOW takes its key point at once (:397-401), so later points see it taken
-    if (bad_levels(kf)) { set_error(std::string(who) + ": n_levels / scale_factors missing"); return OLF_ERR_INVALID; }
-    const float logSF = log_scale_factor(*kf);
-    const Grid grid(*kf);
-    if (!grid.ok) return bad_grid();
-    Batch q;
-    struct Meta { float uvr[3]; int level; };
-    std::vector<Meta> meta;
-    int taken = 0;
-    const float cam[5] = {kf->fx, kf->fy, kf->cx, kf->cy, kf->mbf}, bounds[4] = {kf->minX, kf->maxX, kf->minY, kf->maxY};
-    for (int i = 0; i < n_mp; ++i) {
-        if (best_idx) { best_idx[i] = -1; best_dist[i] = none_dist; }
-        if (skip && skip[i]) continue;
-        // the gates on the point (fuse_point_gate, search_math.hpp)
-        Meta m;
-        float dist3D;
-        if (!fuse_point_gate(Rcw9, tcw3, Ow3, world + 3 * (size_t)i, normal + 3 * (size_t)i, maxd[i], mind[i], cam, bounds, m.uvr, dist3D)) continue;
-        m.level = predict_scale(maxd[i], dist3D, logSF, kf->n_levels);
-        const float radius = th * kf->scale_factors[m.level];
-        if (!grid.area(m.uvr[0], m.uvr[1], radius, -1, -1, q.cand)) continue;
-        q.add(i, desc + 32 * (size_t)i);
-        meta.push_back(m);
-    }
-    const int rc = q.run(c, kf->desc, kf->n);
-    if (rc != OLF_OK) return rc;
-    for (size_t k = 0; k < q.owner.size(); ++k) {
-        const Meta& m = meta[k];
-        int bestDist = none_dist, bestIdx = -1;
-        for (int p = q.offs[k]; p < q.offs[k + 1]; ++p) {
-            const int idx = q.cand[p];
-            if (matched && matched[idx]) continue;
-            const olf_keypoint& kp = kf->keys[idx];
-            const int kpLevel = kp.octave;
-            if (!fuse_level_ok(kpLevel, m.level)) continue;
-            if (stereo_gate) {
-                if (kpLevel < 0 || kpLevel >= kf->n_levels) { set_error(std::string(who) + ": octave outside mvScaleFactors"); return OLF_ERR_INVALID; }
-                if (!fuse_chi2_ok(m.uvr, kp.x, kp.y, kf->uright[idx], kf->scale_factors[kpLevel])) continue;
-            }
-            const int dist = q.dist[p];
-            if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
-        }
-        if (best_idx) { best_idx[q.owner[k]] = bestIdx; best_dist[q.owner[k]] = bestDist; }
-        if (matched && bestDist <= TH_LOW) { matched[bestIdx] = 1; kf_match[bestIdx] = q.owner[k]; ++taken; }
-    }
-    if (nmatches) *nmatches = taken;
-    return OLF_OK;
-}
-
-// (sim3_decompose: search_math.hpp)
-}  // namespace
-
-extern "C" {
 
 int olf_fuse_search(olf_ctx* c, const olf_frame_view* kf, int n_mp, const uint8_t* skip, const float* world, const float* normal,
                     const float* maxd, const float* mind, const uint8_t* desc, float th, const float* Ow, int32_t* best_idx, int32_t* best_dist)
 {
     if (!c || bad_view(kf, true) || n_mp < 0 || !best_idx || !best_dist || !kf->scale_factors || (kf->n && !kf->uright) ||
-        (n_mp && (!world || !normal || !maxd || !mind || !desc))) { set_error("olf_fuse_search: bad argument"); return OLF_ERR_INVALID; }
+        bad_points(n_mp, world, normal, maxd, mind, desc)) { set_error("olf_fuse_search: bad argument"); return OLF_ERR_INVALID; }
     float R[9], t[3], ow[3];
     for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) R[3 * r + k] = kf->Tcw[4 * r + k]; t[r] = kf->Tcw[4 * r + 3]; }
     if (Ow) std::memcpy(ow, Ow, sizeof(ow)); else camera_centre(kf->Tcw, ow);
@@ -838,7 +653,7 @@ int olf_fuse_search_sim3(olf_ctx* c, const olf_frame_view* kf, const float* Scw,
                          int32_t* best_dist)
 {
     if (!c || bad_view(kf, false) || !Scw || n_mp < 0 || !best_idx || !best_dist || !kf->scale_factors ||
-        (n_mp && (!world || !normal || !maxd || !mind || !desc))) { set_error("olf_fuse_search_sim3: bad argument"); return OLF_ERR_INVALID; }
+        bad_points(n_mp, world, normal, maxd, mind, desc)) { set_error("olf_fuse_search_sim3: bad argument"); return OLF_ERR_INVALID; }
     float R[9], t[3], ow[3];
     sim3_decompose(Scw, R, t, ow);
     return fuse_core(c, "olf_fuse_search_sim3", kf, R, t, ow, n_mp, skip, world, normal, maxd, mind, desc, th, false, 2147483647, best_idx,
@@ -850,7 +665,7 @@ int olf_search_by_projection_sim3(olf_ctx* c, const olf_frame_view* kf, const fl
                                   int32_t* matches, int32_t* nmatches)
 {
     if (!c || bad_view(kf, false) || !Scw || n_mp < 0 || !matched || !matches || !nmatches || !kf->scale_factors ||
-        (n_mp && (!world || !normal || !maxd || !mind || !desc))) { set_error("olf_search_by_projection_sim3: bad argument"); return OLF_ERR_INVALID; }
+        bad_points(n_mp, world, normal, maxd, mind, desc)) { set_error("olf_search_by_projection_sim3: bad argument"); return OLF_ERR_INVALID; }
     float R[9], t[3], ow[3];
     sim3_decompose(Scw, R, t, ow);
     for (int i = 0; i < kf->n; ++i) matches[i] = -1;
@@ -861,11 +676,8 @@ int olf_search_by_projection_sim3(olf_ctx* c, const olf_frame_view* kf, const fl
 int olf_search_by_sim3(olf_ctx* c, const olf_frame_view* kf1, const olf_frame_view* kf2, int32_t* matches12, float s12, const float* R12,
                        const float* t12, float th, int32_t* vn_match1, int32_t* vn_match2, int32_t* nfound)
 {
-    auto incomplete = [](const olf_frame_view* k) {
-        return k->n && (!k->mp_valid || !k->mp_bad || !k->mp_world || !k->mp_desc || !k->mp_maxd || !k->mp_mind);
-    };
     if (!c || bad_view(kf1, true) || bad_view(kf2, true) || !matches12 || !R12 || !t12 || !vn_match1 || !vn_match2 || !nfound ||
-        !kf1->scale_factors || !kf2->scale_factors || incomplete(kf1) || incomplete(kf2)) {
+        !kf1->scale_factors || !kf2->scale_factors || bad_kf_points(kf1) || bad_kf_points(kf2)) {
         set_error("olf_search_by_sim3: bad argument"); return OLF_ERR_INVALID;
     }
     if (bad_levels(kf1) || bad_levels(kf2)) { set_error("olf_search_by_sim3: n_levels / scale_factors missing"); return OLF_ERR_INVALID; }
@@ -927,31 +739,6 @@ int olf_search_by_sim3(olf_ctx* c, const olf_frame_view* kf1, const olf_frame_vi
         if (idx2 >= 0 && vn_match2[idx2] == i1) { matches12[i1] = idx2; found++; }
     }
     *nfound = found;
-    return OLF_OK;
-}
-
-// getLineCoords (src/gridStructure.cpp:33-41): the cells visited by the reference's double-precision Bresenham walk (src/LineIterator.cpp:34-77),
-// host arithmetic -- the same walk csrc/linematch.hip makes on the device for the stereo line matcher.  xy: (x, y) pairs; *n receives the
-// number of cells (which may exceed cap; only cap pairs are written).
-int olf_line_coords(double x1, double y1, double x2, double y2, int32_t* xy, int cap, int32_t* n)
-{
-    if (!xy || !n || cap < 0) { set_error("olf_line_coords: bad argument"); return OLF_ERR_INVALID; }
-    const bool steep = std::fabs(y2 - y1) > std::fabs(x2 - x1);
-    if (steep) { std::swap(x1, y1); std::swap(x2, y2); }
-    if (x1 > x2) { std::swap(x1, x2); std::swap(y1, y2); }
-    const double dx = x2 - x1, dy = std::fabs(y2 - y1);
-    double error = dx / 2.0;
-    const int ystep = (y1 < y2) ? 1 : -1;
-    int y = (int)y1, count = 0;
-    const int maxX = (int)x2;
-    for (int x = (int)x1; x <= maxX; ++x) {
-        if (count < cap) { xy[2 * count] = steep ? y : x; xy[2 * count + 1] = steep ? x : y; }
-        ++count;
-        error -= dy;
-        if (error < 0) { y += ystep; error += dx; }
-        if (x == 2147483647) break;
-    }
-    *n = count;
     return OLF_OK;
 }
 

@@ -6,10 +6,9 @@ ten predecessors are its best covisibles; a query is a key frame's vector with h
 python tools/kfdb_latency.py [--kfs 500,4000] [--queries 1,8,64]
 olf_kfdb_tables_dev: HIP events, warmed up, median of five windows of ten calls.  olf_kfdb_detect and the host walk return to the host, so they are timed by
 the host clock over the same windows (detect ends in a synchronise).  The candidate lists of the two are compared."""
-import argparse, ctypes as C, os, subprocess, sys, tempfile, time
+import argparse, ctypes as C, os, subprocess, tempfile, time
 import numpy as np
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
-sys.path.insert(0, ROOT)
+from latency_common import ROOT, side_stream, windows
 import torch
 from orb_line_slam_amd import _lib
 from orb_line_slam_amd._lib import BowCsrC, KfdbTablesC, KFDB_RELOC, KFDB_RELOC_LINE, check, lib
@@ -36,8 +35,7 @@ HW.hw_reloc.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C
 HW.hw_reloc_line.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
 
 ctx = _lib.Context(_lib.default_params(), 640, 480, 1)
-torch.cuda.set_stream(torch.cuda.Stream())          # (the default stream's handle, 0, would send every *_dev call to the context's own stream)
-stream = torch.cuda.current_stream().cuda_stream
+stream = side_stream()
 rng = np.random.default_rng(99)
 
 
@@ -49,27 +47,6 @@ def vector(n_ids, n, base=None):
     ids = np.unique(ids).astype(np.int32)
     w = rng.random(len(ids)) + 0.05
     return ids, w / w.sum()
-
-
-def windows(fn, events):
-    fn(); fn(); torch.cuda.synchronize()
-    ms = []
-    for _ in range(5):
-        if events:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(10):
-                fn()
-            b.record(); torch.cuda.synchronize()
-            ms.append(a.elapsed_time(b) / 10)
-        else:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(10):
-                fn()
-            torch.cuda.synchronize()
-            ms.append(1e2 * (time.perf_counter() - t0))
-    return sorted(ms)[2], min(ms), max(ms)
 
 
 rows = []

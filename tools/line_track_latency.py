@@ -5,42 +5,22 @@ lines (both end points unprojected with their disparities, identity poses); fram
 frames hold nothing on entry; predicted pose: a 0.02 m translation; nnr = Config::minRatio12L():
     python tools/line_track_latency.py [--config C3] [--pairs 3072]
 Device entries: HIP events, warmed up, median of five windows of ten calls.  Host loop: host clock, ending in a synchronise."""
-import argparse, ctypes as C, os, sys, time
+import ctypes as C, time
 import numpy as np
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
-sys.path.insert(0, ROOT)
+from latency_common import BenchBatch, parser, up, zeros as z
 import torch
-from orb_line_slam_amd import _lib, matcher, synth
-from orb_line_slam_amd._lib import KEYLINE_DTYPE, check, lib
-import bench
+from orb_line_slam_amd import _lib, matcher
+from orb_line_slam_amd._lib import KEYLINE_DTYPE
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--config", default="C3")
-ap.add_argument("--pairs", type=int, default=0)
-ap.add_argument("--distinct", type=int, default=512)
+ap = parser()
 ap.add_argument("--host-frames", type=int, default=0, help="frames the host loop covers (0: all)")
 args = ap.parse_args()
-cfg = bench.CONFIGS[args.config]
-W, H, B = cfg["w"], cfg["h"], args.pairs or cfg["pairs"]
-params = _lib.default_params()
-params.orb.nfeatures, params.line.lsd_nfeatures = cfg["nf"], cfg["nl"]
-params.stereo.fx, params.stereo.bf = cfg["fx"], cfg["bf"]
+batch = BenchBatch(args)
+ctx, L, W, H, B, cap, params = batch.ctx, batch.L, batch.W, batch.H, batch.B, batch.ctx.line_capacity, batch.params
 nnr = float(params.stereo.min_ratio_12_l)
-ctx = _lib.Context(params, W, H, 2 * B)
-torch.cuda.set_stream(torch.cuda.Stream())          # (the default stream's handle, 0, would send every *_dev call to the context's own stream)
-cap, L, s = ctx.line_capacity, lib(), torch.cuda.current_stream().cuda_stream
-nd = min(args.distinct, B)
-host = synth.stereo_batch(7000, nd, W, H)
-order = np.random.default_rng(1234).permutation(np.arange(B) % nd)          # the bench's shuffled batch
-imgs = torch.from_numpy(host[np.stack([2 * order, 2 * order + 1], 1).reshape(-1)].copy()).cuda()
-z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda")
-kls, ldesc, lcounts = z((2 * B, cap, 68), torch.uint8), z((2 * B, cap, 32), torch.uint8), z((2 * B,), torch.int32)
-lm12, ldisp, lle = z((B, cap), torch.int32), z((B, cap, 2), torch.float32), z((B, cap, 3), torch.float64)
-check(L.olf_line_extract_dev(ctx.handle, imgs.data_ptr(), 2 * B, kls.data_ptr(), ldesc.data_ptr(), lcounts.data_ptr(), s), "olf_line_extract_dev")
-check(L.olf_stereo_lines_dev(ctx.handle, B, kls.data_ptr(), ldesc.data_ptr(), lcounts.data_ptr(), lm12.data_ptr(), ldisp.data_ptr(), lle.data_ptr(), s), "olf_stereo_lines_dev")
-fx, cx, cy, mbf = float(cfg["fx"]), W / 2.0, H / 2.0, float(cfg["bf"])
-cam, bounds = (fx, fx, cx, cy, mbf), (0.0, float(W), 0.0, float(H))
-Tcw = torch.eye(4, dtype=torch.float32, device="cuda").repeat(B, 1, 1).contiguous()
+kls, ldesc, lcounts, ldisp = batch.kls, batch.ldesc, batch.lcounts, batch.ldisp
+(fx, _, cx, cy, mbf), cam, bounds = batch.cam, batch.cam, batch.bounds
+Tcw = batch.eye          # (this tool reads the identity poses nowhere else: the predicted poses are written into them)
 Tcw[:, 0, 3] = 0.02
 
 # the map: line f * cap + i is the stereo line i of frame f -- GetWorldPos() from the end points and their disparities, the line's own descriptor
@@ -59,7 +39,6 @@ own = [f * cap + np.flatnonzero(stereo[f]) for f in range(B)]
 lists = [np.concatenate([own[f] for f in (j - 1, j, j + 1) if 0 <= f < B]).astype(np.int32) for j in range(B)]
 l_offs = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int32)
 ne = int(l_offs[-1])
-up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
 lm = matcher.LocalLineMapDev(up(m_world), up(m_desc), up(m_obs), up(m_bad), up(l_offs), up(np.concatenate(lists)), n_ml=B * cap)
 out = (z((ne,), torch.uint8), z((ne, 4), torch.float32), z((ne,), torch.int32), z((B, cap), torch.int32), z((B,), torch.int32))
 search = lambda: matcher.search_local_lines_batch(B, kls, ldesc, lcounts, ldisp, Tcw, lm, cam, bounds, nnr, out=out, context=ctx)
@@ -68,27 +47,11 @@ frustum = lambda: matcher.is_in_frustum_l_batch(B, Tcw, lm, cam, bounds, out=fr_
 last_ml = up(np.where(stereo, np.arange(B * cap).reshape(B, cap), -1).astype(np.int32)[:B - 1])
 tr_out = (z((B - 1, cap), torch.int32), z((B - 1, cap), torch.int32), z((B - 1,), torch.int32))
 track = lambda: matcher.track_lines_batch(B, kls, ldesc, lcounts, ldisp, last_ml, bounds, nnr, best_lr=bool(params.stereo.best_lr_matches), out=tr_out, context=ctx)
-
-
-def timed(tag, fn):
-    fn(); fn(); torch.cuda.synchronize()
-    ms = []
-    for _ in range(5):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(10):
-            fn()
-        b.record(); torch.cuda.synchronize()
-        ms.append(a.elapsed_time(b) / 10)
-    ctx.synchronize()
-    print("%-58s %8.3f ms per call (%d frames; median of 5 windows of 10, HIP events; min %.3f max %.3f)" % (tag, sorted(ms)[2], B, min(ms), max(ms)), flush=True)
-    return sorted(ms)[2]
-
-
+frames_note = "%d frames; " % B
 print(f"{args.config} {W}x{H}, {B} stereo pairs, line capacity {cap}, nnr {nnr}; map {B * cap} slots, {ne} list entries ({ne / B:.0f} per frame)", flush=True)
-t_fr = timed("olf_is_in_frustum_l_batch_dev (the frustum pass alone)", frustum)
-t_batch = timed("olf_search_local_lines_batch_dev", search)
-t_track = timed("olf_track_lines_batch_dev (%d pairs)" % (B - 1), track)
+t_fr = batch.timed("olf_is_in_frustum_l_batch_dev (the frustum pass alone)", frustum, note=frames_note)
+t_batch = batch.timed("olf_search_local_lines_batch_dev", search, note=frames_note)
+t_track = batch.timed("olf_track_lines_batch_dev (%d pairs)" % (B - 1), track, note=frames_note)
 torch.cuda.synchronize()
 v_dev, p_dev, m_dev, f_dev, n_dev = (x.cpu().numpy() for x in out)
 print("  lines per frame: mean %.0f; in view: %.1f %% of the entries; n_inliers_ls per frame: mean %.1f, min %d, max %d; f2f n_inliers_ls: mean %.1f" %

@@ -4,57 +4,31 @@ bench's synthetic batch.  The map is made of the batch's own stereo points (olf_
 frames j - 1, j and j + 1, in that order; the frames hold nothing on entry; predicted pose: a 0.02 m translation; th = 1, nnratio = 0.8:
     python tools/local_map_latency.py [--config C3] [--pairs 3072]
 Device entry: HIP events, warmed up, median of five windows of ten calls.  Host loop: host clock, ending in a synchronise."""
-import argparse, ctypes as C, os, sys, time
+import time
 import numpy as np
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
-sys.path.insert(0, ROOT)
+from latency_common import BenchBatch, host_view, parser, up, zeros as z
 import torch
 import orb_line_slam_amd as ola
-from orb_line_slam_amd import _lib, matcher, synth
-from orb_line_slam_amd._lib import KEYPOINT_DTYPE, check, lib
-import bench
+from orb_line_slam_amd import _lib, matcher
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--config", default="C3")
-ap.add_argument("--pairs", type=int, default=0)
-ap.add_argument("--distinct", type=int, default=512)
+ap = parser()
 ap.add_argument("--host-frames", type=int, default=0, help="frames the host loop covers (0: all)")
 ap.add_argument("--th", type=float, default=1.0)
 ap.add_argument("--nnratio", type=float, default=0.8)
 args = ap.parse_args()
-cfg = bench.CONFIGS[args.config]
-W, H, B = cfg["w"], cfg["h"], args.pairs or cfg["pairs"]
-params = _lib.default_params()
-params.orb.nfeatures, params.line.lsd_nfeatures = cfg["nf"], cfg["nl"]
-params.stereo.fx, params.stereo.bf = cfg["fx"], cfg["bf"]
-ctx = _lib.Context(params, W, H, 2 * B)
-torch.cuda.set_stream(torch.cuda.Stream())          # (the default stream's handle, 0, would send every *_dev call to the context's own stream)
-cap, L, s = ctx.orb_capacity, lib(), torch.cuda.current_stream().cuda_stream
-nd = min(args.distinct, B)
-host = synth.stereo_batch(7000, nd, W, H)
-order = np.random.default_rng(1234).permutation(np.arange(B) % nd)          # the bench's shuffled batch
-imgs = torch.from_numpy(host[np.stack([2 * order, 2 * order + 1], 1).reshape(-1)].copy()).cuda()
-z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda")
-kps, desc, counts = z((2 * B, cap, 28), torch.uint8), z((2 * B, cap, 32), torch.uint8), z((2 * B,), torch.int32)
-ur, dp = z((B, cap), torch.float32), z((B, cap), torch.float32)
-check(L.olf_orb_extract_dev(ctx.handle, imgs.data_ptr(), 2 * B, kps.data_ptr(), desc.data_ptr(), counts.data_ptr(), s), "olf_orb_extract_dev")
-check(L.olf_stereo_points_dev(ctx.handle, B, kps.data_ptr(), desc.data_ptr(), counts.data_ptr(), ur.data_ptr(), dp.data_ptr(), s), "olf_stereo_points_dev")
-fx, cx, cy, mbf = float(cfg["fx"]), W / 2.0, H / 2.0, float(cfg["bf"])
-cam, bounds = (fx, fx, cx, cy, mbf), (0.0, float(W), 0.0, float(H))
-eye = torch.eye(4, dtype=torch.float32, device="cuda").repeat(B, 1, 1).contiguous()
-Tcw = eye.clone()
+batch = BenchBatch(args)
+ctx, L, W, H, B, cap = batch.ctx, batch.L, batch.W, batch.H, batch.B, batch.cap
+kps, desc, counts, ur = batch.kps, batch.desc, batch.counts, batch.ur
+cam, bounds = batch.cam, batch.bounds
+Tcw = batch.eye.clone()
 Tcw[:, 0, 3] = 0.02
-world = matcher.unproject_stereo(B, kps, counts, dp, (fx, fx, cx, cy), eye, context=ctx)
-offs, idx = z((B, _lib.GRID_CELLS + 1), torch.int32), z((B, cap), torch.int32)
-check(L.olf_frame_grid_dev(ctx.handle, B, 2, kps.data_ptr(), counts.data_ptr(), *bounds, offs.data_ptr(), idx.data_ptr(), s), "olf_frame_grid_dev")
-sf = np.zeros(ctx.nlevels, np.float32)
-L.olf_orb_scale_tables(ctx.handle, sf.ctypes.data_as(C.c_void_p), None, None, None, None)
+world, offs, idx = batch.world, batch.offs, batch.idx
+batch.grid()
+sf = batch.sf
 
 # the map: point f * cap + i is the stereo point of feature i of frame f, as the frame that made it would describe it (MapPoint::UpdateNormalAndDepth)
 torch.cuda.synchronize()
-cnt = counts.cpu().numpy()[0::2]
-hk = kps.cpu().numpy().reshape(2 * B, cap * 28).view(KEYPOINT_DTYPE)[0::2]
-hd, hu, hw, hz = desc.cpu().numpy()[0::2], ur.cpu().numpy(), world.cpu().numpy().reshape(B * cap, 3), dp.cpu().numpy()
+cnt, hk, hd, hu, hw, hz = batch.cnt, batch.hk, batch.hd, batch.hu, batch.hw.reshape(B * cap, 3), batch.dp.cpu().numpy()
 dist = np.linalg.norm(hw.astype(np.float64), axis=1)
 m_world = hw
 m_normal = (hw / np.maximum(dist, 1e-9)[:, None]).astype(np.float32)
@@ -65,33 +39,16 @@ m_obs, m_bad = np.ones(B * cap, np.uint8), np.zeros(B * cap, np.uint8)
 own = [f * cap + np.flatnonzero(hz[f, :cnt[f]] > 0) for f in range(B)]
 lists = [np.concatenate([own[f] for f in (j - 1, j, j + 1) if 0 <= f < B]).astype(np.int32) for j in range(B)]
 l_offs = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int32)
-up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
 lm = matcher.LocalMapDev(up(m_world), up(m_normal), up(m_maxd), up(m_mind), up(m_desc), up(m_obs), up(m_bad), up(l_offs), up(np.concatenate(lists)), n_mp=B * cap)
 out = (z((B, cap), torch.int32), z((B,), torch.int32))
 search = lambda: matcher.search_local_map_batch(B, kps, desc, counts, ur, offs, idx, Tcw, lm, cam, bounds, th=args.th, nnratio=args.nnratio, out=out, context=ctx)
 fr_out = (z((int(l_offs[-1]),), torch.uint8), z((int(l_offs[-1]),), torch.int32), z((int(l_offs[-1]),), torch.float32), z((int(l_offs[-1]), 3), torch.float32))
 frustum = lambda: matcher.is_in_frustum_batch(B, Tcw, lm, cam, bounds, 0.5, out=fr_out, context=ctx)
-
-
-def timed(tag, fn):
-    fn(); fn(); torch.cuda.synchronize()
-    ms = []
-    for _ in range(5):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(10):
-            fn()
-        b.record(); torch.cuda.synchronize()
-        ms.append(a.elapsed_time(b) / 10)
-    ctx.synchronize()
-    print("%-58s %8.3f ms per call (%d frames; median of 5 windows of 10, HIP events; min %.3f max %.3f)" % (tag, sorted(ms)[2], B, min(ms), max(ms)), flush=True)
-    return sorted(ms)[2]
-
-
+frames_note = "%d frames; " % B
 print(f"{args.config} {W}x{H}, {B} stereo pairs, capacity {cap}, th {args.th}, nnratio {args.nnratio}; map {B * cap} slots, {int(l_offs[-1])} list entries "
       f"({l_offs[-1] / B:.0f} per frame)", flush=True)
-t_fr = timed("olf_is_in_frustum_batch_dev (the frustum pass alone)", frustum)
-t_batch = timed("olf_search_local_map_batch_dev", search)
+t_fr = batch.timed("olf_is_in_frustum_batch_dev (the frustum pass alone)", frustum, note=frames_note)
+t_batch = batch.timed("olf_search_local_map_batch_dev", search, note=frames_note)
 torch.cuda.synchronize()
 n_dev, m_dev = out[1].cpu().numpy(), out[0].cpu().numpy()
 print("  key points per frame: mean %.0f; matches per frame: mean %.1f, min %d, max %d; in view: %.1f %% of the entries" %
@@ -100,18 +57,12 @@ print("  key points per frame: mean %.0f; matches per frame: mean %.1f, min %d, 
 # the host entries, two calls per frame, on the downloaded arrays (each frame's local map gathered beforehand)
 hT = Tcw.cpu().numpy()
 nh = min(args.host_frames or B, B)
-views, pyviews, keep, maps = [], [], [], []
+views, held, maps = [], [], []
 for j in range(nh):
     n = int(cnt[j])
-    v = ola.FrameView.__new__(ola.FrameView)             # (no Python grid: the host entry builds its own)
-    v.mvKeysUn, v.mDescriptors, v.mvuRight, v.N, v.mvScaleFactors = hk[j, :n], hd[j, :n], hu[j, :n], n, sf
-    v.fx = v.fy = fx; v.cx, v.cy, v.mbf = cx, cy, mbf
-    v.mnMinX, v.mnMaxX, v.mnMinY, v.mnMaxY = bounds
-    v.mTcw, v.mFeatVec = hT[j], {}
-    v.mp_valid, v.mp_obs, v.mp_bad, v.mvbOutlier = np.zeros(n, bool), np.zeros(n, bool), np.zeros(n, bool), np.zeros(n, bool)
-    v.mp_world, v.mp_desc = np.zeros((n, 3), np.float32), hd[j, :n]
-    pyviews.append(v)
-    views.append(matcher._view_c(v, keep))
+    held.append((np.zeros(n, bool), np.zeros(n, bool)))      # mp_valid, mp_obs: the search marks the features it fills
+    views.append(host_view(batch, j, mvuRight=hu[j, :n], mTcw=hT[j], mp_valid=held[j][0], mp_obs=held[j][1], mp_bad=np.zeros(n, bool), mvbOutlier=np.zeros(n, bool),
+                           mp_world=np.zeros((n, 3), np.float32), mp_desc=hd[j, :n]))
     li = lists[j]
     a = np.ascontiguousarray
     maps.append(dict(n=len(li), world=a(m_world[li]), normal=a(m_normal[li]), maxd=a(m_maxd[li]), mind=a(m_mind[li]), desc=a(m_desc[li]), obs=a(m_obs[li]),
@@ -131,7 +82,7 @@ def host_frame(j):
 
 
 host_frame(0)                                             # warm
-pyviews[0].mp_valid[:], pyviews[0].mp_obs[:] = False, False      # (the search marks the features it fills)
+held[0][0][:], held[0][1][:] = False, False
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 for j in range(nh):
