@@ -821,6 +821,47 @@ int olf_search_local_lines_batch_dev(olf_ctx* ctx, const olf_line_batch* in, int
 int olf_track_lines_batch_dev(olf_ctx* ctx, const olf_line_batch* in, int n_frames, const int32_t* d_last_ml, float nnr, int best_lr, int skip_null, int gates,
                               double delta_angle, double pos_frac, const int32_t* d_enable, int32_t* d_m12, int32_t* d_cur_ml, int32_t* d_ninliers, void* stream);
 
+/* ---- Tracking::UpdateLocalMap for a batch of frames on the device (csrc/localmap_batch.hip) -----------------------------------------------------------
+ * void Tracking::UpdateLocalMap() (src/Tracking.cc:2028-2205) = UpdateLocalKeyFrames (:2080-2205), then UpdateLocalPointsAndLines (:2039-2078), for n_frames
+ * frames against one snapshot of the map (olf_map_graph, orbline_types.h; device pointers here).  It produces what the two local searches start from:
+ * d_mp_offsets / d_mp_index are list_offsets / list_index of the olf_local_map of olf_search_local_map_batch_dev, d_ml_offsets / d_ml_index those of the
+ * olf_local_line_map of olf_search_local_lines_batch_dev, in the reference's order, element for element, under convention C.16: ascending
+ * key-frame index stands for the iteration order of std::map<KeyFrame*,int> (:2083) and std::set<KeyFrame*> (GetChilds, :2172).  So the reference key frame
+ * among equal vote counts is the lowest index, and the first list is in ascending index.
+ * Frame j is image j * img_stride of d_counts / d_lcounts (N and N_l; NULL: every frame holds olf_orb_capacity() / olf_line_capacity() features);
+ * d_frame_mp [n_frames][olf_orb_capacity()] and d_frame_ml [n_frames][olf_line_capacity()] (or NULL: the frames hold no lines) are mvpMapPoints /
+ * mvpMapLines as map indices with the meaning they have for olf_search_local_map_batch_dev: negative = none, or a temporal point -- such a feature neither
+ * votes nor is cleared.  A held point or line that is bad is cleared (:2097, :2114); lines do not vote (:2110).  d_frame_mp_out / d_frame_ml_out (NULL: not
+ * wanted; may be the inputs themselves): the rows with the bad ones cleared to -1, -1 from N on, everything else as it came.
+ * d_n_voted [n_frames]: the size of keyframeCounter, bad key frames included.  d_ref_kf [n_frames]: pKFmax, the first key frame in ascending index that is
+ * not bad and has the most votes among those, -1 when there is none.  A frame with d_n_voted[j] == 0 gets d_ref_kf[j] = -1 and three empty lists: the
+ * reference returns at :2120 and so keeps the previous frame's lists and reference key frame -- that chain across frames stays the caller's.  A frame whose
+ * voted key frames are all bad gets an empty key-frame list (hence empty point and line lists) and d_ref_kf = -1.
+ * d_kf_offsets [n_frames + 1] / d_kf_index [kf_capacity]: mvpLocalKeyFrames as a CSR; the extension loop (:2149-2198) visits the first list only (its end
+ * iterator is taken before the loop), stops once the list holds more than 80, reads the first 10 covisible key frames, the children in ascending index and
+ * the parent, which is not tested for isBad() and whose insertion ends the loop (:2194).  The three offset arrays are always complete, so a caller can size a
+ * retry; nothing is written at or past a capacity, and a total beyond one sets bit 8192 of the context's status word (olf_ctx_synchronize /
+ * olf_ctx_poll_status, as for olf_features_in_area_dev).
+ * Malformed indices are left out, never dereferenced: a point index outside the map (d_frame_mp, kf_mp_index) sets status bit 512, a line index outside
+ * the map bit 1024, a key-frame index outside [0, n_kf) (mp_obs_kf, kf_covis_index, kf_child_index, kf_parent other than -1) bit 4096.  Rows of a CSR are
+ * clamped to [0, offsets[n]].  That every row of kf_child_index ascends strictly is the caller's contract here (olf_update_local_map checks it).
+ * Errors: n_kf > OLF_LOCALMAP_MAX_KF (a frame's vote table lives in LDS): OLF_ERR_CAPACITY before anything is launched; a NULL required pointer or a negative
+ * size: OLF_ERR_INVALID.  n_frames == 0 writes nothing.  Does not synchronise; runs on `stream` and uses the batch scratch slot: 4 bytes per (frame, key
+ * frame) for the key-frame lists between its passes, and one bit per (frame, map point) and per (frame, map line) when the map holds more than 262144
+ * points and lines together (up to there a frame's two bitmaps live in LDS). */
+#define OLF_LOCALMAP_MAX_KF 8192
+int olf_update_local_map_batch_dev(olf_ctx* ctx, const olf_map_graph* g, int n_frames, int img_stride, const int32_t* d_counts, const int32_t* d_lcounts,
+                                   const int32_t* d_frame_mp, const int32_t* d_frame_ml, int32_t* d_frame_mp_out, int32_t* d_frame_ml_out, int32_t* d_ref_kf,
+                                   int32_t* d_n_voted, int32_t* d_kf_offsets, int32_t* d_kf_index, int kf_capacity, int32_t* d_mp_offsets, int32_t* d_mp_index,
+                                   int mp_capacity, int32_t* d_ml_offsets, int32_t* d_ml_index, int ml_capacity, void* stream);
+/* host buffers, the graph's arrays included: checks the graph (offsets non-decreasing from 0; a row of kf_child_index that is not strictly ascending:
+ * OLF_ERR_INVALID), uploads, runs the same kernels on the context's stream, downloads.  OLF_ERR_CAPACITY when a capacity is too small: the three offset
+ * arrays are complete then and each index array holds its first `capacity` entries; the same code, with the message of the bit, for a malformed index. */
+int olf_update_local_map(olf_ctx* ctx, const olf_map_graph* g, int n_frames, int img_stride, const int32_t* counts, const int32_t* lcounts,
+                         const int32_t* frame_mp, const int32_t* frame_ml, int32_t* frame_mp_out, int32_t* frame_ml_out, int32_t* ref_kf, int32_t* n_voted,
+                         int32_t* kf_offsets, int32_t* kf_index, int kf_capacity, int32_t* mp_offsets, int32_t* mp_index, int mp_capacity, int32_t* ml_offsets,
+                         int32_t* ml_index, int ml_capacity);
+
 /* measurement: rate of a plain 16-byte-per-thread device copy kernel over `bytes` (read + written bytes per second): the practical HBM
  * ceiling bench.py reports next to the specification's 8 TB/s */
 int olf_debug_copy_bandwidth(olf_ctx* ctx, size_t bytes, int reps, double* gbytes_per_s);

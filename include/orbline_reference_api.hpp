@@ -11,6 +11,7 @@
 //   StereoFrameFeatures(frame, imLeft, imRight)  = the feature part of Frame::Frame  src/Frame.cc:164-171,199-207
 //   FrameGrid(frame)                             = AssignFeaturesToGrid()            src/Frame.cc:215            (:334-349)
 //   KeyFrameDatabaseOf<KeyFrame, Frame>          = KeyFrameDatabase                  include/KeyFrameDatabase.h:60-98 (add, erase, clear, the four Detect members)
+//   MapGraphOf<KeyFrame, MapPoint, MapLine>, UpdateLocalMap(...)  = Tracking::UpdateLocalMap   src/Tracking.cc:2028-2205
 //   and every other ORBmatcher call of the reference: SearchByProjection(cur, pKF, sFound, th, ORBdist) Tracking.cc:2322,2336;
 //   SearchForTriangulation LocalMapping.cc:268; Fuse(pKF, vpMapPoints[, th]) LocalMapping.cc:489,514; SearchByBoW(pKF1, pKF2, vpMatches12)
 //   LoopClosing.cc:271; SearchBySim3 LoopClosing.cc:329; SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) LoopClosing.cc:381;
@@ -25,6 +26,7 @@
 // Contexts: the matcher functions run on a small per-thread context (olf_detail::thread_ctx()) -- ORBmatcher objects are stack locals used
 // from the Tracking, LocalMapping and LoopClosing threads concurrently (SURVEY 8(b) "Threading"), and a context serves one thread.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <list>
 #include <map>
@@ -790,5 +792,137 @@ private:
     std::vector<KeyFrameT*> kf_of_;
     std::mutex mMutex;
 };
+
+// ---- Tracking::UpdateLocalMap (src/Tracking.cc:2028-2205) over the reference's own types -------------------------------------------------------------------
+// MapGraphOf<KeyFrame, MapPoint, MapLine> is one snapshot of the map as olf_update_local_map* reads it (olf_map_graph, orbline_types.h), filled through the
+// accessors Tracking itself uses: MapPoint::GetObservations / isBad, KeyFrame::GetMapPointMatches / GetMapLineMatches / GetVectorCovisibleKeyFrames /
+// GetChilds / GetParent / isBad, MapLine::isBad.  Key frames are numbered in the order given -- convention C.16: hand them over in the order that is
+// to stand for the address order of std::map<KeyFrame*,int> and std::set<KeyFrame*> (the order of creation, mnId, is the natural one); children are sorted by
+// that number.  Map points and lines are numbered by their first appearance in the key frames' slots (key-frame order, slot order).  A key frame outside the
+// snapshot (an observation, a neighbour, a child, the parent) is left out; a point or line of a frame that no key frame of the snapshot holds is a temporal
+// one to the call (-1).  The object owns the arrays; graph() points into them, host pointers for olf_update_local_map.
+template <class KeyFrameT, class MapPointT, class MapLineT>
+class MapGraphOf {
+public:
+    explicit MapGraphOf(const std::vector<KeyFrameT*>& kfs) : kfs_(kfs)
+    {
+        const int n = (int)kfs.size();
+        for (int k = 0; k < n; ++k) kf_index_[kfs[k]] = k;
+        kf_mp_off_.assign(1, 0); kf_ml_off_.assign(1, 0); covis_off_.assign(1, 0); child_off_.assign(1, 0);
+        for (int k = 0; k < n; ++k) {
+            KeyFrameT* pKF = kfs[k];
+            kf_bad_.push_back(pKF->isBad() ? 1 : 0);
+            const std::vector<MapPointT*> vpMPs = pKF->GetMapPointMatches();
+            for (size_t i = 0; i < vpMPs.size(); ++i) kf_mp_.push_back(vpMPs[i] ? number(mp_index_, mps_, vpMPs[i]) : -1);
+            kf_mp_off_.push_back((int32_t)kf_mp_.size());
+            const std::vector<MapLineT*> vpMLs = pKF->GetMapLineMatches();
+            for (size_t i = 0; i < vpMLs.size(); ++i) kf_ml_.push_back(vpMLs[i] ? number(ml_index_, mls_, vpMLs[i]) : -1);
+            kf_ml_off_.push_back((int32_t)kf_ml_.size());
+            const std::vector<KeyFrameT*> vNeighs = pKF->GetVectorCovisibleKeyFrames();
+            for (size_t i = 0; i < vNeighs.size(); ++i) { const int c = index_of(vNeighs[i]); if (c >= 0) covis_.push_back(c); }
+            covis_off_.push_back((int32_t)covis_.size());
+            const std::set<KeyFrameT*> spChilds = pKF->GetChilds();
+            std::vector<int32_t> ch;
+            for (typename std::set<KeyFrameT*>::const_iterator it = spChilds.begin(); it != spChilds.end(); ++it) { const int c = index_of(*it); if (c >= 0) ch.push_back(c); }
+            std::sort(ch.begin(), ch.end());                                // (C.16)
+            child_.insert(child_.end(), ch.begin(), ch.end());
+            child_off_.push_back((int32_t)child_.size());
+            parent_.push_back(index_of(pKF->GetParent()));
+        }
+        mp_obs_off_.assign(1, 0);
+        for (size_t i = 0; i < mps_.size(); ++i) {
+            mp_bad_.push_back(mps_[i]->isBad() ? 1 : 0);
+            const std::map<KeyFrameT*, size_t> observations = mps_[i]->GetObservations();
+            for (typename std::map<KeyFrameT*, size_t>::const_iterator it = observations.begin(); it != observations.end(); ++it) { const int c = index_of(it->first); if (c >= 0) mp_obs_.push_back(c); }
+            mp_obs_off_.push_back((int32_t)mp_obs_.size());
+        }
+        for (size_t i = 0; i < mls_.size(); ++i) ml_bad_.push_back(mls_[i]->isBad() ? 1 : 0);
+        kf_bad_.reserve(n + 1); parent_.reserve(n + 1);                     // (never a null pointer)
+        const bool lines = !mls_.empty();
+        g_.n_kf = n; g_.n_mp = (int32_t)mps_.size(); g_.n_ml = (int32_t)mls_.size();
+        g_.mp_obs_offsets = mp_obs_off_.data(); g_.mp_obs_kf = mp_obs_.data(); g_.mp_bad = mp_bad_.data(); g_.ml_bad = lines ? ml_bad_.data() : nullptr;
+        g_.kf_bad = kf_bad_.data(); g_.kf_mp_offsets = kf_mp_off_.data(); g_.kf_mp_index = kf_mp_.data();
+        g_.kf_ml_offsets = lines ? kf_ml_off_.data() : nullptr; g_.kf_ml_index = lines ? kf_ml_.data() : nullptr;
+        g_.kf_covis_offsets = covis_off_.data(); g_.kf_covis_index = covis_.data(); g_.kf_child_offsets = child_off_.data(); g_.kf_child_index = child_.data();
+        g_.kf_parent = parent_.data();
+    }
+    MapGraphOf(const MapGraphOf&) = delete;
+    MapGraphOf& operator=(const MapGraphOf&) = delete;
+
+    const olf_map_graph& graph() const { return g_; }
+    int index_of(KeyFrameT* p) const { return lookup(kf_index_, p); }
+    int index_of(MapPointT* p) const { return lookup(mp_index_, p); }
+    int line_index_of(MapLineT* p) const { return lookup(ml_index_, p); }
+
+    // a frame's mvpMapPoints / mvpMapLines as rows of d_frame_mp / d_frame_ml: mp_row [cap], ml_row [lcap] (or NULL), -1 from N / N_l on
+    template <class FrameT> void FrameRows(const FrameT& F, int32_t* mp_row, int cap, int32_t* ml_row, int lcap) const
+    {
+        for (int i = 0; i < cap; ++i) mp_row[i] = i < (int)F.mvpMapPoints.size() && F.mvpMapPoints[i] ? index_of(F.mvpMapPoints[i]) : -1;
+        if (ml_row) for (int i = 0; i < lcap; ++i) ml_row[i] = i < (int)F.mvpMapLines.size() && F.mvpMapLines[i] ? line_index_of(F.mvpMapLines[i]) : -1;
+    }
+
+    // What UpdateLocalMap leaves behind for frame j of a batch, from the outputs of olf_update_local_map*: the held points and lines that were bad are set to
+    // NULL (:2097, :2114; mp_row_in / mp_row_out: the frame's rows before and after, ml rows or NULL); with n_voted[j] == 0 nothing else changes (the
+    // reference returns at :2120 and rebuilds its point lists from the key frames it had: the caller's chain); otherwise mvpLocalKeyFrames, mvpLocalMapPoints
+    // and mvpLocalMapLines are replaced, and mpReferenceKF and the frame's mpReferenceKF are set when ref_kf[j] >= 0 (:2200-2204).
+    template <class FrameT>
+    void WriteBack(int j, FrameT& F, const int32_t* mp_row_in, const int32_t* mp_row_out, const int32_t* ml_row_in, const int32_t* ml_row_out, const int32_t* ref_kf,
+                   const int32_t* n_voted, const int32_t* kf_offsets, const int32_t* kf_index, const int32_t* mp_offsets, const int32_t* mp_index,
+                   const int32_t* ml_offsets, const int32_t* ml_index, std::vector<KeyFrameT*>& mvpLocalKeyFrames, std::vector<MapPointT*>& mvpLocalMapPoints,
+                   std::vector<MapLineT*>& mvpLocalMapLines, KeyFrameT*& mpReferenceKF) const
+    {
+        for (size_t i = 0; i < F.mvpMapPoints.size(); ++i) if (mp_row_in[i] >= 0 && mp_row_out[i] < 0) F.mvpMapPoints[i] = static_cast<MapPointT*>(nullptr);
+        if (ml_row_in && ml_row_out) for (size_t i = 0; i < F.mvpMapLines.size(); ++i) if (ml_row_in[i] >= 0 && ml_row_out[i] < 0) F.mvpMapLines[i] = static_cast<MapLineT*>(nullptr);
+        if (n_voted[j] == 0) return;
+        mvpLocalKeyFrames.clear(); mvpLocalMapPoints.clear(); mvpLocalMapLines.clear();
+        for (int e = kf_offsets[j]; e < kf_offsets[j + 1]; ++e) mvpLocalKeyFrames.push_back(kfs_[kf_index[e]]);
+        for (int e = mp_offsets[j]; e < mp_offsets[j + 1]; ++e) mvpLocalMapPoints.push_back(mps_[mp_index[e]]);
+        for (int e = ml_offsets[j]; e < ml_offsets[j + 1]; ++e) mvpLocalMapLines.push_back(mls_[ml_index[e]]);
+        if (ref_kf[j] >= 0) { mpReferenceKF = kfs_[ref_kf[j]]; F.mpReferenceKF = mpReferenceKF; }
+    }
+
+private:
+    template <class T> static int lookup(const std::map<T*, int32_t>& m, T* p)
+    {
+        if (!p) return -1;
+        typename std::map<T*, int32_t>::const_iterator it = m.find(p);
+        return it == m.end() ? -1 : it->second;
+    }
+    template <class T> static int32_t number(std::map<T*, int32_t>& m, std::vector<T*>& v, T* p)
+    {
+        typename std::map<T*, int32_t>::const_iterator it = m.find(p);
+        if (it != m.end()) return it->second;
+        const int32_t i = (int32_t)v.size();
+        m[p] = i; v.push_back(p);
+        return i;
+    }
+    std::vector<KeyFrameT*> kfs_; std::vector<MapPointT*> mps_; std::vector<MapLineT*> mls_;
+    std::map<KeyFrameT*, int32_t> kf_index_; std::map<MapPointT*, int32_t> mp_index_; std::map<MapLineT*, int32_t> ml_index_;
+    std::vector<int32_t> mp_obs_off_, mp_obs_, kf_mp_off_, kf_mp_, kf_ml_off_, kf_ml_, covis_off_, covis_, child_off_, child_, parent_;
+    std::vector<uint8_t> mp_bad_, ml_bad_, kf_bad_;
+    olf_map_graph g_;
+};
+
+// UpdateLocalMap for one frame through the host form, as Tracking::UpdateLocalMap is called (:2028): the snapshot, the call, the write-back.  Tracking's
+// members are passed by reference.  A batch caller uses MapGraphOf, olf_update_local_map[_batch_dev] and WriteBack itself.
+template <class KeyFrameT, class MapPointT, class MapLineT, class FrameT>
+void UpdateLocalMap(const std::vector<KeyFrameT*>& vpKeyFrames, FrameT& mCurrentFrame, std::vector<KeyFrameT*>& mvpLocalKeyFrames,
+                    std::vector<MapPointT*>& mvpLocalMapPoints, std::vector<MapLineT*>& mvpLocalMapLines, KeyFrameT*& mpReferenceKF)
+{
+    olf_ctx* c = olf_detail::thread_ctx();
+    const MapGraphOf<KeyFrameT, MapPointT, MapLineT> G(vpKeyFrames);
+    const int cap = olf_orb_capacity(c), lcap = olf_line_capacity(c);
+    if ((int)mCurrentFrame.mvpMapPoints.size() > cap || (int)mCurrentFrame.mvpMapLines.size() > lcap) throw std::runtime_error("UpdateLocalMap: the frame holds more features than the context");
+    std::vector<int32_t> mp_in(cap), mp_out(cap), ml_in(lcap), ml_out(lcap);
+    G.FrameRows(mCurrentFrame, mp_in.data(), cap, ml_in.data(), lcap);
+    const int32_t n = (int32_t)mCurrentFrame.mvpMapPoints.size(), nl = (int32_t)mCurrentFrame.mvpMapLines.size();
+    const olf_map_graph& g = G.graph();
+    std::vector<int32_t> kf_index((size_t)g.n_kf + 1), mp_index((size_t)g.n_mp + 1), ml_index((size_t)g.n_ml + 1);      // (a list holds an item once)
+    int32_t ref = -1, voted = 0, kf_off[2], mp_off[2], ml_off[2];
+    olf_detail::check(olf_update_local_map(c, &g, 1, 1, &n, &nl, mp_in.data(), g.n_ml ? ml_in.data() : nullptr, mp_out.data(), g.n_ml ? ml_out.data() : nullptr, &ref, &voted,
+                                           kf_off, kf_index.data(), g.n_kf, mp_off, mp_index.data(), g.n_mp, ml_off, ml_index.data(), g.n_ml), "olf_update_local_map");
+    G.WriteBack(0, mCurrentFrame, mp_in.data(), mp_out.data(), g.n_ml ? ml_in.data() : nullptr, g.n_ml ? ml_out.data() : nullptr, &ref, &voted, kf_off, kf_index.data(),
+                mp_off, mp_index.data(), ml_off, ml_index.data(), mvpLocalKeyFrames, mvpLocalMapPoints, mvpLocalMapLines, mpReferenceKF);
+}
 
 }  // namespace ORB_SLAM2

@@ -62,6 +62,27 @@ typedef struct olf_area_query {
     int32_t min_level, max_level;
 } olf_area_query;
 
+/* One snapshot of the map as Tracking::UpdateLocalMap walks it (src/Tracking.cc:2028-2205; olf_update_local_map*, include/orbline.h).  Key frames, map
+ * points and map lines are numbered by the caller; every index array is int32, every flag array uint8.  A CSR pair is offsets [n + 1], non-decreasing from
+ * 0, and index [offsets[n]].  Convention C.16: ascending key-frame index stands for ascending KeyFrame* address. */
+typedef struct olf_map_graph {
+    int32_t n_kf, n_mp, n_ml;
+    const int32_t* mp_obs_offsets;    /* [n_mp + 1]  MapPoint::GetObservations() of every map point as key-frame indices;          */
+    const int32_t* mp_obs_kf;         /*             the order inside a point is irrelevant                                        */
+    const uint8_t* mp_bad;            /* [n_mp]      MapPoint::isBad()                                                             */
+    const uint8_t* ml_bad;            /* [n_ml]      MapLine::isBad()                                                              */
+    const uint8_t* kf_bad;            /* [n_kf]      KeyFrame::isBad()                                                             */
+    const int32_t* kf_mp_offsets;     /* [n_kf + 1]  KeyFrame::GetMapPointMatches() in slot order as map-point indices,            */
+    const int32_t* kf_mp_index;       /*             negative = NULL                                                               */
+    const int32_t* kf_ml_offsets;     /* [n_kf + 1]  KeyFrame::GetMapLineMatches() in the same form; n_ml == 0 with ml_bad and     */
+    const int32_t* kf_ml_index;       /*             both of these NULL: a map without lines                                       */
+    const int32_t* kf_covis_offsets;  /* [n_kf + 1]  mvpOrderedConnectedKeyFrames in its order (GetVectorCovisibleKeyFrames());    */
+    const int32_t* kf_covis_index;    /*             the first 10 of a row are read (GetBestCovisibilityKeyFrames(10))             */
+    const int32_t* kf_child_offsets;  /* [n_kf + 1]  KeyFrame::GetChilds(), every row strictly ascending (C.16)                    */
+    const int32_t* kf_child_index;
+    const int32_t* kf_parent;         /* [n_kf]      KeyFrame::GetParent(), -1 = none                                              */
+} olf_map_graph;
+
 /* ORBextractor ctor arguments, src/ORBextractor.cc:412-416; values from
  * Examples/PL/PL_KITTI00-02.yaml:42-55 are the defaults of olf_default_params(). */
 typedef struct olf_orb_params {

@@ -91,6 +91,13 @@ class LocalLineMapC(C.Structure):
                 [(n, C.c_void_p) for n in ("list_offsets", "list_index")] + [("n_entries", C.c_int32)])
 
 
+class MapGraphC(C.Structure):
+    """olf_map_graph (include/orbline_types.h): one snapshot of the map as Tracking::UpdateLocalMap walks it"""
+    _fields_ = ([(n, C.c_int32) for n in ("n_kf", "n_mp", "n_ml")] +
+                [(n, C.c_void_p) for n in ("mp_obs_offsets", "mp_obs_kf", "mp_bad", "ml_bad", "kf_bad", "kf_mp_offsets", "kf_mp_index", "kf_ml_offsets", "kf_ml_index",
+                                           "kf_covis_offsets", "kf_covis_index", "kf_child_offsets", "kf_child_index", "kf_parent")])
+
+
 class BowCsrC(C.Structure):
     """olf_bow_csr (include/orbline.h): n BoW vectors as offsets, ascending word ids and values"""
     _fields_ = [(n, C.c_void_p) for n in ("off", "ids", "vals")]
@@ -272,6 +279,8 @@ def lib():
         L.olf_kfdb_detect.argtypes = ([P, C.c_int, C.c_int, P, C.POINTER(BowCsrC), C.POINTER(BowCsrC)] + [P] * 9 + [C.c_int])
         L.olf_bow_score_pairs_dev.argtypes = [P, C.c_int, C.c_int, P, C.POINTER(BowCsrC), C.c_int, P, P]
         L.olf_bow_score.argtypes = [P, P, P, C.c_int, P, P, C.c_int, C.POINTER(C.c_double)]
+        L.olf_update_local_map_batch_dev.argtypes = ([P, C.POINTER(MapGraphC), C.c_int, C.c_int] + [P] * 8 + [P, P, C.c_int] * 3 + [P])
+        L.olf_update_local_map.argtypes = ([P, C.POINTER(MapGraphC), C.c_int, C.c_int] + [P] * 8 + [P, P, C.c_int] * 3)
         L.olf_profile_enable.argtypes = [C.c_void_p, C.c_int]
         L.olf_profile_reset.argtypes = [C.c_void_p]
         L.olf_profile_stage_name.restype = C.c_char_p

@@ -18,7 +18,7 @@
 namespace olf {
 
 constexpr size_t kCarveAlign = 16;
-constexpr int kCarveMaxRegions = 8;      // (olf_search_local_map_batch_dev cuts seven)
+constexpr int kCarveMaxRegions = 32;     // (olf_update_local_map stages a map graph and its outputs: twenty-six)
 
 class CarveLayout {
 public:

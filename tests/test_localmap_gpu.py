@@ -1,0 +1,405 @@
+"""GPU parity: olf_update_local_map_batch_dev and olf_update_local_map -- Tracking::UpdateLocalMap (src/Tracking.cc:2028-2205) for a batch of frames against
+one snapshot of the map.  Every comparison is exact equality of every output with the line-by-line restatement (tests/localmap_reference.py); the scenes
+(tests/localmap_scenes.py) are the smallest at which each rule can go wrong.  The context is 320 x 240, the smallest image the batch tests use."""
+import ctypes as C
+import numpy as np
+import pytest
+import localmap_reference as R
+import localmap_scenes as S
+import orb_line_slam_amd as ola
+from orb_line_slam_amd import MapGraph, _lib, localmap
+from orb_line_slam_amd._lib import OLF_ERR_CAPACITY, OlfError, lib
+
+pytestmark = pytest.mark.gpu
+
+LINE_CAP = 330
+STATUS_TEXT = {
+    512: "a batched point entry left out a list index or a per-frame map-point index outside the map",
+    1024: "a batched line entry left out a list index or a per-frame map-line index outside the map",
+    4096: "a map-graph entry left out a key-frame index outside the graph",
+    8192: "local key-frame, map-point or map-line list of olf_update_local_map_batch_dev",
+}
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import torch  # noqa: F401  (the device tensors below)
+    p = _lib.default_params()
+    p.orb.nfeatures = 300
+    p.line.lsd_nfeatures = LINE_CAP
+    c = _lib.Context(p, 320, 240, 2)
+    assert c.orb_capacity >= 300 and c.line_capacity == LINE_CAP
+    yield c
+    c.close()
+
+
+def up(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def reference(scene):
+    return R.Map(**scene.graph()).update_local_map(scene.frame_mp, scene.frame_ml)
+
+
+def rows(ctx, frame_rows, cap, img_stride, live):
+    """[n_frames, cap] with `live` (an index that would vote) past every row's end, and the counts in the extractor's layout"""
+    nf = len(frame_rows)
+    a = np.full((max(nf, 1), cap), live, np.int32)
+    cnt = np.full(max(nf * img_stride, 1), 17, np.int32)
+    for j, r in enumerate(frame_rows):
+        a[j, :len(r)] = r
+        cnt[j * img_stride] = len(r)
+    return a, cnt
+
+
+SENTINEL = -7
+
+
+def run_dev(ctx, scene, graph=None, capacities=None, img_stride=1, inplace=False, slack=8):
+    """the device form on a scene; returns (out: dict of numpy arrays, graph).  The index tensors are `slack` longer than the capacity told, filled with
+    SENTINEL: nothing may be written there."""
+    import torch
+    graph = MapGraph(**scene.graph()) if graph is None else graph
+    nf = len(scene.frame_mp)
+    fmp, cnt = rows(ctx, scene.frame_mp, ctx.orb_capacity, img_stride, 0 if graph.n_mp else -1)
+    fml = lcnt = None
+    if scene.frame_ml is not None:
+        fml, lcnt = rows(ctx, scene.frame_ml, ctx.line_capacity, img_stride, 0 if graph.n_ml else -1)
+    if capacities is None:
+        exp = reference(scene)
+        capacities = [sum(len(e[k]) for e in exp) for k in ("local_kfs", "local_points", "local_lines")]
+    out = {k + "_index": torch.full((c + slack,), SENTINEL, dtype=torch.int32, device="cuda") for k, c in zip(("kf", "mp", "ml"), capacities)}
+    for k in ("kf", "mp", "ml"):
+        out[k + "_offsets"] = torch.full((nf + 1,), SENTINEL, dtype=torch.int32, device="cuda")
+    out["ref_kf"] = torch.full((max(nf, 1),), SENTINEL, dtype=torch.int32, device="cuda")
+    out["n_voted"] = torch.full((max(nf, 1),), SENTINEL, dtype=torch.int32, device="cuda")
+    d_fmp, d_fml = up(fmp), None if fml is None else up(fml)
+    res = localmap.update_local_map_batch(graph, nf, d_fmp, up(cnt), d_fml, None if lcnt is None else up(lcnt), img_stride=img_stride, capacities=capacities,
+                                          out=out, inplace=inplace, context=ctx)
+    torch.cuda.synchronize()
+    got = {k: (None if v is None else v.cpu().numpy()) for k, v in res.items()}
+    got["capacities"] = capacities
+    return got, graph
+
+
+def assert_equal(ctx, got, exp, scene, truncated=False):
+    """every output of the device form against the restatement's per-frame answers"""
+    nf = len(exp)
+    for k, key in (("kf", "local_kfs"), ("mp", "local_points"), ("ml", "local_lines")):
+        offs, idx, cap = got[k + "_offsets"], got[k + "_index"], got["capacities"][{"kf": 0, "mp": 1, "ml": 2}[k]]
+        want = np.concatenate([[0], np.cumsum([len(e[key]) for e in exp])])
+        assert np.array_equal(offs, want), (k, offs, want)
+        flat = np.asarray([v for e in exp for v in e[key]], np.int32)
+        assert truncated or len(flat) <= cap
+        assert np.array_equal(idx[:min(len(flat), cap)], flat[:cap]), k
+        assert np.all(idx[min(len(flat), cap):] == SENTINEL), k + ": written past the list or the capacity"
+    assert [int(v) for v in got["ref_kf"][:nf]] == [e["ref_kf"] for e in exp]
+    assert [int(v) for v in got["n_voted"][:nf]] == [e["n_voted"] for e in exp]
+    for j, e in enumerate(exp):
+        n = len(e["frame_mp"])
+        assert got["frame_mp"][j, :n].tolist() == e["frame_mp"] and np.all(got["frame_mp"][j, n:] == -1)
+        if e["frame_ml"] is not None:
+            n = len(e["frame_ml"])
+            assert got["frame_ml"][j, :n].tolist() == e["frame_ml"] and np.all(got["frame_ml"][j, n:] == -1)
+
+
+def check(ctx, scene, **kw):
+    exp = reference(scene)
+    got, graph = run_dev(ctx, scene, **kw)
+    assert_equal(ctx, got, exp, scene)
+    ctx.poll_status()
+    return exp, got, graph
+
+
+# ---- 1: random graphs ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_frames", [1, 17])
+@pytest.mark.parametrize("n_mp", [0, 40, 300])
+@pytest.mark.parametrize("n_kf", [1, 7, 65])
+def test_random_graphs(ctx, n_kf, n_mp, n_frames):
+    scene = S.random_scene(1000 * n_kf + n_mp + n_frames, n_kf, n_mp, n_frames, n_ml=n_mp // 3)
+    exp, _, _ = check(ctx, scene, img_stride=1 + n_frames % 2)
+    if n_mp == 300 and n_frames == 17:
+        assert any(e["n_voted"] > 0 and -1 in e["frame_mp"] for e in exp) and any(len(e["local_points"]) > 40 for e in exp)
+        if n_kf == 65:
+            assert any(e["local_kfs"] != sorted(e["local_kfs"]) for e in exp)      # (the extension loop added some)
+
+
+# ---- 2: ties -------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("scene", [lambda: S.ties(2), lambda: S.ties(3), S.bad_kf_has_most_votes])
+def test_ties_and_a_bad_winner(ctx, scene):
+    exp, _, _ = check(ctx, scene())
+    assert exp[0]["ref_kf"] in (3, 4)
+
+
+# ---- 3: the extension loop --------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("scene, kfs", [(S.eleventh_neighbour_free, [0, 1, 2, 3, 4, 5]), (S.child_after_bad_child, [2, 4, 3]), (S.bad_parent, [2, 0]),
+                                        (S.parent_at_first_member, [1, 2, 3, 0])])
+def test_extension_rules(ctx, scene, kfs):
+    exp, _, _ = check(ctx, scene())
+    assert exp[0]["local_kfs"] == kfs
+
+
+@pytest.mark.parametrize("n_first, n_added", [(79, 2), (80, 1), (81, 0)])
+def test_more_than_80(ctx, n_first, n_added):
+    exp, _, _ = check(ctx, S.first_list_of(n_first))
+    assert len(exp[0]["local_kfs"]) == n_first + n_added
+
+
+def test_five_key_frames(ctx):
+    exp, _, _ = check(ctx, S.five_kf())
+    assert exp == S.FIVE_KF_EXPECTED
+
+
+# ---- 4: positional de-duplication, for points and for lines ----------------------------------------------------------------------------------------
+DEDUP = {"one_kf_slots_3_and_7": S.dup_in_one_kf, "two_kfs_of_5": S.dup_across_two_kfs, "across_64": lambda: S.dup_straddling(64), "across_256": lambda: S.dup_straddling(256), "across_1024": lambda: S.dup_straddling(1024),
+         "pair_across_64": lambda: S.dup_across_two_kfs(62, 8, at_a=61, at_b=2), "pair_across_256": lambda: S.dup_across_two_kfs(254, 8, at_a=253, at_b=3)}
+
+
+@pytest.mark.parametrize("lines", [False, True])
+@pytest.mark.parametrize("name", list(DEDUP))
+def test_first_occurrence_is_positional(ctx, name, lines):
+    scene = DEDUP[name]()
+    if lines:
+        scene.with_lines_like_points()
+    exp, _, _ = check(ctx, scene)
+    slots = [v for k in exp[0]["local_kfs"] for v in scene.kf_mp[k]]
+    assert len(exp[0]["local_points"]) < len(slots)
+    assert not lines or exp[0]["local_lines"] == exp[0]["local_points"]
+
+
+def test_many_equal_points_in_one_chunk(ctx):
+    """every chunk position holds one of three points, and a fourth distinct one sits between: the hash rounds and their fall-back agree with the order"""
+    s = S.Scene(1)
+    a, b, c = s.point([0], slot=False), s.point([0], slot=False), s.point([0], slot=False)
+    rng = np.random.default_rng(9)
+    s.kf_mp[0] = [int(v) for v in rng.choice([a, b, c], 2500)]
+    s.kf_mp[0][300] = s.point([0], slot=False)
+    s.frame_mp = [[a]]
+    check(ctx, s.with_lines_like_points())
+
+
+@pytest.mark.parametrize("scene", [lambda: S.random_scene(5, 7, 300, 5, n_ml=100), lambda: S.dup_straddling(1024), lambda: S.dup_across_two_kfs()])
+def test_bitmaps_in_scratch(ctx, scene):
+    """more points than a frame's LDS bitmap holds (262144 points and lines together): the bitmaps live in scratch, the counting pass sets and the filling pass
+    clears them.  The same scenes, their points spread over a map of 262500."""
+    scene = S.spread_points(scene(), 262500)
+    exp, _, _ = check(ctx, scene)
+    assert len(scene.mp_bad) > 8192 * 32 and any(len(e["local_points"]) > 5 for e in exp)
+    check(ctx, scene)                                                # again on the same stream: the scratch bitmaps start from zero
+
+
+# ---- 5: empty cases --------------------------------------------------------------------------------------------------------------------------------------
+def test_empty_cases(ctx):
+    exp, _, _ = check(ctx, S.frame_holds_nothing())
+    assert [e["n_voted"] for e in exp] == [0, 1, 0]
+    exp, _, _ = check(ctx, S.all_voted_bad())
+    assert exp[0]["n_voted"] == 2 and exp[0]["local_kfs"] == []
+    scene = S.random_scene(4, 7, 40, 3)                              # n_ml == 0 with NULL line arrays
+    assert scene.kf_ml is None and scene.frame_ml is None
+    _, got, graph = check(ctx, scene)
+    assert graph.c_dev().kf_ml_offsets is None and np.all(got["ml_offsets"] == 0)
+
+
+def test_no_frames_writes_nothing(ctx):
+    scene = S.voting(3, {1: 1})
+    scene.frame_mp = []
+    got, _ = run_dev(ctx, scene, capacities=[4, 4, 4])
+    for k in ("kf_offsets", "mp_offsets", "ml_offsets", "kf_index", "mp_index", "ml_index", "ref_kf", "n_voted"):
+        assert np.all(got[k] == SENTINEL), k
+    ctx.poll_status()
+    assert ola.UpdateLocalMap(MapGraph(**scene.graph()), [], context=ctx) == []
+
+
+# ---- 6: malformed indices -----------------------------------------------------------------------------------------------------------------------------
+def _status(ctx, bit):
+    with pytest.raises(OlfError) as e:
+        ctx.poll_status()
+    assert e.value.code == OLF_ERR_CAPACITY and "flags=%d (%d: %s)" % (bit, bit, STATUS_TEXT[bit]) in str(e.value), str(e.value)
+    ctx.poll_status()                                                # (read and cleared)
+
+
+def _malformed_base():
+    scene = S.random_scene(77, 30, 200, 6, n_ml=60)
+    exp = reference(scene)
+    j = next(j for j, e in enumerate(exp) if 0 < e["n_voted"] and 3 <= len(e["local_kfs"]) <= 80 and len(e["local_points"]) > 5 and len(e["local_lines"]) > 2)
+    return scene, exp, j
+
+
+def test_malformed_point_index(ctx):
+    scene, exp, j = _malformed_base()
+    graph = MapGraph(**scene.graph())
+    kf = exp[j]["local_kfs"][1]
+    slot = next(i for i, v in enumerate(scene.kf_mp[kf]) if v >= 0)
+    graph.kf_mp_index[graph.kf_mp_offsets[kf] + slot] = graph.n_mp + 5
+    scene.kf_mp[kf][slot] = -1                                        # left out = as if the slot were NULL
+    held = next(i for i, v in enumerate(scene.frame_mp[j]) if v >= 0)
+    rows_in = [list(r) for r in scene.frame_mp]
+    rows_in[j][held] = graph.n_mp                                     # holds nothing: no vote, and it is handed back as it came
+    scene.frame_mp[j][held] = -1
+    want = reference(scene)
+    want[j]["frame_mp"][held] = graph.n_mp
+    scene.frame_mp = rows_in
+    got, _ = run_dev(ctx, scene, graph=graph, capacities=[sum(len(e[k]) for e in want) for k in ("local_kfs", "local_points", "local_lines")])
+    assert_equal(ctx, got, want, scene)
+    _status(ctx, 512)
+
+
+def test_malformed_line_index(ctx):
+    scene, exp, j = _malformed_base()
+    graph = MapGraph(**scene.graph())
+    kf = next(k for k in exp[j]["local_kfs"] if any(v >= 0 for v in scene.kf_ml[k]))
+    slot = next(i for i, v in enumerate(scene.kf_ml[kf]) if v >= 0)
+    graph.kf_ml_index[graph.kf_ml_offsets[kf] + slot] = graph.n_ml
+    scene.kf_ml[kf][slot] = -1
+    want = reference(scene)
+    got, _ = run_dev(ctx, scene, graph=graph, capacities=[sum(len(e[k]) for e in want) for k in ("local_kfs", "local_points", "local_lines")])
+    assert_equal(ctx, got, want, scene)
+    _status(ctx, 1024)
+
+
+@pytest.mark.parametrize("where", ["observation", "neighbour", "child", "parent", "parent_below_minus_one"])
+def test_malformed_key_frame_index(ctx, where):
+    scene, exp, j = _malformed_base()
+    kf = exp[j]["local_kfs"][0]                                      # the first member: the extension loop visits it whatever else happens
+    if where == "neighbour":
+        scene.kf_covis[kf] = scene.kf_covis[kf][:8] + [kf]          # (a short row, so that leaving one out and skipping it in place are the same)
+    graph = MapGraph(**scene.graph())
+    if where == "observation":
+        p = next(v for v in scene.frame_mp[j] if v >= 0 and not scene.mp_bad[v])
+        graph.mp_obs_kf[graph.mp_obs_offsets[p]] = graph.n_kf
+        scene.mp_obs[p] = scene.mp_obs[p][1:]
+    elif where == "neighbour":
+        graph.kf_covis_index[graph.kf_covis_offsets[kf + 1] - 1] = -3
+        scene.kf_covis[kf] = scene.kf_covis[kf][:-1]
+    elif where == "child":
+        scene.kf_children[kf] = [kf] + scene.kf_children[kf]         # (a row with one more entry, the lowest ...)
+        graph = MapGraph(**scene.graph())
+        row = graph.kf_child_index[graph.kf_child_offsets[kf]:graph.kf_child_offsets[kf + 1]]
+        row[:] = [-5] + sorted(scene.kf_children[kf][1:])            # (... which is malformed and still ascends)
+        scene.kf_children[kf] = scene.kf_children[kf][1:]
+    else:
+        graph.kf_parent[kf] = graph.n_kf if where == "parent" else -2
+        scene.kf_parent[kf] = -1                                     # (its old parent still lists it as a child, in the graph and in the restatement)
+    want = reference(scene)
+    got, _ = run_dev(ctx, scene, graph=graph, capacities=[sum(len(e[k]) for e in want) for k in ("local_kfs", "local_points", "local_lines")])
+    assert_equal(ctx, got, want, scene)
+    _status(ctx, 4096)
+
+
+# ---- 7: capacities ------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", [0, 1, 2])
+def test_list_one_entry_too_long(ctx, which):
+    scene = S.random_scene(12, 20, 120, 5, n_ml=40)
+    exp = reference(scene)
+    caps = [sum(len(e[k]) for e in exp) for k in ("local_kfs", "local_points", "local_lines")]
+    assert min(caps) > 3
+    caps[which] -= 1
+    got, graph = run_dev(ctx, scene, capacities=caps)
+    assert_equal(ctx, got, exp, scene, truncated=True)               # complete offsets, the first `capacity` entries, nothing past the capacity
+    _status(ctx, 8192)
+    # the host form: OLF_ERR_CAPACITY, complete offsets
+    with pytest.raises(OlfError) as e:
+        ola.UpdateLocalMap(graph, scene.frame_mp, scene.frame_ml, context=ctx, capacities=caps)
+    assert e.value.code == OLF_ERR_CAPACITY and STATUS_TEXT[8192] in str(e.value)
+
+
+def test_too_many_key_frames_are_refused_before_any_launch(ctx):
+    import torch
+    n = localmap.OLF_LOCALMAP_MAX_KF + 1
+    g = _lib.MapGraphC()
+    z = torch.zeros(n + 1, dtype=torch.int32, device="cuda")
+    g.n_kf, g.n_mp, g.n_ml = n, 0, 0
+    g.mp_obs_offsets = g.kf_mp_offsets = g.kf_covis_offsets = g.kf_child_offsets = g.kf_parent = g.kf_bad = z.data_ptr()
+    out = torch.full((8,), SENTINEL, dtype=torch.int32, device="cuda")
+    fmp = torch.full((1, ctx.orb_capacity), -1, dtype=torch.int32, device="cuda")
+    rc = lib().olf_update_local_map_batch_dev(ctx.handle, C.byref(g), 1, 1, None, None, fmp.data_ptr(), None, None, None, out.data_ptr(), out.data_ptr(),
+                                              out.data_ptr(), None, 0, out.data_ptr(), None, 0, out.data_ptr(), None, 0, None)
+    assert rc == OLF_ERR_CAPACITY and "OLF_LOCALMAP_MAX_KF" in _lib.last_error()
+    torch.cuda.synchronize()
+    assert np.all(out.cpu().numpy() == SENTINEL)
+    ctx.poll_status()
+
+
+# ---- 8: the host form ----------------------------------------------------------------------------------------------------------------------------------
+def test_host_form_equals_device_form(ctx):
+    scene = S.random_scene(31, 65, 300, 9, n_ml=100)
+    exp = reference(scene)
+    got = ola.UpdateLocalMap(MapGraph(**scene.graph()), scene.frame_mp, scene.frame_ml, context=ctx)
+    for g, e in zip(got, exp):
+        for k in ("local_kfs", "local_points", "local_lines", "frame_mp", "frame_ml"):
+            assert g[k].tolist() == e[k], k
+        assert (g["ref_kf"], g["n_voted"]) == (e["ref_kf"], e["n_voted"])
+    check(ctx, scene)
+    got = ola.UpdateLocalMap(MapGraph(**S.five_kf().graph()), S.five_kf().frame_mp, S.five_kf().frame_ml, context=ctx)
+    assert [{k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in g.items()} for g in got] == S.FIVE_KF_EXPECTED
+
+
+# ---- 9: cleaning in place ---------------------------------------------------------------------------------------------------------------------------------
+def test_in_place(ctx):
+    scene = S.random_scene(8, 20, 150, 7, n_ml=50, bad=0.3)
+    exp = reference(scene)
+    assert sum(a != b for e, r in zip(exp, scene.frame_mp) for a, b in zip(e["frame_mp"], r)) > 5
+    got, _ = run_dev(ctx, scene, inplace=True)
+    assert_equal(ctx, got, exp, scene)
+    ctx.poll_status()
+
+
+# ---- 10: the lists go straight into the two local searches -----------------------------------------------------------------------------------------
+def test_point_lists_feed_the_local_search(ctx):
+    import torch
+    import test_local_batch_gpu as lb
+    rng = np.random.default_rng(21)
+    frames = lb.make_chain(rng, [lb.pose(tx=0.05, ry_deg=1.0), lb.pose(tx=0.05, tz=0.1), lb.pose(ry_deg=-2.0)], n=110, n_dis=25)
+    mp = lb.LocalMap(rng, frames, lb.SF8)
+    held = mp.held(rng, frames, 0.3)
+    nk = len(frames)
+    s = S.Scene(nk, mp.n)                                            # key frame k = frame k: its slots are its own points; point i is seen by its frame and the next
+    for k, f in enumerate(frames):
+        s.kf_mp[k] = [int(mp.base[k] + i) for i in range(len(f.keys))] + ([int(mp.base[k - 1] + i) for i in range(0, len(frames[k - 1].keys), 3)] if k else [])
+        for i in range(len(f.keys)):
+            s.mp_obs[int(mp.base[k] + i)] = [k] + ([k + 1] if k + 1 < nk and i % 3 == 0 else [])
+    s.mp_bad = [int(v) for v in mp.bad]
+    s.kf_covis = [[k2 for k2 in range(nk) if abs(k2 - k) == 1] for k in range(nk)]
+    s.frame_mp = [[int(v) for v in h] for h in held]
+    exp = reference(s)
+    assert all(len(e["local_points"]) > 100 for e in exp) and len({tuple(e["local_points"]) for e in exp}) > 1
+    by_hand = lb.DeviceBatch(ctx, frames, mp, frame_mp=held, lists=[e["local_points"] for e in exp])
+    want = [x.cpu().numpy() for x in by_hand.search()]
+    chained = lb.DeviceBatch(ctx, frames, mp, frame_mp=held)
+    cap = sum(len(e["local_points"]) for e in exp)
+    res = localmap.update_local_map_batch(MapGraph(**s.graph()), nk, chained.frame_mp, chained.counts, capacities=(nk * nk, cap, 0), context=ctx)
+    chained.map.list_offsets, chained.map.list_index = res["mp_offsets"], res["mp_index"]      # device tensors, as they are
+    got = [x.cpu().numpy() for x in chained.search()]
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and want[1].sum() > 10
+    ctx.synchronize()
+
+
+def test_line_lists_feed_the_local_line_search(ctx, oracle):
+    import line_scenes as ls
+    import test_line_batch_gpu as tl
+    frames, mp, lists, _ = ls.local_case(oracle, "lists_a")
+    assert all(len(fr.kls) <= ctx.line_capacity for fr in frames)
+    nf, nk = len(frames), 6
+    rng = np.random.default_rng(22)
+    s = S.Scene(nk, 0, mp.n)
+    for k in range(nk):
+        s.point([k])
+        s.kf_ml[k] = [int(v) for v in rng.choice(mp.n, size=min(mp.n, 40 + 10 * k), replace=False)] + [-1, int(rng.integers(mp.n))]
+    s.ml_bad = [int(v) for v in mp.bad]
+    s.kf_covis = [[(k + 1) % nk] for k in range(nk)]
+    s.frame_mp = [[j % nk, (j + 2) % nk] for j in range(nf)]
+    exp = reference(s)
+    assert all(len(e["local_lines"]) > 30 for e in exp)
+    by_hand = tl.DeviceLines(ctx, frames, mp, [e["local_lines"] for e in exp])
+    want = [x.cpu().numpy() for x in by_hand.search()]
+    chained = tl.DeviceLines(ctx, frames, mp)
+    fmp = np.full((nf, ctx.orb_capacity), -1, np.int32)
+    fmp[:, :2] = s.frame_mp
+    res = localmap.update_local_map_batch(MapGraph(**s.graph()), nf, up(fmp), None, capacities=(nf * nk, nf * nk, sum(len(e["local_lines"]) for e in exp)), context=ctx)
+    chained.map.list_offsets, chained.map.list_index = res["ml_offsets"], res["ml_index"]
+    got = [x.cpu().numpy() for x in chained.search()]
+    for a, b in zip(got, want):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    assert (want[2] >= 0).sum() > 5
+    ctx.synchronize()
