@@ -862,6 +862,58 @@ int olf_update_local_map(olf_ctx* ctx, const olf_map_graph* g, int n_frames, int
                          int32_t* kf_offsets, int32_t* kf_index, int kf_capacity, int32_t* mp_offsets, int32_t* mp_index, int mp_capacity, int32_t* ml_offsets,
                          int32_t* ml_index, int ml_capacity);
 
+/* ---- KeyFrame::UpdateConnections for a list of key frames on the device (csrc/connections_batch.hip) --------------------------------------------------
+ * void KeyFrame::UpdateConnections() (src/KeyFrame.cc:446-557) for n_list key frames against one snapshot of the map (olf_map_graph, device pointers here):
+ * the call of LocalMapping for every new key frame (src/LocalMapping.cc:164) and after SearchInNeighbors (:533), of Tracking for the two initial key frames
+ * (src/Tracking.cc:822-823) and of LoopClosing::CorrectLoop over whole neighbourhoods (src/LoopClosing.cc:438, 521, 560).  It produces kf_covis_offsets /
+ * kf_covis_index of an olf_map_graph on the device, which olf_update_local_map_batch_dev reads.  Each listed key frame is computed as its own call would
+ * compute it from the map as it stands.  That is exact for the key frame's own three members (mConnectedKeyFrameWeights, mvpOrderedConnectedKeyFrames,
+ * mvOrderedWeights): KFcounter depends on slots, observations and isBad() of points only, none of which UpdateConnections changes.  The reciprocal
+ * AddConnection(this, w) on the other key frames (:522, :529) and the parent assignment (:549-554) are mutations in the reference's call order and stay the
+ * caller's; the ordered row with its weights is exactly the list of those reciprocal calls.  Element for element under convention C.16:
+ * ascending key-frame index stands for ascending KeyFrame*.
+ * Counting (:461-479): every slot of the listed key frame (kf_mp_*) that is not NULL (negative) and not bad (mp_bad) adds 1 to each key frame of its
+ * observation row (mp_obs_*), the listed key frame itself excepted (mnId == mnId: index equality); a point held in two slots counts twice; isBad() of the
+ * observing key frames is not looked at; lines do not vote (:496 is commented out), so kf_ml_* and ml_bad are not read.  That a row of mp_obs_kf names a
+ * key frame at most once (the keys of a std::map) is the caller's contract.
+ * d_kf_list [n_list], or NULL for the key frames 0 .. n_list - 1; a key frame may be listed twice (it is computed twice).  th >= 1: the threshold of :508,
+ * OLF_COVIS_TH in the reference.  Outputs per listed key frame j:
+ *   d_n_counted [n_list]   KFcounter.size().  With 0 the reference returns at :501 and keeps the old members: here both rows of j are empty and
+ *                          d_kf_max[j] = -1, d_w_max[j] = 0; keeping the old members stays the caller's.
+ *   d_kf_max / d_w_max     pKFmax, nmax: the comparison at :514 is strict over ascending index, so the LOWEST index among the highest counts.
+ *   d_conn_offsets [n_list + 1], d_conn_index / d_conn_weight [conn_capacity]     KFcounter as a CSR: every key frame with a count > 0 in ascending index --
+ *                          mConnectedKeyFrameWeights (:545), GetConnectedKeyFrames().
+ *   d_covis_offsets [n_list + 1], d_covis_index / d_covis_weight [covis_capacity] mvpOrderedConnectedKeyFrames / mvOrderedWeights: the key frames with count
+ *                          >= th (:519), or, if there are none, the single pair (nmax, pKFmax) (:526-530); sorted as sort(vPairs) followed by push_front
+ *                          leaves them (:532-539): descending weight, and among equal weights DESCENDING index -- the opposite tie rule to d_kf_max.
+ *                          d_covis_index[d_covis_offsets[j]] is the parent candidate of :551; GetCovisiblesByWeight(w) is the prefix with weight >= w.
+ * With d_kf_list == NULL and n_list == n_kf, d_covis_offsets / d_covis_index are kf_covis_offsets / kf_covis_index of an olf_map_graph as they are.
+ * Both offset arrays are always complete; nothing is written at or past a capacity, and a total beyond one sets bit 16384 of the context's status word
+ * (olf_ctx_synchronize / olf_ctx_poll_status).  Malformed indices are left out, never dereferenced: a slot index >= n_mp sets status bit 512, an
+ * observation outside [0, n_kf) bit 4096; a listed key frame outside [0, n_kf) gets empty rows, d_n_counted 0, d_kf_max -1 and bit 4096.  Rows of a CSR are
+ * clamped to [0, offsets[n]].
+ * Errors: n_kf > OLF_LOCALMAP_MAX_KF (a key frame's vote table lives in LDS): OLF_ERR_CAPACITY before anything is launched; a NULL required pointer, a
+ * negative size or th < 1: OLF_ERR_INVALID.  Of the graph only n_kf, n_mp, mp_obs_*, mp_bad and kf_mp_* are required; the other fields may be NULL.
+ * n_list == 0 writes nothing.  Does not synchronise; runs on `stream` and uses the batch scratch slot: 4 bytes per (listed key frame, key frame of the
+ * graph), the vote tables between its passes. */
+#define OLF_COVIS_TH 15                        /* int th = 15, src/KeyFrame.cc:508 */
+int olf_update_connections_batch_dev(olf_ctx* ctx, const olf_map_graph* g, int n_list, const int32_t* d_kf_list, int th, int32_t* d_n_counted, int32_t* d_kf_max,
+                                     int32_t* d_w_max, int32_t* d_conn_offsets, int32_t* d_conn_index, int32_t* d_conn_weight, int conn_capacity,
+                                     int32_t* d_covis_offsets, int32_t* d_covis_index, int32_t* d_covis_weight, int covis_capacity, void* stream);
+/* host buffers, the graph's arrays included: checks mp_obs_* and kf_mp_* (offsets non-decreasing from 0: OLF_ERR_INVALID), uploads, runs the same kernels on
+ * the context's stream, downloads.  OLF_ERR_CAPACITY when a capacity is too small: both offset arrays are complete then and each index / weight array holds
+ * its first `capacity` entries; the same code, with the message of the bit, for a malformed index. */
+int olf_update_connections(olf_ctx* ctx, const olf_map_graph* g, int n_list, const int32_t* kf_list, int th, int32_t* n_counted, int32_t* kf_max, int32_t* w_max,
+                           int32_t* conn_offsets, int32_t* conn_index, int32_t* conn_weight, int conn_capacity, int32_t* covis_offsets, int32_t* covis_index,
+                           int32_t* covis_weight, int covis_capacity);
+/* void KeyFrame::UpdateBestCovisibles() (src/KeyFrame.cc:216-235) for n_rows rows of a CSR (d_conn_offsets [n_rows + 1], d_conn_index / d_conn_weight:
+ * mConnectedKeyFrameWeights, e.g. the conn_* outputs above after the caller applied the reciprocal edges): every entry of a row is kept (no threshold), in
+ * the order rule above (descending weight, among equal weights descending index), at the same offsets of d_covis_index / d_covis_weight.  Index values are
+ * compared, not dereferenced, so nothing can be malformed; a row longer than OLF_LOCALMAP_MAX_KF sets status bit 16384 and is left unwritten.  Rows are
+ * clamped to [0, offsets[n_rows]].  A NULL pointer or a negative n_rows: OLF_ERR_INVALID.  Does not synchronise; runs on `stream`, no scratch. */
+int olf_best_covisibles_batch_dev(olf_ctx* ctx, int n_rows, const int32_t* d_conn_offsets, const int32_t* d_conn_index, const int32_t* d_conn_weight,
+                                  int32_t* d_covis_index, int32_t* d_covis_weight, void* stream);
+
 /* measurement: rate of a plain 16-byte-per-thread device copy kernel over `bytes` (read + written bytes per second): the practical HBM
  * ceiling bench.py reports next to the specification's 8 TB/s */
 int olf_debug_copy_bandwidth(olf_ctx* ctx, size_t bytes, int reps, double* gbytes_per_s);

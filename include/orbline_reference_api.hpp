@@ -850,6 +850,7 @@ public:
     MapGraphOf& operator=(const MapGraphOf&) = delete;
 
     const olf_map_graph& graph() const { return g_; }
+    KeyFrameT* key_frame(int k) const { return kfs_[k]; }
     int index_of(KeyFrameT* p) const { return lookup(kf_index_, p); }
     int index_of(MapPointT* p) const { return lookup(mp_index_, p); }
     int line_index_of(MapLineT* p) const { return lookup(ml_index_, p); }
@@ -923,6 +924,65 @@ void UpdateLocalMap(const std::vector<KeyFrameT*>& vpKeyFrames, FrameT& mCurrent
                                            kf_off, kf_index.data(), g.n_kf, mp_off, mp_index.data(), g.n_mp, ml_off, ml_index.data(), g.n_ml), "olf_update_local_map");
     G.WriteBack(0, mCurrentFrame, mp_in.data(), mp_out.data(), g.n_ml ? ml_in.data() : nullptr, g.n_ml ? ml_out.data() : nullptr, &ref, &voted, kf_off, kf_index.data(),
                 mp_off, mp_index.data(), ml_off, ml_index.data(), mvpLocalKeyFrames, mvpLocalMapPoints, mvpLocalMapLines, mpReferenceKF);
+}
+
+// ---- KeyFrame::UpdateConnections (src/KeyFrame.cc:446-557) over the reference's own types ----------------------------------------------------------------
+// The three members UpdateConnections writes (mConnectedKeyFrameWeights, mvpOrderedConnectedKeyFrames, mvOrderedWeights), mbFirstConnection and mpParent are
+// protected (include/KeyFrame.h:235-262), so the integrator adds ONE accessor to KeyFrame whose body is the locked block :541-556 as it stands:
+//     void KeyFrame::SetConnections(const std::map<KeyFrame*,int>& KFcounter, const std::vector<KeyFrame*>& vpOrdered, const std::vector<int>& vOrderedWeights)
+//     {
+//         unique_lock<mutex> lockCon(mMutexConnections);
+//         mConnectedKeyFrameWeights = KFcounter;  mvpOrderedConnectedKeyFrames = vpOrdered;  mvOrderedWeights = vOrderedWeights;
+//         if(mbFirstConnection && mnId!=0) { mpParent = mvpOrderedConnectedKeyFrames.front();  mpParent->AddChild(this);  mbFirstConnection = false; }
+//     }
+// ApplyConnections performs, in list order, what the reference does to the objects, from the outputs of olf_update_connections* for `list` (entry j = list[j]):
+// the reciprocal AddConnection(this, w) on every key frame of the ordered row (:522, :529; public), in ascending index as the loop :512-524 makes them, then
+// the key frame's own members and first-connection parent through SetConnections.  A key frame with n_counted[j] == 0 is left untouched (:501).
+template <class KeyFrameT, class MapPointT, class MapLineT>
+void ApplyConnections(const MapGraphOf<KeyFrameT, MapPointT, MapLineT>& G, const std::vector<KeyFrameT*>& list, const int32_t* n_counted, const int32_t* conn_offsets,
+                      const int32_t* conn_index, const int32_t* conn_weight, const int32_t* covis_offsets, const int32_t* covis_index, const int32_t* covis_weight)
+{
+    for (size_t j = 0; j < list.size(); ++j) {
+        if (n_counted[j] == 0) continue;
+        KeyFrameT* pKF = list[j];
+        std::map<KeyFrameT*, int> KFcounter;
+        for (int e = conn_offsets[j]; e < conn_offsets[j + 1]; ++e) KFcounter[G.key_frame(conn_index[e])] = conn_weight[e];
+        std::vector<std::pair<int32_t, int32_t> > reciprocal;        // (index, weight)
+        std::vector<KeyFrameT*> vpOrdered;
+        std::vector<int> vOrderedWeights;
+        for (int e = covis_offsets[j]; e < covis_offsets[j + 1]; ++e) {
+            reciprocal.push_back(std::make_pair(covis_index[e], covis_weight[e]));
+            vpOrdered.push_back(G.key_frame(covis_index[e]));
+            vOrderedWeights.push_back(covis_weight[e]);
+        }
+        std::sort(reciprocal.begin(), reciprocal.end());
+        for (size_t i = 0; i < reciprocal.size(); ++i) G.key_frame(reciprocal[i].first)->AddConnection(pKF, reciprocal[i].second);
+        pKF->SetConnections(KFcounter, vpOrdered, vOrderedWeights);
+    }
+}
+
+// UpdateConnections for every key frame of `list`, each against the snapshot G as it stands, through the host form: the call (a first one sizes the two
+// lists), then ApplyConnections.  Every listed key frame must be one of the snapshot's.
+template <class KeyFrameT, class MapPointT, class MapLineT>
+void UpdateConnections(const MapGraphOf<KeyFrameT, MapPointT, MapLineT>& G, const std::vector<KeyFrameT*>& list, int th = OLF_COVIS_TH)
+{
+    olf_ctx* c = olf_detail::thread_ctx();
+    const int n = (int)list.size();
+    std::vector<int32_t> idx(n + 1), n_counted(n + 1), kf_max(n + 1), w_max(n + 1), conn_off(n + 1, 0), covis_off(n + 1, 0), conn(1), conn_w(1), covis(1), covis_w(1);
+    for (int j = 0; j < n; ++j) {
+        idx[j] = G.index_of(list[j]);
+        if (idx[j] < 0) throw std::invalid_argument("UpdateConnections: a listed key frame is not in the snapshot");
+    }
+    const olf_map_graph& g = G.graph();
+    int rc = olf_update_connections(c, &g, n, idx.data(), th, n_counted.data(), kf_max.data(), w_max.data(), conn_off.data(), conn.data(), conn_w.data(), 0, covis_off.data(),
+                                    covis.data(), covis_w.data(), 0);
+    if (rc == OLF_ERR_CAPACITY && conn_off[n] > 0) {                  // (the offsets are complete whatever the capacities)
+        conn.resize(conn_off[n]); conn_w.resize(conn_off[n]); covis.resize(covis_off[n]); covis_w.resize(covis_off[n]);
+        rc = olf_update_connections(c, &g, n, idx.data(), th, n_counted.data(), kf_max.data(), w_max.data(), conn_off.data(), conn.data(), conn_w.data(), conn_off[n],
+                                    covis_off.data(), covis.data(), covis_w.data(), covis_off[n]);
+    }
+    olf_detail::check(rc, "olf_update_connections");
+    ApplyConnections(G, list, n_counted.data(), conn_off.data(), conn.data(), conn_w.data(), covis_off.data(), covis.data(), covis_w.data());
 }
 
 }  // namespace ORB_SLAM2

@@ -281,6 +281,9 @@ def lib():
         L.olf_bow_score.argtypes = [P, P, P, C.c_int, P, P, C.c_int, C.POINTER(C.c_double)]
         L.olf_update_local_map_batch_dev.argtypes = ([P, C.POINTER(MapGraphC), C.c_int, C.c_int] + [P] * 8 + [P, P, C.c_int] * 3 + [P])
         L.olf_update_local_map.argtypes = ([P, C.POINTER(MapGraphC), C.c_int, C.c_int] + [P] * 8 + [P, P, C.c_int] * 3)
+        L.olf_update_connections_batch_dev.argtypes = ([P, C.POINTER(MapGraphC), C.c_int, P, C.c_int] + [P] * 3 + [P, P, P, C.c_int] * 2 + [P])
+        L.olf_update_connections.argtypes = ([P, C.POINTER(MapGraphC), C.c_int, P, C.c_int] + [P] * 3 + [P, P, P, C.c_int] * 2)
+        L.olf_best_covisibles_batch_dev.argtypes = [P, C.c_int] + [P] * 6
         L.olf_profile_enable.argtypes = [C.c_void_p, C.c_int]
         L.olf_profile_reset.argtypes = [C.c_void_p]
         L.olf_profile_stage_name.restype = C.c_char_p

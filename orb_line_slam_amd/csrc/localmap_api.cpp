@@ -6,19 +6,6 @@
 
 using namespace olf;
 
-namespace {
-
-// offsets [n + 1] non-decreasing from 0 (and an index array where there are entries); *total = offsets[n]
-bool csr_ok(const int32_t* offs, const int32_t* index, int n, size_t* total)
-{
-    if (!offs || offs[0] != 0) return false;
-    for (int k = 0; k < n; ++k) if (offs[k + 1] < offs[k]) return false;
-    *total = (size_t)offs[n];
-    return index || !*total;
-}
-
-}  // namespace
-
 extern "C" int olf_update_local_map(olf_ctx* c, const olf_map_graph* g, int n_frames, int img_stride, const int32_t* counts, const int32_t* lcounts,
                                     const int32_t* frame_mp, const int32_t* frame_ml, int32_t* frame_mp_out, int32_t* frame_ml_out, int32_t* ref_kf,
                                     int32_t* n_voted, int32_t* kf_offsets, int32_t* kf_index, int kf_capacity, int32_t* mp_offsets, int32_t* mp_index,

@@ -14,6 +14,7 @@
 // LM_BITS_WORDS words; beyond that they live in scratch, where the counting pass sets the bits and the filling pass clears them again.
 #include <algorithm>
 #include "batch_frames.hpp"
+#include "offset_scan.hpp"
 #include "staging.hpp"
 
 namespace olf {
@@ -38,14 +39,6 @@ struct LocalMapArgs {
     unsigned *seen_mp, *seen_ml;                   // otherwise [n_frames][mpW], [n_frames][mlW] in scratch, zero on entry
     int* kf_list;                                  // [n_frames][n_kf]: mvpLocalKeyFrames between the passes
 };
-
-// row k of a CSR of the graph, inside [0, offs[n]] whatever the offsets hold
-__device__ __forceinline__ void lm_row(const int* __restrict__ offs, int n, int k, int& b, int& e)
-{
-    const int total = max(offs[n], 0);
-    b = min(max(offs[k], 0), total);
-    e = min(max(offs[k + 1], b), total);
-}
 
 // this wave's global writes have reached L2 (the explicit wait: the compiler may leave the fence without one)
 __device__ __forceinline__ void lm_publish()
@@ -319,34 +312,14 @@ __global__ __launch_bounds__(LM_THREADS) void k_localmap_count(LocalMapArgs A, i
     }
 }
 
-// offsets[1 .. n] holds per-frame counts: make them running sums (offsets[0] = 0, saturating at INT_MAX); block x is list x.  A total beyond the list's
-// capacity raises STATUS_LOCALMAP_LIST.
-__global__ __launch_bounds__(1024) void k_localmap_scan(int* __restrict__ kf_offsets, int* __restrict__ mp_offsets, int* __restrict__ ml_offsets, int n,
+// offsets[1 .. n] holds per-frame counts: make them running sums (offset_scan); block x is list x.  A total beyond the list's capacity raises
+// STATUS_LOCALMAP_LIST.
+__global__ __launch_bounds__(OFFSET_SCAN_THREADS) void k_localmap_scan(int* __restrict__ kf_offsets, int* __restrict__ mp_offsets, int* __restrict__ ml_offsets, int n,
                                                         int kf_capacity, int mp_capacity, int ml_capacity, int* __restrict__ status)
 {
-    __shared__ long long s_wave[16];
-    __shared__ long long s_carry;
     int* offs = blockIdx.x == 0 ? kf_offsets : blockIdx.x == 1 ? mp_offsets : ml_offsets;
     const int capacity = blockIdx.x == 0 ? kf_capacity : blockIdx.x == 1 ? mp_capacity : ml_capacity;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (tid == 0) { s_carry = 0; offs[0] = 0; }
-    __syncthreads();
-    for (int b = 0; b < n; b += 1024) {
-        const int i = b + tid;
-        long long v = i < n ? offs[i + 1] : 0;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const long long t = __shfl_up(v, d, 64); if (lane >= d) v += t; }
-        if (lane == 63) s_wave[w] = v;
-        __syncthreads();
-        long long pre = s_carry;
-        for (int k = 0; k < w; ++k) pre += s_wave[k];
-        v += pre;
-        if (i < n) offs[i + 1] = (int)(v < 0x7fffffffLL ? v : 0x7fffffffLL);
-        __syncthreads();
-        if (tid == 1023) s_carry = v;
-        __syncthreads();
-    }
-    if (tid == 0 && s_carry > (long long)capacity) atomicOr(status, STATUS_LOCALMAP_LIST);
+    offset_scan(offs, n, capacity, status, STATUS_LOCALMAP_LIST);
 }
 
 __global__ __launch_bounds__(LM_THREADS) void k_localmap_fill(LocalMapArgs A, int* __restrict__ status)
@@ -411,7 +384,7 @@ int olf_update_local_map_batch_dev(olf_ctx* c, const olf_map_graph* g, int n_fra
     // (the two bitmaps are the slab's first two regions: one memset, the padding between them included)
     if (nb) OLF_HIP_CHECK(hipMemsetAsync(A.seen_mp, 0, (size_t)(reinterpret_cast<char*>(A.kf_list) - reinterpret_cast<char*>(A.seen_mp)), s));
     hipLaunchKernelGGL(k_localmap_count, dim3(n_frames), dim3(LM_THREADS), 0, s, A, ctx_status(c));
-    hipLaunchKernelGGL(k_localmap_scan, dim3(3), dim3(1024), 0, s, d_kf_offsets, d_mp_offsets, d_ml_offsets, n_frames, kf_capacity, mp_capacity, ml_capacity, ctx_status(c));
+    hipLaunchKernelGGL(k_localmap_scan, dim3(3), dim3(OFFSET_SCAN_THREADS), 0, s, d_kf_offsets, d_mp_offsets, d_ml_offsets, n_frames, kf_capacity, mp_capacity, ml_capacity, ctx_status(c));
     hipLaunchKernelGGL(k_localmap_fill, dim3(n_frames), dim3(LM_THREADS), 0, s, A, ctx_status(c));
     OLF_HIP_CHECK(hipGetLastError());
     return OLF_OK;

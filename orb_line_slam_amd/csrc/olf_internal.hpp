@@ -45,11 +45,11 @@ void set_error(const std::string& s);
 // entry enqueued has run, so two entries may share a slot only when their work is ordered: on one stream, or with a synchronise between them.
 //   SCRATCH_KNN    olf_match_bf_dev: the k-NN tables of launch_match_bf.
 //   SCRATCH_STAGE  the descriptor-sized host-pointer entries (api_host.cpp: olf_match_bf, olf_knn2, olf_match_candidates, olf_frame_grid,
-//                  olf_features_in_area, olf_hamming_matrix, olf_distinctive_descriptors; localmap_api.cpp: olf_update_local_map) and the olf_debug_*_sweep counters.  Every one of them ends in
+//                  olf_features_in_area, olf_hamming_matrix, olf_distinctive_descriptors; localmap_api.cpp: olf_update_local_map; connections_api.cpp: olf_update_connections) and the olf_debug_*_sweep counters.  Every one of them ends in
 //                  a synchronise on the context's stream.
 //   SCRATCH_BATCH  the batched matchers (olf_search_by_bow_batch_dev, olf_search_by_projection_batch_dev, olf_is_in_frustum_batch_dev,
 //                  olf_search_local_map_batch_dev, olf_search_for_triangulation_batch_dev, olf_fuse_search_batch_dev, olf_search_by_sim3_pairs_dev,
-//                  olf_search_by_projection_kf_pairs_dev, olf_search_by_projection_sim3_batch_dev, olf_update_local_map_batch_dev
+//                  olf_search_by_projection_kf_pairs_dev, olf_search_by_projection_sim3_batch_dev, olf_update_local_map_batch_dev, olf_update_connections_batch_dev
 //                  and the line entries of line_batch.hip) and the image-sized host-pointer entries (olf_cvt_gray, olf_remap_linear,
 //                  olf_init_undistort_rectify_map, olf_bow_transform).  The matchers do not synchronise: the caller keeps them on one stream.
 //   SCRATCH_PACK   olf_frames_pack_dev: the record's row offsets.
@@ -71,7 +71,8 @@ int ctx_level_thresholds(olf_ctx* c, float* thr);      // the table of olf_predi
 
 // The bits of the context's status word (ctx_status) that the batched matchers set, as every entry means them; include/orbline.h says per entry what was
 // left out.  What a bit means is its row of kStatusText, which is also what check_status (api.cpp) tells the caller about a set bit.
-enum StatusBit : int { STATUS_OCTAVE = 256, STATUS_POINT_INDEX = 512, STATUS_LINE_INDEX = 1024, STATUS_PAIR = 2048, STATUS_KF_INDEX = 4096, STATUS_LOCALMAP_LIST = 8192 };
+enum StatusBit : int { STATUS_OCTAVE = 256, STATUS_POINT_INDEX = 512, STATUS_LINE_INDEX = 1024, STATUS_PAIR = 2048, STATUS_KF_INDEX = 4096, STATUS_LOCALMAP_LIST = 8192,
+                       STATUS_CONNECTIONS_LIST = 16384 };
 struct StatusText { int bit; const char* text; };
 constexpr StatusText kStatusText[] = {
     {1, "ORB corner buffer"},
@@ -88,6 +89,7 @@ constexpr StatusText kStatusText[] = {
     {STATUS_PAIR, "a pair entry skipped a pair whose frame indices are outside the batch or equal"},
     {STATUS_KF_INDEX, "a map-graph entry left out a key-frame index outside the graph"},
     {STATUS_LOCALMAP_LIST, "local key-frame, map-point or map-line list of olf_update_local_map_batch_dev"},
+    {STATUS_CONNECTIONS_LIST, "connected or ordered key-frame list of olf_update_connections_batch_dev, or a row of olf_best_covisibles_batch_dev"},
 };
 
 #ifdef __HIPCC__

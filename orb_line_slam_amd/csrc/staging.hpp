@@ -25,6 +25,16 @@ struct Carve : CarveLayout {
     }
 };
 
+// what a host-pointer entry checks of a CSR pair of its caller's: offsets [n + 1] non-decreasing from 0 (and an index array where there are entries);
+// *total = offsets[n]
+inline bool csr_ok(const int32_t* offs, const int32_t* index, int n, size_t* total)
+{
+    if (!offs || offs[0] != 0) return false;
+    for (int k = 0; k < n; ++k) if (offs[k + 1] < offs[k]) return false;
+    *total = (size_t)offs[n];
+    return index || !*total;
+}
+
 class HostCall : public Carve {
 public:
     HostCall(olf_ctx* c, const char* who) : c_(c), s_(ctx_stream(c)), device_rc_(ctx_check_device(c, who)) {}
