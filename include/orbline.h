@@ -914,6 +914,94 @@ int olf_update_connections(olf_ctx* ctx, const olf_map_graph* g, int n_list, con
 int olf_best_covisibles_batch_dev(olf_ctx* ctx, int n_rows, const int32_t* d_conn_offsets, const int32_t* d_conn_index, const int32_t* d_conn_weight,
                                   int32_t* d_covis_index, int32_t* d_covis_weight, void* stream);
 
+/* ---- LocalMapping::KeyFrameCulling, MapPointCulling and KeyFrame::TrackedMapPoints / TrackedMapLines (csrc/culling_batch.hip, culling_host.cpp) ---------
+ * void LocalMapping::KeyFrameCulling() (src/LocalMapping.cc:632-696; called at :84) for a list of key frames -- GetVectorCovisibleKeyFrames() of the
+ * current key frame, in its order -- against one snapshot of the map: an olf_map_graph and, beside it, an olf_cull_view (orbline_types.h).  It is not a
+ * pure function of the snapshot: a culled key frame erases its observations (KeyFrame::SetBadFlag, src/KeyFrame.cc:647-649; MapPoint::EraseObservation,
+ * src/MapPoint.cc:123-149), a point left with nObs <= 2 goes bad, and so a later key frame of the list can lose redundancy (its points have fewer
+ * observers) or gain it (a point of its own that was not redundant went bad and nMPs fell).  As with the key-frame database, the data-parallel tables are
+ * computed on the device (olf_keyframe_culling_tables_dev: every listed key frame against the map as it stands), the sequential rest is host code
+ * (olf_keyframe_culling_replay) and a third entry runs both (olf_keyframe_culling).  The result is the reference's, decision for decision, in list order.
+ * Integers only, apart from nRedundantObservations > 0.9 * nMPs (:693, one fp64 multiply, not contracted): exact equality, and no result depends on an
+ * iteration order (the break at :680-681 only caps a count), so convention C.16 is not needed.
+ *
+ * olf_keyframe_culling_tables_dev.  Device pointers in g and v.  d_kf_list [n_list], or NULL for the key frames 0 .. n_list - 1; a key frame may be listed
+ * twice.  monocular: mbMonocular.  Counting, :651-691:
+ *   a slot COUNTS (nMPs++) when its point is not NULL (negative), not bad (mp_bad) and, unless monocular, not (depth > kf_th_depth || depth < 0) -- the
+ *     comparisons as written, so a NaN depth counts;
+ *   a counted slot is REDUNDANT when mp_nobs > 3 and at least 3 observations of its point qualify;
+ *   an observation QUALIFIES when its key frame is not the listed one (index equality) and kf_slot_octave[kf_mp_offsets[kf_i] + slot_i] <= octave of this
+ *     slot + 1: the observer's octave at the observation's slot (mp_obs_slot), the own octave at the slot that holds the point.  isBad() of an observer is
+ *     not looked at; kf_bad, kf_mode and kf_slot_stereo are not read.
+ * Outputs per listed key frame j: d_n_mps, d_n_redundant [n_list] (int32), d_redundant [n_list] (uint8) = (double)nRed > 0.9 * (double)nMPs.
+ * Outputs per slot of the listed rows: d_row_offsets [n_list + 1], written here, the running sum of the listed rows' lengths (always complete); for slot i
+ * of listed key frame j at d_row_offsets[j] + i: d_slot_count (int32), the UNCAPPED number of qualifying observations, also where mp_nobs <= 3 (the replay
+ * needs it), and d_slot_flags (uint8), bit 0 counted, bit 1 redundant.  Every slot of a listed row is written; a slot that does not count gets 0 and 0.
+ * The caller sizes the two slot arrays by the sum of the listed rows from its host copy of kf_mp_offsets and passes slot_capacity.  The list is a device
+ * array, so a shortfall is found on the device: nothing is written at or past slot_capacity and bit 16384 of the context's status word is raised
+ * (olf_ctx_synchronize / olf_ctx_poll_status); the per-key-frame outputs are complete all the same.  (olf_keyframe_culling, whose list is a host array,
+ * sizes the arrays itself and cannot fall short.)
+ * Malformed input is left out, never dereferenced: a slot index >= n_mp sets status bit 512; an observing key frame outside [0, n_kf), or an observation
+ * slot outside that key frame's row, bit 4096 (the observation does not qualify); a listed key frame outside [0, n_kf) bit 4096, with zero counts and an
+ * empty row.  An observation by the listed key frame itself is skipped before its slot is looked at.  Rows of a CSR are clamped to [0, offsets[n]].
+ * There is no LDS table per key frame here, so OLF_LOCALMAP_MAX_KF does not apply: any n_kf.  Errors: a NULL required pointer (of g: mp_obs_offsets and
+ * kf_mp_offsets; mp_obs_kf, mp_bad, mp_nobs and mp_obs_slot unless n_mp == 0; kf_mp_index, kf_slot_octave, kf_slot_depth and kf_th_depth unless n_kf == 0 --
+ * an array without entries still needs an address) or a negative size: OLF_ERR_INVALID.
+ * n_list == 0 writes nothing.  Does not synchronise; runs on `stream`; no scratch. */
+int olf_keyframe_culling_tables_dev(olf_ctx* ctx, const olf_map_graph* g, const olf_cull_view* v, int n_list, const int32_t* d_kf_list, int monocular,
+                                    int32_t* d_n_mps, int32_t* d_n_redundant, uint8_t* d_redundant, int32_t* d_row_offsets, int32_t* d_slot_count,
+                                    uint8_t* d_slot_flags, int slot_capacity, void* stream);
+/* The sequential rest, host only (no context): host copies of the graph, the view, the list (NULL: 0 .. n_list - 1) and the tables above.  Walks the list in
+ * order; decision [n_list]:
+ *   0  kept; also a key frame of mode 2 (skipped at :643) and one that was culled earlier in this list -- for these two n_mps / n_redundant are 0;
+ *   1  culled: redundant and kf_mode 0, KeyFrame::SetBadFlag ran through;
+ *   2  redundant but kf_mode 1: mbToBeErased is set, the map does not change (src/KeyFrame.cc:637-641).
+ * n_mps / n_redundant [n_list]: nMPs and nRedundantObservations as the reference saw them at that moment.  After a decision 1 on key frame A the working
+ * state changes as SetBadFlag changes the map: for every non-NULL slot of A whose point p is not bad and whose observation row names A (at slot s), the
+ * observation is removed (once: a point held in two slots is erased at the first) and nobs[p] falls by 2 if kf_slot_stereo[A][s], else by 1 -- the
+ * observation's slot, not the visiting one.  With nobs[p] <= 2 the point goes bad: every still undecided listed key frame that holds p in a counted slot
+ * loses that slot from nMPs, and from nRed if it was redundant.  Otherwise every such slot loses one from its count if octave[A][s] <= its own octave + 1,
+ * and is redundant again iff nobs > 3 && count >= 3.  The point -> (listed position, slot) index is built once from the listed rows.  That the slot an
+ * observation names holds the observed point (AddObservation comes with AddMapPoint) and that an observation row names a key frame at most once are the
+ * caller's contract: a point that goes bad leaves the counts through the slots that hold it.
+ * Optional outputs (NULL: not wanted): mp_nobs_out, mp_bad_out [n_mp], the final counters and flags; went_bad [n_mp] / n_went_bad, the points that went
+ * bad, in order.  Checks the two CSR pairs it reads and that row_offsets is the running sum of the listed rows' lengths (a listed key frame outside the
+ * graph: an empty row, decision 0): OLF_ERR_INVALID otherwise, as for a NULL required pointer or a negative size.  Malformed indices are left out as above. */
+int olf_keyframe_culling_replay(const olf_map_graph* g, const olf_cull_view* v, int n_list, const int32_t* kf_list, const int32_t* table_n_mps,
+                                const int32_t* table_n_redundant, const int32_t* row_offsets, const int32_t* slot_count, const uint8_t* slot_flags,
+                                int32_t* decision, int32_t* n_mps, int32_t* n_redundant, int32_t* mp_nobs_out, uint8_t* mp_bad_out, int32_t* went_bad,
+                                int32_t* n_went_bad);
+/* host buffers: checks mp_obs_* and kf_mp_* (offsets non-decreasing from 0: OLF_ERR_INVALID), sizes the slot arrays from the listed rows, uploads, runs the
+ * tables on the context's stream, downloads, replays.  table_n_mps, table_n_redundant, table_redundant [n_list]: the tables' per-key-frame outputs, or
+ * NULL.  OLF_ERR_CAPACITY with the message of the bit for a malformed index; the outputs are complete then. */
+int olf_keyframe_culling(olf_ctx* ctx, const olf_map_graph* g, const olf_cull_view* v, int n_list, const int32_t* kf_list, int monocular, int32_t* decision,
+                         int32_t* n_mps, int32_t* n_redundant, int32_t* table_n_mps, int32_t* table_n_redundant, uint8_t* table_redundant,
+                         int32_t* mp_nobs_out, uint8_t* mp_bad_out, int32_t* went_bad, int32_t* n_went_bad);
+/* int KeyFrame::TrackedMapPoints(minObs) and TrackedMapLines(minObs) (src/KeyFrame.cc:328-353, 407-432) for n_list key frames: the slots that are not NULL,
+ * not bad and, with min_obs > 0 (bCheckObs), whose Observations() (d_mp_nobs [n_mp], d_ml_nobs [n_ml]) >= min_obs.  Tracking::NeedNewKeyFrame asks it of
+ * every frame's reference key frame (src/Tracking.cc:1626-1627), which olf_update_local_map_batch_dev leaves on the device: its d_ref_kf is d_kf_list here
+ * as it is.  A listed -1 is "no reference key frame": both counts 0 and no status bit.  Any other index outside [0, n_kf) gives 0 and bit 4096; a slot
+ * index >= n_mp is left out with bit 512, a line index >= n_ml with bit 1024.  d_kf_list NULL: the key frames 0 .. n_list - 1.  A graph without lines
+ * (kf_ml_offsets NULL) gives d_n_lines 0; d_ml_nobs may be NULL then, or when min_obs_lines <= 0; d_mp_nobs may be NULL when min_obs_points <= 0.
+ * OLF_ERR_INVALID for a NULL required pointer or a negative size.  n_list == 0 writes nothing.  Does not synchronise; runs on `stream`; no scratch. */
+int olf_tracked_map_points_batch_dev(olf_ctx* ctx, const olf_map_graph* g, const int32_t* d_mp_nobs, const int32_t* d_ml_nobs, int n_list,
+                                     const int32_t* d_kf_list, int min_obs_points, int min_obs_lines, int32_t* d_n_points, int32_t* d_n_lines, void* stream);
+/* host buffers: checks kf_mp_* and kf_ml_*, uploads, runs, downloads */
+int olf_tracked_map_points(olf_ctx* ctx, const olf_map_graph* g, const int32_t* mp_nobs, const int32_t* ml_nobs, int n_list, const int32_t* kf_list,
+                           int min_obs_points, int min_obs_lines, int32_t* n_points, int32_t* n_lines);
+/* void LocalMapping::MapPointCulling() (src/LocalMapping.cc:170-205; called at :64) as a predicate over the n points of mlpRecentAddedMapPoints, given as
+ * arrays: d_bad (uint8, isBad()), d_found / d_visible (int32, mnFound / mnVisible), d_nobs (int32, Observations()), d_first_kf_id (int64, mnFirstKFid);
+ * current_kf_id = mpCurrentKeyFrame->mnId.  d_action [n] (uint8), the branches of :186-203 in their order:
+ *   1  erase from the list (bad);  2  SetBadFlag and erase: GetFoundRatio() = (float)found / (float)visible < 0.25f (visible == 0 gives NaN or inf and
+ *   falls through, as in the reference);  3  SetBadFlag and erase: (int)current - (int)first >= 2 && nobs <= (monocular ? 2 : 3);  4  erase: that
+ *   difference >= 3;  0  keep.
+ * A NULL pointer with n > 0 or a negative n: OLF_ERR_INVALID.  n == 0 writes nothing.  Does not synchronise; runs on `stream`; no scratch. */
+int olf_map_point_culling_dev(olf_ctx* ctx, int n, const uint8_t* d_bad, const int32_t* d_found, const int32_t* d_visible, const int32_t* d_nobs,
+                              const int64_t* d_first_kf_id, int64_t current_kf_id, int monocular, uint8_t* d_action, void* stream);
+/* host buffers: uploads, runs, downloads */
+int olf_map_point_culling(olf_ctx* ctx, int n, const uint8_t* bad, const int32_t* found, const int32_t* visible, const int32_t* nobs,
+                          const int64_t* first_kf_id, int64_t current_kf_id, int monocular, uint8_t* action);
+
 /* measurement: rate of a plain 16-byte-per-thread device copy kernel over `bytes` (read + written bytes per second): the practical HBM
  * ceiling bench.py reports next to the specification's 8 TB/s */
 int olf_debug_copy_bandwidth(olf_ctx* ctx, size_t bytes, int reps, double* gbytes_per_s);

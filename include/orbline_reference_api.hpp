@@ -12,6 +12,7 @@
 //   FrameGrid(frame)                             = AssignFeaturesToGrid()            src/Frame.cc:215            (:334-349)
 //   KeyFrameDatabaseOf<KeyFrame, Frame>          = KeyFrameDatabase                  include/KeyFrameDatabase.h:60-98 (add, erase, clear, the four Detect members)
 //   MapGraphOf<KeyFrame, MapPoint, MapLine>, UpdateLocalMap(...)  = Tracking::UpdateLocalMap   src/Tracking.cc:2028-2205
+//   KeyFrameCulling<KeyFrame, MapPoint, MapLine>(ctx, mpCurrentKeyFrame, mbMonocular)  = LocalMapping::KeyFrameCulling   src/LocalMapping.cc:632-696
 //   and every other ORBmatcher call of the reference: SearchByProjection(cur, pKF, sFound, th, ORBdist) Tracking.cc:2322,2336;
 //   SearchForTriangulation LocalMapping.cc:268; Fuse(pKF, vpMapPoints[, th]) LocalMapping.cc:489,514; SearchByBoW(pKF1, pKF2, vpMatches12)
 //   LoopClosing.cc:271; SearchBySim3 LoopClosing.cc:329; SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) LoopClosing.cc:381;
@@ -851,6 +852,40 @@ public:
 
     const olf_map_graph& graph() const { return g_; }
     KeyFrameT* key_frame(int k) const { return kfs_[k]; }
+    MapPointT* map_point(int i) const { return mps_[i]; }
+
+    // What LocalMapping::KeyFrameCulling reads beyond the graph (olf_cull_view, orbline_types.h), beside graph() and parallel to its arrays; filled at the first
+    // call, through what KeyFrameCulling itself reads -- mvKeysUn[i].octave, mvDepth[i], mThDepth, mnId, MapPoint::Observations() and the size_t of
+    // GetObservations() -- mvuRight[i] as MapPoint::EraseObservation reads it, and mbNotErase, which is protected (include/KeyFrame.h:268): the integrator adds
+    //     bool KeyFrame::GetNotErase() { unique_lock<mutex> lock(mMutexConnections); return mbNotErase; }
+    // Only a caller of cull_view() needs these members of its types.  Host pointers, owned by the object.
+    const olf_cull_view& cull_view()
+    {
+        if (view_filled_) return v_;
+        for (size_t k = 0; k < kfs_.size(); ++k) {
+            KeyFrameT* pKF = kfs_[k];
+            const int n = kf_mp_off_[k + 1] - kf_mp_off_[k];
+            for (int i = 0; i < n; ++i) {
+                const int octave = i < (int)pKF->mvKeysUn.size() ? pKF->mvKeysUn[i].octave : 0;
+                slot_octave_.push_back((uint8_t)std::min(std::max(octave, 0), 255));
+                slot_depth_.push_back(i < (int)pKF->mvDepth.size() ? pKF->mvDepth[i] : -1.0f);
+                slot_stereo_.push_back(i < (int)pKF->mvuRight.size() && pKF->mvuRight[i] >= 0 ? 1 : 0);
+            }
+            th_depth_.push_back(pKF->mThDepth);
+            kf_mode_.push_back(pKF->mnId == 0 ? 2 : pKF->GetNotErase() ? 1 : 0);
+        }
+        for (size_t i = 0; i < mps_.size(); ++i) {
+            mp_nobs_.push_back(mps_[i]->Observations());
+            const std::map<KeyFrameT*, size_t> observations = mps_[i]->GetObservations();      // (the same keys in the same order as in the constructor)
+            for (typename std::map<KeyFrameT*, size_t>::const_iterator it = observations.begin(); it != observations.end(); ++it) if (index_of(it->first) >= 0) obs_slot_.push_back((int32_t)it->second);
+            obs_slot_.resize(mp_obs_off_[i + 1], -1);               // (a map that changed in between: the lengths stay the graph's)
+        }
+        obs_slot_.reserve(1); mp_nobs_.reserve(1); slot_octave_.reserve(1); slot_depth_.reserve(1); slot_stereo_.reserve(1); th_depth_.reserve(1); kf_mode_.reserve(1);
+        v_.mp_obs_slot = obs_slot_.data(); v_.mp_nobs = mp_nobs_.data(); v_.kf_slot_octave = slot_octave_.data(); v_.kf_slot_depth = slot_depth_.data();
+        v_.kf_slot_stereo = slot_stereo_.data(); v_.kf_th_depth = th_depth_.data(); v_.kf_mode = kf_mode_.data();
+        view_filled_ = true;
+        return v_;
+    }
     int index_of(KeyFrameT* p) const { return lookup(kf_index_, p); }
     int index_of(MapPointT* p) const { return lookup(mp_index_, p); }
     int line_index_of(MapLineT* p) const { return lookup(ml_index_, p); }
@@ -902,6 +937,11 @@ private:
     std::vector<int32_t> mp_obs_off_, mp_obs_, kf_mp_off_, kf_mp_, kf_ml_off_, kf_ml_, covis_off_, covis_, child_off_, child_, parent_;
     std::vector<uint8_t> mp_bad_, ml_bad_, kf_bad_;
     olf_map_graph g_;
+    std::vector<int32_t> obs_slot_, mp_nobs_;
+    std::vector<uint8_t> slot_octave_, slot_stereo_, kf_mode_;
+    std::vector<float> slot_depth_, th_depth_;
+    olf_cull_view v_;
+    bool view_filled_ = false;
 };
 
 // UpdateLocalMap for one frame through the host form, as Tracking::UpdateLocalMap is called (:2028): the snapshot, the call, the write-back.  Tracking's
@@ -983,6 +1023,56 @@ void UpdateConnections(const MapGraphOf<KeyFrameT, MapPointT, MapLineT>& G, cons
     }
     olf_detail::check(rc, "olf_update_connections");
     ApplyConnections(G, list, n_counted.data(), conn_off.data(), conn.data(), conn_w.data(), covis_off.data(), covis.data(), covis_w.data());
+}
+
+// ---- LocalMapping::KeyFrameCulling (src/LocalMapping.cc:632-696) over the reference's own types ---------------------------------------------------------
+// The snapshot KeyFrameCulling needs: the listed key frames first, in their order, then every other key frame that observes a point one of them holds (the
+// observer's octave is read, :675).  No order among key frames matters to the result.
+template <class KeyFrameT, class MapPointT>
+std::vector<KeyFrameT*> CullingSnapshot(const std::vector<KeyFrameT*>& list)
+{
+    std::vector<KeyFrameT*> kfs;
+    std::set<KeyFrameT*> seen;
+    for (size_t j = 0; j < list.size(); ++j) if (seen.insert(list[j]).second) kfs.push_back(list[j]);
+    const size_t n_listed = kfs.size();
+    for (size_t j = 0; j < n_listed; ++j) {
+        const std::vector<MapPointT*> vpMapPoints = kfs[j]->GetMapPointMatches();
+        for (size_t i = 0; i < vpMapPoints.size(); ++i) {
+            if (!vpMapPoints[i] || vpMapPoints[i]->isBad()) continue;
+            const std::map<KeyFrameT*, size_t> observations = vpMapPoints[i]->GetObservations();
+            for (typename std::map<KeyFrameT*, size_t>::const_iterator it = observations.begin(); it != observations.end(); ++it) if (seen.insert(it->first).second) kfs.push_back(it->first);
+        }
+    }
+    return kfs;
+}
+
+// What the reference does to the objects, from decision [list.size()] of olf_keyframe_culling*: SetBadFlag() on the key frames whose decision is not 0, in
+// list order.  SetBadFlag itself sorts out mbNotErase (decision 2: it sets mbToBeErased and returns, src/KeyFrame.cc:637-641), erases the observations,
+// lets the points with nObs <= 2 go bad and repairs the spanning tree.
+template <class KeyFrameT>
+void ApplyKeyFrameCulling(const std::vector<KeyFrameT*>& list, const int32_t* decision)
+{
+    for (size_t j = 0; j < list.size(); ++j) if (decision[j] != 0) list[j]->SetBadFlag();
+}
+
+// KeyFrameCulling as LocalMapping calls it (:84): GetVectorCovisibleKeyFrames() of the current key frame, the snapshot, the host form on context c (NULL:
+// the thread's matcher context), then ApplyKeyFrameCulling.  Returns the decisions in list order.
+template <class KeyFrameT, class MapPointT, class MapLineT>
+std::vector<int32_t> KeyFrameCulling(olf_ctx* c, KeyFrameT* pCurrentKF, bool bMonocular)
+{
+    const std::vector<KeyFrameT*> vpLocalKeyFrames = pCurrentKF->GetVectorCovisibleKeyFrames();
+    const int n = (int)vpLocalKeyFrames.size();
+    std::vector<int32_t> decision(n + 1, 0), n_mps(n + 1), n_red(n + 1), idx(n + 1);
+    if (n == 0) { decision.resize(0); return decision; }
+    MapGraphOf<KeyFrameT, MapPointT, MapLineT> G(CullingSnapshot<KeyFrameT, MapPointT>(vpLocalKeyFrames));
+    for (int j = 0; j < n; ++j) idx[j] = G.index_of(vpLocalKeyFrames[j]);
+    const olf_map_graph& g = G.graph();
+    const olf_cull_view& v = G.cull_view();
+    olf_detail::check(olf_keyframe_culling(c ? c : olf_detail::thread_ctx(), &g, &v, n, idx.data(), bMonocular ? 1 : 0, decision.data(), n_mps.data(), n_red.data(), nullptr,
+                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "olf_keyframe_culling");
+    decision.resize(n);
+    ApplyKeyFrameCulling(vpLocalKeyFrames, decision.data());
+    return decision;
 }
 
 }  // namespace ORB_SLAM2

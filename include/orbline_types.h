@@ -83,6 +83,21 @@ typedef struct olf_map_graph {
     const int32_t* kf_parent;         /* [n_kf]      KeyFrame::GetParent(), -1 = none                                              */
 } olf_map_graph;
 
+/* What LocalMapping::KeyFrameCulling (src/LocalMapping.cc:632-696) reads beyond an olf_map_graph, passed beside it (olf_keyframe_culling*, include/orbline.h):
+ * the observer's feature index of every observation, the observation counter of every point and the key point, depth and mode of every slot's key frame.
+ * The observation row of a bad point is never read: MapPoint::SetBadFlag cleared it (src/MapPoint.cc:171), so what mp_obs_kf / mp_obs_slot hold there is
+ * irrelevant. */
+typedef struct olf_cull_view {
+    const int32_t* mp_obs_slot;       /* parallel to mp_obs_kf: the size_t of mObservations, the observer's feature index          */
+    const int32_t* mp_nobs;           /* [n_mp]      MapPoint::Observations(): +2 per stereo observation (src/MapPoint.cc:117-120),  */
+                                      /*             so it is not the length of the observation row                                */
+    const uint8_t* kf_slot_octave;    /* parallel to kf_mp_index: mvKeysUn[i].octave                                               */
+    const float*   kf_slot_depth;     /* parallel to kf_mp_index: mvDepth[i]                                                       */
+    const uint8_t* kf_slot_stereo;    /* parallel to kf_mp_index: mvuRight[i] >= 0; read by olf_keyframe_culling_replay only       */
+    const float*   kf_th_depth;       /* [n_kf]      mThDepth                                                                      */
+    const uint8_t* kf_mode;           /* [n_kf]      0 normal, 1 mbNotErase, 2 mnId == 0; read by olf_keyframe_culling_replay only */
+} olf_cull_view;
+
 /* ORBextractor ctor arguments, src/ORBextractor.cc:412-416; values from
  * Examples/PL/PL_KITTI00-02.yaml:42-55 are the defaults of olf_default_params(). */
 typedef struct olf_orb_params {

@@ -98,6 +98,11 @@ class MapGraphC(C.Structure):
                                            "kf_covis_offsets", "kf_covis_index", "kf_child_offsets", "kf_child_index", "kf_parent")])
 
 
+class CullViewC(C.Structure):
+    """olf_cull_view (include/orbline_types.h): what KeyFrameCulling reads beyond an olf_map_graph"""
+    _fields_ = [(n, C.c_void_p) for n in ("mp_obs_slot", "mp_nobs", "kf_slot_octave", "kf_slot_depth", "kf_slot_stereo", "kf_th_depth", "kf_mode")]
+
+
 class BowCsrC(C.Structure):
     """olf_bow_csr (include/orbline.h): n BoW vectors as offsets, ascending word ids and values"""
     _fields_ = [(n, C.c_void_p) for n in ("off", "ids", "vals")]
@@ -284,6 +289,13 @@ def lib():
         L.olf_update_connections_batch_dev.argtypes = ([P, C.POINTER(MapGraphC), C.c_int, P, C.c_int] + [P] * 3 + [P, P, P, C.c_int] * 2 + [P])
         L.olf_update_connections.argtypes = ([P, C.POINTER(MapGraphC), C.c_int, P, C.c_int] + [P] * 3 + [P, P, P, C.c_int] * 2)
         L.olf_best_covisibles_batch_dev.argtypes = [P, C.c_int] + [P] * 6
+        L.olf_keyframe_culling_tables_dev.argtypes = [P, C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int, P, C.c_int] + [P] * 6 + [C.c_int, P]
+        L.olf_keyframe_culling_replay.argtypes = [C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int] + [P] * 13
+        L.olf_keyframe_culling.argtypes = [P, C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int, P, C.c_int] + [P] * 10
+        L.olf_tracked_map_points_batch_dev.argtypes = [P, C.POINTER(MapGraphC), P, P, C.c_int, P, C.c_int, C.c_int, P, P, P]
+        L.olf_tracked_map_points.argtypes = [P, C.POINTER(MapGraphC), P, P, C.c_int, P, C.c_int, C.c_int, P, P]
+        L.olf_map_point_culling_dev.argtypes = [P, C.c_int] + [P] * 5 + [C.c_int64, C.c_int, P, P]
+        L.olf_map_point_culling.argtypes = [P, C.c_int] + [P] * 5 + [C.c_int64, C.c_int, P]
         L.olf_profile_enable.argtypes = [C.c_void_p, C.c_int]
         L.olf_profile_reset.argtypes = [C.c_void_p]
         L.olf_profile_stage_name.restype = C.c_char_p

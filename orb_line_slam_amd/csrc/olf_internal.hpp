@@ -45,7 +45,8 @@ void set_error(const std::string& s);
 // entry enqueued has run, so two entries may share a slot only when their work is ordered: on one stream, or with a synchronise between them.
 //   SCRATCH_KNN    olf_match_bf_dev: the k-NN tables of launch_match_bf.
 //   SCRATCH_STAGE  the descriptor-sized host-pointer entries (api_host.cpp: olf_match_bf, olf_knn2, olf_match_candidates, olf_frame_grid,
-//                  olf_features_in_area, olf_hamming_matrix, olf_distinctive_descriptors; localmap_api.cpp: olf_update_local_map; connections_api.cpp: olf_update_connections) and the olf_debug_*_sweep counters.  Every one of them ends in
+//                  olf_features_in_area, olf_hamming_matrix, olf_distinctive_descriptors; localmap_api.cpp: olf_update_local_map; connections_api.cpp: olf_update_connections; culling_api.cpp: olf_keyframe_culling,
+//                  olf_tracked_map_points, olf_map_point_culling) and the olf_debug_*_sweep counters.  Every one of them ends in
 //                  a synchronise on the context's stream.
 //   SCRATCH_BATCH  the batched matchers (olf_search_by_bow_batch_dev, olf_search_by_projection_batch_dev, olf_is_in_frustum_batch_dev,
 //                  olf_search_local_map_batch_dev, olf_search_for_triangulation_batch_dev, olf_fuse_search_batch_dev, olf_search_by_sim3_pairs_dev,
