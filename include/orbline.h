@@ -1077,6 +1077,116 @@ int olf_bow_score_pairs_dev(olf_kfdb* db, int line, int n_pairs, const int32_t* 
 /* TemplatedVocabulary::score (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1199-1203) with L1 scoring for two host vectors, on the device */
 int olf_bow_score(olf_ctx* ctx, const int32_t* ids_a, const double* vals_a, int n_a, const int32_t* ids_b, const double* vals_b, int n_b, double* score);
 
+/* ---- Optimizer::PoseOptimizationWithLine for a batch of frames on the device (csrc/pose_batch.hip, pose_host.cpp, pose_terms.hpp) -----------------------
+ * bool Optimizer::PoseOptimizationWithLine(Frame*) (src/Optimizer.cc:604-777): the branch that executes (`if(true)`, :664-697), i.e. the point-and-line
+ * Gauss-Newton solver of StVO-PL -- gaussNewtonOptimization twice, gaussNewtonOptimizationRobust, gaussNewtonOptimization, each from the same prior DT and
+ * each followed by removeOutliers -- and its epilogue; the call of Tracking::TrackReferenceKeyFrameWithLine (src/Tracking.cc:1032),
+ * TrackWithMotionModelWithLine (:1470) and TrackLocalMap (:1544).  Optimizer::PoseOptimization (g2o, points only) has no entry.  Doubles throughout, as the
+ * reference; the arithmetic of every term is csrc/pose_terms.hpp, the same text for the host form and the kernel.  Defaults: src/Config.cpp:42-82. */
+typedef struct olf_pose_params {
+    int32_t max_iters_ref;       /* Config::maxItersRef()       10   (>= 1)                                          */
+    double  homog_th;            /* Config::homogTh()           1e-7 (> 0)                                           */
+    double  min_error;           /* Config::minError()          1e-7                                                 */
+    double  min_error_change;    /* Config::minErrorChange()    1e-7                                                 */
+    double  inlier_k;            /* Config::inlierK()           4.0                                                  */
+    int32_t use_motion_model;    /* Config::useMotionModel()    1: DT = Tcw * inverse(Tcw_prev); 0: the identity     */
+    int32_t has_points;          /* Config::hasPoints()         1; as in the reference it gates removeOutliers only: */
+                                 /* with 0 the points still enter the sums, and their outlier flags on entry stay in  */
+                                 /* force through all four passes (none is set, none is cleared); has_lines likewise  */
+    int32_t has_lines;           /* Config::hasLines()          1                                                    */
+} olf_pose_params;
+void olf_pose_default_params(olf_pose_params* p);
+/* The frames of a batch as the optimiser reads them.  Device pointers; frame j = image j * img_stride of the extractor-layout arrays kps / counts / kls /
+ * lcounts (as olf_track_batch and olf_line_batch); every other plane is per frame, [n_frames][olf_orb_capacity()] or [n_frames][olf_line_capacity()].
+ * A count beyond the capacity is read as the capacity.  mvInvLevelSigma2 is the context's; a line reads it by its key line's octave. */
+typedef struct olf_pose_batch {
+    const olf_keypoint* kps; const int32_t* counts;       /* mvKeysUn, N                                                                           */
+    const olf_keyline* kls; const int32_t* lcounts;       /* mvKeysUn_Line, N_l                                                                    */
+    int32_t img_stride;
+    const double*  lle;               /* [n_frames][line capacity][3] mvle_l (olf_frame_buffers.lle)                                               */
+    const float*   Tcw;               /* [n_frames][16] mTcw, row-major: the prior                                                                 */
+    const float*   Tcw_prev;          /* [n_frames][16] mTcw_prev; NULL: empty, i.e. Tcw (:613-614)                                                */
+    const double*  DT_cov_in;         /* [n_frames][36] pFrame->DT_cov on entry; NULL: zeros.  It is what DT_cov stays when a pass returns early (:790-795), */
+                                      /* also with use_motion_model = 0, where the reference never loads it and leaves DT_cov uninitialised         */
+    float fx, fy, cx, cy;
+    const int32_t* frame_mp;          /* [n_frames][capacity] mvpMapPoints as indices into mp_world, negative = NULL                               */
+    const int32_t* mp_index_offset;   /* [n_frames] added to every non-negative entry of the frame, or NULL.  The frame-to-frame searches return    */
+                                      /* indices into the LAST frame's features: with mp_world = olf_track_batch.mp_world viewed flat and offset  */
+                                      /* j * capacity for the pair's last frame j their output goes in as it is; map indices pass NULL             */
+    const float*   mp_world;          /* [n_mp][3] GetWorldPos()                                                                                   */
+    int32_t        n_mp;
+    const int32_t* frame_ml;          /* [n_frames][line capacity], ml_index_offset [n_frames] or NULL, ml_world [n_ml][6] (olf_local_line_map.world). */
+                                      /* olf_track_lines_batch_dev is NOT like the point search: its d_cur_ml holds the ids the caller gave the last */
+                                      /* frame's lines (d_last_ml), not indices into the last frame.  With map indices as those ids d_cur_ml goes in  */
+                                      /* as it is with ml_index_offset NULL; so does the output of olf_search_local_lines_batch_dev                  */
+    const int32_t* ml_index_offset;
+    const float*   ml_world;
+    int32_t        n_ml;
+    const uint8_t* outlier;           /* [n_frames][capacity] mvbOutlier on entry; NULL: none                                                      */
+    const uint8_t* outlier_l;         /* [n_frames][line capacity] mvbOutlier_Line on entry; NULL: none                                            */
+} olf_pose_batch;
+/* What a call writes per frame.  Every pointer is required. */
+typedef struct olf_pose_outputs {
+    float*   Tcw_out;         /* [16]  the pose SetPose receives (:688-689)                                                                        */
+    double*  DT;              /* [16]  pFrame->DT (:684)                                                                                            */
+    double*  DT_cov;          /* [36]  pFrame->DT_cov                                                                                               */
+    double*  DT_cov_eig;      /* [6]   pFrame->DT_cov_eig, ascending                                                                                */
+    double*  err_norm;        /*       pFrame->err_norm                                                                                             */
+    uint8_t* good;            /*       isGoodSolution(DT, DT_cov, err) (:453-466, :683), which the reference computes and ignores                   */
+    uint8_t* outlier_out;     /* [capacity]      mvbOutlier at the end, 0 from the count on and for a feature that holds nothing; may be `outlier`  */
+    uint8_t* outlier_l_out;   /* [line capacity] mvbOutlier_Line likewise; may be `outlier_l`                                                       */
+    int32_t* n_inliers;       /* [2]   held and not outlier: points, lines (n_inliers_pt, n_inliers_ls)                                             */
+    int32_t* iters;           /* [4]   evaluations of each pass, for diagnosis                                                                      */
+    int32_t* status;          /*       the frame's own status word: 1, 2, 4 below                                                                   */
+} olf_pose_outputs;
+/* One launch for the whole batch: one workgroup per frame carries it through the four passes and the epilogue.  The 28 sums of an evaluation (H's upper
+ * triangle, g, e) have a fixed feature-to-lane assignment and a fixed reduction shape, and the medians of vector_mean_stdv_mad / vector_stdv_mad
+ * (src/Auxiliar.cc:399-472) are exact selections of element n / 2, so a frame's outputs are the same bits wherever it stands in a batch.
+ *
+ * Three things the reference leaves undefined are defined here:
+ *  - a feature that enters with its outlier flag set: its previous-frame position is computed like any other (the reference reads a stale vector there;
+ *    none of its call sites produces such a feature);
+ *  - DT_cov when use_motion_model = 0 and a pass returns early: the reference's is uninitialised there, the entry's is DT_cov_in (or zeros);
+ *  - a pass that starts with no active (held, not outlier) feature, or an H, g or DT that is not finite (the reference divides by zero): the frame stops
+ *    there.  Its pose goes through unchanged (Tcw_out = Tcw), DT = I, DT_cov = 0, err_norm = -1, the eigenvalues 0, good = 0, its outlier flags stay as
+ *    they stood, and bit 1 (no active feature) or bit 2 (not finite) of the frame's status word is set.
+ * A held feature whose octave is outside the context's levels is left out (it holds nothing) and sets bit 4 of the frame's status word; an index at or past
+ * n_mp / n_ml counts as "holds nothing" and sets bit 512 / 1024 of the context's status word.  Like the other batch entries: no synchronisation and no host
+ * read, the batch scratch slot, n_frames == 0 writes nothing, a NULL required pointer is OLF_ERR_INVALID, accesses are never out of bounds. */
+int olf_pose_optimization_with_line_batch_dev(olf_ctx* ctx, const olf_pose_batch* in, int n_frames, const olf_pose_params* params, const olf_pose_outputs* out,
+                                              void* stream);
+/* The host form: one frame (frame 0 of `in`), host pointers, no context and no device; plain doubles, every sum in the reference's index order.  capacity /
+ * line_capacity: the lengths of the per-feature rows; inv_level_sigma2 [n_levels]: mvInvLevelSigma2 (olf_orb_scale_tables).  Without a context the bits
+ * 512 / 1024 go into the frame's status word. */
+int olf_pose_optimization_with_line(const olf_pose_batch* in, int capacity, int line_capacity, const float* inv_level_sigma2, int n_levels,
+                                    const olf_pose_params* params, const olf_pose_outputs* out);
+/* One frame from host pointers on the device: the rows of `in` (lengths counts[0] / lcounts[0], at most the context's capacities, else OLF_ERR_CAPACITY) are
+ * staged, the batched kernel runs on a batch of one, the outputs come back (outlier_out [counts[0]], outlier_l_out [lcounts[0]]); synchronises.  An index
+ * outside the maps makes the call return OLF_ERR_CAPACITY with the bit's text, the outputs complete. */
+int olf_pose_optimization_with_line_frame(olf_ctx* ctx, const olf_pose_batch* in, const olf_pose_params* params, const olf_pose_outputs* out);
+/* The "discard outliers" loops that follow the three calls, on the rows the optimiser read and wrote.  Device pointers, rows as above; frame_mp / frame_ml /
+ * outlier / outlier_l are changed in place; mp_obs [n_mp] / ml_obs [n_ml]: Observations() > 0 (NULL: all).
+ *  mode 0  src/Tracking.cc:1034-1074 (the same loops follow :1470): a held outlier is dropped (-1) and its flag cleared; n_matches = the held rest with
+ *          Observations() > 0 (nmatchesMap_p, nmatchesMap_l);
+ *  mode 1  :1547-1590: n_matches = held and not outlier, with Observations() > 0 unless only_tracking (mnMatchesInliers, mnMatchesInliers_l); a held outlier
+ *          is dropped when `stereo` and keeps its flag.  IncreaseFound() stays the caller's: it is "held and not outlier" of the inputs.
+ * d_n_matches [n_frames][2]: points, lines.  Indices at or past n_mp / n_ml are left alone and set bit 512 / 1024 of the context's status word. */
+typedef struct olf_discard_batch {
+    const int32_t* counts; const int32_t* lcounts; int32_t img_stride;
+    int32_t* frame_mp; int32_t* frame_ml;
+    uint8_t* outlier; uint8_t* outlier_l;
+    const int32_t* mp_index_offset; const int32_t* ml_index_offset;
+    const uint8_t* mp_obs; const uint8_t* ml_obs;
+    int32_t n_mp, n_ml;
+} olf_discard_batch;
+int olf_discard_outliers_batch_dev(olf_ctx* ctx, const olf_discard_batch* io, int n_frames, int mode, int only_tracking, int stereo, int32_t* d_n_matches,
+                                   void* stream);
+/* one frame from host pointers on the device, as olf_pose_optimization_with_line_frame */
+int olf_discard_outliers_frame(olf_ctx* ctx, const olf_discard_batch* io, int mode, int only_tracking, int stereo, int32_t* n_matches);
+/* the host form: one frame, host pointers, no context; *status receives the bits 512 / 1024 */
+int olf_discard_outliers(const olf_discard_batch* io, int capacity, int line_capacity, int mode, int only_tracking, int stereo, int32_t* n_matches,
+                         int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

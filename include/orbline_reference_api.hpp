@@ -1075,4 +1075,76 @@ std::vector<int32_t> KeyFrameCulling(olf_ctx* c, KeyFrameT* pCurrentKF, bool bMo
     return decision;
 }
 
+// ---- Optimizer::PoseOptimizationWithLine (src/Optimizer.cc:604-697) over the reference's own types ----------------------------------------------------------
+// Reads what the reference reads of the frame -- mvpMapPoints with GetWorldPos(), mvpMapLines with mWorldPos_sP / mWorldPos_eP, mvKeysUn, mvKeysUn_Line,
+// mvle_l, mTcw, mTcw_prev (empty: mTcw), DT_cov, the calibration, mvInvLevelSigma2, mvbOutlier, mvbOutlier_Line -- and writes what it writes: mTcw through
+// SetPose, DT, DT_cov, DT_cov_eig, err_norm, mvbOutlier, mvbOutlier_Line and n_inliers, n_inliers_pt, n_inliers_ls.  c == NULL: the host form
+// (olf_pose_optimization_with_line, no device); otherwise the frame runs on the device through context c, whose capacities must hold the frame and whose
+// level table must be the frame's.  params: Config's maxItersRef(), homogTh(), minError(), minErrorChange(), inlierK(), useMotionModel(), hasPoints(),
+// hasLines() (NULL: their defaults).  Returns true, as the reference does; *status (or NULL) receives the frame's status word: the cases the reference
+// leaves undefined pass the pose through (include/orbline.h).
+template <class FrameT>
+bool PoseOptimizationWithLine(olf_ctx* c, FrameT* pFrame, const olf_pose_params* params = nullptr, int32_t* status = nullptr)
+{
+    typedef typename std::remove_const<typename std::remove_reference<decltype(pFrame->mTcw)>::type>::type MatT;
+    typedef typename std::remove_reference<decltype(pFrame->mvKeysUn[0])>::type KP;
+    typedef typename std::remove_reference<decltype(pFrame->mvKeysUn_Line[0])>::type KL;
+    static_assert(sizeof(KP) == sizeof(olf_keypoint) && sizeof(KL) == sizeof(olf_keyline), "cv::KeyPoint / KeyLine layout");
+    olf_pose_params p;
+    if (params) p = *params; else olf_pose_default_params(&p);
+    const int N = (int)pFrame->mvpMapPoints.size(), NL = (int)pFrame->mvpMapLines.size();
+    std::vector<int32_t> fmp(N + 1, -1), fml(NL + 1, -1);
+    std::vector<float> mpw, mlw;
+    std::vector<uint8_t> out(N + 1, 0), outl(NL + 1, 0);
+    std::vector<double> lle(3 * (size_t)NL + 3, 0.0);
+    for (int i = 0; i < N; ++i) {
+        out[i] = pFrame->mvbOutlier[i] ? 1 : 0;
+        if (!pFrame->mvpMapPoints[i]) continue;
+        const auto wp = pFrame->mvpMapPoints[i]->GetWorldPos();
+        fmp[i] = (int32_t)(mpw.size() / 3);
+        for (int k = 0; k < 3; ++k) mpw.push_back(wp.template at<float>(k));
+    }
+    for (int i = 0; i < NL; ++i) {
+        outl[i] = pFrame->mvbOutlier_Line[i] ? 1 : 0;
+        for (int k = 0; k < 3; ++k) lle[3 * i + k] = pFrame->mvle_l[i][k];
+        if (!pFrame->mvpMapLines[i]) continue;
+        fml[i] = (int32_t)(mlw.size() / 6);
+        for (int k = 0; k < 3; ++k) mlw.push_back((float)pFrame->mvpMapLines[i]->mWorldPos_sP[k]);
+        for (int k = 0; k < 3; ++k) mlw.push_back((float)pFrame->mvpMapLines[i]->mWorldPos_eP[k]);
+    }
+    float Tcw[16], Tprev[16], Tout[16];
+    double cov_in[36], DT[16], cov[36], eig[6], err = -1.0;
+    olf_detail::mat4(pFrame->mTcw, Tcw);
+    const bool has_prev = !pFrame->mTcw_prev.empty();
+    if (has_prev) olf_detail::mat4(pFrame->mTcw_prev, Tprev);
+    for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) cov_in[6 * i + j] = pFrame->DT_cov(i, j);
+    const int32_t counts[1] = {N}, lcounts[1] = {NL};
+    olf_pose_batch in;
+    std::memset(&in, 0, sizeof(in));
+    in.kps = reinterpret_cast<const olf_keypoint*>(pFrame->mvKeysUn.data()); in.counts = counts;
+    in.kls = reinterpret_cast<const olf_keyline*>(pFrame->mvKeysUn_Line.data()); in.lcounts = lcounts; in.img_stride = 1;
+    in.lle = lle.data(); in.Tcw = Tcw; in.Tcw_prev = has_prev ? Tprev : nullptr; in.DT_cov_in = cov_in;
+    in.fx = pFrame->fx; in.fy = pFrame->fy; in.cx = pFrame->cx; in.cy = pFrame->cy;
+    in.frame_mp = fmp.data(); in.mp_world = mpw.data(); in.n_mp = (int32_t)(mpw.size() / 3);
+    in.frame_ml = fml.data(); in.ml_world = mlw.data(); in.n_ml = (int32_t)(mlw.size() / 6);
+    in.outlier = out.data(); in.outlier_l = outl.data();
+    uint8_t good = 0;
+    int32_t inl[2] = {0, 0}, iters[4], st = 0;
+    const olf_pose_outputs o = {Tout, DT, cov, eig, &err, &good, out.data(), outl.data(), inl, iters, &st};
+    if (c) olf_detail::check(olf_pose_optimization_with_line_frame(c, &in, &p, &o), "olf_pose_optimization_with_line_frame");
+    else olf_detail::check(olf_pose_optimization_with_line(&in, N, NL, pFrame->mvInvLevelSigma2.data(), (int)pFrame->mvInvLevelSigma2.size(), &p, &o),
+                           "olf_pose_optimization_with_line");
+    MatT T(4, 4, 5 /* CV_32F */);
+    for (int r = 0; r < 4; ++r) for (int k = 0; k < 4; ++k) T.template at<float>(r, k) = Tout[4 * r + k];
+    pFrame->SetPose(T);
+    for (int r = 0; r < 4; ++r) for (int k = 0; k < 4; ++k) pFrame->DT(r, k) = DT[4 * r + k];
+    for (int i = 0; i < 6; ++i) { pFrame->DT_cov_eig(i) = eig[i]; for (int j = 0; j < 6; ++j) pFrame->DT_cov(i, j) = cov[6 * i + j]; }
+    pFrame->err_norm = err;
+    for (int i = 0; i < N; ++i) if (pFrame->mvpMapPoints[i]) pFrame->mvbOutlier[i] = out[i] != 0;          // (removeOutliers looks at held features only)
+    for (int i = 0; i < NL; ++i) if (pFrame->mvpMapLines[i]) pFrame->mvbOutlier_Line[i] = outl[i] != 0;
+    pFrame->n_inliers_pt = inl[0]; pFrame->n_inliers_ls = inl[1]; pFrame->n_inliers = inl[0] + inl[1];
+    if (status) *status = st;
+    return true;
+}
+
 }  // namespace ORB_SLAM2

@@ -103,6 +103,33 @@ class CullViewC(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("mp_obs_slot", "mp_nobs", "kf_slot_octave", "kf_slot_depth", "kf_slot_stereo", "kf_th_depth", "kf_mode")]
 
 
+class PoseParamsC(C.Structure):
+    """olf_pose_params (include/orbline.h): Config's optimisation parameters as Optimizer::PoseOptimizationWithLine reads them"""
+    _fields_ = ([("max_iters_ref", C.c_int32)] + [(n, C.c_double) for n in ("homog_th", "min_error", "min_error_change", "inlier_k")] +
+                [(n, C.c_int32) for n in ("use_motion_model", "has_points", "has_lines")])
+
+
+class PoseBatchC(C.Structure):
+    """olf_pose_batch (include/orbline.h): a batch of frames as the pose optimiser reads them"""
+    _fields_ = ([(n, C.c_void_p) for n in ("kps", "counts", "kls", "lcounts")] + [("img_stride", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("lle", "Tcw", "Tcw_prev", "DT_cov_in")] + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy")] +
+                [(n, C.c_void_p) for n in ("frame_mp", "mp_index_offset", "mp_world")] + [("n_mp", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("frame_ml", "ml_index_offset", "ml_world")] + [("n_ml", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("outlier", "outlier_l")])
+
+
+class PoseOutputsC(C.Structure):
+    """olf_pose_outputs (include/orbline.h): what the pose optimiser writes per frame"""
+    _fields_ = [(n, C.c_void_p) for n in ("Tcw_out", "DT", "DT_cov", "DT_cov_eig", "err_norm", "good", "outlier_out", "outlier_l_out", "n_inliers", "iters", "status")]
+
+
+class DiscardBatchC(C.Structure):
+    """olf_discard_batch (include/orbline.h): the rows the "discard outliers" loops read and change"""
+    _fields_ = ([(n, C.c_void_p) for n in ("counts", "lcounts")] + [("img_stride", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("frame_mp", "frame_ml", "outlier", "outlier_l", "mp_index_offset", "ml_index_offset", "mp_obs", "ml_obs")] +
+                [("n_mp", C.c_int32), ("n_ml", C.c_int32)])
+
+
 class BowCsrC(C.Structure):
     """olf_bow_csr (include/orbline.h): n BoW vectors as offsets, ascending word ids and values"""
     _fields_ = [(n, C.c_void_p) for n in ("off", "ids", "vals")]
@@ -296,6 +323,14 @@ def lib():
         L.olf_tracked_map_points.argtypes = [P, C.POINTER(MapGraphC), P, P, C.c_int, P, C.c_int, C.c_int, P, P]
         L.olf_map_point_culling_dev.argtypes = [P, C.c_int] + [P] * 5 + [C.c_int64, C.c_int, P, P]
         L.olf_map_point_culling.argtypes = [P, C.c_int] + [P] * 5 + [C.c_int64, C.c_int, P]
+        L.olf_pose_default_params.argtypes = [C.POINTER(PoseParamsC)]
+        L.olf_pose_default_params.restype = None
+        L.olf_pose_optimization_with_line_batch_dev.argtypes = [P, C.POINTER(PoseBatchC), C.c_int, C.POINTER(PoseParamsC), C.POINTER(PoseOutputsC), P]
+        L.olf_pose_optimization_with_line.argtypes = [C.POINTER(PoseBatchC), C.c_int, C.c_int, P, C.c_int, C.POINTER(PoseParamsC), C.POINTER(PoseOutputsC)]
+        L.olf_discard_outliers_batch_dev.argtypes = [P, C.POINTER(DiscardBatchC), C.c_int, C.c_int, C.c_int, C.c_int, P, P]
+        L.olf_pose_optimization_with_line_frame.argtypes = [P, C.POINTER(PoseBatchC), C.POINTER(PoseParamsC), C.POINTER(PoseOutputsC)]
+        L.olf_discard_outliers_frame.argtypes = [P, C.POINTER(DiscardBatchC), C.c_int, C.c_int, C.c_int, P]
+        L.olf_discard_outliers.argtypes = [C.POINTER(DiscardBatchC), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]
         L.olf_profile_enable.argtypes = [C.c_void_p, C.c_int]
         L.olf_profile_reset.argtypes = [C.c_void_p]
         L.olf_profile_stage_name.restype = C.c_char_p
