@@ -578,7 +578,7 @@ int olf_search_local_map_batch_dev(olf_ctx* ctx, const olf_track_batch* in, int 
  * `in`: only kps, desc, counts, img_stride, uright, Tcw, mp_valid and fx, fy, cx, cy are read (frame j = image j * img_stride).  mp_valid keeps its
  * meaning -- the features that hold a map point, which this search skips on both sides -- so NULL (every feature holds one) searches nothing: rows -1,
  * counts 0.  mvScaleFactors are the context's.  d_pairs [n_pairs][2] = (kf1, kf2) frame indices, any order, a frame in any number of pairs.
- * d_F12 [n_pairs][9] row-major, used as x1^T F12 x2 (LocalMapping::ComputeF12 stays the caller's).  d_Cw [n_pairs][3] = pKF1->GetCameraCenter(), or NULL:
+ * d_F12 [n_pairs][9] row-major, used as x1^T F12 x2 (LocalMapping::ComputeF12: olf_compute_f12_pairs_dev).  d_Cw [n_pairs][3] = pKF1->GetCameraCenter(), or NULL:
  * -Rcw.t() * tcw of kf1's Tcw.  d_matches12 [n_pairs][capacity]: row p holds per feature idx1 of kf1 the matched feature idx2 of kf2 or -1 (-1 from N1
  * on); vMatchedPairs is the list of (idx1, d_matches12[p][idx1] >= 0) in idx1 order.  d_nmatches [n_pairs]: the return values.
  * A pair whose index lies outside [0, n_frames), or with kf1 == kf2, ends with nmatches = -1 and its row untouched, and sets bit 2048 of the context's
@@ -1001,6 +1001,94 @@ int olf_map_point_culling_dev(olf_ctx* ctx, int n, const uint8_t* d_bad, const i
 /* host buffers: uploads, runs, downloads */
 int olf_map_point_culling(olf_ctx* ctx, int n, const uint8_t* bad, const int32_t* found, const int32_t* visible, const int32_t* nobs,
                           const int64_t* first_kf_id, int64_t current_kf_id, int monocular, uint8_t* action);
+
+/* ---- the entries that produce map arrays: ComputeF12 and UpdateNormalAndDepth (csrc/newpoints_batch.hip, newpoints_host.cpp, newpoints_terms.hpp) ----------
+ * cv::Mat LocalMapping::ComputeF12(KeyFrame *&pKF1, KeyFrame *&pKF2) (src/LocalMapping.cc:536-553; called at :264) for n_pairs pairs of the n_frames
+ * frames of a batch: d_F12 of olf_search_for_triangulation_batch_dev for the same d_pairs, without a host step.  `in`: only Tcw and fx, fy, cx, cy are
+ * read (both key frames share mK).  R12 = R1w * R2w.t() (a transposed operand: double accumulation, one rounding), t12 = -R1w * R2w.t() * t2w + t1w (the
+ * negated R12, then a plain product with t1w as its C term), K1.t().inv() * t12x * R12 * K2.inv() left to right as three plain products (C.12);
+ * cv::invert of the two 3 x 3 matrices is the closed-form adjugate with determinant and cofactors in double, one rounding per element (C.18).
+ * d_pairs [n_pairs][2] = (kf1, kf2); d_F12 [n_pairs][9] row-major, used as x1^T F12 x2.  A pair whose index lies outside [0, n_frames), or with
+ * kf1 == kf2, is left untouched and sets bit 2048 of the context's status word.  n_pairs == 0 writes nothing; a NULL required pointer or a negative
+ * count: OLF_ERR_INVALID, before any launch.  Does not synchronise; runs on `stream`; no scratch. */
+int olf_compute_f12_pairs_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, int n_pairs, const int32_t* d_pairs, float* d_F12, void* stream);
+/* the host form: one pair from its two 4 x 4 poses (row-major), no context and no device; the same text (csrc/newpoints_terms.hpp) */
+int olf_compute_f12(const float* Tcw1, const float* Tcw2, float fx, float fy, float cx, float cy, float* F12);
+/* void LocalMapping::CreateNewMapPoints() after the search (src/LocalMapping.cc:245-253 and :286-431: the baseline test, the parallax test, linear
+ * triangulation or KeyFrame::UnprojectStereo, the depth, reprojection and scale gates) for n_pairs pairs (kf1 = mpCurrentKeyFrame, kf2 = a neighbour) of
+ * the n_frames frames of a batch and the match rows exactly as olf_search_for_triangulation_batch_dev wrote them: d_matches12 [n_pairs][capacity], row p
+ * holding per idx1 the idx2 or -1.  `in`: kps (mvKeysUn), counts, img_stride, uright, Tcw and fx, fy, cx, cy, mbf are read; d_depth [n_frames][capacity]
+ * is mvDepth (as olf_unproject_stereo_dev takes it); mb = mbf / fx as the key frames hold it; mvScaleFactors / mvLevelSigma2 are the context's, and
+ * ratioFactor = 1.5f * mvScaleFactors[1] (mfScaleFactor; 1 in a context of one level).  monocular: mbMonocular -- 0 applies the `baseline < pKF2->mb`
+ * skip of :249-253, 1 skips nothing here (ComputeSceneMedianDepth stays the caller's).
+ * Outputs, one row per pair, indexed by idx1: d_x3D [n_pairs][capacity][3], the new point where d_code is 1 to 3 and zeros elsewhere; d_code
+ * [n_pairs][capacity] (uint8):
+ *    0  no match (also from N1 on)           1  created by triangulation
+ *    2  created by UnprojectStereo of kf1    3  created by UnprojectStereo of kf2
+ *   16  low parallax without stereo (:349)  17  w == 0 (:334)      18  z1 <= 0 (:356)             19  z2 <= 0 (:360)
+ *   20  reprojection in kf1 (:375, :386)    21  reprojection in kf2 (:401, :412)    22  dist1 == 0 || dist2 == 0 (:423)    23  scale ratio (:431)
+ * d_nnew [n_pairs]: the number of codes 1 to 3 of the row, `nnew` of the pair.  A pair skipped by the baseline test has nnew = 0 and an all-0 row.  What
+ * follows a created point in the reference (new MapPoint, AddObservation, AddMapPoint, ComputeDistinctiveDescriptors, UpdateNormalAndDepth) is the
+ * caller's, from the codes; olf_update_normal_and_depth_dev is the last of them.  One call over all pairs is the snapshot answer: see INTEGRATION.md for
+ * the reference's neighbour-by-neighbour staleness.
+ * Arithmetic (csrc/newpoints_terms.hpp, one text for this entry and its host form; C.12 products, C.4 no contraction): cosParallaxRays is a double quotient
+ * of Mat::dot and two cv::norm rounded to float; cos(2 * atan2(mb / 2, depth)) is the float overloads, glibc's atan2f and cosf as csrc/device_math.hpp
+ * restates them; the rows of A are a float product and a float difference per element; cv::SVD::compute is the float one-sided Jacobi iteration of an
+ * OpenCV built without LAPACK (C.19: a build with LAPACK calls sgesdd and differs in the last bits; the tests compare triangulated points by tolerance);
+ * x3D / w multiplies by (float)(1.0 / (double)w) (C.17); z = Rcw.row(2).dot(x3Dt) + tcw(2) is a double sum rounded once; invz = (float)(1.0 / z); the
+ * error sums are float, compared with the double products 5.991 * sigma2 and 7.8 * sigma2; the right-image term of BOTH key frames uses mbf of the
+ * current one (:406, as written); UnprojectStereo is the routine of olf_unproject_stereo_dev on Twc = [Rcw.t() | Ow], Ow = -Rwc * tcw as KeyFrame::SetPose
+ * forms it (src/KeyFrame.cc:154-155: a plain product on the materialised transpose).  A feature with mvuRight >= 0 and mvDepth <= 0, for which the
+ * reference's UnprojectStereo returns an empty matrix, is computed with that depth.
+ * Malformed input: a pair with an index outside [0, n_frames) or kf1 == kf2 gives nnew = -1, leaves its rows untouched and sets bit 2048 of the context's
+ * status word; an idx2 outside [0, N2) is no match; a match either of whose key points holds an octave outside the context's levels is left out (code 0)
+ * with bit 256.  n_pairs == 0 writes nothing; a NULL required pointer or a negative count: OLF_ERR_INVALID, before any launch.  Nothing is read or
+ * written out of bounds.  Results do not depend on scheduling or on a pair's position in the list.  Does not synchronise; runs on `stream`; no scratch. */
+int olf_create_new_map_points_batch_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const float* d_depth, float mb, int n_pairs, const int32_t* d_pairs,
+                                        const int32_t* d_matches12, int monocular, float* d_x3D, uint8_t* d_code, int32_t* d_nnew, void* stream);
+/* the host form: host pointers in `in` and everywhere else, no context and no device; capacity: the row length of the per-frame planes; scale_factors
+ * [n_levels] = mvScaleFactors; *status receives the bits 256 / 2048 */
+int olf_create_new_map_points(const olf_track_batch* in, int capacity, int n_frames, const float* depth, float mb, const float* scale_factors, int n_levels,
+                              int n_pairs, const int32_t* pairs, const int32_t* matches12, int monocular, float* x3D, uint8_t* code, int32_t* nnew,
+                              int32_t* status);
+/* void MapPoint::UpdateNormalAndDepth() (src/MapPoint.cc:342-383; called for new points at src/LocalMapping.cc:444, for fused points at :527, after every bundle
+ * adjustment, src/Optimizer.cc:227, :1743, :2009, in loop correction, src/LoopClosing.cc:506, and at map load, src/Map.cc:665) for n_points map points of one snapshot: d_points [n_points], or NULL for the points 0 .. n_points - 1
+ * (n_points = n_mp: every point).  Reads mp_obs_offsets, mp_obs_kf, mp_bad and kf_mp_offsets of g, mp_obs_slot and kf_slot_octave of v (device pointers),
+ * d_mp_world [n_mp][3] (mWorldPos), d_mp_ref_kf [n_mp] (mpRefKF as a key-frame index) and d_kf_Ow [n_kf][3] (GetCameraCenter()); mvScaleFactors and
+ * mnScaleLevels are the context's.  Writes, in place and only for the listed points: d_normal [n_mp][3] (mNormalVector), d_maxd, d_mind [n_mp]
+ * (mfMaxDistance, mfMinDistance: unscaled, as olf_local_map takes them).  A bad point (:350) or a point with an empty observation row (:357) is left
+ * untouched.
+ * The normal is summed over the observation row IN ROW ORDER, sequentially in float (:362-369).  The reference iterates a std::map<KeyFrame*, size_t>,
+ * i.e. in address order: a caller who wants convention C.15 / C.16 (ascending key-frame index stands for ascending address) passes every row ascending.
+ * normali / cv::norm(normali) multiplies by (float)(1.0 / norm) with the norm kept in double, normal / n by (float)(1.0 / (double)n) (C.17).
+ * mfMaxDistance = (float)cv::norm(Pos - Ow_ref) * mvScaleFactors[level], mfMinDistance = mfMaxDistance / mvScaleFactors[nLevels - 1], in float.  The level
+ * is the octave at slot observations[pRefKF] of the reference key frame (:373): the slot of the row's entry that names d_mp_ref_kf, or, when the row does
+ * not name it, slot 0 -- std::map::operator[] inserts a zero there and the reference reads mvKeysUn[0].octave.
+ * Malformed input is left out, never dereferenced: an observation whose key frame lies outside [0, n_kf) or whose slot lies outside that key frame's row
+ * sets bit 4096 of the context's status word and enters neither the sum, nor n, nor the search for the reference's slot (a point left without
+ * observations counts as an empty row); a reference key frame outside [0, n_kf), or a level slot outside the reference's row, sets bit 4096 and leaves
+ * the point untouched; an octave outside the context's levels does so with bit 256; a point index outside [0, n_mp) with bit 512.  A point listed twice
+ * is computed twice with the same result.  Errors: a NULL required pointer (mp_obs_offsets, kf_mp_offsets; the per-point arrays unless n_mp == 0; the
+ * per-key-frame arrays unless n_kf == 0) or a negative size: OLF_ERR_INVALID.  n_points == 0 writes nothing.  Does not synchronise; runs on `stream`; no
+ * scratch. */
+int olf_update_normal_and_depth_dev(olf_ctx* ctx, const olf_map_graph* g, const olf_cull_view* v, int n_points, const int32_t* d_points, const float* d_mp_world,
+                                    const int32_t* d_mp_ref_kf, const float* d_kf_Ow, float* d_normal, float* d_maxd, float* d_mind, void* stream);
+/* the host form: host pointers, no context and no device; scale_factors [n_levels] = mvScaleFactors (olf_orb_scale_tables), 1 <= n_levels <=
+ * OLF_MAX_LEVELS; *status receives the bits 256 / 512 / 4096.  Checks the two offsets arrays (non-decreasing from 0: OLF_ERR_INVALID otherwise). */
+int olf_update_normal_and_depth(const olf_map_graph* g, const olf_cull_view* v, int n_points, const int32_t* points, const float* mp_world,
+                                const int32_t* mp_ref_kf, const float* kf_Ow, const float* scale_factors, int n_levels, float* normal, float* maxd, float* mind,
+                                int32_t* status);
+
+/* The three entries above from host pointers ON THE DEVICE (csrc/newpoints_api.cpp): the arrays are staged, the same kernels run on the context's stream,
+ * the outputs come back; synchronises.  The outputs are uploaded first, so what the device form leaves untouched (a refused pair's rows, a bad point) comes
+ * back as it went in.  The per-frame planes of `in` and depth are [n_frames][olf_orb_capacity(ctx)], as for the device forms; Tcw [n_frames][16].  The
+ * update entry checks the two offsets arrays (non-decreasing from 0: OLF_ERR_INVALID).  A set status bit makes the call return OLF_ERR_CAPACITY with the
+ * bit's text, the outputs complete. */
+int olf_compute_f12_pairs(olf_ctx* ctx, const float* Tcw, int n_frames, float fx, float fy, float cx, float cy, int n_pairs, const int32_t* pairs, float* F12);
+int olf_create_new_map_points_pairs(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const float* depth, float mb, int n_pairs, const int32_t* pairs,
+                                    const int32_t* matches12, int monocular, float* x3D, uint8_t* code, int32_t* nnew);
+int olf_update_normal_and_depth_points(olf_ctx* ctx, const olf_map_graph* g, const olf_cull_view* v, int n_points, const int32_t* points, const float* mp_world,
+                                       const int32_t* mp_ref_kf, const float* kf_Ow, float* normal, float* maxd, float* mind);
 
 /* measurement: rate of a plain 16-byte-per-thread device copy kernel over `bytes` (read + written bytes per second): the practical HBM
  * ceiling bench.py reports next to the specification's 8 TB/s */

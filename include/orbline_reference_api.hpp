@@ -886,6 +886,51 @@ public:
         view_filled_ = true;
         return v_;
     }
+    // MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:342-383) for the listed points of the snapshot (a point outside it is passed over), through
+    // olf_update_normal_and_depth (c == NULL: the host form, no device) or olf_update_normal_and_depth_points (on the device through context c, whose level
+    // table must be the key frames').  Reads GetWorldPos(), GetReferenceKeyFrame(), GetCameraCenter(), mvScaleFactors of the first key frame and cull_view();
+    // the observation rows are the std::map's own iteration order.  mNormalVector, mfMaxDistance and mfMinDistance are protected (include/MapPoint.h), so
+    // the integrator adds ONE accessor, whose body is the locked block :377-382 with the three values given:
+    //     void MapPoint::SetNormalAndDepth(const cv::Mat& normal, float maxDistance, float minDistance);
+    // It is called for every listed point the reference would have changed (not bad, observed, reference key frame inside the snapshot).  Returns their number.
+    int UpdateNormalAndDepth(olf_ctx* c, const std::vector<MapPointT*>& points)
+    {
+        const olf_cull_view& v = cull_view();
+        const size_t nm = mps_.size(), nk = kfs_.size();
+        std::vector<float> world(3 * nm + 1), Ow(3 * nk + 1), normal(3 * nm + 1, 0.0f), maxd(nm + 1, -1.0f), mind(nm + 1, -1.0f), sf;
+        std::vector<int32_t> ref(nm + 1, -1), list;
+        for (size_t i = 0; i < nm; ++i) {
+            const auto w = mps_[i]->GetWorldPos();
+            for (int k = 0; k < 3; ++k) world[3 * i + k] = w.template at<float>(k);
+            ref[i] = index_of(mps_[i]->GetReferenceKeyFrame());
+        }
+        for (size_t k = 0; k < nk; ++k) {
+            const auto o = kfs_[k]->GetCameraCenter();
+            for (int q = 0; q < 3; ++q) Ow[3 * k + q] = o.template at<float>(q);
+        }
+        for (size_t j = 0; j < points.size(); ++j) { const int i = index_of(points[j]); if (i >= 0 && ref[i] >= 0) list.push_back(i); }
+        if (list.empty() || nk == 0) return 0;
+        if (!c) {
+            for (size_t l = 0; l < kfs_[0]->mvScaleFactors.size(); ++l) sf.push_back(kfs_[0]->mvScaleFactors[l]);
+            int32_t status = 0;
+            olf_detail::check(olf_update_normal_and_depth(&g_, &v, (int)list.size(), list.data(), world.data(), ref.data(), Ow.data(), sf.data(), (int)sf.size(), normal.data(),
+                                                          maxd.data(), mind.data(), &status), "olf_update_normal_and_depth");
+        } else
+            olf_detail::check(olf_update_normal_and_depth_points(c, &g_, &v, (int)list.size(), list.data(), world.data(), ref.data(), Ow.data(), normal.data(), maxd.data(),
+                                                                 mind.data()), "olf_update_normal_and_depth_points");
+        int changed = 0;
+        std::vector<uint8_t> done(nm + 1, 0);
+        for (size_t j = 0; j < list.size(); ++j) {
+            const int i = list[j];
+            if (done[i] || maxd[i] == -1.0f) continue;              // (left untouched: bad, or without observations)
+            done[i] = 1;
+            auto n = mps_[i]->GetWorldPos();                         // (a clone: a 3 x 1 CV_32F matrix to fill)
+            for (int k = 0; k < 3; ++k) n.template at<float>(k) = normal[3 * i + k];
+            mps_[i]->SetNormalAndDepth(n, maxd[i], mind[i]);
+            ++changed;
+        }
+        return changed;
+    }
     int index_of(KeyFrameT* p) const { return lookup(kf_index_, p); }
     int index_of(MapPointT* p) const { return lookup(mp_index_, p); }
     int line_index_of(MapLineT* p) const { return lookup(ml_index_, p); }
@@ -1073,6 +1118,90 @@ std::vector<int32_t> KeyFrameCulling(olf_ctx* c, KeyFrameT* pCurrentKF, bool bMo
     decision.resize(n);
     ApplyKeyFrameCulling(vpLocalKeyFrames, decision.data());
     return decision;
+}
+
+// ---- LocalMapping::ComputeF12 and the triangulation loop of CreateNewMapPoints (src/LocalMapping.cc:536-553, :245-253, :286-431) over the reference's types ----
+// c == NULL: the host forms (olf_compute_f12, olf_create_new_map_points; no device); otherwise the pair runs on the device through context c
+// (olf_compute_f12_pairs, olf_create_new_map_points_pairs), whose capacity must hold both key frames and whose level table must be theirs.
+// ComputeF12 reads GetPose() and fx, fy, cx, cy of pKF1 (mK of both) and returns the reference's matrix type, 3 x 3 CV_32F.
+template <class KeyFrameT>
+auto ComputeF12(olf_ctx* c, KeyFrameT* pKF1, KeyFrameT* pKF2) -> decltype(pKF1->GetRotation())
+{
+    float T[32], F[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    olf_detail::mat4(pKF1->GetPose(), T);
+    olf_detail::mat4(pKF2->GetPose(), T + 16);
+    const int32_t pair[2] = {0, 1};
+    if (!c) olf_detail::check(olf_compute_f12(T, T + 16, pKF1->fx, pKF1->fy, pKF1->cx, pKF1->cy, F), "olf_compute_f12");
+    else olf_detail::check(olf_compute_f12_pairs(c, T, 2, pKF1->fx, pKF1->fy, pKF1->cx, pKF1->cy, 1, pair, F), "olf_compute_f12_pairs");
+    auto F12 = pKF1->GetRotation();                                  // (a clone: a 3 x 3 CV_32F matrix to fill)
+    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) F12.template at<float>(r, k) = F[3 * r + k];
+    return F12;
+}
+
+// What the loop at :286-450 decides for the matches of one neighbour, in the order of vMatchedIndices: code (include/orbline.h: 1 to 3 created, 16 to 23 the
+// reference's `continue`s, 0 left out), the point of the created ones, and nnew.  `new MapPoint(x3D, ...)`, AddObservation, AddMapPoint,
+// ComputeDistinctiveDescriptors, UpdateNormalAndDepth and the two lists (:434-447) stay the caller's, for the codes 1 to 3 in this order.
+struct NewMapPoints {
+    std::vector<uint8_t> code;
+    std::vector<float> x3D;                                          // three per match
+    int nnew = 0;
+    bool skipped = false;                                            // the baseline test of :249-253 skipped the neighbour
+};
+// Reads mvKeysUn, mvuRight, mvDepth, N, GetPose(), fx, fy, cx, cy, mbf, mb and mvScaleFactors of the two key frames.  A match whose idx1 was listed before
+// is computed on its own (the row of the C entry holds one idx2 per idx1, so such a list goes down in several calls).
+template <class KeyFrameT>
+void CreateNewMapPoints(olf_ctx* c, KeyFrameT* pKF1, KeyFrameT* pKF2, const std::vector<std::pair<size_t, size_t> >& vMatchedIndices, bool bMonocular, NewMapPoints& out)
+{
+    const int nm = (int)vMatchedIndices.size();
+    out.code.assign(nm, 0); out.x3D.assign(3 * (size_t)nm, 0.0f); out.nnew = 0; out.skipped = false;
+    const int N1 = (int)pKF1->mvKeysUn.size(), N2 = (int)pKF2->mvKeysUn.size();
+    const int cap = c ? olf_orb_capacity(c) : std::max(std::max(N1, N2), 1);
+    if (N1 > cap || N2 > cap) throw std::runtime_error("CreateNewMapPoints: the context's capacity does not hold the key frames");
+    std::vector<olf_keypoint> kps(2 * (size_t)cap);
+    std::vector<float> ur(2 * (size_t)cap, -1.0f), depth(2 * (size_t)cap, -1.0f), sf, x3D(3 * (size_t)cap);
+    std::vector<uint8_t> code(cap);
+    KeyFrameT* kf[2] = {pKF1, pKF2};
+    const int32_t counts[2] = {N1, N2}, pair[2] = {0, 1};
+    float T[32];
+    for (int j = 0; j < 2; ++j) {
+        olf_detail::mat4(kf[j]->GetPose(), T + 16 * j);
+        if (counts[j]) std::memcpy(&kps[(size_t)j * cap], olf_detail::keypoints(kf[j]->mvKeysUn), (size_t)counts[j] * sizeof(olf_keypoint));
+        for (int i = 0; i < counts[j]; ++i) { ur[(size_t)j * cap + i] = kf[j]->mvuRight[i]; depth[(size_t)j * cap + i] = kf[j]->mvDepth[i]; }
+    }
+    for (size_t l = 0; l < pKF1->mvScaleFactors.size(); ++l) sf.push_back(pKF1->mvScaleFactors[l]);
+    olf_track_batch in;
+    std::memset(&in, 0, sizeof in);
+    in.kps = kps.data(); in.counts = counts; in.img_stride = 1; in.uright = ur.data(); in.Tcw = T;
+    in.fx = pKF1->fx; in.fy = pKF1->fy; in.cx = pKF1->cx; in.cy = pKF1->cy; in.mbf = pKF1->mbf;
+    std::vector<uint8_t> taken(nm, 0);
+    for (int left = nm; left > 0;) {                                 // one call per round of distinct idx1 (one round for a list as the search returns it)
+        std::vector<int32_t> row(cap, -1), who(cap, -1);
+        for (int m = 0; m < nm; ++m) {
+            const size_t i1 = vMatchedIndices[m].first;
+            if (taken[m] || i1 >= (size_t)cap) { if (!taken[m]) { taken[m] = 1; --left; } continue; }
+            if (who[i1] >= 0) continue;
+            who[i1] = m; row[i1] = vMatchedIndices[m].second < (size_t)cap ? (int32_t)vMatchedIndices[m].second : -1;
+            taken[m] = 1; --left;
+        }
+        int32_t nnew = 0, status = 0;
+        if (!c) olf_detail::check(olf_create_new_map_points(&in, cap, 2, depth.data(), pKF2->mb, sf.data(), (int)sf.size(), 1, pair, row.data(), bMonocular ? 1 : 0, x3D.data(),
+                                                            code.data(), &nnew, &status), "olf_create_new_map_points");
+        else olf_detail::check(olf_create_new_map_points_pairs(c, &in, 2, depth.data(), pKF2->mb, 1, pair, row.data(), bMonocular ? 1 : 0, x3D.data(), code.data(), &nnew),
+                               "olf_create_new_map_points_pairs");
+        for (int i = 0; i < cap; ++i) {
+            if (who[i] < 0) continue;
+            out.code[who[i]] = code[i];
+            for (int k = 0; k < 3; ++k) out.x3D[3 * (size_t)who[i] + k] = x3D[3 * (size_t)i + k];
+        }
+        out.nnew += nnew;
+    }
+    // (a skipped neighbour: every row is 0 and nnew is 0 although there were matches; the test itself is cheap to restate for the flag)
+    if (nm && !bMonocular) {
+        const auto O1 = pKF1->GetCameraCenter(), O2 = pKF2->GetCameraCenter();
+        double s = 0;
+        for (int k = 0; k < 3; ++k) { const float d = O2.template at<float>(k) - O1.template at<float>(k); s += (double)d * (double)d; }
+        out.skipped = (float)std::sqrt(s) < pKF2->mb;
+    }
 }
 
 // ---- Optimizer::PoseOptimizationWithLine (src/Optimizer.cc:604-697) over the reference's own types ----------------------------------------------------------

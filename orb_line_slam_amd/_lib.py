@@ -323,6 +323,15 @@ def lib():
         L.olf_tracked_map_points.argtypes = [P, C.POINTER(MapGraphC), P, P, C.c_int, P, C.c_int, C.c_int, P, P]
         L.olf_map_point_culling_dev.argtypes = [P, C.c_int] + [P] * 5 + [C.c_int64, C.c_int, P, P]
         L.olf_map_point_culling.argtypes = [P, C.c_int] + [P] * 5 + [C.c_int64, C.c_int, P]
+        L.olf_compute_f12_pairs_dev.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, C.c_int, P, P, P]
+        L.olf_compute_f12.argtypes = [P, P] + [C.c_float] * 4 + [P]
+        L.olf_create_new_map_points_batch_dev.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, P, C.c_float, C.c_int, P, P, C.c_int, P, P, P, P]
+        L.olf_create_new_map_points.argtypes = [C.POINTER(TrackBatchC), C.c_int, C.c_int, P, C.c_float, P, C.c_int, C.c_int, P, P, C.c_int, P, P, P, P]
+        L.olf_compute_f12_pairs.argtypes = [P, P, C.c_int] + [C.c_float] * 4 + [C.c_int, P, P]
+        L.olf_create_new_map_points_pairs.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, P, C.c_float, C.c_int, P, P, C.c_int, P, P, P]
+        L.olf_update_normal_and_depth_points.argtypes = [P, C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int] + [P] * 7
+        L.olf_update_normal_and_depth_dev.argtypes = [P, C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int] + [P] * 8
+        L.olf_update_normal_and_depth.argtypes = [C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int] + [P] * 5 + [C.c_int] + [P] * 4
         L.olf_pose_default_params.argtypes = [C.POINTER(PoseParamsC)]
         L.olf_pose_default_params.restype = None
         L.olf_pose_optimization_with_line_batch_dev.argtypes = [P, C.POINTER(PoseBatchC), C.c_int, C.POINTER(PoseParamsC), C.POINTER(PoseOutputsC), P]

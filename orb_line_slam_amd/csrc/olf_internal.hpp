@@ -46,7 +46,8 @@ void set_error(const std::string& s);
 //   SCRATCH_KNN    olf_match_bf_dev: the k-NN tables of launch_match_bf.
 //   SCRATCH_STAGE  the descriptor-sized host-pointer entries (api_host.cpp: olf_match_bf, olf_knn2, olf_match_candidates, olf_frame_grid,
 //                  olf_features_in_area, olf_hamming_matrix, olf_distinctive_descriptors; localmap_api.cpp: olf_update_local_map; connections_api.cpp: olf_update_connections; culling_api.cpp: olf_keyframe_culling,
-//                  olf_tracked_map_points, olf_map_point_culling; pose_api.cpp: olf_pose_optimization_with_line_frame, olf_discard_outliers_frame) and the olf_debug_*_sweep counters.  Every one of them ends in
+//                  olf_tracked_map_points, olf_map_point_culling; pose_api.cpp: olf_pose_optimization_with_line_frame, olf_discard_outliers_frame; newpoints_api.cpp: olf_compute_f12_pairs,
+//                  olf_create_new_map_points_pairs, olf_update_normal_and_depth_points) and the olf_debug_*_sweep counters.  Every one of them ends in
 //                  a synchronise on the context's stream.
 //   SCRATCH_BATCH  the batched matchers (olf_search_by_bow_batch_dev, olf_search_by_projection_batch_dev, olf_is_in_frustum_batch_dev,
 //                  olf_search_local_map_batch_dev, olf_search_for_triangulation_batch_dev, olf_fuse_search_batch_dev, olf_search_by_sim3_pairs_dev,

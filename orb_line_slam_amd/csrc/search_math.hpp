@@ -33,6 +33,14 @@ __host__ __device__ __forceinline__ void camera_centre(const float* Tcw, float* 
     }
 }
 
+// Frame::UnprojectStereo / KeyFrame::UnprojectStereo (src/Frame.cc:1073-1087, src/KeyFrame.cc:793-809) of a feature with z > 0: x = (u - cx) * z * invfx left
+// to right in float, then Rwc * x3Dc + Ow under C.12.  Twc: rows of mRwc | mOw, row-major with a row stride of 4
+__host__ __device__ __forceinline__ void unproject_stereo_point(float u, float v, float z, float cx, float cy, float invfx, float invfy, const float* Twc, float* out)
+{
+    const float x3Dc[3] = {(u - cx) * z * invfx, (v - cy) * z * invfy, z};
+    rot_apply(Twc, x3Dc, 1.0f, out);
+}
+
 // One endpoint of Frame::isInFrustum_l (src/Frame.cc:456-479, :480-503) -- the first half of Frame::isInFrustum (:394-412): mRcw * p + mtcw under C.12, the
 // depth gate, the projection and the CLOSED image bounds.  cam = fx, fy, cx, cy; bounds = mnMinX, mnMaxX, mnMinY, mnMaxY.  false: uv is not written.
 // (The point forms, olf_is_in_frustum and k_local_frustum, keep their own spelling of these six lines: they go on to use PcZ's reciprocal for

@@ -237,9 +237,7 @@ __global__ __launch_bounds__(256) void k_unproject_stereo(const olf_keypoint* __
     const float z = i < n ? depth[at] : 0.f;
     if (z > 0) {
         const olf_keypoint& kp = kps[(size_t)f * img_stride * cap + i];
-        const float u = kp.x, v = kp.y;
-        const float x3Dc[3] = {(u - cx) * z * invfx, (v - cy) * z * invfy, z};
-        rot_apply(Twc + 16 * (size_t)f, x3Dc, 1.0f, o);
+        unproject_stereo_point(kp.x, kp.y, z, cx, cy, invfx, invfy, Twc + 16 * (size_t)f, o);
     }
     world[3 * at] = o[0]; world[3 * at + 1] = o[1]; world[3 * at + 2] = o[2];
 }
