@@ -1090,6 +1090,79 @@ int olf_create_new_map_points_pairs(olf_ctx* ctx, const olf_track_batch* in, int
 int olf_update_normal_and_depth_points(olf_ctx* ctx, const olf_map_graph* g, const olf_cull_view* v, int n_points, const int32_t* points, const float* mp_world,
                                        const int32_t* mp_ref_kf, const float* kf_Ow, float* normal, float* maxd, float* mind);
 
+/* ---- Sim3Solver's RANSAC for a list of key-frame pairs on the device (csrc/sim3solver_batch.hip) ------------------------------------------------------
+ * Sim3Solver (src/Sim3Solver.cc, include/Sim3Solver.h) as LoopClosing::ComputeSim3 drives it per candidate (src/LoopClosing.cc:280-307): the constructor's
+ * correspondences, SetRansacParameters(probability, min_inliers, max_iterations) and one iterate(n_iterations, ...) per call, for n_pairs pairs of the
+ * n_frames key frames of a batch.  It stands between olf_search_by_bow_pairs_dev (form OLF_BOW_KF_KF), whose rows it reads, and
+ * olf_search_by_sim3_pairs_dev, which takes best_s / best_R / best_t as its d_s12 / d_R12 / d_t12 without a copy; olf_sim3_filter_matches_dev does
+ * :319-324 between them.  Optimizer::OptimizeSim3 (:332) stays on the host.  Results equal olf_sim3_solver pair by pair, bit for bit, and do not depend
+ * on scheduling, on how the kernel chunks a window or on a pair's position in the list.
+ * `in`: kps (octave), counts, img_stride, Tcw, mp_world, mp_valid (NULL: every feature holds a point) and fx, fy, cx, cy are read (frame j = image
+ * j * img_stride; a count beyond the capacity is read as the capacity); mvLevelSigma2 is the context's.  d_mp_bad [n_frames][capacity] (or NULL: none is
+ * bad): isBad() of the point a feature holds.  d_pairs [n_pairs][2] = (kf1, kf2).  d_matches12 [n_pairs][capacity], read only: exactly the row
+ * olf_search_by_bow_pairs_dev writes or olf_search_by_sim3_pairs_dev has extended; value v at i1 < N1 is a correspondence iff 0 <= v < N2 (-1, -2 and
+ * >= N2 are all "none"), both features hold a point and neither point is bad; indexKF1 = i1, indexKF2 = v.  Correspondences are kept in ascending i1.
+ * The gates are integers: (size_t)(9.210 * sigmaSquare) (level 0: 9, level 1 at 1.2: 13), compared as float.  A correspondence either of whose octaves
+ * lies outside the context's levels is left out and sets bit 256 of the context's status word.
+ * olf_sim3_ransac: fix_scale (bFixScale), probability in (0, 1), min_inliers >= 3, max_iterations >= 1 (the reference: 0.99, 20, 300), n_iterations >= 0:
+ * the window of this call (the reference: 5; max_iterations gives find()).  The iteration cap is a function of the number of correspondences alone; the
+ * call computes it for every N in [0, capacity] on the host with the host's libm (csrc/sim3solver_terms.hpp: s3_iteration_cap) and the kernel looks it up.
+ * d_draws [n_pairs][max_iterations][3] (uint32): the raw rand() values below 2^31 of every iteration, indexed by ABSOLUTE iteration, so a resumed call
+ * reads on where the last one stopped (convention C.20; bit 31 of a value is ignored); draw k picks position (int)(((double)r / 2147483648.0) * (N - k)) of what is still available.
+ * olf_sim3_solver_io, device pointers, one element or row per pair.  In and out -- the solver's carried state, all zero for a new solver:
+ * iterations_done (mnIterations), best_inliers (mnBestInliers), best_s, best_R [9], best_t [3], best_T12 [16] (row-major).  An iteration with
+ * n >= best_inliers replaces them; the first that also has n > min_inliers is accepted and ends the call (:183-200).  Out: accepted (the returned Scm is
+ * not empty), no_more (bNoMore), n_inliers (0 unless accepted), inliers [n_pairs][capacity] (uint8, indexed by i1; positions below N1 are written, all 0
+ * unless accepted; positions from N1 on are left as they are), n_correspondences (N), and counts [n_pairs][max_iterations] (may be NULL): the inlier
+ * count of every iteration this call evaluated at its absolute index, the others untouched.  N < min_inliers: no_more = 1 and the state is untouched.
+ * Arithmetic (csrc/sim3solver_terms.hpp, one text for this entry and its host form; C.4, C.12, C.17, C.20 to C.22 of DESIGN.md).
+ * A pair whose index lies outside [0, n_frames), or with kf1 == kf2, gets n_inliers = -1, nothing else of it is written, and bit 2048 is set.  Errors,
+ * before any launch: a NULL required pointer, a negative count, min_inliers < 3, max_iterations < 1, n_iterations < 0 or probability outside (0, 1):
+ * OLF_ERR_INVALID.  n_pairs == 0 writes nothing.  Does not synchronise; runs on `stream`.  Nothing is read or written out of bounds.
+ * Scratch: 4 bytes per feature of the capacity and, where 52 bytes per feature of the capacity exceed the LDS a workgroup takes, that much per resident
+ * workgroup (at most 1024). */
+typedef struct olf_sim3_ransac {
+    int32_t fix_scale;
+    double  probability;
+    int32_t min_inliers, max_iterations, n_iterations;
+} olf_sim3_ransac;
+typedef struct olf_sim3_solver_io {
+    int32_t* iterations_done;    /* [n_pairs]      in / out */
+    int32_t* best_inliers;       /* [n_pairs]      in / out */
+    float*   best_s;             /* [n_pairs]      in / out: d_s12 of olf_search_by_sim3_pairs_dev */
+    float*   best_R;             /* [n_pairs][9]   in / out: d_R12 */
+    float*   best_t;             /* [n_pairs][3]   in / out: d_t12 */
+    float*   best_T12;           /* [n_pairs][16]  in / out */
+    int32_t* accepted;           /* [n_pairs] */
+    int32_t* no_more;            /* [n_pairs] */
+    int32_t* n_inliers;          /* [n_pairs] */
+    uint8_t* inliers;            /* [n_pairs][capacity] */
+    int32_t* n_correspondences;  /* [n_pairs] */
+    int32_t* counts;             /* [n_pairs][max_iterations], or NULL */
+} olf_sim3_solver_io;
+int olf_sim3_solver_pairs_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const uint8_t* d_mp_bad, int n_pairs, const int32_t* d_pairs,
+                              const int32_t* d_matches12, const olf_sim3_ransac* ransac, const uint32_t* d_draws, const olf_sim3_solver_io* io, void* stream);
+/* LoopClosing.cc:319-324 for every pair: d_out[p][i] = d_matches12[p][i] where d_inliers[p][i] is set, -1 elsewhere, for i in [0, capacity).  d_out may be
+ * d_matches12 itself.  d_n_inliers (or NULL) [n_pairs]: a pair with a negative value (a refused pair) keeps its row of d_out.  Does not synchronise. */
+int olf_sim3_filter_matches_dev(olf_ctx* ctx, int n_pairs, const int32_t* d_matches12, const uint8_t* d_inliers, const int32_t* d_n_inliers, int32_t* d_out,
+                                void* stream);
+/* the host form: ONE pair (kf1, kf2), host pointers in `in` and everywhere else, no context and no device, the literal loop of Sim3Solver::iterate.
+ * capacity: the row length of the per-frame planes; scale_factors [n_levels] = mvScaleFactors; matches12 [capacity], draws [max_iterations][3]; every
+ * pointer of io names this pair's element or row; *status receives the bits 256 / 2048. */
+int olf_sim3_solver(const olf_track_batch* in, int capacity, int n_frames, const uint8_t* mp_bad, const float* scale_factors, int n_levels, int kf1, int kf2,
+                    const int32_t* matches12, const olf_sim3_ransac* ransac, const uint32_t* draws, const olf_sim3_solver_io* io, int32_t* status);
+/* olf_sim3_solver_pairs_dev from host pointers ON THE DEVICE (csrc/sim3solver_api.cpp): the arrays are staged (the in / out state and the outputs are
+ * uploaded first), the same kernel runs on the context's stream, state and outputs come back; synchronises.  A set status bit makes the call return
+ * OLF_ERR_CAPACITY with the bit's text, the outputs complete. */
+int olf_sim3_solver_pairs(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const uint8_t* mp_bad, int n_pairs, const int32_t* pairs,
+                          const int32_t* matches12, const olf_sim3_ransac* ransac, const uint32_t* draws, const olf_sim3_solver_io* io);
+/* tests: the LDS a workgroup of the solver may take for its correspondences (bytes; above it they live in context scratch; <= 0 restores the default),
+ * and the integer gate of a level's scale factor */
+int olf_debug_sim3_solver_lds_limit(int bytes);
+int olf_debug_sim3_solver_gate(float scale_factor, uint64_t* gate);
+/* tests: the iteration cap the solver's table holds for N correspondences (csrc/sim3solver_terms.hpp: s3_iteration_cap) */
+int olf_debug_sim3_solver_cap(int N, double probability, int min_inliers, int max_iterations, int32_t* cap);
+
 /* measurement: rate of a plain 16-byte-per-thread device copy kernel over `bytes` (read + written bytes per second): the practical HBM
  * ceiling bench.py reports next to the specification's 8 TB/s */
 int olf_debug_copy_bandwidth(olf_ctx* ctx, size_t bytes, int reps, double* gbytes_per_s);

@@ -29,6 +29,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <list>
 #include <map>
 #include <set>
@@ -1274,6 +1275,192 @@ bool PoseOptimizationWithLine(olf_ctx* c, FrameT* pFrame, const olf_pose_params*
     pFrame->n_inliers_pt = inl[0]; pFrame->n_inliers_ls = inl[1]; pFrame->n_inliers = inl[0] + inl[1];
     if (status) *status = st;
     return true;
+}
+
+// ---- Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc) over the reference's own types ---------------------------------------------------------------------
+// The reference's members with its signatures: the constructor (pKF1, pKF2, vpMatched12, bFixScale), SetRansacParameters, iterate, find and the three
+// GetEstimated*.  It runs over the host form olf_sim3_solver, so a single solver needs no device.  The constructor keeps the correspondences as :62-103 does,
+// with the real pMP->GetIndexInKeyFrame(pKF) values; the C entry's per-feature model (indexKF1 = i1) is met by laying the kept correspondences out as the
+// features 0 .. N - 1 of two frames of their own.  Reads GetMapPointMatches(), GetPose(), mvKeysUn, mvScaleFactors (mvLevelSigma2 = their squares) and fx,
+// fy, cx, cy of the key frames, isBad(), GetWorldPos() and GetIndexInKeyFrame() of the points.  The random stream: the reference draws from
+// the global rand() iteration by iteration; here SetRansacParameters draws all max_iterations x 3 values with rand() at once, and an iteration reads its own.
+template <class KeyFrameT, class MapPointT>
+class Sim3SolverOf {
+public:
+    typedef decltype(std::declval<KeyFrameT>().GetPose()) MatT;
+
+    Sim3SolverOf(KeyFrameT* pKF1, KeyFrameT* pKF2, const std::vector<MapPointT*>& vpMatched12, const bool bFixScale = true)
+        : mpKF1(pKF1), mpKF2(pKF2), mN1((int)vpMatched12.size()), mbFixScale(bFixScale)
+    {
+        const std::vector<MapPointT*> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+        std::vector<float> w1, w2;
+        for (int i1 = 0; i1 < mN1; i1++) {
+            if (!vpMatched12[i1]) continue;
+            MapPointT* pMP1 = i1 < (int)vpKeyFrameMP1.size() ? vpKeyFrameMP1[i1] : nullptr;
+            MapPointT* pMP2 = vpMatched12[i1];
+            if (!pMP1) continue;
+            if (pMP1->isBad() || pMP2->isBad()) continue;
+            const int indexKF1 = pMP1->GetIndexInKeyFrame(pKF1), indexKF2 = pMP2->GetIndexInKeyFrame(pKF2);
+            if (indexKF1 < 0 || indexKF2 < 0) continue;
+            olf_keypoint k1, k2;
+            std::memcpy(&k1, olf_detail::keypoints(pKF1->mvKeysUn) + indexKF1, sizeof k1);
+            std::memcpy(&k2, olf_detail::keypoints(pKF2->mvKeysUn) + indexKF2, sizeof k2);
+            mKeys1.push_back(k1); mKeys2.push_back(k2);
+            const auto X1 = pMP1->GetWorldPos(), X2 = pMP2->GetWorldPos();
+            for (int k = 0; k < 3; ++k) { w1.push_back(X1.template at<float>(k)); w2.push_back(X2.template at<float>(k)); }
+            mvnIndices1.push_back(i1);
+        }
+        N = (int)mvnIndices1.size();
+        mCap = std::max(N, 1);
+        mKeys.assign(2 * (size_t)mCap, olf_keypoint());
+        mWorld.assign(6 * (size_t)mCap, 0.0f);
+        mRow.assign(mCap, -1);
+        for (int q = 0; q < N; ++q) {
+            mKeys[q] = mKeys1[q]; mKeys[(size_t)mCap + q] = mKeys2[q]; mRow[q] = q;
+            for (int k = 0; k < 3; ++k) { mWorld[3 * (size_t)q + k] = w1[3 * (size_t)q + k]; mWorld[3 * ((size_t)mCap + q) + k] = w2[3 * (size_t)q + k]; }
+        }
+        olf_detail::mat4(pKF1->GetPose(), mT);
+        olf_detail::mat4(pKF2->GetPose(), mT + 16);
+        for (size_t l = 0; l < pKF1->mvScaleFactors.size(); ++l) mSf.push_back(pKF1->mvScaleFactors[l]);
+        mInliers.assign(mCap, 0);
+        std::memset(mBestR, 0, sizeof mBestR); std::memset(mBestt, 0, sizeof mBestt); std::memset(mBestT12, 0, sizeof mBestT12);
+        SetRansacParameters();
+    }
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300)
+    {
+        mRansac.fix_scale = mbFixScale ? 1 : 0; mRansac.probability = probability; mRansac.min_inliers = minInliers; mRansac.max_iterations = maxIterations;
+        mRansac.n_iterations = 0;
+        mnIterations = 0;                                            // (:137; mnBestInliers is the constructor's, as in the reference)
+        mDraws.resize(3 * (size_t)std::max(maxIterations, 0));
+        for (size_t k = 0; k < mDraws.size(); ++k) mDraws[k] = (uint32_t)rand() & 0x7fffffffu;
+    }
+
+    MatT iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers)
+    {
+        olf_track_batch in;
+        const int32_t counts[2] = {N, N};
+        olf_fill_batch(in, counts);
+        mRansac.n_iterations = std::max(nIterations, 0);
+        int32_t status = 0;
+        const olf_sim3_solver_io io = olf_io();
+        olf_detail::check(olf_sim3_solver(&in, mCap, 2, nullptr, mSf.data(), (int)mSf.size(), 0, 1, mRow.data(), &mRansac, mDraws.data(), &io, &status), "olf_sim3_solver");
+        return olf_results(bNoMore, vbInliers, nInliers);
+    }
+
+    MatT find(std::vector<bool>& vbInliers12, int& nInliers)
+    {
+        bool bFlag;
+        return iterate(mRansac.max_iterations, bFlag, vbInliers12, nInliers);
+    }
+
+    MatT GetEstimatedRotation()
+    {
+        MatT R = mpKF1->GetRotation();                               // (a clone: a 3 x 3 CV_32F matrix to fill)
+        for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) R.template at<float>(r, k) = mBestR[3 * r + k];
+        return R;
+    }
+    MatT GetEstimatedTranslation()
+    {
+        MatT t = mpKF1->GetTranslation();                            // (a clone: 3 x 1 CV_32F)
+        for (int r = 0; r < 3; ++r) t.template at<float>(r) = mBestt[r];
+        return t;
+    }
+    float GetEstimatedScale() { return mBests; }
+
+    // ---- what the batched free function below reads and writes (olf_ prefix: not members of the reference's class)
+    void olf_fill_batch(olf_track_batch& in, const int32_t* counts) const
+    {
+        std::memset(&in, 0, sizeof in);
+        in.kps = mKeys.data(); in.counts = counts; in.img_stride = 1; in.Tcw = mT; in.mp_world = mWorld.data();
+        in.fx = mpKF1->fx; in.fy = mpKF1->fy; in.cx = mpKF1->cx; in.cy = mpKF1->cy;
+    }
+    olf_sim3_solver_io olf_io()
+    {
+        const olf_sim3_solver_io io = {&mnIterations, &mnBestInliers, &mBests, mBestR, mBestt, mBestT12, &mAccepted, &mNoMore, &mnInliers, mInliers.data(), &mNCorr, nullptr};
+        return io;
+    }
+    MatT olf_results(bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers)
+    {
+        bNoMore = mNoMore != 0;
+        vbInliers = std::vector<bool>(mN1, false);
+        nInliers = mAccepted ? mnInliers : 0;
+        if (!mAccepted) return MatT();
+        for (int q = 0; q < N; ++q) if (mInliers[q]) vbInliers[mvnIndices1[q]] = true;
+        MatT T = mpKF1->GetPose();                                   // (a clone: 4 x 4 CV_32F)
+        for (int r = 0; r < 4; ++r) for (int k = 0; k < 4; ++k) T.template at<float>(r, k) = mBestT12[4 * r + k];
+        return T;
+    }
+
+    KeyFrameT *mpKF1, *mpKF2;
+    int mN1, N = 0, mCap = 1;
+    bool mbFixScale;
+    olf_sim3_ransac mRansac;
+    std::vector<int> mvnIndices1;
+    std::vector<olf_keypoint> mKeys1, mKeys2, mKeys;                 // the kept correspondences' key points; both frames at the row length mCap
+    std::vector<float> mWorld, mSf;
+    std::vector<int32_t> mRow;
+    std::vector<uint32_t> mDraws;
+    std::vector<uint8_t> mInliers;
+    float mT[32];
+    int32_t mnIterations = 0, mnBestInliers = 0, mAccepted = 0, mNoMore = 0, mnInliers = 0, mNCorr = 0;
+    float mBests = 0.0f, mBestR[9], mBestt[3], mBestT12[16];
+};
+
+// One round of LoopClosing::ComputeSim3's loop (src/LoopClosing.cc:286-307) for a vector of candidates: iterate(nIterations, ...) of every solver in one call
+// of the device entry (olf_sim3_solver_pairs through context c, whose capacity must hold every solver's correspondences and whose level table must be the
+// key frames').  The solvers share their RANSAC parameters, calibration and levels (one ComputeSim3 sets them alike).  Every solver's state advances as its own iterate would
+// advance it; vScm[i] is empty unless solver i accepted.
+template <class KeyFrameT, class MapPointT>
+void Sim3SolversIterate(olf_ctx* c, const std::vector<Sim3SolverOf<KeyFrameT, MapPointT>*>& vpSolvers, int nIterations, std::vector<bool>& vbNoMore,
+                        std::vector<std::vector<bool> >& vvbInliers, std::vector<int>& vnInliers,
+                        std::vector<typename Sim3SolverOf<KeyFrameT, MapPointT>::MatT>& vScm)
+{
+    const size_t n = vpSolvers.size();
+    vbNoMore.assign(n, false); vvbInliers.assign(n, std::vector<bool>()); vnInliers.assign(n, 0); vScm.assign(n, typename Sim3SolverOf<KeyFrameT, MapPointT>::MatT());
+    if (!n) return;
+    const size_t cap = (size_t)olf_orb_capacity(c), mi = (size_t)vpSolvers[0]->mRansac.max_iterations;
+    std::vector<olf_keypoint> kps(2 * n * cap);
+    std::vector<float> world(6 * n * cap, 0.0f), T(32 * n), s(n), R(9 * n), t(3 * n), T12(16 * n);
+    std::vector<int32_t> counts(2 * n), pairs(2 * n), rows(n * cap, -1), done(n), best(n), acc(n), nomore(n), ninl(n), ncorr(n);
+    std::vector<uint32_t> draws(3 * n * mi);
+    std::vector<uint8_t> inl(n * cap, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const auto& S = *vpSolvers[i];
+        const olf_sim3_ransac &a = S.mRansac, &b = vpSolvers[0]->mRansac;
+        if ((size_t)S.N > cap) throw std::runtime_error("Sim3SolversIterate: the context's capacity does not hold a solver's correspondences");
+        if (a.fix_scale != b.fix_scale || a.probability != b.probability || a.min_inliers != b.min_inliers || a.max_iterations != b.max_iterations)
+            throw std::runtime_error("Sim3SolversIterate: the solvers differ in their RANSAC parameters");
+        for (int f = 0; f < 2; ++f) {
+            counts[2 * i + f] = S.N; pairs[2 * i + f] = (int32_t)(2 * i + f);
+            std::memcpy(&T[16 * (2 * i + f)], S.mT + 16 * f, 64);
+            for (int q = 0; q < S.N; ++q) {
+                kps[(2 * i + f) * cap + q] = S.mKeys[(size_t)f * S.mCap + q];
+                for (int k = 0; k < 3; ++k) world[3 * ((2 * i + f) * cap + q) + k] = S.mWorld[3 * ((size_t)f * S.mCap + q) + k];
+            }
+        }
+        for (int q = 0; q < S.N; ++q) rows[i * cap + q] = q;
+        std::memcpy(&draws[3 * i * mi], S.mDraws.data(), 12 * mi);
+        done[i] = S.mnIterations; best[i] = S.mnBestInliers; s[i] = S.mBests;
+        std::memcpy(&R[9 * i], S.mBestR, 36); std::memcpy(&t[3 * i], S.mBestt, 12); std::memcpy(&T12[16 * i], S.mBestT12, 64);
+    }
+    olf_track_batch in;
+    vpSolvers[0]->olf_fill_batch(in, counts.data());
+    in.kps = kps.data(); in.Tcw = T.data(); in.mp_world = world.data();
+    olf_sim3_ransac rn = vpSolvers[0]->mRansac;
+    rn.n_iterations = std::max(nIterations, 0);
+    const olf_sim3_solver_io io = {done.data(), best.data(), s.data(), R.data(), t.data(), T12.data(), acc.data(), nomore.data(), ninl.data(), inl.data(), ncorr.data(), nullptr};
+    olf_detail::check(olf_sim3_solver_pairs(c, &in, (int)(2 * n), nullptr, (int)n, pairs.data(), rows.data(), &rn, draws.data(), &io), "olf_sim3_solver_pairs");
+    for (size_t i = 0; i < n; ++i) {
+        auto& S = *vpSolvers[i];
+        S.mnIterations = done[i]; S.mnBestInliers = best[i]; S.mBests = s[i]; S.mAccepted = acc[i]; S.mNoMore = nomore[i]; S.mnInliers = ninl[i]; S.mNCorr = ncorr[i];
+        std::memcpy(S.mBestR, &R[9 * i], 36); std::memcpy(S.mBestt, &t[3 * i], 12); std::memcpy(S.mBestT12, &T12[16 * i], 64);
+        for (int q = 0; q < S.N; ++q) S.mInliers[q] = inl[i * cap + q];
+        bool nm;
+        int ni;
+        vScm[i] = S.olf_results(nm, vvbInliers[i], ni);
+        vbNoMore[i] = nm; vnInliers[i] = ni;
+    }
 }
 
 }  // namespace ORB_SLAM2

@@ -73,6 +73,17 @@ class TrackBatchC(C.Structure):
                 [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "mbf", "minX", "maxX", "minY", "maxY")])
 
 
+class Sim3RansacC(C.Structure):
+    """olf_sim3_ransac (include/orbline.h): SetRansacParameters and the window of one Sim3Solver::iterate"""
+    _fields_ = [("fix_scale", C.c_int32), ("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("n_iterations", C.c_int32)]
+
+
+class Sim3SolverIoC(C.Structure):
+    """olf_sim3_solver_io (include/orbline.h): the carried state and the outputs of the solvers of a list of pairs"""
+    _fields_ = [(n, C.c_void_p) for n in ("iterations_done", "best_inliers", "best_s", "best_R", "best_t", "best_T12", "accepted", "no_more", "n_inliers",
+                                          "inliers", "n_correspondences", "counts")]
+
+
 class LocalMapC(C.Structure):
     """olf_local_map (include/orbline.h): the local map of a batch as device arrays, and optionally each frame's list of indices into it"""
     _fields_ = ([(n, C.c_void_p) for n in ("world", "normal", "maxd", "mind", "desc", "obs", "bad")] + [("n_mp", C.c_int32)] +
@@ -330,6 +341,14 @@ def lib():
         L.olf_compute_f12_pairs.argtypes = [P, P, C.c_int] + [C.c_float] * 4 + [C.c_int, P, P]
         L.olf_create_new_map_points_pairs.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, P, C.c_float, C.c_int, P, P, C.c_int, P, P, P]
         L.olf_update_normal_and_depth_points.argtypes = [P, C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int] + [P] * 7
+        L.olf_sim3_solver_pairs_dev.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, P, C.c_int, P, P, C.POINTER(Sim3RansacC), P, C.POINTER(Sim3SolverIoC), P]
+        L.olf_sim3_filter_matches_dev.argtypes = [P, C.c_int, P, P, P, P, P]
+        L.olf_sim3_solver.argtypes = [C.POINTER(TrackBatchC), C.c_int, C.c_int, P, P, C.c_int, C.c_int, C.c_int, P, C.POINTER(Sim3RansacC), P,
+                                      C.POINTER(Sim3SolverIoC), P]
+        L.olf_sim3_solver_pairs.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, P, C.c_int, P, P, C.POINTER(Sim3RansacC), P, C.POINTER(Sim3SolverIoC)]
+        L.olf_debug_sim3_solver_lds_limit.argtypes = [C.c_int]
+        L.olf_debug_sim3_solver_gate.argtypes = [C.c_float, P]
+        L.olf_debug_sim3_solver_cap.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, P]
         L.olf_update_normal_and_depth_dev.argtypes = [P, C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int] + [P] * 8
         L.olf_update_normal_and_depth.argtypes = [C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int] + [P] * 5 + [C.c_int] + [P] * 4
         L.olf_pose_default_params.argtypes = [C.POINTER(PoseParamsC)]

@@ -5,6 +5,7 @@
 
 namespace olf {
 int launch_copy16(const void* src, void* dst, size_t bytes, hipStream_t s);
+void sim3_solver_lds_limit(int bytes);      // sim3solver_batch.hip
 }
 
 using namespace olf;
@@ -27,6 +28,12 @@ int olf_orb_pyramid_level(olf_ctx* c, int image, int level, int blurred, uint8_t
     const uint8_t* src = (blurred ? c->ob.blur : c->ob.pyr) + (size_t)image * c->orb.geom.pyrBytes + L.offset;
     OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
     OLF_HIP_CHECK(hipMemcpy2D(dst, L.w, src, L.pitch, L.w, L.h, hipMemcpyDeviceToHost));
+    return OLF_OK;
+}
+
+int olf_debug_sim3_solver_lds_limit(int bytes)
+{
+    sim3_solver_lds_limit(bytes);
     return OLF_OK;
 }
 

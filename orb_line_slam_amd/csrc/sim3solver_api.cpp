@@ -1,0 +1,56 @@
+// sim3solver_api.cpp -- the host-pointer form of sim3solver_batch.hip that runs on the device: olf_sim3_solver_pairs.  It stages the arrays, the carried
+// state and the outputs in one carve -- the outputs are uploaded first, so what the device leaves untouched (a refused pair, a row's tail, counts of
+// iterations not evaluated) comes back as it went in -- and runs the same kernel.  (The form that computes on the host is sim3solver_host.cpp.)
+#include "staging.hpp"
+#include "../../include/orbline.h"
+
+using namespace olf;
+
+extern "C" int olf_sim3_solver_pairs(olf_ctx* c, const olf_track_batch* in, int n_frames, const uint8_t* mp_bad, int n_pairs, const int32_t* pairs,
+                                     const int32_t* matches12, const olf_sim3_ransac* R, const uint32_t* draws, const olf_sim3_solver_io* io)
+{
+    const char* who = "olf_sim3_solver_pairs";
+    bool ok = c && in && R && io && n_frames >= 0 && n_pairs >= 0;
+    ok = ok && R->min_inliers >= 3 && R->max_iterations >= 1 && R->n_iterations >= 0 && R->probability > 0.0 && R->probability < 1.0;
+    ok = ok && (!n_pairs || (pairs && matches12 && draws && io->iterations_done && io->best_inliers && io->best_s && io->best_R && io->best_t && io->best_T12 &&
+                             io->accepted && io->no_more && io->n_inliers && io->inliers && io->n_correspondences));
+    ok = ok && (!n_frames || (in->kps && in->counts && in->img_stride >= 1 && in->Tcw && in->mp_world));
+    if (!ok) { set_error(std::string(who) + ": bad argument"); return OLF_ERR_INVALID; }
+    if (n_pairs == 0) return OLF_OK;
+    const size_t cap = (size_t)olf_orb_capacity(c), nf = (size_t)n_frames, ni = nf * (size_t)in->img_stride, np = (size_t)n_pairs, mi = (size_t)R->max_iterations;
+    olf_keypoint* d_kps;
+    int32_t *d_counts, *d_pairs, *d_m12, *d_done, *d_best, *d_acc, *d_nomore, *d_ninl, *d_ncorr, *d_cnt = nullptr;
+    float *d_T, *d_world, *d_s, *d_R, *d_t, *d_T12;
+    uint8_t *d_valid = nullptr, *d_bad = nullptr, *d_inl;
+    uint32_t* d_draws;
+    HostCall h(c, who);
+    h.add(&d_kps, ni * cap + 1); h.add(&d_counts, ni + 1); h.add(&d_T, 16 * nf + 1); h.add(&d_world, 3 * nf * cap + 1);
+    h.add(&d_pairs, 2 * np); h.add(&d_m12, np * cap); h.add(&d_draws, 3 * np * mi);
+    h.add(&d_done, np); h.add(&d_best, np); h.add(&d_s, np); h.add(&d_R, 9 * np); h.add(&d_t, 3 * np); h.add(&d_T12, 16 * np);
+    h.add(&d_acc, np); h.add(&d_nomore, np); h.add(&d_ninl, np); h.add(&d_ncorr, np);
+    if (io->counts) h.add(&d_cnt, np * mi);
+    h.add(&d_inl, np * cap);
+    if (in->mp_valid) h.add(&d_valid, nf * cap + 1);
+    if (mp_bad) h.add(&d_bad, nf * cap + 1);
+    OLF_TRY(h.bind(SCRATCH_STAGE));
+    OLF_TRY(h.up(d_kps, in->kps, ni * cap * sizeof(olf_keypoint))); OLF_TRY(h.up(d_counts, in->counts, ni * 4)); OLF_TRY(h.up(d_T, in->Tcw, 64 * nf));
+    OLF_TRY(h.up(d_world, in->mp_world, 12 * nf * cap)); OLF_TRY(h.up(d_pairs, pairs, 8 * np)); OLF_TRY(h.up(d_m12, matches12, 4 * np * cap));
+    OLF_TRY(h.up(d_draws, draws, 12 * np * mi));
+    OLF_TRY(h.up(d_done, io->iterations_done, 4 * np)); OLF_TRY(h.up(d_best, io->best_inliers, 4 * np)); OLF_TRY(h.up(d_s, io->best_s, 4 * np));
+    OLF_TRY(h.up(d_R, io->best_R, 36 * np)); OLF_TRY(h.up(d_t, io->best_t, 12 * np)); OLF_TRY(h.up(d_T12, io->best_T12, 64 * np));
+    OLF_TRY(h.up(d_acc, io->accepted, 4 * np)); OLF_TRY(h.up(d_nomore, io->no_more, 4 * np)); OLF_TRY(h.up(d_ninl, io->n_inliers, 4 * np));
+    OLF_TRY(h.up(d_ncorr, io->n_correspondences, 4 * np)); OLF_TRY(h.up(d_inl, io->inliers, np * cap));
+    if (d_cnt) OLF_TRY(h.up(d_cnt, io->counts, 4 * np * mi));
+    if (d_valid) OLF_TRY(h.up(d_valid, in->mp_valid, nf * cap));
+    if (d_bad) OLF_TRY(h.up(d_bad, mp_bad, nf * cap));
+    olf_track_batch d = *in;
+    d.kps = d_kps; d.counts = d_counts; d.Tcw = d_T; d.mp_world = d_world; d.mp_valid = d_valid;
+    const olf_sim3_solver_io dio = {d_done, d_best, d_s, d_R, d_t, d_T12, d_acc, d_nomore, d_ninl, d_inl, d_ncorr, d_cnt};
+    OLF_TRY(olf_sim3_solver_pairs_dev(c, &d, n_frames, d_bad, n_pairs, d_pairs, d_m12, R, d_draws, &dio, h.stream()));
+    OLF_TRY(h.down(io->iterations_done, d_done, 4 * np)); OLF_TRY(h.down(io->best_inliers, d_best, 4 * np)); OLF_TRY(h.down(io->best_s, d_s, 4 * np));
+    OLF_TRY(h.down(io->best_R, d_R, 36 * np)); OLF_TRY(h.down(io->best_t, d_t, 12 * np)); OLF_TRY(h.down(io->best_T12, d_T12, 64 * np));
+    OLF_TRY(h.down(io->accepted, d_acc, 4 * np)); OLF_TRY(h.down(io->no_more, d_nomore, 4 * np)); OLF_TRY(h.down(io->n_inliers, d_ninl, 4 * np));
+    OLF_TRY(h.down(io->n_correspondences, d_ncorr, 4 * np)); OLF_TRY(h.down(io->inliers, d_inl, np * cap));
+    if (d_cnt) OLF_TRY(h.down(io->counts, d_cnt, 4 * np * mi));
+    return h.finish_status();
+}
