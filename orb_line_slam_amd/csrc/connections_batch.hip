@@ -7,18 +7,17 @@
 //   k_conn_scan   the two per-key-frame counts into the two offset arrays; a total beyond its capacity raises STATUS_CONNECTIONS_LIST
 //   k_conn_fill   the table again: KFcounter by an ordered compaction over ascending index, the key frames at or above th (or the one fallback pair) into
 //                 LDS as 64-bit keys (weight, index), sorted descending (conn_sort), to their place
-// A weight is bounded by the length of a slot row only, so a key is 64 bits: the weight never shares a word with the index.
-// Scratch between the passes: 4 bytes per (listed key frame, key frame of the graph), the vote tables.
+// The slot walk, the compaction step, the pKFmax key and the listed key frame are map_kernels.hpp's ("What the map-side kernels share").
+// A weight is bounded by the length of a slot row only, so a sort key is 64 bits.  Scratch between the passes: 4 bytes per (listed key frame, key frame).
 #include <algorithm>
 #include "batch_frames.hpp"
-#include "offset_scan.hpp"
-#include "staging.hpp"
+#include "map_kernels.hpp"
+#include "staging.hpp"      // Carve
 
 namespace olf {
 
 constexpr int CN_THREADS = 256, CN_WAVES = CN_THREADS / 64;
-constexpr int CN_PER = 4, CN_CHUNK = CN_THREADS * CN_PER;      // slots per thread and per chunk of the vote walk
-constexpr int CN_OBS = 4;                                      // observations of a point in flight per thread
+constexpr int CN_CHUNK = CN_THREADS * SLOT_PER;                // slots per chunk of the vote walk
 constexpr int CN_SORT_MAX = OLF_LOCALMAP_MAX_KF;               // keys a workgroup sorts: 64 KB of the CU's 160 KB of LDS, two workgroups per CU
 
 struct ConnArgs {
@@ -71,8 +70,8 @@ __global__ __launch_bounds__(CN_THREADS) void k_conn_count(ConnArgs A, int* __re
     __shared__ int s_counted, s_strong;
     const olf_map_graph& g = A.g;
     const int j = blockIdx.x, tid = threadIdx.x, n_kf = g.n_kf;
-    const int kf = A.kf_list ? A.kf_list[j] : j;
-    if ((unsigned)kf >= (unsigned)n_kf) {                            // (the whole workgroup: kf is uniform)
+    int kf;
+    if (!listed_kf(A.kf_list, j, n_kf, kf)) {                        // (the whole workgroup: kf is uniform)
         if (tid == 0) {
             atomicOr(status, STATUS_KF_INDEX);
             A.n_counted[j] = 0; A.kf_max[j] = -1; A.w_max[j] = 0; A.conn_offsets[j + 1] = 0; A.covis_offsets[j + 1] = 0;
@@ -83,29 +82,21 @@ __global__ __launch_bounds__(CN_THREADS) void k_conn_count(ConnArgs A, int* __re
     if (tid == 0) { s_best = 0; s_counted = 0; s_strong = 0; }
     __syncthreads();
 
-    // ---- the votes, :461-479: CN_PER slots per thread, each load coalesced and all in flight together, then each point's observations ----
+    // ---- the votes, :461-479: the slots by chunks (SlotChunk), then each point's observations ----
     int b, e;
-    lm_row(g.kf_mp_offsets, n_kf, kf, b, e);
+    csr_row(g.kf_mp_offsets, n_kf, kf, b, e);
     const int obs_total = max(g.mp_obs_offsets[g.n_mp], 0);
     for (int c0 = b; c0 < e; c0 += CN_CHUNK) {
-        int v[CN_PER], ob[CN_PER], oe[CN_PER];
+        SlotChunk<SLOT_PER, CN_THREADS> C;
+        C.take(g.kf_mp_index, c0, e, g.n_mp, g.mp_bad, g.mp_obs_offsets, obs_total, status, STATUS_POINT_INDEX, [](int) { return true; });
 #pragma unroll
-        for (int k = 0; k < CN_PER; ++k) { const int s = c0 + k * CN_THREADS + tid; v[k] = s < e ? g.kf_mp_index[s] : -1; }
+        for (int k = 0; k < SLOT_PER; ++k) {
+            for (int o = C.ob[k]; o < C.oe[k]; o += SLOT_OBS) {
+                int q[SLOT_OBS];
 #pragma unroll
-        for (int k = 0; k < CN_PER; ++k) {
-            if (v[k] >= g.n_mp) { atomicOr(status, STATUS_POINT_INDEX); v[k] = -1; }
-            const bool live = v[k] >= 0 && !g.mp_bad[v[k]];
-            ob[k] = live ? min(max(g.mp_obs_offsets[v[k]], 0), obs_total) : 0;
-            oe[k] = live ? min(max(g.mp_obs_offsets[v[k] + 1], ob[k]), obs_total) : 0;
-        }
+                for (int t = 0; t < SLOT_OBS; ++t) q[t] = o + t < C.oe[k] ? g.mp_obs_kf[o + t] : kf;      // (past the row: the key frame itself, which gets nothing)
 #pragma unroll
-        for (int k = 0; k < CN_PER; ++k) {
-            for (int o = ob[k]; o < oe[k]; o += CN_OBS) {
-                int q[CN_OBS];
-#pragma unroll
-                for (int t = 0; t < CN_OBS; ++t) q[t] = o + t < oe[k] ? g.mp_obs_kf[o + t] : kf;      // (past the row: the key frame itself, which gets nothing)
-#pragma unroll
-                for (int t = 0; t < CN_OBS; ++t) {
+                for (int t = 0; t < SLOT_OBS; ++t) {
                     if ((unsigned)q[t] >= (unsigned)n_kf) atomicOr(status, STATUS_KF_INDEX);
                     else if (q[t] != kf) atomicAdd(&s_votes[q[t]], 1);                                // mnId == mnId, :475
                 }
@@ -123,7 +114,7 @@ __global__ __launch_bounds__(CN_THREADS) void k_conn_count(ConnArgs A, int* __re
         row[k] = votes;
         counted += votes > 0;
         strong += votes >= A.th;
-        if (votes > 0) best = max(best, ((unsigned long long)(unsigned)votes << 32) | (unsigned)(0x7fffffff - k));      // more votes first, then the lower index
+        if (votes > 0) best = max(best, vote_key(votes, k));
     }
     counted = wave_sum_i32(counted);
     strong = wave_sum_i32(strong);
@@ -132,8 +123,8 @@ __global__ __launch_bounds__(CN_THREADS) void k_conn_count(ConnArgs A, int* __re
     __syncthreads();
     if (tid == 0) {
         A.n_counted[j] = s_counted;
-        A.kf_max[j] = s_best ? 0x7fffffff - (int)(unsigned)(s_best & 0xffffffffu) : -1;
-        A.w_max[j] = (int)(s_best >> 32);
+        A.kf_max[j] = vote_key_kf(s_best);
+        A.w_max[j] = vote_key_votes(s_best);
         A.conn_offsets[j + 1] = s_counted;
         A.covis_offsets[j + 1] = s_strong ? s_strong : s_counted ? 1 : 0;      // (:526-530: nobody at or above th leaves the one pair (nmax, pKFmax))
     }
@@ -149,8 +140,8 @@ __global__ __launch_bounds__(OFFSET_SCAN_THREADS) void k_conn_scan(int* __restri
 __global__ __launch_bounds__(CN_THREADS) void k_conn_fill(ConnArgs A)
 {
     __shared__ unsigned long long s_keys[CN_SORT_MAX];
-    __shared__ int s_cnt[CN_WAVES], s_str[CN_WAVES];
-    const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n_kf = A.g.n_kf;
+    __shared__ int s_cnt[2][CN_WAVES];
+    const int j = blockIdx.x, tid = threadIdx.x, n_kf = A.g.n_kf;
     if (A.n_counted[j] == 0) return;                                 // (:501; also a listed index outside the graph)
     const int* row = A.votes + (size_t)j * n_kf;
     const long long c0 = A.conn_offsets[j], v0 = A.covis_offsets[j];
@@ -158,14 +149,11 @@ __global__ __launch_bounds__(CN_THREADS) void k_conn_fill(ConnArgs A)
     for (int k0 = 0; k0 < n_kf; k0 += CN_THREADS) {
         const int k = k0 + tid;
         const int votes = k < n_kf ? row[k] : 0;
-        const unsigned long long cm = wave_vote(votes > 0), sm = wave_vote(votes >= A.th);
-        if (lane == 0) { s_cnt[w] = __popcll(cm); s_str[w] = __popcll(sm); }
-        __syncthreads();
-        int at = counted + wave_rank_below(cm), sat = strong + wave_rank_below(sm);
-        for (int q = 0; q < CN_WAVES; ++q) {
-            if (q < w) { at += s_cnt[q]; sat += s_str[q]; }
-            counted += s_cnt[q]; strong += s_str[q];
-        }
+        const bool p[2] = {votes > 0, votes >= A.th};
+        int rank[2], n[2];
+        block_rank<CN_WAVES, 2>(p, s_cnt, rank, n);
+        const int at = counted + rank[0], sat = strong + rank[1];
+        counted += n[0]; strong += n[1];
         if (votes > 0 && c0 + at < (long long)A.conn_capacity) { A.conn_index[c0 + at] = k; A.conn_weight[c0 + at] = votes; }
         if (votes >= A.th) s_keys[sat] = conn_key(votes, k);        // (sat < n_kf <= CN_SORT_MAX)
         __syncthreads();
@@ -185,7 +173,7 @@ __global__ __launch_bounds__(CN_THREADS) void k_best_covisibles(int n_rows, cons
 {
     __shared__ unsigned long long s_keys[CN_SORT_MAX];
     int b, e;
-    lm_row(offsets, n_rows, blockIdx.x, b, e);
+    csr_row(offsets, n_rows, blockIdx.x, b, e);
     const int n = e - b, tid = threadIdx.x;
     if (n > CN_SORT_MAX) { if (tid == 0) atomicOr(status, STATUS_CONNECTIONS_LIST); return; }
     for (int i = tid; i < n; i += CN_THREADS) s_keys[i] = conn_key(weight[b + i], index[b + i]);

@@ -7,25 +7,21 @@
 //   k_cull_tables  one workgroup per listed key frame: nMPs, nRedundantObservations and, per slot, the uncapped count of qualifying observations and two flags
 //   k_tracked      one workgroup per listed key frame: the two counts over its point and line rows
 //   k_mp_culling   one thread per point
-// The slot-to-lane mapping of k_cull_tables: ONE SLOT PER LANE, CL_PER slots of a thread and CL_OBS observations of a slot in flight together, as
-// k_conn_count walks the same rows (connections_batch.hip).  The walk is a chain of dependent gathers per observation (the observation, its key frame's row
+// The slot-to-lane mapping of k_cull_tables: ONE SLOT PER LANE, SLOT_PER slots of a thread and SLOT_OBS observations of a slot in flight together: the
+// walk k_conn_count makes over the same rows (SlotChunk, map_kernels.hpp; DESIGN 4.5, "What the map-side kernels share").  The walk is a chain of dependent gathers per observation (the observation, its key frame's row
 // offsets, the octave at the observer's slot) and is bound by their latency, not by bytes.  A point has about 10 observers: a wave per slot with a lane per
 // observation would keep 10 of 64 lanes busy and need a reduction per slot; a lane per slot keeps all 64 busy on independent chains, needs no cross-lane step
-// before the two sums at the end, and a row of about 2000 slots fills the workgroup's 256 lanes twice with CL_PER = 4.  Every stage of the chain is issued
-// for all CL_OBS observations before the first is used (addresses of left-out observations are replaced by safe ones, not branched round), so a lane has up
-// to CL_OBS loads per stage outstanding; the slot row itself (index, depth, octave) is read coalesced.  There is no per-key-frame LDS table, so
+// before the two sums at the end, and a row of about 2000 slots fills the workgroup's 256 lanes twice with SLOT_PER = 4.  Every stage of the chain is issued
+// for all SLOT_OBS observations before the first is used (addresses of left-out observations are replaced by safe ones, not branched round), so a lane has up
+// to SLOT_OBS loads per stage outstanding; the slot row itself (index, depth, octave) is read coalesced.  There is no per-key-frame LDS table, so
 // OLF_LOCALMAP_MAX_KF does not apply, and a workgroup uses 8 bytes of LDS: occupancy is bounded by registers alone.
-#include <algorithm>
-#include "offset_scan.hpp"
-#include "staging.hpp"
-#include "device_math.hpp"
+#include "map_kernels.hpp"
 #include "../../include/orbline.h"
 
 namespace olf {
 
 constexpr int CL_THREADS = 256;
-constexpr int CL_PER = 4, CL_CHUNK = CL_THREADS * CL_PER;      // slots per thread and per chunk of the walk
-constexpr int CL_OBS = 4;                                      // observations of a point in flight per thread
+constexpr int CL_CHUNK = CL_THREADS * SLOT_PER;                // slots per chunk of the walk
 constexpr int CL_TH_OBS = 3;                                   // thObs, :647-648
 
 struct CullArgs {
@@ -46,9 +42,8 @@ __global__ __launch_bounds__(OFFSET_SCAN_THREADS) void k_cull_rows(CullArgs A, i
 {
     const int n_kf = A.g.n_kf;
     for (int j = threadIdx.x; j < A.n_list; j += OFFSET_SCAN_THREADS) {      // (thread t writes and, in offset_scan, reads the entries j = t mod 1024)
-        const int kf = A.kf_list ? A.kf_list[j] : j;
-        int b = 0, e = 0;
-        if ((unsigned)kf < (unsigned)n_kf) lm_row(A.g.kf_mp_offsets, n_kf, kf, b, e);
+        int kf, b = 0, e = 0;
+        if (listed_kf(A.kf_list, j, n_kf, kf)) csr_row(A.g.kf_mp_offsets, n_kf, kf, b, e);
         A.row_offsets[j + 1] = e - b;
     }
     offset_scan(A.row_offsets, A.n_list, A.slot_capacity, status, STATUS_CONNECTIONS_LIST);
@@ -60,8 +55,8 @@ __global__ __launch_bounds__(CL_THREADS) void k_cull_tables(CullArgs A, int* __r
     const olf_map_graph& g = A.g;
     const olf_cull_view& v = A.v;
     const int j = blockIdx.x, tid = threadIdx.x, n_kf = g.n_kf;
-    const int kf = A.kf_list ? A.kf_list[j] : j;
-    if ((unsigned)kf >= (unsigned)n_kf) {                            // (the whole workgroup: kf is uniform)
+    int kf;
+    if (!listed_kf(A.kf_list, j, n_kf, kf)) {                        // (the whole workgroup: kf is uniform)
         if (tid == 0) { atomicOr(status, STATUS_KF_INDEX); A.n_mps[j] = 0; A.n_red[j] = 0; A.redundant[j] = 0; }
         return;
     }
@@ -69,62 +64,53 @@ __global__ __launch_bounds__(CL_THREADS) void k_cull_tables(CullArgs A, int* __r
     __syncthreads();
 
     int b, e;
-    lm_row(g.kf_mp_offsets, n_kf, kf, b, e);
+    csr_row(g.kf_mp_offsets, n_kf, kf, b, e);
     const int slots_total = max(g.kf_mp_offsets[n_kf], 0);
     const int obs_total = max(g.mp_obs_offsets[g.n_mp], 0);
     const float th_depth = v.kf_th_depth[kf];
     const long long out0 = (long long)A.row_offsets[j] - b;          // slot s of the graph is entry out0 + s of the slot outputs
     int n_mps = 0, n_red = 0;
     for (int c0 = b; c0 < e; c0 += CL_CHUNK) {
-        int p[CL_PER], own[CL_PER], ob[CL_PER], oe[CL_PER], nobs[CL_PER];
-        float depth[CL_PER];
+        SlotChunk<SLOT_PER, CL_THREADS> C;
+        int own[SLOT_PER];
+        float depth[SLOT_PER];
 #pragma unroll
-        for (int k = 0; k < CL_PER; ++k) {
-            const int s = c0 + k * CL_THREADS + tid;
-            p[k] = s < e ? g.kf_mp_index[s] : -1;
+        for (int k = 0; k < SLOT_PER; ++k) {
+            const int s = C.slot(c0, k);
             depth[k] = s < e ? v.kf_slot_depth[s] : 0.0f;
             own[k] = s < e ? (int)v.kf_slot_octave[s] : 0;
         }
+        // a point counts when it is live (:654-656) and, unless monocular, not beyond th_depth or behind (:658-662, as written: a NaN depth counts)
+        C.take(g.kf_mp_index, c0, e, g.n_mp, g.mp_bad, g.mp_obs_offsets, obs_total, status, STATUS_POINT_INDEX,
+               [&](int k) { return A.monocular || !(depth[k] > th_depth || depth[k] < 0); });
 #pragma unroll
-        for (int k = 0; k < CL_PER; ++k) {
-            if (p[k] >= g.n_mp) { atomicOr(status, STATUS_POINT_INDEX); p[k] = -1; }
-            bool counted = p[k] >= 0 && !g.mp_bad[p[k]];             // :654-656
-            if (counted && !A.monocular && (depth[k] > th_depth || depth[k] < 0)) counted = false;      // :658-662, as written: a NaN depth counts
-            if (!counted) p[k] = -1;
-            nobs[k] = counted ? v.mp_nobs[p[k]] : 0;
-            ob[k] = counted ? min(max(g.mp_obs_offsets[p[k]], 0), obs_total) : 0;
-            oe[k] = counted ? min(max(g.mp_obs_offsets[p[k] + 1], ob[k]), obs_total) : 0;
-        }
-#pragma unroll
-        for (int k = 0; k < CL_PER; ++k) {
-            const int s = c0 + k * CL_THREADS + tid;
+        for (int k = 0; k < SLOT_PER; ++k) {
+            const int s = C.slot(c0, k), nobs = C.item[k] >= 0 ? v.mp_nobs[C.item[k]] : 0;
             int count = 0;                                           // the observations that qualify, :670-683 without the break
-            for (int o = ob[k]; o < oe[k]; o += CL_OBS) {
-                int q[CL_OBS], qs[CL_OBS], rb[CL_OBS], re[CL_OBS], oct[CL_OBS];
-                bool ok[CL_OBS];
+            for (int o = C.ob[k]; o < C.oe[k]; o += SLOT_OBS) {
+                int q[SLOT_OBS], qs[SLOT_OBS], rb[SLOT_OBS], re[SLOT_OBS], oct[SLOT_OBS];
+                bool ok[SLOT_OBS];
 #pragma unroll
-                for (int t = 0; t < CL_OBS; ++t) {                   // (past the row: the key frame itself, which is skipped)
-                    q[t] = o + t < oe[k] ? g.mp_obs_kf[o + t] : kf;
-                    qs[t] = o + t < oe[k] ? v.mp_obs_slot[o + t] : 0;
+                for (int t = 0; t < SLOT_OBS; ++t) {                 // (past the row: the key frame itself, which is skipped)
+                    q[t] = o + t < C.oe[k] ? g.mp_obs_kf[o + t] : kf;
+                    qs[t] = o + t < C.oe[k] ? v.mp_obs_slot[o + t] : 0;
                 }
 #pragma unroll
-                for (int t = 0; t < CL_OBS; ++t) {
+                for (int t = 0; t < SLOT_OBS; ++t) {
                     ok[t] = q[t] != kf;                              // pKFi == pKF, :673: before anything of the observation is read
                     if (ok[t] && (unsigned)q[t] >= (unsigned)n_kf) { atomicOr(status, STATUS_KF_INDEX); ok[t] = false; }
-                    const int r = ok[t] ? q[t] : kf;                 // (a row that exists)
-                    rb[t] = min(max(g.kf_mp_offsets[r], 0), slots_total);
-                    re[t] = min(max(g.kf_mp_offsets[r + 1], rb[t]), slots_total);
+                    csr_clamp(g.kf_mp_offsets, ok[t] ? q[t] : kf, slots_total, rb[t], re[t]);      // (else: a row that exists)
                 }
 #pragma unroll
-                for (int t = 0; t < CL_OBS; ++t) {
+                for (int t = 0; t < SLOT_OBS; ++t) {
                     if (ok[t] && (unsigned)qs[t] >= (unsigned)(re[t] - rb[t])) { atomicOr(status, STATUS_KF_INDEX); ok[t] = false; }
                     oct[t] = v.kf_slot_octave[ok[t] ? rb[t] + qs[t] : s];      // (the own slot: an address that exists)
                 }
 #pragma unroll
-                for (int t = 0; t < CL_OBS; ++t) count += ok[t] && oct[t] <= own[k] + 1;      // :677
+                for (int t = 0; t < SLOT_OBS; ++t) count += ok[t] && oct[t] <= own[k] + 1;      // :677
             }
-            const bool counted = p[k] >= 0;
-            const bool red = counted && nobs[k] > CL_TH_OBS && count >= CL_TH_OBS;      // :665, :684
+            const bool counted = C.item[k] >= 0;
+            const bool red = counted && nobs > CL_TH_OBS && count >= CL_TH_OBS;      // :665, :684
             n_mps += counted;
             n_red += red;
             if (s < e && out0 + s < (long long)A.slot_capacity) {
@@ -157,12 +143,10 @@ __device__ __forceinline__ void tracked_row(const int* __restrict__ offs, const 
                                             const int* __restrict__ nobs, int min_obs, int bit, int* __restrict__ status, int* s_sum)
 {
     int b, e, n = 0;
-    lm_row(offs, n_kf, kf, b, e);
+    csr_row(offs, n_kf, kf, b, e);
     for (int s = b + (int)threadIdx.x; s < e; s += CL_THREADS) {
-        const int i = index[s];
-        if (i >= n_items) { atomicOr(status, bit); continue; }
-        if (i < 0 || bad[i]) continue;
-        n += min_obs <= 0 || nobs[i] >= min_obs;
+        const int i = live_item(index[s], n_items, bad, status, bit);
+        if (i >= 0) n += min_obs <= 0 || nobs[i] >= min_obs;
     }
     n = wave_sum_i32(n);
     if ((threadIdx.x & 63) == 0) atomicAdd(s_sum, n);
@@ -173,8 +157,8 @@ __global__ __launch_bounds__(CL_THREADS) void k_tracked(TrackedArgs A, int* __re
     __shared__ int s_points, s_lines;
     const olf_map_graph& g = A.g;
     const int j = blockIdx.x, tid = threadIdx.x;
-    const int kf = A.kf_list ? A.kf_list[j] : j;
-    if ((unsigned)kf >= (unsigned)g.n_kf) {                          // (-1: no reference key frame, which is no error)
+    int kf;
+    if (!listed_kf(A.kf_list, j, g.n_kf, kf)) {                      // (-1: no reference key frame, which is no error)
         if (tid == 0) { if (kf != -1) atomicOr(status, STATUS_KF_INDEX); A.n_points[j] = 0; A.n_lines[j] = 0; }
         return;
     }

@@ -18,7 +18,9 @@
 #include <stdint.h>
 #include <string.h>
 
+// the one host/device marker of the library
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define OLF_HD __host__ __device__ __forceinline__
 #else
 #define OLF_HD static inline

@@ -2,8 +2,7 @@
 // in [list_offsets[j], list_offsets[j + 1]) is item list_index[e] for frame j; without, entry e = j * n_items + i is item i for frame j.  The offsets are
 // device data: whatever they hold, a range stays inside [0, n_entries).  Also the scatter of what a frame already holds into one bit per (frame, item).
 #pragma once
-#include <stdint.h>
-#include <hip/hip_runtime.h>
+#include "olf_internal.hpp"
 
 namespace olf {
 
@@ -32,19 +31,17 @@ struct EntryLists {
     __device__ __forceinline__ void range(int j, int& b, int& e) const
     {
         if (!offsets) { b = j * n_items; e = b + n_items; return; }
-        b = min(max(offsets[j], 0), n_entries);
-        e = min(max(offsets[j + 1], b), n_entries);
+        csr_clamp(offsets, j, n_entries, b, e);
     }
 };
 
 // One feature's item into its frame's held bitmap (one bit per item; held_row: the frame's (n_items + 31) / 32 words, zeroed before).  v is the feature's
-// entry of mvpMapPoints as an index into the map: negative = none; v >= n_items is left out and sets `bit` of *status; a bad item is dropped
-// from its feature.  Returns v where the frame holds a live item now, -1 otherwise.
+// entry of mvpMapPoints as an index into the map, taken as live_item takes it: a bad item is dropped from its feature.  Returns v where the frame holds
+// a live item now, -1 otherwise.
 __device__ __forceinline__ int held_mark(int v, int n_items, const uint8_t* __restrict__ bad, unsigned* __restrict__ held_row, int* __restrict__ status, int bit)
 {
-    if (v >= n_items) { atomicOr(status, bit); return -1; }
-    if (v < 0 || bad[v]) return -1;
-    atomicOr(&held_row[v >> 5], 1u << (v & 31));
+    v = live_item(v, n_items, bad, status, bit);
+    if (v >= 0) atomicOr(&held_row[v >> 5], 1u << (v & 31));
     return v;
 }
 

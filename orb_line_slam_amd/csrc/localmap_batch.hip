@@ -12,9 +12,10 @@
 // which atomic arrives first.  Both passes run the same walk over the same list against a bitmap in the same state, so their counts agree.  A frame's two
 // bitmaps (one bit per map point, one per map line) live in LDS -- in the words of the vote table, which is done with by then -- while they fit
 // LM_BITS_WORDS words; beyond that they live in scratch, where the counting pass sets the bits and the filling pass clears them again.
+// The compaction step, the pKFmax key, the CSR row and the item test: map_kernels.hpp, olf_internal.hpp ("What the map-side kernels share").
 #include <algorithm>
 #include "batch_frames.hpp"
-#include "offset_scan.hpp"
+#include "map_kernels.hpp"
 #include "staging.hpp"
 
 namespace olf {
@@ -66,27 +67,23 @@ template <bool LDS, bool FILL>
 __device__ __forceinline__ long long first_seen(SeenLds& S, unsigned* bits, const int* __restrict__ index, int b, int e, int n_items, const uint8_t* __restrict__ bad,
                                                 int* __restrict__ status, int bit, long long total, int* __restrict__ out, long long out0, int capacity)
 {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     for (int c0 = b; c0 < e; c0 += LM_CHUNK) {
         if (!LDS) lm_publish();                                      // the bitmap writes of the chunk before have reached L2 ...
         __syncthreads();                                             // ... before anyone reads the bitmap again; and its LDS reads are done
         int v[LM_PER];
-        bool bd[LM_PER];
 #pragma unroll
         for (int k = 0; k < LM_PER; ++k) { const int s = c0 + k * LM_THREADS + tid; v[k] = s < e ? index[s] : -1; }
 #pragma unroll
-        for (int k = 0; k < LM_PER; ++k) {
-            if (v[k] >= n_items) { atomicOr(status, bit); v[k] = -1; }
-            bd[k] = v[k] >= 0 && bad[v[k]];
-        }
+        for (int k = 0; k < LM_PER; ++k) v[k] = live_item(v[k], n_items, bad, status, bit);
         unsigned open = 0, win = 0;                                  // per position of this thread.  open: not decided yet
 #pragma unroll
         for (int k = 0; k < LM_PER; ++k) {
-            if (v[k] >= 0 && !bd[k]) {
+            if (v[k] >= 0) {
                 const bool seen = LDS ? (bits[v[k] >> 5] >> (v[k] & 31)) & 1u
                                       : ((__hip_atomic_load(bits + (v[k] >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> (v[k] & 31)) & 1u) != (FILL ? 1u : 0u);
                 if (seen) v[k] = -1;
-            } else v[k] = -1;
+            }
             S.val[k * LM_THREADS + tid] = v[k];
             if (v[k] >= 0) open |= 1u << k;
         }
@@ -127,19 +124,14 @@ __device__ __forceinline__ long long first_seen(SeenLds& S, unsigned* bits, cons
             }                                                        // else another item's: all positions of this one stay open together
             if (!__syncthreads_or(open != 0)) break;
         }
-        int rank[LM_PER];
+        bool won[LM_PER];
+        int rank[LM_PER], cnt[LM_PER];
 #pragma unroll
-        for (int k = 0; k < LM_PER; ++k) {
-            const unsigned long long wm = wave_vote((win >> k) & 1u);
-            rank[k] = wave_rank_below(wm);
-            if (lane == 0) S.wcnt[k][w] = __popcll(wm);
-        }
-        __syncthreads();
-        long long at[LM_PER], base = total;                          // positions ascend with k first, then with the wave, then with the lane
+        for (int k = 0; k < LM_PER; ++k) won[k] = (win >> k) & 1u;
+        block_rank<LM_WAVES, LM_PER>(won, S.wcnt, rank, cnt);       // (the barrier at the chunk's start separates this from the next call)
+        long long at[LM_PER];                                        // positions ascend with k first, then with the wave, then with the lane
 #pragma unroll
-        for (int k = 0; k < LM_PER; ++k)
-            for (int q = 0; q < LM_WAVES; ++q) { if (q == w) at[k] = base + rank[k]; base += S.wcnt[k][q]; }
-        total = base;
+        for (int k = 0; k < LM_PER; ++k) { at[k] = total + rank[k]; total += cnt[k]; }
 #pragma unroll
         for (int k = 0; k < LM_PER; ++k) {
             if (!((win >> k) & 1u)) continue;
@@ -160,10 +152,10 @@ __device__ __forceinline__ void lm_walk(const LocalMapArgs& A, SeenLds& S, unsig
     for (int m = 0; m < size; ++m) {
         const int kf = s_head && m < LM_HEAD ? s_head[m] : __hip_atomic_load(list + m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         int b, e;
-        lm_row(g.kf_mp_offsets, g.n_kf, kf, b, e);
+        csr_row(g.kf_mp_offsets, g.n_kf, kf, b, e);
         np = first_seen<LDS, FILL>(S, bits_mp, g.kf_mp_index, b, e, g.n_mp, g.mp_bad, status, STATUS_POINT_INDEX, np, A.mp_index, mp0, A.mp_capacity);
         if (g.n_ml > 0) {
-            lm_row(g.kf_ml_offsets, g.n_kf, kf, b, e);
+            csr_row(g.kf_ml_offsets, g.n_kf, kf, b, e);
             nl = first_seen<LDS, FILL>(S, bits_ml, g.kf_ml_index, b, e, g.n_ml, g.ml_bad, status, STATUS_LINE_INDEX, nl, A.ml_index, ml0, A.ml_capacity);
         }
     }
@@ -174,10 +166,8 @@ __device__ __forceinline__ void lm_walk(const LocalMapArgs& A, SeenLds& S, unsig
 __device__ __forceinline__ int lm_clean(const int* __restrict__ in, int* __restrict__ out, size_t at, bool inside, int n_items, const uint8_t* __restrict__ bad,
                                         int* __restrict__ status, int bit)
 {
-    int v = inside ? in[at] : -1, held = -1;
-    if (v >= n_items) atomicOr(status, bit);
-    else if (v >= 0) { if (bad[v]) v = -1; else held = v; }
-    if (out) out[at] = v;
+    const int v = inside ? in[at] : -1, held = live_item(v, n_items, bad, status, bit);
+    if (out) out[at] = (unsigned)v < (unsigned)n_items ? held : v;      // (an index outside the map stays as it came, a bad item becomes -1)
     return held;
 }
 
@@ -188,7 +178,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_localmap_count(LocalMapArgs A, i
     __shared__ int s_head[LM_HEAD];
     __shared__ SeenLds S;
     __shared__ unsigned long long s_best;
-    __shared__ int s_cnt[LM_WAVES], s_voted[LM_WAVES], s_size;
+    __shared__ int s_cnt[2][LM_WAVES], s_size;
     const olf_map_graph& g = A.g;
     const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n_kf = g.n_kf;
     int* list = A.kf_list + (size_t)j * n_kf;
@@ -204,7 +194,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_localmap_count(LocalMapArgs A, i
         const int v = lm_clean(A.frame_mp, A.frame_mp_out, (size_t)j * A.cap + i, i < n, g.n_mp, g.mp_bad, status, STATUS_POINT_INDEX);
         if (v < 0) continue;
         int b, e;
-        lm_row(g.mp_obs_offsets, g.n_mp, v, b, e);
+        csr_row(g.mp_obs_offsets, g.n_mp, v, b, e);
         for (int o = b; o < e; ++o) {
             const int kf = g.mp_obs_kf[o];
             if ((unsigned)kf >= (unsigned)n_kf) atomicOr(status, STATUS_KF_INDEX); else atomicAdd(&s_votes[kf], 1);
@@ -224,15 +214,17 @@ __global__ __launch_bounds__(LM_THREADS) void k_localmap_count(LocalMapArgs A, i
         const int k = k0 + tid;
         const int votes = k < n_kf ? s_votes[k] : 0;
         const bool member = votes > 0 && !g.kf_bad[k];
-        const unsigned long long vm = wave_vote(votes > 0), mm = wave_vote(member);
-        if (lane == 0) { s_voted[w] = __popcll(vm); s_cnt[w] = __popcll(mm); if (k < n_kf) s_stamp[k >> 6] = mm; }
-        __syncthreads();
-        int at = size + wave_rank_below(mm);
-        for (int q = 0; q < LM_WAVES; ++q) { if (q < w) at += s_cnt[q]; size += s_cnt[q]; voted += s_voted[q]; }
+        const unsigned long long mm = wave_vote(member);
+        if (lane == 0 && k < n_kf) s_stamp[k >> 6] = mm;
+        const bool p[2] = {member, votes > 0};
+        int rank[2], n[2];
+        block_rank<LM_WAVES, 2>(p, s_cnt, rank, n);
+        const int at = size + rank[0];
+        size += n[0]; voted += n[1];
         if (member) {
             list[at] = k;
             if (at < LM_HEAD) s_head[at] = k;
-            best = max(best, ((unsigned long long)(unsigned)votes << 32) | (unsigned)(0x7fffffff - k));      // more votes first, then the lower index
+            best = max(best, vote_key(votes, k));
         }
         __syncthreads();
     }
@@ -240,7 +232,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_localmap_count(LocalMapArgs A, i
     __syncthreads();
     if (tid == 0) {
         A.n_voted[j] = voted;
-        A.ref_kf[j] = s_best ? 0x7fffffff - (int)(unsigned)(s_best & 0xffffffffu) : -1;
+        A.ref_kf[j] = vote_key_kf(s_best);
     }
 
     // ---- the extension, :2149-2198, by wave 0.  The end iterator is the first list's: `first` members are visited, what is appended is not ----
@@ -252,7 +244,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_localmap_count(LocalMapArgs A, i
             const int kf = s_head[m];                                // (m <= 80 < LM_HEAD)
             int b, e;
             // GetBestCovisibilityKeyFrames(10): the first min(10, size) of the ordered list -- the first that is not bad and not stamped
-            lm_row(g.kf_covis_offsets, n_kf, kf, b, e);
+            csr_row(g.kf_covis_offsets, n_kf, kf, b, e);
             e = min(e, b + 10);
             {
                 const int c = b + lane < e ? g.kf_covis_index[b + lane] : -1;
@@ -267,7 +259,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_localmap_count(LocalMapArgs A, i
                 }
             }
             // GetChilds(): std::set order = ascending index (C.16) -- the first that is not bad and not stamped
-            lm_row(g.kf_child_offsets, n_kf, kf, b, e);
+            csr_row(g.kf_child_offsets, n_kf, kf, b, e);
             for (int c0 = b; c0 < e; c0 += 64) {
                 const int c = c0 + lane < e ? g.kf_child_index[c0 + lane] : -1;
                 const bool oob = c0 + lane < e && (unsigned)c >= (unsigned)n_kf;

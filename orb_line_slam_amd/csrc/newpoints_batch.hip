@@ -12,6 +12,7 @@
 //                   by the gathers' latency, hidden across the 64 independent points of a wave and the waves of a CU, not by bytes.
 #include "newpoints_terms.hpp"
 #include "batch_frames.hpp"
+#include "map_kernels.hpp"
 #include "../../include/orbline.h"
 
 namespace olf {
@@ -54,15 +55,15 @@ __global__ __launch_bounds__(NP_THREADS) void k_f12_pairs(F12Args A, int* __rest
 
 // One workgroup per pair.  A row of d_matches12 is sparse (a few hundred matches among a capacity of about 2000) and a match costs some thousand
 // operations, most of them the Jacobi sweeps: a lane per idx1 slot would leave most lanes of every wave idle through them.  So the row is taken in segments
-// of NP_SEG slots: the slots that hold a usable match are compacted into LDS in idx1 order (a ballot per wave, the four waves' counts through LDS; no
-// atomics), then dense lanes take one match each and write code and x3D back to its idx1 slot.  A match's result depends on nothing but its own inputs and
-// nnew is an integer sum, so nothing depends on scheduling or on where the pair stands.
+// of NP_SEG slots: the slots that hold a usable match are compacted into LDS in idx1 order (block_rank, map_kernels.hpp; DESIGN 4.5, "What the map-side
+// kernels share"), then dense lanes take one match each and write code and x3D back to its idx1 slot.  A match's result depends on nothing but its own
+// inputs and nnew is an integer sum, so nothing depends on scheduling or on where the pair stands.
 __global__ __launch_bounds__(NP_THREADS) void k_create_new_map_points(NewPointsArgs A, int* __restrict__ status)
 {
     __shared__ int s_list[NP_SEG];
-    __shared__ int s_cnt[NP_THREADS / 64];
-    __shared__ int s_n, s_new;
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, cap = A.cap;
+    __shared__ int s_cnt[1][NP_THREADS / 64];
+    __shared__ int s_new;
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, cap = A.cap;
     const int f1 = A.pairs[2 * (size_t)p], f2 = A.pairs[2 * (size_t)p + 1];
     if (!pair_in_batch(f1, f2, A.n_frames)) {                        // (the whole workgroup: the pair is uniform)
         if (tid == 0) { atomicOr(status, STATUS_PAIR); A.nnew[p] = -1; }
@@ -80,8 +81,7 @@ __global__ __launch_bounds__(NP_THREADS) void k_create_new_map_points(NewPointsA
     int created = 0;
     for (int seg0 = 0; seg0 < cap; seg0 += NP_SEG) {
         const int seg1 = min(seg0 + NP_SEG, cap);
-        if (tid == 0) s_n = 0;
-        __syncthreads();
+        int n = 0;
         for (int base = seg0; base < seg1; base += NP_THREADS) {     // (uniform trip count)
             const int i = base + tid;
             bool live = false;
@@ -94,17 +94,12 @@ __global__ __launch_bounds__(NP_THREADS) void k_create_new_map_points(NewPointsA
                 }
             }
             if (i < seg1 && !live) { A.code[row + i] = 0; A.x3D[3 * (row + i)] = 0.f; A.x3D[3 * (row + i) + 1] = 0.f; A.x3D[3 * (row + i) + 2] = 0.f; }
-            const unsigned long long m = wave_vote(live);
-            if (lane == 0) s_cnt[w] = __popcll(m);
-            __syncthreads();
-            int at = s_n;
-            for (int k = 0; k < w; ++k) at += s_cnt[k];
-            if (live) s_list[at + wave_rank_below(m)] = i;
-            __syncthreads();
-            if (tid == 0) s_n += s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+            int step;
+            const int at = n + block_rank<NP_THREADS / 64>(live, s_cnt, step);
+            if (live) s_list[at] = i;                                // (at <= i - seg0 < NP_SEG)
+            n += step;
             __syncthreads();
         }
-        const int n = s_n;
         for (int q = tid; q < n; q += NP_THREADS) {
             const int i = s_list[q], idx2 = A.matches12[row + i];
             const olf_keypoint a = kp1[i], b = kp2[idx2];

@@ -1,7 +1,7 @@
 // newpoints_terms.hpp -- the arithmetic the host forms (newpoints_host.cpp) and the kernels (newpoints_batch.hip) of the map-producing entries both run:
 // LocalMapping::ComputeF12 (src/LocalMapping.cc:536-553) and MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:342-383).  One text for both sides; every
 // file that includes it is built with -ffp-contract=off (C.4).  The cv::Mat products are those of search_math.hpp (C.12); new here:
-//   C.17  cv::Mat / scalar is a scaling by the double reciprocal rounded to float, (float)(1.0 / (double)s): normali / cv::norm(normali) (the norm stays
+//   C.17  cv::Mat / scalar is a scaling by the double reciprocal rounded to float, (float)(1.0 / (double)s) (recip_f32, search_math.hpp): normali / cv::norm(normali) (the norm stays
 //         a double: cv::norm returns one) and normal / n (an int, widened)
 //   C.18  cv::invert of a 3 x 3 CV_32F matrix is the closed-form adjugate: determinant and cofactors in double, times the double 1 / det, one rounding
 //         per element (the float sibling of C.13's form); a zero determinant gives the zero matrix
@@ -12,27 +12,8 @@
 
 namespace olf {
 
-// a status bit: the context's word on the device, the caller's on the host
-__host__ __device__ __forceinline__ void np_raise(int* status, int bit)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicOr(status, bit);
-#else
-    *status |= bit;
-#endif
-}
-
-// row k of a CSR of n rows, clamped to [0, offs[n]] (a malformed offsets array reads nothing out of bounds)
-__host__ __device__ __forceinline__ void np_row(const int* offs, int n, int k, int& b, int& e)
-{
-    const int last = offs[n], total = last > 0 ? last : 0;
-    const int ob = offs[k], oe = offs[k + 1];
-    b = ob < 0 ? 0 : (ob > total ? total : ob);
-    e = oe < b ? b : (oe > total ? total : oe);
-}
-
 // C.18
-__host__ __device__ __forceinline__ void inv3_f32(const float* s, float* out)
+OLF_HD void inv3_f32(const float* s, float* out)
 {
     const double m0 = s[0], m1 = s[1], m2 = s[2], m3 = s[3], m4 = s[4], m5 = s[5], m6 = s[6], m7 = s[7], m8 = s[8];
     double d = m0 * (m4 * m8 - m5 * m7) - m1 * (m3 * m8 - m5 * m6) + m2 * (m3 * m7 - m4 * m6);
@@ -44,7 +25,7 @@ __host__ __device__ __forceinline__ void inv3_f32(const float* s, float* out)
 }
 
 // a plain 3 x 3 product, cv::gemm's small-matrix path (C.12): ((a0 * b0 + a1 * b1) + a2 * b2) in float
-__host__ __device__ __forceinline__ void mat3_mul_small(const float* A, const float* B, float* C)
+OLF_HD void mat3_mul_small(const float* A, const float* B, float* C)
 {
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) C[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
@@ -55,7 +36,7 @@ __host__ __device__ __forceinline__ void mat3_mul_small(const float* A, const fl
 //   t12 = -R1w * R2w.t() * t2w + t1w    ((-R1w) * R2w.t()) is evaluated first, alpha = -1 applied to the double sum: the negated R12 exactly; then a
 //                                       plain product with t1w as the C term (rot_apply's form)
 //   K1.t().inv() * t12x * R12 * K2.inv()   left to right, three plain products; the two inverses by C.18
-__host__ __device__ __forceinline__ void f12_compute(const float* T1, const float* T2, const float* cam, float* F12)
+OLF_HD void f12_compute(const float* T1, const float* T2, const float* cam, float* F12)
 {
     float R12[9], M[9], t12[3];
     for (int i = 0; i < 3; ++i)
@@ -92,7 +73,7 @@ enum NewPointCode : int {
 // sums; a sweep without a rotation ends the iteration.  The singular values are then ordered descending by a selection that takes the first of equal
 // maxima, the rows of V with them.  gamma = hypot(2p, a - b) is spelled sqrt(p p + beta beta) so that host and device run the same operations.  All
 // indices are static after unrolling: A, V and W stay in registers on the device.
-__host__ __device__ __forceinline__ void jacobi_null4(const float (&A)[4][4], float* v4)
+OLF_HD void jacobi_null4(const float (&A)[4][4], float* v4)
 {
     float At[4][4], V[4][4];
     double W[4];
@@ -171,7 +152,7 @@ __host__ __device__ __forceinline__ void jacobi_null4(const float (&A)[4][4], fl
 // KeyFrame::SetPose (src/KeyFrame.cc:148-162) of a 4 x 4 pose: Rcw, tcw, and Ow = -Rwc * tcw on the materialised transpose Rwc = Rcw.t(): a plain product
 // (cv::gemm's small-matrix path, C.12), alpha = -1 applied to the float sum in double -- not Frame's -mRcw.t() * mtcw (camera_centre)
 struct KfPose { float R[9], t[3], Ow[3]; };
-__host__ __device__ __forceinline__ void kf_pose(const float* Tcw, KfPose& P)
+OLF_HD void kf_pose(const float* Tcw, KfPose& P)
 {
     for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) P.R[3 * r + k] = Tcw[4 * r + k]; P.t[r] = Tcw[4 * r + 3]; }
     for (int r = 0; r < 3; ++r) {
@@ -180,12 +161,9 @@ __host__ __device__ __forceinline__ void kf_pose(const float* Tcw, KfPose& P)
     }
 }
 // cv::norm(Ow2 - Ow1) < pKF2->mb, :245-252
-__host__ __device__ __forceinline__ bool np_short_baseline(const KfPose& P1, const KfPose& P2, float mb)
+OLF_HD bool np_short_baseline(const KfPose& P1, const KfPose& P2, float mb)
 {
-    double nrm = 0;
-    for (int k = 0; k < 3; ++k) { const float d = P2.Ow[k] - P1.Ow[k]; nrm += (double)d * (double)d; }
-    const float baseline = (float)d_sqrt(nrm);
-    return baseline < mb;
+    return dist3_f32(P2.Ow, P1.Ow) < mb;
 }
 
 // the calibration of both key frames as the loop reads it: invfx = 1.0f / fx formed once in float (src/Frame.cc:188-189, copied by the KeyFrame);
@@ -200,14 +178,14 @@ inline int np_count(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
 
 // KeyFrame::UnprojectStereo (src/KeyFrame.cc:793-809) for a feature with z > 0: Twc.rowRange(0,3).colRange(0,3) * x3Dc + Twc.rowRange(0,3).col(3) with
 // Twc = [Rwc | Ow] of kf_pose -- unproject_stereo_point (search_math.hpp), the routine of olf_unproject_stereo_dev, on that Twc
-__host__ __device__ __forceinline__ void np_unproject(const KfPose& P, const NewPointCam& K, float u, float v, float z, float* x3D)
+OLF_HD void np_unproject(const KfPose& P, const NewPointCam& K, float u, float v, float z, float* x3D)
 {
     float Twc[12];
     for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) Twc[4 * r + k] = P.R[3 * k + r]; Twc[4 * r + 3] = P.Ow[r]; }
     unproject_stereo_point(u, v, z, K.cx, K.cy, K.invfx, K.invfy, Twc, x3D);
 }
 // Rcw.row(r).dot(x3Dt) + tcw.at<float>(r) (:354-365): Mat::dot is a double sum, the float is added in double, the assignment rounds once
-__host__ __device__ __forceinline__ float np_row_dot(const KfPose& P, int r, const float* x)
+OLF_HD float np_row_dot(const KfPose& P, int r, const float* x)
 {
     double acc = 0;
     for (int k = 0; k < 3; ++k) acc += (double)P.R[3 * r + k] * (double)x[k];
@@ -215,11 +193,11 @@ __host__ __device__ __forceinline__ float np_row_dot(const KfPose& P, int r, con
 }
 // the reprojection gate of one key frame (:362-413): true = rejected.  ur >= 0: the stereo form with mpCurrentKeyFrame->mbf for both key frames (:380,
 // :406, as written); sigma2 = mvLevelSigma2[octave] = sf * sf in float; the float sum is compared with the double product
-__host__ __device__ __forceinline__ bool np_reproj_fails(const KfPose& P, const NewPointCam& K, const float* x3D, float z, float kx, float ky, float ur, float sf)
+OLF_HD bool np_reproj_fails(const KfPose& P, const NewPointCam& K, const float* x3D, float z, float kx, float ky, float ur, float sf)
 {
     const float sigmaSquare = sf * sf;
     const float x = np_row_dot(P, 0, x3D), y = np_row_dot(P, 1, x3D);
-    const float invz = (float)d_div(1.0, (double)z);
+    const float invz = recip_f32((double)z);
     const float u = K.fx * x * invz + K.cx, v = K.fy * y * invz + K.cy;
     const float errX = u - kx, errY = v - ky;
     if (!(ur >= 0)) return (double)(errX * errX + errY * errY) > 5.991 * (double)sigmaSquare;
@@ -235,7 +213,7 @@ __host__ __device__ __forceinline__ bool np_reproj_fails(const KfPose& P, const 
 //   cosParallaxStereo = cos(2 * atan2(mb / 2, depth)): the float overloads (using namespace std), glibc's atan2f and cosf as device_math.hpp restates
 //     them for both sides; only compared, never stored
 //   A.row(0) = xn1[0] * Tcw1.row(2) - Tcw1.row(0): a float product and a float difference per element; x3D = vt.row(3) / w by C.17
-__host__ __device__ __forceinline__ int np_create_point(const KfPose& P1, const KfPose& P2, const NewPointCam& K, float x1, float y1, float ur1, float depth1, float sf1,
+OLF_HD int np_create_point(const KfPose& P1, const KfPose& P2, const NewPointCam& K, float x1, float y1, float ur1, float depth1, float sf1,
                                                         float x2, float y2, float ur2, float depth2, float sf2, float* x3D)
 {
     const bool bStereo1 = ur1 >= 0, bStereo2 = ur2 >= 0;
@@ -270,7 +248,7 @@ __host__ __device__ __forceinline__ int np_create_point(const KfPose& P1, const 
         float v4[4];
         jacobi_null4(A, v4);
         if (v4[3] == 0) return NP_W_ZERO;
-        const float inv = (float)d_div(1.0, (double)v4[3]);
+        const float inv = recip_f32((double)v4[3]);
         for (int k = 0; k < 3; ++k) x3D[k] = v4[k] * inv;
         code = NP_TRIANGULATED;
     } else if (bStereo1 && cosParallaxStereo1 < cosParallaxStereo2) {
@@ -291,9 +269,7 @@ __host__ __device__ __forceinline__ int np_create_point(const KfPose& P1, const 
     if (np_reproj_fails(P1, K, x3D, z1, x1, y1, ur1, sf1)) return NP_REPROJ_1;
     if (np_reproj_fails(P2, K, x3D, z2, x2, y2, ur2, sf2)) return NP_REPROJ_2;
     // Check scale consistency
-    double d1 = 0, d2 = 0;
-    for (int k = 0; k < 3; ++k) { const float a = x3D[k] - P1.Ow[k], b = x3D[k] - P2.Ow[k]; d1 += (double)a * (double)a; d2 += (double)b * (double)b; }
-    const float dist1 = (float)d_sqrt(d1), dist2 = (float)d_sqrt(d2);
+    const float dist1 = dist3_f32(x3D, P1.Ow), dist2 = dist3_f32(x3D, P2.Ow);
     if (dist1 == 0 || dist2 == 0) return NP_ZERO_DIST;
     const float ratioDist = f_div(dist2, dist1);
     const float ratioOctave = f_div(sf1, sf2);
@@ -320,46 +296,43 @@ struct NormalDepthView {
 // (bit 4096) does not enter the sum, n or the search for the reference's slot; a point none of whose observations is left counts as an empty row.  A
 // reference key frame outside [0, n_kf) or the slot read for the level outside the reference's row (4096), or a level outside [0, n_levels) (256),
 // leaves the point untouched; so does a point index outside [0, n_mp) (512).
-__host__ __device__ __forceinline__ void normal_depth_point(const NormalDepthView& a, int p, int* status)
+OLF_HD void normal_depth_point(const NormalDepthView& a, int p, int* status)
 {
-    if ((unsigned)p >= (unsigned)a.n_mp) { np_raise(status, STATUS_POINT_INDEX); return; }
+    if ((unsigned)p >= (unsigned)a.n_mp) { status_raise(status, STATUS_POINT_INDEX); return; }
     if (a.mp_bad[p]) return;
     int b, e;
-    np_row(a.obs_off, a.n_mp, p, b, e);
+    csr_row(a.obs_off, a.n_mp, p, b, e);
     if (b == e) return;
     const int ref = a.ref_kf[p];
-    if ((unsigned)ref >= (unsigned)a.n_kf) { np_raise(status, STATUS_KF_INDEX); return; }
+    if ((unsigned)ref >= (unsigned)a.n_kf) { status_raise(status, STATUS_KF_INDEX); return; }
     const float P[3] = {a.world[3 * (size_t)p], a.world[3 * (size_t)p + 1], a.world[3 * (size_t)p + 2]};
     float nv[3] = {0.0f, 0.0f, 0.0f};
     int n = 0, ref_slot = 0;
     bool named = false;
     for (int o = b; o < e; ++o) {
         const int kf = a.obs_kf[o], slot = a.obs_slot[o];
-        if ((unsigned)kf >= (unsigned)a.n_kf) { np_raise(status, STATUS_KF_INDEX); continue; }
+        if ((unsigned)kf >= (unsigned)a.n_kf) { status_raise(status, STATUS_KF_INDEX); continue; }
         int rb, re;
-        np_row(a.kmp_off, a.n_kf, kf, rb, re);
-        if ((unsigned)slot >= (unsigned)(re - rb)) { np_raise(status, STATUS_KF_INDEX); continue; }
+        csr_row(a.kmp_off, a.n_kf, kf, rb, re);
+        if ((unsigned)slot >= (unsigned)(re - rb)) { status_raise(status, STATUS_KF_INDEX); continue; }
         if (kf == ref && !named) { named = true; ref_slot = slot; }
         float d[3];
-        double nrm = 0;
-        for (int k = 0; k < 3; ++k) { d[k] = P[k] - a.Ow[3 * (size_t)kf + k]; nrm += (double)d[k] * (double)d[k]; }
-        const float inv = (float)d_div(1.0, d_sqrt(nrm));
+        for (int k = 0; k < 3; ++k) d[k] = P[k] - a.Ow[3 * (size_t)kf + k];
+        const float inv = recip_f32(norm3(d));
         for (int k = 0; k < 3; ++k) nv[k] = nv[k] + d[k] * inv;
         ++n;
     }
     if (n == 0) return;
     int rb, re;
-    np_row(a.kmp_off, a.n_kf, ref, rb, re);
-    if ((unsigned)ref_slot >= (unsigned)(re - rb)) { np_raise(status, STATUS_KF_INDEX); return; }
+    csr_row(a.kmp_off, a.n_kf, ref, rb, re);
+    if ((unsigned)ref_slot >= (unsigned)(re - rb)) { status_raise(status, STATUS_KF_INDEX); return; }
     const int level = a.slot_octave[rb + ref_slot];
-    if (level >= a.n_levels) { np_raise(status, STATUS_OCTAVE); return; }
-    double nrm = 0;
-    for (int k = 0; k < 3; ++k) { const float pc = P[k] - a.Ow[3 * (size_t)ref + k]; nrm += (double)pc * (double)pc; }
-    const float dist = (float)d_sqrt(nrm);
+    if (level >= a.n_levels) { status_raise(status, STATUS_OCTAVE); return; }
+    const float dist = dist3_f32(P, a.Ow + 3 * (size_t)ref);
     const float maxd = dist * a.sf[level];                           // :379
     a.maxd[p] = maxd;
     a.mind[p] = f_div(maxd, a.sf[a.n_levels - 1]);                   // :380
-    const float invn = (float)d_div(1.0, (double)n);                 // :381
+    const float invn = recip_f32((double)n);                         // :381
     for (int k = 0; k < 3; ++k) a.normal[3 * (size_t)p + k] = nv[k] * invn;
 }
 

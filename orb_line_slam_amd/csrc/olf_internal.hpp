@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "../../include/orbline_types.h"
+#include "device_math.hpp"      // OLF_HD
 
 #define OLF_HIP_CHECK(expr)                                                                 \
     do {                                                                                    \
@@ -94,6 +95,33 @@ constexpr StatusText kStatusText[] = {
     {STATUS_LOCALMAP_LIST, "local key-frame, map-point or map-line list of olf_update_local_map_batch_dev"},
     {STATUS_CONNECTIONS_LIST, "connected or ordered key-frame list of olf_update_connections_batch_dev, or a row of olf_best_covisibles_batch_dev"},
 };
+// raise a status bit: the context's word on the device (atomic), the caller's on the host
+OLF_HD void status_raise(int* status, int bit)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicOr(status, bit);
+#else
+    *status |= bit;
+#endif
+}
+
+// Row k of a CSR of n rows, inside [0, offs[n]] whatever the offsets hold: malformed offsets read nothing out of bounds.  csr_clamp is the form for a
+// caller that holds total = max(offs[n], 0) already.
+OLF_HD void csr_clamp(const int* __restrict__ offs, int k, int total, int& b, int& e)
+{
+    const int ob = offs[k], oe = offs[k + 1], lo = ob > 0 ? ob : 0, first = lo < total ? lo : total, hi = oe > first ? oe : first;
+    b = first;                       // min(max(ob, 0), total)
+    e = hi < total ? hi : total;     // min(max(oe, b), total)
+}
+OLF_HD void csr_row(const int* __restrict__ offs, int n, int k, int& b, int& e) { const int last = offs[n]; csr_clamp(offs, k, last > 0 ? last : 0, b, e); }
+
+// What a slot holds, as an index into a map of n_items: v itself, or -1 for NULL (negative), an index outside the map (which raises `bit` of *status)
+// or a bad item.
+OLF_HD int live_item(int v, int n_items, const uint8_t* __restrict__ bad, int* __restrict__ status, int bit)
+{
+    if (v >= n_items) { status_raise(status, bit); return -1; }
+    return v < 0 || bad[v] ? -1 : v;
+}
 
 #ifdef __HIPCC__
 // a pair (f1, f2) of a pair entry is searched when both are frames of the batch and differ; otherwise the entry skips it and sets STATUS_PAIR

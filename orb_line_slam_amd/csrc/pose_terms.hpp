@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include <string.h>
 
+// Not OLF_HD (device_math.hpp), which forces inlining and made k_pose_frames longer and slower ("What the map-side kernels share").
 #if defined(__HIPCC__)
 #define PT_HD __host__ __device__ inline
 #else

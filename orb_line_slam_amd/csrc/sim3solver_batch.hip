@@ -2,8 +2,8 @@
 // (src/LoopClosing.cc:280-307), and the filter of the matches by the accepted inliers (:319-324).  The arithmetic is sim3solver_terms.hpp, the text the
 // host form (sim3solver_host.cpp) runs too.
 //   k_sim3_solver   one workgroup of four waves per pair (a grid of at most 1024 workgroups strides the list).
-//     1. The row's correspondences are compacted in ascending i1 (the order decides what a draw picks): a ballot per wave, the four waves' counts through
-//        LDS, no atomics.  Each keeps 13 words -- both camera-frame points, both images, both gates, i1 -- as planes of `cap` words, in LDS where
+//     1. The row's correspondences are compacted in ascending i1 (the order decides what a draw picks): block_rank (map_kernels.hpp; DESIGN 4.5, "What the
+//        map-side kernels share").  Each keeps 13 words -- both camera-frame points, both images, both gates, i1 -- as planes of `cap` words, in LDS where
 //        52 * cap bytes fit the limit and in the workgroup's part of the batch scratch slot above it (one flat pointer, one text).
 //     2. The window [iterations_done, min(cap(N), iterations_done + n_iterations)) is taken in rounds of 64 iterations.  The hypotheses do not depend on one
 //        another once the draws are fixed: in a round every wave takes 16 iterations (dealt round-robin, so a window of 5 works all four), ONE LANE PER FIT (the Jacobi sweeps are the long dependent chain
@@ -21,6 +21,7 @@
 #include <vector>
 #include "sim3solver_terms.hpp"
 #include "batch_frames.hpp"
+#include "map_kernels.hpp"
 #include "staging.hpp"
 #include "../../include/orbline.h"
 
@@ -68,8 +69,8 @@ __device__ __forceinline__ void s3_fit_iteration(const Sim3SolverArgs& A, const 
 
 __global__ __launch_bounds__(S3_THREADS) void k_sim3_solver(Sim3SolverArgs A, int* __restrict__ status)
 {
-    __shared__ int s_cnt[S3_THREADS / 64];
-    __shared__ int s_n, s_accept, s_best_it, s_carry;
+    __shared__ int s_cnt[1][S3_WAVES];
+    __shared__ int s_accept, s_best_it, s_carry;
     __shared__ int s_counts[S3_ROUND];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, cap = A.cap;
     float* st = A.state ? A.state + (size_t)blockIdx.x * S3_WORDS * cap : s3_dyn;
@@ -86,9 +87,8 @@ __global__ __launch_bounds__(S3_THREADS) void k_sim3_solver(Sim3SolverArgs A, in
         const olf_keypoint* kp1 = A.kps + (size_t)f1 * A.img_stride * cap;
         const olf_keypoint* kp2 = A.kps + (size_t)f2 * A.img_stride * cap;
         const size_t row = (size_t)p * cap, r1 = (size_t)f1 * cap, r2 = (size_t)f2 * cap;
-        if (tid == 0) s_n = 0;
-        __syncthreads();
         // ---- 1. the correspondences, in ascending i1 (:62-109)
+        int N = 0;
         for (int base = 0; base < N1; base += S3_THREADS) {          // (uniform trip count)
             const int i = base + tid;
             bool live = false;
@@ -108,23 +108,17 @@ __global__ __launch_bounds__(S3_THREADS) void k_sim3_solver(Sim3SolverArgs A, in
                     } else atomicOr(status, STATUS_OCTAVE);
                 }
             }
-            const unsigned long long m = wave_vote(live);
-            if (lane == 0) s_cnt[w] = __popcll(m);
-            __syncthreads();
-            int at = s_n;
-            for (int k = 0; k < w; ++k) at += s_cnt[k];
+            int step;
+            const int q = N + block_rank<S3_WAVES>(live, s_cnt, step);      // q <= i < cap
+            N += step;
             if (live) {
-                const int q = at + wave_rank_below(m);               // q <= i < cap
                 for (int k = 0; k < 3; ++k) { st[(size_t)k * cap + q] = X1[k]; st[(size_t)(3 + k) * cap + q] = X2[k]; }
                 st[(size_t)6 * cap + q] = p1[0]; st[(size_t)7 * cap + q] = p1[1]; st[(size_t)8 * cap + q] = p2[0]; st[(size_t)9 * cap + q] = p2[1];
                 st[(size_t)10 * cap + q] = g1; st[(size_t)11 * cap + q] = g2;
                 st_i1[q] = i;
             }
             __syncthreads();
-            if (tid == 0) s_n += s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-            __syncthreads();
         }
-        const int N = s_n;
         if (N < A.min_inliers) {                                     // :146-150: bNoMore, nothing else changes
             if (tid == 0) { A.io.n_correspondences[p] = N; A.io.accepted[p] = 0; A.io.no_more[p] = 1; A.io.n_inliers[p] = 0; }
             continue;

@@ -140,7 +140,7 @@ struct S3Hyp { float s, R[9], t[3], T12[16], T21[16]; };
 OLF_HD void s3_fit(const float (&P1)[3][3], const float (&P2)[3][3], bool fix_scale, S3Hyp& H)
 {
     // ComputeCentroid (:215-224): the row sums in double, stored as float; C / P.cols by C.17; Pr = P - C in float.  Pr[coordinate][point]
-    const float third = (float)d_div(1.0, 3.0);
+    const float third = recip_f32(3.0);
     float O1[3], O2[3], Pr1[3][3], Pr2[3][3];
     for (int r = 0; r < 3; ++r) {
         O1[r] = f_mul((float)d_add(d_add((double)P1[0][r], (double)P1[1][r]), (double)P1[2][r]), third);

@@ -146,6 +146,20 @@ def test_more_than_80(ctx, n_first, n_added):
     assert len(exp[0]["local_kfs"]) == n_first + n_added
 
 
+def test_first_lists_across_a_compaction_step(ctx):
+    """first lists of 255, 256 and 257 voted key frames among 300 -- one step of the kernel's ordered compaction takes 256 key frames --, a few of them
+    bad (key frame 0, which would win the tie, the two sides of a wave's end and the step's last), so that voted and listed differ; more than 80
+    members: no extension"""
+    sizes, bad = (255, 256, 257), (0, 63, 64, 200, 255)
+    s = S.Scene(300)
+    for k in bad:
+        s.kf_bad[k] = 1
+    s.frame_mp = [[s.point(range(n))] for n in sizes]
+    exp, _, _ = check(ctx, s)
+    for e, n in zip(exp, sizes):
+        assert e["n_voted"] == n and e["local_kfs"] == [k for k in range(n) if k not in bad] and e["ref_kf"] == 1
+
+
 def test_five_key_frames(ctx):
     exp, _, _ = check(ctx, S.five_kf())
     assert exp == S.FIVE_KF_EXPECTED

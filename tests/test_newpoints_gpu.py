@@ -144,6 +144,43 @@ def test_create_malformed(ctx):
     ctx.poll_status()
 
 
+def test_create_row_across_steps_and_segments():
+    """A first frame of more than 2049 key points in a context whose capacity exceeds a segment of the kernel's compaction (2048 idx1 slots), usable
+    matches at both sides of the first step boundary (255, 256, 257), of the segment boundary (2046 to 2049), at slot 0 and at the frame's last key
+    point, -1 everywhere else: the second turn of the segment loop runs.  The frame tiles the pool's key points -- a match's result depends on its own
+    inputs only --, slot s of the nine holding the feature of one usable match of pair 5.  Equal to the host form bit for bit."""
+    p = _lib.default_params()
+    p.orb.nfeatures = 2100
+    big = _lib.Context(p, S.W, S.H, 2)
+    try:
+        cap = big.orb_capacity
+        assert 2049 + 5 < cap <= 4096
+        sc = S.scene_set()
+        (a, b), n1 = sc.pairs[5], cap - 5
+        slots = [0, 255, 256, 257, 2046, 2047, 2048, 2049, n1 - 1]
+        src = np.arange(n1) % S.POOL
+        row = np.full(n1, -1, np.int32)
+        for s, i1 in zip(slots, sorted(sc.refs[5])[::30]):
+            src[s], row[s] = i1, sc.rows[5][i1]
+        fr = copy.copy(sc.frames[a])
+        fr.keys, fr.uright, fr.depth = sc.frames[a].keys[src], sc.frames[a].uright[src], sc.frames[a].depth[src]
+        frames = list(sc.frames)
+        frames[a] = fr
+        big.poll_status()
+        got = DeviceBatch(big, frames).create([(a, b)], [row])
+        big.poll_status()
+        host = host_create(frames, [(a, b)], [row], cap=cap)
+        assert host[3] == 0
+        same_as_host(got, host[:3])
+        used = np.zeros(cap, bool)
+        used[slots] = True
+        assert (got[1][0][used] != 0).all() and not got[1][0][~used].any() and not got[0][0][~used].any()
+        for s, i1 in zip(slots, sorted(sc.refs[5])[::30]):               # and the slot's result is that of the match where the pool has it
+            assert got[1][0][s] == sc.refs[5][i1][0]
+    finally:
+        big.close()
+
+
 # ---- ComputeF12 -----------------------------------------------------------------------------------------------------------------------------------------
 def test_f12_pairs(ctx):
     import torch
