@@ -622,7 +622,7 @@ int olf_stereo_lines_dev(olf_ctx* c, int n_pairs, const olf_keyline* d_kls, cons
 {
     if (!c || !d_kls || !d_ldesc || !d_lcounts || !d_m12 || !d_disp || !d_le) { set_error("olf_stereo_lines_dev: null argument"); return OLF_ERR_INVALID; }
     OLF_TRY(check_device(c, "olf_stereo_lines_dev"));
-    if (n_pairs < 0 || 2 * n_pairs > c->max_images) return OLF_ERR_CAPACITY;
+    if (n_pairs < 0 || 2 * n_pairs > c->max_images) { set_error("olf_stereo_lines_dev: n_pairs exceeds the context's max_images"); return OLF_ERR_CAPACITY; }
     if (n_pairs == 0) return OLF_OK;
     hipStream_t s = ctx_stream(c, stream);
     // key lines / descriptors of a frame call whose line path is still running (deferred join): this stream waits for it first

@@ -102,7 +102,7 @@ int olf_stereo_lines(olf_ctx* c, int n_pairs, const olf_keyline* kls, const uint
                      double* le)
 {
     if (!c || !kls || !ldesc || !lcounts || !m12 || !disp || !le) { set_error("olf_stereo_lines: null argument"); return OLF_ERR_INVALID; }
-    if (n_pairs < 0 || 2 * n_pairs > c->max_images) return OLF_ERR_CAPACITY;
+    if (n_pairs < 0 || 2 * n_pairs > c->max_images) { set_error("olf_stereo_lines: n_pairs exceeds the context's max_images"); return OLF_ERR_CAPACITY; }
     if (n_pairs == 0) return OLF_OK;
     const size_t cap = c->line.geom.outCap, ni = 2 * (size_t)n_pairs;
     for (size_t i = 0; i < ni; ++i)

@@ -165,6 +165,7 @@ int launch_lsd_sort(const LineGeom& g, const LineDeviceBufs& b, int n_images, hi
 int launch_lsd_seedsort(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p, int n_images, hipStream_t s, int nOverride, int kthrOverride, int depthOverride);
 int launch_lsd_sort_wide(const LineGeom& g, const LineDeviceBufs& b, int n_images, hipStream_t s, int nOverride, long long kthrOverride, int depthOverride, int fullOverride);
 
+constexpr int kDistWaveMaxPairs = 256;       // pairs per call up to which a wave (k_lines_dist_w), not a thread (k_lines_dist), takes a right line
 size_t stereo_lines_prep_bytes(int n_images, int cap);
 int launch_stereo_lines(int W, int H, const olf_stereo_params& P, int n_pairs, const olf_keyline* d_kls, const uint8_t* d_desc,
                         const int* d_counts, int cap, void* d_prep, uint16_t* d_dist /* [pairs][cap][cap] */, int* d_m21, int* d_m12,

@@ -252,8 +252,6 @@ int launch_stereo_lines(int W, int H, const olf_stereo_params& P, int n_pairs, c
 {
     LinePrep* prep = reinterpret_cast<LinePrep*>(d_prep);
     hipLaunchKernelGGL(k_lines_prep, dim3((cap + 63) / 64, 2 * n_pairs), dim3(64), 0, s, d_kls, d_counts, cap, W, H, prep);
-    // pairs per call up to which a wave (not a thread) takes a right line
-    constexpr int kDistWaveMaxPairs = 256;
     if (n_pairs <= kDistWaveMaxPairs)
         hipLaunchKernelGGL(k_lines_dist_w, dim3((cap + 3) / 4, n_pairs), dim3(256), 0, s, prep, d_desc, d_counts, cap, P.matching_s_ws, P.line_sim_th,
                            P.best_lr_matches, d_dist, d_m21);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Regenerates tests/golden/reference_containers.npz and tests/golden/reference_config.json: what the reference's own
-STL-only code returns on the inputs of tests/test_oracle_cpu.py, and the defaults of its Config / KITTI settings file
+"""Regenerates tests/golden/reference_containers.npz, tests/golden/stereo_line_edges.npz and tests/golden/reference_config.json: what the
+reference's own STL-only code returns on the inputs of tests/test_oracle_cpu.py and on the border, cell-boundary, steep and clipped lines of
+tests/stereo_line_scenes.py (tests/test_stereo_lines_cpu.py), and the defaults of its Config / KITTI settings file
 that tests/test_host_cpu.py checks olf_default_params against.  The tests compare against these recorded results, so
 they do not need the reference checkout; where oracle/_ref is built they also check the live reference against them.
 
@@ -17,6 +18,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle_lib as oracle
+import stereo_line_scenes
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
@@ -37,6 +39,27 @@ def grid_query_trials():
         q = rng.integers(-2, 66, 4)
         out.append((segs, q))
     return out
+
+
+def stereo_line_edges(grid):
+    """getLineCoords' cell lists and GridStructure::get's candidates (iteration order included) on stereo_line_scenes.edge_inputs()"""
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    cases, trials = stereo_line_scenes.edge_inputs()
+    buf, xy, offs = np.zeros((4096, 2), np.int32), [], [0]
+    for x1, y1, x2, y2 in cases:
+        n = grid.ref_line_coords(C.c_double(x1), C.c_double(y1), C.c_double(x2), C.c_double(y2), P(buf), 4096)
+        xy.append(buf[:n].copy()); offs.append(offs[-1] + n)
+    rec = dict(line_cases=cases, line_xy=np.concatenate(xy), line_offs=np.array(offs, np.int64))
+    a = np.zeros(4096, np.int32)
+    for t, (segs, queries) in enumerate(trials):
+        cand, coffs = [], [0]
+        for spx, spy, epx, epy, ws in queries:
+            na = grid.ref_grid_query(48, 64, P(segs), len(segs), int(spx), int(spy), int(ws), 0, 0, 0, int(epx), int(epy), 1, P(a), 4096)
+            cand.append(a[:na].copy()); coffs.append(coffs[-1] + na)
+        rec.update({f"grid{t}_segs": segs, f"grid{t}_q": queries, f"grid{t}_cand": np.concatenate(cand), f"grid{t}_cand_offs": np.array(coffs, np.int64)})
+    rec["n_trials"] = np.int64(len(trials))
+    np.savez_compressed(os.path.join(GOLDEN, "stereo_line_edges.npz"), **rec)
+    return len(cases), sum(len(q) for _, q in trials)
 
 
 def bow_inputs():
@@ -106,6 +129,7 @@ def main(ref_checkout):
     rec.update({k: np.concatenate(v) for k, v in fields.items()})
     rec["bow_counts"] = np.array(counts, np.int64)
     np.savez_compressed(os.path.join(GOLDEN, "reference_containers.npz"), **rec)
+    n_edge_lines, n_edge_queries = stereo_line_edges(grid)
 
     # Config::Config() defaults (src/Config.cpp) and the KITTI settings file of the PL example, as name -> value
     text = open(os.path.join(ref_checkout, "src", "Config.cpp"), encoding="utf-8", errors="replace").read()
@@ -117,6 +141,7 @@ def main(ref_checkout):
     with open(os.path.join(GOLDEN, "reference_config.json"), "w") as f:
         json.dump({"Config.cpp": {k: cfg[k] for k in CONFIG_KEYS}, "PL_KITTI00-02.yaml": {k: kitti[k] for k in KITTI_KEYS}}, f, indent=1, sort_keys=True)
         f.write("\n")
+    print(n_edge_lines, "edge line cases,", n_edge_queries, "edge grid queries,")
     print(len(cases), "line cases,", len(qs), "grid queries,", len(combos), "BoW combinations,", len(CONFIG_KEYS), "Config defaults,", len(KITTI_KEYS), "KITTI settings")
 
 

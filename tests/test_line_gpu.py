@@ -218,6 +218,15 @@ def test_stereo_frames_odd_sizes(oracle, w, h):
         assert np.array_equal(g["mDescriptors_Line"], ol["desc"]) and np.array_equal(g["mDescriptorsRight_Line"], orr["desc"])
         m, disp, le = oracle.stereo_lines(ol["kls"], ol["desc"], orr["kls"], orr["desc"], w, h, p.stereo)
         assert np.array_equal(g["line_matches_12"], m) and np.array_equal(g["mvDisparity_l"].view(np.uint32), disp.view(np.uint32))
+    # key lines that sit on the border of this size (x == w and y == h included: cell column 64, row 48), which the extractor rarely delivers:
+    # constructed ones through the same context's stand-alone entry
+    import stereo_line_scenes as S
+    sc = S.border_scene(w, h)
+    gm, gdisp, gle = fe.stereo_lines(*S.pack([sc], fe.ctx.line_capacity))
+    m, disp, le = oracle.stereo_lines(*sc, w, h, p.stereo)
+    n = len(m)
+    assert np.array_equal(gm[0, :n], m) and np.array_equal(gdisp[0, :n].view(np.uint32), disp.view(np.uint32))
+    assert np.array_equal(gle[0, :n].view(np.uint64), le.view(np.uint64)) and (m >= 0).sum() >= 8
 
 
 @pytest.mark.parametrize("orb,line", [
