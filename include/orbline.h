@@ -237,7 +237,10 @@ int olf_debug_align_sweep(olf_ctx* ctx, uint64_t seed, int blocks, int per_threa
 /* Stereo point matching for n_pairs pairs whose ORB features (images 2p = left, 2p+1 = right) came from
  * the immediately preceding olf_orb_extract*_dev call on this context (its device-resident
  * mvImagePyramid of both extractors is read for the 11x11 SAD refinement, src/Frame.cc:799-816).
- * Outputs per pair, stride olf_orb_capacity(): mvuRight / mvDepth (-1 = no match), src/Frame.cc:704-705. */
+ * Outputs per pair, stride olf_orb_capacity(): mvuRight / mvDepth (-1 = no match), src/Frame.cc:704-705.
+ * The key points may be the caller's own (the buffers are read, only the pyramids come from the extractor call), as long as every SAD window
+ * stays inside its level as the extractor's would.  A context whose olf_orb_capacity() exceeds 32768 is refused with OLF_ERR_CAPACITY before
+ * anything is launched: the row sort and the median sort hold one image's keys in LDS. */
 int olf_stereo_points_dev(olf_ctx* ctx, int n_pairs, const olf_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_counts,
                           float* d_uright, float* d_depth, void* stream);
 /* host convenience: ExtractORB x2 + ComputeStereoMatches for n_pairs pairs (images: 2*n_pairs) */

@@ -57,6 +57,32 @@ int orc_stereo_points(const uint8_t* imgL, const uint8_t* imgR, int w, int h, co
     return OLF_OK;
 }
 
+// ComputeStereoMatches on the CALLER's key points and descriptors: both pyramids come from orb_extract (whose own key points are
+// discarded), everything else from the arguments.  Outputs uRight / depth / sad [nL]; nL == 0 leaves them untouched
+// (Frame ctor returns early, src/Frame.cc:176-177).
+int orc_stereo_match_keys(const uint8_t* imgL, const uint8_t* imgR, int w, int h, const olf_params* p,
+                          const olf_keypoint* kpsL, const uint8_t* descL, int nL, const olf_keypoint* kpsR, const uint8_t* descR, int nR,
+                          float* uRight, float* depth, int* sad)
+{
+    if (nL < 0 || nR < 0) return OLF_ERR_INVALID;
+    if (nL == 0) return OLF_OK;
+    Image L(w, h), R(w, h);
+    std::memcpy(L.d.data(), imgL, (size_t)w * h);
+    std::memcpy(R.d.data(), imgR, (size_t)w * h);
+    OrbResult rl, rr;
+    orb_extract(L, p->orb, rl);
+    orb_extract(R, p->orb, rr);
+    std::vector<olf_keypoint> kl(kpsL, kpsL + nL), kr(kpsR, kpsR + nR);
+    for (const olf_keypoint& k : kl) if (k.octave < 0 || k.octave >= p->orb.nlevels) return OLF_ERR_INVALID;
+    for (const olf_keypoint& k : kr) if (k.octave < 0 || k.octave >= p->orb.nlevels) return OLF_ERR_INVALID;
+    std::vector<float> sf, inv_sf, u, d;
+    std::vector<int> s;
+    orb_scale_tables(p->orb, sf, inv_sf);
+    compute_stereo_matches(kl, descL, kr, descR, rl.pyramid, rr.pyramid, sf, inv_sf, p->stereo.bf, p->stereo.fx, u, d, &s);
+    for (int i = 0; i < nL; ++i) { uRight[i] = u[i]; depth[i] = d[i]; if (sad) sad[i] = s[i]; }
+    return OLF_OK;
+}
+
 // The whole feature part of Frame::Frame (stereo + lines), src/Frame.cc:136-221.  threads = 4 runs the four
 // extractions on std::threads exactly like src/Frame.cc:164-171 (the cpu_baseline "reference-shaped" mode);
 // threads = 1 runs them back to back.  Any output pointer may be null.

@@ -190,7 +190,8 @@ __global__ __launch_bounds__(256) void k_stereo_match(const OrbGeom* __restrict_
 #pragma unroll
             for (int k = 0; k < 2; ++k) a[k] = lane + 64 * k < 121 ? araw[k] - cL : 0;
             __builtin_amdgcn_wave_barrier();
-            // the 11 sums of absolute differences: per lane two shifts' partial sums share a dword (a sum is below 121 * 255 < 2^15), six wave sums through
+            // the 11 sums of absolute differences: per lane two shifts' partial sums share a dword (a difference is |(IL - cL) - (IR - cR)| <= 510 and
+            // the centre pixel's is 0, so a sum is at most 120 * 510 = 61200 < 2^16: it fits with nothing to spare), six wave sums through
             // DPP instead of eleven butterflies through the LDS crossbar (66 dependent ds_bpermute per key point were most of the kernel's latency)
             int part[11];
 #pragma unroll
@@ -593,23 +594,32 @@ int launch_distinctive(const uint8_t* desc, const int* offs, int n_points, int* 
 }
 
 // ---------------------------------------------------------------------------------------------
+constexpr int kStereoSortMax = 32768;    // keys of one LDS sort: 128 KB, beside k_stereo_median's 4 static bytes inside the CU's 160 KB
 int launch_stereo_points(const OrbGeom& g, const OrbDeviceBufs& b, int n_pairs, const olf_keypoint* d_kps, const uint8_t* d_desc,
                          const int* d_counts, int cap, float mbf, float fx, float* d_uRight, float* d_depth, int* d_sad, int* d_bestKey,
                          unsigned* d_perm /* [2 * n_pairs][cap] */, hipStream_t s)
 {
-    if (cap > 65534) { set_error("stereo points: more than 65534 key points per image"); return OLF_ERR_CAPACITY; }   // 16-bit indices in the keys
+    // k_stereo_rowsort and k_stereo_median sort next_pow2(cap) 32-bit keys in dynamic LDS: up to 16384 key points per image fit the 64 KB a launch may ask
+    // for by default, up to 32768 (128 KB of the CU's 160 KB) once the limit is raised, more do not fit at all (and 16-bit indices end at 65534)
+    if (cap > kStereoSortMax) {
+        set_error("stereo points: more than 32768 key points per image (the row and median sorts hold one image's keys in LDS)");
+        return OLF_ERR_CAPACITY;
+    }
     // d_sad doubles as the (distance, index) scratch of the candidate search until k_stereo_match overwrites it per key point
     unsigned* bestKey = reinterpret_cast<unsigned*>(d_bestKey);
     int sortK = 64;
     while (sortK < cap) sortK <<= 1;
+    if (sortK * sizeof(unsigned) > 64 * 1024) {
+        // the attribute belongs to the (function, device) pair: set it on whichever device this launch goes to
+        OLF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_rowsort), hipFuncAttributeMaxDynamicSharedMemorySize, kStereoSortMax * (int)sizeof(unsigned)));
+        OLF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_median), hipFuncAttributeMaxDynamicSharedMemorySize, kStereoSortMax * (int)sizeof(unsigned)));
+    }
     hipLaunchKernelGGL(k_stereo_rowsort, dim3(2 * n_pairs), dim3(256), sortK * sizeof(unsigned), s, d_kps, d_counts, cap, sortK, d_perm);
     hipLaunchKernelGGL(k_stereo_cand, dim3((cap + 255) / 256, n_pairs), dim3(256), 0, s, b.geom, d_kps, d_desc, d_counts, cap, mbf, fx, d_perm,
                        bestKey);
     hipLaunchKernelGGL(k_stereo_match, dim3((cap + 3) / 4, n_pairs), dim3(256), 0, s, b.geom, b.pyr, d_kps, d_desc, d_counts, cap, mbf,
                        fx, bestKey, d_uRight, d_depth, d_sad);
-    int sortN = 64;
-    while (sortN < cap) sortN <<= 1;
-    hipLaunchKernelGGL(k_stereo_median, dim3(n_pairs), dim3(256), sortN * sizeof(unsigned), s, d_counts, cap, sortN, d_uRight, d_depth,
+    hipLaunchKernelGGL(k_stereo_median, dim3(n_pairs), dim3(256), sortK * sizeof(unsigned), s, d_counts, cap, sortK, d_uRight, d_depth,
                        d_sad);
     OLF_HIP_CHECK(hipGetLastError());
     return OLF_OK;

@@ -66,6 +66,41 @@ class StereoFrontEnd:
         f.mvuRight, f.mvDepth = ur, dp
         return f
 
+    def stereo_points_on(self, images, kps, desc, counts, fill=None):
+        """ComputeStereoMatches on the CALLER's key points: images (2*n_pairs, H, W) uint8 go through olf_orb_extract_dev (which leaves their pyramids in
+        the context), its key point, descriptor and count buffers are overwritten with kps (2*n_pairs, capacity) / desc (2*n_pairs, capacity, 32) /
+        counts (2*n_pairs,), and olf_stereo_points_dev runs on those.  fill: value the two outputs hold before the call.
+        Returns (mvuRight, mvDepth), each (n_pairs, capacity)."""
+        import torch
+        from .matcher import _torch_stream
+        images = np.ascontiguousarray(images)
+        n = images.shape[0]
+        cap = self.ctx.orb_capacity
+        if images.dtype != np.uint8 or images.shape[1:] != (self.height, self.width) or n % 2 or n > 2 * self.max_pairs:
+            raise TypeError("stereo_points_on: (2*n_pairs, H, W) uint8 images of the context's size expected")
+        kps, desc = np.ascontiguousarray(kps, KEYPOINT_DTYPE), np.ascontiguousarray(desc, np.uint8)
+        counts = np.ascontiguousarray(counts, np.int32)
+        if kps.shape != (n, cap) or desc.shape != (n, cap, DESC_BYTES) or counts.shape != (n,) or counts.min(initial=0) < 0 or counts.max(initial=0) > cap:
+            raise ValueError("stereo_points_on: kps (n, capacity), desc (n, capacity, 32), counts (n,) within the capacity expected")
+        d_img = torch.from_numpy(images).cuda()
+        d_kps = torch.zeros((n, cap, KEYPOINT_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+        d_desc = torch.zeros((n, cap, DESC_BYTES), dtype=torch.uint8, device="cuda")
+        d_counts = torch.zeros(n, dtype=torch.int32, device="cuda")
+        ur = torch.full((n // 2, cap), 0.0 if fill is None else float(fill), dtype=torch.float32, device="cuda")
+        dp = ur.clone()
+        with _torch_stream() as s:
+            check(lib().olf_orb_extract_dev(self.ctx.handle, d_img.data_ptr(), n, d_kps.data_ptr(), d_desc.data_ptr(), d_counts.data_ptr(), s),
+                  "olf_orb_extract_dev")
+        # (each `with` ends device-wide synchronised when torch is on its default stream: the copies land after the extractor's own results)
+        d_kps.copy_(torch.from_numpy(kps.view(np.uint8).reshape(n, cap, -1)))
+        d_desc.copy_(torch.from_numpy(desc))
+        d_counts.copy_(torch.from_numpy(counts))
+        with _torch_stream() as s:
+            check(lib().olf_stereo_points_dev(self.ctx.handle, n // 2, d_kps.data_ptr(), d_desc.data_ptr(), d_counts.data_ptr(), ur.data_ptr(),
+                                              dp.data_ptr(), s), "olf_stereo_points_dev")
+        torch.cuda.synchronize()
+        return ur.cpu().numpy(), dp.cpu().numpy()
+
     def stereo_lines(self, kls, ldesc, lcounts):
         """ComputeStereoMatches_Lines on already extracted key lines: kls (2*n_pairs, cap), ldesc, lcounts."""
         kls, ldesc = np.ascontiguousarray(kls), np.ascontiguousarray(ldesc)

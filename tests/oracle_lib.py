@@ -143,6 +143,20 @@ def stereo_points(imgL, imgR, p, cap=None):
     return dict(kpsL=kl[:n], descL=dl[:n], kpsR=kr[:m], descR=dr[:m], uRight=ur[:n], depth=dp[:n], sad=sad[:n])
 
 
+def stereo_match_keys(imgL, imgR, p, kpsL, descL, kpsR, descR):
+    """ComputeStereoMatches on the caller's key points (the images only supply the two pyramids): dict(uRight, depth, sad) [nL]."""
+    imgL = np.ascontiguousarray(imgL); imgR = np.ascontiguousarray(imgR)
+    h, w = imgL.shape
+    kpsL, kpsR = np.ascontiguousarray(kpsL, KEYPOINT_DTYPE), np.ascontiguousarray(kpsR, KEYPOINT_DTYPE)
+    descL, descR = np.ascontiguousarray(descL, np.uint8).reshape(-1, 32), np.ascontiguousarray(descR, np.uint8).reshape(-1, 32)
+    nL, nR = len(kpsL), len(kpsR)
+    assert len(descL) == nL and len(descR) == nR
+    ur, dp, sad = np.full(nL, -1, np.float32), np.full(nL, -1, np.float32), np.full(nL, -1, np.int32)
+    rc = _L.orc_stereo_match_keys(_p(imgL), _p(imgR), w, h, C.byref(p), _p(kpsL), _p(descL), nL, _p(kpsR), _p(descR), nR, _p(ur), _p(dp), _p(sad))
+    assert rc == 0, rc
+    return dict(uRight=ur, depth=dp, sad=sad)
+
+
 def lsd_detect(img, lp, cap=20000):
     img = np.ascontiguousarray(img)
     h, w = img.shape

@@ -32,6 +32,17 @@ def test_bad_arguments_are_reported():
     bad = _lib.default_params(); bad.orb.nfeatures = 2500; bad.orb.nlevels = 1
     assert L.olf_ctx_create(C.byref(bad), 640, 480, 1, C.byref(h)) == OLF_OK                                  # (round 1 refused this: 2500 key points on one level)
     L.olf_ctx_destroy(h)
+    big = _lib.default_params(); big.orb.nfeatures = 40000                                                  # ORB alone works on such a context; stereo matching sorts one
+    bctx = _lib.Context(big, 640, 480, 2)                                                                   # image's keys in LDS: more than 32768 do not fit and are refused
+    import torch                                                                                            # before any launch
+    bcap = bctx.orb_capacity
+    assert bcap > 32768
+    dk, dd = torch.zeros((2, bcap, 28), dtype=torch.uint8, device="cuda"), torch.zeros((2, bcap, 32), dtype=torch.uint8, device="cuda")
+    dc, du = torch.zeros(2, dtype=torch.int32, device="cuda"), torch.full((2, bcap), -7.0, device="cuda")
+    torch.cuda.synchronize()
+    assert L.olf_stereo_points_dev(bctx.handle, 1, dk.data_ptr(), dd.data_ptr(), dc.data_ptr(), du[0].data_ptr(), du[1].data_ptr(), None) == OLF_ERR_CAPACITY
+    assert b"32768" in L.olf_last_error() and bctx.synchronize() is None and bool((du == -7.0).all())
+    bctx.close()
     ctx = _lib.Context(p, 640, 480, 2)
     img = np.zeros((4, 480, 640), np.uint8)
     cap, lcap = ctx.orb_capacity, ctx.line_capacity

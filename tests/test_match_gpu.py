@@ -80,3 +80,51 @@ def test_distinctive_descriptors(oracle):
     with pytest.raises(Exception):
         matcher.ComputeDistinctiveDescriptors([np.zeros((1025, 32), np.uint8)])
     assert len(matcher.ComputeDistinctiveDescriptors([])) == 0
+
+
+def test_match_bf_dev_batched_interleaved(oracle):
+    """olf_match_bf_dev as the frame-to-frame matcher calls it: 8 sets in one launch, descriptors and counts of every second image of a buffer whose
+    rows are 4100 descriptors long (a_step = b_step = 2, set s = image 2(s+1) of A against image 2s of B), per-set counts from empty to the 12-bit and
+    16-bit key paths side by side.  Rows past a set's count hold the other side's descriptors: distance 0, they would win if read."""
+    import torch
+    from orb_line_slam_amd._lib import check, lib
+    counts_ab = [(0, 5), (5, 0), (1, 1), (2, 1), (1, 2), (33, 31), (300, 4096), (257, 4097)]
+    n_sets, stride, n_img = len(counts_ab), 4100, 2 * len(counts_ab) + 2
+    rng = np.random.default_rng(77)
+    A, B = np.zeros((n_img, stride, 32), np.uint8), np.zeros((n_img, stride, 32), np.uint8)
+    cA, cB = np.full(n_img, 4000, np.int32), np.full(n_img, 4000, np.int32)      # (the images between the sets: never read)
+    sets = []
+    for s, (na, nb) in enumerate(counts_ab):
+        a, b = _rand_desc(rng, na, dup=na // 8), _rand_desc(rng, nb, dup=nb // 8)
+        for i in range(0, min(na, nb), 2):               # every second query is a train row with a few bits flipped: real matches exist
+            a[i] = b[(7 * i) % nb]
+            for bit in rng.integers(0, 256, i % 5):
+                a[i, bit >> 3] ^= np.uint8(1 << (bit & 7))
+        if na >= 2:
+            a[0], a[1] = 0, 255                          # all-zero and all-one rows: distances 0 and 256 occur
+        if nb >= 2:
+            b[0], b[1] = 255, 0
+        if na >= 4 and nb >= 4:
+            b[2] = b[3] = a[2]                           # exact duplicates: the lower train index wins, and the ratio test sees d0 == d1 == 0
+            a[3] = a[2]
+        ia, ib = 2 * (s + 1), 2 * s
+        A[ia], B[ib] = rng.integers(0, 256, (stride, 32)), rng.integers(0, 256, (stride, 32))
+        A[ia, :na], B[ib, :nb] = a, b
+        ka, kb = min(stride - na, nb), min(stride - nb, na)
+        A[ia, na:na + ka], B[ib, nb:nb + kb] = b[:ka], a[:kb]
+        cA[ia], cB[ib] = na, nb
+        sets.append((a, b))
+    dA, dB, dcA, dcB = (torch.from_numpy(x).cuda() for x in (A, B, cA, cB))
+    ctx = matcher._ctx(None)
+    for nnr in (0.75, 0.9):
+        for lr in (1, 0):
+            m12 = torch.full((n_sets, 2 * stride), -5, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            check(lib().olf_match_bf_dev(ctx.handle, dA.data_ptr() + 2 * stride * 32, dcA.data_ptr() + 8, 2 * stride, 2, dB.data_ptr(), dcB.data_ptr(),
+                                         2 * stride, 2, n_sets, nnr, lr, m12.data_ptr(), None), "olf_match_bf_dev")
+            ctx.synchronize()
+            got = m12.cpu().numpy()
+            for s, (a, b) in enumerate(sets):
+                assert np.array_equal(got[s, :len(a)], oracle.match_bf(a, b, nnr, bool(lr))), (s, nnr, lr)
+                assert (got[s, len(a):] == -5).all(), s
+    assert (oracle.match_bf(sets[6][0], sets[6][1], 0.9, True) >= 0).sum() > 5
