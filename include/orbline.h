@@ -1166,6 +1166,98 @@ int olf_debug_sim3_solver_gate(float scale_factor, uint64_t* gate);
 /* tests: the iteration cap the solver's table holds for N correspondences (csrc/sim3solver_terms.hpp: s3_iteration_cap) */
 int olf_debug_sim3_solver_cap(int N, double probability, int min_inliers, int max_iterations, int32_t* cap);
 
+/* ---- PnPsolver's RANSAC for a list of (key frame, frame) pairs on the device (csrc/pnpsolver_batch.hip) --------------------------------------------------
+ * PnPsolver (src/PnPsolver.cc: EPnP inside a RANSAC) as Tracking::Relocalization drives it per candidate key frame (src/Tracking.cc:2255-2308): the
+ * constructor's correspondences (:67-110), SetRansacParameters(probability, min_inliers, max_iterations, min_set, epsilon, th2) (:121-157; the tracker:
+ * 0.99, 10, 300, 4, 0.5, 5.991) and one iterate(n_iterations, ...) per call (:165-258) with Refine (:260-305), for n_pairs pairs of the n_frames frames of
+ * a batch.  It stands between olf_search_by_bow_pairs_dev (form OLF_BOW_KF_FRAME), whose rows it reads, and olf_search_by_projection_kf_pairs_dev, whose
+ * d_Tcw takes Tcw; olf_pnp_apply_inliers_dev does :2297-2308 between them.  Optimizer::PoseOptimization (:2310) stays on the host.  Results equal
+ * olf_pnp_solver pair by pair, bit for bit, and do not depend on scheduling, on how the kernel chunks a window or on a pair's position in the list.
+ * `in`: kps (pt of the frame's features, octave), counts, img_stride, mp_world and mp_valid of the key frame (NULL: every feature holds a point) and fx,
+ * fy, cx, cy are read (frame j = image j * img_stride; a count beyond the capacity is read as the capacity); mvLevelSigma2 is the context's.  d_mp_bad
+ * [n_frames][capacity] (or NULL: none is bad): isBad() of the point a feature holds.  d_pairs [n_pairs][2] = (key frame, frame), as the BoW form orders
+ * them.  d_matches [n_pairs][capacity], read only: exactly the row olf_search_by_bow_pairs_dev writes; value v at frame feature i < N_frame is a
+ * correspondence iff 0 <= v < N_kf (-1, -2 and >= N_kf are all "none"), key-frame feature v holds a point and that point is not bad: the 2-D point is
+ * kps[i].pt, the 3-D point mp_world[kf][v], mvMaxError = sf * sf * th2 in float from the frame feature's octave.  Correspondences are kept in ascending i.
+ * One whose octave lies outside the context's levels is left out and sets bit 256 of the context's status word.
+ * olf_pnp_ransac: probability in (0, 1), min_inliers >= 1, max_iterations >= 1, min_set == 4, epsilon in (0, 1], th2 > 0, n_iterations >= 0: the window of
+ * this call (the tracker: 5; max_iterations gives find()).  The effective min_inliers (max(N * epsilon truncated, min_inliers, min_set)) and the iteration
+ * cap are functions of the number of correspondences alone; the call computes them for every N in [0, capacity] on the host with the host's libm
+ * (csrc/pnpsolver_terms.hpp: pnp_parameters -- the exponent of epsilon is 3 as in the reference) and the kernel looks them up.
+ * The loop condition of iterate (:182) is an OR: a call runs until the cap is reached AND n_iterations of its own are done, unless it accepts first; so
+ * every call that does not accept ends with no_more = 1, and a call beyond the cap still runs n_iterations.
+ * d_draws [n_pairs][max_iterations][4] (uint32): the raw rand() values below 2^31 of every iteration (convention C.20; bit 31 is ignored), indexed by
+ * ABSOLUTE iteration modulo max_iterations (C.26), so a resumed call reads on where the last one stopped.
+ * olf_pnp_solver_io, device pointers, one element or row per pair.  In and out -- the solver's carried state, all zero for a new solver: iterations_done
+ * (mnIterations), best_inliers (mnBestInliers), best_Tcw [16] (mBestTcw, row-major), best_flags [capacity] (mvbBestInliers, uint8, by frame feature;
+ * only features that are correspondences are written), and Refine's outcome for the current best set -- Refine is a function of that set alone, so it
+ * runs when the best changes and is carried: refined_inliers (mnRefinedInliers), refined_Tcw [16], refined_flags [capacity].  An iteration with
+ * n >= min_inliers and n > best_inliers replaces the best; the first iteration with n >= min_inliers whose best set's refined_inliers > min_inliers
+ * (strict, :292) is accepted and ends the call -- so a solver that has accepted accepts again at the next such iteration (Tracking.cc:2312 `continue`).
+ * Out: accepted (the returned pose is not empty: Refine accepted, or the cap was reached with best_inliers >= min_inliers, :241-255), no_more (bNoMore),
+ * n_inliers (0 unless accepted), inliers [n_pairs][capacity] (uint8, by frame feature; positions below N_frame are written, all 0 unless accepted;
+ * positions from N_frame on are left as they are), Tcw [16] (written only when accepted: refined_Tcw, or best_Tcw at the cap), n_correspondences (N), and
+ * counts [n_pairs][max_iterations] (may be NULL): the inlier count of every iteration this call evaluated at its index modulo max_iterations, the others
+ * untouched.  N < the effective min_inliers: no_more = 1 and the state is untouched.
+ * Arithmetic (csrc/pnpsolver_terms.hpp, one text for this entry and its host form; C.4, C.19, C.20, C.23 to C.26 of DESIGN.md): compute_pose in double as
+ * written; the OpenCV calls as an OpenCV without LAPACK makes them (one-sided Jacobi in double; cvSolve / cvInvert skip singular values at or below
+ * 2 DBL_EPSILON times their sum); qr_solve's singular return leaves x at 0 in the first Gauss-Newton round; sums over the correspondences in the
+ * reference's order in a four-point fit and in a fixed blocked order in Refine (256 partial sums by index modulo 256, a balanced tree of neighbours per
+ * 64, the four results in ascending order).  OpenCV's fill of a singular vector whose norm is <= DBL_MIN from its fixed-seed generator is NOT restated:
+ * a hypothesis that would read such a vector (the PCA of the control points, M^t M, ABt) counts no inlier, a Refine that would fails, and bit 32768 of the
+ * context's status word is set (the status text names the bit by number only).
+ * A pair whose index lies outside [0, n_frames), or with both indices equal, gets n_inliers = -1, nothing else of it is written, and bit 2048 is set.
+ * Errors, before any launch: a NULL required pointer, a negative count, min_set != 4, epsilon outside (0, 1], th2 <= 0, min_inliers < 1,
+ * max_iterations < 1, n_iterations < 0 or probability outside (0, 1): OLF_ERR_INVALID.  n_pairs == 0 writes nothing.  Does not synchronise; runs on
+ * `stream`.  Nothing is read or written out of bounds.
+ * Scratch: 8 bytes per feature of the capacity (+ 8) and, where 32 bytes per feature of the capacity exceed the 46 KiB of LDS a workgroup has beside
+ * its fit workspaces, that much per resident workgroup (at most 1024). */
+typedef struct olf_pnp_ransac {
+    double  probability;
+    int32_t min_inliers, max_iterations, min_set, n_iterations;
+    float   epsilon, th2;
+} olf_pnp_ransac;
+typedef struct olf_pnp_solver_io {
+    int32_t* iterations_done;    /* [n_pairs]            in / out */
+    int32_t* best_inliers;       /* [n_pairs]            in / out */
+    float*   best_Tcw;           /* [n_pairs][16]        in / out */
+    uint8_t* best_flags;         /* [n_pairs][capacity]  in / out */
+    int32_t* refined_inliers;    /* [n_pairs]            in / out */
+    float*   refined_Tcw;        /* [n_pairs][16]        in / out */
+    uint8_t* refined_flags;      /* [n_pairs][capacity]  in / out */
+    int32_t* accepted;           /* [n_pairs] */
+    int32_t* no_more;            /* [n_pairs] */
+    int32_t* n_inliers;          /* [n_pairs] */
+    uint8_t* inliers;            /* [n_pairs][capacity] */
+    float*   Tcw;                /* [n_pairs][16]: d_Tcw of olf_search_by_projection_kf_pairs_dev */
+    int32_t* n_correspondences;  /* [n_pairs] */
+    int32_t* counts;             /* [n_pairs][max_iterations], or NULL */
+} olf_pnp_solver_io;
+int olf_pnp_solver_pairs_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const uint8_t* d_mp_bad, int n_pairs, const int32_t* d_pairs,
+                             const int32_t* d_matches, const olf_pnp_ransac* ransac, const uint32_t* d_draws, const olf_pnp_solver_io* io, void* stream);
+/* Tracking.cc:2297-2308 for every pair with accepted > 0 (d_n_inliers < 0, a refused pair, or accepted <= 0: its rows stay as they are), for i in
+ * [0, capacity): d_out[p][i] = d_matches[p][i] where d_inliers[p][i] is set and i < N_frame, -1 elsewhere (d_out may be d_matches itself);
+ * d_cur_valid[p][i] = 1 / 0 likewise; d_already_found[p][v] = 1 for every such inlier's key-frame feature v, 0 elsewhere.  These are d_cur_valid and
+ * d_already_found of olf_search_by_projection_kf_pairs_dev, whose pairs are ordered (current frame, key frame).  Any of the three outputs may be NULL.
+ * `in`: counts and img_stride are read.  Does not synchronise. */
+int olf_pnp_apply_inliers_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, int n_pairs, const int32_t* d_pairs, const int32_t* d_matches,
+                              const uint8_t* d_inliers, const int32_t* d_accepted, const int32_t* d_n_inliers, int32_t* d_out, uint8_t* d_cur_valid,
+                              uint8_t* d_already_found, void* stream);
+/* the host form: ONE pair (kf, frame), host pointers in `in` and everywhere else, no context and no device, the loop of PnPsolver::iterate.  capacity: the
+ * row length of the per-frame planes; scale_factors [n_levels] = mvScaleFactors; matches [capacity], draws [max_iterations][4]; every pointer of io names
+ * this pair's element or row; *status receives the bits 256 / 2048 / 32768. */
+int olf_pnp_solver(const olf_track_batch* in, int capacity, int n_frames, const uint8_t* mp_bad, const float* scale_factors, int n_levels, int kf, int frame,
+                   const int32_t* matches, const olf_pnp_ransac* ransac, const uint32_t* draws, const olf_pnp_solver_io* io, int32_t* status);
+/* olf_pnp_solver_pairs_dev from host pointers ON THE DEVICE (csrc/pnpsolver_api.cpp): the arrays are staged (the in / out state and the outputs are
+ * uploaded first), the same kernel runs on the context's stream, state and outputs come back; synchronises.  A set status bit makes the call return
+ * OLF_ERR_CAPACITY, the outputs complete. */
+int olf_pnp_solver_pairs(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const uint8_t* mp_bad, int n_pairs, const int32_t* pairs,
+                         const int32_t* matches, const olf_pnp_ransac* ransac, const uint32_t* draws, const olf_pnp_solver_io* io);
+/* tests: the LDS a workgroup of the solver may take for its correspondences (bytes; above it they live in context scratch; <= 0 restores the default),
+ * and the parameters the solver's table holds for N correspondences (csrc/pnpsolver_terms.hpp: pnp_parameters) */
+int olf_debug_pnp_solver_lds_limit(int bytes);
+int olf_debug_pnp_solver_parameters(int N, const olf_pnp_ransac* ransac, int32_t* min_inliers, int32_t* cap);
+
 /* measurement: rate of a plain 16-byte-per-thread device copy kernel over `bytes` (read + written bytes per second): the practical HBM
  * ceiling bench.py reports next to the specification's 8 TB/s */
 int olf_debug_copy_bandwidth(olf_ctx* ctx, size_t bytes, int reps, double* gbytes_per_s);

@@ -1463,4 +1463,170 @@ void Sim3SolversIterate(olf_ctx* c, const std::vector<Sim3SolverOf<KeyFrameT, Ma
     }
 }
 
+// ---- PnPsolver (include/PnPsolver.h, src/PnPsolver.cc) over the reference's own types ------------------------------------------------------------------------
+// The reference's members with its signatures: the constructor (F, vpMapPointMatches), SetRansacParameters, iterate and find.  It runs over the host form
+// olf_pnp_solver, so a single solver needs no device.  The constructor keeps the correspondences as :79-101 does; the C entry's per-feature model (a row
+// from frame feature to key-frame feature) is met by laying the kept correspondences out as the features 0 .. N - 1 of two frames of their own: frame 0
+// holds the points, frame 1 the key points.  Reads mvKeysUn, mvScaleFactors (mvLevelSigma2 = their squares) and fx, fy, cx, cy of the frame, isBad() and
+// GetWorldPos() of the points.  The random stream: the reference draws from the global rand() iteration by iteration; here
+// SetRansacParameters draws all max_iterations x 4 values with rand() at once, and an iteration reads its own (modulo max_iterations, C.26).
+template <class FrameT, class MapPointT>
+class PnPsolverOf {
+public:
+    typedef typename std::decay<decltype(std::declval<FrameT>().mTcw)>::type MatT;
+
+    PnPsolverOf(const FrameT& F, const std::vector<MapPointT*>& vpMapPointMatches) : mnMatches((int)vpMapPointMatches.size())
+    {
+        std::vector<float> w;
+        std::vector<olf_keypoint> keys;
+        for (int i = 0; i < mnMatches; i++) {
+            MapPointT* pMP = vpMapPointMatches[i];
+            if (!pMP || pMP->isBad()) continue;
+            olf_keypoint k;
+            std::memcpy(&k, olf_detail::keypoints(F.mvKeysUn) + i, sizeof k);
+            keys.push_back(k);
+            const auto X = pMP->GetWorldPos();
+            for (int c = 0; c < 3; ++c) w.push_back(X.template at<float>(c));
+            mvKeyPointIndices.push_back(i);
+        }
+        N = (int)mvKeyPointIndices.size();
+        mCap = std::max(N, 1);
+        mKeys.assign(2 * (size_t)mCap, olf_keypoint());
+        mWorld.assign(6 * (size_t)mCap, 0.0f);
+        mRow.assign(mCap, -1);
+        for (int q = 0; q < N; ++q) {
+            mKeys[(size_t)mCap + q] = keys[q]; mRow[q] = q;
+            for (int c = 0; c < 3; ++c) mWorld[3 * (size_t)q + c] = w[3 * (size_t)q + c];
+        }
+        for (size_t l = 0; l < F.mvScaleFactors.size(); ++l) mSf.push_back(F.mvScaleFactors[l]);
+        fx = F.fx; fy = F.fy; cx = F.cx; cy = F.cy;
+        mBestFlags.assign(mCap, 0); mRefinedFlags.assign(mCap, 0); mInliers.assign(mCap, 0);
+        std::memset(mBestTcw, 0, sizeof mBestTcw); std::memset(mRefinedTcw, 0, sizeof mRefinedTcw); std::memset(mTcw, 0, sizeof mTcw);
+        SetRansacParameters();
+    }
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4, float th2 = 5.991)
+    {
+        mRansac.probability = probability; mRansac.min_inliers = minInliers; mRansac.max_iterations = maxIterations; mRansac.min_set = minSet;
+        mRansac.n_iterations = 0; mRansac.epsilon = epsilon; mRansac.th2 = th2;
+        mDraws.resize(4 * (size_t)std::max(maxIterations, 0));
+        for (size_t k = 0; k < mDraws.size(); ++k) mDraws[k] = (uint32_t)rand() & 0x7fffffffu;
+    }
+
+    MatT iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers)
+    {
+        olf_track_batch in;
+        const int32_t counts[2] = {N, N};
+        olf_fill_batch(in, counts);
+        mRansac.n_iterations = std::max(nIterations, 0);
+        int32_t status = 0;
+        const olf_pnp_solver_io io = olf_io();
+        olf_detail::check(olf_pnp_solver(&in, mCap, 2, nullptr, mSf.data(), (int)mSf.size(), 0, 1, mRow.data(), &mRansac, mDraws.data(), &io, &status), "olf_pnp_solver");
+        return olf_results(bNoMore, vbInliers, nInliers);
+    }
+
+    MatT find(std::vector<bool>& vbInliers, int& nInliers)            // iterate(mRansacMaxIts, ...) with the cap SetRansacParameters adjusted to N (:159-163)
+    {
+        bool bFlag;
+        int32_t m = 0, cap = 1;
+        olf_detail::check(olf_debug_pnp_solver_parameters(N, &mRansac, &m, &cap), "olf_debug_pnp_solver_parameters");
+        return iterate(cap, bFlag, vbInliers, nInliers);
+    }
+
+    // ---- what the batched free function below reads and writes (olf_ prefix: not members of the reference's class)
+    void olf_fill_batch(olf_track_batch& in, const int32_t* counts) const
+    {
+        std::memset(&in, 0, sizeof in);
+        in.kps = mKeys.data(); in.counts = counts; in.img_stride = 1; in.mp_world = mWorld.data();
+        in.fx = fx; in.fy = fy; in.cx = cx; in.cy = cy;
+    }
+    olf_pnp_solver_io olf_io()
+    {
+        const olf_pnp_solver_io io = {&mnIterations, &mnBestInliers, mBestTcw, mBestFlags.data(), &mnRefinedInliers, mRefinedTcw, mRefinedFlags.data(), &mAccepted,
+                                      &mNoMore, &mnInliers, mInliers.data(), mTcw, &mNCorr, nullptr};
+        return io;
+    }
+    MatT olf_results(bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers)
+    {
+        bNoMore = mNoMore != 0;
+        vbInliers.clear();
+        nInliers = mAccepted ? mnInliers : 0;
+        if (!mAccepted) return MatT();
+        vbInliers = std::vector<bool>(mnMatches, false);
+        for (int q = 0; q < N; ++q) if (mInliers[q]) vbInliers[mvKeyPointIndices[q]] = true;
+        MatT T(4, 4, 5 /* CV_32F */);
+        for (int r = 0; r < 4; ++r) for (int k = 0; k < 4; ++k) T.template at<float>(r, k) = mTcw[4 * r + k];
+        return T;
+    }
+
+    int mnMatches, N = 0, mCap = 1;
+    float fx, fy, cx, cy;
+    olf_pnp_ransac mRansac;
+    std::vector<int> mvKeyPointIndices;
+    std::vector<olf_keypoint> mKeys;                                 // both frames at the row length mCap: frame 1 holds the kept key points
+    std::vector<float> mWorld, mSf;                                  // frame 0 holds the kept points
+    std::vector<int32_t> mRow;
+    std::vector<uint32_t> mDraws;
+    std::vector<uint8_t> mBestFlags, mRefinedFlags, mInliers;
+    int32_t mnIterations = 0, mnBestInliers = 0, mnRefinedInliers = 0, mAccepted = 0, mNoMore = 0, mnInliers = 0, mNCorr = 0;
+    float mBestTcw[16], mRefinedTcw[16], mTcw[16];
+};
+
+// One round of Tracking::Relocalization's loop (src/Tracking.cc:2267-2308) for a vector of candidates: iterate(nIterations, ...) of every solver in one call
+// of the device entry (olf_pnp_solver_pairs through context c, whose capacity must hold every solver's correspondences and whose level table must be the
+// frame's).  The solvers share their RANSAC parameters, calibration and levels (one Relocalization sets them alike).  Every solver's state advances as its
+// own iterate would advance it; vTcw[i] is empty unless solver i returned a pose.
+template <class FrameT, class MapPointT>
+void PnPsolversIterate(olf_ctx* c, const std::vector<PnPsolverOf<FrameT, MapPointT>*>& vpSolvers, int nIterations, std::vector<bool>& vbNoMore,
+                       std::vector<std::vector<bool> >& vvbInliers, std::vector<int>& vnInliers,
+                       std::vector<typename PnPsolverOf<FrameT, MapPointT>::MatT>& vTcw)
+{
+    const size_t n = vpSolvers.size();
+    vbNoMore.assign(n, false); vvbInliers.assign(n, std::vector<bool>()); vnInliers.assign(n, 0); vTcw.assign(n, typename PnPsolverOf<FrameT, MapPointT>::MatT());
+    if (!n) return;
+    const size_t cap = (size_t)olf_orb_capacity(c), mi = (size_t)vpSolvers[0]->mRansac.max_iterations;
+    std::vector<olf_keypoint> kps(2 * n * cap);
+    std::vector<float> world(6 * n * cap, 0.0f), bT(16 * n), rT(16 * n), T(16 * n);
+    std::vector<int32_t> counts(2 * n), pairs(2 * n), rows(n * cap, -1), done(n), best(n), ref(n), acc(n), nomore(n), ninl(n), ncorr(n);
+    std::vector<uint32_t> draws(4 * n * mi);
+    std::vector<uint8_t> bf(n * cap, 0), rf(n * cap, 0), inl(n * cap, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const auto& S = *vpSolvers[i];
+        const olf_pnp_ransac &a = S.mRansac, &b = vpSolvers[0]->mRansac;
+        if ((size_t)S.N > cap) throw std::runtime_error("PnPsolversIterate: the context's capacity does not hold a solver's correspondences");
+        if (a.probability != b.probability || a.min_inliers != b.min_inliers || a.max_iterations != b.max_iterations || a.min_set != b.min_set ||
+            a.epsilon != b.epsilon || a.th2 != b.th2)
+            throw std::runtime_error("PnPsolversIterate: the solvers differ in their RANSAC parameters");
+        for (int f = 0; f < 2; ++f) { counts[2 * i + f] = S.N; pairs[2 * i + f] = (int32_t)(2 * i + f); }
+        for (int q = 0; q < S.N; ++q) {
+            kps[(2 * i + 1) * cap + q] = S.mKeys[(size_t)S.mCap + q];
+            for (int k = 0; k < 3; ++k) world[3 * (2 * i * cap + q) + k] = S.mWorld[3 * (size_t)q + k];
+            rows[i * cap + q] = q;
+            bf[i * cap + q] = S.mBestFlags[q]; rf[i * cap + q] = S.mRefinedFlags[q];
+        }
+        std::memcpy(&draws[4 * i * mi], S.mDraws.data(), 16 * mi);
+        done[i] = S.mnIterations; best[i] = S.mnBestInliers; ref[i] = S.mnRefinedInliers;
+        std::memcpy(&bT[16 * i], S.mBestTcw, 64); std::memcpy(&rT[16 * i], S.mRefinedTcw, 64); std::memcpy(&T[16 * i], S.mTcw, 64);
+    }
+    olf_track_batch in;
+    vpSolvers[0]->olf_fill_batch(in, counts.data());
+    in.kps = kps.data(); in.mp_world = world.data();
+    olf_pnp_ransac rn = vpSolvers[0]->mRansac;
+    rn.n_iterations = std::max(nIterations, 0);
+    const olf_pnp_solver_io io = {done.data(), best.data(), bT.data(), bf.data(), ref.data(), rT.data(), rf.data(), acc.data(), nomore.data(), ninl.data(), inl.data(),
+                                  T.data(), ncorr.data(), nullptr};
+    olf_detail::check(olf_pnp_solver_pairs(c, &in, (int)(2 * n), nullptr, (int)n, pairs.data(), rows.data(), &rn, draws.data(), &io), "olf_pnp_solver_pairs");
+    for (size_t i = 0; i < n; ++i) {
+        auto& S = *vpSolvers[i];
+        S.mnIterations = done[i]; S.mnBestInliers = best[i]; S.mnRefinedInliers = ref[i]; S.mAccepted = acc[i]; S.mNoMore = nomore[i]; S.mnInliers = ninl[i];
+        S.mNCorr = ncorr[i];
+        std::memcpy(S.mBestTcw, &bT[16 * i], 64); std::memcpy(S.mRefinedTcw, &rT[16 * i], 64); std::memcpy(S.mTcw, &T[16 * i], 64);
+        for (int q = 0; q < S.N; ++q) { S.mBestFlags[q] = bf[i * cap + q]; S.mRefinedFlags[q] = rf[i * cap + q]; S.mInliers[q] = inl[i * cap + q]; }
+        bool nm;
+        int ni;
+        vTcw[i] = S.olf_results(nm, vvbInliers[i], ni);
+        vbNoMore[i] = nm; vnInliers[i] = ni;
+    }
+}
+
 }  // namespace ORB_SLAM2

@@ -84,6 +84,18 @@ class Sim3SolverIoC(C.Structure):
                                           "inliers", "n_correspondences", "counts")]
 
 
+class PnpRansacC(C.Structure):
+    """olf_pnp_ransac (include/orbline.h): SetRansacParameters and the window of one PnPsolver::iterate"""
+    _fields_ = [("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("min_set", C.c_int32), ("n_iterations", C.c_int32),
+                ("epsilon", C.c_float), ("th2", C.c_float)]
+
+
+class PnpSolverIoC(C.Structure):
+    """olf_pnp_solver_io (include/orbline.h): the carried state and the outputs of the solvers of a list of pairs"""
+    _fields_ = [(n, C.c_void_p) for n in ("iterations_done", "best_inliers", "best_Tcw", "best_flags", "refined_inliers", "refined_Tcw", "refined_flags",
+                                          "accepted", "no_more", "n_inliers", "inliers", "Tcw", "n_correspondences", "counts")]
+
+
 class LocalMapC(C.Structure):
     """olf_local_map (include/orbline.h): the local map of a batch as device arrays, and optionally each frame's list of indices into it"""
     _fields_ = ([(n, C.c_void_p) for n in ("world", "normal", "maxd", "mind", "desc", "obs", "bad")] + [("n_mp", C.c_int32)] +
@@ -349,6 +361,13 @@ def lib():
         L.olf_debug_sim3_solver_lds_limit.argtypes = [C.c_int]
         L.olf_debug_sim3_solver_gate.argtypes = [C.c_float, P]
         L.olf_debug_sim3_solver_cap.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, P]
+        L.olf_pnp_solver_pairs_dev.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, P, C.c_int, P, P, C.POINTER(PnpRansacC), P, C.POINTER(PnpSolverIoC), P]
+        L.olf_pnp_apply_inliers_dev.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, C.c_int] + [P] * 9
+        L.olf_pnp_solver.argtypes = [C.POINTER(TrackBatchC), C.c_int, C.c_int, P, P, C.c_int, C.c_int, C.c_int, P, C.POINTER(PnpRansacC), P,
+                                     C.POINTER(PnpSolverIoC), P]
+        L.olf_pnp_solver_pairs.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, P, C.c_int, P, P, C.POINTER(PnpRansacC), P, C.POINTER(PnpSolverIoC)]
+        L.olf_debug_pnp_solver_lds_limit.argtypes = [C.c_int]
+        L.olf_debug_pnp_solver_parameters.argtypes = [C.c_int, C.POINTER(PnpRansacC), P, P]
         L.olf_update_normal_and_depth_dev.argtypes = [P, C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int] + [P] * 8
         L.olf_update_normal_and_depth.argtypes = [C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int] + [P] * 5 + [C.c_int] + [P] * 4
         L.olf_pose_default_params.argtypes = [C.POINTER(PoseParamsC)]

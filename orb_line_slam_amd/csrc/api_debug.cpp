@@ -6,6 +6,7 @@
 namespace olf {
 int launch_copy16(const void* src, void* dst, size_t bytes, hipStream_t s);
 void sim3_solver_lds_limit(int bytes);      // sim3solver_batch.hip
+void pnp_solver_lds_limit(int bytes);       // pnpsolver_batch.hip
 }
 
 using namespace olf;
@@ -34,6 +35,12 @@ int olf_orb_pyramid_level(olf_ctx* c, int image, int level, int blurred, uint8_t
 int olf_debug_sim3_solver_lds_limit(int bytes)
 {
     sim3_solver_lds_limit(bytes);
+    return OLF_OK;
+}
+
+int olf_debug_pnp_solver_lds_limit(int bytes)
+{
+    pnp_solver_lds_limit(bytes);
     return OLF_OK;
 }
 
