@@ -1171,7 +1171,7 @@ int olf_debug_sim3_solver_cap(int N, double probability, int min_inliers, int ma
  * constructor's correspondences (:67-110), SetRansacParameters(probability, min_inliers, max_iterations, min_set, epsilon, th2) (:121-157; the tracker:
  * 0.99, 10, 300, 4, 0.5, 5.991) and one iterate(n_iterations, ...) per call (:165-258) with Refine (:260-305), for n_pairs pairs of the n_frames frames of
  * a batch.  It stands between olf_search_by_bow_pairs_dev (form OLF_BOW_KF_FRAME), whose rows it reads, and olf_search_by_projection_kf_pairs_dev, whose
- * d_Tcw takes Tcw; olf_pnp_apply_inliers_dev does :2297-2308 between them.  Optimizer::PoseOptimization (:2310) stays on the host.  Results equal
+ * d_Tcw takes Tcw; olf_pnp_apply_inliers_dev does :2297-2308 between them and olf_pose_optimization_batch_dev is Optimizer::PoseOptimization (:2310).  Results equal
  * olf_pnp_solver pair by pair, bit for bit, and do not depend on scheduling, on how the kernel chunks a window or on a pair's position in the list.
  * `in`: kps (pt of the frame's features, octave), counts, img_stride, mp_world and mp_valid of the key frame (NULL: every feature holds a point) and fx,
  * fy, cx, cy are read (frame j = image j * img_stride; a count beyond the capacity is read as the capacity); mvLevelSigma2 is the context's.  d_mp_bad
@@ -1337,7 +1337,7 @@ int olf_bow_score(olf_ctx* ctx, const int32_t* ids_a, const double* vals_a, int 
  * bool Optimizer::PoseOptimizationWithLine(Frame*) (src/Optimizer.cc:604-777): the branch that executes (`if(true)`, :664-697), i.e. the point-and-line
  * Gauss-Newton solver of StVO-PL -- gaussNewtonOptimization twice, gaussNewtonOptimizationRobust, gaussNewtonOptimization, each from the same prior DT and
  * each followed by removeOutliers -- and its epilogue; the call of Tracking::TrackReferenceKeyFrameWithLine (src/Tracking.cc:1032),
- * TrackWithMotionModelWithLine (:1470) and TrackLocalMap (:1544).  Optimizer::PoseOptimization (g2o, points only) has no entry.  Doubles throughout, as the
+ * TrackWithMotionModelWithLine (:1470) and TrackLocalMap (:1544).  Optimizer::PoseOptimization (g2o, points only) is olf_pose_optimization* below.  Doubles throughout, as the
  * reference; the arithmetic of every term is csrc/pose_terms.hpp, the same text for the host form and the kernel.  Defaults: src/Config.cpp:42-82. */
 typedef struct olf_pose_params {
     int32_t max_iters_ref;       /* Config::maxItersRef()       10   (>= 1)                                          */
@@ -1442,6 +1442,71 @@ int olf_discard_outliers_frame(olf_ctx* ctx, const olf_discard_batch* io, int mo
 /* the host form: one frame, host pointers, no context; *status receives the bits 512 / 1024 */
 int olf_discard_outliers(const olf_discard_batch* io, int capacity, int line_capacity, int mode, int only_tracking, int stereo, int32_t* n_matches,
                          int32_t* status);
+
+/* ---- Optimizer::PoseOptimization for a list of rows on the device (csrc/posepoints_batch.hip, posepoints_host.cpp, posepoints_terms.hpp) --------------------
+ * int Optimizer::PoseOptimization(Frame*) (src/Optimizer.cc:239-451): the g2o graph of one free VertexSE3Expmap and one EdgeSE3ProjectXYZOnlyPose
+ * (mvuRight[i] < 0) or EdgeStereoSE3ProjectXYZOnlyPose per held feature, in ascending feature index, Huber kernels with the float deltas sqrt(5.991) /
+ * sqrt(7.815), four passes of OptimizationAlgorithmLevenberg (10 iterations, LinearSolverDense) each from toSE3Quat(mTcw), each followed by the chi2
+ * classification in float, the kernels removed after the third, one pass only below 10 edges; the call of Tracking::Relocalization
+ * (src/Tracking.cc:2310, :2326, :2341), TrackWithMotionModel (:1242 ff.) and TrackReferenceKeyFrame (:932 ff.).  Doubles throughout; the arithmetic of every
+ * term, of Eigen's LDLT and of the Levenberg loop is csrc/posepoints_terms.hpp, the same text for the host form and the kernel (C.4, C.27 of DESIGN.md).
+ * A ROW is one call of the reference: relocalisation optimises one frame once per candidate key frame.  Device pointers.  Without `pairs`, row r reads
+ * frame r (image r * img_stride of kps / counts, row r of uright) and a non-negative frame_mp value v is point v + mp_index_offset[r] of mp_world: the
+ * convention of olf_pose_batch, so the output of the frame-to-frame and key-frame BoW searches goes in as documented there (n_rows <= n_frames).  With
+ * `pairs` = (key frame, frame), the array olf_pnp_solver_pairs_dev takes, row r reads frame pairs[r][1]'s features and v is point
+ * pairs[r][0] * capacity + v (+ mp_index_offset[r]) of olf_track_batch.mp_world viewed flat (n_mp = n_frames * capacity): Tcw is olf_pnp_solver_io.Tcw,
+ * frame_mp is d_out of olf_pnp_apply_inliers_dev and row_active its d_accepted, nothing copied or re-indexed in between.  A row with row_active <= 0, or a
+ * pair outside [0, n_frames) or with both indices equal (bit 2048 of the context's status word), gets n_good = -1 and nothing else of it is written.
+ * There is no outlier input: the reference clears every held feature's flag on entry (:289, :323).
+ * The stale-error quirk of the reference is kept: after a pass an edge whose flag is clear is classified with the _error the last computeActiveErrors()
+ * left, which is the error at the REJECTED estimate when the pass's last Levenberg trial was rejected (pop() restores the vertex, not the edges).
+ * Defined here, not by the reference: a held point at depth exactly 0 at an evaluation (status bit 1) or an H, b, step or estimate that is not finite
+ * (bit 2) stops the row: Tcw_out = Tcw, the flags as they stood after the last completed pass, n_good = 0, `passes` the passes completed.  A pass whose
+ * active set is empty leaves the estimate at toSE3Quat(mTcw) with iters = 0 and classifies every edge there (what g2o does: see posepoints_terms.hpp).  A
+ * held feature whose octave is outside the context's levels holds nothing and sets bit 4 of the row's status; an index outside [0, n_mp) holds nothing and
+ * sets bit 512 of the context's status word.
+ * The loops that follow a call need no new entry: src/Tracking.cc:934-953 is olf_discard_outliers* mode 0 and :2315-2317 / :2343-2345 mode 1 with
+ * stereo = 1 (dropped, flag kept) on frame_mp / outlier_out, without lines -- those entries want non-NULL line rows, so the caller passes an lcounts
+ * array of zeros and any valid frame_ml / outlier_l pointers, which are then never read. */
+typedef struct olf_pose_points_batch {
+    const olf_keypoint* kps; const int32_t* counts; int32_t img_stride;   /* mvKeysUn (pt, octave), N                                         */
+    const float*   uright;            /* [n_frames][capacity] mvuRight (olf_frame_buffers.uright); negative: a monocular edge               */
+    float fx, fy, cx, cy, bf;         /* bf = mbf                                                                                            */
+    const float*   Tcw;               /* [n_rows][16] mTcw, row-major                                                                        */
+    const int32_t* frame_mp;          /* [n_rows][capacity] mvpMapPoints as indices, negative = NULL                                         */
+    const float*   mp_world;          /* [n_mp][3] GetWorldPos()                                                                             */
+    int32_t        n_mp;
+    const int32_t* mp_index_offset;   /* [n_rows] or NULL                                                                                    */
+    const int32_t* pairs;             /* [n_rows][2] (key frame, frame) or NULL                                                              */
+    const int32_t* row_active;        /* [n_rows] or NULL: every row runs                                                                    */
+} olf_pose_points_batch;
+/* What a call writes per row.  Every pointer is required. */
+typedef struct olf_pose_points_outputs {
+    float*   Tcw_out;         /* [16]        the pose SetPose receives (:445-448)                                                              */
+    uint8_t* outlier_out;     /* [capacity]  mvbOutlier at the end; 0 from the count on and where nothing is held                              */
+    int32_t* n_good;          /*             the return value, nInitialCorrespondences - nBad of the last pass that ran; 0 below 3 edges       */
+    int32_t* n_initial;       /*             nInitialCorrespondences                                                                           */
+    float*   chi2;            /* [capacity]  the value each held feature was last classified with (0 elsewhere, and below 3 edges)             */
+    int32_t* passes;          /*             passes completed (0 below 3 edges, 1 below 10)                                                    */
+    int32_t* iters;           /* [4]         Levenberg iterations of each pass                                                                 */
+    int32_t* status;          /*             the row's own status word: 1, 2, 4 above                                                          */
+} olf_pose_points_outputs;
+/* One launch: one workgroup per row (grid-strided above 1024 rows) carries it through the four passes; activeRobustChi2 and the 21 + 6 sums of
+ * buildSystem have a fixed feature-to-lane assignment and a fixed reduction shape, so a row's outputs are the same bits wherever it stands in the list.
+ * Like the other batch entries: no synchronisation and no host read, the batch scratch slot (only where 29 bytes per feature of the capacity exceed
+ * 60 KiB of LDS: that much per resident workgroup), n_rows == 0 writes nothing, a NULL required pointer is OLF_ERR_INVALID, a count beyond the capacity is
+ * read as the capacity, accesses are never out of bounds. */
+int olf_pose_optimization_batch_dev(olf_ctx* ctx, const olf_pose_points_batch* in, int n_rows, int n_frames, const olf_pose_points_outputs* out, void* stream);
+/* The host form: row 0 of `in`, host pointers, no context and no device; plain doubles, every sum in ascending feature index.  capacity: the length of
+ * the per-feature rows; inv_level_sigma2 [n_levels]: mvInvLevelSigma2.  Without a context the bits 512 / 2048 go into the row's status word. */
+int olf_pose_optimization(const olf_pose_points_batch* in, int capacity, int n_frames, const float* inv_level_sigma2, int n_levels,
+                          const olf_pose_points_outputs* out);
+/* olf_pose_optimization_batch_dev from host pointers (csrc/posepoints_api.cpp): every array at the context's capacity is staged (the outputs are uploaded
+ * first, so an untouched row comes back as it went in), the kernel runs on the context's stream, the outputs come back; synchronises.  A set bit of the
+ * context's status word makes the call return OLF_ERR_CAPACITY with the bit's text, the outputs complete. */
+int olf_pose_optimization_rows(olf_ctx* ctx, const olf_pose_points_batch* in, int n_rows, int n_frames, const olf_pose_points_outputs* out);
+/* tests: the LDS a workgroup may take for a row's edges (bytes; above it they live in context scratch; <= 0 restores the default) */
+int olf_debug_pose_points_lds_limit(int bytes);
 
 #ifdef __cplusplus
 }

@@ -1277,6 +1277,54 @@ bool PoseOptimizationWithLine(olf_ctx* c, FrameT* pFrame, const olf_pose_params*
     return true;
 }
 
+// ---- Optimizer::PoseOptimization (src/Optimizer.cc:239-451) over the reference's own types --------------------------------------------------------------------
+// Reads what the reference reads of the frame -- mvpMapPoints with GetWorldPos(), mvKeysUn, mvuRight, mTcw, fx, fy, cx, cy, mbf, mvInvLevelSigma2 -- and
+// writes what it writes: mvbOutlier of every held feature and mTcw through SetPose; returns nInitialCorrespondences - nBad.  c == NULL: the host form
+// (olf_pose_optimization, no device); otherwise the frame runs on the device through context c (olf_pose_optimization_rows), whose capacity must hold the
+// frame and whose level table must be the frame's.  *status (or NULL) receives the row's status word: where the reference is undefined (a depth of 0, a
+// non-finite system) the pose is not set, the flags stay as the last completed pass left them and 0 is returned (include/orbline.h).
+template <class FrameT>
+int PoseOptimization(olf_ctx* c, FrameT* pFrame, int32_t* status = nullptr)
+{
+    typedef typename std::remove_const<typename std::remove_reference<decltype(pFrame->mTcw)>::type>::type MatT;
+    typedef typename std::remove_reference<decltype(pFrame->mvKeysUn[0])>::type KP;
+    static_assert(sizeof(KP) == sizeof(olf_keypoint), "cv::KeyPoint layout");
+    const int N = (int)pFrame->mvpMapPoints.size();
+    const int cap = c ? olf_orb_capacity(c) : N;
+    if (N > cap) olf_detail::check(OLF_ERR_CAPACITY, "PoseOptimization: more features than the context's capacity");
+    std::vector<olf_keypoint> kps((size_t)cap + 1);
+    std::vector<int32_t> fmp((size_t)cap + 1, -1);
+    std::vector<float> mpw, ur((size_t)cap + 1, -1.f), chi2((size_t)cap + 1, 0.f);
+    std::vector<uint8_t> out((size_t)cap + 1, 0);
+    if (N) std::memcpy(kps.data(), pFrame->mvKeysUn.data(), (size_t)N * sizeof(olf_keypoint));
+    for (int i = 0; i < N; ++i) {
+        ur[i] = pFrame->mvuRight[i];
+        if (!pFrame->mvpMapPoints[i]) continue;
+        const auto wp = pFrame->mvpMapPoints[i]->GetWorldPos();
+        fmp[i] = (int32_t)(mpw.size() / 3);
+        for (int k = 0; k < 3; ++k) mpw.push_back(wp.template at<float>(k));
+    }
+    float Tcw[16], Tout[16];
+    olf_detail::mat4(pFrame->mTcw, Tcw);
+    const int32_t counts[1] = {N};
+    olf_pose_points_batch in;
+    std::memset(&in, 0, sizeof(in));
+    in.kps = kps.data(); in.counts = counts; in.img_stride = 1; in.uright = ur.data();
+    in.fx = pFrame->fx; in.fy = pFrame->fy; in.cx = pFrame->cx; in.cy = pFrame->cy; in.bf = pFrame->mbf;
+    in.Tcw = Tcw; in.frame_mp = fmp.data(); in.mp_world = mpw.data(); in.n_mp = (int32_t)(mpw.size() / 3);
+    int32_t good = 0, initial = 0, passes = 0, iters[4], st = 0;
+    const olf_pose_points_outputs o = {Tout, out.data(), &good, &initial, chi2.data(), &passes, iters, &st};
+    if (c) olf_detail::check(olf_pose_optimization_rows(c, &in, 1, 1, &o), "olf_pose_optimization_rows");
+    else olf_detail::check(olf_pose_optimization(&in, cap, 1, pFrame->mvInvLevelSigma2.data(), (int)pFrame->mvInvLevelSigma2.size(), &o), "olf_pose_optimization");
+    for (int i = 0; i < N; ++i) if (pFrame->mvpMapPoints[i]) pFrame->mvbOutlier[i] = out[i] != 0;
+    if (status) *status = st;
+    if (initial < 3 || (st & 3)) return 0;                          // :364-365 returns before SetPose; a stopped row leaves the pose alone
+    MatT T(4, 4, 5 /* CV_32F */);
+    for (int r = 0; r < 4; ++r) for (int k = 0; k < 4; ++k) T.template at<float>(r, k) = Tout[4 * r + k];
+    pFrame->SetPose(T);
+    return good;
+}
+
 // ---- Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc) over the reference's own types ---------------------------------------------------------------------
 // The reference's members with its signatures: the constructor (pKF1, pKF2, vpMatched12, bFixScale), SetRansacParameters, iterate, find and the three
 // GetEstimated*.  It runs over the host form olf_sim3_solver, so a single solver needs no device.  The constructor keeps the correspondences as :62-103 does,

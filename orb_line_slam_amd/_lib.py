@@ -146,6 +146,18 @@ class PoseOutputsC(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("Tcw_out", "DT", "DT_cov", "DT_cov_eig", "err_norm", "good", "outlier_out", "outlier_l_out", "n_inliers", "iters", "status")]
 
 
+class PosePointsBatchC(C.Structure):
+    """olf_pose_points_batch (include/orbline.h): the rows Optimizer::PoseOptimization reads"""
+    _fields_ = ([(n, C.c_void_p) for n in ("kps", "counts")] + [("img_stride", C.c_int32), ("uright", C.c_void_p)] +
+                [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "bf")] + [(n, C.c_void_p) for n in ("Tcw", "frame_mp", "mp_world")] + [("n_mp", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("mp_index_offset", "pairs", "row_active")])
+
+
+class PosePointsOutputsC(C.Structure):
+    """olf_pose_points_outputs (include/orbline.h): what Optimizer::PoseOptimization writes per row"""
+    _fields_ = [(n, C.c_void_p) for n in ("Tcw_out", "outlier_out", "n_good", "n_initial", "chi2", "passes", "iters", "status")]
+
+
 class DiscardBatchC(C.Structure):
     """olf_discard_batch (include/orbline.h): the rows the "discard outliers" loops read and change"""
     _fields_ = ([(n, C.c_void_p) for n in ("counts", "lcounts")] + [("img_stride", C.c_int32)] +
@@ -378,6 +390,10 @@ def lib():
         L.olf_pose_optimization_with_line_frame.argtypes = [P, C.POINTER(PoseBatchC), C.POINTER(PoseParamsC), C.POINTER(PoseOutputsC)]
         L.olf_discard_outliers_frame.argtypes = [P, C.POINTER(DiscardBatchC), C.c_int, C.c_int, C.c_int, P]
         L.olf_discard_outliers.argtypes = [C.POINTER(DiscardBatchC), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]
+        L.olf_pose_optimization_batch_dev.argtypes = [P, C.POINTER(PosePointsBatchC), C.c_int, C.c_int, C.POINTER(PosePointsOutputsC), P]
+        L.olf_pose_optimization.argtypes = [C.POINTER(PosePointsBatchC), C.c_int, C.c_int, P, C.c_int, C.POINTER(PosePointsOutputsC)]
+        L.olf_pose_optimization_rows.argtypes = [P, C.POINTER(PosePointsBatchC), C.c_int, C.c_int, C.POINTER(PosePointsOutputsC)]
+        L.olf_debug_pose_points_lds_limit.argtypes = [C.c_int]
         L.olf_profile_enable.argtypes = [C.c_void_p, C.c_int]
         L.olf_profile_reset.argtypes = [C.c_void_p]
         L.olf_profile_stage_name.restype = C.c_char_p

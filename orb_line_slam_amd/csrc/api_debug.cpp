@@ -7,6 +7,7 @@ namespace olf {
 int launch_copy16(const void* src, void* dst, size_t bytes, hipStream_t s);
 void sim3_solver_lds_limit(int bytes);      // sim3solver_batch.hip
 void pnp_solver_lds_limit(int bytes);       // pnpsolver_batch.hip
+void pose_points_lds_limit(int bytes);      // posepoints_batch.hip
 }
 
 using namespace olf;
@@ -41,6 +42,12 @@ int olf_debug_sim3_solver_lds_limit(int bytes)
 int olf_debug_pnp_solver_lds_limit(int bytes)
 {
     pnp_solver_lds_limit(bytes);
+    return OLF_OK;
+}
+
+int olf_debug_pose_points_lds_limit(int bytes)
+{
+    pose_points_lds_limit(bytes);
     return OLF_OK;
 }
 

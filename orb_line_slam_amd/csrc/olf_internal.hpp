@@ -47,13 +47,13 @@ void set_error(const std::string& s);
 //   SCRATCH_KNN    olf_match_bf_dev: the k-NN tables of launch_match_bf.
 //   SCRATCH_STAGE  the descriptor-sized host-pointer entries (api_host.cpp: olf_match_bf, olf_knn2, olf_match_candidates, olf_frame_grid,
 //                  olf_features_in_area, olf_hamming_matrix, olf_distinctive_descriptors; localmap_api.cpp: olf_update_local_map; connections_api.cpp: olf_update_connections; culling_api.cpp: olf_keyframe_culling,
-//                  olf_tracked_map_points, olf_map_point_culling; pose_api.cpp: olf_pose_optimization_with_line_frame, olf_discard_outliers_frame; newpoints_api.cpp: olf_compute_f12_pairs,
+//                  olf_tracked_map_points, olf_map_point_culling; pose_api.cpp: olf_pose_optimization_with_line_frame, olf_discard_outliers_frame; posepoints_api.cpp: olf_pose_optimization_rows; newpoints_api.cpp: olf_compute_f12_pairs,
 //                  olf_create_new_map_points_pairs, olf_update_normal_and_depth_points) and the olf_debug_*_sweep counters.  Every one of them ends in
 //                  a synchronise on the context's stream.
 //   SCRATCH_BATCH  the batched matchers (olf_search_by_bow_batch_dev, olf_search_by_projection_batch_dev, olf_is_in_frustum_batch_dev,
 //                  olf_search_local_map_batch_dev, olf_search_for_triangulation_batch_dev, olf_fuse_search_batch_dev, olf_search_by_sim3_pairs_dev,
 //                  olf_search_by_projection_kf_pairs_dev, olf_search_by_projection_sim3_batch_dev, olf_update_local_map_batch_dev, olf_update_connections_batch_dev,
-//                  olf_pose_optimization_with_line_batch_dev above the LDS a frame's state fits in, olf_sim3_solver_pairs_dev (its table of iteration caps, and
+//                  olf_pose_optimization_with_line_batch_dev above the LDS a frame's state fits in, olf_pose_optimization_batch_dev likewise, olf_sim3_solver_pairs_dev (its table of iteration caps, and
 //                  the correspondences above the LDS they fit in), olf_pnp_solver_pairs_dev (its table of parameters, and the correspondences above the LDS they fit in), and the line entries of line_batch.hip) and the image-sized host-pointer entries (olf_cvt_gray, olf_remap_linear,
 //                  olf_init_undistort_rectify_map, olf_bow_transform).  The matchers do not synchronise: the caller keeps them on one stream.
 //   SCRATCH_PACK   olf_frames_pack_dev: the record's row offsets.

@@ -4,7 +4,7 @@
 // One launch, one workgroup of 256 lanes per frame, which carries the frame through the four passes and the epilogue; no grid-wide synchronisation.  The
 // driver and every term are pose_terms.hpp, the text pose_host.cpp runs too.  Every lane runs the driver on the same values, so all lanes take the same
 // branches and the 6 x 6 pieces need no broadcast; the workgroup cooperates inside DevOps:
-//   sums            feature i belongs to lane i % 256, which adds its features in ascending i, points then lines, into 28 doubles; the lanes' sums are
+//   sums            (wg_sums.hpp) feature i belongs to lane i % 256, which adds its features in ascending i, points then lines, into 28 doubles; the lanes' sums are
 //                   combined by an xor butterfly over the wave (both partners form the same sum, so every lane ends with the same bits) and the four
 //                   waves' sums are added in wave order.  No floating-point atomics; the shape depends on nothing but the frame's own rows.
 //   select          element n / 2 of the ascending residuals, exactly: a radix select over the ordered 64-bit patterns, eight bits a round (integer
@@ -15,6 +15,7 @@
 #include <mutex>
 #include "pose_terms.hpp"
 #include "staging.hpp"
+#include "wg_sums.hpp"
 #include "../../include/orbline.h"
 
 namespace olf {
@@ -67,32 +68,14 @@ struct DevOps {
     uint8_t *pf, *poct, *lf, *loct;
     const float* inv_sigma2;
     // static LDS of the kernel
-    double (*red)[PO_WAVES][pose::N_SUMS];
-    int (*redn)[PO_WAVES];
+    WgSums<PO_THREADS, pose::N_SUMS> wg;
     unsigned* hist;
     unsigned* gsum;
-    int parity;
 
     __device__ double sq_of(int oct) const { return sqrt((double)inv_sigma2[oct]); }
     __device__ void line_obs(int i, double* o) const { o[0] = kls[i].startPointX; o[1] = kls[i].startPointY; o[2] = kls[i].endPointX; o[3] = kls[i].endPointY; }
 
-    // the workgroup's sums of S[0 .. m) and of *n, the same bits in every lane
-    __device__ void reduce(double* S, int m, int* n)
-    {
-        int cnt = *n;
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-        for (int k = 0; k < m; ++k) {
-            double v = S[k];
-            for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
-            S[k] = v;
-        }
-        const int w = tid >> 6;
-        if ((tid & 63) == 0) { for (int k = 0; k < m; ++k) red[parity][w][k] = S[k]; redn[parity][w] = cnt; }
-        __syncthreads();
-        for (int k = 0; k < m; ++k) S[k] = ((red[parity][0][k] + red[parity][1][k]) + red[parity][2][k]) + red[parity][3][k];
-        *n = ((redn[parity][0] + redn[parity][1]) + redn[parity][2]) + redn[parity][3];
-        parity ^= 1;             // the next call writes the other buffer: whoever reaches it has passed a barrier behind every lane's reads of this one
-    }
+    __device__ void reduce(double* S, int m, int* n) { wg.reduce(S, m, n); }      // wg_sums.hpp
 
     // the key of rank `rank` (0-based, ascending) among keys[0 .. n_items); rank < n_items
     __device__ unsigned long long select(const unsigned long long* keys, int n_items, int rank)
@@ -240,8 +223,7 @@ struct DevOps {
 __global__ __launch_bounds__(PO_THREADS) void k_pose_frames(PoseArgs A, int* __restrict__ status)
 {
     extern __shared__ __align__(16) unsigned char po_dyn[];
-    __shared__ double s_red[2][PO_WAVES][pose::N_SUMS];
-    __shared__ int s_redn[2][PO_WAVES];
+    __shared__ WgSums<PO_THREADS, pose::N_SUMS>::Lds s_sums;
     __shared__ unsigned s_hist[256], s_gsum[16];
 
     const int j = blockIdx.x, tid = threadIdx.x;
@@ -266,7 +248,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_frames(PoseArgs A, int* __r
     ops.key = reinterpret_cast<unsigned long long*>(slab + lay.key); ops.key2 = reinterpret_cast<unsigned long long*>(slab + lay.key2);
     ops.pf = slab + lay.pf; ops.poct = slab + lay.poct; ops.lf = slab + lay.lf; ops.loct = slab + lay.loct;
     ops.inv_sigma2 = A.inv_sigma2;
-    ops.red = s_red; ops.redn = s_redn; ops.hist = s_hist; ops.gsum = s_gsum; ops.parity = 0;
+    ops.wg.lds = &s_sums; ops.wg.tid = tid; ops.wg.parity = 0; ops.hist = s_hist; ops.gsum = s_gsum;
 
     // who holds what: mvpMapPoints / mvpMapLines as flags, with the entry's outlier flags
     int bad_octave = 0;

@@ -122,44 +122,54 @@ PT_HD void expmap_se3(const double* x, double* T)
     mat4_identity(T);
     for (int i = 0; i < 3; ++i) { T[i * 4] = R[i * 3]; T[i * 4 + 1] = R[i * 3 + 1]; T[i * 4 + 2] = R[i * 3 + 2]; T[i * 4 + 3] = t[i]; }
 }
+// g2o::SE3Quat(R, t)'s rotation (se3quat.h:58-60, :280-285): Eigen's Quaterniond(R) of the rotation block of the row-major 4 x 4 T, then
+// normalizeRotation(), i.e. w >= 0 and unit norm.  q = x, y, z, w.  Shared with posepoints_terms.hpp.
+PT_HD void quat_normalize_positive(double* q)
+{
+    if (q[3] < 0.0) for (int i = 0; i < 4; ++i) q[i] = q[i] * -1.0;
+    const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    for (int i = 0; i < 4; ++i) q[i] = q[i] / n;
+}
+PT_HD void quat_from_mat4(const double* T, double* q)
+{
+    const double m00 = T[0], m11 = T[5], m22 = T[10];
+    double t = (m00 + m11) + m22;
+    if (t > 0.0) {
+        t = sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (T[9] - T[6]) * t; q[1] = (T[2] - T[8]) * t; q[2] = (T[4] - T[1]) * t;
+    } else {
+        int i = 0;
+        if (m11 > m00) i = 1;
+        if (m22 > T[i * 5]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = sqrt(((T[i * 5] - T[j * 5]) - T[k * 5]) + 1.0);
+        q[i] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (T[k * 4 + j] - T[j * 4 + k]) * t;
+        q[j] = (T[j * 4 + i] + T[i * 4 + j]) * t;
+        q[k] = (T[k * 4 + i] + T[i * 4 + k]) * t;
+    }
+    quat_normalize_positive(q);
+}
+// Quaterniond::toRotationMatrix(), row-major 3 x 3
+PT_HD void quat_to_mat3(const double* q, double* R)
+{
+    const double tx = 2.0 * q[0], ty = 2.0 * q[1], tz = 2.0 * q[2];
+    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3], txx = tx * q[0], txy = ty * q[0], txz = tz * q[0], tyy = ty * q[1], tyz = tz * q[1],
+                 tzz = tz * q[2];
+    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+    R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
+}
 // logmap_se3 (src/Auxiliar.cc:146-152): g2o::SE3Quat(R, t).log() with the halves swapped, so x = (upsilon, omega).  The constructor goes through a
 // normalised quaternion with w >= 0 (se3quat.h:58-60, :280-285) and log() through its rotation matrix again (:178-215).
 PT_HD void logmap_se3(const double* T, double* x)
 {
-    double q[4];                                                    // x, y, z, w
-    {
-        const double m00 = T[0], m11 = T[5], m22 = T[10];
-        double t = (m00 + m11) + m22;
-        if (t > 0.0) {
-            t = sqrt(t + 1.0);
-            q[3] = 0.5 * t;
-            t = 0.5 / t;
-            q[0] = (T[9] - T[6]) * t; q[1] = (T[2] - T[8]) * t; q[2] = (T[4] - T[1]) * t;
-        } else {
-            int i = 0;
-            if (m11 > m00) i = 1;
-            if (m22 > T[i * 5]) i = 2;
-            const int j = (i + 1) % 3, k = (j + 1) % 3;
-            t = sqrt(((T[i * 5] - T[j * 5]) - T[k * 5]) + 1.0);
-            q[i] = 0.5 * t;
-            t = 0.5 / t;
-            q[3] = (T[k * 4 + j] - T[j * 4 + k]) * t;
-            q[j] = (T[j * 4 + i] + T[i * 4 + j]) * t;
-            q[k] = (T[k * 4 + i] + T[i * 4 + k]) * t;
-        }
-        if (q[3] < 0.0) for (int i = 0; i < 4; ++i) q[i] = q[i] * -1.0;
-        const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-        for (int i = 0; i < 4; ++i) q[i] = q[i] / n;
-    }
-    double R[9];
-    {
-        const double tx = 2.0 * q[0], ty = 2.0 * q[1], tz = 2.0 * q[2];
-        const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3], txx = tx * q[0], txy = ty * q[0], txz = tz * q[0], tyy = ty * q[1], tyz = tz * q[1],
-                     tzz = tz * q[2];
-        R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-        R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-        R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
-    }
+    double q[4], R[9];                                              // x, y, z, w
+    quat_from_mat4(T, q);
+    quat_to_mat3(q, R);
     const double d = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
     const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
     double om[3], Om[9], OO[9], Vi[9];
