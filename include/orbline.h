@@ -1098,7 +1098,7 @@ int olf_update_normal_and_depth_points(olf_ctx* ctx, const olf_map_graph* g, con
  * correspondences, SetRansacParameters(probability, min_inliers, max_iterations) and one iterate(n_iterations, ...) per call, for n_pairs pairs of the
  * n_frames key frames of a batch.  It stands between olf_search_by_bow_pairs_dev (form OLF_BOW_KF_KF), whose rows it reads, and
  * olf_search_by_sim3_pairs_dev, which takes best_s / best_R / best_t as its d_s12 / d_R12 / d_t12 without a copy; olf_sim3_filter_matches_dev does
- * :319-324 between them.  Optimizer::OptimizeSim3 (:332) stays on the host.  Results equal olf_sim3_solver pair by pair, bit for bit, and do not depend
+ * :319-324 between them.  Optimizer::OptimizeSim3 (:332) is olf_optimize_sim3_pairs_dev below.  Results equal olf_sim3_solver pair by pair, bit for bit, and do not depend
  * on scheduling, on how the kernel chunks a window or on a pair's position in the list.
  * `in`: kps (octave), counts, img_stride, Tcw, mp_world, mp_valid (NULL: every feature holds a point) and fx, fy, cx, cy are read (frame j = image
  * j * img_stride; a count beyond the capacity is read as the capacity); mvLevelSigma2 is the context's.  d_mp_bad [n_frames][capacity] (or NULL: none is
@@ -1165,6 +1165,70 @@ int olf_debug_sim3_solver_lds_limit(int bytes);
 int olf_debug_sim3_solver_gate(float scale_factor, uint64_t* gate);
 /* tests: the iteration cap the solver's table holds for N correspondences (csrc/sim3solver_terms.hpp: s3_iteration_cap) */
 int olf_debug_sim3_solver_cap(int N, double probability, int min_inliers, int max_iterations, int32_t* cap);
+
+/* ---- Optimizer::OptimizeSim3 for a list of key-frame pairs on the device (csrc/optsim3_batch.hip, optsim3_host.cpp, optsim3_terms.hpp) ------------------
+ * int Optimizer::OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches1, g2o::Sim3 &g2oS12, const float th2, const bool bFixScale)
+ * (src/Optimizer.cc:2013-2208), called per loop candidate by LoopClosing::ComputeSim3 (src/LoopClosing.cc:332): the g2o graph of one free
+ * VertexSim3Expmap and, per correspondence in ascending i, one EdgeSim3ProjectXYZ and one EdgeInverseSim3ProjectXYZ against fixed camera-frame points,
+ * Huber kernels of the float delta sqrt(th2), optimize(5), the chi2 check against th2 that removes a failing correspondence's two edges and nulls its
+ * match, the `< 10` gate, optimize(10 or 5) from the current estimate, the final check.  The edges have no analytic Jacobian in the reference, so every
+ * linearisation differentiates numerically (14 perturbed estimates); that and every other term is csrc/optsim3_terms.hpp, one text for the host form
+ * and the kernel (C.4, C.27, C.28 of DESIGN.md).  The stale-error quirk of olf_pose_optimization_batch_dev holds here too: a check reads the _error the
+ * last computeActiveErrors() left, the rejected estimate's after a rejected last trial.
+ * The entry takes exactly what olf_search_by_sim3_pairs_dev took and wrote: `in`, d_mp_bad, d_pairs, the solver's best_s / best_R / best_t as d_s12 /
+ * d_R12 / d_t12, and its d_matches12 rows as io->matches12, nothing copied or re-indexed in between.  `in`: kps (pt, octave), counts, img_stride, Tcw,
+ * mp_world, mp_valid (NULL: every feature holds a point) and fx, fy, cx, cy are read (K1 = K2); mvInvLevelSigma2 is the context's.  matches12
+ * [n_pairs][capacity], in / out: value v at i < N1 is a correspondence iff 0 <= v < N2 (-1, -2 and >= N2 are "none" and stay as they are), both features
+ * hold a point and neither point is bad (:2068-2103; an entry that fails these keeps its value and is counted nowhere); an outlier of either check
+ * becomes -1.  d_row_active (or NULL: every pair runs) [n_pairs]: olf_sim3_solver_io.accepted.  th2 > 0 (the reference: 10); fix_scale: bFixScale.
+ * Per pair: S12_out [8] doubles (the quaternion as x, y, z, w -- g2o does not normalise it --, t, s) with its float forms s12_out, R12_out [9] (row-major,
+ * toRotationMatrix), t12_out [3], which olf_search_by_sim3_pairs_dev or another round takes; Scw_out [16] = toCvMat(gScm * Sim3(R2w, t2w, 1.0))
+ * (src/LoopClosing.cc:339-341), row-major, the d_Scw of olf_search_by_projection_sim3_batch_dev; n_inliers, the return value (0 where the `< 10` gate
+ * returned: the matches are nulled and S12_out is the input; -1 for an inactive or refused pair, of which nothing else is written); n_correspondences;
+ * n_bad_first (nBad); iters [2], the Levenberg iterations of the two optimize() calls; status, the pair's own word; chi2 [capacity][2], the values
+ * (e12, e21) each correspondence was last classified with, 0 elsewhere.
+ * Defined here, not by the reference: a depth of exactly 0 at any evaluation, the perturbed ones included (status bit 1), or an H, b, step or estimate that
+ * is not finite (bit 2) stops the pair: S12_out is the input, the match row as it stood at that moment, n_inliers = 0.  An empty graph returns 0.  A
+ * correspondence either of whose octaves lies outside the context's levels is left out and sets bit 4.  A pair whose index lies outside [0, n_frames), or
+ * with kf1 == kf2, sets bit 2048 of the context's status word.
+ * One launch: one workgroup per pair (grid-strided above 1024 pairs); the sums have a fixed correspondence-to-lane assignment and a fixed reduction shape,
+ * so a pair's outputs are the same bits wherever it stands in the list.  The device's exp / sin / cos are not the host's, and the numeric Jacobian
+ * amplifies a last-bit difference: device and host form agree on the real outputs within the tolerance the tests state, not bit for bit.  Like the other
+ * batch entries: no synchronisation and no host read, the batch scratch slot (only where 69 bytes per feature of the capacity exceed 60 KiB of LDS: that
+ * much per resident workgroup), n_pairs == 0 writes nothing, a NULL required pointer or th2 <= 0 is OLF_ERR_INVALID before any launch, a count beyond the
+ * capacity is read as the capacity, accesses are never out of bounds. */
+typedef struct olf_optimize_sim3_io {
+    int32_t* matches12;          /* [n_pairs][capacity]     in / out */
+    double*  S12_out;            /* [n_pairs][8]  */
+    float*   s12_out;            /* [n_pairs]     */
+    float*   R12_out;            /* [n_pairs][9]  */
+    float*   t12_out;            /* [n_pairs][3]  */
+    float*   Scw_out;            /* [n_pairs][16] */
+    int32_t* n_inliers;          /* [n_pairs]     */
+    int32_t* n_correspondences;  /* [n_pairs]     */
+    int32_t* n_bad_first;        /* [n_pairs]     */
+    int32_t* iters;              /* [n_pairs][2]  */
+    int32_t* status;             /* [n_pairs]     */
+    float*   chi2;               /* [n_pairs][capacity][2] */
+} olf_optimize_sim3_io;
+int olf_optimize_sim3_pairs_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const uint8_t* d_mp_bad, int n_pairs, const int32_t* d_pairs,
+                                const float* d_s12, const float* d_R12, const float* d_t12, float th2, int fix_scale, const int32_t* d_row_active,
+                                const olf_optimize_sim3_io* io, void* stream);
+/* the host form: ONE pair (kf1, kf2), host pointers in `in` and everywhere else, no context and no device, every sum serial in edge order.  capacity: the
+ * row length of the per-frame planes; inv_level_sigma2 [n_levels] = mvInvLevelSigma2; every pointer of io names this pair's element or row; without a
+ * context bit 2048 goes into the pair's status word. */
+int olf_optimize_sim3(const olf_track_batch* in, int capacity, int n_frames, const uint8_t* mp_bad, const float* inv_level_sigma2, int n_levels, int kf1,
+                      int kf2, float s12, const float* R12, const float* t12, float th2, int fix_scale, const olf_optimize_sim3_io* io);
+/* olf_optimize_sim3_pairs_dev from host pointers ON THE DEVICE (csrc/optsim3_api.cpp): the arrays are staged (the in / out rows and the outputs are
+ * uploaded first, so what the kernel leaves untouched comes back as it went in), the same kernel runs on the context's stream, the outputs come back;
+ * synchronises.  A set bit of the context's status word makes the call return OLF_ERR_CAPACITY with the bit's text, the outputs complete. */
+int olf_optimize_sim3_pairs(olf_ctx* ctx, const olf_track_batch* in, int n_frames, const uint8_t* mp_bad, int n_pairs, const int32_t* pairs, const float* s12,
+                            const float* R12, const float* t12, float th2, int fix_scale, const int32_t* row_active, const olf_optimize_sim3_io* io);
+/* tests: the LDS a workgroup may take for a pair's correspondences (bytes; above it they live in context scratch; <= 0 restores the default), and the
+ * numeric Jacobian of one edge (base_binary_edge.hpp:176-200) at an estimate: S12 [8] as S12_out, cam = fx, fy, cx, cy, X [3] the fixed point (P2c, or
+ * P1c with inverse != 0 for the inverse edge), obs [2], J [2][7] row-major; a depth of exactly 0 is OLF_ERR_INVALID */
+int olf_debug_optimize_sim3_lds_limit(int bytes);
+int olf_debug_optimize_sim3_jacobian(const double* S12, int fix_scale, const double* cam, const double* X, const double* obs, int inverse, double* J);
 
 /* ---- PnPsolver's RANSAC for a list of (key frame, frame) pairs on the device (csrc/pnpsolver_batch.hip) --------------------------------------------------
  * PnPsolver (src/PnPsolver.cc: EPnP inside a RANSAC) as Tracking::Relocalization drives it per candidate key frame (src/Tracking.cc:2255-2308): the

@@ -1325,6 +1325,75 @@ int PoseOptimization(olf_ctx* c, FrameT* pFrame, int32_t* status = nullptr)
     return good;
 }
 
+// ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:2013-2208) over the reference's own types ------------------------------------------------------------------------
+// The reference's signature behind the context: reads GetMapPointMatches(), GetPose(), mvKeysUn, mvInvLevelSigma2 and fx, fy, cx, cy of the key frames
+// (K1 = K2), isBad(), GetWorldPos() and GetIndexInKeyFrame() of the points, and rotation() / translation() / scale() of g2oS12; nulls the outliers of
+// vpMatches1, writes g2oS12 where the reference writes it and returns nIn.  The C entry's per-feature model (a match row of kf2 feature indices) is met by
+// laying kf2's matched features out at their kf1 index in a frame of their own.  The start passes through floats (s, the rotation matrix, t), which is what
+// LoopClosing::ComputeSim3 builds g2oS12 from (src/LoopClosing.cc:325-327).  c == NULL: the host form (olf_optimize_sim3, no device); otherwise the pair
+// runs on the device through context c (olf_optimize_sim3_pairs), whose capacity must hold vpMatches1 and whose level table must be the key frames'.
+// *status (or NULL) receives the pair's status word: where the reference is undefined (a depth of 0, a non-finite system) g2oS12 is not written, the
+// matches stay as they stood at that moment and 0 is returned (include/orbline.h).
+template <class KeyFrameT, class MapPointT, class Sim3T>
+int OptimizeSim3(olf_ctx* c, KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches1, Sim3T& g2oS12, const float th2, const bool bFixScale,
+                 int32_t* status = nullptr)
+{
+    typedef typename std::remove_const<typename std::remove_reference<decltype(g2oS12.rotation())>::type>::type QuatT;
+    typedef typename std::remove_const<typename std::remove_reference<decltype(g2oS12.translation())>::type>::type VecT;
+    const int N = (int)vpMatches1.size();
+    const int cap = c ? olf_orb_capacity(c) : std::max(N, 1);
+    if (N > cap) olf_detail::check(OLF_ERR_CAPACITY, "OptimizeSim3: more matches than the context's capacity");
+    const std::vector<MapPointT*> vpMapPoints1 = pKF1->GetMapPointMatches();
+    std::vector<olf_keypoint> kps(2 * (size_t)cap);
+    std::vector<float> world(6 * (size_t)cap, 0.f), chi2(2 * (size_t)cap, 0.f);
+    std::vector<uint8_t> valid(2 * (size_t)cap, 0), bad(2 * (size_t)cap, 0);
+    std::vector<int32_t> row((size_t)cap, -1);
+    for (int i = 0; i < N; ++i) {
+        std::memcpy(&kps[i], olf_detail::keypoints(pKF1->mvKeysUn) + i, sizeof(olf_keypoint));
+        MapPointT* pMP1 = i < (int)vpMapPoints1.size() ? vpMapPoints1[i] : nullptr;
+        MapPointT* pMP2 = vpMatches1[i];
+        if (pMP1) {
+            valid[i] = 1; bad[i] = pMP1->isBad() ? 1 : 0;
+            const auto X1 = pMP1->GetWorldPos();
+            for (int k = 0; k < 3; ++k) world[3 * (size_t)i + k] = X1.template at<float>(k);
+        }
+        if (!pMP2) continue;
+        const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+        if (i2 < 0) { row[i] = -2; continue; }
+        row[i] = i;
+        valid[(size_t)cap + i] = 1; bad[(size_t)cap + i] = pMP2->isBad() ? 1 : 0;
+        std::memcpy(&kps[(size_t)cap + i], olf_detail::keypoints(pKF2->mvKeysUn) + i2, sizeof(olf_keypoint));
+        const auto X2 = pMP2->GetWorldPos();
+        for (int k = 0; k < 3; ++k) world[3 * ((size_t)cap + i) + k] = X2.template at<float>(k);
+    }
+    float T[32];
+    olf_detail::mat4(pKF1->GetPose(), T);
+    olf_detail::mat4(pKF2->GetPose(), T + 16);
+    const int32_t counts[2] = {N, N}, pair[2] = {0, 1};
+    olf_track_batch in;
+    std::memset(&in, 0, sizeof in);
+    in.kps = kps.data(); in.counts = counts; in.img_stride = 1; in.Tcw = T; in.mp_world = world.data(); in.mp_valid = valid.data();
+    in.fx = pKF1->fx; in.fy = pKF1->fy; in.cx = pKF1->cx; in.cy = pKF1->cy;
+    const double qx = g2oS12.rotation().x(), qy = g2oS12.rotation().y(), qz = g2oS12.rotation().z(), qw = g2oS12.rotation().w();
+    const double tx = 2.0 * qx, ty = 2.0 * qy, tz = 2.0 * qz;                                                 // Quaterniond::toRotationMatrix
+    const double twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx, tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
+    const float R12[9] = {(float)(1.0 - (tyy + tzz)), (float)(txy - twz), (float)(txz + twy), (float)(txy + twz), (float)(1.0 - (txx + tzz)), (float)(tyz - twx),
+                          (float)(txz - twy), (float)(tyz + twx), (float)(1.0 - (txx + tyy))};
+    const float t12[3] = {(float)g2oS12.translation()[0], (float)g2oS12.translation()[1], (float)g2oS12.translation()[2]}, s12 = (float)g2oS12.scale();
+    double S[8];
+    float so, Ro[9], to[3], Scw[16];
+    int32_t nin = 0, ncorr = 0, nbad = 0, iters[2] = {0, 0}, st = 0;
+    const olf_optimize_sim3_io io = {row.data(), S, &so, Ro, to, Scw, &nin, &ncorr, &nbad, iters, &st, chi2.data()};
+    if (c) olf_detail::check(olf_optimize_sim3_pairs(c, &in, 2, bad.data(), 1, pair, &s12, R12, t12, th2, bFixScale ? 1 : 0, nullptr, &io), "olf_optimize_sim3_pairs");
+    else olf_detail::check(olf_optimize_sim3(&in, cap, 2, bad.data(), pKF1->mvInvLevelSigma2.data(), (int)pKF1->mvInvLevelSigma2.size(), 0, 1, s12, R12, t12, th2,
+                                             bFixScale ? 1 : 0, &io), "olf_optimize_sim3");
+    for (int i = 0; i < N; ++i) if (vpMatches1[i] && row[i] == -1) vpMatches1[i] = nullptr;
+    if (status) *status = st;
+    if ((st & 3) || ncorr - nbad < 10) return 0;                    // :2178-2179 returns before g2oS12 is written; a stopped pair leaves it alone
+    g2oS12 = Sim3T(QuatT(S[3], S[0], S[1], S[2]), VecT(S[4], S[5], S[6]), S[7]);
+    return nin;
+}
+
 // ---- Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc) over the reference's own types ---------------------------------------------------------------------
 // The reference's members with its signatures: the constructor (pKF1, pKF2, vpMatched12, bFixScale), SetRansacParameters, iterate, find and the three
 // GetEstimated*.  It runs over the host form olf_sim3_solver, so a single solver needs no device.  The constructor keeps the correspondences as :62-103 does,

@@ -158,6 +158,12 @@ class PosePointsOutputsC(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("Tcw_out", "outlier_out", "n_good", "n_initial", "chi2", "passes", "iters", "status")]
 
 
+class OptSim3IoC(C.Structure):
+    """olf_optimize_sim3_io (include/orbline.h): the in / out match rows and the outputs of Optimizer::OptimizeSim3 for a list of pairs"""
+    _fields_ = [(n, C.c_void_p) for n in ("matches12", "S12_out", "s12_out", "R12_out", "t12_out", "Scw_out", "n_inliers", "n_correspondences", "n_bad_first",
+                                          "iters", "status", "chi2")]
+
+
 class DiscardBatchC(C.Structure):
     """olf_discard_batch (include/orbline.h): the rows the "discard outliers" loops read and change"""
     _fields_ = ([(n, C.c_void_p) for n in ("counts", "lcounts")] + [("img_stride", C.c_int32)] +
@@ -394,6 +400,12 @@ def lib():
         L.olf_pose_optimization.argtypes = [C.POINTER(PosePointsBatchC), C.c_int, C.c_int, P, C.c_int, C.POINTER(PosePointsOutputsC)]
         L.olf_pose_optimization_rows.argtypes = [P, C.POINTER(PosePointsBatchC), C.c_int, C.c_int, C.POINTER(PosePointsOutputsC)]
         L.olf_debug_pose_points_lds_limit.argtypes = [C.c_int]
+        L.olf_optimize_sim3_pairs_dev.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, P, C.c_int, P, P, P, P, C.c_float, C.c_int, P, C.POINTER(OptSim3IoC), P]
+        L.olf_optimize_sim3.argtypes = [C.POINTER(TrackBatchC), C.c_int, C.c_int, P, P, C.c_int, C.c_int, C.c_int, C.c_float, P, P, C.c_float, C.c_int,
+                                        C.POINTER(OptSim3IoC)]
+        L.olf_optimize_sim3_pairs.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, P, C.c_int, P, P, P, P, C.c_float, C.c_int, P, C.POINTER(OptSim3IoC)]
+        L.olf_debug_optimize_sim3_lds_limit.argtypes = [C.c_int]
+        L.olf_debug_optimize_sim3_jacobian.argtypes = [P, C.c_int, P, P, P, C.c_int, P]
         L.olf_profile_enable.argtypes = [C.c_void_p, C.c_int]
         L.olf_profile_reset.argtypes = [C.c_void_p]
         L.olf_profile_stage_name.restype = C.c_char_p

@@ -8,6 +8,7 @@ int launch_copy16(const void* src, void* dst, size_t bytes, hipStream_t s);
 void sim3_solver_lds_limit(int bytes);      // sim3solver_batch.hip
 void pnp_solver_lds_limit(int bytes);       // pnpsolver_batch.hip
 void pose_points_lds_limit(int bytes);      // posepoints_batch.hip
+void optimize_sim3_lds_limit(int bytes);    // optsim3_batch.hip
 }
 
 using namespace olf;
@@ -48,6 +49,12 @@ int olf_debug_pnp_solver_lds_limit(int bytes)
 int olf_debug_pose_points_lds_limit(int bytes)
 {
     pose_points_lds_limit(bytes);
+    return OLF_OK;
+}
+
+int olf_debug_optimize_sim3_lds_limit(int bytes)
+{
+    optimize_sim3_lds_limit(bytes);
     return OLF_OK;
 }
 

@@ -130,27 +130,33 @@ PT_HD void quat_normalize_positive(double* q)
     const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
     for (int i = 0; i < 4; ++i) q[i] = q[i] / n;
 }
-PT_HD void quat_from_mat4(const double* T, double* q)
+// Eigen's Quaterniond(Matrix3d) of the 3 x 3 block at M (row-major, rows ld apart), NOT normalised (what g2o::Sim3 keeps; optsim3_terms.hpp)
+PT_HD void quat_of_rotation(const double* M, int ld, double* q)
 {
-    const double m00 = T[0], m11 = T[5], m22 = T[10];
+    const int dg = ld + 1;
+    const double m00 = M[0], m11 = M[dg], m22 = M[2 * dg];
     double t = (m00 + m11) + m22;
     if (t > 0.0) {
         t = sqrt(t + 1.0);
         q[3] = 0.5 * t;
         t = 0.5 / t;
-        q[0] = (T[9] - T[6]) * t; q[1] = (T[2] - T[8]) * t; q[2] = (T[4] - T[1]) * t;
+        q[0] = (M[2 * ld + 1] - M[ld + 2]) * t; q[1] = (M[2] - M[2 * ld]) * t; q[2] = (M[ld] - M[1]) * t;
     } else {
         int i = 0;
         if (m11 > m00) i = 1;
-        if (m22 > T[i * 5]) i = 2;
+        if (m22 > M[i * dg]) i = 2;
         const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(((T[i * 5] - T[j * 5]) - T[k * 5]) + 1.0);
+        t = sqrt(((M[i * dg] - M[j * dg]) - M[k * dg]) + 1.0);
         q[i] = 0.5 * t;
         t = 0.5 / t;
-        q[3] = (T[k * 4 + j] - T[j * 4 + k]) * t;
-        q[j] = (T[j * 4 + i] + T[i * 4 + j]) * t;
-        q[k] = (T[k * 4 + i] + T[i * 4 + k]) * t;
+        q[3] = (M[k * ld + j] - M[j * ld + k]) * t;
+        q[j] = (M[j * ld + i] + M[i * ld + j]) * t;
+        q[k] = (M[k * ld + i] + M[i * ld + k]) * t;
     }
+}
+PT_HD void quat_from_mat4(const double* T, double* q)
+{
+    quat_of_rotation(T, 4, q);
     quat_normalize_positive(q);
 }
 // Quaterniond::toRotationMatrix(), row-major 3 x 3

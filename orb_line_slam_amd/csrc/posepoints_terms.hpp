@@ -94,16 +94,21 @@ PT_HD void se3_exp(const double* u, Se3* s)
     pose::quat_from_mat4(T, s->q);                                  // SE3Quat(Quaterniond(R), V * upsilon) normalises
     pose::mat3_vec(V, up, s->t);
 }
+// Quaterniond * Quaterniond, the generic (not the SSE) product; o may not alias a or b
+PT_HD void quat_mul(const double* a, const double* b, double* o)
+{
+    const double ax = a[0], ay = a[1], az = a[2], aw = a[3], bx = b[0], by = b[1], bz = b[2], bw = b[3];
+    o[3] = ((aw * bw - ax * bx) - ay * by) - az * bz;
+    o[0] = ((aw * bx + ax * bw) + ay * bz) - az * by;
+    o[1] = ((aw * by + ay * bw) + az * bx) - ax * bz;
+    o[2] = ((aw * bz + az * bw) + ax * by) - ay * bx;
+}
 // SE3Quat::operator*, se3quat.h:104-110
 PT_HD void se3_mul(const Se3& a, const Se3& b, Se3* o)
 {
     double r[3], q[4];
     quat_rotate(a.q, b.t, r);
-    const double ax = a.q[0], ay = a.q[1], az = a.q[2], aw = a.q[3], bx = b.q[0], by = b.q[1], bz = b.q[2], bw = b.q[3];
-    q[3] = ((aw * bw - ax * bx) - ay * by) - az * bz;
-    q[0] = ((aw * bx + ax * bw) + ay * bz) - az * by;
-    q[1] = ((aw * by + ay * bw) + az * bx) - ax * bz;
-    q[2] = ((aw * bz + az * bw) + ax * by) - ay * bx;
+    quat_mul(a.q, b.q, q);
     for (int i = 0; i < 3; ++i) o->t[i] = a.t[i] + r[i];
     pose::quat_normalize_positive(q);
     for (int i = 0; i < 4; ++i) o->q[i] = q[i];

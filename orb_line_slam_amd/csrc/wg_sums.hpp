@@ -1,4 +1,4 @@
-// wg_sums.hpp -- the workgroup sum of the one-workgroup-per-row optimisers (pose_batch.hip, posepoints_batch.hip), stated once.  Each lane brings the sums
+// wg_sums.hpp -- the workgroup sum of the one-workgroup-per-row optimisers (pose_batch.hip, posepoints_batch.hip, optsim3_batch.hip), stated once.  Each lane brings the sums
 // of its own items (item i belongs to lane i % THREADS, added in ascending i); the lanes' sums are combined by an xor butterfly over the wave (both partners
 // form the same sum, so every lane ends with the same bits) and the waves' sums are added in wave order.  No floating-point atomics; the shape depends on
 // nothing but THREADS.

@@ -3,7 +3,7 @@ rows of 100 / 500 / 2000 held points, and the host form's (olf_pose_optimization
 capacity, where the edges of a row take 58 KB of LDS).  The rows are synthetic (no image is read): points at 2-15 m observed with half a pixel of noise
 times the level's scale, two in three stereo, one gross outlier in ten, a start pose a few centimetres and tenths of a degree off.  --distinct different
 rows are tiled over the list.
-    python tools/pose_points_latency.py [--distinct 16] [--host-rows 8]
+    python tools/pose_points_latency.py [--distinct 16] [--host-rows 8] [--held 100,500,2000] [--rows 1,64,1024]
 HIP events, warmed up, median of five windows of ten calls; the host form by the host clock over --host-rows rows."""
 import math
 import time
@@ -16,6 +16,8 @@ from orb_line_slam_amd._lib import KEYPOINT_DTYPE
 ap = parser()
 ap.set_defaults(distinct=16)
 ap.add_argument("--host-rows", type=int, default=8)
+ap.add_argument("--held", default="100,500,2000", help="held points per row, comma-separated")
+ap.add_argument("--rows", default="1,64,1024", help="rows per call, comma-separated")
 args = ap.parse_args()
 W, H, fx, bf = 1241, 376, 718.856, 386.1448
 cx, cy = W / 2.0, H / 2.0
@@ -61,10 +63,10 @@ def rows(D, held):
 
 
 line = "%-34s %5d rows of %4d held: %9.3f ms per call, %10.0f rows/s (median of 5 windows of 10, HIP events; min %.3f max %.3f ms)"
-for held in (100, 500, 2000):
+for held in (int(v) for v in args.held.split(",")):
     D = args.distinct
     kps, ur, Tcw, fmp, world = rows(D, min(held, cap))
-    for B in (1, 64, 1024):
+    for B in (int(v) for v in args.rows.split(",")):
         tile = np.arange(B) % D
         d = dict(kps=up(kps[tile].view(np.uint8).reshape(-1)), counts=up(np.full(B, min(held, cap), np.int32)), ur=up(ur[tile]), Tcw=up(Tcw[tile]), fmp=up(fmp[tile]), mpw=up(world))
         out = {}
