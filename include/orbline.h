@@ -41,7 +41,10 @@ int olf_default_params(olf_params* p);
  * the caller.
  * Image size: at most 4131 pixels wide and high (FAST candidates are packed with 12 bits per coordinate relative to the 16-pixel border, and the largest
  * coordinate is the side - 36), and large enough that every pyramid level keeps 62 x 62 pixels; anything else is OLF_ERR_INVALID, before any device allocation or
- * launch, and olf_last_error() names which limit was missed. */
+ * launch, and olf_last_error() names which limit was missed.
+ * A portrait image -- one whose pyramid has a level with round((w - 32) / (h - 32)) == 0, where ORBextractor's DistributeOctTree divides by zero -- gets a
+ * context in which no detector runs: olf_orb_extract*, olf_stereo_points, olf_line_extract* and olf_stereo_frames* return OLF_ERR_INVALID with a message;
+ * the entries on caller-supplied key points, key lines and descriptors (olf_lbd_compute among them) serve it. */
 int  olf_ctx_create(const olf_params* p, int width, int height, int max_images, olf_ctx** out);
 void olf_ctx_destroy(olf_ctx* ctx);
 /* Capacity overflows (more corners / key points / segments than a fixed-size device buffer holds) are never silent: the blocking
@@ -391,7 +394,14 @@ int olf_line_extract_dev(olf_ctx* ctx, const uint8_t* d_images, int n_images, ol
                          void* stream);
 int olf_line_extract(olf_ctx* ctx, const uint8_t* images, int n_images, olf_keyline* kls, uint8_t* ldesc, int32_t* lcounts);
 /* BinaryDescriptor::compute(image, keylines, descriptors) on caller-supplied key lines (host buffers;
- * Thirdparty/line_descriptor/src/binary_descriptor_custom.cpp:524-687): kls [n_images][capacity], counts[n_images] */
+ * Thirdparty/line_descriptor/src/binary_descriptor_custom.cpp:524-687): kls [n_images][capacity], counts[n_images].
+ * Only sPointInOctaveX/Y, ePointInOctaveX/Y, numOfPixels and angle of a key line are read.  Accepted domain: the four coordinates
+ * finite and within +-1e6, the angle finite, numOfPixels any int32 (the reference casts it to short: a value that casts to <= 0 gives
+ * an all-zero descriptor).  Inside that domain the key lines may lie anywhere, outside the image included: sample coordinates beyond
+ * +-32767 wrap through the reference's (short) cast (modulo 65536, as its x86 build does) before they are clamped into the image.
+ * With conv_libm_float = 1 the angle must also satisfy |angle| < 120: the device's cosf / sinf restate glibc's fast range reduction
+ * only, which is what glibc itself uses below 120.  A key line inside its image's count that leaves the domain fails the call with
+ * OLF_ERR_INVALID and a message, before anything is uploaded or launched; records past the count are not looked at. */
 int olf_lbd_compute(olf_ctx* ctx, const uint8_t* images, int n_images, const olf_keyline* kls, const int32_t* lcounts, uint8_t* ldesc);
 /* debug/test: the sigma-0.6 blurred, x1.2 upsampled LSD working image of `image` (dst >= ws*hs bytes) */
 int olf_lsd_debug_scaled(olf_ctx* ctx, int image, uint8_t* dst, int32_t* ws, int32_t* hs);

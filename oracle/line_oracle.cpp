@@ -867,6 +867,21 @@ int orc_lbd_compute(const uint8_t* img, int w, int h, const olf_keyline* kls, in
     return OLF_OK;
 }
 
+// orc_lbd_compute under conventions C.6 (libm_float: cosf / sinf of the angle, float 1 / sqrtf) and C.11 (gauss_sum256: the 5x5 blur's taps sum to 256)
+int orc_lbd_compute_conv(const uint8_t* img, int w, int h, const olf_keyline* kls, int n, uint8_t* desc, float* float_desc, int libm_float, int gauss_sum256)
+{
+    Image im(w, h);
+    std::memcpy(im.d.data(), img, (size_t)w * h);
+    std::vector<olf_keyline> k(kls, kls + n);
+    std::vector<uint8_t> d;
+    std::vector<float> fd;
+    LibmScope libm_scope(libm_float);
+    lbd_compute(im, k, d, float_desc ? &fd : nullptr, gauss_sum256);
+    std::memcpy(desc, d.data(), d.size());
+    if (float_desc) std::memcpy(float_desc, fd.data(), fd.size() * sizeof(float));
+    return OLF_OK;
+}
+
 int orc_sobel3(const uint8_t* img, int w, int h, int16_t* dx, int16_t* dy)
 {
     Image im(w, h);

@@ -18,6 +18,17 @@ int check_device(const olf_ctx* c, const char* who)
     return OLF_OK;
 }
 
+// the detectors (ORB, LSD) run in landscape contexts only; a portrait context (include/orbline.h, olf_ctx_create) describes and matches what the caller supplies
+static int check_landscape(const olf_ctx* c, const char* who)
+{
+    if (c->orb.portrait) {
+        set_error(std::string(who) + ": the context's image is portrait (a pyramid level's octree would have round(width / height) == 0 root cells, where the "
+                                     "reference divides by zero): no detector runs in it");
+        return OLF_ERR_INVALID;
+    }
+    return OLF_OK;
+}
+
 int scratch_get(olf_ctx* c, ScratchSlot slot, size_t bytes, void** out)
 {
     if (c->scratch_bytes[slot] < bytes) {
@@ -227,7 +238,7 @@ int olf_ctx_create(const olf_params* p, int width, int height, int max_images, o
     if (rc != OLF_OK) {
         set_error(rc == OLF_ERR_CAPACITY ? "olf_ctx_create: more than 32760 key points on one pyramid level (nfeatures too large for this scale factor / level count)"
                   : (width > kMaxOrbSide || height > kMaxOrbSide) ? "olf_ctx_create: image wider or higher than 4131 pixels (FAST candidates are packed with 12 bits per coordinate)"
-                                         : "olf_ctx_create: image size / ORB parameters not supported (every pyramid level needs at least 62 x 62 pixels and a landscape cell grid)");
+                                         : "olf_ctx_create: image size / ORB parameters not supported (every pyramid level needs at least 62 x 62 pixels)");
         delete c; return rc;
     }
     auto fail = [&](int code) { olf_ctx_destroy(c); return code; };
@@ -439,7 +450,7 @@ static int stage_line_lbd(olf_ctx* c, const uint8_t* d_images, int n, olf_keylin
     StageScope t(c, s, ST_LINE_LBD);
     OLF_TRY(launch_line_select(c->line.geom, c->lb, n, d_kls, d_lcounts, s));
     OLF_TRY(launch_lbd_dense(c->line.geom, c->lb, d_images, c->W, n, s));
-    return launch_lbd_desc(c->line.geom, c->lb, n, d_kls, d_ldesc, d_lcounts, s);
+    return launch_lbd_desc(c->line.geom, c->lb, n, d_kls, d_ldesc, d_lcounts, true, s);
 }
 static int stage_stereo_lines(olf_ctx* c, int n_pairs, const olf_keyline* d_kls, const uint8_t* d_ldesc, const int32_t* d_lcounts, int32_t* d_m12, float* d_disp, double* d_le, hipStream_t s)
 {
@@ -454,6 +465,7 @@ int olf_orb_extract_dev(olf_ctx* c, const uint8_t* d_images, int n_images, olf_k
     OLF_TRY(check_device(c, "olf_orb_extract_dev"));
     if (n_images < 0 || n_images > c->max_images) { set_error("olf_orb_extract_dev: n_images exceeds the context capacity"); return OLF_ERR_CAPACITY; }
     if (n_images == 0) return OLF_OK;   // ORBextractor::operator() returns silently on an empty image
+    OLF_TRY(check_landscape(c, "olf_orb_extract_dev"));
     hipStream_t s = ctx_stream(c, stream);
     OLF_TRY(stage_orb_pyramid(c, d_images, n_images, s));
     OLF_TRY(stage_orb_fast(c, n_images, s));
@@ -495,6 +507,7 @@ int olf_stereo_points_dev(olf_ctx* c, int n_pairs, const olf_keypoint* d_kps, co
     OLF_TRY(check_device(c, "olf_stereo_points_dev"));
     if (n_pairs < 0 || 2 * n_pairs > c->max_images) return OLF_ERR_CAPACITY;
     if (n_pairs == 0) return OLF_OK;
+    OLF_TRY(check_landscape(c, "olf_stereo_points_dev"));      // (it reads the pyramids of the ORB extraction before it)
     return stage_stereo_points(c, n_pairs, d_kps, d_desc, d_counts, d_uright, d_depth, ctx_stream(c, stream));
 }
 
@@ -609,6 +622,7 @@ int olf_line_extract_dev(olf_ctx* c, const uint8_t* d_images, int n_images, olf_
     OLF_TRY(check_device(c, "olf_line_extract_dev"));
     if (n_images < 0 || n_images > c->max_images) return OLF_ERR_CAPACITY;
     if (n_images == 0) return OLF_OK;
+    OLF_TRY(check_landscape(c, "olf_line_extract_dev"));
     hipStream_t s = ctx_stream(c, stream);
     const LsdPlan plan = lsd_plan(c->line.geom, c->lb, c->lsd_force, c->limits, n_images);
     OLF_TRY(stage_lsd_front(c, plan, d_images, n_images, s, true));
@@ -638,6 +652,7 @@ int olf_stereo_frames_dev(olf_ctx* c, const uint8_t* d_images, int n_pairs, cons
     OLF_TRY(check_device(c, "olf_stereo_frames_dev"));
     if (n_pairs < 0 || 2 * n_pairs > c->max_images) return OLF_ERR_CAPACITY;
     if (n_pairs == 0) return OLF_OK;
+    OLF_TRY(check_landscape(c, "olf_stereo_frames_dev"));
     hipStream_t s = ctx_stream(c, stream), ls = c->stream2;
     const int n_images = 2 * n_pairs;
     const LineGeom& lg = c->line.geom;
@@ -725,7 +740,7 @@ int olf_stereo_frames_dev(olf_ctx* c, const uint8_t* d_images, int n_pairs, cons
     {
         StageScope t(c, ls, ST_LINE_LBD);
         OLF_TRY(launch_line_select(lg, c->lb, n_images, o->kls, o->lcounts, ls));
-        OLF_TRY(launch_lbd_desc(lg, c->lb, n_images, o->kls, o->ldesc, o->lcounts, ls));
+        OLF_TRY(launch_lbd_desc(lg, c->lb, n_images, o->kls, o->ldesc, o->lcounts, true, ls));
     }
     OLF_TRY(stage_stereo_lines(c, n_pairs, o->kls, o->ldesc, o->lcounts, o->lmatches12, o->ldisp, o->lle, ls));
     OLF_HIP_CHECK(hipEventRecord(c->ev_join, ls));

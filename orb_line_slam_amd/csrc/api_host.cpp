@@ -1,6 +1,8 @@
 // api_host.cpp -- the host-pointer entries of the C ABI: each stages its arrays on the device, calls the _dev entry or the launcher of the same name and
 // brings the results back.  The entries on caller-sized arrays go through HostCall (staging.hpp); those on the context's own frame arrays (fb_copy, the
 // one-pair slab of olf_stereo_frames) keep the copies they were measured with.  Every entry checks its arguments, then the device, then touches HIP.
+#include <cmath>
+#include <string>
 #include "ctx.hpp"
 #include "staging.hpp"
 
@@ -85,6 +87,25 @@ int olf_lbd_compute(olf_ctx* c, const uint8_t* images, int n_images, const olf_k
     if (n_images == 0) return OLF_OK;
     for (int i = 0; i < n_images; ++i)
         if (lcounts[i] < 0 || lcounts[i] > c->line.geom.outCap) { set_error("olf_lbd_compute: count exceeds capacity"); return OLF_ERR_CAPACITY; }
+    // the accepted domain (include/orbline.h): beyond it the reference's float -> short conversion and its libm calls have no defined answer to reproduce
+    for (int i = 0; i < n_images; ++i)
+        for (int j = 0; j < lcounts[i]; ++j) {
+            const olf_keyline& kl = kls[(size_t)i * c->line.geom.outCap + j];
+            const float xy[4] = {kl.sPointInOctaveX, kl.sPointInOctaveY, kl.ePointInOctaveX, kl.ePointInOctaveY};
+            for (float v : xy)
+                if (!std::isfinite(v) || std::fabs(v) > 1e6f) {
+                    set_error("olf_lbd_compute: key line " + std::to_string(j) + " of image " + std::to_string(i) + " has a non-finite coordinate or one beyond +-1e6");
+                    return OLF_ERR_INVALID;
+                }
+            if (!std::isfinite(kl.angle)) {
+                set_error("olf_lbd_compute: key line " + std::to_string(j) + " of image " + std::to_string(i) + " has a non-finite angle");
+                return OLF_ERR_INVALID;
+            }
+            if (c->line.geom.libmFloat && !(std::fabs(kl.angle) < 120.0f)) {      // (glibc_sincosf_core, device_math.hpp: glibc's fast range reduction only)
+                set_error("olf_lbd_compute: key line " + std::to_string(j) + " of image " + std::to_string(i) + " has |angle| >= 120 under conv_libm_float");
+                return OLF_ERR_INVALID;
+            }
+        }
     OLF_TRY(check_device(c, "olf_lbd_compute"));
     olf_frame_buffers h = {}; h.kls = const_cast<olf_keyline*>(kls); h.ldesc = ldesc; h.lcounts = const_cast<int32_t*>(lcounts);
     OLF_HIP_CHECK(hipMemcpyAsync(c->d_images, images, (size_t)c->W * c->H * n_images, hipMemcpyHostToDevice, c->stream));
@@ -92,7 +113,7 @@ int olf_lbd_compute(olf_ctx* c, const uint8_t* images, int n_images, const olf_k
     OLF_TRY(fb_copy(c, h, FB_KLS, FB_KLS, n_images, hipMemcpyHostToDevice));
     OLF_TRY(fb_copy(c, h, FB_LCOUNTS, FB_LCOUNTS, n_images, hipMemcpyHostToDevice));
     OLF_TRY(launch_lbd_dense(c->line.geom, c->lb, c->d_images, c->W, n_images, c->stream));
-    OLF_TRY(launch_lbd_desc(c->line.geom, c->lb, n_images, c->d_out.kls, c->d_out.ldesc, c->d_out.lcounts, c->stream));
+    OLF_TRY(launch_lbd_desc(c->line.geom, c->lb, n_images, c->d_out.kls, c->d_out.ldesc, c->d_out.lcounts, false, c->stream));
     OLF_TRY(fb_copy(c, h, FB_LDESC, FB_LDESC, n_images, hipMemcpyDeviceToHost));
     OLF_HIP_CHECK(hipStreamSynchronize(c->stream));
     return OLF_OK;

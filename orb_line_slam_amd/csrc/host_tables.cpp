@@ -161,7 +161,8 @@ int OrbHostTables::build(const olf_orb_params& p, int W, int H)
         L.quota = nPerLevel[l];
         maxQuota = std::max(maxQuota, L.quota);
         L.nIni = (int)std::round(width / height);
-        if (L.nIni < 1) return OLF_ERR_INVALID;   // portrait images divide by zero in the reference
+        // portrait images divide by zero in the reference: no detector runs in such a context (olf_ctx_create); one root keeps the tables well formed
+        if (L.nIni < 1) { portrait = true; L.nIni = 1; }
         L.hX = width / L.nIni;
         L.scale = sf[l]; L.inv_scale = inv_sf[l];
         L.patch_size = (int)(31 * sf[l]);

@@ -156,7 +156,8 @@ __global__ __launch_bounds__(64) void k_lbd_prep(const LineGeom* __restrict__ gp
 // row's 16 pixel offsets to LDS, the wave loads them as (4 rows x 16 consecutive samples) per instruction -- 4 to 8 cache lines -- and hands the values back
 // through the same LDS words.  Steep lines keep the direct form (their rows are horizontal: 63 neighbouring pixels per instruction as it is).
 constexpr int LR_U = 16, LR_P = LR_U + 1;      // samples per step; row pitch of the LDS tile in words (17: lanes = rows and lanes = samples both hit distinct banks)
-template <bool LEAN>      // LEAN: the image is smaller than 32768 - 256 pixels a side (chosen at the launch): the lean form of the sample coordinates below
+template <bool LEAN>      // LEAN: the key lines are the detector's own (inside the image) and the image is smaller than 32768 - 256 pixels a side
+                          // (chosen at the launch): the lean form of the sample coordinates below.  Caller-supplied key lines take the general form.
 __global__ __launch_bounds__(256) void k_lbd_rows(const LineGeom* __restrict__ gp, const uint32_t* __restrict__ dxdyAll,
                                                   const olf_keyline* __restrict__ kls, const int* __restrict__ counts,
                                                   const float2* __restrict__ starts, float4* __restrict__ rowSums)
@@ -198,10 +199,14 @@ __global__ __launch_bounds__(256) void k_lbd_rows(const LineGeom* __restrict__ g
                 const float bx = f_sub(sCorX, rx) == 0.5f ? f_add(rx, 1.0f) : rx, by = f_sub(sCorY, ry) == 0.5f ? f_add(ry, 1.0f) : ry;
                 xCor = min(max((int)bx, 0), (int)imageWidth); yCor = min(max((int)by, 0), (int)imageHeight);
             } else {
-            int tc = (int)(short)roundf(sCorX);
-            xCor = tc < 0 ? 0 : (tc > imageWidth ? imageWidth : tc);
-            tc = (int)(short)roundf(sCorY);
-            yCor = tc < 0 ? 0 : (tc > imageHeight ? imageHeight : tc);
+                // the reference's own form: round(), (short), clamp.  The cast goes through int so that a coordinate beyond +-32767 wraps modulo 65536, as
+                // the reference's x86 build does (cvttss2si, low word), instead of hitting the undefined float -> short conversion; the sums of
+                // olf_lbd_compute's domain (|coordinate| <= 1e6, at most 32767 unit steps, 31 rows) stay far inside int.  Whatever tc is -- a masked
+                // tail sample past the row's end included -- the clamp below leaves 0 <= xCor <= W - 1 and 0 <= yCor <= H - 1.
+                int tc = (int)(short)(int)roundf(sCorX);
+                xCor = tc < 0 ? 0 : (tc > imageWidth ? imageWidth : tc);
+                tc = (int)(short)(int)roundf(sCorY);
+                yCor = tc < 0 ? 0 : (tc > imageHeight ? imageHeight : tc);
             }
             off[u] = yCor * realWidth + xCor;           // (coordinates past the row end are clamped into the image, the value is unused)
             sCorX = f_add(sCorX, dL0);
@@ -367,11 +372,14 @@ int launch_line_select(const LineGeom& g, const LineDeviceBufs& b, int n_images,
     return OLF_OK;
 }
 
-// BinaryDescriptor::compute on the key lines in d_kls / d_counts, behind launch_lbd_dense
-int launch_lbd_desc(const LineGeom& g, const LineDeviceBufs& b, int n_images, const olf_keyline* d_kls, uint8_t* d_desc, const int* d_counts, hipStream_t s)
+// BinaryDescriptor::compute on the key lines in d_kls / d_counts, behind launch_lbd_dense.  detected_lines: the key lines are LSDDetectorC's own, clipped
+// into the image with numOfPixels counted along them -- the lean coordinate form is exact for those; a caller's key lines may lie anywhere and take the
+// reference's (short) cast as it stands.
+int launch_lbd_desc(const LineGeom& g, const LineDeviceBufs& b, int n_images, const olf_keyline* d_kls, uint8_t* d_desc, const int* d_counts, bool detected_lines,
+                    hipStream_t s)
 {
     hipLaunchKernelGGL(k_lbd_prep, dim3((g.outCap + 63) / 64, n_images), dim3(64), 0, s, b.geom, d_kls, d_counts, reinterpret_cast<float2*>(b.lbdStarts));
-    if (g.W + 256 < 32768 && g.H + 256 < 32768)
+    if (detected_lines && g.W + 256 < 32768 && g.H + 256 < 32768)
         hipLaunchKernelGGL(k_lbd_rows<true>, dim3((g.outCap + 3) / 4, n_images), dim3(256), 0, s, b.geom, b.dxdy, d_kls, d_counts,
                            reinterpret_cast<const float2*>(b.lbdStarts), reinterpret_cast<float4*>(b.rowSums));
     else

@@ -148,7 +148,8 @@ int launch_lsd_rect(const LineGeom& g, const LineDeviceBufs& b, const LsdPlan& p
 // selection of the key lines, the LBD gradient images (of the input images alone), the descriptors (of both)
 int launch_line_select(const LineGeom& g, const LineDeviceBufs& b, int n_images, olf_keyline* d_kls, int* d_counts, hipStream_t s);
 int launch_lbd_dense(const LineGeom& g, const LineDeviceBufs& b, const uint8_t* d_in, int in_pitch, int n_images, hipStream_t s);
-int launch_lbd_desc(const LineGeom& g, const LineDeviceBufs& b, int n_images, const olf_keyline* d_kls, uint8_t* d_desc, const int* d_counts, hipStream_t s);
+int launch_lbd_desc(const LineGeom& g, const LineDeviceBufs& b, int n_images, const olf_keyline* d_kls, uint8_t* d_desc, const int* d_counts, bool detected_lines,
+                    hipStream_t s);
 int launch_gauss7_img(const uint8_t* src, int srcPitch, size_t srcStride, uint8_t* dst, int dstPitch, size_t dstStride, int W, int H,
                       const LineGeom& g, int which, int n_images, hipStream_t s);
 int launch_lsd_angle_table(LineDeviceBufs& b, int libmFloat, hipStream_t s);

@@ -210,6 +210,7 @@ struct OrbHostTables {
     std::vector<int> nPerLevel;
     OrbGeom geom;
     std::vector<ResizeCoef> rx, ry;    // concatenated over levels
+    bool portrait = false;             // a level's octree would have round(width / height) == 0 root cells: the context describes and matches only
     int build(const olf_orb_params& p, int W, int H);
 };
 

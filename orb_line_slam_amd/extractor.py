@@ -182,6 +182,23 @@ class Lineextractor:
         check(lib().olf_lbd_compute(ctx.handle, ptr(image[None].copy()), 1, ptr(k), ptr(counts), ptr(desc)), "olf_lbd_compute")
         return desc[0, :len(keylines)].copy()
 
+    def compute_batch(self, images, keylines, counts):
+        """olf_lbd_compute as it is: images (n, H, W) uint8, keylines (n, capacity) records of which image i supplies the first counts[i]
+        -> descriptors (n, capacity, 32); rows past an image's count are not computed (they hold whatever the context's buffer held)."""
+        images = np.ascontiguousarray(images)
+        if images.dtype != np.uint8 or images.ndim != 3:
+            raise TypeError("compute_batch: images must be (n, H, W) uint8")
+        n, h, w = images.shape
+        ctx = self._context(w, h, n)
+        cap = ctx.line_capacity
+        keylines = np.ascontiguousarray(keylines, KEYLINE_DTYPE)
+        counts = np.ascontiguousarray(counts, np.int32)
+        if keylines.shape != (n, cap) or counts.shape != (n,):
+            raise ValueError(f"compute_batch: keylines must be ({n}, {cap}) and counts ({n},)")
+        desc = np.zeros((n, cap, DESC_BYTES), np.uint8)
+        check(lib().olf_lbd_compute(ctx.handle, ptr(images), n, ptr(keylines), ptr(counts), ptr(desc)), "olf_lbd_compute")
+        return desc
+
     def debug_scaled(self, image=0):
         ctx = self._ctx
         buf = np.zeros(int(ctx.width * 1.5) * int(ctx.height * 1.5), np.uint8)

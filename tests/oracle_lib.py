@@ -213,14 +213,18 @@ def line_extract(img, lp, use_std_sort=False, cap=None, all_cap=20000):
     return dict(kls=kls[:n.value].copy(), desc=desc[:n.value].copy(), all=allk[:min(na.value, all_cap)].copy(), n_all=na.value)
 
 
-def lbd_compute(img, kls, want_float=False):
+def lbd_compute(img, kls, want_float=False, libm_float=0, gauss_sum256=0):
+    """BinaryDescriptor::compute on the caller's key lines; libm_float / gauss_sum256: conventions C.6 / C.11 (0 = the defaults)"""
     img = np.ascontiguousarray(img)
     kls = np.ascontiguousarray(kls)
     h, w = img.shape
     n = len(kls)
     desc = np.zeros((n, 32), np.uint8)
     fd = np.zeros((n, 72), np.float32) if want_float else None
-    _L.orc_lbd_compute(_p(img), w, h, _p(kls), n, _p(desc), _p(fd))
+    if libm_float or gauss_sum256:
+        _L.orc_lbd_compute_conv(_p(img), w, h, _p(kls), n, _p(desc), _p(fd), int(libm_float), int(gauss_sum256))
+    else:
+        _L.orc_lbd_compute(_p(img), w, h, _p(kls), n, _p(desc), _p(fd))
     return (desc, fd) if want_float else desc
 
 

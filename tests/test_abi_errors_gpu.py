@@ -79,6 +79,88 @@ def test_bad_arguments_are_reported():
     assert L.olf_orb_extract(ctx.handle, _p(np.full((1, 480, 640), 50, np.uint8)), 1, _p(k), _p(dd), _p(c)) == OLF_OK and c[0] == 0
 
 
+def test_lbd_compute_rejects_key_lines_outside_its_domain(oracle):
+    """olf_lbd_compute (include/orbline.h): a key line inside its count with a non-finite coordinate or angle, or a coordinate beyond +-1e6, fails the
+    call with OLF_ERR_INVALID and a message before anything is uploaded or launched; under conv_libm_float also |angle| >= 120.  Records past the
+    count are not looked at, and the context works afterwards."""
+    import lbd_scenes as S
+    L = _lib.lib()
+    W, H = 64, 64
+    img = S.image("noise", W, H)[None].copy()
+    good, _ = S.scene(11, W, H)
+    for libm_float in (0, 1):
+        p = _lib.default_params()
+        p.line.lsd_nfeatures, p.line.conv_libm_float, p.orb.nlevels = 8, libm_float, 1
+        ctx = _lib.Context(p, W, H, 2)
+        cap = ctx.line_capacity
+        assert cap >= 8
+        cnt = np.array([5], np.int32)
+
+        def call(field, value, row=4, images=img, counts=cnt):
+            k = np.zeros((len(counts), cap), _lib.KEYLINE_DTYPE)
+            k[:] = good[:cap]
+            k[len(counts) - 1, row][field] = value
+            d = np.full((len(counts), cap, 32), 0xAB, np.uint8)
+            rc = L.olf_lbd_compute(ctx.handle, _p(images), len(counts), _p(k), _p(counts), _p(d))
+            return rc, d, k
+
+        for field in ("sPointInOctaveX", "sPointInOctaveY", "ePointInOctaveX", "ePointInOctaveY"):
+            for value in (np.nan, np.inf, -np.inf, 1.5e6, -1.5e6):
+                rc, d, _ = call(field, value)
+                assert rc == OLF_ERR_INVALID and b"olf_lbd_compute" in L.olf_last_error() and b"coordinate" in L.olf_last_error(), (field, value)
+                assert (d == 0xAB).all()                                      # nothing was written
+        for value in (np.nan, np.inf, -np.inf):
+            rc, d, _ = call("angle", value)
+            assert rc == OLF_ERR_INVALID and b"angle" in L.olf_last_error() and (d == 0xAB).all()
+        # the last key line of the second image of a two-image call is found too
+        rc, d, _ = call("ePointInOctaveY", np.nan, row=2, images=np.concatenate([img, img]), counts=np.array([0, 3], np.int32))
+        assert rc == OLF_ERR_INVALID and b"image 1" in L.olf_last_error() and (d == 0xAB).all()
+        # |angle| >= 120: only the float overloads' range reduction stops there
+        for value in (120.0, -120.0, 1e6):
+            rc, d, k = call("angle", value)
+            if libm_float:
+                assert rc == OLF_ERR_INVALID and b"120" in L.olf_last_error() and (d == 0xAB).all()
+            else:
+                assert rc == OLF_OK
+        # inside the domain: its edge, and anything in a record past the count
+        for field, value, row in (("sPointInOctaveX", 1e6, 4), ("ePointInOctaveY", -1e6, 4), ("angle", float(np.nextafter(np.float32(120), np.float32(0))), 4),
+                                  ("sPointInOctaveX", np.nan, 5), ("angle", np.inf, 7), ("ePointInOctaveY", 3e7, 6)):
+            rc, d, k = call(field, value, row)
+            assert rc == OLF_OK, (field, value, L.olf_last_error())
+            assert np.array_equal(d[0, :5], oracle.lbd_compute(img[0], k[0, :5], libm_float=libm_float)), (field, value)
+        ctx.close()
+
+
+def test_portrait_context_describes_but_does_not_detect(oracle):
+    """A 64 x 203 image has round((w - 32) / (h - 32)) == 0 octree roots, where ORBextractor divides by zero: its context exists, every entry that runs a
+    detector says so with OLF_ERR_INVALID and launches nothing, and olf_lbd_compute on the caller's key lines works (tests/test_lbd_gpu.py runs its scenes
+    at this size)."""
+    import lbd_scenes as S
+    L = _lib.lib()
+    W, H = 64, 203
+    p = _lib.default_params()
+    p.orb.nlevels, p.line.lsd_nfeatures = 1, 16
+    ctx = _lib.Context(p, W, H, 2)
+    img = np.stack([S.image("noise", W, H), S.image("sinusoids", W, H)])
+    cap, lcap = ctx.orb_capacity, ctx.line_capacity
+    kps, desc, cnt = np.zeros((2, cap), _lib.KEYPOINT_DTYPE), np.full((2, cap, 32), 0xAB, np.uint8), np.full(2, -7, np.int32)
+    ur, dp = np.zeros((1, cap), np.float32), np.zeros((1, cap), np.float32)
+    kls, ldesc = np.zeros((2, lcap), _lib.KEYLINE_DTYPE), np.full((2, lcap, 32), 0xAB, np.uint8)
+    assert L.olf_orb_extract(ctx.handle, _p(img), 1, _p(kps), _p(desc), _p(cnt)) == OLF_ERR_INVALID and b"portrait" in L.olf_last_error()
+    assert L.olf_stereo_points(ctx.handle, _p(img), 1, _p(kps), _p(desc), _p(cnt), _p(ur), _p(dp)) == OLF_ERR_INVALID and b"portrait" in L.olf_last_error()
+    assert L.olf_line_extract(ctx.handle, _p(img), 2, _p(kls), _p(ldesc), _p(cnt)) == OLF_ERR_INVALID and b"portrait" in L.olf_last_error()
+    assert (desc == 0xAB).all() and (ldesc == 0xAB).all() and (cnt == -7).all()
+    assert L.olf_orb_extract(ctx.handle, _p(img), 0, _p(kps), _p(desc), _p(cnt)) == OLF_OK                    # an empty batch is still fine
+    k, _ = S.scene(11, W, H)
+    kls[:] = k[:lcap]
+    lc = np.array([lcap, 5], np.int32)
+    assert L.olf_lbd_compute(ctx.handle, _p(img), 2, _p(kls), _p(lc), _p(ldesc)) == OLF_OK, L.olf_last_error()
+    for i in range(2):
+        assert np.array_equal(ldesc[i, :lc[i]], oracle.lbd_compute(img[i], kls[i, :lc[i]]))
+    assert L.olf_ctx_synchronize(ctx.handle) == OLF_OK
+    ctx.close()
+
+
 def test_noise_beyond_the_old_segment_capacity_and_async_overflow_report(oracle):
     """Pure noise at lsd_scale 2 gives 9105 raw segments: rounds 1-3 refused it at run time (capacity 4096 / 8192, fuzz configuration #678).  The raw list is
     now sized by the working image (Ps / 48) and k_line_select sorts lists beyond its 64 KB of LDS in global memory: the top 100 must equal the oracle's.
