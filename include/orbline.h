@@ -1128,7 +1128,8 @@ int olf_update_normal_and_depth_points(olf_ctx* ctx, const olf_map_graph* g, con
  * not empty), no_more (bNoMore), n_inliers (0 unless accepted), inliers [n_pairs][capacity] (uint8, indexed by i1; positions below N1 are written, all 0
  * unless accepted; positions from N1 on are left as they are), n_correspondences (N), and counts [n_pairs][max_iterations] (may be NULL): the inlier
  * count of every iteration this call evaluated at its absolute index, the others untouched.  N < min_inliers: no_more = 1 and the state is untouched.
- * Arithmetic (csrc/sim3solver_terms.hpp, one text for this entry and its host form; C.4, C.12, C.17, C.20 to C.22 of DESIGN.md).
+ * Arithmetic (csrc/sim3solver_terms.hpp and, for the sample of C.20, ransac_terms.hpp: one text for this entry and its host form; C.4, C.12, C.17,
+ * C.20 to C.22 of DESIGN.md).
  * A pair whose index lies outside [0, n_frames), or with kf1 == kf2, gets n_inliers = -1, nothing else of it is written, and bit 2048 is set.  Errors,
  * before any launch: a NULL required pointer, a negative count, min_inliers < 3, max_iterations < 1, n_iterations < 0 or probability outside (0, 1):
  * OLF_ERR_INVALID.  n_pairs == 0 writes nothing.  Does not synchronise; runs on `stream`.  Nothing is read or written out of bounds.
@@ -1273,8 +1274,8 @@ int olf_debug_optimize_sim3_jacobian(const double* S12, int fix_scale, const dou
  * positions from N_frame on are left as they are), Tcw [16] (written only when accepted: refined_Tcw, or best_Tcw at the cap), n_correspondences (N), and
  * counts [n_pairs][max_iterations] (may be NULL): the inlier count of every iteration this call evaluated at its index modulo max_iterations, the others
  * untouched.  N < the effective min_inliers: no_more = 1 and the state is untouched.
- * Arithmetic (csrc/pnpsolver_terms.hpp, one text for this entry and its host form; C.4, C.19, C.20, C.23 to C.26 of DESIGN.md): compute_pose in double as
- * written; the OpenCV calls as an OpenCV without LAPACK makes them (one-sided Jacobi in double; cvSolve / cvInvert skip singular values at or below
+ * Arithmetic (csrc/pnpsolver_terms.hpp and, for the sample of C.20, ransac_terms.hpp: one text for this entry and its host form; C.4, C.19, C.20,
+ * C.23 to C.26 of DESIGN.md): compute_pose in double as written; the OpenCV calls as an OpenCV without LAPACK makes them (one-sided Jacobi in double; cvSolve / cvInvert skip singular values at or below
  * 2 DBL_EPSILON times their sum); qr_solve's singular return leaves x at 0 in the first Gauss-Newton round; sums over the correspondences in the
  * reference's order in a four-point fit and in a fixed blocked order in Refine (256 partial sums by index modulo 256, a balanced tree of neighbours per
  * 64, the four results in ascending order).  OpenCV's fill of a singular vector whose norm is <= DBL_MIN from its fixed-seed generator is NOT restated:
@@ -1523,7 +1524,7 @@ int olf_discard_outliers(const olf_discard_batch* io, int capacity, int line_cap
  * sqrt(7.815), four passes of OptimizationAlgorithmLevenberg (10 iterations, LinearSolverDense) each from toSE3Quat(mTcw), each followed by the chi2
  * classification in float, the kernels removed after the third, one pass only below 10 edges; the call of Tracking::Relocalization
  * (src/Tracking.cc:2310, :2326, :2341), TrackWithMotionModel (:1242 ff.) and TrackReferenceKeyFrame (:932 ff.).  Doubles throughout; the arithmetic of every
- * term, of Eigen's LDLT and of the Levenberg loop is csrc/posepoints_terms.hpp, the same text for the host form and the kernel (C.4, C.27 of DESIGN.md).
+ * term is csrc/posepoints_terms.hpp, of Eigen's LDLT and of the Levenberg loop csrc/g2o_levenberg.hpp, the same text for the host form and the kernel (C.4, C.27).
  * A ROW is one call of the reference: relocalisation optimises one frame once per candidate key frame.  Device pointers.  Without `pairs`, row r reads
  * frame r (image r * img_stride of kps / counts, row r of uright) and a non-negative frame_mp value v is point v + mp_index_offset[r] of mp_world: the
  * convention of olf_pose_batch, so the output of the frame-to-frame and key-frame BoW searches goes in as documented there (n_rows <= n_frames).  With

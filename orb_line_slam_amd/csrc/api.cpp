@@ -150,6 +150,13 @@ int ctx_level_scales(const olf_ctx* c, float* sf)
     for (int l = 0; l < OLF_MAX_LEVELS; ++l) sf[l] = l < n ? c->orb.sf[l] : 1.f;
     return n;
 }
+int ctx_level_inv_sigma2(const olf_ctx* c, float* inv_sigma2)
+{
+    float sf[OLF_MAX_LEVELS];
+    const int n = ctx_level_scales(c, sf);
+    for (int l = 0; l < OLF_MAX_LEVELS; ++l) { const float sigma2 = sf[l] * sf[l]; inv_sigma2[l] = 1.0f / sigma2; }      // src/ORBextractor.cc:434-436
+    return n;
+}
 int ctx_level_thresholds(olf_ctx* c, float* thr)
 {
     const int n = c->params.orb.nlevels;

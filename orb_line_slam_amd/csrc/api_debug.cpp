@@ -2,13 +2,10 @@
 // (olf_orb_pyramid_level, olf_orb_debug_candidates, olf_lsd_debug_scaled).
 #include "ctx.hpp"
 #include "staging.hpp"
+#include "wg_state.hpp"
 
 namespace olf {
 int launch_copy16(const void* src, void* dst, size_t bytes, hipStream_t s);
-void sim3_solver_lds_limit(int bytes);      // sim3solver_batch.hip
-void pnp_solver_lds_limit(int bytes);       // pnpsolver_batch.hip
-void pose_points_lds_limit(int bytes);      // posepoints_batch.hip
-void optimize_sim3_lds_limit(int bytes);    // optsim3_batch.hip
 }
 
 using namespace olf;
@@ -36,25 +33,25 @@ int olf_orb_pyramid_level(olf_ctx* c, int image, int level, int blurred, uint8_t
 
 int olf_debug_sim3_solver_lds_limit(int bytes)
 {
-    sim3_solver_lds_limit(bytes);
+    g_sim3_solver_lds.set(bytes);
     return OLF_OK;
 }
 
 int olf_debug_pnp_solver_lds_limit(int bytes)
 {
-    pnp_solver_lds_limit(bytes);
+    g_pnp_solver_lds.set(bytes);
     return OLF_OK;
 }
 
 int olf_debug_pose_points_lds_limit(int bytes)
 {
-    pose_points_lds_limit(bytes);
+    g_pose_points_lds.set(bytes);
     return OLF_OK;
 }
 
 int olf_debug_optimize_sim3_lds_limit(int bytes)
 {
-    optimize_sim3_lds_limit(bytes);
+    g_optimize_sim3_lds.set(bytes);
     return OLF_OK;
 }
 

@@ -71,7 +71,8 @@ int ctx_check_status(olf_ctx* c);                      // reads the device's cap
 // line outputs of a frame call whose line path is still running (olf_ctx_set_deferred_join): when one of the pointers lies in them, stream s waits for it first
 int ctx_join_line_outputs(olf_ctx* c, hipStream_t s, const void* p0, const void* p1, const void* p2, const void* p3);
 int ctx_level_scales(const olf_ctx* c, float* sf);     // mvScaleFactors into sf[0 .. OLF_MAX_LEVELS), 1.0 above the context's levels; returns the level count
-int ctx_level_thresholds(olf_ctx* c, float* thr);      // the table of olf_predict_scale_thresholds for the context's levels, built once
+int ctx_level_inv_sigma2(const olf_ctx* c, float* inv_sigma2);      // mvInvLevelSigma2 = 1.0f / (sf * sf), both in float, into [0 .. OLF_MAX_LEVELS); the level count
+int ctx_level_thresholds(olf_ctx* c, float* thr);     // the table of olf_predict_scale_thresholds for the context's levels, built once
 
 // The bits of the context's status word (ctx_status) that the batched matchers set, as every entry means them; include/orbline.h says per entry what was
 // left out.  What a bit means is its row of kStatusText, which is also what check_status (api.cpp) tells the caller about a set bit.

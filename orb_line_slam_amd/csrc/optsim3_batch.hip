@@ -1,8 +1,8 @@
 // optsim3_batch.hip -- olf_optimize_sim3_pairs_dev: int Optimizer::OptimizeSim3 (src/Optimizer.cc:2013-2208) for a list of key-frame pairs.
 //
 // One launch; one workgroup of 256 lanes carries a pair through both optimisations and both checks (grid-strided over the pairs, at most OS_MAX_GRID
-// workgroups), no grid-wide synchronisation.  The driver, the Levenberg loop, the 7 x 7 LDLT, the Sim3 algebra and every edge term are optsim3_terms.hpp /
-// posepoints_terms.hpp, the text optsim3_host.cpp runs too.  Every lane runs the driver on the same values, so all lanes take the same branches and the
+// workgroups), no grid-wide synchronisation.  The driver, the Sim3 algebra and every edge term are optsim3_terms.hpp, the Levenberg loop and the 7 x 7 LDLT
+// g2o_levenberg.hpp, the text optsim3_host.cpp runs too.  Every lane runs the driver on the same values, so all lanes take the same branches and the
 // dense pieces need no broadcast.  The workgroup cooperates in two places.  The sums (wg_sums.hpp): feature i belongs to lane i % 256, which adds e12_i
 // then e21_i in ascending i -- activeRobustChi2's one sum, buildSystem's 28 + 7 -- then the butterfly over the wave and the four waves in wave order; no
 // floating-point atomics, a pair's outputs depend on nothing but its own inputs.  And the numeric Jacobian's 14 perturbed estimates with their 14
@@ -10,11 +10,11 @@
 // them; the barrier inside the sum that ends the linearisation stands between these reads and the next linearisation's writes.
 // State: per feature of the capacity both edges' current _error (4 doubles: what the stale-error quirk lives in), P1c and P2c (6 floats: they are floats
 // widened), both invSigma2 (2 floats), the kf2 feature (the row itself is written) and one byte: 69 bytes, one slab per workgroup, in LDS when it fits and
-// otherwise in the batch scratch slot; the code is the same.  Every slab element is read and written by its owning lane only.
+// otherwise in the batch scratch slot; the code is the same (wg_state.hpp).  Every slab element is read and written by its owning lane only.
 #include <algorithm>
 #include <math.h>
 #include "optsim3_terms.hpp"
-#include "staging.hpp"
+#include "wg_state.hpp"
 #include "wg_sums.hpp"
 #include "../../include/orbline.h"
 
@@ -22,8 +22,7 @@ namespace olf {
 
 constexpr int OS_THREADS = 256, OS_MAX_GRID = 1024;
 constexpr int OS_LDS_DEFAULT = 60 * 1024;                            // the slab beside the kernel's static LDS, within the 64 KB a launch gets unasked
-static int g_os_lds_limit = OS_LDS_DEFAULT;
-void optimize_sim3_lds_limit(int bytes) { g_os_lds_limit = bytes > 0 ? std::min(bytes, OS_LDS_DEFAULT) : OS_LDS_DEFAULT; }
+LdsLimit g_optimize_sim3_lds(OS_LDS_DEFAULT);
 
 struct OptSim3Args {
     olf_track_batch in;
@@ -34,24 +33,21 @@ struct OptSim3Args {
     int n_pairs, n_frames, cap, nlevels, use_lds, fix_scale;
     double th2, delta;
     float inv_sigma2[OLF_MAX_LEVELS];
-    unsigned char* slabs;
+    unsigned char* slabs;                           // [gridDim.x][slab_bytes] in scratch, or NULL: LDS
     size_t slab_bytes;
 };
 
-__host__ __device__ inline size_t os_align(size_t v) { return (v + 15) & ~(size_t)15; }
 struct OsSlab {
     size_t err, P, w, i2, f, total;
-    __host__ __device__ explicit OsSlab(int cap)
+    __host__ __device__ constexpr explicit OsSlab(int cap) : err(0), P(0), w(0), i2(0), f(0), total(0)
     {
-        size_t o = 0;
-        err = o; o = os_align(o + 32 * (size_t)cap);
-        P = o; o = os_align(o + 24 * (size_t)cap);
-        w = o; o = os_align(o + 8 * (size_t)cap);
-        i2 = o; o = os_align(o + 4 * (size_t)cap);
-        f = o; o = os_align(o + (size_t)cap);
-        total = o;
+        Regions r;
+        err = r.cut(32 * (size_t)cap); P = r.cut(24 * (size_t)cap); w = r.cut(8 * (size_t)cap); i2 = r.cut(4 * (size_t)cap); f = r.cut((size_t)cap);
+        total = r.total;
     }
 };
+static_assert(OsSlab(2000).P == 64000 && OsSlab(2000).w == 112000 && OsSlab(2000).i2 == 128000 && OsSlab(2000).f == 136000 && OsSlab(2000).total == 138000 &&
+              OsSlab(1001).P == 32032 && OsSlab(1001).total == 69104, "the slab's offsets");
 
 using namespace optsim3;
 
@@ -122,14 +118,13 @@ struct OsDevOps {
     }
     __device__ int check(double th2)
     {
-        double none[1];
         int bad = 0;
         for (int i = tid; i < n; i += OS_THREADS) if (f[i] == C_HELD) {
             const double a = edge_chi2(err + 4 * i, (double)w[2 * i]), b = edge_chi2(err + 4 * i + 2, (double)w[2 * i + 1]);
             chi2[2 * i] = (float)a; chi2[2 * i + 1] = (float)b;
             if (a > th2 || b > th2) { f[i] = C_HELD | C_OUT; matches[i] = -1; ++bad; }
         }
-        wg.reduce(none, 0, &bad);
+        bad = wg.count(bad);
         active -= bad;
         return bad;
     }
@@ -144,7 +139,7 @@ __global__ __launch_bounds__(OS_THREADS) void k_optimize_sim3_pairs(OptSim3Args 
     const int tid = threadIdx.x;
     const olf_track_batch& in = A.in;
     const OsSlab lay(A.cap);
-    unsigned char* slab = A.use_lds ? os_dyn : A.slabs + (size_t)blockIdx.x * A.slab_bytes;
+    unsigned char* slab = wg_state_ptr(A.use_lds != 0, os_dyn, A.slabs, A.slab_bytes);
     const size_t cap = (size_t)A.cap;
 
     OsDevOps ops;
@@ -198,9 +193,8 @@ __global__ __launch_bounds__(OS_THREADS) void k_optimize_sim3_pairs(OptSim3Args 
             }
             ops.f[i] = f;
         }
-        double none[1];
-        ops.wg.reduce(none, 0, &bad_octave);
-        ops.wg.reduce(none, 0, &ncorr);
+        bad_octave = ops.wg.count(bad_octave);
+        ncorr = ops.wg.count(ncorr);
         ops.ncorr = ncorr; ops.active = ncorr;
 
         Sim3 S12;
@@ -211,7 +205,7 @@ __global__ __launch_bounds__(OS_THREADS) void k_optimize_sim3_pairs(OptSim3Args 
         if (tid == 0) {
             double R[9];
             float Scw[16];
-            pose::quat_to_mat3(res.S12.q, R);
+            quat_to_mat3(res.S12.q, R);
             sim3_scw(res.S12, T2, Scw);
             double* So = A.io.S12_out + 8 * (size_t)p;
             for (int k = 0; k < 4; ++k) So[k] = res.S12.q[k];
@@ -249,19 +243,11 @@ extern "C" int olf_optimize_sim3_pairs_dev(olf_ctx* c, const olf_track_batch* in
     A.th2 = (double)th2;
     A.delta = (double)sqrtf(th2);                                    // const float deltaHuber = sqrt(th2), :2062
     A.cap = olf_orb_capacity(c);
-    float sf[OLF_MAX_LEVELS];
-    A.nlevels = ctx_level_scales(c, sf);
-    for (int l = 0; l < OLF_MAX_LEVELS; ++l) { const float sigma2 = sf[l] * sf[l]; A.inv_sigma2[l] = 1.0f / sigma2; }      // mvInvLevelSigma2, src/ORBextractor.cc:434-436
+    A.nlevels = ctx_level_inv_sigma2(c, A.inv_sigma2);
     const OsSlab lay(A.cap);
     const int grid = std::min(n_pairs, OS_MAX_GRID);
     A.slab_bytes = lay.total;
-    A.use_lds = lay.total <= (size_t)g_os_lds_limit;
-    A.slabs = nullptr;
-    if (!A.use_lds) {
-        Carve k;
-        k.add(&A.slabs, lay.total * (size_t)grid);
-        OLF_TRY(k.bind(c, SCRATCH_BATCH));
-    }
+    OLF_TRY(wg_state_place(c, g_optimize_sim3_lds, lay.total, grid, &A.slabs, &A.use_lds));
     hipLaunchKernelGGL(k_optimize_sim3_pairs, dim3(grid), dim3(OS_THREADS), A.use_lds ? lay.total : 0, ctx_stream(c, stream), A, ctx_status(c));
     OLF_HIP_CHECK(hipGetLastError());
     return OLF_OK;

@@ -1,7 +1,7 @@
 // optsim3_host.cpp -- olf_optimize_sim3: int Optimizer::OptimizeSim3 (src/Optimizer.cc:2013-2208) for one key-frame pair on the host.  Plain C++ doubles,
 // every sum in the order of the reference's _activeEdges (e12_i, e21_i for ascending i), no context and no device: the definition the kernel of
 // optsim3_batch.hip is read against.  The Sim3 algebra, the edges' terms, the numeric Jacobian, the Levenberg loop and the driver are optsim3_terms.hpp /
-// posepoints_terms.hpp, shared with the kernel; this file owns the graph construction (:2066-2145) and the loops over a pair's correspondences.
+// g2o_levenberg.hpp, shared with the kernel; this file owns the graph construction (:2066-2145) and the loops over a pair's correspondences.
 #include <math.h>
 #include <string>
 #include <vector>
@@ -109,7 +109,7 @@ extern "C" int olf_optimize_sim3(const olf_track_batch* in, int capacity, int n_
     Result r;
     run_pair(ops, S12, fix_scale != 0, (double)th2, &r);
     double R[9];
-    pose::quat_to_mat3(r.S12.q, R);
+    quat_to_mat3(r.S12.q, R);
     for (int k = 0; k < 4; ++k) io->S12_out[k] = r.S12.q[k];
     for (int k = 0; k < 3; ++k) { io->S12_out[4 + k] = r.S12.t[k]; io->t12_out[k] = (float)r.S12.t[k]; }
     io->S12_out[7] = r.S12.s;

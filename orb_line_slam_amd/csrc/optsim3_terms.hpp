@@ -2,7 +2,7 @@
 // (optsim3_host.cpp) and the batched kernel (optsim3_batch.hip): one free VertexSim3Expmap, per correspondence one EdgeSim3ProjectXYZ (e12) and one
 // EdgeInverseSim3ProjectXYZ (e21) against fixed points, Huber kernels, OptimizationAlgorithmLevenberg over LinearSolverDense -- in plain C++ doubles, no
 // Eigen, built with -ffp-contract=off on both sides.  The Levenberg loop (lm_optimize<V, Ops>), Eigen's LDLT (ldlt_solve<7>), the Huber kernel and the
-// quaternion pieces are posepoints_terms.hpp / pose_terms.hpp; what is stated here is what is specific to this graph.
+// row status bits are g2o_levenberg.hpp, the quaternion and 3 x 3 pieces dense_math.hpp; what is stated here is what is specific to this graph.
 //
 // What is restated (Thirdparty/g2o/g2o/...):
 //   types/sim3.h                          the Vector7d constructor with its four branches, map, inverse, operator* (no normalisation anywhere)
@@ -15,26 +15,18 @@
 // by its linearisation (g2o restores it).  -omega * _error is (-(w e)), exactly; the sums carry -b, whose terms are the exact negatives of b's.
 // information * _error with information = Identity * invSigma2 is w e per component (the zero off-diagonal adds nothing).
 //
-// Defined here, not by the reference, as posepoints_terms.hpp does: a depth of exactly 0 at any evaluation, the perturbed ones included (ST_DEPTH), and an H,
+// Defined here, not by the reference, with g2o_levenberg.hpp: a depth of exactly 0 at any evaluation, the perturbed ones included (ST_DEPTH), and an H,
 // b, step or estimate that is not finite (ST_NOT_FINITE) stop the pair: S12_out = the input, the matches as they stood, n_inliers = 0.  An empty graph:
 // optimize() returns at once, nothing is bad, 0 - 0 < 10 returns 0.
 #pragma once
-#include "posepoints_terms.hpp"
+#include "dense_math.hpp"
+#include "g2o_levenberg.hpp"
 
 namespace olf {
 namespace optsim3 {
 
-using pose::finite_d;
-using posepoints::cross3;
-using posepoints::huber;
-using posepoints::ldlt_solve;
-using posepoints::lm_optimize;
-using posepoints::quat_mul;
-using posepoints::quat_rotate;
-using posepoints::LM_STOP;
-using posepoints::ST_DEPTH;
-using posepoints::ST_NOT_FINITE;
-using posepoints::ST_OCTAVE;
+using namespace dense;
+using namespace levenberg;
 
 enum { C_HELD = 1, C_OUT = 2 };                                     // a correspondence's byte: both edges are in the graph; both were removed
 enum { N_H = 28, N_SUMS = 35, N_PERT = 28 };                        // H's lower triangle, + 7 of -b; 14 perturbed estimates and their 14 inverses
@@ -47,7 +39,7 @@ PT_HD void sim3_from_floats(float s, const float* R, const float* t, Sim3* o)
 {
     double M[9];
     for (int i = 0; i < 9; ++i) M[i] = (double)R[i];
-    pose::quat_of_rotation(M, 3, o->q);
+    quat_of_rotation(M, 3, o->q);
     for (int i = 0; i < 3; ++i) o->t[i] = (double)t[i];
     o->s = (double)s;
 }
@@ -67,9 +59,9 @@ PT_HD void sim3_exp(const double* u, Sim3* o)
     const double om[3] = {u[0], u[1], u[2]}, up[3] = {u[3], u[4], u[5]}, sigma = u[6];
     const double theta = sqrt((om[0] * om[0] + om[1] * om[1]) + om[2] * om[2]);
     double Om[9], O2[9], R[9], W[9], A, B, C;
-    pose::skew3(om, Om);
+    skew3(om, Om);
     const double s = exp(sigma);
-    pose::mat3_mul(Om, Om, O2);
+    mat3_mul(Om, Om, O2);
     const double eps = 0.00001;
     const bool small = theta < eps;
     if (fabs(sigma) < eps) {
@@ -99,9 +91,9 @@ PT_HD void sim3_exp(const double* u, Sim3* o)
         const double ra = sin(theta) / theta, rb = (1.0 - cos(theta)) / (theta * theta);
         for (int i = 0; i < 9; ++i) R[i] = (((i % 4 == 0) ? 1.0 : 0.0) + ra * Om[i]) + rb * O2[i];
     }
-    pose::quat_of_rotation(R, 3, o->q);
+    quat_of_rotation(R, 3, o->q);
     for (int i = 0; i < 9; ++i) W[i] = (A * Om[i] + B * O2[i]) + C * ((i % 4 == 0) ? 1.0 : 0.0);
-    pose::mat3_vec(W, up, o->t);
+    mat3_vec(W, up, o->t);
     o->s = s;
 }
 // Sim3::map, :144-146: s * (r * xyz) + t
@@ -172,11 +164,11 @@ PT_HD void sim3_scw(const Sim3& S12, const float* T2w, float* Scw)
     double M[16], R[9];
     for (int i = 0; i < 16; ++i) M[i] = (double)T2w[i];
     Sim3 w, r;
-    pose::quat_of_rotation(M, 4, w.q);
+    quat_of_rotation(M, 4, w.q);
     w.t[0] = M[3]; w.t[1] = M[7]; w.t[2] = M[11];
     w.s = 1.0;
     sim3_mul(S12, w, &r);
-    pose::quat_to_mat3(r.q, R);
+    quat_to_mat3(r.q, R);
     for (int i = 0; i < 16; ++i) Scw[i] = (i == 15) ? 1.f : 0.f;
     for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) Scw[i * 4 + j] = (float)(r.s * R[i * 3 + j]); Scw[i * 4 + 3] = (float)r.t[i]; }
 }

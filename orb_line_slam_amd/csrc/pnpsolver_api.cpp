@@ -2,13 +2,9 @@
 // state and the outputs in one carve -- the outputs are uploaded first, so what the device leaves untouched (a refused pair, a row's tail, counts of
 // iterations not evaluated, the pose of a call that returns none) comes back as it went in -- and runs the same kernel.  (The form that computes on the
 // host is pnpsolver_host.cpp.)
+#include "solver_args.hpp"
 #include "staging.hpp"
 #include "../../include/orbline.h"
-
-namespace olf {
-bool pnp_ransac_ok(const olf_pnp_ransac* R);       // pnpsolver_host.cpp
-bool pnp_io_ok(const olf_pnp_solver_io* io);
-}
 
 using namespace olf;
 

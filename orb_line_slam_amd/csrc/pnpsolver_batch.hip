@@ -18,25 +18,21 @@
 //        are dropped, so nothing depends on the round size.
 //     Bound by instruction issue and LDS latency of the dependent Jacobi chain: 32 fits per round on 32 of 256 lanes.
 //   k_pnp_apply    one workgroup per pair, a lane per feature.
-#include <mutex>
-#include <vector>
 #include "pnpsolver_terms.hpp"
 #include "batch_frames.hpp"
+#include "host_table_cache.hpp"
 #include "map_kernels.hpp"
-#include "staging.hpp"
+#include "solver_args.hpp"
+#include "wg_state.hpp"
 #include "../../include/orbline.h"
 
 namespace olf {
-
-bool pnp_ransac_ok(const olf_pnp_ransac* R);       // pnpsolver_host.cpp
-bool pnp_io_ok(const olf_pnp_solver_io* io);
 
 constexpr int PNP_FITS = 32, PNP_SLOTS = PNP_FITS + 1, PNP_PER_WAVE = PNP_FITS / PNP_WAVES, PNP_MAX_GRID = 1024;
 constexpr int PNP_WS_BYTES = PNP_WS * PNP_SLOTS * (int)sizeof(double);      // 111408
 constexpr int PNP_LDS_DEFAULT = 46 * 1024;          // what the planes may take beside the workspaces and 3 KB of static LDS, of 160 KiB
 static_assert(PNP_WS_BYTES + PNP_LDS_DEFAULT + 4096 <= 160 * 1024, "a workgroup's LDS");
-static int g_pnp_lds_limit = PNP_LDS_DEFAULT;
-void pnp_solver_lds_limit(int bytes) { g_pnp_lds_limit = bytes > 0 ? std::min(bytes, PNP_LDS_DEFAULT) : PNP_LDS_DEFAULT; }
+LdsLimit g_pnp_solver_lds(PNP_LDS_DEFAULT);
 
 struct PnpSolverArgs {
     const olf_keypoint* kps;
@@ -103,7 +99,7 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_solver(PnpSolverArgs A, int
     __shared__ double s_red[PNP_WAVES][78];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, cap = A.cap;
     double* ws = pnp_dyn;
-    float* st = A.state ? A.state + (size_t)blockIdx.x * PNP_WORDS * cap : reinterpret_cast<float*>(pnp_dyn + PNP_WS * PNP_SLOTS);
+    float* st = wg_state_ptr(!A.state, reinterpret_cast<float*>(pnp_dyn + PNP_WS * PNP_SLOTS), A.state, (size_t)PNP_WORDS * cap);
     int* st_feat = reinterpret_cast<int*>(st + (size_t)6 * cap);
     int* st_list = reinterpret_cast<int*>(st + (size_t)7 * cap);
     const PnpPlanes P = {st, cap};
@@ -161,7 +157,7 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_solver(PnpSolverArgs A, int
                     const uint32_t* r = A.draws + 4 * ((size_t)p * A.max_iterations + j % A.max_iterations);      // C.26
                     const uint32_t rr[4] = {r[0], r[1], r[2], r[3]};
                     int idx[4];
-                    pnp_sample(N, rr, idx);
+                    ransac_sample<4>(N, rr, idx);
                     PnpSeqEnv e = {ws + slot, PNP_SLOTS, P, idx[0], idx[1], idx[2], idx[3]};
                     pnp_compute_pose(e, A.cam);
                 }
@@ -286,58 +282,8 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_apply(int cap, int n_frames
     }
 }
 
-// The parameters of every N in [0, cap] for one parameter set, built on the host (libm) and uploaded on the call's stream from pinned memory: the scheme
-// of sim3solver_batch.hip (a table is never changed while its last upload can be pending; at most PNP_TABLES sets are kept).
-constexpr int PNP_TABLES = 8;
-struct PnpTable { double p; int m, maxit, cap; float eps; int room; int* host; hipEvent_t last; unsigned long long used; };
-static std::mutex g_pnp_mutex;
-static std::vector<PnpTable> g_pnp_tables;
-static unsigned long long g_pnp_clock = 0;
-static int pnp_upload_table(const olf_pnp_ransac* R, int cap, int* d_tab, hipStream_t s)
-{
-    std::lock_guard<std::mutex> lock(g_pnp_mutex);
-    const size_t words = 2 * ((size_t)cap + 1);
-    PnpTable* t = nullptr;
-    for (PnpTable& e : g_pnp_tables) if (e.p == R->probability && e.m == R->min_inliers && e.maxit == R->max_iterations && e.cap == cap && e.eps == R->epsilon) t = &e;
-    if (!t) {
-        if ((int)g_pnp_tables.size() < PNP_TABLES) {
-            PnpTable e = {0, 0, 0, 0, 0.f, 0, nullptr, nullptr, 0};
-            OLF_HIP_CHECK(hipEventCreateWithFlags(&e.last, hipEventDisableTiming));
-            g_pnp_tables.push_back(e);
-            t = &g_pnp_tables.back();
-        } else {
-            t = &g_pnp_tables[0];
-            for (PnpTable& e : g_pnp_tables) if (e.used < t->used) t = &e;
-            OLF_HIP_CHECK(hipEventSynchronize(t->last));
-        }
-        if ((size_t)t->room < words) {
-            if (t->host) OLF_HIP_CHECK(hipHostFree(t->host));
-            t->host = nullptr; t->room = 0;
-            OLF_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&t->host), words * sizeof(int), hipHostMallocDefault));
-            t->room = (int)words;
-        }
-        t->p = R->probability; t->m = R->min_inliers; t->maxit = R->max_iterations; t->cap = cap; t->eps = R->epsilon;
-        for (int N = 0; N <= cap; ++N) pnp_parameters(N, R->probability, R->min_inliers, R->max_iterations, R->min_set, R->epsilon, t->host + 2 * N, t->host + 2 * N + 1);
-    }
-    t->used = ++g_pnp_clock;
-    OLF_HIP_CHECK(hipMemcpyAsync(d_tab, t->host, words * sizeof(int), hipMemcpyHostToDevice, s));
-    OLF_HIP_CHECK(hipEventRecord(t->last, s));
-    return OLF_OK;
-}
-
-// dynamic LDS above 64 KB has to be allowed once per device
-static int pnp_allow_large_lds()
-{
-    static std::mutex mu;
-    static bool done[64] = {false};
-    int dev = 0;
-    OLF_HIP_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev >= 0 && dev < 64 && done[dev]) return OLF_OK;
-    OLF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pnp_solver), hipFuncAttributeMaxDynamicSharedMemorySize, PNP_WS_BYTES + PNP_LDS_DEFAULT));
-    if (dev >= 0 && dev < 64) done[dev] = true;
-    return OLF_OK;
-}
+// the effective min_inliers and the cap of every N in [0, cap] for one parameter set (host_table_cache.hpp)
+static HostTableCache g_pnp_tables(2);
 
 }  // namespace olf
 
@@ -358,19 +304,18 @@ int olf_pnp_solver_pairs_dev(olf_ctx* c, const olf_track_batch* in, int n_frames
     PnpSolverArgs A;
     A.cap = olf_orb_capacity(c);
     const size_t state_bytes = (size_t)PNP_WORDS * A.cap * sizeof(float);
-    const bool lds = state_bytes <= (size_t)g_pnp_lds_limit;
     const int grid = std::min(n_pairs, PNP_MAX_GRID);
     int* d_tab;
-    float* d_state = nullptr;
     Carve k;
     k.add(&d_tab, 2 * ((size_t)A.cap + 1));
-    if (!lds) k.add(&d_state, (size_t)grid * PNP_WORDS * A.cap);
+    const bool lds = wg_state_in_lds(k, g_pnp_solver_lds, state_bytes, grid, &A.state);
     OLF_TRY(k.bind(c, SCRATCH_BATCH));
     hipStream_t s = ctx_stream(c, stream);
-    OLF_TRY(pnp_upload_table(ransac, A.cap, d_tab, s));
-    OLF_TRY(pnp_allow_large_lds());
+    OLF_TRY(g_pnp_tables.upload({ransac->probability, ransac->min_inliers, ransac->max_iterations, A.cap, ransac->epsilon}, [&](int N, int* row) {
+        pnp_parameters(N, ransac->probability, ransac->min_inliers, ransac->max_iterations, ransac->min_set, ransac->epsilon, row, row + 1); }, d_tab, s));
+    OLF_TRY(allow_large_lds(reinterpret_cast<const void*>(&k_pnp_solver), PNP_WS_BYTES + PNP_LDS_DEFAULT));
     A.kps = in->kps; A.counts = in->counts; A.pairs = d_pairs; A.matches = d_matches; A.table = d_tab; A.world = in->mp_world;
-    A.valid = in->mp_valid; A.bad = d_mp_bad; A.draws = d_draws; A.io = *io; A.state = d_state;
+    A.valid = in->mp_valid; A.bad = d_mp_bad; A.draws = d_draws; A.io = *io;
     A.img_stride = in->img_stride; A.n_frames = n_frames; A.n_pairs = n_pairs;
     A.max_iterations = ransac->max_iterations; A.n_iterations = ransac->n_iterations; A.th2 = ransac->th2;
     A.cam[0] = (double)in->fx; A.cam[1] = (double)in->fy; A.cam[2] = (double)in->cx; A.cam[3] = (double)in->cy;

@@ -4,14 +4,11 @@
 // tests hold the two against each other and both against a literal restatement.
 #include <vector>
 #include "pnpsolver_terms.hpp"
+#include "solver_args.hpp"
 #include "olf_internal.hpp"
 #include "../../include/orbline.h"
 
 using namespace olf;
-
-namespace {
-inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-}
 
 namespace olf {
 bool pnp_ransac_ok(const olf_pnp_ransac* R)
@@ -82,7 +79,7 @@ extern "C" int olf_pnp_solver(const olf_track_batch* in, int capacity, int n_fra
         ++cur;
         const int j = it++, slot = j % R->max_iterations;            // C.26
         int idx[4];
-        pnp_sample(N, draws + 4 * (size_t)slot, idx);
+        ransac_sample<4>(N, draws + 4 * (size_t)slot, idx);
         PnpSeqEnv e = {ws.data(), 1, P, idx[0], idx[1], idx[2], idx[3]};
         pnp_compute_pose(e, cam);
         int n = 0;

@@ -1,5 +1,5 @@
 // pnpsolver_terms.hpp -- the arithmetic of PnPsolver (src/PnPsolver.cc) that the host form (pnpsolver_host.cpp) and the kernel (pnpsolver_batch.hip) both
-// run: the parameters of SetRansacParameters as a function of N (:121-157), the sample of one iteration from its four draws (:188-201), EPnP's
+// run: the parameters of SetRansacParameters as a function of N (:121-157), EPnP's
 // compute_pose with everything it calls (:375-950) and the inlier test of one correspondence (:308-339).  One text for both sides; every file that includes
 // it is built with -ffp-contract=off (C.4) and the rounded operations are spelled through device_math.hpp.  All of compute_pose is double, as written.
 //
@@ -29,8 +29,10 @@
 //   C.25  qr_solve's `eta == 0` return (:887-891) leaves x as it is, which in the reference's first Gauss-Newton round is uninitialised: x starts at 0.
 //   C.26  the loop of iterate (:182) goes on while mnIterations < cap OR nCurrentIterations < n_iterations, so iterations beyond max_iterations exist:
 //         iteration j reads draws[j % max_iterations] and writes counts[j % max_iterations].
+// The sample of an iteration is ransac_sample<4> and a row value's test s3_is_match, both of ransac_terms.hpp (shared with sim3solver_terms.hpp, of which
+// nothing else is needed here: that header is not included).
 #pragma once
-#include "sim3solver_terms.hpp"
+#include "ransac_terms.hpp"
 
 // OLF_HD on a member function (device_math.hpp's host form is `static inline`, which a member cannot be)
 #if defined(__HIPCC__)
@@ -78,19 +80,6 @@ inline void pnp_parameters(int N, double probability, int min_inliers, int max_i
 
 // mvMaxError[i] = mvSigma2[i] * th2 with mvSigma2 = mvLevelSigma2[octave] = sf * sf, all float (:90, :156)
 OLF_HD float pnp_max_error(float sf, float th2) { return f_mul(f_mul(sf, sf), th2); }
-
-// the four sample indices of one iteration (:188-201) under C.20: s3_sample with three remembered substitutions.  N >= 4.
-OLF_HD void pnp_sample(int N, const uint32_t* r, int* idx)
-{
-    const int p0 = s3_pos(r[0], N), p1 = s3_pos(r[1], N - 1), p2 = s3_pos(r[2], N - 2), p3 = s3_pos(r[3], N - 3);
-#define OLF_PNP_A1(x) ((x) == p0 ? N - 1 : (x))
-#define OLF_PNP_A2(x) ((x) == p1 ? OLF_PNP_A1(N - 2) : OLF_PNP_A1(x))
-#define OLF_PNP_A3(x) ((x) == p2 ? OLF_PNP_A2(N - 3) : OLF_PNP_A2(x))
-    idx[0] = p0; idx[1] = OLF_PNP_A1(p1); idx[2] = OLF_PNP_A2(p2); idx[3] = OLF_PNP_A3(p3);
-#undef OLF_PNP_A1
-#undef OLF_PNP_A2
-#undef OLF_PNP_A3
-}
 
 // ---- C.23: the singular value decomposition of the N x M matrix At(i, k) = e.at(oA + i * M + k) (the transposed operand), in place.  Afterwards row i
 // is the i-th left singular vector of the operand, e.at(oW + i) its singular value, row i of V (e.at(oV + i * N + k), when WANT_V) the right one.

@@ -10,11 +10,11 @@
 //   select          element n / 2 of the ascending residuals, exactly: a radix select over the ordered 64-bit patterns, eight bits a round (integer
 //                   LDS atomics into 256 bins, whose counts do not depend on the order of arrival).
 // State: a frame's previous-frame points (3 doubles) and lines (6), the held / outlier flags, the octaves and two 64-bit keys per feature for the
-// selections are one slab, in LDS when it fits (it does at the default capacities) and otherwise in the batch scratch slot; the code is the same.
+// selections are one slab, in LDS when it fits (it does at the default capacities) and otherwise in the batch scratch slot; the code is the same
+// (wg_state.hpp).
 #include <algorithm>
-#include <mutex>
 #include "pose_terms.hpp"
-#include "staging.hpp"
+#include "wg_state.hpp"
 #include "wg_sums.hpp"
 #include "../../include/orbline.h"
 
@@ -30,12 +30,13 @@ struct PoseArgs {
     olf_pose_params p;
     int n_frames, cap, lcap, nlevels, use_lds;
     float inv_sigma2[OLF_MAX_LEVELS];
-    unsigned char* slabs;
+    unsigned char* slabs;                           // [n_frames][slab_bytes] in scratch, or NULL: LDS
     size_t slab_bytes;
 };
 
-__host__ __device__ inline size_t po_align(size_t v) { return (v + 15) & ~(size_t)15; }
-// offsets of the slab's regions
+// offsets of the slab's regions.  Its own text, not Regions of wg_state.hpp, and the integer sums below are reduce(none, 0, &n), not WgSums::count: with
+// either shared form k_pose_frames, which is at its register limit, compiles to other code and falls outside the timing rule.
+__host__ __device__ inline size_t po_align(size_t v) { return Regions::round16(v); }
 struct SlabLayout {
     size_t P, L, key, key2, pf, poct, lf, loct, total;
     __host__ __device__ SlabLayout(int cap, int lcap)
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_frames(PoseArgs A, int* __r
     const int j = blockIdx.x, tid = threadIdx.x;
     const olf_pose_batch& in = A.in;
     const SlabLayout lay(A.cap, A.lcap);
-    unsigned char* slab = A.use_lds ? po_dyn : A.slabs + (size_t)j * A.slab_bytes;
+    unsigned char* slab = wg_state_ptr(A.use_lds != 0, po_dyn, A.slabs, A.slab_bytes);
 
     DevOps ops;
     pose::Cfg& c = ops.c;
@@ -357,20 +358,6 @@ __global__ __launch_bounds__(PO_THREADS) void k_discard_outliers(DiscardArgs A, 
     if (tid < 2) A.n_matches[2 * j + tid] = s_cnt[tid];
 }
 
-// dynamic LDS above 64 KB has to be allowed once per device: remembered here, so the entry makes no attribute call after the first on a device
-static int allow_large_lds()
-{
-    static std::mutex mu;
-    static bool done[64] = {false};
-    int dev = 0;
-    OLF_HIP_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev >= 0 && dev < 64 && done[dev]) return OLF_OK;
-    OLF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pose_frames), hipFuncAttributeMaxDynamicSharedMemorySize, PO_LDS_BUDGET));
-    if (dev >= 0 && dev < 64) done[dev] = true;
-    return OLF_OK;
-}
-
 }  // namespace olf
 
 using namespace olf;
@@ -389,20 +376,12 @@ int olf_pose_optimization_with_line_batch_dev(olf_ctx* c, const olf_pose_batch* 
     PoseArgs A;
     A.in = *in; A.out = *o; A.p = *p; A.n_frames = n_frames;
     A.cap = olf_orb_capacity(c); A.lcap = olf_line_capacity(c);
-    float sf[OLF_MAX_LEVELS];
-    A.nlevels = ctx_level_scales(c, sf);
-    for (int l = 0; l < OLF_MAX_LEVELS; ++l) { const float sigma2 = sf[l] * sf[l]; A.inv_sigma2[l] = 1.0f / sigma2; }      // mvInvLevelSigma2, src/ORBextractor.cc:434-436
+    A.nlevels = ctx_level_inv_sigma2(c, A.inv_sigma2);
     const SlabLayout lay(A.cap, A.lcap);
     A.slab_bytes = lay.total;
-    A.use_lds = lay.total <= (size_t)PO_LDS_BUDGET;
-    A.slabs = nullptr;
-    if (A.use_lds) {
-        if (lay.total > 64 * 1024) OLF_TRY(allow_large_lds());       // (the launch asks for lay.total bytes: a small slab leaves room for more workgroups on a CU)
-    } else {
-        Carve k;
-        k.add(&A.slabs, lay.total * (size_t)n_frames);
-        OLF_TRY(k.bind(c, SCRATCH_BATCH));
-    }
+    OLF_TRY(wg_state_place(c, LdsLimit(PO_LDS_BUDGET), lay.total, n_frames, &A.slabs, &A.use_lds));
+    // (the launch asks for lay.total bytes: a small slab leaves room for more workgroups on a CU)
+    if (A.use_lds && lay.total > 64 * 1024) OLF_TRY(allow_large_lds(reinterpret_cast<const void*>(&k_pose_frames), PO_LDS_BUDGET));
     hipLaunchKernelGGL(k_pose_frames, dim3(n_frames), dim3(PO_THREADS), A.use_lds ? lay.total : 0, ctx_stream(c, stream), A, ctx_status(c));
     OLF_HIP_CHECK(hipGetLastError());
     return OLF_OK;

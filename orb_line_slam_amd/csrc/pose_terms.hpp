@@ -7,20 +7,15 @@
 //
 // Conventions where the reference's build decides: sqrt(mvInvLevelSigma2[octave]) is the C function on the widened float (C.6, conv_libm_float = 0);
 // vector / scalar divides every coefficient (Eigen 3.2+, conv_eigen_recip = 0); an Eigen product sums over k in ascending order.
+// The 4 x 4, 3 x 3 and quaternion pieces and the PT_HD marker are dense_math.hpp; what is here belongs to this optimiser alone.
 #pragma once
-#include <math.h>
-#include <stdint.h>
 #include <string.h>
-
-// Not OLF_HD (device_math.hpp), which forces inlining and made k_pose_frames longer and slower ("What the map-side kernels share").
-#if defined(__HIPCC__)
-#define PT_HD __host__ __device__ inline
-#else
-#define PT_HD inline
-#endif
+#include "dense_math.hpp"
 
 namespace olf {
 namespace pose {
+
+using namespace dense;
 
 enum { ST_NO_FEATURE = 1, ST_NOT_FINITE = 2, ST_OCTAVE = 4 };      // the frame's own status word
 enum { N_SUMS = 28 };                                              // 21 of H's upper triangle (row by row), 6 of g, 1 of e
@@ -38,10 +33,6 @@ struct Result {
     int good, status, iters[4];
 };
 
-PT_HD bool finite_d(double x) { return x - x == 0.0; }
-PT_HD double max_d(double a, double b) { return a < b ? b : a; }      // std::max(a, b)
-PT_HD double min_d(double a, double b) { return b < a ? b : a; }      // std::min(a, b)
-
 // the ordered 64-bit pattern of a residual (>= 0 or NaN): its order is the order of the values, every NaN is one pattern above the infinities
 PT_HD uint64_t key_of(double r)
 {
@@ -54,48 +45,7 @@ PT_HD double value_of(uint64_t k) { double r; __builtin_memcpy(&r, &k, 8); retur
 // residues[i] = fabsf(residues[i] - median), src/Auxiliar.cc:413: the deviation rounded to float
 PT_HD double mad_dev(double r, double median) { return (double)fabsf((float)(r - median)); }
 
-// ---- 4 x 4 and se(3), row-major ------------------------------------------------------------------------------------------------------------------------
-PT_HD void mat4_identity(double* T) { for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.0 : 0.0; }
-PT_HD void mat4_mul(const double* A, const double* B, double* C)
-{
-    double t[16];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            double s = A[i * 4] * B[j];
-            for (int k = 1; k < 4; ++k) s = s + A[i * 4 + k] * B[k * 4 + j];
-            t[i * 4 + j] = s;
-        }
-    for (int i = 0; i < 16; ++i) C[i] = t[i];
-}
-PT_HD bool mat4_finite(const double* T) { bool ok = true; for (int i = 0; i < 16; ++i) ok = ok && finite_d(T[i]); return ok; }
-// inverse_se3 (src/Auxiliar.cc:113-122) and Converter::toInvMatrix4d: R^T | -R^T t
-PT_HD void inverse_se3(const double* T, double* Ti)
-{
-    double o[16];
-    mat4_identity(o);
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) o[i * 4 + j] = T[j * 4 + i];
-        o[i * 4 + 3] = ((-T[0 * 4 + i]) * T[3] + (-T[1 * 4 + i]) * T[7]) + (-T[2 * 4 + i]) * T[11];
-    }
-    for (int i = 0; i < 16; ++i) Ti[i] = o[i];
-}
-PT_HD void skew3(const double* w, double* S)
-{
-    S[0] = 0.0; S[1] = -w[2]; S[2] = w[1];
-    S[3] = w[2]; S[4] = 0.0; S[5] = -w[0];
-    S[6] = -w[1]; S[7] = w[0]; S[8] = 0.0;
-}
-PT_HD void mat3_mul(const double* A, const double* B, double* C)
-{
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) C[i * 3 + j] = (A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j]) + A[i * 3 + 2] * B[6 + j];
-}
-PT_HD void mat3_vec(const double* A, const double* v, double* o)
-{
-    double t[3];
-    for (int i = 0; i < 3; ++i) t[i] = (A[i * 3] * v[0] + A[i * 3 + 1] * v[1]) + A[i * 3 + 2] * v[2];
-    o[0] = t[0]; o[1] = t[1]; o[2] = t[2];
-}
+// ---- se(3) ---------------------------------------------------------------------------------------------------------------------------------------------
 // expmap_se3, src/Auxiliar.cc:124-144: x = (t, w)
 PT_HD void expmap_se3(const double* x, double* T)
 {
@@ -121,53 +71,6 @@ PT_HD void expmap_se3(const double* x, double* T)
     }
     mat4_identity(T);
     for (int i = 0; i < 3; ++i) { T[i * 4] = R[i * 3]; T[i * 4 + 1] = R[i * 3 + 1]; T[i * 4 + 2] = R[i * 3 + 2]; T[i * 4 + 3] = t[i]; }
-}
-// g2o::SE3Quat(R, t)'s rotation (se3quat.h:58-60, :280-285): Eigen's Quaterniond(R) of the rotation block of the row-major 4 x 4 T, then
-// normalizeRotation(), i.e. w >= 0 and unit norm.  q = x, y, z, w.  Shared with posepoints_terms.hpp.
-PT_HD void quat_normalize_positive(double* q)
-{
-    if (q[3] < 0.0) for (int i = 0; i < 4; ++i) q[i] = q[i] * -1.0;
-    const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    for (int i = 0; i < 4; ++i) q[i] = q[i] / n;
-}
-// Eigen's Quaterniond(Matrix3d) of the 3 x 3 block at M (row-major, rows ld apart), NOT normalised (what g2o::Sim3 keeps; optsim3_terms.hpp)
-PT_HD void quat_of_rotation(const double* M, int ld, double* q)
-{
-    const int dg = ld + 1;
-    const double m00 = M[0], m11 = M[dg], m22 = M[2 * dg];
-    double t = (m00 + m11) + m22;
-    if (t > 0.0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (M[2 * ld + 1] - M[ld + 2]) * t; q[1] = (M[2] - M[2 * ld]) * t; q[2] = (M[ld] - M[1]) * t;
-    } else {
-        int i = 0;
-        if (m11 > m00) i = 1;
-        if (m22 > M[i * dg]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(((M[i * dg] - M[j * dg]) - M[k * dg]) + 1.0);
-        q[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (M[k * ld + j] - M[j * ld + k]) * t;
-        q[j] = (M[j * ld + i] + M[i * ld + j]) * t;
-        q[k] = (M[k * ld + i] + M[i * ld + k]) * t;
-    }
-}
-PT_HD void quat_from_mat4(const double* T, double* q)
-{
-    quat_of_rotation(T, 4, q);
-    quat_normalize_positive(q);
-}
-// Quaterniond::toRotationMatrix(), row-major 3 x 3
-PT_HD void quat_to_mat3(const double* q, double* R)
-{
-    const double tx = 2.0 * q[0], ty = 2.0 * q[1], tz = 2.0 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3], txx = tx * q[0], txy = ty * q[0], txz = tz * q[0], tyy = ty * q[1], tyz = tz * q[1],
-                 tzz = tz * q[2];
-    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
 }
 // logmap_se3 (src/Auxiliar.cc:146-152): g2o::SE3Quat(R, t).log() with the halves swapped, so x = (upsilon, omega).  The constructor goes through a
 // normalised quaternion with w >= 0 (se3quat.h:58-60, :280-285) and log() through its rotation matrix again (:178-215).

@@ -1,18 +1,18 @@
 // posepoints_batch.hip -- olf_pose_optimization_batch_dev: int Optimizer::PoseOptimization(Frame*) (src/Optimizer.cc:239-451) for a list of rows.
 //
 // One launch; one workgroup of 256 lanes carries a row through the four passes and the epilogue (grid-strided over the rows, at most PP_MAX_GRID
-// workgroups), no grid-wide synchronisation.  The driver, the Levenberg loop, the 6 x 6 LDLT and every edge term are posepoints_terms.hpp, the text
-// posepoints_host.cpp runs too.  Every lane runs the driver on the same values, so all lanes take the same branches and the dense pieces need no broadcast;
+// workgroups), no grid-wide synchronisation.  The driver and every edge term are posepoints_terms.hpp, the Levenberg loop and the 6 x 6 LDLT
+// g2o_levenberg.hpp, the text posepoints_host.cpp runs too.  Every lane runs the driver on the same values, so all lanes take the same branches and the dense pieces need no broadcast;
 // the workgroup cooperates inside DevOps only through the sums of wg_sums.hpp (shared with pose_batch.hip): feature i belongs to lane i % 256, which adds
 // its edges in ascending i -- activeRobustChi2's one sum, buildSystem's 21 + 6 -- then the butterfly over the wave and the four waves in wave order.  No
 // floating-point atomics; a row's outputs depend on nothing but its own inputs.
 // State: per feature of the capacity the edge's current _error (3 doubles: what the stale-error quirk of the reference lives in), invSigma2 (float, widened
 // at use as the reference widens it) and one byte (held, outlier, stereo): 29 bytes, one slab per workgroup, in LDS when it fits (58 KB at the default
-// capacity of 2000, so two rows share a CU) and otherwise in the batch scratch slot; the code is the same.  Xw and the observation are re-read from global
-// memory as floats and widened.  Every slab element is read and written by its owning lane only, so the slab needs no barrier of its own.
+// capacity of 2000, so two rows share a CU) and otherwise in the batch scratch slot; the code is the same (wg_state.hpp).  Xw and the observation are
+// re-read from global memory as floats and widened.  Every slab element is read and written by its owning lane only, so the slab needs no barrier of its own.
 #include <algorithm>
 #include "posepoints_terms.hpp"
-#include "staging.hpp"
+#include "wg_state.hpp"
 #include "wg_sums.hpp"
 #include "../../include/orbline.h"
 
@@ -20,30 +20,28 @@ namespace olf {
 
 constexpr int PP_THREADS = 256, PP_MAX_GRID = 1024, PP_SUMS = 27;
 constexpr int PP_LDS_DEFAULT = 60 * 1024;                            // the slab beside the kernel's static LDS, within the 64 KB a launch gets unasked
-static int g_pp_lds_limit = PP_LDS_DEFAULT;
-void pose_points_lds_limit(int bytes) { g_pp_lds_limit = bytes > 0 ? std::min(bytes, PP_LDS_DEFAULT) : PP_LDS_DEFAULT; }
+LdsLimit g_pose_points_lds(PP_LDS_DEFAULT);
 
 struct PosePointsArgs {
     olf_pose_points_batch in;
     olf_pose_points_outputs out;
     int n_rows, n_frames, cap, nlevels, use_lds;
     float inv_sigma2[OLF_MAX_LEVELS];
-    unsigned char* slabs;
+    unsigned char* slabs;                           // [gridDim.x][slab_bytes] in scratch, or NULL: LDS
     size_t slab_bytes;
 };
 
-__host__ __device__ inline size_t pp_align(size_t v) { return (v + 15) & ~(size_t)15; }
 struct PpSlab {
     size_t err, w, f, total;
-    __host__ __device__ explicit PpSlab(int cap)
+    __host__ __device__ constexpr explicit PpSlab(int cap) : err(0), w(0), f(0), total(0)
     {
-        size_t o = 0;
-        err = o; o = pp_align(o + 24 * (size_t)cap);
-        w = o; o = pp_align(o + 4 * (size_t)cap);
-        f = o; o = pp_align(o + (size_t)cap);
-        total = o;
+        Regions r;
+        err = r.cut(24 * (size_t)cap); w = r.cut(4 * (size_t)cap); f = r.cut((size_t)cap);
+        total = r.total;
     }
 };
+static_assert(PpSlab(2000).w == 48000 && PpSlab(2000).f == 56000 && PpSlab(2000).total == 58000 && PpSlab(1001).w == 24032 && PpSlab(1001).f == 28048 &&
+              PpSlab(1001).total == 29056, "the slab's offsets");
 
 using namespace posepoints;
 
@@ -98,7 +96,7 @@ struct PpDevOps {
     }
     __device__ bool classify(const Se3& est, int* n_bad)
     {
-        double X[3], obs[3], none[1];
+        double X[3], obs[3];
         int bad = 0;
         for (int i = tid; i < n; i += PP_THREADS) if ((f[i] & (E_HELD | E_OUT)) == (E_HELD | E_OUT)) {
             double e[3];
@@ -106,7 +104,7 @@ struct PpDevOps {
             if (!edge_error(c, est, X, obs, f[i] & E_STEREO, e)) { ++bad; continue; }
             err[3 * i] = e[0]; err[3 * i + 1] = e[1]; err[3 * i + 2] = e[2];
         }
-        wg.reduce(none, 0, &bad);
+        bad = wg.count(bad);
         if (bad) return false;                                      // (uniform) the flags stay as they stood
         for (int i = tid; i < n; i += PP_THREADS) if (f[i] & E_HELD) {
             const double e[3] = {err[3 * i], err[3 * i + 1], err[3 * i + 2]};
@@ -114,7 +112,7 @@ struct PpDevOps {
             chi2[i] = v;
             if (v > chi2_threshold(f[i] & E_STEREO)) { f[i] |= E_OUT; ++bad; } else f[i] &= ~E_OUT;
         }
-        wg.reduce(none, 0, &bad);
+        bad = wg.count(bad);
         *n_bad = bad;
         active = held - bad;
         return true;
@@ -129,7 +127,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pose_points_rows(PosePointsArgs 
     const int tid = threadIdx.x;
     const olf_pose_points_batch& in = A.in;
     const PpSlab lay(A.cap);
-    unsigned char* slab = A.use_lds ? pp_dyn : A.slabs + (size_t)blockIdx.x * A.slab_bytes;
+    unsigned char* slab = wg_state_ptr(A.use_lds != 0, pp_dyn, A.slabs, A.slab_bytes);
 
     PpDevOps ops;
     ops.c.fx = (double)in.fx; ops.c.fy = (double)in.fy; ops.c.cx = (double)in.cx; ops.c.cy = (double)in.cy; ops.c.bf = (double)in.bf;
@@ -171,9 +169,8 @@ __global__ __launch_bounds__(PP_THREADS) void k_pose_points_rows(PosePointsArgs 
             ops.f[i] = f; ops.w[i] = w;
             ops.chi2[i] = 0.f;
         }
-        double none[1];
-        ops.wg.reduce(none, 0, &bad_octave);
-        ops.wg.reduce(none, 0, &held);
+        bad_octave = ops.wg.count(bad_octave);
+        held = ops.wg.count(held);
         ops.held = held; ops.active = held;
 
         Result res;
@@ -206,19 +203,11 @@ extern "C" int olf_pose_optimization_batch_dev(olf_ctx* c, const olf_pose_points
     PosePointsArgs A;
     A.in = *in; A.out = *o; A.n_rows = n_rows; A.n_frames = n_frames;
     A.cap = olf_orb_capacity(c);
-    float sf[OLF_MAX_LEVELS];
-    A.nlevels = ctx_level_scales(c, sf);
-    for (int l = 0; l < OLF_MAX_LEVELS; ++l) { const float sigma2 = sf[l] * sf[l]; A.inv_sigma2[l] = 1.0f / sigma2; }      // mvInvLevelSigma2, src/ORBextractor.cc:434-436
+    A.nlevels = ctx_level_inv_sigma2(c, A.inv_sigma2);
     const PpSlab lay(A.cap);
     const int grid = std::min(n_rows, PP_MAX_GRID);
     A.slab_bytes = lay.total;
-    A.use_lds = lay.total <= (size_t)g_pp_lds_limit;
-    A.slabs = nullptr;
-    if (!A.use_lds) {
-        Carve k;
-        k.add(&A.slabs, lay.total * (size_t)grid);
-        OLF_TRY(k.bind(c, SCRATCH_BATCH));
-    }
+    OLF_TRY(wg_state_place(c, g_pose_points_lds, lay.total, grid, &A.slabs, &A.use_lds));
     hipLaunchKernelGGL(k_pose_points_rows, dim3(grid), dim3(PP_THREADS), A.use_lds ? lay.total : 0, ctx_stream(c, stream), A, ctx_status(c));
     OLF_HIP_CHECK(hipGetLastError());
     return OLF_OK;

@@ -1,7 +1,7 @@
 // posepoints_host.cpp -- olf_pose_optimization: int Optimizer::PoseOptimization(Frame*) (src/Optimizer.cc:239-451) for one row on the host.  Plain C++
 // doubles, every sum in the order of the reference's _activeEdges (ascending feature index, the two kinds interleaved), no context and no device: the
-// definition the kernel of posepoints_batch.hip is read against.  The edges' terms, the LDLT, the Levenberg loop and the driver of the four passes are
-// posepoints_terms.hpp, shared with the kernel; this file owns the loops over a row's edges.
+// definition the kernel of posepoints_batch.hip is read against.  The edges' terms and the driver of the four passes are
+// posepoints_terms.hpp, the LDLT and the Levenberg loop g2o_levenberg.hpp, shared with the kernel; this file owns the loops over a row's edges.
 #include <algorithm>
 #include <string>
 #include <vector>

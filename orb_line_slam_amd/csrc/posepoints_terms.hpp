@@ -8,60 +8,42 @@
 // What is restated (Thirdparty/g2o/g2o/...):
 //   types/types_six_dof_expmap.{h,cpp}   computeError and linearizeOplus of the two ...OnlyPose edges, VertexSE3Expmap::oplusImpl
 //   types/se3quat.h, se3_ops.hpp         the constructor's normalizeRotation, map, exp (with its theta < 1e-5 branch), operator*, to_homogeneous_matrix
-//   core/base_edge.h, base_unary_edge.hpp:43-72, robust_kernel_impl.cpp    chi2, constructQuadraticForm with rho[1] on b and on omega, Huber
-//   core/optimization_algorithm_levenberg.cpp:61-189, sparse_optimizer.cpp:354-419, block_solver.hpp   the loop, lambda, the stop rules
-//   solvers/linear_solver_dense.h        Eigen::LDLT<MatrixXd> and isPositive()
+//   core/base_edge.h, base_unary_edge.hpp:43-72    chi2, constructQuadraticForm with rho[1] on b and on omega
+// The Levenberg loop, Eigen's LDLT, the Huber kernel and the row status bits ST_DEPTH / ST_NOT_FINITE / ST_OCTAVE are g2o_levenberg.hpp; the matrix and
+// quaternion pieces are dense_math.hpp.
 //
 // Conventions where the reference's build decides: an Eigen fixed-size product sums over k in ascending order and is formed before it
-// is added to its destination; Quaterniond * Vector3d is v + w * uv + vec x uv with uv = 2 (vec x v); the quaternion product is the generic (not the
-// SSE) form; a quaternion's norm is summed x, y, z, w (pose_terms.hpp, shared); LDLT is Eigen 3.3's unblocked in-place form on the LOWER triangle (the one
-// block of this problem is copied whole, and Eigen::LDLT reads the lower half): the pivot is the first largest |diagonal| of what remains, a column whose
-// pivot is exactly zero is not scaled, isPositive() is "no negative pivot was seen", and solve() sets a component whose |D| <= DBL_MIN to zero.
+// is added to its destination; Quaterniond * Vector3d, the generic quaternion product and a quaternion's norm are dense_math.hpp's; LDLT is
+// g2o_levenberg.hpp's.
 //
-// Four things the reference leaves undefined, or that cannot happen through its call sites, are defined here:
-//   - a held point whose depth in the camera is exactly 0 at an evaluation (the reference divides by z): the row stops, ST_DEPTH;
-//   - an H, b, step or estimate that is not finite: the row stops, ST_NOT_FINITE.  A stopped row returns Tcw_out = Tcw, its flags as they stood at that
-//     moment, n_good = 0 and the passes it completed;
+// Beside what g2o_levenberg.hpp defines (a depth of exactly 0: ST_DEPTH; an H, b, step or estimate that is not finite: ST_NOT_FINITE; a failed LDLT), two
+// things the reference leaves undefined, or that cannot happen through its call sites, are defined here:
+//   - a stopped row returns Tcw_out = Tcw, its flags as they stood at that moment, n_good = 0 and the passes it completed;
 //   - a pass whose active set is empty: g2o's initializeOptimization leaves the vertex out and optimize() returns before its first iteration; carrying the
 //     algebra through instead (H = 0, b = 0, lambda = 0, LDLT of a zero matrix is "positive" with x = 0, rho = 0 / 1e-3 = 0: rejected, pop(), Terminate) ends
-//     at the same place.  Either way the estimate is toSE3Quat(mTcw), iters = 0, and every edge -- all are flagged -- is classified with its error there;
-//   - a failed LDLT: g2o applies the solver's previous x again and sets tempChi = DBL_MAX; that is followed literally (x is zero at a pass's start).
+//     at the same place.  Either way the estimate is toSE3Quat(mTcw), iters = 0, and every edge -- all are flagged -- is classified with its error there.
 #pragma once
-#include <float.h>
-#include "pose_terms.hpp"
+#include "dense_math.hpp"
+#include "g2o_levenberg.hpp"
 
 namespace olf {
 namespace posepoints {
 
-using pose::finite_d;
+using namespace dense;
+using namespace levenberg;
 
-enum { ST_DEPTH = 1, ST_NOT_FINITE = 2, ST_OCTAVE = 4 };          // the row's own status word (the host form adds 512 / 2048 of the context's)
 enum { E_HELD = 1, E_OUT = 2, E_STEREO = 4 };                     // an edge's byte: holds a point, mvbOutlier (= level 1), the stereo kind
 
 struct Cam { double fx, fy, cx, cy, bf; };
 struct Se3 { double q[4], t[3]; };                                // g2o::SE3Quat: _r as x, y, z, w and _t
 
-// Converter::toSE3Quat (src/Converter.cc:37-47): the floats widen, SE3Quat(R, t) normalises (pose_terms.hpp: quat_from_mat4)
+// Converter::toSE3Quat (src/Converter.cc:37-47): the floats widen, SE3Quat(R, t) normalises (quat_from_mat4)
 PT_HD void se3_from_tcw(const float* Tcw, Se3* s)
 {
     double T[16];
     for (int i = 0; i < 16; ++i) T[i] = (double)Tcw[i];
-    pose::quat_from_mat4(T, s->q);
+    quat_from_mat4(T, s->q);
     s->t[0] = T[3]; s->t[1] = T[7]; s->t[2] = T[11];
-}
-PT_HD void cross3(const double* a, const double* b, double* o)
-{
-    const double x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
-    o[0] = x; o[1] = y; o[2] = z;
-}
-// Quaterniond * Vector3d (Eigen's _transformVector)
-PT_HD void quat_rotate(const double* q, const double* v, double* o)
-{
-    double uv[3], c[3];
-    cross3(q, v, uv);
-    for (int i = 0; i < 3; ++i) uv[i] = uv[i] + uv[i];
-    cross3(q, uv, c);
-    for (int i = 0; i < 3; ++i) o[i] = (v[i] + q[3] * uv[i]) + c[i];
 }
 // SE3Quat::map, se3quat.h:217-220: _r * xyz + _t
 PT_HD void se3_map(const Se3& s, const double* X, double* o)
@@ -76,8 +58,8 @@ PT_HD void se3_exp(const double* u, Se3* s)
     const double om[3] = {u[0], u[1], u[2]}, up[3] = {u[3], u[4], u[5]};
     const double theta = sqrt((om[0] * om[0] + om[1] * om[1]) + om[2] * om[2]);
     double Om[9], OO[9], R[9], V[9];
-    pose::skew3(om, Om);
-    pose::mat3_mul(Om, Om, OO);
+    skew3(om, Om);
+    mat3_mul(Om, Om, OO);
     if (theta < 0.00001) {
         for (int i = 0; i < 9; ++i) { R[i] = (((i % 4 == 0) ? 1.0 : 0.0) + Om[i]) + OO[i]; V[i] = R[i]; }
     } else {
@@ -89,19 +71,10 @@ PT_HD void se3_exp(const double* u, Se3* s)
         }
     }
     double T[16];
-    pose::mat4_identity(T);
+    mat4_identity(T);
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) T[i * 4 + j] = R[i * 3 + j];
-    pose::quat_from_mat4(T, s->q);                                  // SE3Quat(Quaterniond(R), V * upsilon) normalises
-    pose::mat3_vec(V, up, s->t);
-}
-// Quaterniond * Quaterniond, the generic (not the SSE) product; o may not alias a or b
-PT_HD void quat_mul(const double* a, const double* b, double* o)
-{
-    const double ax = a[0], ay = a[1], az = a[2], aw = a[3], bx = b[0], by = b[1], bz = b[2], bw = b[3];
-    o[3] = ((aw * bw - ax * bx) - ay * by) - az * bz;
-    o[0] = ((aw * bx + ax * bw) + ay * bz) - az * by;
-    o[1] = ((aw * by + ay * bw) + az * bx) - ax * bz;
-    o[2] = ((aw * bz + az * bw) + ax * by) - ay * bx;
+    quat_from_mat4(T, s->q);                                        // SE3Quat(Quaterniond(R), V * upsilon) normalises
+    mat3_vec(V, up, s->t);
 }
 // SE3Quat::operator*, se3quat.h:104-110
 PT_HD void se3_mul(const Se3& a, const Se3& b, Se3* o)
@@ -110,7 +83,7 @@ PT_HD void se3_mul(const Se3& a, const Se3& b, Se3* o)
     quat_rotate(a.q, b.t, r);
     quat_mul(a.q, b.q, q);
     for (int i = 0; i < 3; ++i) o->t[i] = a.t[i] + r[i];
-    pose::quat_normalize_positive(q);
+    quat_normalize_positive(q);
     for (int i = 0; i < 4; ++i) o->q[i] = q[i];
 }
 PT_HD bool se3_finite(const Se3& s)
@@ -131,7 +104,7 @@ struct VertexSE3 {
 PT_HD void se3_to_tcw(const Se3& s, float* Tcw)
 {
     double R[9];
-    pose::quat_to_mat3(s.q, R);
+    quat_to_mat3(s.q, R);
     for (int i = 0; i < 16; ++i) Tcw[i] = (i % 5 == 0) ? 1.f : 0.f;
     for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) Tcw[i * 4 + j] = (float)R[i * 3 + j]; Tcw[i * 4 + 3] = (float)s.t[i]; }
 }
@@ -163,13 +136,6 @@ PT_HD double edge_chi2(const double* e, double w, bool stereo)
     double s = e[0] * (w * e[0]) + e[1] * (w * e[1]);
     if (stereo) s = s + e[2] * (w * e[2]);
     return s;
-}
-// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91): rho[0], rho[1]
-PT_HD void huber(double e, double delta, double* rho0, double* rho1)
-{
-    const double dsqr = delta * delta;
-    if (e <= dsqr) { *rho0 = e; *rho1 = 1.0; }
-    else { const double sq = sqrt(e); *rho0 = (2.0 * sq) * delta - dsqr; *rho1 = delta / sq; }
 }
 // what activeRobustChi2 (sparse_optimizer.cpp:100-114) adds for an edge
 PT_HD double edge_robust_chi2(const double* e, double w, bool stereo, bool robust)
@@ -229,132 +195,8 @@ PT_HD bool edge_quadratic_form(const Cam& c, const Se3& est, const double* Xw, c
     return true;
 }
 
-// ---- Eigen::LDLT<MatrixXd> of a D x D matrix and its solve (what LinearSolverDense calls) ------------------------------------------------------------------
-// A: row-major, only the lower triangle is read.  Returns isPositive(); x is written only then (linear_solver_dense.h:107-112).
-template <int D>
-PT_HD bool ldlt_solve(const double* A, const double* b, double* x)
-{
-    double M[D * D], tmp[D], y[D];
-    int tr[D];
-    for (int i = 0; i < D; ++i) for (int j = 0; j < D; ++j) M[i * D + j] = j <= i ? A[i * D + j] : 0.0;
-    int sign = 0;                                                   // ZeroSign; 1 PositiveSemiDef, -1 NegativeSemiDef, 2 Indefinite
-    bool all_zero = false;
-    for (int k = 0; k < D; ++k) {
-        int p = k;
-        double big = fabs(M[k * D + k]);
-        for (int i = k + 1; i < D; ++i) if (fabs(M[i * D + i]) > big) { big = fabs(M[i * D + i]); p = i; }
-        tr[k] = p;
-        if (p != k) {
-            for (int j = 0; j < k; ++j) { const double t = M[k * D + j]; M[k * D + j] = M[p * D + j]; M[p * D + j] = t; }
-            for (int i = p + 1; i < D; ++i) { const double t = M[i * D + k]; M[i * D + k] = M[i * D + p]; M[i * D + p] = t; }
-            { const double t = M[k * D + k]; M[k * D + k] = M[p * D + p]; M[p * D + p] = t; }
-            for (int i = k + 1; i < p; ++i) { const double t = M[i * D + k]; M[i * D + k] = M[p * D + i]; M[p * D + i] = t; }
-        }
-        if (k > 0) {
-            for (int j = 0; j < k; ++j) tmp[j] = M[j * D + j] * M[k * D + j];
-            double s = M[k * D] * tmp[0];
-            for (int j = 1; j < k; ++j) s = s + M[k * D + j] * tmp[j];
-            M[k * D + k] = M[k * D + k] - s;
-            for (int i = k + 1; i < D; ++i) {
-                double r = M[i * D] * tmp[0];
-                for (int j = 1; j < k; ++j) r = r + M[i * D + j] * tmp[j];
-                M[i * D + k] = M[i * D + k] - r;
-            }
-        }
-        const double akk = M[k * D + k];
-        const bool valid = fabs(akk) > 0.0;
-        if (k == 0 && !valid) { for (int j = 0; j < D; ++j) tr[j] = j; all_zero = true; break; }      // the whole diagonal is zero: ZeroSign
-        if (valid) for (int i = k + 1; i < D; ++i) M[i * D + k] = M[i * D + k] / akk;
-        if (sign == 1) { if (akk < 0.0) sign = 2; }
-        else if (sign == -1) { if (akk > 0.0) sign = 2; }
-        else if (sign == 0) { if (akk > 0.0) sign = 1; else if (akk < 0.0) sign = -1; }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    for (int i = 0; i < D; ++i) y[i] = b[i];
-    for (int k = 0; k < D; ++k) if (tr[k] != k) { const double t = y[k]; y[k] = y[tr[k]]; y[tr[k]] = t; }
-    if (!all_zero) for (int j = 0; j < D; ++j) for (int i = j + 1; i < D; ++i) y[i] = y[i] - M[i * D + j] * y[j];          // L^-1, column by column
-    for (int i = 0; i < D; ++i) y[i] = fabs(M[i * D + i]) > DBL_MIN ? y[i] / M[i * D + i] : 0.0;                            // D^-1
-    if (!all_zero)
-        for (int i = D - 2; i >= 0; --i) {                                                                                  // L^-T, row by row
-            double s = M[(i + 1) * D + i] * y[i + 1];
-            for (int j = i + 2; j < D; ++j) s = s + M[j * D + i] * y[j];
-            y[i] = y[i] - s;
-        }
-    for (int k = D - 1; k >= 0; --k) if (tr[k] != k) { const double t = y[k]; y[k] = y[tr[k]]; y[tr[k]] = t; }
-    for (int i = 0; i < D; ++i) x[i] = y[i];
-    return true;
-}
-
-// ---- OptimizationAlgorithmLevenberg over one vertex of dimension V::D --------------------------------------------------------------------------------------
-// Ops:  bool errors(const V& v, bool robust, double* chi)      computeActiveErrors at v (every active edge's _error is replaced) and activeRobustChi2;
-//                                                               false: a depth of 0 (the stored errors are then unspecified, the row stops)
-//       bool system(const V& v, bool robust, double* S)        buildSystem: S[D (D + 1) / 2 + D], H's lower triangle row by row and -b, over the active edges
-enum { LM_STOP = -1 };
-template <class V, class Ops>
-PT_HD int lm_optimize(Ops& ops, V& v, int iterations, bool robust, int* status)
-{
-    enum { D = V::D, NH = D * (D + 1) / 2 };
-    double lambda = -1.0, ni = 2.0, x[D], H[D * D], Hl[D * D], b[D], S[NH + D];
-    int n_bad = 0, done = 0;
-    for (int i = 0; i < D; ++i) x[i] = 0.0;
-    for (int it = 0; it < iterations; ++it) {                       // SparseOptimizer::optimize, sparse_optimizer.cpp:376-414
-        // ---- OptimizationAlgorithmLevenberg::solve(it), optimization_algorithm_levenberg.cpp:61-164
-        double cur, tmp;
-        if (!ops.errors(v, robust, &cur)) { *status |= ST_DEPTH; return LM_STOP; }
-        const double ini = cur;
-        if (!ops.system(v, robust, S)) { *status |= ST_DEPTH; return LM_STOP; }
-        bool ok = true;
-        for (int i = 0; i < NH + D; ++i) ok = ok && finite_d(S[i]);
-        if (!ok) { *status |= ST_NOT_FINITE; return LM_STOP; }
-        int k = 0;
-        for (int i = 0; i < D; ++i) for (int j = 0; j <= i; ++j) { H[i * D + j] = S[k]; H[j * D + i] = S[k]; ++k; }
-        for (int i = 0; i < D; ++i) b[i] = -S[NH + i];
-        if (it == 0) {                                              // computeLambdaInit, :166-180
-            double md = 0.0;
-            for (int j = 0; j < D; ++j) md = pose::max_d(fabs(H[j * D + j]), md);
-            lambda = 1e-5 * md; ni = 2.0; n_bad = 0;
-        }
-        double rho = 0.0;
-        int qmax = 0;
-        do {
-            const V backup = v;                                     // push()
-            for (int i = 0; i < D * D; ++i) Hl[i] = H[i];
-            for (int i = 0; i < D; ++i) Hl[i * D + i] = Hl[i * D + i] + lambda;      // setLambda; restoreDiagonal is H itself
-            const bool ok2 = ldlt_solve<D>(Hl, b, x);
-            for (int i = 0; i < D; ++i) ok = ok && finite_d(x[i]);
-            if (!ok) { *status |= ST_NOT_FINITE; return LM_STOP; }
-            v.oplus(x);
-            if (!v.finite()) { v = backup; *status |= ST_NOT_FINITE; return LM_STOP; }
-            if (!ops.errors(v, robust, &tmp)) { v = backup; *status |= ST_DEPTH; return LM_STOP; }
-            if (!ok2) tmp = DBL_MAX;
-            rho = cur - tmp;
-            double scale = 0.0;                                     // computeScale, :182-189
-            for (int j = 0; j < D; ++j) scale = scale + x[j] * (lambda * x[j] + b[j]);
-            scale = scale + 1e-3;
-            rho = rho / scale;
-            if (rho > 0.0 && finite_d(tmp)) {
-                double alpha = 1.0 - pow(2.0 * rho - 1.0, 3.0);
-                alpha = pose::min_d(alpha, 2. / 3.);
-                lambda = lambda * pose::max_d(1. / 3., alpha);
-                ni = 2.0;
-                cur = tmp;
-            } else {
-                lambda = lambda * ni;
-                ni = ni * 2.0;
-                v = backup;                                         // pop(): the vertex comes back, the edges keep the errors of the rejected estimate
-            }
-            qmax++;
-        } while (rho < 0.0 && qmax < 10);
-        ++done;
-        if (qmax == 10 || rho == 0.0) break;                        // Terminate
-        if ((ini - cur) * 1e3 < ini) n_bad++; else n_bad = 0;
-        if (n_bad >= 3) break;
-    }
-    return done;
-}
-
 // ---- the four passes and the epilogue, src/Optimizer.cc:364-450 ---------------------------------------------------------------------------------------------
-// Ops, beyond the two above:
+// Ops, beyond errors() and system() of lm_optimize (g2o_levenberg.hpp):
 //       int  n_edges()                        nInitialCorrespondences = optimizer.edges().size(): the held features
 //       int  n_active()                       edges of level 0
 //       bool classify(const Se3& est, int* n_bad)      :382-438 for every edge: a flagged one gets computeError at est first, an unflagged one is read with

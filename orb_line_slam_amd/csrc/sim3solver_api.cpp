@@ -1,6 +1,7 @@
 // sim3solver_api.cpp -- the host-pointer form of sim3solver_batch.hip that runs on the device: olf_sim3_solver_pairs.  It stages the arrays, the carried
 // state and the outputs in one carve -- the outputs are uploaded first, so what the device leaves untouched (a refused pair, a row's tail, counts of
 // iterations not evaluated) comes back as it went in -- and runs the same kernel.  (The form that computes on the host is sim3solver_host.cpp.)
+#include "solver_args.hpp"
 #include "staging.hpp"
 #include "../../include/orbline.h"
 
@@ -10,10 +11,8 @@ extern "C" int olf_sim3_solver_pairs(olf_ctx* c, const olf_track_batch* in, int 
                                      const int32_t* matches12, const olf_sim3_ransac* R, const uint32_t* draws, const olf_sim3_solver_io* io)
 {
     const char* who = "olf_sim3_solver_pairs";
-    bool ok = c && in && R && io && n_frames >= 0 && n_pairs >= 0;
-    ok = ok && R->min_inliers >= 3 && R->max_iterations >= 1 && R->n_iterations >= 0 && R->probability > 0.0 && R->probability < 1.0;
-    ok = ok && (!n_pairs || (pairs && matches12 && draws && io->iterations_done && io->best_inliers && io->best_s && io->best_R && io->best_t && io->best_T12 &&
-                             io->accepted && io->no_more && io->n_inliers && io->inliers && io->n_correspondences));
+    bool ok = c && in && io && n_frames >= 0 && n_pairs >= 0 && sim3_ransac_ok(R);
+    ok = ok && (!n_pairs || (pairs && matches12 && draws && sim3_io_ok(io)));
     ok = ok && (!n_frames || (in->kps && in->counts && in->img_stride >= 1 && in->Tcw && in->mp_world));
     if (!ok) { set_error(std::string(who) + ": bad argument"); return OLF_ERR_INVALID; }
     if (n_pairs == 0) return OLF_OK;

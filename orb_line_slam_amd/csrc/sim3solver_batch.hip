@@ -17,20 +17,19 @@
 //     Bound by instruction issue: a fit is some thousand dependent float operations, a hypothesis 2 * N projections; the bytes are the row and 100 per
 //     correspondence, read once.
 //   k_sim3_filter   one lane per (pair, i1).
-#include <mutex>
-#include <vector>
 #include "sim3solver_terms.hpp"
 #include "batch_frames.hpp"
+#include "host_table_cache.hpp"
 #include "map_kernels.hpp"
-#include "staging.hpp"
+#include "solver_args.hpp"
+#include "wg_state.hpp"
 #include "../../include/orbline.h"
 
 namespace olf {
 
 constexpr int S3_THREADS = 256, S3_WAVES = 4, S3_PER_WAVE = 16, S3_ROUND = 64, S3_MAX_GRID = 1024;
 constexpr int S3_LDS_DEFAULT = 60 * 1024;           // of the 64 KiB a workgroup takes without asking for more; the kernel's own LDS is below 1 KiB
-static int g_s3_lds_limit = S3_LDS_DEFAULT;
-void sim3_solver_lds_limit(int bytes) { g_s3_lds_limit = bytes > 0 ? std::min(bytes, S3_LDS_DEFAULT) : S3_LDS_DEFAULT; }
+LdsLimit g_sim3_solver_lds(S3_LDS_DEFAULT);
 
 struct Sim3SolverArgs {
     const olf_keypoint* kps;
@@ -60,7 +59,7 @@ __device__ __forceinline__ void s3_fit_iteration(const Sim3SolverArgs& A, const 
     const uint32_t* r = A.draws + 3 * ((size_t)p * A.max_iterations + j);
     const uint32_t rr[3] = {r[0], r[1], r[2]};
     int idx[3];
-    s3_sample(N, rr, idx);
+    ransac_sample<3>(N, rr, idx);
     float P1[3][3], P2[3][3];
     for (int k = 0; k < 3; ++k)
         for (int c = 0; c < 3; ++c) { P1[k][c] = st[(size_t)c * A.cap + idx[k]]; P2[k][c] = st[(size_t)(3 + c) * A.cap + idx[k]]; }
@@ -73,6 +72,7 @@ __global__ __launch_bounds__(S3_THREADS) void k_sim3_solver(Sim3SolverArgs A, in
     __shared__ int s_accept, s_best_it, s_carry;
     __shared__ int s_counts[S3_ROUND];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, cap = A.cap;
+    // (its own text, not wg_state_ptr: the product in another order moved this kernel, which is at its scalar register limit, outside the timing rule)
     float* st = A.state ? A.state + (size_t)blockIdx.x * S3_WORDS * cap : s3_dyn;
     int* st_i1 = reinterpret_cast<int*>(st + (size_t)12 * cap);
 
@@ -209,45 +209,8 @@ __global__ __launch_bounds__(S3_THREADS) void k_sim3_filter(int n_pairs, int cap
     out[e] = inl[e] ? m12[e] : -1;
 }
 
-// The iteration caps of every N in [0, cap] for one parameter set, built on the host (libm) and uploaded on the call's stream from pinned memory.  The
-// upload of a call may read its table after the call has returned, so a table is never changed while its last upload can be pending: at most S3_TABLES
-// parameter sets are kept; one more takes the place of the least recently used, after that one's last upload has completed (an event per table; the wait
-// is the only one this entry ever makes, and only a caller that sweeps more than S3_TABLES parameter sets meets it).
-constexpr int S3_TABLES = 8;
-struct S3Table { double p; int m, maxit, cap, room; int* host; hipEvent_t last; unsigned long long used; };
-static std::mutex g_s3_mutex;
-static std::vector<S3Table> g_s3_tables;
-static unsigned long long g_s3_clock = 0;
-static int s3_upload_table(double p, int m, int maxit, int cap, int* d_its, hipStream_t s)
-{
-    std::lock_guard<std::mutex> lock(g_s3_mutex);
-    S3Table* t = nullptr;
-    for (S3Table& e : g_s3_tables) if (e.p == p && e.m == m && e.maxit == maxit && e.cap == cap) t = &e;
-    if (!t) {
-        if ((int)g_s3_tables.size() < S3_TABLES) {
-            S3Table e = {p, m, maxit, cap, 0, nullptr, nullptr, 0};
-            OLF_HIP_CHECK(hipEventCreateWithFlags(&e.last, hipEventDisableTiming));
-            g_s3_tables.push_back(e);
-            t = &g_s3_tables.back();
-        } else {
-            t = &g_s3_tables[0];
-            for (S3Table& e : g_s3_tables) if (e.used < t->used) t = &e;
-            OLF_HIP_CHECK(hipEventSynchronize(t->last));
-        }
-        if (t->room < cap + 1) {
-            if (t->host) OLF_HIP_CHECK(hipHostFree(t->host));
-            t->host = nullptr; t->room = 0;
-            OLF_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&t->host), ((size_t)cap + 1) * sizeof(int), hipHostMallocDefault));
-            t->room = cap + 1;
-        }
-        t->p = p; t->m = m; t->maxit = maxit; t->cap = cap;
-        for (int N = 0; N <= cap; ++N) t->host[N] = s3_iteration_cap(N, p, m, maxit);
-    }
-    t->used = ++g_s3_clock;
-    OLF_HIP_CHECK(hipMemcpyAsync(d_its, t->host, ((size_t)cap + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-    OLF_HIP_CHECK(hipEventRecord(t->last, s));
-    return OLF_OK;
-}
+// the iteration caps of every N in [0, cap] for one parameter set (host_table_cache.hpp)
+static HostTableCache g_s3_tables(1);
 
 }  // namespace olf
 
@@ -259,10 +222,8 @@ int olf_sim3_solver_pairs_dev(olf_ctx* c, const olf_track_batch* in, int n_frame
                               const int32_t* d_matches12, const olf_sim3_ransac* ransac, const uint32_t* d_draws, const olf_sim3_solver_io* io, void* stream)
 {
     const char* who = "olf_sim3_solver_pairs_dev";
-    bool ok = c && in && ransac && io && n_frames >= 0 && n_pairs >= 0;
-    ok = ok && ransac->min_inliers >= 3 && ransac->max_iterations >= 1 && ransac->n_iterations >= 0 && ransac->probability > 0.0 && ransac->probability < 1.0;
-    ok = ok && (!n_pairs || (d_pairs && d_matches12 && d_draws && io->iterations_done && io->best_inliers && io->best_s && io->best_R && io->best_t &&
-                             io->best_T12 && io->accepted && io->no_more && io->n_inliers && io->inliers && io->n_correspondences));
+    bool ok = c && in && io && n_frames >= 0 && n_pairs >= 0 && sim3_ransac_ok(ransac);
+    ok = ok && (!n_pairs || (d_pairs && d_matches12 && d_draws && sim3_io_ok(io)));
     ok = ok && (!n_pairs || !n_frames || (in->kps && in->counts && in->img_stride >= 1 && in->Tcw && in->mp_world));
     if (!ok) { set_error(std::string(who) + ": bad argument"); return OLF_ERR_INVALID; }
     OLF_TRY(ctx_check_device(c, who));
@@ -270,18 +231,17 @@ int olf_sim3_solver_pairs_dev(olf_ctx* c, const olf_track_batch* in, int n_frame
     Sim3SolverArgs A;
     A.cap = olf_orb_capacity(c);
     const size_t state_bytes = (size_t)S3_WORDS * A.cap * sizeof(float);
-    const bool lds = state_bytes <= (size_t)g_s3_lds_limit;
     const int grid = std::min(n_pairs, S3_MAX_GRID);
     int* d_its;
-    float* d_state = nullptr;
     Carve k;
     k.add(&d_its, (size_t)A.cap + 1);
-    if (!lds) k.add(&d_state, (size_t)grid * S3_WORDS * A.cap);
+    const bool lds = wg_state_in_lds(k, g_sim3_solver_lds, state_bytes, grid, &A.state);
     OLF_TRY(k.bind(c, SCRATCH_BATCH));
     hipStream_t s = ctx_stream(c, stream);
-    OLF_TRY(s3_upload_table(ransac->probability, ransac->min_inliers, ransac->max_iterations, A.cap, d_its, s));
+    OLF_TRY(g_s3_tables.upload({ransac->probability, ransac->min_inliers, ransac->max_iterations, A.cap, 0.f},
+                               [&](int N, int* row) { *row = s3_iteration_cap(N, ransac->probability, ransac->min_inliers, ransac->max_iterations); }, d_its, s));
     A.kps = in->kps; A.counts = in->counts; A.pairs = d_pairs; A.matches12 = d_matches12; A.its_of_N = d_its; A.Tcw = in->Tcw; A.world = in->mp_world;
-    A.valid = in->mp_valid; A.bad = d_mp_bad; A.draws = d_draws; A.io = *io; A.state = d_state;
+    A.valid = in->mp_valid; A.bad = d_mp_bad; A.draws = d_draws; A.io = *io;
     A.img_stride = in->img_stride; A.n_frames = n_frames; A.n_pairs = n_pairs; A.fix_scale = ransac->fix_scale ? 1 : 0;
     A.min_inliers = ransac->min_inliers; A.max_iterations = ransac->max_iterations; A.n_iterations = ransac->n_iterations;
     A.cam[0] = in->fx; A.cam[1] = in->fy; A.cam[2] = in->cx; A.cam[3] = in->cy;

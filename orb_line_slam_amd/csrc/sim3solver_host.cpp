@@ -3,6 +3,7 @@
 // window as a scan, and the tests hold the two against each other.
 #include <vector>
 #include "sim3solver_terms.hpp"
+#include "solver_args.hpp"
 #include "olf_internal.hpp"
 #include "../../include/orbline.h"
 
@@ -10,7 +11,18 @@ using namespace olf;
 
 namespace {
 struct Corr { float X1[3], X2[3], p1[2], p2[2], g1, g2; int i1; };
-inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+}
+
+namespace olf {
+bool sim3_ransac_ok(const olf_sim3_ransac* R)
+{
+    return R && R->min_inliers >= 3 && R->max_iterations >= 1 && R->n_iterations >= 0 && R->probability > 0.0 && R->probability < 1.0;
+}
+bool sim3_io_ok(const olf_sim3_solver_io* io)
+{
+    return io && io->iterations_done && io->best_inliers && io->best_s && io->best_R && io->best_t && io->best_T12 && io->accepted && io->no_more &&
+           io->n_inliers && io->inliers && io->n_correspondences;
+}
 }
 
 extern "C" int olf_debug_sim3_solver_gate(float scale_factor, uint64_t* gate)
@@ -31,10 +43,8 @@ extern "C" int olf_sim3_solver(const olf_track_batch* in, int capacity, int n_fr
                                int kf2, const int32_t* matches12, const olf_sim3_ransac* R, const uint32_t* draws, const olf_sim3_solver_io* io, int32_t* status)
 {
     const char* who = "olf_sim3_solver";
-    bool ok = in && R && io && status && capacity >= 0 && n_frames >= 0 && scale_factors && n_levels >= 1 && n_levels <= OLF_MAX_LEVELS && matches12 && draws;
-    ok = ok && R->min_inliers >= 3 && R->max_iterations >= 1 && R->n_iterations >= 0 && R->probability > 0.0 && R->probability < 1.0;
-    ok = ok && io->iterations_done && io->best_inliers && io->best_s && io->best_R && io->best_t && io->best_T12 && io->accepted && io->no_more &&
-         io->n_inliers && io->inliers && io->n_correspondences;
+    bool ok = in && status && capacity >= 0 && n_frames >= 0 && scale_factors && n_levels >= 1 && n_levels <= OLF_MAX_LEVELS && matches12 && draws;
+    ok = ok && sim3_ransac_ok(R) && sim3_io_ok(io);
     ok = ok && (!n_frames || (in->kps && in->counts && in->img_stride >= 1 && in->Tcw && in->mp_world));
     if (!ok) { set_error(std::string(who) + ": bad argument"); return OLF_ERR_INVALID; }
     *status = 0;
@@ -75,7 +85,7 @@ extern "C" int olf_sim3_solver(const olf_track_batch* in, int capacity, int n_fr
         ++cur;
         const int j = it++;
         int idx[3];
-        s3_sample(N, draws + 3 * (size_t)j, idx);
+        ransac_sample<3>(N, draws + 3 * (size_t)j, idx);
         float P1[3][3], P2[3][3];
         for (int k = 0; k < 3; ++k)
             for (int c = 0; c < 3; ++c) { P1[k][c] = cs[idx[k]].X1[c]; P2[k][c] = cs[idx[k]].X2[c]; }

@@ -1,6 +1,7 @@
 // sim3solver_terms.hpp -- the arithmetic of Sim3Solver (src/Sim3Solver.cc) that the host form (sim3solver_host.cpp) and the kernel (sim3solver_batch.hip)
-// both run: the correspondence of one match row entry (:62-109), the integer gates (:87-88, include/Sim3Solver.h:78-79), the sample of one iteration from
-// its three draws (:163-177), Horn's fit (:226-337) and the inlier test of one correspondence (:340-364, :382-403).  One text for both sides; every file
+// both run: the correspondence of one match row entry (:62-109), the integer gates (:87-88, include/Sim3Solver.h:78-79), Horn's fit (:226-337) and the
+// inlier test of one correspondence (:340-364, :382-403); the sample of one iteration from its three draws (:163-177) is ransac_sample<3> of
+// ransac_terms.hpp, shared with pnpsolver_terms.hpp.  One text for both sides; every file
 // that includes it is built with -ffp-contract=off (C.4) and the rounded operations are spelled through device_math.hpp.  cv::Mat products follow C.12
 // (plain product: float sums, alpha and the C term in double, one rounding; transposed operand: double accumulation) and C.17 (Mat / scalar); new here:
 //   C.20  the random stream is the caller's: draws[iteration][3], raw rand() values below 2^31; draw k of an iteration picks position
@@ -12,6 +13,7 @@
 //         c I + (1 - c) r r^T + s [r]x with r = v / |v|, each element rounded once: no libm on either side.  |v| == 0 divides 0 by 0 as the reference
 //         does: every element of R is NaN and the iteration counts no inlier.
 #pragma once
+#include "ransac_terms.hpp"
 #include "search_math.hpp"
 
 namespace olf {
@@ -33,23 +35,6 @@ OLF_HD void s3_image(const float* X, const float* cam, float* uv)
     const float x = f_mul(X[0], invz), y = f_mul(X[1], invz);
     uv[0] = f_add(f_mul(cam[0], x), cam[2]);
     uv[1] = f_add(f_mul(cam[1], y), cam[3]);
-}
-
-// is row value v of matches12 a correspondence: 0 <= v < N2 (-1, -2 and >= N2 of olf_search_by_sim3 are all "none")
-OLF_HD bool s3_is_match(int v, int N2) { return (unsigned)v < (unsigned)N2; }
-
-// the three sample indices of one iteration (:163-177): vAvailableIndices starts as 0 .. N - 1; a drawn position takes the back's value and the back is
-// dropped.  Only three draws: the array is two remembered substitutions.  N >= 3.
-// (bit 31 of a draw is dropped: rand() never sets it, and with it the position would leave [0, n))
-OLF_HD int s3_pos(uint32_t r, int n) { return (int)d_mul(d_div((double)(r & 0x7fffffffu), 2147483648.0), (double)n); }
-OLF_HD void s3_sample(int N, const uint32_t* r, int* idx)
-{
-    const int p0 = s3_pos(r[0], N), p1 = s3_pos(r[1], N - 1), p2 = s3_pos(r[2], N - 2);
-    // after draw 0: a1[x] = x == p0 ? N - 1 : x  for x < N - 1
-    const int a1_p1 = p1 == p0 ? N - 1 : p1, back1 = (N - 2) == p0 ? N - 1 : N - 2;
-    // after draw 1: a2[x] = x == p1 ? a1[N - 2] : a1[x]  for x < N - 2
-    const int a1_p2 = p2 == p0 ? N - 1 : p2;
-    idx[0] = p0; idx[1] = a1_p1; idx[2] = p2 == p1 ? back1 : a1_p2;
 }
 
 OLF_HD float s3_hypot(float a, float b)             // OpenCV's own hypot<float> (modules/core/src/lapack.cpp)

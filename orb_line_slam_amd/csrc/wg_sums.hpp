@@ -31,6 +31,13 @@ struct WgSums {
         *n = ((lds->redn[parity][0] + lds->redn[parity][1]) + lds->redn[parity][2]) + lds->redn[parity][3];
         parity ^= 1;             // the next call writes the other buffer: whoever reaches it has passed a barrier behind every lane's reads of this one
     }
+    // the workgroup's sum of one integer alone: reduce() with no doubles, so the same barrier and the same parity flip
+    __device__ int count(int n)
+    {
+        double none[1];
+        reduce(none, 0, &n);
+        return n;
+    }
 };
 
 }  // namespace olf

@@ -12,7 +12,7 @@ The random stream is the caller's: draws [n_pairs, max_iteratio
 resumed call reads on.  Tcw of the state is what ORBmatcher's search_by_projection_kf_pairs takes as the candidate's own pose."""
 import ctypes as C
 import numpy as np
-from . import _lib
+from . import _lib, _ransac
 from ._lib import lib, ptr
 from .matcher import _call_dev, _ctx, _dev
 
@@ -22,7 +22,6 @@ _STATE = (("iterations_done", np.int32, ()), ("best_inliers", np.int32, ()), ("b
           ("refined_inliers", np.int32, ()), ("refined_Tcw", np.float32, (16,)), ("refined_flags", np.uint8, None), ("accepted", np.int32, ()),
           ("no_more", np.int32, ()), ("n_inliers", np.int32, ()), ("inliers", np.uint8, None), ("Tcw", np.float32, (16,)), ("n_correspondences", np.int32, ()),
           ("counts", np.int32, None))
-_ROWS = ("best_flags", "refined_flags", "inliers")
 
 
 def pnp_ransac(probability=0.99, min_inliers=10, max_iterations=300, min_set=4, epsilon=0.5, th2=5.991, n_iterations=5):
@@ -37,30 +36,16 @@ def pnp_ransac(probability=0.99, min_inliers=10, max_iterations=300, min_set=4, 
 def pnp_state(n_pairs, capacity, max_iterations, device=True, counts=True):
     """The arrays of olf_pnp_solver_io for n_pairs new solvers, all zero, as a dict: device tensors (device=True) or numpy arrays.  counts=False leaves the
     per-iteration counts out."""
-    st = {}
-    for name, dt, tail in _STATE:
-        if name == "counts" and not counts:
-            st[name] = None
-            continue
-        shape = (n_pairs,) + ((capacity,) if name in _ROWS else (max_iterations,) if name == "counts" else tail)
-        if device:
-            import torch
-            st[name] = torch.zeros(shape, dtype=getattr(torch, np.dtype(dt).name), device="cuda")
-        else:
-            st[name] = np.zeros(shape, dt)
-    return st
+    return _ransac.new_state(_STATE, n_pairs, capacity, max_iterations, device, counts)
 
 
 def _io(st, address, row=None):
-    io = _lib.PnpSolverIoC()
-    for name, _, _ in _STATE:
-        setattr(io, name, address(st[name] if row is None or st[name] is None else st[name][row], name))
-    return io
+    return _ransac.io_block(_lib.PnpSolverIoC, _STATE, st, address, row)
 
 
 def pnp_draws(n_pairs, max_iterations, seed):
     """[n_pairs, max_iterations, 4] uint32 values below 2^31, as rand() returns them"""
-    return np.random.default_rng(seed).integers(0, 1 << 31, size=(n_pairs, max_iterations, 4), dtype=np.uint32)
+    return _ransac.draws(n_pairs, max_iterations, 4, seed)
 
 
 def _dev_batch(kps, counts, mp_world, camera, mp_valid, img_stride):
@@ -107,32 +92,18 @@ def pnp_apply_inliers(n_frames, counts, pairs, matches, state, out=None, cur_val
     return out, cur_valid, already_found
 
 
-def _host_batch(kps, counts, mp_world, camera, mp_valid, img_stride):
-    kps = np.ascontiguousarray(kps, dtype=_lib.KEYPOINT_DTYPE)
-    world = np.ascontiguousarray(mp_world, dtype=np.float32)
-    n_frames, cap = world.shape[0], world.shape[1]
-    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
-    if kps.shape != (n_frames * img_stride, cap) or counts.shape[0] != n_frames * img_stride or world.shape != (n_frames, cap, 3):
-        raise ValueError("kps [n_frames * img_stride, capacity], counts and mp_world [n_frames, capacity, 3] expected")
-    valid = None if mp_valid is None else np.ascontiguousarray(mp_valid, dtype=np.uint8)
-    tb = _lib.TrackBatchC()
-    tb.kps, tb.counts, tb.img_stride, tb.mp_world, tb.mp_valid = ptr(kps), ptr(counts), int(img_stride), ptr(world), ptr(valid)
-    tb.fx, tb.fy, tb.cx, tb.cy = (float(v) for v in camera)
-    return tb, n_frames, cap, (kps, counts, world, valid)
-
-
 def PnPSolve(kps, counts, mp_world, camera, scale_factors, pair, matches, draws, state, ransac, row=0, mp_valid=None, mp_bad=None, img_stride=1):
     """One iterate(n_iterations) of one PnPsolver from host arrays, no device: olf_pnp_solver.  pair = (key frame, frame); matches [capacity]; draws
     [max_iterations, 4]; state: pnp_state(..., device=False), whose row `row` is this solver's and is changed in place.  Returns the status bits (256 an
     octave outside the levels, 2048 a refused pair, 32768 a degenerate hypothesis)."""
-    tb, n_frames, cap, keep = _host_batch(kps, counts, mp_world, camera, mp_valid, img_stride)
+    tb, n_frames, cap, keep = _ransac.host_batch(kps, counts, mp_world, camera, mp_valid, img_stride)
     m = np.ascontiguousarray(matches, dtype=np.int32).reshape(-1)
     dr = np.ascontiguousarray(draws, dtype=np.uint32).reshape(-1)
     sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
     bad = None if mp_bad is None else np.ascontiguousarray(mp_bad, dtype=np.uint8)
     if m.shape[0] != cap or dr.shape[0] < 4 * ransac.max_iterations:
         raise ValueError("PnPSolve: matches [capacity] and draws [max_iterations, 4] expected")
-    io = _io(state, lambda a, name: None if a is None else a.ctypes.data, row=slice(row, row + 1))
+    io = _io(state, _ransac.host_address, row=slice(row, row + 1))
     status = C.c_int32(0)
     _lib.check(lib().olf_pnp_solver(C.byref(tb), cap, n_frames, ptr(bad), ptr(sf), sf.shape[0], int(pair[0]), int(pair[1]), ptr(m), C.byref(ransac), ptr(dr),
                                     C.byref(io), C.addressof(status)), "olf_pnp_solver")
@@ -143,7 +114,7 @@ def pnp_solver_pairs(kps, counts, mp_world, camera, pairs, matches, draws, state
     """The batch from host arrays ON THE DEVICE: olf_pnp_solver_pairs (stages, runs the kernel, synchronises).  Shapes as pnp_solver_batch; state:
     pnp_state(..., device=False), changed in place.  A set status bit raises OlfError with the outputs complete."""
     ctx = _ctx(context)
-    tb, n_frames, cap, keep = _host_batch(kps, counts, mp_world, camera, mp_valid, img_stride)
+    tb, n_frames, cap, keep = _ransac.host_batch(kps, counts, mp_world, camera, mp_valid, img_stride)
     pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
     m = np.ascontiguousarray(matches, dtype=np.int32)
     dr = np.ascontiguousarray(draws, dtype=np.uint32)
@@ -151,7 +122,7 @@ def pnp_solver_pairs(kps, counts, mp_world, camera, pairs, matches, draws, state
     n_pairs = pairs.shape[0]
     if cap != ctx.orb_capacity or m.shape != (n_pairs, cap) or dr.size != 4 * n_pairs * ransac.max_iterations:
         raise ValueError("pnp_solver_pairs: planes of the context's capacity, matches [n_pairs, capacity] and draws [n_pairs, max_iterations, 4] expected")
-    io = _io(state, lambda a, name: None if a is None else a.ctypes.data)
+    io = _io(state, _ransac.host_address)
     _lib.check(lib().olf_pnp_solver_pairs(ctx.handle, C.byref(tb), n_frames, ptr(bad), n_pairs, ptr(pairs), ptr(m), C.byref(ransac), ptr(dr), C.byref(io)),
                "olf_pnp_solver_pairs")
     return state

@@ -12,7 +12,7 @@ The random stream is the caller's: draws [n_pairs, max_iteratio
 best_s / best_R / best_t of the state are what ORBmatcher.search_by_sim3_pairs takes as s12 / R12 / t12."""
 import ctypes as C
 import numpy as np
-from . import _lib
+from . import _lib, _ransac
 from ._lib import lib, ptr
 from .matcher import _call_dev, _ctx, _dev
 
@@ -33,30 +33,16 @@ def sim3_ransac(fix_scale=False, probability=0.99, min_inliers=20, max_iteration
 def sim3_state(n_pairs, capacity, max_iterations, device=True, counts=True):
     """The arrays of olf_sim3_solver_io for n_pairs new solvers, all zero, as a dict: device tensors (device=True) or numpy arrays.  counts=False leaves the
     per-iteration counts out."""
-    st = {}
-    for name, dt, tail in _STATE:
-        if name == "counts" and not counts:
-            st[name] = None
-            continue
-        shape = (n_pairs,) + ((capacity,) if name == "inliers" else (max_iterations,) if name == "counts" else tail)
-        if device:
-            import torch
-            st[name] = torch.zeros(shape, dtype=getattr(torch, np.dtype(dt).name), device="cuda")
-        else:
-            st[name] = np.zeros(shape, dt)
-    return st
+    return _ransac.new_state(_STATE, n_pairs, capacity, max_iterations, device, counts)
 
 
 def _io(st, address, row=None):
-    io = _lib.Sim3SolverIoC()
-    for name, _, _ in _STATE:
-        setattr(io, name, address(st[name] if row is None or st[name] is None else st[name][row], name))
-    return io
+    return _ransac.io_block(_lib.Sim3SolverIoC, _STATE, st, address, row)
 
 
 def sim3_draws(n_pairs, max_iterations, seed):
     """[n_pairs, max_iterations, 3] uint32 values below 2^31, as rand() returns them"""
-    return np.random.default_rng(seed).integers(0, 1 << 31, size=(n_pairs, max_iterations, 3), dtype=np.uint32)
+    return _ransac.draws(n_pairs, max_iterations, 3, seed)
 
 
 def sim3_solver_batch(n_frames, kps, counts, Tcw, mp_world, camera, pairs, matches12, draws, state, ransac, mp_valid=None, mp_bad=None, img_stride=2,
@@ -93,18 +79,7 @@ def sim3_filter_matches(matches12, inliers, n_inliers=None, out=None, context=No
 
 
 def _host_batch(kps, counts, Tcw, mp_world, camera, mp_valid, img_stride):
-    kps = np.ascontiguousarray(kps, dtype=_lib.KEYPOINT_DTYPE)
-    world = np.ascontiguousarray(mp_world, dtype=np.float32)
-    n_frames, cap = world.shape[0], world.shape[1]
-    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
-    Tcw = np.ascontiguousarray(Tcw, dtype=np.float32)
-    if kps.shape != (n_frames * img_stride, cap) or counts.shape[0] != n_frames * img_stride or Tcw.size != 16 * n_frames or world.shape != (n_frames, cap, 3):
-        raise ValueError("kps [n_frames * img_stride, capacity], counts, Tcw [n_frames, 4, 4] and mp_world [n_frames, capacity, 3] expected")
-    valid = None if mp_valid is None else np.ascontiguousarray(mp_valid, dtype=np.uint8)
-    tb = _lib.TrackBatchC()
-    tb.kps, tb.counts, tb.img_stride, tb.Tcw, tb.mp_world, tb.mp_valid = ptr(kps), ptr(counts), int(img_stride), ptr(Tcw), ptr(world), ptr(valid)
-    tb.fx, tb.fy, tb.cx, tb.cy = (float(v) for v in camera)
-    return tb, n_frames, cap, (kps, counts, Tcw, world, valid)
+    return _ransac.host_batch(kps, counts, mp_world, camera, mp_valid, img_stride, Tcw=Tcw)
 
 
 def Sim3Solve(kps, counts, Tcw, mp_world, camera, scale_factors, pair, matches12, draws, state, ransac, row=0, mp_valid=None, mp_bad=None, img_stride=1):
@@ -118,7 +93,7 @@ def Sim3Solve(kps, counts, Tcw, mp_world, camera, scale_factors, pair, matches12
     bad = None if mp_bad is None else np.ascontiguousarray(mp_bad, dtype=np.uint8)
     if m12.shape[0] != cap or dr.shape[0] < 3 * ransac.max_iterations:
         raise ValueError("Sim3Solve: matches12 [capacity] and draws [max_iterations, 3] expected")
-    io = _io(state, lambda a, name: None if a is None else a.ctypes.data, row=slice(row, row + 1))
+    io = _io(state, _ransac.host_address, row=slice(row, row + 1))
     status = C.c_int32(0)
     _lib.check(lib().olf_sim3_solver(C.byref(tb), cap, n_frames, ptr(bad), ptr(sf), sf.shape[0], int(pair[0]), int(pair[1]), ptr(m12), C.byref(ransac), ptr(dr),
                                      C.byref(io), C.addressof(status)), "olf_sim3_solver")
@@ -137,7 +112,7 @@ def sim3_solver_pairs(kps, counts, Tcw, mp_world, camera, pairs, matches12, draw
     n_pairs = pairs.shape[0]
     if cap != ctx.orb_capacity or m12.shape != (n_pairs, cap) or dr.size != 3 * n_pairs * ransac.max_iterations:
         raise ValueError("sim3_solver_pairs: planes of the context's capacity, matches12 [n_pairs, capacity] and draws [n_pairs, max_iterations, 3] expected")
-    io = _io(state, lambda a, name: None if a is None else a.ctypes.data)
+    io = _io(state, _ransac.host_address)
     _lib.check(lib().olf_sim3_solver_pairs(ctx.handle, C.byref(tb), n_frames, ptr(bad), n_pairs, ptr(pairs), ptr(m12), C.byref(ransac), ptr(dr), C.byref(io)),
                "olf_sim3_solver_pairs")
     return state

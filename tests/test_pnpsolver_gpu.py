@@ -301,3 +301,20 @@ def test_adaptor_on_the_device(tmp_path):
     build_adaptor(exe)
     out = subprocess.run([exe, "device"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
     assert out.returncode == 0 and b"ADAPTOR_PNPSOLVER_OK" in out.stdout, out.stdout.decode()[-3000:]
+
+
+def test_more_parameter_sets_than_the_table_cache_keeps(ctx):
+    """Ten distinct (probability, min_inliers, max_iterations) through olf_pnp_solver_pairs_dev in one process, the first once more at the end: the host
+    table cache keeps eight, so tables are evicted, their pinned buffers refilled and the first set's table built again.  Each call against the host form,
+    on four small pairs (11, 21, 63 and 40 correspondences); the effective min_inliers and the cap of a pair are read from the table."""
+    sc = S.scene_set()
+    P, order = len(sc.pairs), [5, 8, 10, 16]
+    sets = [(0.99, 10, 40), (0.9, 10, 40), (0.99, 9, 40), (0.99, 10, 39), (0.5, 12, 16), (0.999, 11, 40), (0.95, 5, 7), (0.8, 20, 30), (0.99, 4, 1), (0.7, 12, 25)]
+    assert len(set(sets)) == 10
+    for pr, m, mx in sets + sets[:1]:
+        rn = ransac(False, probability=pr, min_inliers=m, max_iterations=mx)
+        host = fresh_state(P, sc.cap, mx)
+        host_call(sc, host, rn, only=set(order))
+        dev = device_call(ctx, sc, fresh_state(P, sc.cap, mx), rn, order=order)
+        same_state({k: v[order] for k, v in dev.items()}, {k: v[order] for k, v in host.items()})
+    ctx.poll_status()

@@ -270,3 +270,20 @@ def test_host_form_under_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     assert "sim3solver_host_main ok" in r.stdout
+
+
+def test_ransac_sample_equals_the_literal_procedure(tmp_path):
+    """tests/ransac_sample_main.cpp: ransac_sample<3> (this solver's sample) and ransac_sample<4> (PnPsolver's) of csrc/ransac_terms.hpp against the
+    literal array procedure, for every N from K to 9 and every tuple of positions, bit 31 of a draw included; built as the host form above is (without
+    the sanitizers where the machine has no runtime for them)"""
+    tmp = str(tmp_path)
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if _san_probe(tmp) else []
+    exe = os.path.join(tmp, "ransac_sample_main")
+    csrc = os.path.join(ROOT, "orb_line_slam_amd", "csrc")
+    cmd = ["g++", "-std=c++17", "-O1", "-g"] + san + ["-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + csrc,
+                                                      os.path.join(ROOT, "tests", "ransac_sample_main.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    assert "ransac_sample_main ok" in r.stdout

@@ -308,3 +308,21 @@ def test_adaptor_on_the_device(tmp_path):
     build_adaptor(exe)
     out = subprocess.run([exe, "device"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
     assert out.returncode == 0 and b"ADAPTOR_SIM3SOLVER_OK" in out.stdout, out.stdout.decode()[-3000:]
+
+
+def test_more_parameter_sets_than_the_table_cache_keeps(ctx):
+    """Ten distinct (probability, min_inliers, max_iterations) through olf_sim3_solver_pairs_dev in one process, the first once more at the end: the host
+    table cache keeps eight, so tables are evicted, their pinned buffers refilled and the first set's table built again.  Each call against the host form,
+    on four small pairs; pair 10 (40 correspondences, never accepted) ends exactly at its set's cap, which is read from the table."""
+    sc = S.scene_set(False, ctx.orb_capacity)
+    P, order = len(sc.pairs), [3, 4, 5, 10]
+    sets = [(0.99, 20, 300), (0.9, 20, 300), (0.99, 19, 300), (0.99, 20, 299), (0.5, 10, 64), (0.999, 21, 300), (0.95, 5, 7), (0.8, 30, 120), (0.99, 3, 1),
+            (0.7, 12, 200)]
+    assert len(set(sets)) == 10
+    for pr, m, mx in sets + sets[:1]:
+        rn = sim3solver.sim3_ransac(sc.fix_scale, pr, m, mx, mx)
+        host = fresh_state(len(order), sc.cap, mx)
+        host_call(sc, host, rn, pairs=[sc.pairs[p] for p in order], rows=[sc.rows[p] for p in order], draws=sc.draws[order])
+        dev = device_call(ctx, sc, fresh_state(P, sc.cap, mx), rn, order=order)
+        same_state({k: v[order] for k, v in dev.items()}, host)
+    ctx.poll_status()
