@@ -1103,6 +1103,113 @@ int olf_create_new_map_points_pairs(olf_ctx* ctx, const olf_track_batch* in, int
 int olf_update_normal_and_depth_points(olf_ctx* ctx, const olf_map_graph* g, const olf_cull_view* v, int n_points, const int32_t* points, const float* mp_world,
                                        const int32_t* mp_ref_kf, const float* kf_Ow, float* normal, float* maxd, float* mind);
 
+/* ---- Tracking::NeedNewKeyFrame and the three producers of stereo landmarks for a batch on the device (csrc/keyframe_batch.hip) --------------------------
+ * Which stereo features of a frame get a new map point or map line, in which order, and what the new landmark holds -- the loops of
+ *   OLF_LANDMARKS_INIT       Tracking::StereoInitialization (src/Tracking.cc:639-677): every point with z > 0 and every line whose two disparities are
+ *                            > 0, in index order; no sort, held entries are not consulted
+ *   OLF_LANDMARKS_KEYFRAME   Tracking::CreateNewKeyFrame (:1744-1865)
+ *   OLF_LANDMARKS_LASTFRAME  Tracking::UpdateLastFrame (:1092-1204), with its early return: a frame without a stereo point visits no line (:1105-1106)
+ * for n_frames device-resident frames; frame j = image j * img_stride of kps / counts / kls / lcounts (as olf_track_batch and olf_line_batch), every other
+ * plane is per frame.  Each frame is answered on its own, from the arrays as they stand (a snapshot answer).
+ * The two sorted modes: vDepthIdx holds (z, i) for the points with z > 0 (:1749-1756), for the lines (max(sz, ez), i) with sz = mbf / disparity in float
+ * unless sz < 0 || ez < 0 (:1806-1813: a disparity of -1 or -0.0f is skipped, +0.0f gives +inf and is kept); std::sort by pair's operator<, a total
+ * order, so the result is the order of the 64-bit keys (bits of z << 32 | i); the walk visits entries until the first one with z > thDepth once more
+ * than 100 (lines: 50) have been visited (:1796, :1862: the test comes after the visit and nPoints counts both branches), i.e. the first
+ * min(n, max(nClose, 100) + 1) entries, nClose = the number of entries with !(z > thDepth).  A visited feature gets a new landmark when it holds none or
+ * one with Observations() < 1 (:1769-1776, :1119-1125).
+ * The new landmarks.  Points: mp_world = Frame::UnprojectStereo, the routine of olf_unproject_stereo_dev on Twc (rows of mRwc | mOw).  mp_normal,
+ * mp_maxd, mp_mind with Ow = column 3 of Twc: in LASTFRAME mode the constructor MapPoint(Pos, pMap, pFrame, idxF) (src/MapPoint.cc:58-83): normal =
+ * (Pos - Ow) * (float)(1.0 / cv::norm) (C.17); in the other two modes MapPoint::UpdateNormalAndDepth of a point with the one observation (zeros + that
+ * vector, times (float)(1.0 / 1): a -0 component becomes +0; a caller who wants the key frame's own camera centre passes Twc = [Rcw.t() | Ow] of
+ * KeyFrame::SetPose).  mfMaxDistance = (float)cv::norm(Pos - Ow) * mvScaleFactors[octave], mfMinDistance = mfMaxDistance / mvScaleFactors[nLevels - 1].
+ * Lines: Frame::backProjection (src/Frame.cc:1089-1098) of both endpoints in double (C.29): bd = (double)mb / (double)disp with mb the float mbf / fx;
+ * P = (bd * (u - cx), bd * (v - cy), bd * fx) with the floats widened; Rwc * P + Ow summed over k ascending, without contraction.  ml_world_d holds the
+ * doubles, ml_world their Converter::toCvMat (one rounding to float), the layout of olf_local_line_map.world.
+ * Outputs per frame j (all planes are written for every feature slot of the frame, whatever the count):
+ *   n_visited [2], n_created [2]       points, lines: the final nPoints / nLines (INIT: the number created) and the number of new landmarks
+ *   visit_order, visit_order_l         feature indices in visit order, -1 past the end
+ *   created_order, created_order_l     the created subset in visit order (the order of mnId and of mlpTemporalPoints / mlpTemporalLines), -1 past the end
+ *   created, created_l                 1 where a landmark was created, by feature index: mp_valid of olf_track_batch for the temporal points
+ *   frame_mp_out, frame_ml_out         mvpMapPoints / mvpMapLines after the loop: new_base[j] + k for the k-th created of the frame (new_base_* NULL:
+ *                                      n_mp / n_ml), the input entry elsewhere (-1 where frame_mp / frame_ml is NULL)
+ *   mp_world, mp_normal [.][3], mp_maxd, mp_mind; ml_world_d (or NULL), ml_world [.][6]      by feature index, zeros where nothing was created
+ *   status                             the frame's own word: 1 a line depth that is NaN (std::sort is undefined there: the frame's line outputs are
+ *                                      empty); 2 a held index >= n_mp / n_ml (treated as NULL); 4 a created point whose octave is outside the
+ *                                      context's levels (maxd = mind = 0)
+ * A count beyond the capacity is read as the capacity.  frame_mp / frame_ml NULL: nothing is held; mp_nobs / ml_nobs (Observations()) are read only for
+ * held entries.  n_frames == 0 writes nothing.  Contexts above OLF_GRID_MAX_KEYS key points or key lines: OLF_ERR_CAPACITY; a NULL required pointer,
+ * n_frames < 0, img_stride < 1, n_mp or n_ml < 0 or an unknown mode: OLF_ERR_INVALID.  Does not synchronise; runs on `stream`; no scratch; the context's
+ * status word is not touched.  Results do not depend on scheduling. */
+enum { OLF_LANDMARKS_INIT = 0, OLF_LANDMARKS_KEYFRAME = 1, OLF_LANDMARKS_LASTFRAME = 2 };
+typedef struct olf_landmarks_batch {
+    const olf_keypoint* kps; const int32_t* counts;      /* mvKeysUn, N                                                   */
+    const olf_keyline*  kls; const int32_t* lcounts;     /* mvKeysUn_Line, N_l                                            */
+    int32_t img_stride;
+    const float*   depth;          /* [n_frames][capacity] mvDepth                                                       */
+    const float*   ldisp;          /* [n_frames][line capacity][2] mvDisparity_l                                         */
+    const float*   Twc;            /* [n_frames][16] rows of mRwc | mOw (olf_unproject_stereo_dev)                        */
+    const int32_t* frame_mp;       /* [n_frames][capacity] mvpMapPoints as map indices, negative = NULL; or NULL         */
+    const int32_t* frame_ml;       /* [n_frames][line capacity] mvpMapLines; or NULL                                      */
+    const int32_t* mp_nobs; int32_t n_mp;                /* Observations() of the n_mp map points                         */
+    const int32_t* ml_nobs; int32_t n_ml;
+    const int32_t* new_base_mp;    /* [n_frames] index of the frame's first new point; NULL: n_mp for every frame         */
+    const int32_t* new_base_ml;    /* [n_frames]; NULL: n_ml                                                               */
+    float fx, fy, cx, cy, mbf, thDepth;
+} olf_landmarks_batch;
+typedef struct olf_landmarks_outputs {
+    int32_t* n_visited; int32_t* n_created;              /* [n_frames][2]                                                  */
+    int32_t* visit_order; int32_t* visit_order_l;        /* [n_frames][capacity], [n_frames][line capacity]                */
+    int32_t* created_order; int32_t* created_order_l;
+    uint8_t* created; uint8_t* created_l;
+    int32_t* frame_mp_out; int32_t* frame_ml_out;
+    float* mp_world; float* mp_normal; float* mp_maxd; float* mp_mind;
+    double* ml_world_d; float* ml_world;                 /* ml_world_d may be NULL                                         */
+    int32_t* status;                                     /* [n_frames]                                                     */
+} olf_landmarks_outputs;
+int olf_stereo_landmarks_batch_dev(olf_ctx* ctx, const olf_landmarks_batch* in, int n_frames, int mode, const olf_landmarks_outputs* out, void* stream);
+/* the host form: host pointers, no context and no device; capacity / line_capacity: the row lengths of the per-frame planes (at most OLF_GRID_MAX_KEYS);
+ * scale_factors [n_levels] = mvScaleFactors, 1 <= n_levels <= OLF_MAX_LEVELS.  The same text (csrc/keyframe_terms.hpp). */
+int olf_stereo_landmarks(const olf_landmarks_batch* in, int capacity, int line_capacity, int n_frames, int mode, const float* scale_factors, int n_levels,
+                         const olf_landmarks_outputs* out);
+/* bool Tracking::NeedNewKeyFrame() (src/Tracking.cc:1606-1725) for n_frames frames.  The four counts of :1632-1667 come from the frame's planes: a point
+ * with 0 < mvDepth < thDepth is tracked when it holds a map point and is no outlier, else untracked; a line with minz > 0 && maxz < thDepth (minz, maxz =
+ * the ordered mbf / disparity of its endpoints, in float) likewise.  The line loop reads mLastFrame.mvDisparity_l[i] for i < mCurrentFrame.N_l
+ * (:1651-1652, as written): row j reads the disparities of frame ldisp_frame[j] (NULL: j itself; the reference as written: j - 1).  An i at or beyond
+ * that frame's line count -- where the reference reads out of bounds -- is not counted and sets bit 1 of the row's status; so is every line when
+ * ldisp_frame[j] is outside [0, n_frames).  A monocular row counts nothing (:1637).
+ * The decision (:1609-1724) is one function of csrc/keyframe_terms.hpp in the reference's types: frame ids are unsigned, mnLastKeyFrameId + mMaxFrames
+ * wraps at 32 bits; mnMatchesInliers < nRefMatches * 0.25 compares in double, mnMatchesInliers < nRefMatches * thRefRatio in float.  rows [n_frames][11]
+ * (int32): mnId, mnLastKeyFrameId, mnLastRelocFrameId, mMinFrames, mMaxFrames, nKFs (KeyFramesInMap()), bLocalMappingIdle (AcceptKeyFrames()),
+ * KeyframesInQueue(), mbOnlyTracking, stopped (isStopped() || stopRequested()), monocular.  n_ref_matches, n_ref_matches_l [n_frames]: the outputs of
+ * olf_tracked_map_points_batch_dev as they are (no reference key frame: 0); n_inliers [n_frames][2]: that of olf_pose_outputs as it is
+ * (mnMatchesInliers, mnMatchesInliers_l).
+ * Outputs per frame: need (the return value), interrupt_ba (1: InterruptBA() was called, :1711), counts [4] = nTrackedClose, nNonTrackedClose,
+ * nTrackedClose_l, nNonTrackedClose_l; conditions = c1a | c1b << 1 | c1c << 2 | c1c_l << 3 | c2 << 4 | c2_l << 5 (0 when an early return came first);
+ * status.  outlier / outlier_l NULL: none; frame_mp / frame_ml NULL: nothing is held (any value >= 0 counts as held).  A count beyond the capacity is
+ * read as the capacity.  n_frames == 0 writes nothing; a NULL required pointer, n_frames < 0 or img_stride < 1: OLF_ERR_INVALID; contexts above
+ * OLF_GRID_MAX_KEYS: OLF_ERR_CAPACITY.  Does not synchronise; runs on `stream`; no scratch. */
+#define OLF_KEYFRAME_ROW 11
+typedef struct olf_keyframe_test_batch {
+    const int32_t* counts; const int32_t* lcounts; int32_t img_stride;      /* N, N_l                                    */
+    const float*   depth;  const int32_t* frame_mp; const uint8_t* outlier;       /* mvDepth, mvpMapPoints, mvbOutlier          */
+    const float*   ldisp;  const int32_t* frame_ml; const uint8_t* outlier_l;     /* mvDisparity_l, mvpMapLines, mvbOutlier_Line */
+    const int32_t* ldisp_frame;
+    const int32_t* rows; const int32_t* n_ref_matches; const int32_t* n_ref_matches_l; const int32_t* n_inliers;
+    float mbf, thDepth;
+} olf_keyframe_test_batch;
+typedef struct olf_keyframe_test_outputs {
+    uint8_t* need; uint8_t* interrupt_ba;                /* [n_frames]                                                      */
+    int32_t* counts;                                     /* [n_frames][4]                                                   */
+    int32_t* conditions; int32_t* status;                /* [n_frames]                                                      */
+} olf_keyframe_test_outputs;
+int olf_need_new_keyframe_batch_dev(olf_ctx* ctx, const olf_keyframe_test_batch* in, int n_frames, const olf_keyframe_test_outputs* out, void* stream);
+/* the host form: host pointers, no context and no device; capacity / line_capacity: the row lengths of the per-frame planes */
+int olf_need_new_keyframe(const olf_keyframe_test_batch* in, int capacity, int line_capacity, int n_frames, const olf_keyframe_test_outputs* out);
+/* The two device entries from host pointers ON THE DEVICE (csrc/keyframe_api.cpp): the arrays are staged, the same kernels run on the context's stream,
+ * the outputs come back; synchronises.  The planes are [n_frames * img_stride] or [n_frames] rows of the context's capacities. */
+int olf_stereo_landmarks_frames(olf_ctx* ctx, const olf_landmarks_batch* in, int n_frames, int mode, const olf_landmarks_outputs* out);
+int olf_need_new_keyframe_frames(olf_ctx* ctx, const olf_keyframe_test_batch* in, int n_frames, const olf_keyframe_test_outputs* out);
+
 /* ---- Sim3Solver's RANSAC for a list of key-frame pairs on the device (csrc/sim3solver_batch.hip) ------------------------------------------------------
  * Sim3Solver (src/Sim3Solver.cc, include/Sim3Solver.h) as LoopClosing::ComputeSim3 drives it per candidate (src/LoopClosing.cc:280-307): the constructor's
  * correspondences, SetRansacParameters(probability, min_inliers, max_iterations) and one iterate(n_iterations, ...) per call, for n_pairs pairs of the

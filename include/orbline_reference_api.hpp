@@ -1746,4 +1746,141 @@ void PnPsolversIterate(olf_ctx* c, const std::vector<PnPsolverOf<FrameT, MapPoin
     }
 }
 
+// ---- the landmark loops of Tracking::StereoInitialization, CreateNewKeyFrame and UpdateLastFrame, and Tracking::NeedNewKeyFrame, over the reference's types ----
+// What the three loops decide for one frame, through the host form (olf_stereo_landmarks, no context and no device): which features are visited and which
+// get a new MapPoint / MapLine, in the reference's order, with the new landmark's geometry.  Creating the objects (new MapPoint, AddObservation,
+// AddMapPoint, ComputeDistinctiveDescriptors, mlpTemporalPoints.push_back) stays the caller's, in the order of `created` / `created_l`.
+struct StereoLandmarks {
+    int nPoints = 0, nLines = 0;                  // the final counters of the two loops
+    std::vector<int> visited, created;            // feature indices in visit order; the created subset in creation order (the order of mnId)
+    std::vector<int> visited_l, created_l;
+    std::vector<float> world, normal;             // [3 k ..]: mWorldPos and mNormalVector of the k-th created point
+    std::vector<float> maxd, mind;                // [k]: mfMaxDistance, mfMinDistance
+    std::vector<double> world_l;                  // [6 k ..]: sp3D, ep3D of the k-th created line (Frame::backProjection)
+    int32_t status = 0;                           // 1 a NaN line depth (no line visited), 4 an octave outside mvScaleFactors
+};
+namespace olf_detail {
+// Reads N, N_l, mvKeysUn, mvKeysUn_Line, mvDepth, mvDisparity_l, mvpMapPoints / mvpMapLines with Observations(), mRwc, mOw, fx, fy, cx, cy, mbf and
+// mvScaleFactors of the frame.
+template <class FrameT>
+StereoLandmarks stereo_landmarks(FrameT& F, int mode, float mThDepth)
+{
+    typedef typename std::remove_reference<decltype(F.mvKeysUn[0])>::type KP;
+    typedef typename std::remove_reference<decltype(F.mvKeysUn_Line[0])>::type KL;
+    static_assert(sizeof(KP) == sizeof(olf_keypoint) && sizeof(KL) == sizeof(olf_keyline), "cv::KeyPoint / KeyLine layout");
+    const int N = (int)F.N, Nl = (int)F.N_l;
+    if (N > OLF_GRID_MAX_KEYS || Nl > OLF_GRID_MAX_KEYS) check(OLF_ERR_CAPACITY, "stereo_landmarks: more than OLF_GRID_MAX_KEYS features");
+    const size_t cap = (size_t)N + 1, lcap = (size_t)Nl + 1;
+    std::vector<float> depth(cap, -1.f), ldisp(2 * lcap, -1.f);
+    std::vector<int32_t> fmp(cap, -1), fml(lcap, -1), nobs, lnobs;
+    for (int i = 0; i < N; ++i) {
+        depth[i] = F.mvDepth[i];
+        if (F.mvpMapPoints[i]) { fmp[i] = (int32_t)nobs.size(); nobs.push_back((int32_t)F.mvpMapPoints[i]->Observations()); }
+    }
+    for (int i = 0; i < Nl; ++i) {
+        ldisp[2 * i] = F.mvDisparity_l[i].first; ldisp[2 * i + 1] = F.mvDisparity_l[i].second;
+        if (F.mvpMapLines[i]) { fml[i] = (int32_t)lnobs.size(); lnobs.push_back((int32_t)F.mvpMapLines[i]->Observations()); }
+    }
+    std::vector<olf_keypoint> kps(cap);
+    std::vector<olf_keyline> kls(lcap);
+    if (N) std::memcpy(kps.data(), F.mvKeysUn.data(), (size_t)N * sizeof(olf_keypoint));
+    if (Nl) std::memcpy(kls.data(), F.mvKeysUn_Line.data(), (size_t)Nl * sizeof(olf_keyline));
+    float Twc[16] = {0};
+    for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) Twc[4 * r + k] = F.mRwc.template at<float>(r, k); Twc[4 * r + 3] = F.mOw.template at<float>(r); }
+    Twc[15] = 1.f;
+    nobs.push_back(0); lnobs.push_back(0);                           // (an array without entries keeps an address)
+    const int32_t counts[1] = {N}, lcounts[1] = {Nl};
+    olf_landmarks_batch in;
+    std::memset(&in, 0, sizeof(in));
+    in.kps = kps.data(); in.counts = counts; in.kls = kls.data(); in.lcounts = lcounts; in.img_stride = 1;
+    in.depth = depth.data(); in.ldisp = ldisp.data(); in.Twc = Twc; in.frame_mp = fmp.data(); in.frame_ml = fml.data();
+    in.mp_nobs = nobs.data(); in.n_mp = (int32_t)nobs.size() - 1; in.ml_nobs = lnobs.data(); in.n_ml = (int32_t)lnobs.size() - 1;
+    in.fx = F.fx; in.fy = F.fy; in.cx = F.cx; in.cy = F.cy; in.mbf = F.mbf; in.thDepth = mThDepth;
+    int32_t nv[2], nc[2], st = 0;
+    std::vector<int32_t> vo(cap), vl(lcap), co(cap), cl(lcap), fo(cap), fl(lcap);
+    std::vector<uint8_t> cr(cap), crl(lcap);
+    std::vector<float> w(3 * cap), nr(3 * cap), mx(cap), mn(cap), lw(6 * lcap);
+    std::vector<double> lwd(6 * lcap);
+    const olf_landmarks_outputs o = {nv, nc, vo.data(), vl.data(), co.data(), cl.data(), cr.data(), crl.data(), fo.data(), fl.data(), w.data(), nr.data(), mx.data(),
+                                     mn.data(), lwd.data(), lw.data(), &st};
+    check(olf_stereo_landmarks(&in, (int)cap, (int)lcap, 1, mode, F.mvScaleFactors.data(), (int)F.mvScaleFactors.size(), &o), "olf_stereo_landmarks");
+    StereoLandmarks R;
+    R.nPoints = nv[0]; R.nLines = nv[1]; R.status = st;
+    for (int q = 0; q < N && vo[q] >= 0; ++q) R.visited.push_back(vo[q]);
+    for (int q = 0; q < Nl && vl[q] >= 0; ++q) R.visited_l.push_back(vl[q]);
+    for (int k = 0; k < nc[0]; ++k) {
+        const int i = co[k];
+        R.created.push_back(i);
+        for (int c = 0; c < 3; ++c) { R.world.push_back(w[3 * i + c]); R.normal.push_back(nr[3 * i + c]); }
+        R.maxd.push_back(mx[i]); R.mind.push_back(mn[i]);
+    }
+    for (int k = 0; k < nc[1]; ++k) {
+        const int i = cl[k];
+        R.created_l.push_back(i);
+        for (int c = 0; c < 6; ++c) R.world_l.push_back(lwd[6 * i + c]);
+    }
+    return R;
+}
+}  // namespace olf_detail
+
+// the loops `for(int i=0; i<mCurrentFrame.N;i++)` and `for(int i=0; i<mCurrentFrame.N_l; ++i)` of Tracking::StereoInitialization, src/Tracking.cc:639-677
+template <class FrameT> StereoLandmarks StereoInitializationLandmarks(FrameT& mCurrentFrame) { return olf_detail::stereo_landmarks(mCurrentFrame, OLF_LANDMARKS_INIT, 0.f); }
+// the two sorted loops of void Tracking::CreateNewKeyFrame(), src/Tracking.cc:1744-1865
+template <class FrameT> StereoLandmarks CreateNewKeyFrameLandmarks(FrameT& mCurrentFrame, float mThDepth) { return olf_detail::stereo_landmarks(mCurrentFrame, OLF_LANDMARKS_KEYFRAME, mThDepth); }
+// the two sorted loops of void Tracking::UpdateLastFrame(), src/Tracking.cc:1092-1204, with the early return of :1105-1106
+template <class FrameT> StereoLandmarks UpdateLastFrameLandmarks(FrameT& mLastFrame, float mThDepth) { return olf_detail::stereo_landmarks(mLastFrame, OLF_LANDMARKS_LASTFRAME, mThDepth); }
+
+// bool Tracking::NeedNewKeyFrame(), src/Tracking.cc:1606-1725: the tracker's members and what it asks of mpMap, mpReferenceKF and mpLocalMapper ...
+struct KeyFrameTest {
+    unsigned long mnId = 0;                                   // mCurrentFrame.mnId
+    unsigned mnLastKeyFrameId = 0, mnLastRelocFrameId = 0;
+    int mMinFrames = 0, mMaxFrames = 0;
+    int nKFs = 0;                                             // mpMap->KeyFramesInMap()
+    int nRefMatches = 0, nRefMatches_l = 0;                   // mpReferenceKF->TrackedMapPoints(nKFs <= 2 ? 2 : 3), TrackedMapLines(2)
+    int mnMatchesInliers = 0, mnMatchesInliers_l = 0;
+    bool bLocalMappingIdle = false;                           // mpLocalMapper->AcceptKeyFrames()
+    int KeyframesInQueue = 0;
+    bool mbOnlyTracking = false, stopped = false, monocular = false;      // stopped: isStopped() || stopRequested(); monocular: mSensor == System::MONOCULAR
+};
+// ... and what it answers: the return value, whether mpLocalMapper->InterruptBA() is due (:1711), the four counts of :1632-1667, the six conditions
+struct KeyFrameDecision {
+    bool need = false, interrupt_ba = false;
+    int nTrackedClose = 0, nNonTrackedClose = 0, nTrackedClose_l = 0, nNonTrackedClose_l = 0;
+    int conditions = 0;                                       // c1a | c1b << 1 | c1c << 2 | c1c_l << 3 | c2 << 4 | c2_l << 5
+    int32_t status = 0;                                       // 1: mLastFrame has fewer lines than mCurrentFrame (:1651 reads out of bounds there; not counted)
+};
+// Reads N, N_l, mvDepth, mvpMapPoints, mvbOutlier, mvpMapLines, mvbOutlier_Line and mbf of mCurrentFrame and mvDisparity_l of mLastFrame (:1651-1652, as
+// written).  Through the host form (olf_need_new_keyframe): no context, no device.
+template <class FrameT>
+KeyFrameDecision NeedNewKeyFrame(const FrameT& mCurrentFrame, const FrameT& mLastFrame, const KeyFrameTest& t, float mThDepth)
+{
+    const int N = (int)mCurrentFrame.N, Nl = (int)mCurrentFrame.N_l, Nlast = (int)mLastFrame.N_l;
+    if (N > OLF_GRID_MAX_KEYS || std::max(Nl, Nlast) > OLF_GRID_MAX_KEYS) olf_detail::check(OLF_ERR_CAPACITY, "NeedNewKeyFrame: more than OLF_GRID_MAX_KEYS features");
+    const size_t cap = (size_t)N + 1, lcap = (size_t)std::max(Nl, Nlast) + 1;
+    std::vector<float> depth(2 * cap, -1.f), ldisp(4 * lcap, -1.f);                  // two rows: the current frame, then the last one
+    std::vector<int32_t> fmp(2 * cap, -1), fml(2 * lcap, -1);
+    std::vector<uint8_t> out(2 * cap, 0), out_l(2 * lcap, 0);
+    for (int i = 0; i < N; ++i) { depth[i] = mCurrentFrame.mvDepth[i]; fmp[i] = mCurrentFrame.mvpMapPoints[i] ? 0 : -1; out[i] = mCurrentFrame.mvbOutlier[i] ? 1 : 0; }
+    for (int i = 0; i < Nl; ++i) { fml[i] = mCurrentFrame.mvpMapLines[i] ? 0 : -1; out_l[i] = mCurrentFrame.mvbOutlier_Line[i] ? 1 : 0; }
+    for (int i = 0; i < Nlast; ++i) { ldisp[2 * (lcap + i)] = mLastFrame.mvDisparity_l[i].first; ldisp[2 * (lcap + i) + 1] = mLastFrame.mvDisparity_l[i].second; }
+    const int32_t counts[2] = {N, 0}, lcounts[2] = {Nl, Nlast}, ldisp_frame[2] = {1, 1}, nref[2] = {t.nRefMatches, 0}, nref_l[2] = {t.nRefMatches_l, 0};
+    const int32_t ninl[4] = {t.mnMatchesInliers, t.mnMatchesInliers_l, 0, 0};
+    int32_t rows[2 * OLF_KEYFRAME_ROW] = {(int32_t)(uint32_t)t.mnId, (int32_t)t.mnLastKeyFrameId, (int32_t)t.mnLastRelocFrameId, t.mMinFrames, t.mMaxFrames, t.nKFs,
+                                          t.bLocalMappingIdle, t.KeyframesInQueue, t.mbOnlyTracking, t.stopped, t.monocular};
+    rows[OLF_KEYFRAME_ROW + 8] = 1;                                  // (the second row is not asked anything: mbOnlyTracking)
+    olf_keyframe_test_batch in;
+    std::memset(&in, 0, sizeof(in));
+    in.counts = counts; in.lcounts = lcounts; in.img_stride = 1; in.depth = depth.data(); in.frame_mp = fmp.data(); in.outlier = out.data();
+    in.ldisp = ldisp.data(); in.frame_ml = fml.data(); in.outlier_l = out_l.data(); in.ldisp_frame = ldisp_frame; in.rows = rows;
+    in.n_ref_matches = nref; in.n_ref_matches_l = nref_l; in.n_inliers = ninl; in.mbf = mCurrentFrame.mbf; in.thDepth = mThDepth;
+    uint8_t need[2], ba[2];
+    int32_t cnt[8], cond[2], st[2];
+    const olf_keyframe_test_outputs o = {need, ba, cnt, cond, st};
+    olf_detail::check(olf_need_new_keyframe(&in, (int)cap, (int)lcap, 2, &o), "olf_need_new_keyframe");
+    KeyFrameDecision d;
+    d.need = need[0] != 0; d.interrupt_ba = ba[0] != 0; d.nTrackedClose = cnt[0]; d.nNonTrackedClose = cnt[1]; d.nTrackedClose_l = cnt[2]; d.nNonTrackedClose_l = cnt[3];
+    d.conditions = cond[0]; d.status = st[0];
+    return d;
+}
+
 }  // namespace ORB_SLAM2

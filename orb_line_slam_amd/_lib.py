@@ -171,6 +171,37 @@ class DiscardBatchC(C.Structure):
                 [("n_mp", C.c_int32), ("n_ml", C.c_int32)])
 
 
+class LandmarksBatchC(C.Structure):
+    """olf_landmarks_batch (include/orbline.h): the frames of a batch as the three producers of stereo landmarks read them"""
+    _fields_ = ([(n, C.c_void_p) for n in ("kps", "counts", "kls", "lcounts")] + [("img_stride", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("depth", "ldisp", "Twc", "frame_mp", "frame_ml", "mp_nobs")] + [("n_mp", C.c_int32), ("ml_nobs", C.c_void_p), ("n_ml", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("new_base_mp", "new_base_ml")] + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "mbf", "thDepth")])
+
+
+LANDMARKS_OUTPUTS = ("n_visited", "n_created", "visit_order", "visit_order_l", "created_order", "created_order_l", "created", "created_l", "frame_mp_out",
+                     "frame_ml_out", "mp_world", "mp_normal", "mp_maxd", "mp_mind", "ml_world_d", "ml_world", "status")
+
+
+class LandmarksOutputsC(C.Structure):
+    """olf_landmarks_outputs (include/orbline.h)"""
+    _fields_ = [(n, C.c_void_p) for n in LANDMARKS_OUTPUTS]
+
+
+class KeyFrameTestBatchC(C.Structure):
+    """olf_keyframe_test_batch (include/orbline.h): what Tracking::NeedNewKeyFrame reads of a batch of frames"""
+    _fields_ = ([(n, C.c_void_p) for n in ("counts", "lcounts")] + [("img_stride", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("depth", "frame_mp", "outlier", "ldisp", "frame_ml", "outlier_l", "ldisp_frame", "rows", "n_ref_matches",
+                                           "n_ref_matches_l", "n_inliers")] + [("mbf", C.c_float), ("thDepth", C.c_float)])
+
+
+KEYFRAME_TEST_OUTPUTS = ("need", "interrupt_ba", "counts", "conditions", "status")
+
+
+class KeyFrameTestOutputsC(C.Structure):
+    """olf_keyframe_test_outputs (include/orbline.h)"""
+    _fields_ = [(n, C.c_void_p) for n in KEYFRAME_TEST_OUTPUTS]
+
+
 class BowCsrC(C.Structure):
     """olf_bow_csr (include/orbline.h): n BoW vectors as offsets, ascending word ids and values"""
     _fields_ = [(n, C.c_void_p) for n in ("off", "ids", "vals")]
@@ -406,6 +437,12 @@ def lib():
         L.olf_optimize_sim3_pairs.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, P, C.c_int, P, P, P, P, C.c_float, C.c_int, P, C.POINTER(OptSim3IoC)]
         L.olf_debug_optimize_sim3_lds_limit.argtypes = [C.c_int]
         L.olf_debug_optimize_sim3_jacobian.argtypes = [P, C.c_int, P, P, P, C.c_int, P]
+        L.olf_stereo_landmarks_batch_dev.argtypes = [P, C.POINTER(LandmarksBatchC), C.c_int, C.c_int, C.POINTER(LandmarksOutputsC), P]
+        L.olf_stereo_landmarks.argtypes = [C.POINTER(LandmarksBatchC), C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int, C.POINTER(LandmarksOutputsC)]
+        L.olf_stereo_landmarks_frames.argtypes = [P, C.POINTER(LandmarksBatchC), C.c_int, C.c_int, C.POINTER(LandmarksOutputsC)]
+        L.olf_need_new_keyframe_batch_dev.argtypes = [P, C.POINTER(KeyFrameTestBatchC), C.c_int, C.POINTER(KeyFrameTestOutputsC), P]
+        L.olf_need_new_keyframe.argtypes = [C.POINTER(KeyFrameTestBatchC), C.c_int, C.c_int, C.c_int, C.POINTER(KeyFrameTestOutputsC)]
+        L.olf_need_new_keyframe_frames.argtypes = [P, C.POINTER(KeyFrameTestBatchC), C.c_int, C.POINTER(KeyFrameTestOutputsC)]
         L.olf_profile_enable.argtypes = [C.c_void_p, C.c_int]
         L.olf_profile_reset.argtypes = [C.c_void_p]
         L.olf_profile_stage_name.restype = C.c_char_p
