@@ -1440,6 +1440,93 @@ int olf_pnp_solver_pairs(olf_ctx* ctx, const olf_track_batch* in, int n_frames, 
 int olf_debug_pnp_solver_lds_limit(int bytes);
 int olf_debug_pnp_solver_parameters(int N, const olf_pnp_ransac* ransac, int32_t* min_inliers, int32_t* cap);
 
+/* ---- Initializer::Initialize for a list of frame pairs on the device (csrc/initializer_batch.hip) --------------------------------------------------------
+ * Initializer (src/Initializer.cc: the homography / fundamental-matrix RANSAC with model selection and two-view reconstruction) as
+ * Tracking::MonocularInitialization drives it (src/Tracking.cc:722 `new Initializer(frame, 1.0, 200)`, :756 `Initialize(...)`): Initialize (:44-121) with
+ * FindHomography, FindFundamental, ComputeH21, ComputeF21, CheckHomography, CheckFundamental, Normalize, ReconstructF, ReconstructH, DecomposeE, CheckRT
+ * and Triangulate, for n_pairs pairs of the n_frames frames of a batch.  It stands behind olf_search_for_initialization, whose rows it reads as they
+ * are; olf_initializer_apply_dev does :758-772 behind it.  Results equal olf_initializer pair by pair, bit for bit, and do not depend on scheduling, on a
+ * pair's position in the list or on where a pair's correspondences live.
+ * `in`: kps (pt of mvKeysUn), counts, img_stride and fx, fy, cx, cy are read (frame j = image j * img_stride; a count beyond the capacity is read as the
+ * capacity).  d_pairs [n_pairs][2] = (reference frame 1, current frame 2).  d_matches [n_pairs][capacity], read only: exactly the vnMatches12 row
+ * olf_search_for_initialization writes; value v at reference feature i < N1 is a correspondence iff 0 <= v < N2.  Correspondences are kept in ascending
+ * i: mvMatches12.  Normalize runs over ALL key points of each frame, as written.
+ * olf_initializer_params: sigma (> 0), max_iterations (>= 1), min_parallax (degrees, finite), min_triangulated (>= 0); the tracker: 1.0, 200, 1.0, 50.
+ * d_draws [n_pairs][max_iterations][8] (uint32): the raw rand() values of every iteration's eight draws (convention C.20; bit 31 is ignored); both
+ * RANSACs read the same sets (mvSets).  The reference's SeedRandOnce(0) + rand() stream is the caller's business (InitializerOf,
+ * include/orbline_reference_api.hpp).
+ * olf_initializer_io, device pointers, one element or row per pair, all outputs (Initialize carries no state): ok (the return value; -1: a refused
+ * pair), n_correspondences (N), model (0: none was evaluated, 1: H was reconstructed, 2: F), score_H, score_F, H21 [9], F21 [9] (the best of each
+ * RANSAC, row-major; left untouched when no iteration scored above 0), inliers_H, inliers_F [capacity] (uint8 by reference feature; positions below N1
+ * are written, positions from N1 on are left as they are), R21 [9], t21 [3] (written only when ok), P3D [capacity][3] and triangulated [capacity] (vP3D
+ * and vbTriangulated of the chosen hypothesis, written below N1 only when ok; entries CheckRT did not assign are the zeros of resize), n_good [8]
+ * (nGood of every hypothesis evaluated, 4 for F and 8 for H; the others 0), cos_parallax [8] (vCosParallax[min(50, n - 1)] of each, 0 where
+ * nGood == 0 -- the COSINE, not degrees: parallax = acos(c) * 180 / pi is formed by the caller on the host, as the Python wrapper and the adaptor
+ * do), hypothesis (the chosen index, or -1).  N < 8 (undefined in the reference, which draws from an empty list): ok = 0, model = 0, and beside them
+ * only n_correspondences is written.  With N >= 8 everything but H21 / F21 / R21 / t21 / P3D / triangulated is written.
+ * Arithmetic (csrc/initializer_terms.hpp and, for the sample of C.20, ransac_terms.hpp: one text for this entry and its host form; C.4, C.12, C.17 to
+ * C.20, C.30 to C.35 of DESIGN.md): cv::SVDecomp as an OpenCV without LAPACK makes it at 16 x 9, 8 x 9, 3 x 3 (C.30) and 4 x 4 (C.19, the text of
+ * olf_create_new_map_points); the fundamental matrix's null vector is the row OpenCV fills for a zero singular value from its fixed-seed generator
+ * (C.31, restated from memory and UNVERIFIED; at most 4 attempts, then the hypothesis is degenerate: it scores 0 and bit 32768 of the context's status
+ * word is set, as for one of the eight rows at norm <= FLT_MIN); scores are summed sequentially in float in ascending reference feature and the first of
+ * the maxima wins (C.32); no acos on the device: the entry finds, on the host with the host's libm, the float cosine thresholds equivalent to
+ * `parallax > min_parallax` (ReconstructF) and `parallax >= min_parallax` (ReconstructH) and the kernel compares cosines (C.34); the 51st cosine is a
+ * selection with NaN last, and a NaN among a hypothesis' good cosines sets bit 65536 (C.35).
+ * A pair whose index lies outside [0, n_frames), or with both indices equal, gets ok = -1, nothing else of it is written, and bit 2048 is set.
+ * Errors, before any launch: a NULL required pointer, a negative count, sigma <= 0, max_iterations < 1, min_triangulated < 0 or a parameter that is not
+ * finite: OLF_ERR_INVALID.  n_pairs == 0 writes nothing.  Does not synchronise; runs on `stream`.  Nothing is read or written out of bounds.
+ * Scratch: where 32 bytes per feature of the capacity exceed the 24 KiB of LDS a workgroup has beside its fit workspaces, that much per resident
+ * workgroup (at most 1024). */
+typedef struct olf_initializer_params {
+    float   sigma;
+    int32_t max_iterations;
+    float   min_parallax;
+    int32_t min_triangulated;
+} olf_initializer_params;
+typedef struct olf_initializer_io {
+    int32_t* ok;                 /* [n_pairs] */
+    int32_t* n_correspondences;  /* [n_pairs] */
+    int32_t* model;              /* [n_pairs] */
+    float*   score_H;            /* [n_pairs] */
+    float*   score_F;            /* [n_pairs] */
+    float*   H21;                /* [n_pairs][9] */
+    float*   F21;                /* [n_pairs][9] */
+    uint8_t* inliers_H;          /* [n_pairs][capacity] */
+    uint8_t* inliers_F;          /* [n_pairs][capacity] */
+    float*   R21;                /* [n_pairs][9] */
+    float*   t21;                /* [n_pairs][3] */
+    float*   P3D;                /* [n_pairs][capacity][3] */
+    uint8_t* triangulated;       /* [n_pairs][capacity] */
+    int32_t* n_good;             /* [n_pairs][8] */
+    float*   cos_parallax;       /* [n_pairs][8] */
+    int32_t* hypothesis;         /* [n_pairs] */
+} olf_initializer_io;
+int olf_initializer_pairs_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, int n_pairs, const int32_t* d_pairs, const int32_t* d_matches,
+                              const olf_initializer_params* params, const uint32_t* d_draws, const olf_initializer_io* io, void* stream);
+/* Tracking.cc:758-772 for every pair with d_ok > 0 (the rows of the others stay as they are), for i in [0, capacity): d_out[p][i] = d_matches[p][i]
+ * where i < N1, the value is a correspondence and d_triangulated[p][i] is set, -1 elsewhere (d_out may be d_matches itself); d_n_matches[p]: how many
+ * remain; d_Tcw [n_pairs][16]: the current frame's pose, eye(4, 4) with d_R21 and d_t21 copied in (the reference frame's is the identity).  Any of the
+ * three outputs may be NULL.  `in`: counts and img_stride are read.  Does not synchronise. */
+int olf_initializer_apply_dev(olf_ctx* ctx, const olf_track_batch* in, int n_frames, int n_pairs, const int32_t* d_pairs, const int32_t* d_matches,
+                              const uint8_t* d_triangulated, const int32_t* d_ok, const float* d_R21, const float* d_t21, int32_t* d_out,
+                              int32_t* d_n_matches, float* d_Tcw, void* stream);
+/* the host form: ONE pair (ref, cur), host pointers in `in` and everywhere else, no context and no device.  capacity: the row length of the per-frame
+ * planes; matches [capacity], draws [max_iterations][8]; every pointer of io names this pair's element or row; *status receives the bits 2048 / 32768 /
+ * 65536. */
+int olf_initializer(const olf_track_batch* in, int capacity, int n_frames, int ref, int cur, const int32_t* matches, const olf_initializer_params* params,
+                    const uint32_t* draws, const olf_initializer_io* io, int32_t* status);
+/* olf_initializer_pairs_dev from host pointers ON THE DEVICE (csrc/initializer_api.cpp): the arrays are staged (the outputs are uploaded first, so what
+ * the device leaves untouched comes back as it went in), the same kernel runs on the context's stream, the outputs come back; synchronises.  A set
+ * status bit makes the call return OLF_ERR_CAPACITY, the outputs complete. */
+int olf_initializer_pairs(olf_ctx* ctx, const olf_track_batch* in, int n_frames, int n_pairs, const int32_t* pairs, const int32_t* matches,
+                          const olf_initializer_params* params, const uint32_t* draws, const olf_initializer_io* io);
+/* tests: the LDS a workgroup of the initialiser may take for its correspondences (bytes; above it they live in context scratch; <= 0 restores the
+ * default), and C.34's two cosine thresholds for a min_parallax as this machine's acosf gives them (NaN: no cosine passes) */
+int olf_debug_initializer_lds_limit(int bytes);
+int olf_debug_initializer_cos_thresholds(float min_parallax, float* cos_gt, float* cos_ge);
+/* tests: the eight sample indices ransac_sample<8> (csrc/ransac_terms.hpp) makes of eight draws among N >= 8 correspondences */
+int olf_debug_initializer_sample(int N, const uint32_t* draws8, int32_t* idx8);
+
 /* measurement: rate of a plain 16-byte-per-thread device copy kernel over `bytes` (read + written bytes per second): the practical HBM
  * ceiling bench.py reports next to the specification's 8 TB/s */
 int olf_debug_copy_bandwidth(olf_ctx* ctx, size_t bytes, int reps, double* gbytes_per_s);

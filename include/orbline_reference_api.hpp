@@ -1746,6 +1746,161 @@ void PnPsolversIterate(olf_ctx* c, const std::vector<PnPsolverOf<FrameT, MapPoin
     }
 }
 
+// ---- Initializer (include/Initializer.h, src/Initializer.cc) over the reference's own types ---------------------------------------------------------------
+// The reference's members with its signatures: the constructor (ReferenceFrame, sigma, iterations) and Initialize.  It runs over the host form
+// olf_initializer, so a single initialiser needs no device.  Reads mK and mvKeysUn of both frames.  The two frames are laid out as frames 0 and 1 of a
+// batch of their own, at a row length that holds both; vMatches12 is the row as it is.  The random stream: srand(0) once per process
+// (DUtils::Random::SeedRandOnce(0), :80), then every Initialize call draws its max_iterations x 8 values with rand() in the reference's order (:82-97).
+// The library stores and compares cosines (C.34): olf_parallax() turns the stored cosine of a hypothesis into CheckRT's degrees, on the host.
+namespace olf_detail {
+inline void seed_rand_once(unsigned seed) { static bool seeded = false; if (!seeded) { srand(seed); seeded = true; } }
+}
+template <class FrameT>
+class InitializerOf {
+public:
+    InitializerOf(const FrameT& ReferenceFrame, float sigma = 1.0, int iterations = 200)
+    {
+        fx = ReferenceFrame.mK.template at<float>(0, 0); fy = ReferenceFrame.mK.template at<float>(1, 1);
+        cx = ReferenceFrame.mK.template at<float>(0, 2); cy = ReferenceFrame.mK.template at<float>(1, 2);
+        olf_copy_keys(ReferenceFrame, mKeys1);
+        mParams.sigma = sigma; mParams.max_iterations = iterations; mParams.min_parallax = 1.0f; mParams.min_triangulated = 50;      // :116-118
+    }
+
+    template <class MatT, class Point3fT>
+    bool Initialize(const FrameT& CurrentFrame, const std::vector<int>& vMatches12, MatT& R21, MatT& t21, std::vector<Point3fT>& vP3D,
+                    std::vector<bool>& vbTriangulated)
+    {
+        olf_prepare(CurrentFrame, vMatches12);
+        const size_t cap = mCap;
+        std::vector<olf_keypoint> kps(2 * cap);
+        std::copy(mKeys1.begin(), mKeys1.end(), kps.begin());
+        std::copy(mKeys2.begin(), mKeys2.end(), kps.begin() + cap);
+        const int32_t counts[2] = {(int32_t)mKeys1.size(), (int32_t)mKeys2.size()};
+        olf_track_batch in;
+        olf_fill_batch(in, counts);
+        in.kps = kps.data();
+        olf_resize(cap);
+        const olf_initializer_io io = olf_io(0);
+        int32_t status = 0;
+        olf_detail::check(olf_initializer(&in, (int)cap, 2, 0, 1, mRow.data(), &mParams, mDraws.data(), &io, &status), "olf_initializer");
+        return olf_results(R21, t21, vP3D, vbTriangulated);
+    }
+
+    // CheckRT's parallax of hypothesis h in degrees (:901), from the stored cosine
+    float olf_parallax(int h) const { return mnGood[h] > 0 ? (float)((double)(std::acos(mCos[h]) * 180.0f) / 3.1415926535897932384626433832795) : 0.0f; }
+
+    // ---- what the batched free function below reads and writes (olf_ prefix: not members of the reference's class)
+    static void olf_copy_keys(const FrameT& F, std::vector<olf_keypoint>& keys)
+    {
+        keys.resize(F.mvKeysUn.size());
+        if (!keys.empty()) std::memcpy(keys.data(), olf_detail::keypoints(F.mvKeysUn), keys.size() * sizeof(olf_keypoint));
+    }
+    void olf_prepare(const FrameT& CurrentFrame, const std::vector<int>& vMatches12)
+    {
+        olf_copy_keys(CurrentFrame, mKeys2);
+        mCap = std::max<size_t>(std::max(mKeys1.size(), mKeys2.size()), 1);
+        mRow.assign(mCap, -1);
+        for (size_t i = 0; i < vMatches12.size() && i < mKeys1.size(); ++i) mRow[i] = vMatches12[i];
+        olf_detail::seed_rand_once(0);
+        mDraws.resize(8 * (size_t)std::max(mParams.max_iterations, 0));
+        for (size_t k = 0; k < mDraws.size(); ++k) mDraws[k] = (uint32_t)rand() & 0x7fffffffu;
+    }
+    void olf_fill_batch(olf_track_batch& in, const int32_t* counts) const
+    {
+        std::memset(&in, 0, sizeof in);
+        in.counts = counts; in.img_stride = 1;
+        in.fx = fx; in.fy = fy; in.cx = cx; in.cy = cy;
+    }
+    void olf_resize(size_t cap) { mInlH.assign(cap, 0); mInlF.assign(cap, 0); mTri.assign(cap, 0); mP3D.assign(3 * cap, 0.0f); }
+    olf_initializer_io olf_io(size_t)
+    {
+        const olf_initializer_io io = {&mOk, &mNCorr, &mModel, &mScoreH, &mScoreF, mH21, mF21, mInlH.data(), mInlF.data(), mR21, mt21, mP3D.data(), mTri.data(),
+                                       mnGood, mCos, &mHypothesis};
+        return io;
+    }
+    template <class MatT, class Point3fT>
+    bool olf_results(MatT& R21, MatT& t21, std::vector<Point3fT>& vP3D, std::vector<bool>& vbTriangulated)
+    {
+        if (mModel == 2) { R21 = MatT(); t21 = MatT(); }           // ReconstructF empties both before it decides (:501-502)
+        if (mOk <= 0) return false;
+        R21 = MatT(3, 3, 5 /* CV_32F */); t21 = MatT(3, 1, 5);
+        for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) R21.template at<float>(r, k) = mR21[3 * r + k]; t21.template at<float>(r) = mt21[r]; }
+        const size_t N1 = mKeys1.size();
+        vP3D.resize(N1);
+        vbTriangulated = std::vector<bool>(N1, false);
+        for (size_t i = 0; i < N1; ++i) { vP3D[i] = Point3fT(mP3D[3 * i], mP3D[3 * i + 1], mP3D[3 * i + 2]); vbTriangulated[i] = mTri[i] != 0; }
+        return true;
+    }
+
+    float fx, fy, cx, cy;
+    olf_initializer_params mParams;
+    size_t mCap = 1;
+    std::vector<olf_keypoint> mKeys1, mKeys2;
+    std::vector<int32_t> mRow;
+    std::vector<uint32_t> mDraws;
+    std::vector<uint8_t> mInlH, mInlF, mTri;
+    std::vector<float> mP3D;
+    int32_t mOk = 0, mNCorr = 0, mModel = 0, mHypothesis = -1, mnGood[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float mScoreH = 0, mScoreF = 0, mH21[9], mF21[9], mR21[9], mt21[3], mCos[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+// Initialize of every initialiser against its current frame in one call of the device entry (olf_initializer_pairs through context c, whose capacity must
+// hold every frame's key points).  The initialisers share sigma, the iteration count and the calibration.  Every initialiser draws as its own Initialize
+// would, in the order of the vector; vbOk[i] is the return value and the other outputs are what Initialize would have left.
+template <class FrameT, class MatT, class Point3fT>
+void InitializersInitialize(olf_ctx* c, const std::vector<InitializerOf<FrameT>*>& vpInitializers, const std::vector<const FrameT*>& vpCurrentFrames,
+                            const std::vector<std::vector<int> >& vvMatches12, std::vector<bool>& vbOk, std::vector<MatT>& vR21, std::vector<MatT>& vt21,
+                            std::vector<std::vector<Point3fT> >& vvP3D, std::vector<std::vector<bool> >& vvbTriangulated)
+{
+    const size_t n = vpInitializers.size();
+    vbOk.assign(n, false); vR21.assign(n, MatT()); vt21.assign(n, MatT()); vvP3D.assign(n, std::vector<Point3fT>()); vvbTriangulated.assign(n, std::vector<bool>());
+    if (!n) return;
+    if (vpCurrentFrames.size() != n || vvMatches12.size() != n) throw std::runtime_error("InitializersInitialize: one current frame and one row per initialiser");
+    const size_t cap = (size_t)olf_orb_capacity(c), mi = (size_t)vpInitializers[0]->mParams.max_iterations;
+    std::vector<olf_keypoint> kps(2 * n * cap);
+    std::vector<int32_t> counts(2 * n), pairs(2 * n), rows(n * cap, -1), ok(n), nc(n), model(n), ng(8 * n), hyp(n);
+    std::vector<uint32_t> draws(8 * n * mi);
+    std::vector<float> sh(n), sf(n), H(9 * n), F(9 * n), R(9 * n), t(3 * n), P(3 * n * cap, 0.0f), cs(8 * n);
+    std::vector<uint8_t> iH(n * cap, 0), iF(n * cap, 0), tri(n * cap, 0);
+    for (size_t i = 0; i < n; ++i) {
+        auto& S = *vpInitializers[i];
+        const olf_initializer_params &a = S.mParams, &b = vpInitializers[0]->mParams;
+        if (a.sigma != b.sigma || a.max_iterations != b.max_iterations || a.min_parallax != b.min_parallax || a.min_triangulated != b.min_triangulated ||
+            S.fx != vpInitializers[0]->fx || S.fy != vpInitializers[0]->fy || S.cx != vpInitializers[0]->cx || S.cy != vpInitializers[0]->cy)
+            throw std::runtime_error("InitializersInitialize: the initialisers differ in their parameters or calibration");
+        S.olf_prepare(*vpCurrentFrames[i], vvMatches12[i]);
+        if (S.mCap > cap) throw std::runtime_error("InitializersInitialize: the context's capacity does not hold a frame's key points");
+        std::copy(S.mKeys1.begin(), S.mKeys1.end(), kps.begin() + 2 * i * cap);
+        std::copy(S.mKeys2.begin(), S.mKeys2.end(), kps.begin() + (2 * i + 1) * cap);
+        counts[2 * i] = (int32_t)S.mKeys1.size(); counts[2 * i + 1] = (int32_t)S.mKeys2.size();
+        pairs[2 * i] = (int32_t)(2 * i); pairs[2 * i + 1] = (int32_t)(2 * i + 1);
+        std::copy(S.mRow.begin(), S.mRow.end(), rows.begin() + i * cap);
+        std::memcpy(&draws[8 * i * mi], S.mDraws.data(), 32 * mi);
+    }
+    olf_track_batch in;
+    vpInitializers[0]->olf_fill_batch(in, counts.data());
+    in.kps = kps.data();
+    const olf_initializer_io io = {ok.data(), nc.data(), model.data(), sh.data(), sf.data(), H.data(), F.data(), iH.data(), iF.data(), R.data(), t.data(), P.data(),
+                                   tri.data(), ng.data(), cs.data(), hyp.data()};
+    olf_detail::check(olf_initializer_pairs(c, &in, (int)(2 * n), (int)n, pairs.data(), rows.data(), &vpInitializers[0]->mParams, draws.data(), &io),
+                      "olf_initializer_pairs");
+    for (size_t i = 0; i < n; ++i) {
+        auto& S = *vpInitializers[i];
+        const size_t N1 = S.mKeys1.size();
+        S.olf_resize(S.mCap);
+        S.mOk = ok[i]; S.mNCorr = nc[i]; S.mModel = model[i]; S.mHypothesis = hyp[i]; S.mScoreH = sh[i]; S.mScoreF = sf[i];
+        std::memcpy(S.mH21, &H[9 * i], 36); std::memcpy(S.mF21, &F[9 * i], 36); std::memcpy(S.mR21, &R[9 * i], 36); std::memcpy(S.mt21, &t[3 * i], 12);
+        std::memcpy(S.mnGood, &ng[8 * i], 32); std::memcpy(S.mCos, &cs[8 * i], 32);
+        for (size_t q = 0; q < N1; ++q) {
+            S.mInlH[q] = iH[i * cap + q]; S.mInlF[q] = iF[i * cap + q]; S.mTri[q] = tri[i * cap + q];
+            for (int k = 0; k < 3; ++k) S.mP3D[3 * q + k] = P[3 * (i * cap + q) + k];
+        }
+        MatT R21, t21;
+        vbOk[i] = S.olf_results(R21, t21, vvP3D[i], vvbTriangulated[i]);
+        vR21[i] = R21; vt21[i] = t21;
+    }
+}
+
 // ---- the landmark loops of Tracking::StereoInitialization, CreateNewKeyFrame and UpdateLastFrame, and Tracking::NeedNewKeyFrame, over the reference's types ----
 // What the three loops decide for one frame, through the host form (olf_stereo_landmarks, no context and no device): which features are visited and which
 // get a new MapPoint / MapLine, in the reference's order, with the new landmark's geometry.  Creating the objects (new MapPoint, AddObservation,

@@ -25,9 +25,11 @@ from .keyframe import (stereo_landmarks_batch, need_new_keyframe_batch, StereoIn
 from .sim3solver import sim3_ransac, sim3_state, sim3_draws, sim3_solver_batch, sim3_filter_matches, Sim3Solve, sim3_solver_pairs
 from .optsim3 import optimize_sim3_state, optimize_sim3_batch, OptimizeSim3, optimize_sim3_pairs, optimize_sim3_jacobian
 from .pnpsolver import pnp_ransac, pnp_state, pnp_draws, pnp_solver_batch, pnp_apply_inliers, PnPSolve, pnp_solver_pairs
+from .initializer import (initializer_params, initializer_draws, initializer_state, initializer_batch, initializer_pairs, Initialize, initializer_apply,
+                          parallax_degrees)
 from . import matcher as LineMatcher
 from .frame import StereoFrontEnd, StereoFrames, assign_features_to_grid, features_in_area
 from . import synth
 
-__all__ = ["ORBextractor", "Lineextractor", "ORBmatcher", "FrameView", "KeyFrameView", "MapPointView", "MapPointGeom", "ORBVocabulary", "LineVocabulary", "KeyFrameDatabase", "MapGraph", "UpdateLocalMap", "update_local_map_batch", "UpdateConnections", "update_connections_batch", "best_covisibles_batch", "CullView", "keyframe_culling_tables_batch", "keyframe_culling_replay", "KeyFrameCulling", "tracked_map_points_batch", "TrackedMapPoints", "map_point_culling", "MapPointCulling", "pose_params", "pose_optimization_with_line_batch", "PoseOptimizationWithLine", "pose_optimization_with_line_host", "discard_outliers_batch", "DiscardOutliers", "discard_outliers_host", "pose_optimization_batch", "PoseOptimization", "pose_optimization_host", "compute_f12_pairs", "ComputeF12", "create_new_map_points_batch", "CreateNewMapPoints", "update_normal_and_depth", "UpdateNormalAndDepth", "stereo_landmarks_batch", "need_new_keyframe_batch", "StereoInitialization", "CreateNewKeyFrame", "UpdateLastFrame", "NeedNewKeyFrame", "keyframe_rows", "sim3_ransac", "sim3_state", "sim3_draws", "sim3_solver_batch", "sim3_filter_matches", "Sim3Solve", "sim3_solver_pairs", "optimize_sim3_state", "optimize_sim3_batch", "OptimizeSim3", "optimize_sim3_pairs", "optimize_sim3_jacobian", "pnp_ransac", "pnp_state", "pnp_draws", "pnp_solver_batch", "pnp_apply_inliers", "PnPSolve", "pnp_solver_pairs", "LineMatcher", "StereoFrontEnd", "StereoFrames", "assign_features_to_grid", "features_in_area", "KEYPOINT_DTYPE", "KEYLINE_DTYPE", "OlfError", "OlfParams", "default_params",
+__all__ = ["ORBextractor", "Lineextractor", "ORBmatcher", "FrameView", "KeyFrameView", "MapPointView", "MapPointGeom", "ORBVocabulary", "LineVocabulary", "KeyFrameDatabase", "MapGraph", "UpdateLocalMap", "update_local_map_batch", "UpdateConnections", "update_connections_batch", "best_covisibles_batch", "CullView", "keyframe_culling_tables_batch", "keyframe_culling_replay", "KeyFrameCulling", "tracked_map_points_batch", "TrackedMapPoints", "map_point_culling", "MapPointCulling", "pose_params", "pose_optimization_with_line_batch", "PoseOptimizationWithLine", "pose_optimization_with_line_host", "discard_outliers_batch", "DiscardOutliers", "discard_outliers_host", "pose_optimization_batch", "PoseOptimization", "pose_optimization_host", "compute_f12_pairs", "ComputeF12", "create_new_map_points_batch", "CreateNewMapPoints", "update_normal_and_depth", "UpdateNormalAndDepth", "stereo_landmarks_batch", "need_new_keyframe_batch", "StereoInitialization", "CreateNewKeyFrame", "UpdateLastFrame", "NeedNewKeyFrame", "keyframe_rows", "sim3_ransac", "sim3_state", "sim3_draws", "sim3_solver_batch", "sim3_filter_matches", "Sim3Solve", "sim3_solver_pairs", "optimize_sim3_state", "optimize_sim3_batch", "OptimizeSim3", "optimize_sim3_pairs", "optimize_sim3_jacobian", "pnp_ransac", "pnp_state", "pnp_draws", "pnp_solver_batch", "pnp_apply_inliers", "PnPSolve", "pnp_solver_pairs", "initializer_params", "initializer_draws", "initializer_state", "initializer_batch", "initializer_pairs", "Initialize", "initializer_apply", "parallax_degrees", "LineMatcher", "StereoFrontEnd", "StereoFrames", "assign_features_to_grid", "features_in_area", "KEYPOINT_DTYPE", "KEYLINE_DTYPE", "OlfError", "OlfParams", "default_params",
            "device_count", "lib", "last_error", "synth"]

@@ -96,6 +96,17 @@ class PnpSolverIoC(C.Structure):
                                           "accepted", "no_more", "n_inliers", "inliers", "Tcw", "n_correspondences", "counts")]
 
 
+class InitializerParamsC(C.Structure):
+    """olf_initializer_params (include/orbline.h): Initializer(frame, sigma, iterations) and ReconstructH / ReconstructF's minParallax, minTriangulated"""
+    _fields_ = [("sigma", C.c_float), ("max_iterations", C.c_int32), ("min_parallax", C.c_float), ("min_triangulated", C.c_int32)]
+
+
+class InitializerIoC(C.Structure):
+    """olf_initializer_io (include/orbline.h): the outputs of Initializer::Initialize for a list of pairs"""
+    _fields_ = [(n, C.c_void_p) for n in ("ok", "n_correspondences", "model", "score_H", "score_F", "H21", "F21", "inliers_H", "inliers_F", "R21", "t21", "P3D",
+                                          "triangulated", "n_good", "cos_parallax", "hypothesis")]
+
+
 class LocalMapC(C.Structure):
     """olf_local_map (include/orbline.h): the local map of a batch as device arrays, and optionally each frame's list of indices into it"""
     _fields_ = ([(n, C.c_void_p) for n in ("world", "normal", "maxd", "mind", "desc", "obs", "bad")] + [("n_mp", C.c_int32)] +
@@ -417,6 +428,13 @@ def lib():
         L.olf_pnp_solver_pairs.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, P, C.c_int, P, P, C.POINTER(PnpRansacC), P, C.POINTER(PnpSolverIoC)]
         L.olf_debug_pnp_solver_lds_limit.argtypes = [C.c_int]
         L.olf_debug_pnp_solver_parameters.argtypes = [C.c_int, C.POINTER(PnpRansacC), P, P]
+        L.olf_initializer_pairs_dev.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, C.c_int, P, P, C.POINTER(InitializerParamsC), P, C.POINTER(InitializerIoC), P]
+        L.olf_initializer_apply_dev.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, C.c_int] + [P] * 10
+        L.olf_initializer.argtypes = [C.POINTER(TrackBatchC), C.c_int, C.c_int, C.c_int, C.c_int, P, C.POINTER(InitializerParamsC), P, C.POINTER(InitializerIoC), P]
+        L.olf_initializer_pairs.argtypes = [P, C.POINTER(TrackBatchC), C.c_int, C.c_int, P, P, C.POINTER(InitializerParamsC), P, C.POINTER(InitializerIoC)]
+        L.olf_debug_initializer_lds_limit.argtypes = [C.c_int]
+        L.olf_debug_initializer_cos_thresholds.argtypes = [C.c_float, P, P]
+        L.olf_debug_initializer_sample.argtypes = [C.c_int, P, P]
         L.olf_update_normal_and_depth_dev.argtypes = [P, C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int] + [P] * 8
         L.olf_update_normal_and_depth.argtypes = [C.POINTER(MapGraphC), C.POINTER(CullViewC), C.c_int] + [P] * 5 + [C.c_int] + [P] * 4
         L.olf_pose_default_params.argtypes = [C.POINTER(PoseParamsC)]

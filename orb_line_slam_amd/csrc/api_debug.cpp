@@ -43,6 +43,12 @@ int olf_debug_pnp_solver_lds_limit(int bytes)
     return OLF_OK;
 }
 
+int olf_debug_initializer_lds_limit(int bytes)
+{
+    g_initializer_lds.set(bytes);
+    return OLF_OK;
+}
+
 int olf_debug_pose_points_lds_limit(int bytes)
 {
     g_pose_points_lds.set(bytes);

@@ -54,7 +54,7 @@ void set_error(const std::string& s);
 //                  olf_search_local_map_batch_dev, olf_search_for_triangulation_batch_dev, olf_fuse_search_batch_dev, olf_search_by_sim3_pairs_dev,
 //                  olf_search_by_projection_kf_pairs_dev, olf_search_by_projection_sim3_batch_dev, olf_update_local_map_batch_dev, olf_update_connections_batch_dev,
 //                  olf_pose_optimization_with_line_batch_dev above the LDS a frame's state fits in, olf_pose_optimization_batch_dev likewise, olf_sim3_solver_pairs_dev (its table of iteration caps, and
-//                  the correspondences above the LDS they fit in), olf_pnp_solver_pairs_dev (its table of parameters, and the correspondences above the LDS they fit in), and the line entries of line_batch.hip) and the image-sized host-pointer entries (olf_cvt_gray, olf_remap_linear,
+//                  the correspondences above the LDS they fit in), olf_pnp_solver_pairs_dev (its table of parameters, and the correspondences above the LDS they fit in), olf_initializer_pairs_dev (the correspondences above the LDS they fit in), and the line entries of line_batch.hip) and the image-sized host-pointer entries (olf_cvt_gray, olf_remap_linear,
 //                  olf_init_undistort_rectify_map, olf_bow_transform).  The matchers do not synchronise: the caller keeps them on one stream.
 //   SCRATCH_PACK   olf_frames_pack_dev: the record's row offsets.
 // Live at the same time: STAGE over KNN inside olf_match_bf (it stages, then calls olf_match_bf_dev); KNN, BATCH and PACK in a pipeline step that

@@ -28,8 +28,8 @@ struct LdsLimit {
     void set(int bytes) { cur = bytes > 0 ? std::min(bytes, def) : def; }      // 0 or less: back to the default; never above it
     bool fits(size_t bytes) const { return bytes <= (size_t)cur; }
 };
-// the four limits a test can lower, each defined beside its kernel (api_debug.cpp sets them)
-extern LdsLimit g_pose_points_lds, g_optimize_sim3_lds, g_sim3_solver_lds, g_pnp_solver_lds;
+// the five limits a test can lower, each defined beside its kernel (api_debug.cpp sets them)
+extern LdsLimit g_pose_points_lds, g_optimize_sim3_lds, g_sim3_solver_lds, g_pnp_solver_lds, g_initializer_lds;
 
 // True: `bytes` of state per workgroup fit the limit, the launch asks for that much dynamic LDS and *slabs stays NULL.  False: `grid` slabs of `bytes` are
 // added to k, which the launcher binds to SCRATCH_BATCH with whatever else it carves there.
