@@ -185,6 +185,10 @@ int olf_orb_pyramid_level(olf_ctx* ctx, int image, int level, int blurred, uint8
 /* debug/test: per-level FAST candidates handed to DistributeOctTree (vToDistributeKeys,
  * src/ORBextractor.cc:821-827) as int32 triples (x,y,score) relative to minBorder. */
 int olf_orb_debug_candidates(olf_ctx* ctx, int image, int level, int32_t* xys, int cap, int32_t* count);
+/* debug/test, host only (no context, no device): the launches of the octree kernel for these parameters and this image size.  Returns their number (1 to 3)
+ * or an error; level_launch [nlevels] = the launch a level goes in, launch_lds [3] = the dynamic LDS bytes each launch asks for (-1: no such launch; 0: the
+ * one launch of a configuration whose lists live in global memory). */
+int olf_debug_octree_launches(const olf_orb_params* params, int width, int height, int32_t* level_launch, int32_t* launch_lds);
 /* debug: the context's 64-int device status block (overflow flags in [0]; instrumented builds put cycle counters at [16..31]). */
 int olf_debug_status(olf_ctx* ctx, int32_t* out64);
 int olf_debug_status_n(olf_ctx* ctx, int32_t* out, int n);

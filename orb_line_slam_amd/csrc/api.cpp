@@ -262,7 +262,7 @@ int olf_ctx_create(const olf_params* p, int width, int height, int max_images, o
     A(b.pyr, n * g.pyrBytes); A(b.blur, n * g.pyrBytes);
     A(b.cells, n * g.totalCells * g.cellCap); A(b.cellCount, n * g.totalCells);
     A(b.cand, n * g.candTotal); A(b.candNode, n * g.candTotal); A(b.candCount, n * g.nlevels);
-    if (g.maxNodes > 2048) A(b.octSpill, n * g.nlevels * octree_lds_bytes(g.maxNodes));
+    if (g.maxNodes > 2048) A(b.octSpill, n * g.nlevels * octree_spill_bytes(g));
     A(b.lvlKp, n * g.kpTotal); A(b.lvlCount, n * g.nlevels); A(b.lvlAngle, n * g.kpTotal);
     A(b.rx, c->orb.rx.size() + 1); A(b.ry, c->orb.ry.size() + 1); A(b.geom, 1); A(b.status, 256);
     A(c->d_sad, ((n + 1) / 2) * g.outCap); A(c->d_bestkey, ((n + 1) / 2) * g.outCap); A(c->d_rowperm, n * g.outCap);

@@ -31,6 +31,19 @@ int olf_orb_pyramid_level(olf_ctx* c, int image, int level, int blurred, uint8_t
     return OLF_OK;
 }
 
+int olf_debug_octree_launches(const olf_orb_params* p, int width, int height, int32_t* level_launch, int32_t* launch_lds)
+{
+    if (!p || !level_launch || !launch_lds) return OLF_ERR_INVALID;
+    OrbHostTables t;
+    OLF_TRY(t.build(*p, width, height));
+    OctLaunch la[3];
+    const int n = octree_launches(t.geom, la);
+    for (int i = 0; i < 3; ++i) launch_lds[i] = i < n ? (int32_t)la[i].lds : -1;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < la[i].lv.n; ++k) level_launch[la[i].lv.id[k]] = i;
+    return n;
+}
+
 int olf_debug_sim3_solver_lds_limit(int bytes)
 {
     g_sim3_solver_lds.set(bytes);

@@ -168,6 +168,7 @@ int OrbHostTables::build(const olf_orb_params& p, int W, int H)
         L.patch_size = (int)(31 * sf[l]);
         // DistributeOctTree returns at most quota + 3 nodes once its size checks run, but the first sweep splits all nIni root nodes
         // unconditionally (src/ORBextractor.cc:556-640): a small quota can come back as 4 * nIni key points
+        // (k_octree's LDS lists hold exactly kpCap nodes, rounded up to 8: whoever changes this formula revisits the bound at octree_node_cap, olf_internal.hpp)
         L.kpBase = kps; L.kpCap = std::max(L.quota + 8, 4 * L.nIni + 4); kps += L.kpCap;
         maxKp = std::max(maxKp, L.kpCap);
         if (l > 0) {
@@ -199,10 +200,30 @@ int OrbHostTables::build(const olf_orb_params& p, int W, int H)
     int mn = 64;
     while (mn < maxKp) mn <<= 1;
     g.maxNodes = mn;
-    // k_octree keeps a level's node list in LDS (orb_octree.hip, octree_lds_bytes: 66 bytes per node + 16 KB): 2048 nodes fit the 160 KB,
+    // k_octree keeps a level's node list in LDS (orb_octree.hip, octree_lds_bytes: 62 bytes per node + 4 per sort key, per level): 2048 nodes fit the 160 KB,
     // i.e. up to 2040 key points on one level; larger levels spill the lists to global memory (node ids are 16-bit: at most 32768 nodes)
     if (mn > 32768) return OLF_ERR_CAPACITY;
     return OLF_OK;
+}
+
+int octree_launches(const OrbGeom& g, OctLaunch out[3])
+{
+    OctLaunch grp[3] = {};
+    if (g.maxNodes > 2048) {
+        for (int l = 0; l < g.nlevels; ++l) grp[0].lv.id[grp[0].lv.n++] = l;
+        out[0] = grp[0];
+        return 1;
+    }
+    for (int l = 0; l < g.nlevels; ++l) {
+        const size_t need = octree_lds_bytes(octree_node_cap(g.lv[l]), octree_sort_cap(g.lv[l]));
+        OctLaunch& o = grp[need > 36 * 1024 ? 0 : (need > 18 * 1024 ? 1 : 2)];
+        o.lv.id[o.lv.n++] = l;
+        o.lds = std::max(o.lds, need);
+    }
+    int n = 0;
+    for (int c = 0; c < 3; ++c)
+        if (grp[c].lv.n) out[n++] = grp[c];
+    return n;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -197,7 +197,7 @@ struct OrbGeom {
     int kpTotal;            // per image (sum of kpCap)
     int outCap;             // max key points per image returned (nfeatures + 4*nlevels)
     int iniTh, minTh;
-    int maxNodes;           // octree LDS node capacity (power of two)
+    int maxNodes;           // power of two at or above the largest kpCap: above 2048 k_octree spills its lists to global memory (sizes octSpill)
     LevelGeom lv[OLF_MAX_LEVELS];
     int umax[16];
     int blurTaps[7];
@@ -235,14 +235,33 @@ struct OrbDeviceBufs {
     ResizeCoef* ry = nullptr;
     OrbGeom* geom = nullptr;      // device copy
     int* status = nullptr;        // device error flags (capacity overflow etc.)
-    unsigned char* octSpill = nullptr;   // [max_images][nlevels][octree_lds_bytes(maxNodes)] only when maxNodes > 2048 (orb_octree.hip)
+    unsigned char* octSpill = nullptr;   // [max_images][nlevels][octree_spill_bytes] only when maxNodes > 2048 (orb_octree.hip)
 };
 
 // kernel launchers (orb_*.hip)
 int launch_orb_pyramid(const OrbGeom& g, const OrbDeviceBufs& b, const uint8_t* d_in, int n_images, hipStream_t s);
 int launch_orb_fast(const OrbGeom& g, const OrbDeviceBufs& b, int n_images, hipStream_t s);
 int launch_orb_octree(const OrbGeom& g, const OrbDeviceBufs& b, int n_images, hipStream_t s);
-size_t octree_lds_bytes(int M);
+// k_octree's working set of one level (orb_octree.hip), the same on both sides of the launch.  The arrays hold exactly the level's capacity, so the kernel
+// rests on this bound: the first sweep divides at most nIni roots (4 * nIni nodes); a later full sweep runs only while size + 3 * expandable <= quota and so
+// ends with at most quota nodes; a careful round stops at the first division that reaches the quota, which adds at most 3 (quota + 2 nodes).  All are below
+// kpCap = max(quota + 8, 4 * nIni + 4).  A careful round sorts the expandable nodes of a list that is still shorter than the quota.
+__host__ __device__ inline int octree_node_cap(const LevelGeom& L) { return (L.kpCap + 7) & ~7; }
+__host__ __device__ inline int octree_sort_cap(const LevelGeom& L)
+{
+    int s = 64;
+    while (s < L.quota) s <<= 1;
+    return s;
+}
+__host__ __device__ inline size_t octree_lds_bytes(int nodeCap, int sortCap) { return (size_t)nodeCap * 62 + (size_t)sortCap * 4; }
+size_t octree_spill_bytes(const OrbGeom& g);      // per (image, level) slice of octSpill
+// The launches of k_octree for a geometry (host_tables.cpp), at most three, the largest request first.  A launch carries one dynamic LDS size, so the levels are
+// grouped by what their lists need: above 36 KB, 18 to 36 KB, at most 18 KB.  The LSD growth agents that run beside this kernel in the fused frame call hold
+// 5120 B of LDS each, 24 of them a CU, which leaves 40 KB of the 160 KB: a level of the middle group fits once beside them, one of the small group twice, and
+// neither waits with a larger level's request.  With maxNodes > 2048 it is one launch of every level with no LDS (the lists live in octSpill).
+struct OctLevels { int n; int id[OLF_MAX_LEVELS]; };
+struct OctLaunch { OctLevels lv; size_t lds; };
+int octree_launches(const OrbGeom& g, OctLaunch out[3]);
 int launch_orb_blur(const OrbGeom& g, const OrbDeviceBufs& b, int n_images, hipStream_t s);
 int launch_orb_describe(const OrbGeom& g, const OrbDeviceBufs& b, int n_images, olf_keypoint* d_kps, uint8_t* d_desc,
                         int* d_counts, int out_cap, hipStream_t s);

@@ -29,7 +29,7 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane)
     return v;
 }
 
-// exclusive scan of a[0..n) in place (n <= 16*256); returns the total.  256 threads, 4 waves.
+// exclusive scan of a[0..n) in place; returns the total.  256 threads, 4 waves.
 __device__ int block_excl_scan(int* a, int n, int* wsum)
 {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -65,15 +65,17 @@ __global__ __launch_bounds__(256) void k_octree(const OrbGeom* __restrict__ gp, 
                                                 const int* __restrict__ cellCount, uint32_t* __restrict__ cand,
                                                 uint16_t* __restrict__ candNode, int* __restrict__ candCount,
                                                 uint32_t* __restrict__ lvlKp, int* __restrict__ lvlCount, int* __restrict__ status,
-                                                unsigned char* __restrict__ spill, size_t spillBytes)
+                                                unsigned char* __restrict__ spill, size_t spillBytes, OctLevels lv)
 {
     extern __shared__ __align__(16) unsigned char lds_smem[];
-    unsigned char* smem = SPILL ? spill + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * spillBytes : lds_smem;
     const OrbGeom& g = *gp;
-    const int level = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
+    const int level = lv.id[blockIdx.x], img = blockIdx.y, tid = threadIdx.x;
+    unsigned char* smem = SPILL ? spill + ((size_t)img * g.nlevels + level) * spillBytes : lds_smem;
     const LevelGeom& L = g.lv[level];
-    const int M = g.maxNodes;
-    // LDS carve-up
+    // M: the nodes this level's list can hold; S: the power of two a careful round's sort runs over (olf_internal.hpp).  With the maximum over the levels
+    // for both, and 16 KB of scan scratch, every level asked for 50 KB at 2000 features: three workgroups a CU, and none beside 24 resident LSD growth agents.
+    const int M = octree_node_cap(L), S = octree_sort_cap(L);
+    // LDS carve-up (octree_lds_bytes: 62 M + 4 S bytes)
     NodeRec* nodeA = reinterpret_cast<NodeRec*>(smem);            // M
     NodeRec* nodeB = nodeA + M;                                     // M
     int* cntA = reinterpret_cast<int*>(nodeB + M);                  // M
@@ -82,13 +84,13 @@ __global__ __launch_bounds__(256) void k_octree(const OrbGeom* __restrict__ gp, 
     int* scanA = childCnt + 4 * M;                                  // M   (rank among expandable / scratch)
     int* scanB = scanA + M;                                         // M   (nc in processing order -> exclusive scan)
     int* scanC = scanB + M;                                         // M   (survivor flags -> exclusive scan)
-    uint32_t* sortKey = reinterpret_cast<uint32_t*>(scanC + M);     // M
-    unsigned short* seqA = reinterpret_cast<unsigned short*>(sortKey + M);   // M  creation index of node (cur list)
+    uint32_t* sortKey = reinterpret_cast<uint32_t*>(scanC + M);     // S
+    unsigned short* seqA = reinterpret_cast<unsigned short*>(sortKey + S);   // M  creation index of node (cur list)
     unsigned short* seqB = seqA + M;                                // M
     unsigned short* procNode = seqB + M;                            // M  processing order -> node
     unsigned short* rankOf = procNode + M;                          // M  node -> rank (0xffff: not processed)
     unsigned short* seqToNode = rankOf + M;                         // M
-    int* cellScan = reinterpret_cast<int*>(seqToNode + M);          // 4096 (cells of a level, scanned in chunks)
+    int* cellScan = childCnt;                                       // the cells of a level are scanned in chunks of 4M, before the first child is counted
     __shared__ int wsum[4];
     __shared__ int sh[8];
 
@@ -99,8 +101,8 @@ __global__ __launch_bounds__(256) void k_octree(const OrbGeom* __restrict__ gp, 
 
     // ---- gather the cells' candidates in reference order (cell-row, cell-col, row-major in cell)
     int C = 0;
-    for (int base = 0; base < nCells; base += 4096) {
-        const int n = min(4096, nCells - base);
+    for (int base = 0; base < nCells; base += 4 * M) {
+        const int n = min(4 * M, nCells - base);
         for (int i = tid; i < n; i += 256) cellScan[i] = cc[base + i];
         __syncthreads();
         const int tot = block_excl_scan(cellScan, n, wsum);
@@ -184,8 +186,8 @@ __global__ __launch_bounds__(256) void k_octree(const OrbGeom* __restrict__ gp, 
             for (int i = tid; i < Lsz; i += 256)
                 if (curCnt[i] > 1) procNode[scanA[i]] = (unsigned short)i;
         } else {
-            // sort expandable nodes by (count, creation index) descending: bitonic over M keys
-            for (int i = tid; i < M; i += 256) {
+            // sort expandable nodes by (count, creation index) descending: bitonic over S keys (a list that gets a careful round is shorter than the quota)
+            for (int i = tid; i < S; i += 256) {
                 uint32_t k = 0;
                 if (i < Lsz && curCnt[i] > 1) {
                     k = ((uint32_t)min(curCnt[i], 0xffff) << 16) | curSeq[i];      // (a level holds at most 65535 candidates; creation indices < M <= 32768)
@@ -194,9 +196,9 @@ __global__ __launch_bounds__(256) void k_octree(const OrbGeom* __restrict__ gp, 
                 sortKey[i] = k;
             }
             __syncthreads();
-            for (int k = 2; k <= M; k <<= 1)
+            for (int k = 2; k <= S; k <<= 1)
                 for (int j = k >> 1; j > 0; j >>= 1) {
-                    for (int i = tid; i < M; i += 256) {
+                    for (int i = tid; i < S; i += 256) {
                         const int ixj = i ^ j;
                         if (ixj > i) {
                             const uint32_t a = sortKey[i], b = sortKey[ixj];
@@ -209,7 +211,7 @@ __global__ __launch_bounds__(256) void k_octree(const OrbGeom* __restrict__ gp, 
             if (tid == 0) sh[0] = 0;
             __syncthreads();
             int cntE = 0;
-            for (int i = tid; i < M; i += 256)
+            for (int i = tid; i < S; i += 256)
                 if (sortKey[i] != 0) { procNode[i] = seqToNode[sortKey[i] & 0xffff]; ++cntE; }
             atomicAdd(&sh[0], cntE);
             __syncthreads();
@@ -326,31 +328,36 @@ __global__ __launch_bounds__(256) void k_octree(const OrbGeom* __restrict__ gp, 
     for (int c = tid; c < C; c += 256) atomicMax(&bestKey[myNode[c]], ((myCand[c] & 0xffu) << 16) | (uint32_t)(0xffff - c));
     __syncthreads();
     uint32_t* out = lvlKp + (size_t)img * g.kpTotal + L.kpBase;
-    if (Lsz > L.kpCap) { if (tid == 0) atomicOr(status, 2); Lsz = L.kpCap; }
+    // (Lsz <= kpCap: the bound the lists are sized by, olf_internal.hpp)
     for (int i = tid; i < Lsz; i += 256) out[i] = myCand[0xffff - (bestKey[i] & 0xffff)];
     if (tid == 0) lvlCount[img * g.nlevels + level] = Lsz;
 }
 
-size_t octree_lds_bytes(int M)
+size_t octree_spill_bytes(const OrbGeom& g)
 {
-    return (size_t)M * (2 * sizeof(NodeRec) + 2 * 4 + 4 * 4 + 3 * 4 + 4 + 5 * 2) + 4096 * 4;
+    size_t m = 0;
+    for (int l = 0; l < g.nlevels; ++l) m = std::max(m, octree_lds_bytes(octree_node_cap(g.lv[l]), octree_sort_cap(g.lv[l])));
+    return (m + 15) & ~(size_t)15;
 }
 
 int launch_orb_octree(const OrbGeom& g, const OrbDeviceBufs& b, int n_images, hipStream_t s)
 {
-    const size_t lds = octree_lds_bytes(g.maxNodes);
+    OctLaunch la[3];
+    const int n = octree_launches(g, la);
     if (g.maxNodes > 2048) {
-        hipLaunchKernelGGL(k_octree<true>, dim3(g.nlevels, n_images), dim3(256), 0, s, b.geom, b.cells, b.cellCount, b.cand, b.candNode,
-                           b.candCount, b.lvlKp, b.lvlCount, b.status, b.octSpill, lds);
+        hipLaunchKernelGGL(k_octree<true>, dim3(la[0].lv.n, n_images), dim3(256), 0, s, b.geom, b.cells, b.cellCount, b.cand, b.candNode,
+                           b.candCount, b.lvlKp, b.lvlCount, b.status, b.octSpill, octree_spill_bytes(g), la[0].lv);
         OLF_HIP_CHECK(hipGetLastError());
         return OLF_OK;
     }
-    // the attribute belongs to the (function, device) pair: set it on whichever device this launch goes to
-    if (lds > 64 * 1024)
+    // (only the first launch can be above 64 KB; the attribute belongs to the (function, device) pair: set it on whichever device this launch goes to)
+    if (la[0].lds > 64 * 1024)
         OLF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_octree<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-    hipLaunchKernelGGL(k_octree<false>, dim3(g.nlevels, n_images), dim3(256), lds, s, b.geom, b.cells, b.cellCount, b.cand, b.candNode,
-                       b.candCount, b.lvlKp, b.lvlCount, b.status, nullptr, 0);
-    OLF_HIP_CHECK(hipGetLastError());
+    for (int i = 0; i < n; ++i) {
+        hipLaunchKernelGGL(k_octree<false>, dim3(la[i].lv.n, n_images), dim3(256), la[i].lds, s, b.geom, b.cells, b.cellCount, b.cand, b.candNode,
+                           b.candCount, b.lvlKp, b.lvlCount, b.status, nullptr, 0, la[i].lv);
+        OLF_HIP_CHECK(hipGetLastError());
+    }
     return OLF_OK;
 }
 
